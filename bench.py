@@ -15,6 +15,9 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): BASELINE.json confi
   accumulate, ONE sum all-reduce of the additive tables across ranks (RCCL over xGMI), commit + prepare -- all inside
   the timed region.  metric = Gibbs-sweep rows/sec = rows of all ranks / seconds per step.  The N = 1 line carries the
   same workload at one rank as `c5_shard`, so a weak-scaling ratio is value(N) / (N * c5_shard.value).
+
+`--steps` is the number of timed steps, `ms_per_step` the wall milliseconds of one.  At N = 1, `--dump-outputs DIR` writes
+what the last timed step computed as DIR/scores.npy (dump_scores); the inputs are seeded, the same for the same arguments.
 """
 import argparse
 import json
@@ -52,6 +55,10 @@ def valu_weighted(insts, busy_slots, ms):
                     "plain instructions at the SIMD's 2 cycles and transcendentals at 8, f64 / packed ones (4) counted as plain"}
 C5_ROWS_PER_RANK = 12_500_000
 C5_GROUPS = 1024
+# --dump-outputs: at most DUMP_ROWS rows of the score matrix (16 MB at K = 256), never more than DUMP_MAX_BYTES in all
+DUMP_ROWS = 16384
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SEED = 0
 
 
 def parse():
@@ -77,7 +84,15 @@ def parse():
     ap.add_argument("--min-region-ms", type=float, default=10.0,
                     help="a timed region shorter than this gets a longer one measured beside it (config.long_region); "
                          "`value` is always the --steps region")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed C2 pass handed its caller as DIR/<name>.npy: "
+                         "scores.npy, float32, the [N, K] score matrix or a fixed, seeded sample of its rows (see dump_scores)")
+    a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup is not None and a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def cpu_baseline(K, sample_rows):
@@ -160,6 +175,30 @@ def c2_data(torch, dev, N, K, seed):
     return x, z
 
 
+def dump_scores(torch, out, dump_dir):
+    """--dump-outputs: the [N, K] f32 score matrix the C2 pass hands its caller, as dump_dir/scores.npy (float32).  Up to
+    DUMP_ROWS rows it is written whole; beyond that, DUMP_ROWS of its rows, drawn without replacement by
+    numpy.random.default_rng(DUMP_SEED).choice(N, DUMP_ROWS, replace=False) and sorted: the same rows for the same --rows,
+    so two builds' files compare row for row.  Returns the description that goes into the line."""
+    import numpy as np
+    N, K = out.shape
+    nrows = min(N, DUMP_ROWS, (DUMP_MAX_BYTES - 4096) // (4 * K))        # (4096: room for the .npy header)
+    if nrows < 1:
+        raise SystemExit("bench.py: --dump-outputs: one row of %d groups is more than %d bytes" % (K, DUMP_MAX_BYTES))
+    if nrows < N:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(N, nrows, replace=False))
+        scores = out.index_select(0, torch.from_numpy(rows).to(out.device)).cpu().numpy()
+    else:
+        scores = out.cpu().numpy()
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "scores.npy"), np.ascontiguousarray(scores, dtype=np.float32))
+    return {"dir": os.path.abspath(dump_dir),
+            "arrays": {"scores": {"shape": list(scores.shape), "dtype": "float32", "of_shape": [N, K],
+                                  "rows": "all" if nrows == N else
+                                          "numpy.random.default_rng(%d).choice(%d, %d, replace=False), sorted"
+                                          % (DUMP_SEED, N, nrows)}}}
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -193,6 +232,10 @@ def spawn_ranks(a):
 
 def main():
     a = parse()
+    if a.dump_outputs and (a.gpus > 1 or os.environ.get("MSC_BENCH_FORCE_C5", "0") not in ("", "0")):
+        print("bench.py: --dump-outputs writes the C2 scoring pass of the one-GPU line; the C5 sweep (--gpus N > 1, "
+              "MSC_BENCH_FORCE_C5) has no dump", file=sys.stderr)
+        sys.exit(2)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a))
     import torch
@@ -479,6 +522,8 @@ def run_c2(a, torch, dist, common_amd, ctx, sync_all):
         sync_all()
         return time.perf_counter() - t0, ev0.elapsed_time(ev1) / steps
     dt, kern_avg_ms = region(out, a.steps)
+    # (what the last timed pass left in `out`, before any later pass rewrites it; outside the timed region)
+    dumped = dump_scores(torch, out, a.dump_outputs) if a.dump_outputs else None
     headline_kernel = ctx.last_kernel("score")              # the instantiation the timed region ran, as rocprofv3 spells it
     timed_from = launched
     launched += a.steps
@@ -541,6 +586,8 @@ def run_c2(a, torch, dist, common_amd, ctx, sync_all):
                      "kernel_min_ms_single_launch_events": kern_ms[0], "algorithmic_bytes_per_launch": alg_bytes,
                      "out_va": "%#x" % out.data_ptr()},
     }
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     if not a.no_sweep:
         line["sweep"] = c2_sweep(a, torch, common_amd, ctx, st, view, z)
     del out

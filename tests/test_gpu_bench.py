@@ -47,6 +47,21 @@ def test_single_gpu_line_has_every_object_and_no_error(gpu_ctx):
     assert len(sm["candidates_fill_GBps"]) <= 12
 
 
+def test_steps_are_the_timed_steps_and_the_last_ones_scores_are_dumped(gpu_ctx, tmp_path):
+    import numpy as np
+    rc, out, err = _run(["--steps", "7", "--warmup", "2", "--no-cpu-baseline", "--no-extra", "--no-sweep",
+                         "--dump-outputs", str(tmp_path)])
+    assert rc == 0, err[-2000:]
+    r = _line(out)
+    assert r["steps"] == 7 and r["warmup"] == 2 and r["ms_per_step"] > 0
+    a, b = r["roofline"]["timed_region_launches"]
+    assert b - a == 7
+    s = np.load(tmp_path / "scores.npy")
+    assert s.dtype == np.float32 and s.shape == (16384, 256) and np.isfinite(s).all()
+    assert os.path.getsize(tmp_path / "scores.npy") <= 64_000_000
+    assert r["dump_outputs"]["arrays"]["scores"]["of_shape"] == [1_000_000, 256]
+
+
 @pytest.mark.parametrize("ranks", [2, 4])      # (four ranks + this process on the one card: the box allows six)
 def test_gpus_n_launches_its_ranks_by_itself(gpu_ctx, ranks):
     rc, out, err = _run(["--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--c5-rows", "20000"], MSC_BENCH_BACKEND="gloo")
