@@ -21,6 +21,7 @@ SCORE_NIW_F32 = 0x2
 ACC_RESET, ACC_SUBTRACT, ACC_NO_COMMIT = 0x1, 0x2, 0x4
 OP_ADD, OP_REMOVE, OP_SCORE_VALUE, OP_SCORE_DATA = range(4)
 ABI_VERSION = 1
+HP_CLUSTER = 0xFFFFFFFF          # msc_hp_grid_create's feature index of the CRP concentration
 
 
 class MicroscopesHipError(RuntimeError):
@@ -111,6 +112,12 @@ _SIGS = {
     "msc_sweep_step_sharded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                          C.c_uint64, C.c_uint64, C.c_void_p]),
     "msc_accumulate_sharded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "msc_hp_grid_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                     C.POINTER(C.c_void_p)]),
+    "msc_hp_grid_destroy": (C.c_int, [C.c_void_p]),
+    "msc_hp_grid_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "msc_hp_grid_gibbs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                    C.c_void_p]),
     "msc_value_op_single": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "msc_relation_slice_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,

@@ -1322,11 +1322,14 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
   return MSC_OK;
 }
 
+static void hp_state_release(msc_state *st);
+
 extern "C" int msc_state_destroy(msc_state *st) {
   if (!st) return MSC_OK;
   (void)hipSetDevice(st->ctx->device);
   (void)hipStreamSynchronize(st->ctx->stream);
   if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
+  hp_state_release(st);
   free_all(st->owned);
   delete st;
   return MSC_OK;
@@ -2749,4 +2752,229 @@ extern "C" int msc_value_op_single(msc_context *ctx, int family, uint32_t dim, i
   if (op <= MSC_OP_REMOVE) std::memcpy(host_ss, mb + hd.ss_off, ss_bytes);
   else *score = back.score;
   return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// grid hyper-parameter inference (kernels_hp.hip)
+// ---------------------------------------------------------------------------
+static void hp_grid_free(msc_hp_grid *g) {
+  (void)hipFree(g->grid_dev);
+  (void)hipFree(g->logprior_dev);
+  (void)hipFree(g->job_dev);
+  delete g;
+}
+
+// a device buffer of at least n elements; a smaller one is freed first (after the stream is idle: an earlier
+// asynchronous call may still read it)
+template <typename T>
+static int hp_reserve(msc_state *st, T **buf, size_t &cap, size_t n) {
+  if (n <= cap && *buf) return MSC_OK;
+  MSC_HIP(hipStreamSynchronize(st->ctx->stream));
+  (void)hipFree(*buf);
+  *buf = nullptr;
+  cap = 0;
+  void *p = nullptr;
+  MSC_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+  *buf = static_cast<T *>(p);
+  cap = n;
+  return MSC_OK;
+}
+
+// group blocks of a score launch: enough workgroups for a few per CU, at least one LDS stage of slots per block
+static uint32_t hp_group_blocks(const msc_state *st, size_t point_blocks) {
+  const uint32_t stages = (st->K + 63) / 64;
+  const size_t want = (4 * (size_t)st->ctx->num_cus + point_blocks - 1) / point_blocks;
+  return (uint32_t)std::max<size_t>(1, std::min<size_t>(stages, want));
+}
+
+static void hp_state_release(msc_state *st) {
+  for (msc_hp_grid *g : st->hp_grids) hp_grid_free(g);
+  st->hp_grids.clear();
+  (void)hipFree(st->hp_part);
+  (void)hipFree(st->hp_out);
+  (void)hipFree(st->hp_jobs_dev);
+  (void)hipFree(st->hp_chosen_dev);
+}
+
+extern "C" int msc_hp_grid_create(msc_state *st, uint32_t feature, const float *host_blocks, size_t block_floats,
+                                  uint32_t npoints, const double *host_logprior, msc_hp_grid **out) {
+  MSC_REQUIRE(st && host_blocks && out, "null argument");
+  *out = nullptr;
+  MSC_REQUIRE(npoints > 0, "a grid needs at least one point");
+  HpJob job;
+  std::memset(&job, 0, sizeof job);
+  if (feature == MSC_HP_CLUSTER) {
+    MSC_REQUIRE(block_floats == 1, "the alpha grid has blocks of one float, not %zu", block_floats);
+    for (uint32_t g = 0; g < npoints; g++)
+      MSC_REQUIRE(host_blocks[g] > 0.f, "alpha grid point %u is %g: alpha must be positive (group_manager.hpp:78)", g,
+                  (double)host_blocks[g]);
+    job.family = kHpCluster;
+  } else {
+    MSC_REQUIRE(feature < st->nfeat, "feature %u out of range", feature);
+    const msc_feature_host &h = st->feats[feature];
+    if (h.family == MSC_NIW)
+      return fail(MSC_EUNSUPPORTED, "feature %u: niw has no hyper-parameter grid (upstream defines none, and every point "
+                  "would need its own factorisation of Psi)", feature);
+    MSC_REQUIRE(block_floats == h.hp.size(), "feature %u: hp block has %zu floats, expected %zu", feature, block_floats,
+                h.hp.size());
+    job.family = h.family;
+    job.dim = h.dim;
+    job.nu32 = raw_u32_rows(h.family, h.dim);
+    job.nf32 = raw_f32_rows(h.family);
+    job.raw_u32 = h.raw_u32;
+    job.raw_f32 = h.raw_f32;
+  }
+  job.hpf = (uint32_t)block_floats;
+  job.npoints = npoints;
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  std::unique_ptr<msc_hp_grid, void (*)(msc_hp_grid *)> g(new (std::nothrow) msc_hp_grid(), hp_grid_free);
+  if (!g) return fail(MSC_ENOMEM, "out of host memory");
+  g->st = st;
+  g->feature = feature;
+  g->blocks.assign(host_blocks, host_blocks + (size_t)npoints * block_floats);
+  const hipStream_t s = st->ctx->stream;
+  MSC_HIP(hipMalloc(reinterpret_cast<void **>(&g->grid_dev), g->blocks.size() * sizeof(float)));
+  MSC_HIP(hipMemcpyAsync(g->grid_dev, g->blocks.data(), g->blocks.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  if (host_logprior) {
+    MSC_HIP(hipMalloc(reinterpret_cast<void **>(&g->logprior_dev), (size_t)npoints * sizeof(double)));
+    MSC_HIP(hipMemcpyAsync(g->logprior_dev, host_logprior, (size_t)npoints * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+  job.grid = g->grid_dev;
+  job.logprior = g->logprior_dev;
+  g->job = job;
+  MSC_HIP(hipMalloc(reinterpret_cast<void **>(&g->job_dev), sizeof(HpJob)));
+  MSC_HIP(hipMemcpyAsync(g->job_dev, &g->job, sizeof(HpJob), hipMemcpyHostToDevice, s));
+  MSC_HIP(hipStreamSynchronize(s));
+  st->hp_grids.push_back(g.get());
+  *out = g.release();
+  return MSC_OK;
+}
+
+extern "C" int msc_hp_grid_destroy(msc_hp_grid *grid) {
+  if (!grid) return MSC_OK;
+  msc_state *st = grid->st;
+  (void)hipSetDevice(st->ctx->device);
+  (void)hipStreamSynchronize(st->ctx->stream);
+  st->hp_grids.erase(std::remove(st->hp_grids.begin(), st->hp_grids.end(), grid), st->hp_grids.end());
+  hp_grid_free(grid);
+  return MSC_OK;
+}
+
+extern "C" int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, double *out_dev) {
+  MSC_REQUIRE(grid && out_dev, "null argument");
+  msc_state *st = grid->st;
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_hp_grid_score between msc_sweep_step_begin and msc_state_commit_reduce: the "
+              "tables hold one rank's uncommitted sums");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(ensure_raw(st));
+  const uint32_t np = grid->job.npoints;
+  if (grid->job.family == kHpCluster) {
+    if (launch_crp_grid_score(st->ctx->stream, grid->job_dev, np, st->cnt_u32, st->K, out_dev))
+      return fail(MSC_EHIP, "k_crp_grid_score launch failed");
+    return MSC_OK;
+  }
+  const uint32_t nblk = hp_group_blocks(st, (np + 255) / 256);
+  MSC_TRY(hp_reserve(st, &st->hp_part, st->hp_part_cap, (size_t)nblk * np));
+  if (launch_hp_grid_score(st->ctx->stream, grid->job_dev, 1, np, st->K, st->kpad, st->cnt_u32, slots_dev, nblk,
+                           st->hp_part, out_dev))
+    return fail(MSC_EHIP, "k_hp_grid_score launch failed");
+  return MSC_OK;
+}
+
+extern "C" int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint32_t n, const uint8_t *slots_dev,
+                                 uint64_t seed, uint64_t sweep, uint32_t *chosen_host, double *const *scores_dev) {
+  MSC_REQUIRE(st && grids && chosen_host, "null argument");
+  MSC_REQUIRE(n > 0, "no grids");
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_hp_grid_gibbs between msc_sweep_step_begin and msc_state_commit_reduce: the "
+              "tables hold one rank's uncommitted sums");
+  // the feature grids first (one score launch), the alpha grid last; order[j] = the caller's index of job j
+  std::vector<uint32_t> order;
+  std::vector<bool> seen(st->nfeat + 1, false);
+  for (int pass = 0; pass < 2; pass++)
+    for (uint32_t i = 0; i < n; i++) {
+      MSC_REQUIRE(grids[i] && grids[i]->st == st, "grid %u is null or belongs to another state", i);
+      const bool cluster = grids[i]->feature == MSC_HP_CLUSTER;
+      if (cluster != (pass == 1)) continue;
+      const uint32_t slot = cluster ? st->nfeat : grids[i]->feature;
+      MSC_REQUIRE(!seen[slot], "two grids of %s %u in one step", cluster ? "alpha" : "feature", grids[i]->feature);
+      seen[slot] = true;
+      order.push_back(i);
+    }
+  const uint32_t nfj = (uint32_t)(order.size() - (seen[st->nfeat] ? 1 : 0));
+  size_t max_np = 0, pblocks = 0;
+  for (uint32_t j = 0; j < nfj; j++) {
+    const uint32_t np = grids[order[j]]->job.npoints;
+    max_np = std::max<size_t>(max_np, np);
+    pblocks += (np + 255) / 256;
+  }
+  const uint32_t nblk = nfj ? hp_group_blocks(st, pblocks) : 1;
+  std::vector<HpJob> &jobs = st->hp_jobs_host;
+  jobs.assign(n, HpJob());
+  size_t part = 0, out = 0;
+  for (uint32_t j = 0; j < n; j++) {
+    const msc_hp_grid *g = grids[order[j]];
+    HpJob &J = jobs[j];
+    J = g->job;
+    J.part_off = part;
+    J.out_off = out;
+    part += (size_t)nblk * J.npoints;
+    out += J.npoints;
+    J.scores_out = scores_dev ? scores_dev[order[j]] : nullptr;
+    if (g->feature == MSC_HP_CLUSTER) {
+      J.stream = UINT64_MAX - st->nfeat;
+    } else {
+      const msc_feature_host &h = st->feats[g->feature];
+      J.stream = UINT64_MAX - g->feature;
+      J.hp_dst = h.hp_dev;
+      J.aux_dst = h.family == MSC_DD || h.family == MSC_DM ? &st->desc_dev[g->feature].aux : nullptr;
+    }
+  }
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(ensure_raw(st));
+  MSC_TRY(hp_reserve(st, &st->hp_part, st->hp_part_cap, part));
+  MSC_TRY(hp_reserve(st, &st->hp_out, st->hp_out_cap, out));
+  MSC_TRY(hp_reserve(st, &st->hp_jobs_dev, st->hp_jobs_cap, n));
+  MSC_TRY(hp_reserve(st, &st->hp_chosen_dev, st->hp_chosen_cap, n));
+  const hipStream_t s = st->ctx->stream;
+  MSC_HIP(hipMemcpyAsync(st->hp_jobs_dev, jobs.data(), n * sizeof(HpJob), hipMemcpyHostToDevice, s));
+  if (nfj && launch_hp_grid_score(s, st->hp_jobs_dev, nfj, (uint32_t)max_np, st->K, st->kpad, st->cnt_u32, slots_dev, nblk,
+                                  st->hp_part, st->hp_out))
+    return fail(MSC_EHIP, "k_hp_grid_score launch failed");
+  if (nfj < n && launch_crp_grid_score(s, st->hp_jobs_dev + nfj, jobs[nfj].npoints, st->cnt_u32, st->K, st->hp_out))
+    return fail(MSC_EHIP, "k_crp_grid_score launch failed");
+  if (launch_hp_grid_draw(s, st->hp_jobs_dev, n, st->hp_out, seed, sweep, st->hp_chosen_dev))
+    return fail(MSC_EHIP, "k_hp_grid_draw launch failed");
+  std::vector<uint32_t> picked(n);
+  MSC_HIP(hipMemcpyAsync(picked.data(), st->hp_chosen_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  MSC_HIP(hipStreamSynchronize(s));                   // the step's one wait
+  // the draw kernel has set the device hp (and a dd / dm descriptor's alpha sum); the host's bookkeeping follows as
+  // msc_state_set_hp / msc_state_set_alpha keep it
+  int rc = MSC_OK;
+  for (uint32_t j = 0; j < n; j++) {
+    const msc_hp_grid *g = grids[order[j]];
+    const uint32_t k = picked[j];
+    chosen_host[order[j]] = k;
+    if (k >= jobs[j].npoints) {
+      rc = fail(MSC_EINVAL, "grid %u: no point has a finite positive weight; nothing installed", order[j]);
+      continue;
+    }
+    const float *blk = g->blocks.data() + (size_t)k * jobs[j].hpf;
+    if (g->feature == MSC_HP_CLUSTER) {
+      st->alpha = blk[0];
+      st->crp_valid = false;
+      continue;
+    }
+    msc_feature_host &h = st->feats[g->feature];
+    std::copy(blk, blk + h.hp.size(), h.hp.begin());
+    h.derived_valid = false;
+    if (h.family == MSC_DD || h.family == MSC_DM) {
+      double asum = 0;
+      for (float a : h.hp) asum += (double)a;
+      st->desc_host[g->feature].aux = asum;
+      for (auto *v : {&st->desc_tile_host, &st->desc_fuse_host, &st->desc_acc_host})
+        for (FeatDesc &d : *v)
+          if (d.hp == h.hp_dev) d.aux = asum;
+    }
+  }
+  return rc;
 }

@@ -149,6 +149,16 @@ MSC_DEV float dd_prepare_entry(float alpha_i, uint32_t count_i, double alpha_sum
 MSC_DEV double dd_loo(float alpha_v, uint32_t count_v, double alpha_sum, uint32_t count_sum) {
   return log(((double)alpha_v + (double)count_v - 1.0) / (alpha_sum + (double)count_sum - 1.0));
 }
+// counts of category i at counts[i * cstride]; count_sum = their sum
+MSC_DEV double dd_score_data(const float *hp, uint32_t dim, const uint32_t *counts, size_t cstride, uint32_t count_sum) {
+  double s = 0, asum = 0;
+  for (uint32_t i = 0; i < dim; i++) {
+    const double a = hp[i];
+    asum += a;
+    s += lgamma(a + (double)counts[(size_t)i * cstride]) - lgamma(a);
+  }
+  return s + (lgamma(asum) - lgamma(asum + (double)count_sum));
+}
 
 // ============================ Gamma-Poisson =================================
 // Posterior a = alpha + sum, b = inv_beta + count; negative-binomial predictive

@@ -397,15 +397,7 @@ __global__ __launch_bounds__(256) void k_score_data(const FeatDesc *__restrict__
     case MSC_BB: s = bb_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k]); break;
     case MSC_BBNC: s = bbnc_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k], fd.raw_f32[k]); break;
     case MSC_GP: s = gp_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k], (double)fd.raw_f32[k]); break;
-    case MSC_DD: {
-      double asum = 0;
-      for (uint32_t i = 0; i < fd.dim; i++) {
-        const double a = fd.hp[i];
-        asum += a;
-        s += lgamma(a + (double)fd.raw_u32[(size_t)(1 + i) * kpad + k]) - lgamma(a);
-      }
-      s += lgamma(asum) - lgamma(asum + (double)fd.raw_u32[k]);
-    } break;
+    case MSC_DD: s = dd_score_data(fd.hp, fd.dim, fd.raw_u32 + kpad + k, kpad, fd.raw_u32[k]); break;
     case MSC_NICH: s = nich_score_data(fd.hp, fd.raw_u32[k], fd.raw_f32[k], fd.raw_f32[kpad + k]); break;
     case MSC_BNB: s = bnb_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k]); break;
     case MSC_DM: s = dm_score_data(fd.hp, fd.dim, fd.raw_u32 + k, kpad, (double)fd.raw_f32[k]); break;

@@ -215,6 +215,15 @@ int launch_pack_bits(hipStream_t stream, const void *const *cols, int m, uint32_
 int launch_pack_nich_x(hipStream_t stream, const float *const *cols_dev, uint32_t n2, uint32_t n2p, uint64_t n, float *out);
 int launch_pack_look_idx(hipStream_t stream, const LookIdxSrc *src_dev, uint32_t nsrc, uint32_t l4, uint64_t n, uint32_t *out);
 int launch_fuse_tables(hipStream_t stream, const FeatDesc *feats_dev, int nsplit, int nblocks, uint32_t kpad);
+// kernels_hp.hip (msc_hp_grid_*): score + reduce of njobs feature grids (partials [nblk][npoints] per job, then out), the CRP
+// grid, and the draw of njobs grids (every job of the draw is scored into `scores` at its out_off)
+int launch_hp_grid_score(hipStream_t stream, const HpJob *jobs_dev, uint32_t njobs, uint32_t max_points, uint32_t K,
+                         uint32_t kpad, const uint32_t *cnt, const uint8_t *slots, uint32_t nblk, double *part,
+                         double *out);
+int launch_crp_grid_score(hipStream_t stream, const HpJob *job_dev, uint32_t npoints, const uint32_t *cnt, uint32_t K,
+                          double *out);
+int launch_hp_grid_draw(hipStream_t stream, const HpJob *jobs_dev, uint32_t njobs, const double *scores, uint64_t seed,
+                        uint64_t sweep, uint32_t *chosen);
 int launch_unpack(hipStream_t stream, const uint8_t *records, const uint8_t *mask, uint64_t nrows,
                   uint32_t rowsize, uint32_t maskrowsize, const void *feats_dev, uint32_t nfeat);
 

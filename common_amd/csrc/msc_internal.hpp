@@ -204,6 +204,29 @@ struct FeatDesc {
   uint32_t lk_l4;          // dwords per row
   uint32_t lk_goff;        // the group's first dword inside a row's record
 };
+// One grid of hyper-parameter points as the kernels of kernels_hp.hip read it (msc_hp_grid_*): a feature's grid, or the
+// CRP concentration's (family kHpCluster, one float per point, no tables).  The score kernel writes per (group block,
+// point) partial sums at part_off, the reduce kernel their fixed-order sum at out_off; the draw kernel reads those,
+// writes prior + likelihood to scores_out (nullable) and the chosen block into hp_dst (+ its alpha sum into aux_dst).
+constexpr int32_t kHpCluster = -1;
+struct HpJob {
+  int32_t family;
+  uint32_t dim;
+  uint32_t hpf;              // floats per point (msc_hp_floats)
+  uint32_t npoints;
+  uint32_t nu32, nf32;       // raw table rows of the family (raw_u32_rows / raw_f32_rows)
+  const float *grid;         // [npoints][hpf] (device)
+  const double *logprior;    // [npoints] (device) or null
+  const uint32_t *raw_u32;   // the feature's raw tables, rows of kpad
+  const float *raw_f32;
+  size_t part_off;           // doubles: [nblk][npoints] partial sums
+  size_t out_off;            // doubles: [npoints] log marginal likelihood
+  double *scores_out;        // draw: prior + likelihood, or null
+  float *hp_dst;             // draw: the feature's device hp block (null: the CRP grid, index only)
+  double *aux_dst;           // draw, dd / dm: FeatDesc::aux of the state's descriptor (null otherwise)
+  uint64_t stream;           // draw: Philox counter (msc_hp_grid_gibbs)
+};
+
 // one feature of the index matrix as k_pack_look_idx reads it
 struct LookIdxSrc {
   const void *col;
@@ -414,6 +437,7 @@ struct msc_feature_host {
   bool derived_valid = false;   // score tables are in sync with raw
 };
 
+struct msc_hp_grid;
 struct msc_state {
   msc_context *ctx = nullptr;
   uint32_t nfeat = 0, K = 0, kpad = 0;
@@ -497,4 +521,26 @@ struct msc_state {
   int32_t *one_z = nullptr;          // a one-entry assignment vector (msc_entity_op's general path)
   uint32_t *niw_scratch = nullptr;   // row bucketing for niw accumulate: 2 K + 1 + rows uint32
   size_t niw_scratch_len = 0;
+  // grid hyper-parameter inference (abi.cpp msc_hp_grid_*): the live grids (destroyed with the state at the latest) and
+  // the workspaces of the calls, grown on demand
+  std::vector<msc_hp_grid *> hp_grids;
+  double *hp_part = nullptr;          // per (group block, point) partial sums
+  size_t hp_part_cap = 0;
+  double *hp_out = nullptr;           // msc_hp_grid_gibbs: every grid's likelihoods
+  size_t hp_out_cap = 0;
+  msc::HpJob *hp_jobs_dev = nullptr;  // msc_hp_grid_gibbs: the grids of the call, then the indices drawn
+  uint32_t *hp_chosen_dev = nullptr;
+  size_t hp_jobs_cap = 0, hp_chosen_cap = 0;
+  std::vector<msc::HpJob> hp_jobs_host;
+};
+
+// a grid of hyper-parameter points of one feature (or of alpha: feature == MSC_HP_CLUSTER), uploaded once
+struct msc_hp_grid {
+  msc_state *st = nullptr;
+  uint32_t feature = 0;
+  std::vector<float> blocks;          // [npoints][hpf], the host copy
+  float *grid_dev = nullptr;
+  double *logprior_dev = nullptr;     // null: no prior
+  msc::HpJob job;                     // the grid alone (part_off = out_off = 0)
+  msc::HpJob *job_dev = nullptr;
 };

@@ -5,6 +5,11 @@ The scoring pass has no collective.  A Gibbs sweep has exactly one exchange: the
 of the additive suff-stat tables (int64 counts -> bit-exact, float64 sums) between sweeps; the
 payload is K * O(10) * 8 bytes, i.e. latency-bound, so both tables travel in one float64 all-reduce
 (counts below 2**53 add exactly as doubles) and nothing is bucketed or overlapped.
+
+Hyper-parameter inference needs no exchange of its own: run the grid Gibbs step (State.hp_gibbs,
+common_amd.hypers.FeatureHpGibbs.step) after commit_reduce.  Every rank then holds the same tables, the grid scores are
+summed in a fixed order (the same bits on every rank) and the draw uses the same seed and sweep, so every rank installs
+the same points.
 """
 import os
 

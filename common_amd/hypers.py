@@ -1,0 +1,126 @@
+"""Grid Gibbs inference of hyper-parameters the way downstream runs it (grid_feature_hp / grid_cluster_hp): every point of
+a model descriptor's partial grid is merged into the feature's current hp, scored by the marginal likelihood of the
+feature's groups plus the descriptor's hyper-priors, and one point is drawn from the softmax.  The scoring, the draw
+and the installation of the chosen point run on the device (State.hp_gibbs, msc_hp_grid_gibbs: one host
+synchronisation per step whatever the number of features); this module holds the upstream semantics of the grids:
+
+  merged_points(desc, current_hp, partial_grid)   each partial point merged into the current hp (dicts)
+  grid_blocks(desc, current_hp, partial_grid)     the same points packed as the ABI's hp blocks (runtime.pack_hp)
+  grid_logprior(desc, points, hyperpriors)        sum of the hyper-priors at each point; a tuple key such as
+                                                   ("alpha", "beta") is called with the values in the tuple's order
+  FeatureHpGibbs(state, descs, ...)               the grids of a state's features built once, .step(seed, sweep)
+
+A sharded sweep (common_amd.dist.ShardedSweep) calls .step after commit_reduce: every rank holds the same tables and
+draws with the same seed, so every rank installs the same points without exchanging anything.
+"""
+import numpy as np
+
+from . import _lib as L
+from .runtime import pack_hp
+
+_FIELDS = {L.BB: ("alpha", "beta"), L.BBNC: ("alpha", "beta"), L.GP: ("alpha", "inv_beta"),
+           L.BNB: ("alpha", "beta", "r"), L.NICH: ("mu", "kappa", "sigmasq", "nu")}
+
+
+def unpack_hp(family, block, dim=0):
+    """the flat hp block of the ABI (State.get_hp) -> the dict microscopes/models.pyx keys it by (niw excluded)"""
+    block = [float(v) for v in np.asarray(block, dtype=np.float32).ravel()]
+    if family in (L.DD, L.DM):
+        return {"alphas": block}
+    if family not in _FIELDS:
+        raise ValueError("family %d has no hyper-parameter grid" % family)
+    hp = dict(zip(_FIELDS[family], block))
+    if family == L.BNB:
+        hp["r"] = int(round(hp["r"]))
+    return hp
+
+
+def _current(desc, current_hp):
+    if current_hp is None:
+        return dict(desc.default_hyperparams())
+    if isinstance(current_hp, dict):
+        return dict(current_hp)
+    return unpack_hp(desc.family, current_hp, desc.dim)
+
+
+def merged_points(desc, current_hp=None, partial_grid=None):
+    """[current hp updated with each point of partial_grid] (default grid: desc.default_partial_hypergrid())"""
+    base = _current(desc, current_hp)
+    grid = desc.default_partial_hypergrid() if partial_grid is None else partial_grid
+    out = []
+    for pt in grid:
+        m = dict(base)
+        m.update(pt)
+        out.append(m)
+    return out
+
+
+def grid_blocks(desc, current_hp=None, partial_grid=None):
+    """float32 [npoints, msc_hp_floats]: the merged points packed with runtime.pack_hp"""
+    pts = merged_points(desc, current_hp, partial_grid)
+    if not pts:
+        return np.zeros((0, len(pack_hp(desc.family, _current(desc, current_hp), desc.dim))), dtype=np.float32)
+    return np.stack([pack_hp(desc.family, p, desc.dim) for p in pts])
+
+
+def grid_logprior(desc, points, hyperpriors=None):
+    """float64 [npoints]: sum over the hyper-priors (default desc.default_hyperpriors()) at each merged point"""
+    priors = desc.default_hyperpriors() if hyperpriors is None else hyperpriors
+    out = np.zeros(len(points), dtype=np.float64)
+    for i, pt in enumerate(points):
+        s = 0.0
+        for key, fn in priors.items():
+            s += fn(*[pt[k] for k in key]) if isinstance(key, tuple) else fn(pt[key])
+        out[i] = s
+    return out
+
+
+class FeatureHpGibbs(object):
+    """Grid Gibbs steps over the hyper-parameters of a state's features (and, optionally, alpha).
+
+    descs[f]: the model descriptor of state feature f.  grids: None, or per feature None (the descriptor's default
+    partial grid) or an explicit partial grid; hyperpriors likewise.  Features whose default grid is empty (dd, dm,
+    niw) are skipped; an explicit empty grid is an error.  cluster_grid: None or a sequence of alpha values (> 0), with
+    cluster_hyperprior a callable of alpha (None: flat).  The grids are merged into the features' hp as the state holds
+    them now and uploaded once."""
+
+    def __init__(self, state, descs, grids=None, cluster_grid=None, hyperpriors=None, cluster_hyperprior=None):
+        if len(descs) != len(state.features):
+            raise ValueError("one model descriptor per state feature expected")
+        self.state = state
+        self.features, self.points, self._grids = [], {}, []
+        for f, desc in enumerate(descs):
+            partial = None if grids is None else grids[f]
+            if partial is not None and len(partial) == 0:
+                raise ValueError("feature %d: explicit empty hyper-parameter grid" % f)
+            if partial is None and len(desc.default_partial_hypergrid()) == 0:
+                continue
+            if (desc.family, desc.dim) != tuple(state.features[f]):
+                raise ValueError("feature %d: descriptor does not match the state's feature" % f)
+            pts = merged_points(desc, state.get_hp(f), partial)
+            prior = grid_logprior(desc, pts, None if hyperpriors is None else hyperpriors[f])
+            self._grids.append(state.hp_grid(f, np.stack([pack_hp(desc.family, p, desc.dim) for p in pts]), prior))
+            self.features.append(f)
+            self.points[f] = pts
+        self.alphas = None
+        if cluster_grid is not None:
+            self.alphas = [float(a) for a in cluster_grid]
+            if not self.alphas:
+                raise ValueError("explicit empty alpha grid")
+            prior = None if cluster_hyperprior is None else np.array([cluster_hyperprior(a) for a in self.alphas])
+            self._grids.append(state.crp_grid(self.alphas, prior))
+
+    def step(self, seed, sweep, slots=None):
+        """one grid Gibbs step of every grid -> {feature: chosen merged hp dict, "alpha": chosen alpha (if any)}"""
+        if not self._grids:
+            return {}
+        chosen = self.state.hp_gibbs(self._grids, seed, sweep, slots=slots)
+        out = {f: self.points[f][int(k)] for f, k in zip(self.features, chosen)}
+        if self.alphas is not None:
+            out["alpha"] = self.alphas[int(chosen[-1])]
+        return out
+
+    def close(self):
+        for g in self._grids:
+            g.close()
+        self._grids = []

@@ -484,10 +484,100 @@ class State(object):
         """rows of the WHOLE dataset when this state sweeps a shard through a view of its own (msc_state_set_sweep_rows)"""
         L.check(self.ctx.lib.msc_state_set_sweep_rows(self._h, int(global_rows)))
 
+    # grid hyper-parameter inference (msc_hp_grid_*; common_amd/hypers.py builds the grids upstream's way) -----------
+    def hp_grid(self, f, blocks, logprior=None):
+        """an HpGrid of feature f: `blocks` = [npoints, msc_hp_floats] floats (or a list of hp dicts, packed with
+        pack_hp), `logprior` = npoints float64 values or None"""
+        fam, dim = self.features[f]
+        if not isinstance(blocks, np.ndarray):
+            blocks = np.stack([pack_hp(fam, b, dim) for b in blocks]) if len(blocks) else np.zeros((0, 0), np.float32)
+        return HpGrid(self, int(f), blocks, logprior)
+
+    def crp_grid(self, alphas, logprior=None):
+        """an HpGrid of the CRP concentration alpha (every value > 0)"""
+        return HpGrid(self, L.HP_CLUSTER, np.asarray(alphas, dtype=np.float32).reshape(-1, 1), logprior)
+
+    def hp_gibbs(self, grids, seed, sweep, slots=None, want_scores=False):
+        """one grid Gibbs step over `grids` (at most one per feature, one crp_grid): score, add the prior, draw, install
+        (msc_hp_grid_gibbs; one host synchronisation).  -> chosen indices (numpy uint32, one per grid), and with
+        want_scores the float64 tensors of prior + likelihood per grid"""
+        grids = list(grids)
+        for g in grids:
+            if g.state is not self or not g._h:
+                raise ValueError("every grid must be a live grid of this state")
+        hs = (C.c_void_p * len(grids))(*[g._h.value for g in grids])
+        chosen = np.zeros(len(grids), dtype=np.uint32)
+        scores, sp = None, None
+        if want_scores:
+            scores = [torch.empty(g.npoints, dtype=torch.float64, device=self.ctx.torch_device) for g in grids]
+            sp = (C.c_void_p * len(grids))(*[t.data_ptr() for t in scores])
+        L.check(self.ctx.lib.msc_hp_grid_gibbs(self._h, hs, len(grids), _slots_ptr(slots, self.K), int(seed), int(sweep),
+                                               chosen.ctypes.data_as(C.c_void_p), sp))
+        return (chosen, scores) if want_scores else chosen
+
     def close(self):
         if getattr(self, "_h", None):
+            for g in list(getattr(self, "_grids", ())):  # (the library frees a state's grids with it)
+                g._h = None
             if getattr(self.ctx, "_h", None):           # (see DataView.close)
                 self.ctx.lib.msc_state_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _slots_ptr(slots, K):
+    if slots is None:
+        return None
+    if not (torch.is_tensor(slots) and slots.dtype == torch.uint8 and slots.is_cuda and slots.is_contiguous()
+            and slots.numel() >= K):
+        raise ValueError("slots must be a contiguous uint8 device tensor of ngroups entries")
+    return C.c_void_p(slots.data_ptr())
+
+
+class HpGrid(object):
+    """npoints hyper-parameter blocks of one feature (or alpha values, feature = HP_CLUSTER) and their log-prior,
+    uploaded once and owned by the state (msc_hp_grid_create)"""
+
+    def __init__(self, state, feature, blocks, logprior=None):
+        import weakref
+        b = np.ascontiguousarray(blocks, dtype=np.float32)
+        if b.ndim != 2:
+            raise ValueError("blocks must be [npoints, floats per block]")
+        lp = None if logprior is None else np.ascontiguousarray(logprior, dtype=np.float64)
+        if lp is not None and lp.shape != (b.shape[0],):
+            raise ValueError("logprior must hold one value per grid point")
+        self.state, self.feature, self.npoints = state, feature, int(b.shape[0])
+        self.blocks, self.logprior = b, lp
+        h = C.c_void_p()
+        L.check(state.ctx.lib.msc_hp_grid_create(state._h, feature, b.ctypes.data_as(C.c_void_p), b.shape[1],
+                                                 self.npoints, None if lp is None else lp.ctypes.data_as(C.c_void_p),
+                                                 C.byref(h)))
+        self._h = h
+        if not hasattr(state, "_grids"):
+            state._grids = weakref.WeakSet()
+        state._grids.add(self)
+
+    def scores(self, slots=None, out=None):
+        """float64 [npoints] device tensor: each point's log marginal likelihood of the groups (no prior); slots: uint8
+        device mask of the counted groups (default: the non-empty ones).  Asynchronous (msc_hp_grid_score)."""
+        if not self._h:
+            raise ValueError("grid is closed")
+        if out is None:
+            out = torch.empty(self.npoints, dtype=torch.float64, device=self.state.ctx.torch_device)
+        if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < self.npoints:
+            raise ValueError("out must be a contiguous float64 tensor of npoints entries")
+        L.check(self.state.ctx.lib.msc_hp_grid_score(self._h, _slots_ptr(slots, self.state.K), C.c_void_p(out.data_ptr())))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.state, "_h", None) and getattr(self.state.ctx, "_h", None):
+                self.state.ctx.lib.msc_hp_grid_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -205,6 +205,51 @@ public:
     check(msc_accumulate(st_, view_, nullptr, 0, n_, z_dev_, MSC_ACC_RESET));
   }
 
+  // Grid hyper-parameter inference (msc_hp_grid_*): what downstream's grid_feature_hp / grid_cluster_hp do point by
+  // point, one device pass per call.  `blocks` = npoints hp blocks back to back in the msc_state_set_hp layout of the
+  // component; `logprior` = npoints values or empty (flat).  The likelihood sums over every group the partition holds,
+  // empty ones included, as score_likelihood does.
+  std::vector<double> score_likelihood_grid(size_t c, const std::vector<float> &blocks) const {
+    sync();
+    mixture_state *self = const_cast<mixture_state *>(this);
+    self->push_params();
+    hp_grid g(*self, uint32_t(c), blocks, std::vector<double>());
+    std::vector<double> out(g.npoints);
+    double *out_dev = nullptr;
+    check(msc_device_alloc(ctx_, 8 * out.size(), reinterpret_cast<void **>(&out_dev)));
+    const int rc = msc_hp_grid_score(g.h, g.slots, out_dev);
+    if (rc == MSC_OK) check(msc_device_download(ctx_, out.data(), out_dev, 8 * out.size()));
+    msc_device_free(ctx_, out_dev);
+    check(rc);
+    return out;
+  }
+  // one grid Gibbs step of component c: draws a point from the softmax of prior + likelihood (Philox(seed, sweep, ...),
+  // msc_hp_grid_gibbs) and installs it on the device and in the component's hypers object; returns its index
+  size_t grid_component_hp(size_t c, const std::vector<float> &blocks, const std::vector<double> &logprior, uint64_t seed,
+                           uint64_t sweep) {
+    sync();
+    if (c >= hypers_.size()) throw std::runtime_error("invalid component");
+    push_params();
+    hp_grid g(*this, uint32_t(c), blocks, logprior);
+    uint32_t k = 0;
+    check(msc_hp_grid_gibbs(st_, &g.h, 1, g.slots, seed, sweep, &k, nullptr));
+    const size_t nf = blocks.size() / g.npoints;
+    install_component_hp(c, std::vector<float>(blocks.begin() + k * nf, blocks.begin() + (k + 1) * nf));
+    return k;
+  }
+  // the same for the CRP concentration: `alphas` (> 0) and their log-prior; gm_'s alpha follows
+  size_t grid_cluster_hp(const std::vector<float> &alphas, const std::vector<double> &logprior, uint64_t seed,
+                         uint64_t sweep) {
+    sync();
+    push_params();
+    hp_grid g(*this, MSC_HP_CLUSTER, alphas, logprior);
+    uint32_t k = 0;
+    check(msc_hp_grid_gibbs(st_, &g.h, 1, g.slots, seed, sweep, &k, nullptr));
+    gm_.get_hp_mutator("alpha").set<float>(alphas[k]);
+    alpha_pushed_ = alphas[k];                           // (the device took it in the same call)
+    return k;
+  }
+
   // One synchronous Gibbs sweep over all entities on the device: every entity is scored leave-one-out against the
   // tables as they stand, with the CRP prior (every free slot is an empty group on offer and they share alpha,
   // which is the prior of "a new group" however many empty groups the host has created), re-drawn with the
@@ -301,6 +346,53 @@ private:
     }
   }
   mutable bool stale_ = false;
+
+  // a grid of one call and the device mask of the slots the partition holds
+  struct hp_grid {
+    msc_context *ctx;
+    msc_hp_grid *h = nullptr;
+    uint8_t *slots = nullptr;
+    uint32_t npoints;
+    hp_grid(mixture_state &s, uint32_t feature, const std::vector<float> &blocks, const std::vector<double> &logprior)
+        : ctx(s.ctx_) {
+      const size_t nf = feature == MSC_HP_CLUSTER ? 1 : s.hp_pushed_.at(feature).size();
+      if (!nf || blocks.empty() || blocks.size() % nf) throw std::runtime_error("grid blocks do not match the hp size");
+      npoints = uint32_t(blocks.size() / nf);
+      if (!logprior.empty() && logprior.size() != npoints) throw std::runtime_error("one log-prior value per point expected");
+      check(msc_hp_grid_create(s.st_, feature, blocks.data(), nf, npoints, logprior.empty() ? nullptr : logprior.data(), &h));
+      std::vector<uint8_t> mask(s.kmax_, 0);
+      for (auto it = s.gm_.begin(); it != s.gm_.end(); ++it) mask[it->second.data_] = 1;
+      check(msc_device_alloc(ctx, mask.size(), reinterpret_cast<void **>(&slots)));
+      check(msc_device_upload(ctx, slots, mask.data(), mask.size()));
+    }
+    ~hp_grid() {
+      msc_hp_grid_destroy(h);
+      msc_device_free(ctx, slots);
+    }
+  };
+  // the chosen block into the component's hypers object (its mutators), and what the device now holds
+  void install_component_hp(size_t c, const std::vector<float> &blk) {
+    msc_feature_spec spec;
+    std::vector<float> hp;
+    hypers_[c]->device_spec(spec, hp);
+    static const char *const two[] = {"alpha", "beta"}, *const gp[] = {"alpha", "inv_beta"},
+                             *const bnb[] = {"alpha", "beta", "r"}, *const nich[] = {"mu", "kappa", "sigmasq", "nu"};
+    const char *const *keys = nullptr;
+    switch (spec.family) {
+      case MSC_BB: case MSC_BBNC: keys = two; break;
+      case MSC_GP: keys = gp; break;
+      case MSC_BNB: keys = bnb; break;
+      case MSC_NICH: keys = nich; break;
+      case MSC_DD: case MSC_DM: {
+        auto m = hypers_[c]->get_hp_mutator("alphas");
+        for (size_t i = 0; i < blk.size(); i++) m.set<float>(blk[i], i);
+      } break;
+      default: throw std::runtime_error("component has no hyper-parameter grid");
+    }
+    if (keys)
+      for (size_t i = 0; i < blk.size(); i++) hypers_[c]->get_hp_mutator(keys[i]).set<float>(blk[i]);
+    hp_pushed_[c] = blk;
+  }
 
   // hyper-parameters can change behind our back (mutators are raw pointers), so what the device holds is
   // compared with the hypers objects before every device call; a handful of floats per component

@@ -385,6 +385,43 @@ int msc_sweep_step_sharded(msc_state *st, const msc_dataview *view, const uint32
 int msc_accumulate_sharded(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                            uint64_t nrows, const int32_t *z_dev, msc_comm *comm);
 
+/* ---- grid hyper-parameter inference (grid_feature_hp / grid_cluster_hp downstream) ---- */
+/*
+ * A grid of hyper-parameter points of one feature, or of the CRP concentration (feature MSC_HP_CLUSTER: blocks of one
+ * float, alpha, every one > 0), owned by the state: npoints full hp blocks of block_floats = msc_hp_floats(family, dim)
+ * floats each (the msc_state_set_hp layout) and, nullable, npoints log-prior values, copied to the device once and kept
+ * on the host.  Freed by msc_hp_grid_destroy or with the state.  Synchronous.  MSC_EINVAL for a block size that is not
+ * msc_hp_floats, npoints == 0 or a non-positive alpha; MSC_EUNSUPPORTED for niw (upstream defines no niw grid, and every
+ * point would need its own factorisation of Psi).
+ */
+typedef struct msc_hp_grid msc_hp_grid;
+#define MSC_HP_CLUSTER 0xFFFFFFFFu
+int msc_hp_grid_create(msc_state *st, uint32_t feature, const float *host_blocks, size_t block_floats, uint32_t npoints,
+                       const double *host_logprior, msc_hp_grid **out);
+int msc_hp_grid_destroy(msc_hp_grid *grid);
+/*
+ * out_dev[g] (double[npoints]) = log marginal likelihood of the feature's groups under grid point g, no prior:
+ * sum over the counted slots k of score_data(hp = point g, group k) (entity_state.hpp score_likelihood), in double, in a
+ * fixed order (two calls on the same tables give the same bits).  The counted slots are those with a non-zero group count,
+ * or, with slots_dev (device uint8[ngroups]), those with a non-zero byte -- e.g. every group a group_manager holds, empty
+ * ones included; no other slot is read.  The CRP grid: out_dev[g] = score_assignment(alpha_g) of the group counts
+ * (group_manager.hpp:207-218; slots_dev does not apply).  Asynchronous.  MSC_EINVAL between msc_sweep_step_begin and
+ * msc_state_commit_reduce.
+ */
+int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, double *out_dev);
+/*
+ * One grid Gibbs step for n grids of the state (at most one per feature; MSC_HP_CLUSTER allowed): score every grid as
+ * above, add its prior, draw a point from the softmax (the CDF in double in index order, dart = Philox(seed, sweep,
+ * stream) with stream = 2^64 - 1 - feature, and 2^64 - 1 - nfeatures for alpha: counters no sweep gives a row), and
+ * install it exactly as msc_state_set_hp / msc_state_set_alpha would.  chosen_host[i] = index drawn from grids[i];
+ * scores_dev (nullable; per grid a device double[npoints] or NULL) receives prior + likelihood.  Every rank of a sharded
+ * sweep holding the same tables and passing the same seed draws the same points.  Synchronous: ONE host synchronisation
+ * whatever n is.  MSC_EINVAL when a grid has no point of finite positive weight (its feature keeps its hp) and between
+ * msc_sweep_step_begin and msc_state_commit_reduce.
+ */
+int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint32_t n, const uint8_t *slots_dev, uint64_t seed,
+                      uint64_t sweep, uint32_t *chosen_host, double *const *scores_dev);
+
 /* ---- per-value entry (the virtual group API, base.hpp:25-28) ----------- */
 typedef enum msc_value_op {
   MSC_OP_ADD = 0, MSC_OP_REMOVE = 1, MSC_OP_SCORE_VALUE = 2, MSC_OP_SCORE_DATA = 3
