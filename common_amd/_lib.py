@@ -22,6 +22,8 @@ ACC_RESET, ACC_SUBTRACT, ACC_NO_COMMIT = 0x1, 0x2, 0x4
 OP_ADD, OP_REMOVE, OP_SCORE_VALUE, OP_SCORE_DATA = range(4)
 ABI_VERSION = 1
 HP_CLUSTER = 0xFFFFFFFF          # msc_hp_grid_create's feature index of the CRP concentration
+PRED_MASKED_ONLY = 0x1
+PRED_GROUP_KEY = 0xD1B54A32D192ED03   # msc_sample_predictive's group draw uses key = seed ^ this
 
 
 class MicroscopesHipError(RuntimeError):
@@ -118,6 +120,8 @@ _SIGS = {
     "msc_hp_grid_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "msc_hp_grid_gibbs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                     C.c_void_p]),
+    "msc_sample_predictive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "msc_value_op_single": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "msc_relation_slice_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,

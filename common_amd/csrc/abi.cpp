@@ -1323,6 +1323,7 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
 }
 
 static void hp_state_release(msc_state *st);
+static void pred_state_release(msc_state *st);
 
 extern "C" int msc_state_destroy(msc_state *st) {
   if (!st) return MSC_OK;
@@ -1330,6 +1331,7 @@ extern "C" int msc_state_destroy(msc_state *st) {
   (void)hipStreamSynchronize(st->ctx->stream);
   if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
   hp_state_release(st);
+  pred_state_release(st);
   free_all(st->owned);
   delete st;
   return MSC_OK;
@@ -2977,4 +2979,122 @@ extern "C" int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint3
     }
   }
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// posterior predictive sampling (group::sample_value, base.hpp:29, for a block of rows; kernels_pred.hip)
+// ---------------------------------------------------------------------------
+static constexpr uint64_t kPredGroupKey = 0xD1B54A32D192ED03ull;   // the group draw's key is seed ^ this
+
+static void pred_state_release(msc_state *st) {
+  (void)hipHostFree(st->pred_stage);
+  if (st->pred_upload) (void)hipEventDestroy(st->pred_upload);
+  st->pred_stage = nullptr;
+  st->pred_upload = nullptr;
+  st->pred_stage_cap = 0;
+  st->pred_feats_host.clear();
+  (void)hipFree(st->pred_feats_dev);
+  (void)hipFree(st->pred_par);
+  (void)hipFree(st->pred_z);
+  st->pred_feats_dev = nullptr;
+  st->pred_par = nullptr;
+  st->pred_z = nullptr;
+  st->pred_feats_cap = st->pred_par_cap = st->pred_z_cap = 0;
+}
+
+extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                     uint64_t nrows, uint64_t row_id0, const int32_t *z_dev, int32_t *z_out_dev,
+                                     uint32_t flags, uint64_t seed, uint64_t sweep, void *const *out_dev) {
+  MSC_REQUIRE(st && view && out_dev, "null argument");
+  MSC_REQUIRE((flags & ~MSC_PRED_MASKED_ONLY) == 0, "unknown flags 0x%x", flags);
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_sample_predictive between msc_sweep_step_begin and msc_state_commit_reduce: the "
+              "tables hold one rank's uncommitted sums");
+  for (uint32_t f = 0; f < st->nfeat; f++) {
+    if (out_dev[f] == nullptr) continue;
+    const int fam = st->feats[f].family;
+    if (fam == MSC_DM)
+      return fail(MSC_EUNSUPPORTED, "feature %u: dm has no sample_value upstream (dm.cpp:100-111)", f);
+    if (fam == MSC_NOOP) return fail(MSC_EUNSUPPORTED, "feature %u: the noop model has no values to draw", f);
+    MSC_REQUIRE(f < 0x8000u, "feature %u: the draw's Philox counter holds feature indices below 32768", f);
+  }
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  if (nrows == 0) return MSC_OK;
+  MSC_TRY(ensure_derived(st));                              // (raw tables current; niw: the whitening matrices)
+  const hipStream_t s = st->ctx->stream;
+  // the features drawn and their parameter blocks
+  std::vector<PredFeat> pfs;
+  std::vector<size_t> par_off;                              // each drawn feature's first double in pred_par
+  size_t par_len = 0;
+  for (uint32_t f = 0; f < st->nfeat; f++) {
+    if (out_dev[f] == nullptr) continue;
+    const msc_feature_host &h = st->feats[f];
+    const FeatDesc &d = st->desc_host[f];
+    PredFeat p;
+    p.family = h.family;
+    p.dim = h.dim;
+    p.feature = f;
+    p.stride = pred_par_stride(h.family, h.dim);
+    p.par = nullptr;                                        // (set below, once the buffer is known)
+    p.hp = h.hp_dev;
+    p.raw_u32 = h.raw_u32;
+    p.raw_f32 = h.raw_f32;
+    p.niw_w64 = h.niw_w64;
+    p.col = d.col;
+    p.mask = d.mask;
+    p.out = out_dev[f];
+    pfs.push_back(p);
+    par_off.push_back(par_len);
+    par_len += (size_t)p.stride * st->K;
+  }
+  MSC_TRY(hp_reserve(st, &st->pred_par, st->pred_par_cap, par_len));
+  if (pfs.size() > st->pred_feats_cap || !st->pred_feats_dev) st->pred_feats_host.clear();   // (a new buffer holds nothing)
+  MSC_TRY(hp_reserve(st, &st->pred_feats_dev, st->pred_feats_cap, pfs.size()));
+  for (size_t i = 0; i < pfs.size(); i++) pfs[i].par = st->pred_par + par_off[i];
+  // the descriptors go up only when they changed (a loop of calls uploads nothing), from pinned staging memory: the copy
+  // reads it when it runs, so the host waits -- for the previous upload only -- before it writes the staging again
+  const size_t pbytes = pfs.size() * sizeof(PredFeat);
+  if (pbytes && (st->pred_feats_host.size() != pfs.size() ||
+                 std::memcmp(st->pred_feats_host.data(), pfs.data(), pbytes) != 0)) {
+    if (st->pred_stage_cap < pfs.size()) {
+      if (st->pred_upload_pending) MSC_HIP(hipEventSynchronize(st->pred_upload));
+      st->pred_upload_pending = false;
+      (void)hipHostFree(st->pred_stage);
+      st->pred_stage = nullptr;
+      st->pred_stage_cap = 0;
+      MSC_HIP(hipHostMalloc(reinterpret_cast<void **>(&st->pred_stage), pbytes, hipHostMallocDefault));
+      st->pred_stage_cap = pfs.size();
+    }
+    if (!st->pred_upload) MSC_HIP(hipEventCreateWithFlags(&st->pred_upload, hipEventDisableTiming));
+    if (st->pred_upload_pending) MSC_HIP(hipEventSynchronize(st->pred_upload));
+    std::memcpy(st->pred_stage, pfs.data(), pbytes);
+    MSC_HIP(hipMemcpyAsync(st->pred_feats_dev, st->pred_stage, pbytes, hipMemcpyHostToDevice, s));
+    MSC_HIP(hipEventRecord(st->pred_upload, s));
+    st->pred_upload_pending = true;
+    st->pred_feats_host = pfs;
+  }
+  if (launch_pred_prepare(s, st->pred_feats_dev, pfs, st->K, st->kpad)) return fail(MSC_EHIP, "k_pred_prepare launch failed");
+  // the group draw: the sweep's own assignment pass for rows that are all unassigned, under a key no sweep uses; the
+  // sweep's (seed, sweep) pair on the device is put back afterwards
+  const int32_t *z = z_dev;
+  if (z == nullptr) {
+    MSC_TRY(hp_reserve(st, &st->pred_z, st->pred_z_cap, nrows));
+    MSC_HIP(hipMemsetAsync(st->pred_z, 0xff, nrows * sizeof(int32_t), s));
+    const bool had = st->rng_valid;
+    const uint64_t had_seed = st->rng_seed, had_sweep = st->rng_sweep;
+    MSC_TRY(sweep_assign_impl(st, view, cols, row0, nrows, row_id0, st->pred_z, seed ^ kPredGroupKey, sweep));
+    st->rng_valid = false;
+    if (had) {
+      if (launch_rng_set(s, st->rng_dev, had_seed, had_sweep)) return fail(MSC_EHIP, "k_rng_set launch failed");
+      st->rng_valid = true;
+      st->rng_seed = had_seed;
+      st->rng_sweep = had_sweep;
+    }
+    z = st->pred_z;
+  }
+  if (launch_pred_sample(s, st->pred_feats_dev, pfs, st->K, row0, nrows, row_id0, z, z_out_dev,
+                         (flags & MSC_PRED_MASKED_ONLY) != 0, seed, sweep))
+    return fail(MSC_EHIP, "k_pred_sample launch failed");
+  return MSC_OK;
 }

@@ -227,4 +227,11 @@ int launch_hp_grid_draw(hipStream_t stream, const HpJob *jobs_dev, uint32_t njob
 int launch_unpack(hipStream_t stream, const uint8_t *records, const uint8_t *mask, uint64_t nrows,
                   uint32_t rowsize, uint32_t maskrowsize, const void *feats_dev, uint32_t nfeat);
 
+// kernels_pred.hip
+int launch_pred_prepare(hipStream_t stream, const PredFeat *pfs_dev, const std::vector<PredFeat> &pfs, uint32_t K,
+                        uint32_t kpad);
+int launch_pred_sample(hipStream_t stream, const PredFeat *pfs_dev, const std::vector<PredFeat> &pfs, uint32_t K,
+                       uint64_t row0, uint64_t nrows, uint64_t row_id0, const int32_t *z, int32_t *z_out,
+                       bool masked_only, uint64_t seed, uint64_t sweep);
+
 }  // namespace msc

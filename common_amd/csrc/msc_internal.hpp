@@ -227,6 +227,38 @@ struct HpJob {
   uint64_t stream;           // draw: Philox counter (msc_hp_grid_gibbs)
 };
 
+// One drawn feature of msc_sample_predictive as the kernels of kernels_pred.hip read it: where its hp and raw tables are,
+// the predictive parameters k_pred_prepare writes (par: [K][stride] doubles, pred_par_stride), and the columns a draw
+// reads (the bound view's column in the model's value type, its mask) and writes (out: nrows x count values).
+struct PredFeat {
+  int32_t family;
+  uint32_t dim;
+  uint32_t feature;          // the state's feature index (the draw's Philox counter)
+  uint32_t stride;           // doubles of par per group
+  double *par;
+  const float *hp;
+  const uint32_t *raw_u32;
+  const float *raw_f32;
+  const double *niw_w64;     // niw: k_niw_prepare's whitening matrices
+  const void *col;
+  const uint8_t *mask;
+  void *out;
+};
+// bb / bbnc {P(v = 0)}, gp {shape, scale}, bnb {alpha', beta', r}, dd {cumulative weights[dim]}, nich {mu', scale, nu'},
+// niw {mu'[d], L[d (d + 1) / 2], dof}
+inline uint32_t pred_par_stride(int family, uint32_t dim) {
+  switch (family) {
+    case MSC_BB:
+    case MSC_BBNC: return 1;
+    case MSC_GP: return 2;
+    case MSC_BNB:
+    case MSC_NICH: return 3;
+    case MSC_DD: return dim;
+    case MSC_NIW: return dim + dim * (dim + 1) / 2 + 1;
+    default: return 0;
+  }
+}
+
 // one feature of the index matrix as k_pack_look_idx reads it
 struct LookIdxSrc {
   const void *col;
@@ -532,6 +564,19 @@ struct msc_state {
   uint32_t *hp_chosen_dev = nullptr;
   size_t hp_jobs_cap = 0, hp_chosen_cap = 0;
   std::vector<msc::HpJob> hp_jobs_host;
+  // posterior predictive sampling (abi.cpp msc_sample_predictive): the drawn features' descriptors and parameters, and
+  // the scratch assignment of a group draw, grown on demand
+  msc::PredFeat *pred_feats_dev = nullptr;
+  size_t pred_feats_cap = 0;
+  double *pred_par = nullptr;
+  size_t pred_par_cap = 0;
+  int32_t *pred_z = nullptr;
+  size_t pred_z_cap = 0;
+  std::vector<msc::PredFeat> pred_feats_host;   // what pred_feats_dev holds
+  msc::PredFeat *pred_stage = nullptr;          // pinned staging of the upload, pred_stage_cap descriptors
+  size_t pred_stage_cap = 0;
+  hipEvent_t pred_upload = nullptr;             // recorded after the upload from pred_stage
+  bool pred_upload_pending = false;
 };
 
 // a grid of hyper-parameter points of one feature (or of alpha: feature == MSC_HP_CLUSTER), uploaded once

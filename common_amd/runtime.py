@@ -515,6 +515,58 @@ class State(object):
                                                chosen.ctypes.data_as(C.c_void_p), sp))
         return (chosen, scores) if want_scores else chosen
 
+    # posterior predictive sampling -------------------------------------------
+    _PRED_DTYPES = {L.BB: torch.uint8, L.BBNC: torch.uint8, L.GP: torch.uint32, L.BNB: torch.uint32, L.DD: torch.int32,
+                    L.NICH: torch.float32, L.NIW: torch.float32}
+
+    def sample_predictive(self, view, z=None, seed=0, sweep=0, masked_only=False, features=None, row0=0, nrows=None,
+                          row_id0=None, cols=None, out=None):
+        """Posterior predictive draws for rows [row0, row0 + nrows) of the view (msc_sample_predictive).
+        z: int32 device tensor of the rows' groups, or None to draw each row's group from the CRP term plus the scores of
+        its observed entries.  features: state feature indices to draw (default: all).  out: optional dict feature ->
+        device tensor to write into (rows that are skipped keep what it held).  -> (dict feature -> device tensor of
+        nrows values -- [nrows, dim] for niw --, int32 device tensor of the groups used)."""
+        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
+        n = view.nrows - row0 if nrows is None else int(nrows)
+        if row0 < 0 or n < 0 or row0 + n > view.nrows:
+            raise ValueError("rows [%d, %d) outside the view (%d rows)" % (row0, row0 + n, view.nrows))
+        feats = list(range(len(self.features))) if features is None else [int(f) for f in features]
+        for f in feats:
+            if not 0 <= f < len(self.features):
+                raise ValueError("feature %d outside the state (%d features)" % (f, len(self.features)))
+            if self.features[f][0] == L.DM:
+                raise L.MicroscopesHipError(-4, "feature %d: dm has no sample_value upstream" % f)
+            if self.features[f][0] not in self._PRED_DTYPES:
+                raise L.MicroscopesHipError(-4, "feature %d: the family has no values to draw" % f)
+        zp = None
+        if z is not None:
+            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n or z.device != self.ctx.torch_device:
+                raise ValueError("z must be a contiguous int32 device tensor of nrows entries")
+            zp = C.c_void_p(z.data_ptr())
+        out = dict(out or {})
+        ptrs = (C.c_void_p * len(self.features))()
+        for f in feats:
+            fam, dim = self.features[f]
+            shape = (n, dim) if fam == L.NIW else (n,)
+            dt = self._PRED_DTYPES[fam]
+            t = out.get(f)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=self.ctx.torch_device)
+            elif t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.ctx.torch_device:
+                raise ValueError("out[%d] must be a contiguous %s device tensor of shape %s" % (f, dt, shape))
+            out[f] = t
+            ptrs[f] = t.data_ptr() if n else None
+        groups = torch.full((n,), -1, dtype=torch.int32, device=self.ctx.torch_device)
+        L.check(self.ctx.lib.msc_sample_predictive(self._h, view._h, self._cols(cols), int(row0), n,
+                                                   int(row0 if row_id0 is None else row_id0), zp,
+                                                   C.c_void_p(groups.data_ptr()) if n else None,
+                                                   L.PRED_MASKED_ONLY if masked_only else 0, int(seed), int(sweep), ptrs))
+        return {f: out[f] for f in feats}, groups
+
+    def impute(self, view, z=None, seed=0, sweep=0, **kw):
+        """sample_predictive with masked_only=True: masked entries drawn, observed ones copied (the completed columns)."""
+        return self.sample_predictive(view, z=z, seed=seed, sweep=sweep, masked_only=True, **kw)
+
     def close(self):
         if getattr(self, "_h", None):
             for g in list(getattr(self, "_grids", ())):  # (the library frees a state's grids with it)

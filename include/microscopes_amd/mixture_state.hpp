@@ -21,6 +21,8 @@
 #include <map>
 #include <memory>
 #include <set>
+#include <cstring>
+#include <string>
 #include <stdexcept>
 #include <vector>
 
@@ -56,6 +58,8 @@ public:
       any_nonconj_ = any_nonconj_ || nonconj_.back();
     }
     view_ = data.to_device(ctx_, &col_types);
+    specs_ = specs;
+    col_types_ = col_types;
     check(msc_state_create(ctx_, specs.data(), uint32_t(specs.size()), uint32_t(kmax_), &st_));
     check(msc_device_alloc(ctx_, 4 * (n_ ? n_ : 1), reinterpret_cast<void **>(&z_dev_)));
     check(msc_pinned_alloc(ctx_, 4 * kmax_, reinterpret_cast<void **>(&row_host_), reinterpret_cast<void **>(&row_dev_)));   // the score row lands in host memory
@@ -270,6 +274,74 @@ public:
     stale_ = true;      // the host partition follows when somebody looks at it: sweep after sweep costs the host nothing
   }
 
+  // Posterior predictive draws for new, partly observed rows (downstream's sample_post_pred): each row of `rows` (the
+  // state's column layout, with its mask) gets a group drawn from the CRP term plus the scores of its observed entries
+  // against the tables as they stand, then its masked entries are drawn from that group's posterior predictive -- ONE
+  // msc_sample_predictive call (z NULL, MSC_PRED_MASKED_ONLY; Philox counters of seed and sweep as the header documents).
+  // Returns the completed records in `rows`' own layout: observed bytes as they were, masked values converted to their
+  // field's type (a vector value with any masked element is drawn whole).  groups (nullable) receives each row's slot.
+  std::vector<uint8_t> sample_post_pred(const common::recarray::row_major_dataview &rows, uint64_t seed, uint64_t sweep,
+                                        std::vector<int32_t> *groups = nullptr) {
+    if (rows.types().size() != specs_.size()) throw std::runtime_error("one column per component model expected");
+    const size_t n = rows.size(), nf = specs_.size();
+    const auto layout = common::runtime_type::GetOffsetsAndSize(rows.types());
+    std::vector<uint8_t> out(n * layout.rowsize_);
+    std::memcpy(out.data(), rows.records(), out.size());
+    if (groups) groups->assign(n, -1);
+    if (n == 0) return out;
+    push_params(true);
+    msc_dataview *v = rows.to_device(ctx_, &col_types_);
+    std::vector<void *> cols(nf, nullptr);
+    std::vector<size_t> esize(nf, 0);
+    int32_t *z_out = nullptr;
+    int rc = msc_device_alloc(ctx_, 4 * n, reinterpret_cast<void **>(&z_out));
+    for (size_t f = 0; f < nf && rc == MSC_OK; f++) {
+      esize[f] = specs_[f].family == MSC_BB || specs_[f].family == MSC_BBNC ? 1 : 4;    // the header's output types
+      rc = msc_device_alloc(ctx_, n * rows.types()[f].n() * esize[f], &cols[f]);
+    }
+    if (rc == MSC_OK)
+      rc = msc_sample_predictive(st_, v, nullptr, 0, n, 0, nullptr, z_out, MSC_PRED_MASKED_ONLY, seed, sweep, cols.data());
+    std::vector<std::vector<uint8_t>> host(nf);
+    std::vector<int32_t> zh(n);
+    for (size_t f = 0; f < nf && rc == MSC_OK; f++) {
+      host[f].resize(n * rows.types()[f].n() * esize[f]);
+      rc = msc_device_download(ctx_, host[f].data(), cols[f], host[f].size());
+    }
+    if (rc == MSC_OK) rc = msc_device_download(ctx_, zh.data(), z_out, 4 * n);
+    const std::string err = rc == MSC_OK ? std::string() : std::string(msc_last_error());
+    for (void *c : cols) msc_device_free(ctx_, c);
+    msc_device_free(ctx_, z_out);
+    msc_dataview_destroy(v);
+    if (rc != MSC_OK) throw std::runtime_error(err);
+    // masked values into the records, converted as runtime_cast does
+    size_t moff = 0;
+    for (size_t f = 0; f < nf; f++) {
+      const common::runtime_type &t = rows.types()[f];
+      const unsigned cnt = t.n();
+      for (size_t i = 0; i < n; i++) {
+        const bool *m = rows.mask() ? rows.mask() + i * layout.maskrowsize_ : nullptr;
+        bool any = false;
+        for (unsigned e = 0; e < cnt && m; e++) any = any || m[moff + e];
+        if (!any) continue;
+        common::value_mutator vm(out.data() + i * layout.rowsize_ + layout.offsets_[f], t);
+        const uint8_t *src = host[f].data() + (i * cnt) * esize[f];
+        for (unsigned e = 0; e < cnt; e++) {
+          switch (specs_[f].family) {
+            case MSC_BB:
+            case MSC_BBNC: vm.set<bool>(src[e] != 0, e); break;
+            case MSC_GP:
+            case MSC_BNB: { uint32_t x; std::memcpy(&x, src + 4 * e, 4); vm.set<uint32_t>(x, e); break; }
+            case MSC_DD: { int32_t x; std::memcpy(&x, src + 4 * e, 4); vm.set<int32_t>(x, e); break; }
+            default: { float x; std::memcpy(&x, src + 4 * e, 4); vm.set<float>(x, e); break; }
+          }
+        }
+      }
+      moff += cnt;
+    }
+    if (groups) *groups = zh;
+    return out;
+  }
+
   // the device handles, for callers that mix in calls of microscopes_hip.h
   msc_state *device_state() const { return st_; }
   msc_dataview *device_view() const { return view_; }
@@ -444,6 +516,8 @@ private:
   common::group_manager<size_t> gm_;                   // group data = the group's device slot
   std::vector<models::hypers_shared_ptr> hypers_;
   std::vector<std::vector<float>> hp_pushed_;
+  std::vector<msc_feature_spec> specs_;                // the device families of the components
+  std::vector<int32_t> col_types_;                     // the value type each column is converted to on upload
   std::vector<bool> nonconj_;                          // per component: does a new group start from a draw?
   bool any_nonconj_ = false;
   float alpha_pushed_ = -1.f;

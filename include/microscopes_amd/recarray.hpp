@@ -144,6 +144,9 @@ public:
   row_accessor get(std::size_t i) const override {
     return row_accessor(data_ + rowsize() * i, mask_ ? mask_ + maskrowsize() * i : nullptr, &types());
   }
+  // the packed records and their mask (one bool per element, null: nothing masked), in storage order
+  const uint8_t *records() const { return data_; }
+  const bool *mask() const { return mask_; }
   void reset_permutation() { pi_.clear(); }
   // Fisher-Yates over 0..n-1 (util::inplace_permute, util.hpp:85-94)
   void permute(rng_t &rng) {

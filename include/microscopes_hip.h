@@ -422,6 +422,44 @@ int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, double *out_d
 int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint32_t n, const uint8_t *slots_dev, uint64_t seed,
                       uint64_t sweep, uint32_t *chosen_host, double *const *scores_dev);
 
+/* ---- posterior predictive sampling (group::sample_value, base.hpp:29) ---- */
+#define MSC_PRED_MASKED_ONLY 0x1u /* draw masked entries only; observed ones are copied */
+/*
+ * Posterior predictive draws for rows [row0, row0+nrows) of the view (cols as in msc_score_value).
+ * Groups:
+ *   z_dev non-NULL (int32[nrows], indexed from row0): row r uses group z_dev[r] (in-sample imputation).  A row whose id
+ *     is < 0 or >= ngroups is skipped: none of its outputs is written.
+ *   z_dev NULL: every row's group is drawn as msc_sweep_assign draws an UNASSIGNED row -- its observed entries scored
+ *     against the tables as they stand (no leave-one-out), plus log pseudocount, util::sample_discrete_log -- with the
+ *     uniform Philox4x32-10(key = seed ^ 0xD1B54A32D192ED03, counter = (global row id, sweep)): a key no sweep with the
+ *     same (seed, sweep) uses.
+ *   z_out_dev (nullable, int32[nrows]) receives the group each row used.
+ * Values: out_dev has one entry per state feature; out_dev[f] == NULL: feature f is not drawn, else it receives nrows x
+ * count values of the type the kernels read for the family:
+ *   bb / bbnc uint8 0|1, gp / bnb uint32, dd int32, nich float, niw float[dim] row-major.
+ * Without MSC_PRED_MASKED_ONLY every entry is drawn from the posterior predictive of its row's group; with it only the
+ * masked ones are, and observed entries are copied as the model's value type (the output is the completed column).  A niw
+ * value with any masked element counts as missing and is drawn whole.
+ * Draws (the predictives of the host sampler, include/microscopes_amd/hip_models.hpp detail::sampler): bb / bbnc / dd by inverse CDF of ONE
+ * uniform, gp Gamma then Poisson, bnb Beta then Gamma then Poisson, nich Student-t, niw mu' + L z sqrt(dof / chi2).
+ * Counters: the entry (global row id R = row_id0 + r, state feature f) reads the Philox4x32-10 blocks b = 0, 1, ... of
+ *   key = seed, counter = (R & 0xffffffff, R >> 32, sweep & 0xffffffff, 0x80000000 | (f & 0x7fff) << 16 | b)
+ * word by word (w0..w3 of block 0, then block 1, ...).  A one-uniform draw takes u = (w0 >> 8) * 2^-24 of block 0 and
+ * picks the smallest value v whose predictive CDF exceeds u (bb: v = 1 iff u >= P(v = 0); dd: u * sum of weights
+ * against the cumulative weights alpha_i + counts_i).  Every other uniform takes two consecutive words a, b:
+ * u = ((a >> 5) * 2^26 + (b >> 6) + 0.5) * 2^-53; normals are Box-Muller pairs (r cos, r sin) of two such uniforms.
+ * Sweeps' counters have a last word below 2^31, so no draw here shares one with a sweep; the sweep index enters mod 2^32.
+ * The same arguments give the same bits, and the draws of a row do not depend on the rows around it (calls over row
+ * ranges with matching row_id0 give the bits of one call over all of them).
+ * The state is read-only: tables, counts, score tables, alpha and hp are left as they were.
+ * MSC_EUNSUPPORTED for a dm (or noop) feature with a non-NULL output (upstream dm.cpp:100-111 throws), the state
+ * untouched; MSC_EINVAL for bad arguments, a feature index >= 32768 drawn, and between msc_sweep_step_begin and
+ * msc_state_commit_reduce.  Asynchronous on the context's stream.
+ */
+int msc_sample_predictive(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                          uint64_t row_id0, const int32_t *z_dev, int32_t *z_out_dev, uint32_t flags, uint64_t seed,
+                          uint64_t sweep, void *const *out_dev);
+
 /* ---- per-value entry (the virtual group API, base.hpp:25-28) ----------- */
 typedef enum msc_value_op {
   MSC_OP_ADD = 0, MSC_OP_REMOVE = 1, MSC_OP_SCORE_VALUE = 2, MSC_OP_SCORE_DATA = 3
