@@ -51,6 +51,19 @@ static int dev_alloc(std::vector<void *> &owned, T **out, size_t count) {
   return MSC_OK;
 }
 
+// a state's buffer that grows on demand to `n` elements.  No sync and no free: the old buffer stays in st->owned until
+// the state is destroyed, because a captured step graph may still use it (hp_reserve syncs and frees instead)
+template <typename T>
+static int grow(msc_state *st, T *&buf, size_t &cap, size_t n) {
+  if (cap >= n) return MSC_OK;
+  void *p = nullptr;
+  MSC_HIP(hipMalloc(&p, n * sizeof(T)));
+  st->owned.push_back(p);
+  buf = static_cast<T *>(p);
+  cap = n;
+  return MSC_OK;
+}
+
 }  // namespace msc
 
 using namespace msc;
@@ -726,9 +739,12 @@ static void default_hp(int family, uint32_t dim, std::vector<float> &hp) {
 // kGrpRows rows per group, never across the two phases.
 // what the choice of kernels depends on, for one plan
 struct PlanFacts {
-  bool roles_ok = false, nich_only = false, lookups_only = false, tail_ok = false, tail_masked_nich = false, tail_dm = false;
+  ScorePath path = MSC_PATH_TILE;      // (msc_state::tile_path)
+  bool tail_ok = false, tail_masked_nich = false, tail_dm = false;
   uint32_t tail_max_rows = 0, tail_pack_rows = 0;
 };
+// the tile plans whose nich waves read the pack and the x matrix (msc::NichPos)
+static bool stages_nich(ScorePath path) { return path == MSC_PATH_TILE_ROLES || path == MSC_PATH_NICH_PACK; }
 
 // group packing, lookup kinds and runs of a plan `t` whose first `split` entries are the first phase (`extra`: one more
 // table row for a masked lookup column's zero row)
@@ -790,22 +806,23 @@ static PlanFacts plan_layout(std::vector<FeatDesc> &t, uint32_t split, const std
   }
   PlanFacts pf;
   bool has_dm = false;
-  pf.roles_ok = split > 0 && split < n;
+  bool roles_ok = split > 0 && split < n;
   for (uint32_t i = 0; i < n; i++) {
     has_dm |= t[i].family == MSC_DM;
-    if (i < split && t[i].kind == MSC_KIND_GENERIC) pf.roles_ok = false;
+    if (i < split && t[i].kind == MSC_KIND_GENERIC) roles_ok = false;
   }
-  if (has_dm) pf.roles_ok = false;
+  if (has_dm) roles_ok = false;
   // the kernels whose waves are all nich waves (k_score_nich_pack): no first phase at all and two or more plain nich features,
   // or a first phase of at most kPackMaxLookups lookup features beside at least twice as many nich features (the lookups
   // are gathered from L2 there, ~0.03 ms a feature and million rows: 8 bb + 8 nich sweep 0.81 -> 0.70 ms, 2 gp + 12 nich
   // 0.99 -> 0.86; with 16 bb + 4 nich -- four fused lookups, four nich -- the role-split kernels are as good or better)
-  pf.nich_only = (split == 0 && n >= 2) || (pf.roles_ok && !has_dm && split <= (uint32_t)kPackMaxLookups && n - split >= 2 * split &&
-                                            std::getenv("MSC_NO_PACK_LOOKUPS") == nullptr);
-  if (pf.nich_only) pf.roles_ok = false;
+  const bool nich_only = (split == 0 && n >= 2) || (roles_ok && !has_dm && split <= (uint32_t)kPackMaxLookups && n - split >= 2 * split &&
+                                                    std::getenv("MSC_NO_PACK_LOOKUPS") == nullptr);
   // staged lookup features and nothing else: k_score_lookups / k_sweep_lookups (sixteen lookup waves of 16 sums)
-  pf.lookups_only = split == n && n > 0 && !has_dm && std::getenv("MSC_NO_LOOKUPS_KERNEL") == nullptr;
-  for (uint32_t i = 0; i < n; i++) pf.lookups_only &= t[i].kind != MSC_KIND_GENERIC;
+  bool lookups_only = split == n && n > 0 && !has_dm && std::getenv("MSC_NO_LOOKUPS_KERNEL") == nullptr;
+  for (uint32_t i = 0; i < n; i++) lookups_only &= t[i].kind != MSC_KIND_GENERIC;
+  // (roles_ok needs split < n and lookups_only split == n; nich_only wins over roles_ok)
+  pf.path = nich_only ? MSC_PATH_NICH_PACK : roles_ok ? MSC_PATH_TILE_ROLES : lookups_only ? MSC_PATH_LOOKUPS : MSC_PATH_TILE;
   // the lane <-> row kernel for a partly filled last tile (k_score_tail_rows): lookup features only in the first phase
   // (what it implements), whatever the second holds of plain nich features
   pf.tail_ok = std::getenv("MSC_NO_NARROW_TAIL") == nullptr;
@@ -1054,14 +1071,7 @@ static int plan_groups(msc_state *st) {
       left -= m;
     }
   }
-  const size_t need = quads.size() * 32 * (size_t)st->kpad;
-  if (st->fuse_tab_floats < need) {
-    void *p = nullptr;
-    MSC_HIP(hipMalloc(&p, need * sizeof(float)));
-    st->owned.push_back(p);
-    st->fuse_tab = static_cast<float *>(p);
-    st->fuse_tab_floats = need;
-  }
+  MSC_TRY(grow(st, st->fuse_tab, st->fuse_tab_floats, quads.size() * 32 * (size_t)st->kpad));
   std::vector<bool> taken(n, false);
   for (size_t q = 0; q < quads.size(); q++) {
     const Fused &fq = quads[q];
@@ -1127,8 +1137,8 @@ static int plan_groups(msc_state *st) {
   for (FeatDesc &d : tf) d.rn_pack = nullptr, d.rn_pos = nullptr, d.rn_x = nullptr, d.rn_n2 = d.rn_n2p = 0;
   for (FeatDesc &d : t) d.rn_pack = nullptr, d.rn_pos = nullptr, d.rn_x = nullptr, d.rn_n2 = d.rn_n2p = 0;
   static const bool no_roles_pack = std::getenv("MSC_NO_ROLES") != nullptr;      // (A/B knob: the kernels that run the phases one after the other)
-  if (bview == nullptr || no_roles_pack) facts.roles_ok = facts.nich_only = false;
-  if (facts.roles_ok || facts.nich_only) {
+  if (stages_nich(facts.path) && (bview == nullptr || no_roles_pack)) facts.path = MSC_PATH_TILE;
+  if (stages_nich(facts.path)) {
     const uint32_t s0 = st->fuse_split, n2 = st->fuse_nfeat - s0, n2p = (n2 + 3u) & ~3u;
     std::vector<NichPos> pos(n2p);
     std::vector<const void *> xcols(n2);
@@ -1147,21 +1157,19 @@ static int plan_groups(msc_state *st) {
       MSC_HIP(hipStreamSynchronize(st->ctx->stream));           // (`pos` is this function's)
       FeatDesc &h = tf[s0];
       h.rn_pack = st->rn_pack, h.rn_pos = st->rn_pos, h.rn_x = xm, h.rn_n2 = n2, h.rn_n2p = n2p;
-    } else facts.roles_ok = facts.nich_only = false;           // (no copy: the kernels that stage the nich constants need none)
+    } else facts.path = MSC_PATH_TILE;                         // (no copy: the kernels that stage the nich constants need none)
   }
   // ... and what their lookup waves read (FeatDesc::lk_idx): the first phase's slot rows, row by row
   for (FeatDesc &d : tf) d.lk_idx = nullptr, d.lk_l4 = d.lk_goff = 0;
   for (FeatDesc &d : t) d.lk_idx = nullptr, d.lk_l4 = d.lk_goff = 0;
-  if (bview == nullptr) facts.lookups_only = false;
-  if (facts.roles_ok || facts.lookups_only) {
+  if (bview == nullptr && facts.path == MSC_PATH_LOOKUPS) facts.path = MSC_PATH_TILE;
+  if (facts.path == MSC_PATH_TILE_ROLES || facts.path == MSC_PATH_LOOKUPS) {
     const uint32_t *im = nullptr;
     uint32_t l4 = 0;
     if (look_idx_matrix(bview, tf, st->fuse_split, &im, &l4)) tf[0].lk_idx = im, tf[0].lk_l4 = l4;
-    else facts.roles_ok = facts.lookups_only = false;
+    else facts.path = MSC_PATH_TILE;
   }
-  st->tile_roles_ok = facts.roles_ok;
-  st->tile_nich_only = facts.nich_only;
-  st->tile_lookups_only = facts.lookups_only;
+  st->tile_path = facts.path;
   {
     // the prices the kernels are chosen by (launchers.hpp PlanCost): staged lookup features and table rows of the first
     // phase, nich features (the second phase's, and masked ones evaluated in the first)
@@ -1173,7 +1181,8 @@ static int plan_groups(msc_state *st) {
     }
     PlanCost pc;
     const double first = 6.0 + 0.45 * lookups + 0.012 * rows;
-    pc.tile_round_us = facts.nich_only ? 6.0 + 1.3 * nich + 3.0 * lookups : facts.roles_ok ? first + 0.75 * nich : facts.lookups_only ? 0.75 * first : first + 1.5 * nich;
+    pc.tile_round_us = facts.path == MSC_PATH_NICH_PACK ? 6.0 + 1.3 * nich + 3.0 * lookups : facts.path == MSC_PATH_TILE_ROLES ? first + 0.75 * nich
+                       : facts.path == MSC_PATH_LOOKUPS ? 0.75 * first : first + 1.5 * nich;
     pc.sweep_round_us = pc.tile_round_us + 2.5;              // (+ the draws)
     pc.tail_fixed_us = 2.0;                                  // (per launch and round of 1024 rows a CU: tools/scans/grid_scan.py at 1M rows,
     pc.tail_group_us = 0.5 + 0.03 * lookups + 0.057 * nich;  //  K = 8 against K = 32 for six feature lists; C3: 2 + 2.5 a group)
@@ -1240,6 +1249,8 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
   }
   st->n_i64 = n_i64;
   st->n_f64 = n_f64;
+  st->nich1 = nfeatures == 1 && st->feats[0].family == MSC_NICH;
+  for (const msc_feature_host &h : st->feats) st->has_dm |= h.family == MSC_DM, st->n_niw += h.family == MSC_NIW;
   int rc;
   auto bail = [&](int code) { free_all(st->owned); return code; };
   if ((rc = dev_alloc(st->owned, &st->red_i64, n_i64))) return bail(rc);
@@ -1788,14 +1799,11 @@ static int ensure_crp(msc_state *st) {
 // ---------------------------------------------------------------------------
 // scalar families go through one fused kernel (scores summed over features in registers);
 // every niw feature then adds its MFMA pass on top.
-static int ensure_own(msc_state *st, uint64_t nrows) {
-  if (st->own_cap >= nrows) return MSC_OK;
-  void *p = nullptr;
-  MSC_HIP(hipMalloc(&p, nrows * sizeof(float)));
-  st->owned.push_back(p);
-  st->own = static_cast<float *>(p);
-  st->own_cap = nrows;
-  return MSC_OK;
+
+// the rows the choice of kernels goes by: the bound view's, or those of the whole a sharded driver announced
+// (msc_state_set_sweep_rows) -- never a call's (route_sweep)
+static uint64_t view_rows(const msc_state *st) {
+  return st->sweep_rows_hint ? st->sweep_rows_hint : st->bound_view ? st->bound_view->nrows : 0;
 }
 
 // the tables of the plan's fused bb runs follow their members' (whatever updated those -- prepare, commit, an entity op):
@@ -1803,26 +1811,21 @@ static int ensure_own(msc_state *st, uint64_t nrows) {
 // ... and so does what the plan's nich blocks go by (NichPlanInfo: is a block's c1 one number per group, how far a value may
 // lie before a product of four could overflow) -- the same launch
 static int refresh_fused_tables(msc_state *st) {
-  const bool packed = st->tile_roles_ok || st->tile_nich_only;
+  const bool packed = stages_nich(st->tile_path);
   if (!st->fuse_any && !st->nich_blocks_any && !packed) return MSC_OK;
   if (launch_fuse_tables(st->ctx->stream, st->desc_fuse_dev, (int)st->fuse_split, (st->nich_blocks_any || packed) ? (int)st->fuse_nfeat : (int)st->fuse_split, st->kpad))
     return fail(MSC_EHIP, "k_fuse_tables launch failed");
   return MSC_OK;
 }
 
-// what the narrow kernels of a partly filled last tile need (launchers.hpp); the packed-table scratch grows on demand
-static int tail_plan(msc_state *st, TailPlan &tp) {
+// what the narrow kernels of a partly filled last tile need (launchers.hpp): a last tile of at most kTailMaxGroups groups
+// on a plan they take; the packed-table scratch grows on demand
+static int tail_plan(msc_state *st, TailPlan &tp, bool exact = true) {
   tp = TailPlan();
   tp.cost = st->plan_cost;
-  if (!st->tile_narrow_tail_ok) return MSC_OK;
-  const size_t need = (size_t)st->tail_pack_rows * 64;
-  if (st->tail_pack_floats < need) {
-    void *p = nullptr;
-    MSC_HIP(hipMalloc(&p, need * sizeof(float)));
-    st->owned.push_back(p);
-    st->tail_pack = static_cast<float *>(p);
-    st->tail_pack_floats = need;
-  }
+  tp.exact = exact;
+  if (!st->tile_narrow_tail_ok || st->K - (st->kpad - kGroupTile) > kTailMaxGroups) return MSC_OK;
+  MSC_TRY(grow(st, st->tail_pack, st->tail_pack_floats, (size_t)st->tail_pack_rows * 64));
   tp.ok = true;
   tp.masked_nich = st->tail_masked_nich;
   tp.dm = st->tail_dm;
@@ -1852,21 +1855,25 @@ static bool loo_needs_heavy(const msc_state *st) {
   return false;
 }
 
+// every row's leave-one-out value (its own group's score, the prior's when crp) into st->own
+static int run_loo_own(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z, bool crp) {
+  MSC_TRY(grow(st, st->own, st->own_cap, nrows));
+  if (launch_loo_own(st->ctx->stream, st->ctx->num_cus, loo_needs_heavy(st), st->loo_staged != 0, st->desc_tile_dev, (int)st->nfeat,
+                     st->K, st->kpad, row0, nrows, z, crp ? st->logpc : nullptr, st->own))
+    return fail(MSC_EHIP, "k_loo_own launch failed");
+  return MSC_OK;
+}
+
 // K <= 64 and nothing but scalar families whose tables all fit 64 KiB of LDS at 4 L groups per row: the narrow tiling
 // (kernels_sweep.hip k_narrow).  Returns L = lanes per row (4 / 8 / 16) or 0, and the table rows to stage.
 static int narrow_lanes(const msc_state *st, uint32_t *table_rows) {
   static const bool off = std::getenv("MSC_NO_NARROW") != nullptr;        // (A/B knob; the tests run both tilings)
   // (32 lanes per row for K <= 128 was measured and loses to the 256-group tiling: 8 bb at K = 100, 0.52 against 0.20 ms)
   if (off || st->K > 64) return 0;
-  // Views of many rows leave it to the lane <-> row kernel (round 3's; by the bound VIEW's rows or the rows of the whole a
-  // sharded driver announced, so that a state keeps one kernel for all of a view's rows: the two add a row's features in
-  // different orders).  At a million rows that kernel is 1.3-2.7x the faster one (tools/scans/k_monotone.sh, MSC_NO_NARROW:
+  // Views of many rows leave it to the lane <-> row kernel (round 3's; by view_rows: route_sweep's shard rule).  At a million rows that kernel is 1.3-2.7x the faster one (tools/scans/k_monotone.sh, MSC_NO_NARROW:
   // sixteen dd32 columns at K = 32 0.34 -> 0.13 ms, 8 bb + 8 nich at K = 64 0.48 -> 0.26, sixteen nich at K = 32 0.30 -> 0.18);
   // this tiling is for the small problems it was made for (C1: 10k rows, 8 us a pass): views below kNarrowMaxRows rows.
-  {
-    const uint64_t view_rows = st->sweep_rows_hint ? st->sweep_rows_hint : st->bound_view ? st->bound_view->nrows : 0;
-    if (view_rows >= kNarrowMaxRows && st->tile_narrow_tail_ok && std::getenv("MSC_TAIL_MIN_ROWS") == nullptr) return 0;
-  }
+  if (view_rows(st) >= kNarrowMaxRows && st->tile_narrow_tail_ok && std::getenv("MSC_TAIL_MIN_ROWS") == nullptr) return 0;
   const int L = st->K <= 16 ? 4 : st->K <= 32 ? 8 : 16;
   uint32_t rows = 0;
   for (uint32_t f = 0; f < st->nfeat; f++) {
@@ -1884,8 +1891,8 @@ static int narrow_lanes(const msc_state *st, uint32_t *table_rows) {
     }
   }
   if ((size_t)rows * L * 16 > 64u * 1024u) return 0;
-  // ... and only where it is the cheaper tiling for THIS plan (by the plan alone, not the call's rows: the narrow kernel
-  // adds the features in the caller's order, the tile kernels in the plan's, so a state keeps one of them for all its rows).
+  // ... and only where it is the cheaper tiling for THIS plan (by the plan alone: the narrow kernel adds the features in
+  // the caller's order, the tile kernels in the plan's).
   // Per million rows, us, at 16 lanes a row (tools/scans/grid_scan.py at 100k rows, k_monotone.sh): a bb column 30 (the tile
   // plan fuses four of them into one lookup, this tiling cannot), dd / gp 50, nich 60, half of it at 8 lanes and no less at
   // 4; against the tile kernels' rounds at the plan's price (launchers.hpp PlanCost; up to 128 groups the role-split /
@@ -1898,12 +1905,22 @@ static int narrow_lanes(const msc_state *st, uint32_t *table_rows) {
       us += fam == MSC_BB || fam == MSC_BBNC ? 30.0 : fam == MSC_NICH ? 60.0 : fam == MSC_NOOP ? 0.0 : 50.0;
     }
     us *= std::max(L, 8) / 16.0;
-    const bool pair = pair_mode_ok(st->tile_roles_ok ? MSC_PATH_TILE_ROLES : st->tile_nich_only ? MSC_PATH_NICH_PACK : st->tile_lookups_only ? MSC_PATH_LOOKUPS : MSC_PATH_TILE, st->K, false);
+    const bool pair = pair_mode_ok(st->tile_path, st->K, false);
     const double tile = st->plan_cost.tile_round_us * (1.0e6 / 128.0 / st->ctx->num_cus) * (pair ? kPairTileShare : 1.0);
     if (us > 1.25 * tile) return 0;
   }
   *table_rows = rows;
   return L;
+}
+
+// Which kernels score a state (by the plan and view_rows: route_sweep's shard rule): k_narrow when `lanes` is set
+// (lanes, table_rows: narrow_lanes), else the scalar features' pass on `path`; then every niw feature's own pass
+struct ScoreRoute { int lanes = 0; uint32_t table_rows = 0; ScorePath path = MSC_PATH_TILE; };
+static ScoreRoute route_score(const msc_state *st) {
+  ScoreRoute r;
+  r.lanes = narrow_lanes(st, &r.table_rows);
+  r.path = st->nich1 ? MSC_PATH_NICH1 : st->has_dm ? MSC_PATH_TILE_DM : st->tile_path;
+  return r;
 }
 
 // k_score_nich1's launch shape for a pass of `nrows` x K into `out`: what msc_score_tune remembered for this very
@@ -1934,42 +1951,29 @@ static int nich1_shape_for(msc_context *ctx, const void *out, uint64_t nrows, ui
 static int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z_dev, bool crp,
                      bool niw_f32, float *out_dev, uint64_t ld_out) {
   hipStream_t s = st->ctx->stream;
-  if (z_dev) {
-    MSC_TRY(ensure_own(st, nrows));
-    if (launch_loo_own(s, st->ctx->num_cus, loo_needs_heavy(st), st->loo_staged != 0, st->desc_tile_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z_dev, crp ? st->logpc : nullptr, st->own))
-      return fail(MSC_EHIP, "k_loo_own launch failed");
-  }
-  uint32_t n_niw = 0;
-  for (auto &h : st->feats) n_niw += h.family == MSC_NIW;
-  const bool nich1 = st->nfeat == 1 && st->feats[0].family == MSC_NICH;
-  uint32_t narrow_rows = 0;
-  if (const int nl = narrow_lanes(st, &narrow_rows)) {
-    if (launch_narrow(s, st->ctx->num_cus, nl, narrow_rows, false, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows,
-                      z_dev, st->own, crp ? st->logpc : nullptr, out_dev, ld_out, 0, nullptr, nullptr, ZeroSpans()))
+  const float *prior = crp ? st->logpc : nullptr;
+  if (z_dev) MSC_TRY(run_loo_own(st, row0, nrows, z_dev, crp));
+  const ScoreRoute r = route_score(st);
+  if (r.lanes) {
+    if (launch_narrow(s, st->ctx->num_cus, r.lanes, r.table_rows, false, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows,
+                      z_dev, st->own, prior, out_dev, ld_out, 0, nullptr, nullptr, ZeroSpans()))
       return fail(MSC_EHIP, "k_narrow launch failed: %s", hipGetErrorString(hipGetLastError()));
     return MSC_OK;
   }
   bool written = false;
-  if (n_niw < st->nfeat || crp) {
-    bool has_dm = false;
-    for (auto &h : st->feats) has_dm |= h.family == MSC_DM;
-    const int path = nich1 ? MSC_PATH_NICH1 : has_dm ? MSC_PATH_TILE_DM : st->tile_roles_ok ? MSC_PATH_TILE_ROLES : st->tile_nich_only ? MSC_PATH_NICH_PACK : st->tile_lookups_only ? MSC_PATH_LOOKUPS : MSC_PATH_TILE;
-    const FeatDesc *descs = path == MSC_PATH_NICH1 ? st->desc_dev : st->desc_fuse_dev;
+  if (st->n_niw < st->nfeat || crp) {
+    const bool nich1 = r.path == MSC_PATH_NICH1;
     TailPlan tail;
-    tail.cost = st->plan_cost;
-    if (path != MSC_PATH_NICH1 && st->K - (st->kpad - kGroupTile) <= kTailMaxGroups)
+    if (!nich1) {
       MSC_TRY(tail_plan(st, tail));
-    if (path != MSC_PATH_NICH1) MSC_TRY(refresh_fused_tables(st));
-    auto launch = [&](int shape) {
-      return launch_score(s, st->ctx->num_cus, path, tail, shape, descs,
-                          (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0,
-                          nrows, z_dev, st->own, crp ? st->logpc : nullptr, out_dev, ld_out);
-    };
+      MSC_TRY(refresh_fused_tables(st));
+    }
     // The single-nich pass is bound by the HBM write stream; its launch shape (rows per visit, visits per wave =
     // write fronts) is the default (4 rows, 2 visits) unless msc_score_tune settled another one for passes like this
     // (same buffer first, else same size), or MSC_NICH1_SHAPE fixes it.  Nothing here waits for the device.
-    const int shape = path == MSC_PATH_NICH1 ? nich1_shape_for(st->ctx, out_dev, nrows, st->K) : 0;
-    if (launch(shape))
+    const int shape = nich1 ? nich1_shape_for(st->ctx, out_dev, nrows, st->K) : 0;
+    if (launch_score(s, st->ctx->num_cus, r.path, tail, shape, nich1 ? st->desc_dev : st->desc_fuse_dev, (int)st->fuse_nfeat,
+                     (int)st->fuse_split, st->K, st->kpad, row0, nrows, z_dev, st->own, prior, out_dev, ld_out))
       return fail(MSC_EHIP, "score kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     written = true;
     for (uint32_t f = 0; f < st->nfeat; f++)
@@ -1979,13 +1983,7 @@ static int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t
   }
   for (uint32_t f = 0; f < st->nfeat; f++) {
     if (st->feats[f].family != MSC_NIW) continue;
-    if (z_dev && st->niw_qown_cap < nrows) {            // leave-one-out: the score kernel parks q of the own group here
-      void *p = nullptr;
-      MSC_HIP(hipMalloc(&p, nrows * sizeof(double)));
-      st->owned.push_back(p);
-      st->niw_qown = static_cast<double *>(p);
-      st->niw_qown_cap = nrows;
-    }
+    if (z_dev) MSC_TRY(grow(st, st->niw_qown, st->niw_qown_cap, nrows));   // leave-one-out: the score kernel parks q of the own group here
     if (launch_niw_score(s, st->ctx->num_cus, st->desc_dev, f, st->feats[f].dim, st->K, st->kpad, row0, nrows, z_dev, written,
                          niw_f32, st->niw_qown, out_dev, ld_out))
       return fail(MSC_EHIP, "k_score_niw launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -2023,9 +2021,8 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
   if (ms_out) *ms_out = 0.f;
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  uint32_t narrow_rows = 0;
-  const bool nich1 = st->nfeat == 1 && st->feats[0].family == MSC_NICH && narrow_lanes(st, &narrow_rows) == 0;
-  if (!nich1 || nrows == 0) return MSC_OK;
+  const ScoreRoute r = route_score(st);
+  if (r.lanes || r.path != MSC_PATH_NICH1 || nrows == 0) return MSC_OK;
   MSC_TRY(ensure_derived(st));
   hipStream_t s = st->ctx->stream;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -2146,14 +2143,7 @@ static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32
     for (uint32_t f = 0; f < st->nfeat; f++) {
       if (st->feats[f].family != MSC_NIW) continue;
       MSC_REQUIRE(nrows < (1ull << 32), "niw accumulate takes at most 2^32 - 1 rows per call");
-      const size_t need = 2 * (size_t)st->K + 1 + (size_t)nrows;
-      if (st->niw_scratch_len < need) {
-        void *p = nullptr;
-        MSC_HIP(hipMalloc(&p, need * sizeof(uint32_t)));
-        st->owned.push_back(p);
-        st->niw_scratch = static_cast<uint32_t *>(p);
-        st->niw_scratch_len = need;
-      }
+      MSC_TRY(grow(st, st->niw_scratch, st->niw_scratch_len, 2 * (size_t)st->K + 1 + (size_t)nrows));
       if (launch_niw_accumulate(s, st->ctx->num_cus, st->desc_dev, f, st->K, row0, nrows, z_dev,
                                 (flags & MSC_ACC_SUBTRACT) ? -1 : 1, st->niw_scratch, st->feats[f].dim))
         return fail(MSC_EHIP, "niw accumulate launch failed");
@@ -2218,9 +2208,7 @@ extern "C" int msc_score_data(msc_state *st, float *out_dev) {
   MSC_TRY(ensure_raw(st));
   if (launch_score_data(st->ctx->stream, st->desc_dev, (int)st->nfeat, st->K, st->kpad, out_dev))
     return fail(MSC_EHIP, "k_score_data launch failed");
-  bool any_niw = false;
-  for (auto &h : st->feats) any_niw |= h.family == MSC_NIW;
-  if (any_niw) {
+  if (st->n_niw) {
     MSC_TRY(ensure_derived(st));   // ln det Psi_n comes from the prepare step
     for (uint32_t f = 0; f < st->nfeat; f++)
       if (st->feats[f].family == MSC_NIW &&
@@ -2237,19 +2225,17 @@ static bool sweep_is_niw1(const msc_state *st) {
 }
 
 // the lane <-> row kernel fills the chip from ~260k rows on; with fewer the tile kernels' rounds of 128-row chunks can be
-// shorter.  Decided on the bound view's row count, so every row range of it takes the same kernels.
+// shorter.  Decided on the view's row count, so every row range of it takes the same kernels.
 // (priced with the cost model of launchers.hpp: the lane <-> row launches -- plus, beyond 64 groups, the trip through
 // 128 floats per row and the row sampler -- against the rounds of the fused tile sweep kernel; for a tail beyond a full
 // tile, against one more tile pass, the materialised matrix and the sampler)
-// PAIR mode of the role-split sweep kernel (at most 128 groups; kernels_sweep.hip): by the bound view's rows (or the rows
-// of the whole a sharded driver announced), never the call's -- its draw associates a row's entries differently from the
-// other tile kernels', so every row range of a view takes the same one
+// PAIR mode of the role-split sweep kernel (at most 128 groups; kernels_sweep.hip): its draw associates a row's entries
+// differently from the other tile kernels'
 static bool sweep_pair_mode(const msc_state *st) {
-  const uint64_t rows = st->sweep_rows_hint ? st->sweep_rows_hint : st->bound_view ? st->bound_view->nrows : 0;
-  return rows >= kTailMinRows && pair_mode_ok(st->tile_roles_ok ? MSC_PATH_TILE_ROLES : st->tile_nich_only ? MSC_PATH_NICH_PACK : st->tile_lookups_only ? MSC_PATH_LOOKUPS : MSC_PATH_TILE, st->K, false);
+  return view_rows(st) >= kTailMinRows && pair_mode_ok(st->tile_path, st->K, false);
 }
 static bool sweep_rows_pays(const msc_state *st, uint32_t groups) {
-  const uint64_t rows = st->sweep_rows_hint ? st->sweep_rows_hint : st->bound_view ? st->bound_view->nrows : 0;
+  const uint64_t rows = view_rows(st);
   if (const char *forced = std::getenv("MSC_TAIL_MIN_ROWS")) return rows >= (uint64_t)std::atoll(forced);
   if (rows < kTailMinRows) return false;
   const int cus = st->ctx->num_cus;
@@ -2271,12 +2257,53 @@ static bool sweep_rows_pays(const msc_state *st, uint32_t groups) {
   return rows_us < tile_us;
 }
 
+// no niw feature and no count beyond the tables: what the fused sweep kernels score
+static bool sweep_plain(const msc_state *st) {
+  for (uint32_t f = 0; f < st->nfeat; f++) if (gp_beyond_table(st, f)) return false;
+  return st->n_niw == 0;
+}
+
 static bool sweep_is_fused(const msc_state *st) {
   if (sweep_is_niw1(st)) return true;
-  const bool nich1 = st->nfeat == 1 && st->feats[0].family == MSC_NICH;
-  for (uint32_t f = 0; f < st->nfeat; f++)
-    if (st->feats[f].family == MSC_NIW || gp_beyond_table(st, f)) return false;
-  return nich1 ? st->K <= sweep_nich1_rows_max_groups() : st->K <= 256;
+  if (!sweep_plain(st)) return false;
+  return st->nich1 ? st->K <= sweep_nich1_rows_max_groups() : st->K <= 256;
+}
+
+// How a sweep assigns a state's rows: the kind sweep_assign_impl switches on, and what that kind needs.
+// THE SHARD RULE: some kernels add a row's terms in a different order from others, so the choice depends only on the plan
+// and on view_rows (the bound view's, or the whole's a sharded driver announced), never on the call's rows: that is what
+// makes a shard draw the same bits as the whole.  Recomputed on every call (the bound view, the hint and the knobs read
+// here change between calls).  A launcher may still decline a call by its geometry: the caller then falls back.
+// (rows: K <= 64, the lane <-> row kernel draws its own row; rows_sampler: up to 128 groups, its scores into 128 floats a
+// row, then the row sampler; roles_tail: 256 < K <= 384, the groups beyond the tile from the narrow kernel into tail_ld
+// floats a row, then the fused kernel over the tile draws over both; generic: chunks scored into scratch, then sampled)
+enum class SweepKind { niw1, nich1, nich1_rows, narrow, rows, rows_sampler, mixed, roles_tail, generic };
+struct SweepRoute {
+  SweepKind kind = SweepKind::generic;
+  int lanes = 0; uint32_t table_rows = 0;   // narrow (narrow_lanes)
+  bool pair = false;                        // rows, rows_sampler, mixed: PAIR mode of the tile kernels (sweep_pair_mode)
+  uint64_t tail_ld = 0;                     // roles_tail
+};
+static SweepRoute route_sweep(const msc_state *st) {
+  SweepRoute r;
+  if (sweep_is_niw1(st)) {
+    r.kind = SweepKind::niw1;
+  } else if (sweep_is_fused(st)) {
+    if (st->nich1) r.kind = st->K > 1024 ? SweepKind::nich1_rows : SweepKind::nich1;
+    else if ((r.lanes = narrow_lanes(st, &r.table_rows)) != 0) r.kind = SweepKind::narrow;
+    else {
+      r.pair = sweep_pair_mode(st);
+      r.kind = SweepKind::mixed;
+      if (st->tile_narrow_tail_ok && st->K <= kTailMaxGroups && std::getenv("MSC_NO_SWEEP_ROWS") == nullptr && sweep_rows_pays(st, st->K))
+        r.kind = st->K <= 64 ? SweepKind::rows : SweepKind::rows_sampler;
+    }
+  } else if (!st->nich1 && !st->has_dm && st->tile_path != MSC_PATH_TILE && st->tile_narrow_tail_ok && st->K > 256 &&
+             st->K <= (uint32_t)kGroupTile + kTailMaxGroups && std::getenv("MSC_NO_FUSED_TAIL") == nullptr &&
+             sweep_rows_pays(st, st->K - kGroupTile) && sweep_plain(st)) {
+    r.kind = SweepKind::roles_tail;
+    r.tail_ld = st->K <= (uint32_t)kGroupTile + 64 ? 64 : 128;
+  }
+  return r;
 }
 
 // the sampling kernels read (seed, sweep) from the state's device pair and the step ends by incrementing the sweep
@@ -2298,118 +2325,83 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
   MSC_TRY(ensure_crp(st));
   hipStream_t s = st->ctx->stream;
   const int cus = st->ctx->num_cus;
-  const bool nich1 = st->nfeat == 1 && st->feats[0].family == MSC_NICH;
-  bool has_dm = false;
-  for (uint32_t f = 0; f < st->nfeat; f++) has_dm |= st->feats[f].family == MSC_DM;
-  int rc = -2;
-  bool not_zeroed = false;
   ZeroSpans zero;
   if (zeroed) {
     zero.a = reinterpret_cast<unsigned long long *>(st->red_i64); zero.na = st->n_i64;
     zero.b = reinterpret_cast<unsigned long long *>(st->red_f64); zero.nb = st->n_f64;
   }
-  if (sweep_is_niw1(st)) {
-    rc = launch_sweep_niw1(s, cus, st->feats[0].dim, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc,
-                           st->rng_dev, zero);
-    if (zeroed) *zeroed = rc == 0;
-  } else if (sweep_is_fused(st)) {
-    if (!nich1) {                                       // (the single-nich kernel computes the own-group values itself)
-      MSC_TRY(ensure_own(st, nrows));
-      if (launch_loo_own(s, st->ctx->num_cus, loo_needs_heavy(st), st->loo_staged != 0, st->desc_tile_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z_dev, st->logpc, st->own))
-        return fail(MSC_EHIP, "k_loo_own launch failed");
-    }
-    uint32_t narrow_rows = 0;
-    const int nl = nich1 ? 0 : narrow_lanes(st, &narrow_rows);
-    if (nich1 && st->K > 1024) {                          // beyond the register-resident table: lane <-> row
-      if (!st->rows_table) {
-        void *p = nullptr;
-        MSC_HIP(hipMalloc(&p, sweep_nich1_rows_table_floats(st->kpad) * sizeof(float)));
-        st->owned.push_back(p);
-        st->rows_table = static_cast<float *>(p);
-      }
+  const SweepRoute r = route_sweep(st);
+  int rc = 0;
+  bool zeroes = true;                                   // the kernel emptied the additive tables on its way (with `zeroed`)
+  bool generic = r.kind == SweepKind::generic;          // (or a launcher declined this call: see below)
+  switch (r.kind) {
+    case SweepKind::niw1:
+      rc = launch_sweep_niw1(s, cus, st->feats[0].dim, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero);
+      break;
+    case SweepKind::nich1_rows:
+      MSC_TRY(grow(st, st->rows_table, st->rows_table_floats, sweep_nich1_rows_table_floats(st->kpad)));
       rc = launch_sweep_nich1_rows(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero, st->rows_table);
-    } else if (nich1) rc = launch_sweep_nich1(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero);
-    else if (nl) rc = launch_narrow(s, cus, nl, narrow_rows, true, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z_dev,
-                                    st->own, st->logpc, nullptr, 0, row_id0, z_dev, st->rng_dev, zero);
-    else if (refresh_fused_tables(st)) return MSC_EHIP;    // (everything below walks the fused plan)
-    else if (st->tile_narrow_tail_ok && st->K <= kTailMaxGroups && std::getenv("MSC_NO_SWEEP_ROWS") == nullptr &&
-             sweep_rows_pays(st, st->K)) {
-      // at most 128 groups on a plan of lookup + plain nich features: the lane <-> row kernel, whose cost follows the
-      // groups (a tile pass costs what 256 cost).  Up to 64: scores and draw in one launch, a lane draws its own row.
-      // Beyond: the scores into 128 floats per row, then the row sampler.  The choice looks at the VIEW's rows, not the
-      // call's (a shard draws what the whole draws).
-      TailPlan tail;
-      MSC_TRY(tail_plan(st, tail));
-      tail.exact = false;
-      if (st->K <= 64) {
-        rc = launch_sweep_rows(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0,
-                               z_dev, st->own, st->logpc, st->rng_dev, zero);
-        if (rc == 1) rc = -2;
-      } else {
-        const size_t need = ((size_t)nrows + 16) * 128;
-        if (st->tail_floats < need) {
-          void *p = nullptr;
-          MSC_HIP(hipMalloc(&p, need * sizeof(float)));
-          st->owned.push_back(p);
-          st->tail_scores = static_cast<float *>(p);
-          st->tail_floats = need;
+      break;
+    case SweepKind::nich1:                                // (the single-nich kernel computes the own-group values itself)
+      rc = launch_sweep_nich1(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero);
+      break;
+    case SweepKind::narrow:
+      MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
+      rc = launch_narrow(s, cus, r.lanes, r.table_rows, true, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z_dev,
+                         st->own, st->logpc, nullptr, 0, row_id0, z_dev, st->rng_dev, zero);
+      break;
+    case SweepKind::rows:
+    case SweepKind::rows_sampler:
+    case SweepKind::mixed:
+      MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
+      MSC_TRY(refresh_fused_tables(st));                  // (these walk the fused plan)
+      rc = 1;
+      if (r.kind != SweepKind::mixed) {
+        TailPlan tail;
+        MSC_TRY(tail_plan(st, tail, false));
+        if (r.kind == SweepKind::rows) {
+          rc = launch_sweep_rows(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0,
+                                 z_dev, st->own, st->logpc, st->rng_dev, zero);
+        } else {
+          MSC_TRY(grow(st, st->tail_scores, st->tail_floats, ((size_t)nrows + 16) * 128));
+          rc = launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, 0, row0, nrows,
+                                 z_dev, st->own, st->logpc, st->tail_scores, 128);
+          if (rc == 0) {
+            rc = launch_sample_rows(s, cus, st->tail_scores, 128, st->K, nrows, row_id0, z_dev, st->rng_dev);
+            zeroes = false;                               // (nothing emptied the additive tables on the way)
+          }
         }
-        rc = launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, 0, row0, nrows,
-                               z_dev, st->own, st->logpc, st->tail_scores, 128);
-        if (rc == 0) {
-          rc = launch_sample_rows(s, cus, st->tail_scores, 128, st->K, nrows, row_id0, z_dev, st->rng_dev);
-          not_zeroed = true;                              // (nothing emptied the additive tables on the way)
-        } else if (rc == 1) rc = -2;
       }
-      if (rc == -2) rc = launch_sweep_mixed(s, cus, has_dm, st->tile_roles_ok, sweep_pair_mode(st), st->tile_nich_only, st->tile_lookups_only, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero);
-    } else rc = launch_sweep_mixed(s, cus, has_dm, st->tile_roles_ok, sweep_pair_mode(st), st->tile_nich_only, st->tile_lookups_only, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero);
-    if (zeroed) *zeroed = rc == 0 && !not_zeroed;
-  }
-  // 256 < K <= 384 on a role-split state: the groups beyond the tile from the narrow kernel (leave-one-out value and prior
-  // included) into 64 or 128 floats per row, then the fused kernel over the tile draws over both -- nothing materialised
-  // but that.  Where it pays (sweep_rows_pays: by the view's row count, so that a shard draws from the same bits as the whole).
-  if (rc == -2 && !nich1 && !has_dm && (st->tile_roles_ok || st->tile_nich_only || st->tile_lookups_only) && st->tile_narrow_tail_ok && tile_roles_enabled() && st->K > 256 &&
-      st->K <= (uint32_t)kGroupTile + kTailMaxGroups && std::getenv("MSC_NO_FUSED_TAIL") == nullptr &&
-      sweep_rows_pays(st, st->K - kGroupTile)) {
-    const uint64_t tail_ld = st->K <= (uint32_t)kGroupTile + 64 ? 64 : 128;
-    bool plain = true;
-    for (uint32_t f = 0; f < st->nfeat; f++) plain &= st->feats[f].family != MSC_NIW && !gp_beyond_table(st, f);
-    if (plain) {
+      if (rc == 1)                                        // (mixed, or the lane <-> row kernel declined this call's rows)
+        rc = launch_sweep_mixed(s, cus, st->has_dm, st->tile_path, r.pair, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero);
+      break;
+    case SweepKind::roles_tail: {
       MSC_TRY(refresh_fused_tables(st));
-      MSC_TRY(ensure_own(st, nrows));
-      if (launch_loo_own(s, cus, loo_needs_heavy(st), st->loo_staged != 0, st->desc_tile_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z_dev, st->logpc, st->own))
-        return fail(MSC_EHIP, "k_loo_own launch failed");
-      const size_t need = ((size_t)nrows + 16) * tail_ld;
-      if (st->tail_floats < need) {
-        void *p = nullptr;
-        MSC_HIP(hipMalloc(&p, need * sizeof(float)));
-        st->owned.push_back(p);
-        st->tail_scores = static_cast<float *>(p);
-        st->tail_floats = need;
-      }
-      // (the kernel stores at out + row * ld + k: handing it tail_scores - 256 puts group 256 + j at column j)
+      MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
+      MSC_TRY(grow(st, st->tail_scores, st->tail_floats, ((size_t)nrows + 16) * r.tail_ld));
+      // (the kernel stores at out + row * ld + k: handing it tail_scores - 256 puts group 256 + j at column j; one sum per
+      // group: nothing else scores these groups for a draw)
       TailPlan tail;
-      MSC_TRY(tail_plan(st, tail));
-      tail.exact = false;                                  // (nothing else scores these groups for a draw: one sum per group)
+      MSC_TRY(tail_plan(st, tail, false));
       // (65 .. 128 groups beyond the tile on a role-split plan: ONE pass of the role-split kernel in PAIR mode at tile 1
-      // instead of three launches of the lane <-> row kernel -- round 5; by the plan and K alone, so a shard takes what the
-      // whole takes)
+      // instead of three launches of the lane <-> row kernel -- round 5)
       int tail_rc = -2;
-      if (st->tile_roles_ok && tail_ld == 128 && std::getenv("MSC_NO_PAIR") == nullptr)
+      if (st->tile_path == MSC_PATH_TILE_ROLES && r.tail_ld == 128 && std::getenv("MSC_NO_PAIR") == nullptr)
         tail_rc = launch_score_pair_tail(s, cus, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
-                                         z_dev, st->own, st->logpc, st->tail_scores, tail_ld);
+                                         z_dev, st->own, st->logpc, st->tail_scores, r.tail_ld);
       if (tail_rc == -2)
         tail_rc = launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad,
-                                    kGroupTile, row0, nrows, z_dev, st->own, st->logpc, st->tail_scores - kGroupTile, tail_ld);
-      if (tail_rc == 0) {
-        rc = launch_sweep_roles_tail(s, cus, st->tile_roles_ok ? 0 : st->tile_nich_only ? 1 : 2, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0,
-                                     z_dev, st->own, st->logpc, st->rng_dev, zero, st->tail_scores);
-        if (zeroed) *zeroed = rc == 0;
-      }
+                                    kGroupTile, row0, nrows, z_dev, st->own, st->logpc, st->tail_scores - kGroupTile, r.tail_ld);
+      if (tail_rc == 0)
+        rc = launch_sweep_roles_tail(s, cus, st->tile_path, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
+                                     row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero, st->tail_scores);
+      else generic = true;                                 // (the tail kernels declined this call's rows)
+      break;
     }
+    case SweepKind::generic: break;
   }
-  if (rc == -2) {
-    // generic shape: score a chunk of rows (leave-one-out + prior) into scratch, then sample it
+  if (generic || rc == -2) {                             // (-2: launch_sweep_niw1 / _nich1 / _mixed, launch_narrow declined)
+    // score a chunk of rows (leave-one-out + prior) into scratch, then sample it
     // (rows of K rounded up to 64 floats, not of the padded table width: at K = 300 the chunk is 320 wide, not 512 --
     // neither the score kernels nor the sampler touch a row beyond K)
     const uint64_t ld = std::min<uint64_t>(st->kpad, ((uint64_t)st->K + 63) & ~63ull);
@@ -2422,23 +2414,21 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
     uint64_t chunk = ((forced_mib ? forced_mib : 4096ull) << 20) / (ld * sizeof(float));
     if (chunk == 0) chunk = 1;
     if (chunk > nrows) chunk = nrows;
-    if (st->scratch_floats < chunk * ld) {
-      void *p = nullptr;
-      MSC_HIP(hipMalloc(&p, chunk * ld * sizeof(float)));
-      st->owned.push_back(p);
-      st->scratch = static_cast<float *>(p);
-      st->scratch_floats = chunk * ld;
-    }
-    for (uint64_t r = 0; r < nrows; r += chunk) {
-      const uint64_t n = std::min<uint64_t>(chunk, nrows - r);
-      MSC_TRY(run_score(st, row0 + r, n, z_dev + r, true, false, st->scratch, ld));
-      if (launch_sample_rows(s, cus, st->scratch, ld, st->K, n, row_id0 + r, z_dev + r, st->rng_dev))
+    MSC_TRY(grow(st, st->scratch, st->scratch_floats, chunk * ld));
+    for (uint64_t at = 0; at < nrows; at += chunk) {
+      const uint64_t n = std::min<uint64_t>(chunk, nrows - at);
+      MSC_TRY(run_score(st, row0 + at, n, z_dev + at, true, false, st->scratch, ld));
+      if (launch_sample_rows(s, cus, st->scratch, ld, st->K, n, row_id0 + at, z_dev + at, st->rng_dev))
         return fail(MSC_EHIP, "k_sample_rows launch failed");
     }
     rc = 0;
+    zeroes = false;
   }
   if (rc) return fail(MSC_EHIP, "sweep kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-  if (zeroed) return MSC_OK;
+  if (zeroed) {
+    *zeroed = zeroes;
+    return MSC_OK;
+  }
   if (launch_rng_bump(s, st->rng_dev)) return fail(MSC_EHIP, "k_rng_bump launch failed");
   st->rng_sweep = sweep + 1;
   return MSC_OK;

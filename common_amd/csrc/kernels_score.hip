@@ -1195,13 +1195,12 @@ int launch_gp_large_fix(hipStream_t stream, int num_cus, const FeatDesc *feats_d
 }
 
 // PAIR mode of the role-split kernels: one k-tile of at most 128 groups, rows enough for the role-split kernels at all
-bool pair_mode_ok(int path, uint32_t K, bool few_rows) {
-  static const bool off = std::getenv("MSC_NO_PAIR") != nullptr;     // (A/B knob)
-  return !off && (path == MSC_PATH_TILE_ROLES || path == MSC_PATH_NICH_PACK || path == MSC_PATH_LOOKUPS) && tile_roles_enabled() && K <= 128 && !few_rows;
-}
 // (the A/B switch between these kernels and the ones that run the phases one after the other is the plan's: MSC_NO_ROLES,
 // abi.cpp plan_groups)
-bool tile_roles_enabled() { return true; }
+bool pair_mode_ok(ScorePath path, uint32_t K, bool few_rows) {
+  static const bool off = std::getenv("MSC_NO_PAIR") != nullptr;     // (A/B knob)
+  return !off && (path == MSC_PATH_TILE_ROLES || path == MSC_PATH_NICH_PACK || path == MSC_PATH_LOOKUPS) && K <= 128 && !few_rows;
+}
 
 // (blocks of one row, like a memset's, lose in this kernel although they win as a bare fill: a wave that visits only a few
 // rows does not pay for loading the group constants, and with many visits the fronts are too many)
@@ -1663,7 +1662,7 @@ int launch_score_tail(hipStream_t stream, int num_cus, const TailPlan &tp, const
 }
 
 template <bool LOO, bool CRP>
-static void launch_score_t(hipStream_t stream, int num_cus, int path, const TailPlan &narrow_tail, int nich1_shape, const FeatDesc *feats_dev,
+static void launch_score_t(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, int nich1_shape, const FeatDesc *feats_dev,
                            int nfeat, int nsplit, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows,
                            const int32_t *z, const float *own, const float *crp, float *out, uint64_t ld) {
   const uint32_t ktiles = kpad / kGroupTile;
@@ -1764,7 +1763,7 @@ static void launch_score_t(hipStream_t stream, int num_cus, int path, const Tail
     else if (pair)
       hipLaunchKernelGGL((k_score_tile_roles<LOO, CRP, true>), (note_kernel(0, "k_score_tile_roles<%s, %s, true>", tf(LOO), tf(CRP)), dim3((unsigned)std::min<uint64_t>((nrows + 255) / 256, cap), 1)), dim3(1024), 0, stream,
                          feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld, 0u);
-    else if (!small4 && path == MSC_PATH_TILE_ROLES && tile_roles_enabled())
+    else if (!small4 && path == MSC_PATH_TILE_ROLES)
       hipLaunchKernelGGL((k_score_tile_roles<LOO, CRP>), (note_kernel(0, "k_score_tile_roles<%s, %s, false>", tf(LOO), tf(CRP)), grid), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0,
                          nrows, z, own, crp, out, ld, 0u);
     else if (small2)
@@ -1792,7 +1791,7 @@ int launch_score_pair_tail(hipStream_t stream, int num_cus, const FeatDesc *feat
 }
 
 // own: per-row leave-one-out values from launch_loo_own (required when z != null)
-int launch_score(hipStream_t stream, int num_cus, int path, const TailPlan &narrow_tail, int nich1_shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
+int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, int nich1_shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
                  uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z,
                  const float *own, const float *crp, float *out, uint64_t ld) {
   const bool loo = z != nullptr, pri = crp != nullptr;

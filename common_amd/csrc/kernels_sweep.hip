@@ -1869,7 +1869,13 @@ int launch_sweep_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_de
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, bool roles_ok, bool pair, bool nich_only, bool lookups_only, const FeatDesc *feats_dev, int nfeat, int nsplit,
+// one workgroup for every `rows_per_wg` rows, at least one and at most `cap`
+static dim3 rows_grid(uint64_t nrows, uint64_t rows_per_wg, uint64_t cap) {
+  return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + rows_per_wg - 1) / rows_per_wg, cap)));
+}
+
+// (path: the state's tile plan, msc_state::tile_path; has_dm overrides it)
+int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath path, bool pair, const FeatDesc *feats_dev, int nfeat, int nsplit,
                        uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z,
                        const float *own, const float *crp, const uint64_t *rng, ZeroSpans zero) {
   if (K > 256) return -2;
@@ -1878,40 +1884,36 @@ int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, bool roles_
   // (and 4 rows per wave only while the 64-row workgroups fit one round themselves)
   const bool small = !has_dm && (nrows + 63) / 64 <= (uint64_t)num_cus;
   const bool small4 = small && (nrows + 31) / 32 > (uint64_t)num_cus;      // (2 rows per wave would need a second round)
-  const uint64_t rows_per_wg = has_dm ? 64 : small4 ? 64 : small ? 32 : 128;
-  uint64_t gx = (nrows + rows_per_wg - 1) / rows_per_wg;
   const uint64_t cap = (uint64_t)num_cus * 4;
-  if (gx > cap) gx = cap;
-  const dim3 grid((unsigned)(gx ? gx : 1));
+  const dim3 grid = rows_grid(nrows, has_dm ? 64 : small4 ? 64 : small ? 32 : 128, cap);
   if (has_dm)
     hipLaunchKernelGGL((k_sweep_tile<8, 8, true>), (note_kernel(1, "k_sweep_tile<8, 8, true>"), grid), dim3(512), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows,
                        row_id0, z, own, crp, rng, zero);
-  else if (lookups_only && pair && K <= 128)
-    hipLaunchKernelGGL((k_sweep_lookups<true>), (note_kernel(1, "k_sweep_lookups<true, 0>"), dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 511) / 512, cap)))), dim3(1024), 0, stream,
+  else if (path == MSC_PATH_LOOKUPS && pair && K <= 128)
+    hipLaunchKernelGGL((k_sweep_lookups<true>), (note_kernel(1, "k_sweep_lookups<true, 0>"), rows_grid(nrows, 512, cap)), dim3(1024), 0, stream,
                        feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
-  else if (lookups_only && !small && !pair)
-    hipLaunchKernelGGL((k_sweep_lookups<false>), (note_kernel(1, "k_sweep_lookups<false, 0>"), dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 255) / 256, cap)))), dim3(1024), 0, stream,
+  else if (path == MSC_PATH_LOOKUPS && !small && !pair)
+    hipLaunchKernelGGL((k_sweep_lookups<false>), (note_kernel(1, "k_sweep_lookups<false, 0>"), rows_grid(nrows, 256, cap)), dim3(1024), 0, stream,
                        feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
-  else if (nich_only && pair && K <= 128)                 // (PAIR follows the view's rows, whatever this call's are: see below)
+  else if (path == MSC_PATH_NICH_PACK && pair && K <= 128)
   {
-    const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 32 * kNichPackWaves - 1) / (32 * kNichPackWaves), cap * (16 / kNichPackWaves))));
+    const dim3 g = rows_grid(nrows, 32 * kNichPackWaves, cap * (16 / kNichPackWaves));
     if (nsplit > 0)
       hipLaunchKernelGGL((k_sweep_nich_pack<true, true>), (note_kernel(1, "k_sweep_nich_pack<true, true, 0>"), g), dim3(kNichPackWaves * 64), 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
     else
       hipLaunchKernelGGL((k_sweep_nich_pack<true, false>), (note_kernel(1, "k_sweep_nich_pack<true, false, 0>"), g), dim3(kNichPackWaves * 64), 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
   }
-  else if (nich_only && !small && !pair)
+  else if (path == MSC_PATH_NICH_PACK && !small && !pair)
   {
-    const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 16 * kNichPackWaves - 1) / (16 * kNichPackWaves), cap * (16 / kNichPackWaves))));
+    const dim3 g = rows_grid(nrows, 16 * kNichPackWaves, cap * (16 / kNichPackWaves));
     if (nsplit > 0)
       hipLaunchKernelGGL((k_sweep_nich_pack<false, true>), (note_kernel(1, "k_sweep_nich_pack<false, true, 0>"), g), dim3(kNichPackWaves * 64), 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
     else
       hipLaunchKernelGGL((k_sweep_nich_pack<false, false>), (note_kernel(1, "k_sweep_nich_pack<false, false, 0>"), g), dim3(kNichPackWaves * 64), 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
   }
-  else if (pair && roles_ok && K <= 128)
-    // PAIR mode (abi.cpp decides on the bound view's rows, not this call's: its draw sums a row's entries two to a lane
-    // where the other tile kernels sum four, so every row range of a view must take the same one)
-    hipLaunchKernelGGL((k_sweep_tile_roles<0, true>), (note_kernel(1, "k_sweep_tile_roles<0, true>"), dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 255) / 256, cap)))), dim3(1024), 0,
+  else if (pair && path == MSC_PATH_TILE_ROLES && K <= 128)
+    // PAIR mode (its draw sums a row's entries two to a lane where the other tile kernels sum four: abi.cpp route_sweep)
+    hipLaunchKernelGGL((k_sweep_tile_roles<0, true>), (note_kernel(1, "k_sweep_tile_roles<0, true>"), rows_grid(nrows, 256, cap)), dim3(1024), 0,
                        stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, static_cast<const float *>(nullptr));
   else if (small4)
     hipLaunchKernelGGL((k_sweep_tile<4, 16, false>), (note_kernel(1, "k_sweep_tile<4, 16, false>"), grid), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows,
@@ -1919,7 +1921,7 @@ int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, bool roles_
   else if (small)
     hipLaunchKernelGGL((k_sweep_tile<2, 16, false>), (note_kernel(1, "k_sweep_tile<2, 16, false>"), grid), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows,
                        row_id0, z, own, crp, rng, zero);
-  else if (roles_ok && tile_roles_enabled())
+  else if (path == MSC_PATH_TILE_ROLES)
     hipLaunchKernelGGL(k_sweep_tile_roles<0>, (note_kernel(1, "k_sweep_tile_roles<0, false>"), grid), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows,
                        row_id0, z, own, crp, rng, zero, static_cast<const float *>(nullptr));
   else
@@ -1928,24 +1930,22 @@ int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, bool roles_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// 256 < K <= 384 (abi.cpp decides on the bound view's row count, so that a shard draws from the same bits as the whole): the role-split kernel
-// over the full tile, the tail's scores from `tail` (k_score_tail_rows wrote them)
-// (kind: 0 the role-split kernel, 1 the nich-only kernel -- with a few lookups when nsplit > 0 --, 2 the lookups-only kernel)
-int launch_sweep_roles_tail(hipStream_t stream, int num_cus, int kind, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,
+// 256 < K <= 384 (abi.cpp route_sweep): the kernel of the plan's path over the full tile -- TILE_ROLES the role-split
+// kernel, NICH_PACK the nich-only kernel (with a few lookups when nsplit > 0), LOOKUPS the lookups-only kernel --, the
+// tail's scores from `tail` (k_score_tail_rows wrote them)
+int launch_sweep_roles_tail(hipStream_t stream, int num_cus, ScorePath path, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,
                             uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z, const float *own,
                             const float *crp, const uint64_t *rng, ZeroSpans zero, const float *tail) {
-  uint64_t gx = (nrows + 127) / 128;
   const uint64_t cap = (uint64_t)num_cus * 4;
-  if (gx > cap) gx = cap;
   const bool wide = K > (uint32_t)kGroupTile + 64;
-  if (kind == 2) {
-    const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 255) / 256, cap)));
+  if (path == MSC_PATH_LOOKUPS) {
+    const dim3 g = rows_grid(nrows, 256, cap);
     if (!wide) hipLaunchKernelGGL((k_sweep_lookups<false, 1>), (note_kernel(1, "k_sweep_lookups<false, 1>"), g), dim3(1024), 0, stream, feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, tail);
     else hipLaunchKernelGGL((k_sweep_lookups<false, 2>), (note_kernel(1, "k_sweep_lookups<false, 2>"), g), dim3(1024), 0, stream, feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, tail);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  if (kind == 1) {
-    const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 16 * kNichPackWaves - 1) / (16 * kNichPackWaves), cap * (16 / kNichPackWaves))));
+  if (path == MSC_PATH_NICH_PACK) {
+    const dim3 g = rows_grid(nrows, 16 * kNichPackWaves, cap * (16 / kNichPackWaves));
     const dim3 b(kNichPackWaves * 64);
     if (nsplit > 0) {
       if (!wide) hipLaunchKernelGGL((k_sweep_nich_pack<false, true, 1>), (note_kernel(1, "k_sweep_nich_pack<false, true, 1>"), g), b, 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, tail);
@@ -1956,11 +1956,11 @@ int launch_sweep_roles_tail(hipStream_t stream, int num_cus, int kind, const Fea
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  if (K <= (uint32_t)kGroupTile + 64)
-    hipLaunchKernelGGL(k_sweep_tile_roles<1>, (note_kernel(1, "k_sweep_tile_roles<1, false>"), dim3((unsigned)(gx ? gx : 1))), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad,
+  if (!wide)
+    hipLaunchKernelGGL(k_sweep_tile_roles<1>, (note_kernel(1, "k_sweep_tile_roles<1, false>"), rows_grid(nrows, 128, cap)), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad,
                        row0, nrows, row_id0, z, own, crp, rng, zero, tail);
   else
-    hipLaunchKernelGGL(k_sweep_tile_roles<2>, (note_kernel(1, "k_sweep_tile_roles<2, false>"), dim3((unsigned)(gx ? gx : 1))), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad,
+    hipLaunchKernelGGL(k_sweep_tile_roles<2>, (note_kernel(1, "k_sweep_tile_roles<2, false>"), rows_grid(nrows, 128, cap)), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad,
                        row0, nrows, row_id0, z, own, crp, rng, zero, tail);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

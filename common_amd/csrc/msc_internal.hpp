@@ -108,6 +108,11 @@ struct PlanCost {
   double tile_round_us = 50.0, sweep_round_us = 55.0;    // (C3's, until a plan says otherwise)
   double tail_fixed_us = 30.0, tail_group_us = 1.7;
 };
+// which scoring kernel a state takes (abi.cpp decides from its feature list; a state's tile plan is one of TILE,
+// TILE_ROLES, NICH_PACK and LOOKUPS, msc_state::tile_path)
+// (TILE_ROLES: a tile state whose first phase is lookup runs only and whose second phase is not empty -- with enough
+// rows its workgroups split the phases between their waves, k_score_tile_roles)
+enum ScorePath { MSC_PATH_NICH1 = 0, MSC_PATH_TILE = 1, MSC_PATH_TILE_DM = 2, MSC_PATH_TILE_ROLES = 3, MSC_PATH_NICH_PACK = 4, MSC_PATH_LOOKUPS = 5 };
 struct NichPos {                                         // (32-bit fields: a scalar load fetches no less)
   float xlim;
   uint32_t blk_ok;
@@ -475,6 +480,8 @@ struct msc_state {
   uint32_t nfeat = 0, K = 0, kpad = 0;
   float alpha = 1.f;
   std::vector<msc_feature_host> feats;
+  bool nich1 = false, has_dm = false;   // msc_state_create (no call changes the families): a single nich feature, any dm
+  uint32_t n_niw = 0;                   // feature, how many niw features
   long long *red_i64 = nullptr;   // [cnt[kpad] | feature slices]
   double *red_f64 = nullptr;
   size_t n_i64 = 0, n_f64 = 0;
@@ -515,10 +522,11 @@ struct msc_state {
   float *tail_scores = nullptr;   // 64 floats per row: the groups beyond the first tile (k_score_tail_rows -> k_sweep_tile_roles<true>)
   size_t tail_floats = 0;
   float *own = nullptr;           // per-row leave-one-out values (k_loo_own)
-  bool tile_roles_ok = false;     // plan_groups: lookup runs only before tile_split, unmasked nich features after it
+  // plan_groups: which tile kernels the plan takes -- TILE_ROLES: lookup runs only before tile_split, unmasked nich
+  // features after it; NICH_PACK: no first phase at all (or a few lookups), two or more plain nich features
+  // (k_score_nich_pack); LOOKUPS: staged lookup features and nothing else (k_score_lookups); else TILE
+  msc::ScorePath tile_path = msc::MSC_PATH_TILE;
   msc::PlanCost plan_cost;            // plan_groups: what a round of the tile kernels / a launch of the lane <-> row kernel costs for THIS plan
-  bool tile_lookups_only = false;     // plan_groups: staged lookup features and nothing else (k_score_lookups)
-  bool tile_nich_only = false;    // plan_groups: no first phase at all, two or more plain nich features (k_score_nich_pack)
   bool tile_narrow_tail_ok = false;   // plan_groups: a partly filled last tile may take k_score_tail_rows
   uint32_t tail_max_rows = 0, tail_pack_rows = 0;   // the lookup tables of the tile plan's first phase: the largest, all together
   bool tail_masked_nich = false;      // ... and masked nich columns among them (evaluated in place, under the row's mask)
@@ -527,6 +535,7 @@ struct msc_state {
   size_t tail_pack_floats = 0;
   uint32_t loo_staged = 0;        // plan_groups: features whose leave-one-out block k_loo_own_lds stages in LDS
   float *rows_table = nullptr;    // k_sweep_nich1_rows: per-group constants as scalar operands (single nich, K > 1024)
+  size_t rows_table_floats = 0;
   size_t own_cap = 0;
   uint32_t *colmax_dev = nullptr;
   size_t scratch_floats = 0;
