@@ -93,7 +93,7 @@ static int device_error_word(int device, volatile uint32_t **host_out) {
     h[0] = h[1] = 0;
     MSC_HIP(hipHostGetDevicePointer(&d, h, 0));
     uint32_t *w = static_cast<uint32_t *>(d);
-    if (bind_error_word_score(w) || bind_error_word_sweep(w) || bind_error_word_state(w))
+    if (bind_error_word_score(w) || bind_error_word_sweep(w) || bind_error_word_state(w) || bind_error_word_seq(w))
       return fail(MSC_EHIP, "binding the device error word failed: %s", hipGetErrorString(hipGetLastError()));
     words[device] = h;
   }
@@ -113,7 +113,8 @@ static int device_error_check(msc_context *ctx) {
   if (code & 1u) add("a wave-subset barrier of a tile kernel timed out (detail: workgroup): rows of that launch are wrong");
   if (code & 2u) add("msc_entity_op: leave from a group the row is not in / an empty group, or join of an assigned row (detail: group)");
   if (code & 4u) add("msc_relation_slice_scores: a block offset beyond the score row (detail: cell)");
-  if (code & ~7u) add("unknown device-side error");
+  if (code & 8u) add("msc_sweep_sequential: an order entry >= nrows (visit skipped; detail: entry), or a leave from an empty group or counter (detail: group)");
+  if (code & ~15u) add("unknown device-side error");
   return fail(MSC_EDEVICE, "reported by an earlier kernel on device %d: %s [detail of the first: %u]; rebuild the affected state's tables",
               ctx->device, what.c_str(), detail);
 }
@@ -2581,6 +2582,95 @@ extern "C" int msc_sweep_step_stats(const msc_state *st, uint64_t *eager_steps, 
   MSC_REQUIRE(st, "null argument");
   if (eager_steps) *eager_steps = st->step_graph.n_eager;
   if (graph_steps) *graph_steps = st->step_graph.n_replayed;
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The sequential sweep (k_sweep_seq): one workgroup carries the chain; the state carries over in global memory between
+// launches, and a launch takes as many row visits as fit kSeqLaunchUs by seq_visit_us.
+// ---------------------------------------------------------------------------
+constexpr double kSeqLaunchUs = 20000.0;        // what one launch may take (estimated)
+constexpr uint64_t kSeqMaxVisitsPerLaunch = 10000;
+
+// An upper estimate of one row visit, in microseconds: a fixed part (barriers, the draw, a nich prepare) plus the table
+// entries a leave and a join rebuild and the (group, feature) scores; fitted to the visits of profiles/sequential.txt (one
+// nich column to the C3 mix, K = 16 to 1024): launches measured there at 11.9 ms on average, 26.3 ms the longest
+static double seq_visit_us(const msc_state *st) {
+  double rows = 0.0;                              // table entries prepare_group writes per (feature, group)
+  for (uint32_t f = 0; f < st->nfeat; f++) {
+    switch (st->feats[f].family) {
+      case MSC_BB: rows += 4; break;
+      case MSC_GP:
+      case MSC_BNB: rows += 2.0 * st->desc_host[f].vcap + 4; break;
+      case MSC_DD: rows += 2.0 * st->feats[f].dim + 2; break;
+      case MSC_NICH: rows += 14; break;
+      default: break;
+    }
+  }
+  return 16.0 + 0.02 * 2.0 * rows + 0.007 * (double)st->K * (double)st->nfeat;
+}
+
+// whether the sequential kernel takes a state: ok, or the status and why not
+struct SeqRoute { int rc = MSC_OK; const char *why = ""; };
+static SeqRoute route_sequential(const msc_state *st) {
+  SeqRoute r;
+  for (const auto &h : st->feats) {
+    // niw, dm: prepare kernels of their own (msc_entity_op sends them down the general path); bbnc: a slot that empties
+    // mid-sweep would be offered with a stale p (free slots' p is drawn between sweeps, mixture_state refresh_free_slots)
+    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
+      r.rc = MSC_EUNSUPPORTED;
+      r.why = "the sequential sweep takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
+      return r;
+    }
+  }
+  if (st->nfeat > (uint32_t)kSeqMaxFeat) {
+    r.rc = MSC_EUNSUPPORTED;
+    r.why = "the sequential sweep takes at most 256 features";
+  } else if (st->K > kSeqMaxGroups) {
+    r.rc = MSC_EUNSUPPORTED;
+    r.why = "the sequential sweep takes at most 8192 groups";
+  }
+  return r;
+}
+
+extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                    uint64_t nrows, uint64_t row_id0, int32_t *z_dev, const uint32_t *order_dev,
+                                    uint32_t nsweeps, uint64_t seed, uint64_t sweep, int32_t *trace_dev) {
+  MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
+  MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_sweep_sequential between msc_sweep_step_begin and msc_state_commit_reduce: the "
+                                     "additive tables hold uncommitted sums");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  const SeqRoute route = route_sequential(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  if (nrows == 0 || nsweeps == 0) return MSC_OK;
+  // every table current before (as msc_entity_op): the reference's fields, the additive sums, score constants, CRP terms
+  hipStream_t s = st->ctx->stream;
+  MSC_TRY(ensure_raw(st));
+  for (uint32_t f = 0; f < st->nfeat; f++)
+    if (!st->feats[f].additive_valid && launch_lift(s, st->desc_dev + f, 1, st->kpad, st->red_i64, st->cnt_u32, 0))
+      return fail(MSC_EHIP, "k_lift launch failed");
+  if (!st->cnt_additive_valid && launch_lift(s, st->desc_dev, 0, st->kpad, st->red_i64, st->cnt_u32, 1))
+    return fail(MSC_EHIP, "k_lift launch failed");
+  for (auto &h : st->feats) h.additive_valid = true;
+  st->cnt_additive_valid = true;
+  MSC_TRY(ensure_derived(st));
+  MSC_TRY(ensure_crp(st));
+  const uint64_t visits = (uint64_t)nsweeps * nrows;
+  const uint64_t per_launch = (uint64_t)std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / seq_visit_us(st)));
+  for (uint64_t v0 = 0; v0 < visits; v0 += per_launch) {
+    const uint64_t v1 = std::min(visits, v0 + per_launch);
+    const int rc = launch_sweep_seq(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, row_id0, z_dev, order_dev,
+                                    v0, v1, seed, sweep, st->red_i64, st->cnt_u32, st->alpha, st->logpc, trace_dev);
+    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq does not take this shape");
+    if (rc) return fail(MSC_EHIP, "k_sweep_seq launch failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  // the kernel kept every table current: additive sums, fields, constants, counts and CRP terms
+  for (auto &h : st->feats) { h.raw_valid = true; h.additive_valid = true; h.derived_valid = true; }
+  st->cnt_additive_valid = true;
+  st->crp_valid = true;
   return MSC_OK;
 }
 

@@ -14,6 +14,8 @@ enum : uint32_t {
   MSC_DEVERR_BARRIER_TIMEOUT = 1u,   // WaveSubsetBarrier gave up waiting (score_block.hpp); detail = blockIdx.x
   MSC_DEVERR_ENTITY_OP = 2u,         // k_entity_op: leave from an empty group / a group the row is not in, join of an assigned row; detail = group
   MSC_DEVERR_RELATION_RANGE = 4u,    // k_relation_slice_scores: off[c] + g * stride beyond the score row; detail = cell
+  MSC_DEVERR_SEQ_SWEEP = 8u,         // k_sweep_seq: an order entry >= nrows (visit skipped; detail = entry), a leave from an
+                                     // empty group (the row only joins) or from an empty counter of a feature (detail = group)
 };
 
 static __device__ uint32_t *g_dev_error = nullptr;

@@ -1,0 +1,324 @@
+// kernels_seq.hip -- the sequential collapsed Gibbs sweep (msc_sweep_sequential, include/microscopes_hip.h; SURVEY 3.2, the
+// reference's chain, entity_state.hpp:57-89): row i + 1 is scored against the tables row i has just changed.
+//   k_sweep_seq   ONE workgroup carries the chain.  Per row visit, phases separated by __syncthreads:
+//                   read   every thread reads the order entry, the row's old group and its count; threads f < nfeat
+//                          stage feature f's value (and whether it is masked) in LDS
+//                   leave  feature f's additive sums and fields (thread f, as k_entity_op's block f), the group count and
+//                          its CRP terms (the last thread); then prepare_group of every (feature, table slice) for that group
+//                   score  sum over the features of score_value (threads over groups, and over feature slices when K is
+//                          below the block), into LDS; then log pseudocount + the slices in a fixed order
+//                   draw   block max -> exp -> block scan of the per-thread sums (thread t owns a run of consecutive
+//                          groups) -> every thread counts its CDF steps below the dart (util::sample_discrete_log: the
+//                          draw is the number of steps below it)
+//                   join   as leave, for the drawn group; the row's slot in z is written there
+//                 Only the two groups that changed, and the empty-slot terms, have their CRP terms rewritten; the count of
+//                 empty slots lives in LDS for the launch.  The score tables are read from global memory (L2 at these
+//                 sizes).  A launch takes the visits that fit a time budget (abi.cpp seq_visit_us); the state carries over in
+//                 global memory.
+#include "commit_ops.hpp"
+#include "device_error.hpp"
+#include "family_math.hpp"
+#include "launchers.hpp"
+#include "score_block.hpp"
+
+namespace msc {
+
+MSC_DEV void seq_split(double v, float &hi, float &lo) {      // (kernels_score.hip crp_split: -inf has no lo part)
+  hi = (float)v;
+  lo = __builtin_isinf(hi) ? 0.f : (float)(v - (double)hi);
+}
+
+// feature f of one row joins (sign > 0) or leaves (sign < 0) group g: the additive sums and the reference's fields
+// (k_entity_op's feature blocks); false when a leave finds the counter it would take a unit from empty
+MSC_DEV bool seq_feature_op(const FeatDesc &fd, uint32_t v, uint32_t g, uint32_t kpad, int sign) {
+  const long long sgn = sign;
+  bool has = true;
+  if (sign < 0) switch (fd.family) {
+    case MSC_BB: has = fd.acc_i64[(v != 0 ? 0 : kpad) + g] > 0; break;
+    case MSC_GP:
+    case MSC_BNB:
+    case MSC_NICH: has = fd.acc_i64[g] > 0; break;
+    case MSC_DD: has = !((int)v >= 0 && (int)v < (int)fd.dim) || fd.acc_i64[(size_t)v * kpad + g] > 0; break;
+    default: break;
+  }
+  if (!has) return false;
+  switch (fd.family) {
+    case MSC_BB: fd.acc_i64[(v != 0 ? 0 : kpad) + g] += sgn; break;
+    case MSC_GP:
+      fd.acc_i64[g] += sgn;
+      fd.acc_i64[kpad + g] += sgn * (long long)v;
+      fd.acc_f64[g] += (double)sign * log_factorial(v);
+      break;
+    case MSC_BNB:
+      fd.acc_i64[g] += sgn;
+      fd.acc_i64[kpad + g] += sgn * (long long)v;
+      break;
+    case MSC_DD:
+      if ((int)v >= 0 && (int)v < (int)fd.dim) fd.acc_i64[(size_t)v * kpad + g] += sgn;
+      break;
+    case MSC_NICH: {
+      const double x = __uint_as_float(v);
+      fd.acc_i64[g] += sgn;
+      fd.acc_f64[g] += (double)sign * x;
+      fd.acc_f64[kpad + g] += (double)sign * x * x;
+    } break;
+    default: return true;
+  }
+  commit_group(fd, g, kpad);
+  return true;
+}
+
+// score_value of value v against group k, read from the prepared tables -- the arithmetic of the batched kernels
+// (score_block.hpp add_feature; counts beyond the exact table: k_gp_large_fix)
+MSC_DEV float seq_feature_score(const FeatDesc &fd, uint32_t v, uint32_t k, uint32_t kpad, double gp_rowc) {
+  switch (fd.family) {
+    case MSC_BB: return fd.tab[(v != 0 ? kpad : 0u) + k];
+    case MSC_DD: {
+      const int c = (int)v < 0 ? 0 : ((int)v >= (int)fd.dim ? (int)fd.dim - 1 : (int)v);
+      return fd.tab[(size_t)c * kpad + k];
+    }
+    case MSC_GP:
+      if (v < fd.vcap) return fd.tab[(size_t)(GP_T0 + v) * kpad + k];
+      return gp_eval_large((double)v, gp_rowc, (double)fd.hp[0] + (double)fd.raw_u32[(size_t)kpad + k],
+                           (double)fd.hp[1] + (double)fd.raw_u32[k],
+                           (double)fd.tab[(size_t)GP_NSE_HI * kpad + k] + (double)fd.tab[(size_t)GP_NSE_LO * kpad + k]);
+    case MSC_BNB:
+      if (v < fd.vcap) return fd.tab[(size_t)(GP_T0 + v) * kpad + k];
+      return (float)bnb_score(fd.hp, (double)fd.raw_u32[k], (double)fd.raw_u32[(size_t)kpad + k], (double)v);
+    case MSC_NICH:
+      return nich_eval(__uint_as_float(v), fd.tab[(size_t)NICH_MU_HI * kpad + k], fd.tab[(size_t)NICH_MU_LO * kpad + k],
+                       fd.tab[(size_t)NICH_C0 * kpad + k], fd.tab[(size_t)NICH_C1LN2 * kpad + k],
+                       fd.tab[(size_t)NICH_C1 * kpad + k], fd.tab[(size_t)NICH_C2 * kpad + k]);
+    default: return 0.f;     // noop (models/noop.hpp:17)
+  }
+}
+
+MSC_DEV float seq_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+MSC_DEV float seq_wave_scan(float v, int lane) {     // inclusive prefix sum over the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float u = __shfl_up(v, (unsigned)o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// shared state of the chain's workgroup
+struct SeqShared {
+  float sc[kSeqMaxGroups];        // score partials [slice][K], then every slot's score (slice 0's place)
+  uint32_t val[kSeqMaxFeat];      // the visited row's value of every feature (raw 32 bits)
+  uint8_t skip[kSeqMaxFeat];      // masked for that feature (no part in the sums or the score)
+  float wmax[kSeqThreads / 64], wsum[kSeqThreads / 64];   // per-wave max / sum of the draw
+  uint32_t nempty;                // empty slots among [0, K)
+  uint32_t below;                 // CDF steps below the dart
+};
+
+// leave (sign < 0) / join (sign > 0) of the staged row: every table of group g current afterwards
+MSC_DEV void seq_move(SeqShared &sh, const FeatDesc *__restrict__ feats, int nfeat, uint32_t K, uint32_t kpad, uint32_t g,
+                      int sign, long long *cnt_acc, uint32_t *cnt_u32, float alpha, float *crp, int32_t *zslot) {
+  const uint32_t t = threadIdx.x, nt = kSeqThreads;
+  for (uint32_t f = t; f < (uint32_t)nfeat; f += nt)
+    if (!sh.skip[f] && !seq_feature_op(feats[f], sh.val[f], g, kpad, sign)) report_device_error(MSC_DEVERR_SEQ_SWEEP, g);
+  if (t == nt - 1) {
+    const long long c = cnt_acc[g] + sign;
+    cnt_acc[g] = c;
+    cnt_u32[g] = (uint32_t)c;
+    seq_split(c ? log((double)c) : -(double)INFINITY, crp[g], crp[crp_lo_cnt(kpad) + g]);
+    seq_split(c > 1 ? log((double)c - 1.0) : -(double)INFINITY, crp[kpad + g], crp[crp_lo_cntm1(kpad) + g]);
+    uint32_t ne = sh.nempty;
+    if (sign < 0 && c == 0) ne++;
+    if (sign > 0 && c == 1) ne--;
+    sh.nempty = ne;
+    seq_split(ne > 0 ? log((double)alpha / (double)ne) : -(double)INFINITY, crp[2 * (size_t)kpad], crp[2 * (size_t)kpad + 2]);
+    seq_split(log((double)alpha / ((double)ne + 1.0)), crp[2 * (size_t)kpad + 1], crp[2 * (size_t)kpad + 3]);
+    if (zslot != nullptr) *zslot = (int32_t)g;
+  }
+  __syncthreads();                                     // (the group's fields are written; every slice prepares from them)
+  const uint32_t per = nfeat > 0 ? nt / (uint32_t)nfeat : 1u;   // slices of one (feature, group)'s table rows
+  const uint32_t S = per > 64u ? 64u : (per > 0u ? per : 1u);
+  for (uint32_t i = t; i < (uint32_t)nfeat * S; i += nt)
+    if (!sh.skip[i / S]) prepare_group(feats[i / S], g, kpad, i % S, S);     // (a masked / noop feature's group is as it was)
+  __syncthreads();
+}
+
+// MSC_SEQ_PHASES (an experiment build, Makefile VARIANT / EXTRA; tools/bench_sequential.py --phases): thread 0 stamps
+// s_memtime after the barrier that closes each phase and adds the cycles per phase -- read, leave, score (sums, prior,
+// max), draw (exp, scan, count), join -- and the visits into g_seq_phase; msc_seq_phase_cycles reads and clears it
+#ifdef MSC_SEQ_PHASES
+static __device__ unsigned long long g_seq_phase[6];
+#define SEQ_STAMP(i)                                                   \
+  do {                                                                 \
+    if (t == 0) {                                                      \
+      const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
+      ph_acc[i] += now_ - ph_last;                                     \
+      ph_last = now_;                                                  \
+    }                                                                  \
+  } while (0)
+#else
+#define SEQ_STAMP(i) do {} while (0)
+#endif
+
+// visits [v0, v1) of the call's nsweeps x nrows: visit v is sweep v / nrows, position v % nrows of the order.
+// Scoring: K >= the block, thread t sums every feature for groups t, t + 256, ...; fewer groups, the block is nq = 256 / K
+// slices of K threads and slice q sums features q, q + nq, ... (partials summed in slice order: the same bits every run)
+__global__ __launch_bounds__(kSeqThreads) void k_sweep_seq(const FeatDesc *__restrict__ feats, int nfeat, uint32_t K,
+                                                           uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
+                                                           int32_t *z, const uint32_t *__restrict__ order, uint64_t v0,
+                                                           uint64_t v1, uint64_t seed, uint64_t sweep, long long *cnt_acc,
+                                                           uint32_t *cnt_u32, float alpha, float *crp, int32_t *trace) {
+  __shared__ SeqShared sh;
+  const uint32_t t = threadIdx.x, nt = kSeqThreads, lane = t & 63u, wave = t >> 6, nw = kSeqThreads / 64;
+  if (t == 0) sh.nempty = 0;
+  __syncthreads();
+  uint32_t mine = 0;
+  for (uint32_t k = t; k < K; k += nt) mine += cnt_u32[k] == 0u;
+  atomicAdd(&sh.nempty, mine);
+  __syncthreads();
+  const float *lo0 = crp + crp_lo_cnt(kpad);
+  const uint32_t nq = K < nt ? nt / K : 1u, q = t / K, kq = t - q * K;     // (scoring slices, K < the block)
+  const uint32_t chunk = (K + nt - 1) / nt, kb = t * chunk;                  // the draw: thread t owns [kb, kb + chunk)
+#ifdef MSC_SEQ_PHASES
+  unsigned long long ph_acc[5] = {0, 0, 0, 0, 0}, ph_last = __builtin_amdgcn_s_memtime();
+#endif
+  for (uint64_t v = v0; v < v1; v++) {
+    const uint64_t s = v / nrows, pos = v - s * nrows;
+    // ---- read ----
+    const uint32_t off = order != nullptr ? order[pos] : (uint32_t)pos;
+    if (off >= nrows) {                                // (uniform: the whole block skips the visit)
+      if (t == 0) report_device_error(MSC_DEVERR_SEQ_SWEEP, off);
+    } else {
+      const uint64_t row = row0 + off;
+      const int32_t old = z[off];
+      bool leave = old >= 0 && (uint32_t)old < K;
+      if (leave && cnt_acc[old] <= 0) {               // a leave from an empty group: reported, the row only joins
+        if (t == 0) report_device_error(MSC_DEVERR_SEQ_SWEEP, (uint32_t)old);
+        leave = false;
+      }
+      for (uint32_t f = t; f < (uint32_t)nfeat; f += nt) {
+        const FeatDesc &fd = feats[f];
+        const bool skip = fd.family == MSC_NOOP || fd.col == nullptr || load_masked(fd, row, true);
+        sh.skip[f] = skip;
+        sh.val[f] = skip ? 0u : load_raw_value<false>(fd, 0, row, true);
+      }
+      __syncthreads();
+      SEQ_STAMP(0);
+      // leave (phase 0, when the row has a group), then score, draw and join (phase 1): one copy of seq_move's code
+      uint32_t g = (uint32_t)old;
+#pragma unroll 1
+      for (int ph = leave ? 0 : 1; ph < 2; ph++) {
+        if (ph == 1) {
+          SEQ_STAMP(1);
+          // ---- score: feature sums ----
+          if (nq > 1) {
+            if (q < nq) {
+              float acc = 0.f;
+              for (uint32_t f = q; f < (uint32_t)nfeat; f += nq) {
+                if (sh.skip[f]) continue;
+                const FeatDesc &fd = feats[f];
+                const uint32_t x = sh.val[f];
+                acc += seq_feature_score(fd, x, kq, kpad, fd.family == MSC_GP && x >= fd.vcap ? gp_row_const(x) : 0.0);
+              }
+              sh.sc[q * K + kq] = acc;
+            }
+          } else {
+            for (uint32_t k = t; k < K; k += nt) {
+              float acc = 0.f;
+              for (int f = 0; f < nfeat; f++) {
+                if (sh.skip[f]) continue;
+                const FeatDesc &fd = feats[f];
+                const uint32_t x = sh.val[f];
+                acc += seq_feature_score(fd, x, k, kpad, fd.family == MSC_GP && x >= fd.vcap ? gp_row_const(x) : 0.0);
+              }
+              sh.sc[k] = acc;
+            }
+          }
+          if (t == 0) sh.below = 0;
+          __syncthreads();
+          // ---- score: + log pseudocount (hi, the slices, lo), the block max ----
+          const float e_hi = crp[2 * (size_t)kpad], e_lo = crp[2 * (size_t)kpad + 2];
+          float m = -INFINITY;
+          for (uint32_t k = kb; k < kb + chunk && k < K; k++) {
+            const bool used = cnt_u32[k] != 0u;
+            float sk = used ? crp[k] : e_hi;
+            for (uint32_t j = 0; j < nq; j++) sk += sh.sc[j * K + k];
+            sk += used ? lo0[k] : e_lo;
+            sh.sc[k] = sk;
+            m = fmaxf(m, sk);
+          }
+          m = seq_wave_max(m);
+          if (lane == 0) sh.wmax[wave] = m;
+          __syncthreads();
+          SEQ_STAMP(2);
+          // ---- draw ----
+          m = sh.wmax[0];
+          for (uint32_t w = 1; w < nw; w++) m = fmaxf(m, sh.wmax[w]);
+          float part = 0.f;
+          for (uint32_t k = kb; k < kb + chunk && k < K; k++)
+            part += __builtin_amdgcn_exp2f((sh.sc[k] - m) * 1.44269504088896340736f);   // exp(-inf) = 0
+          const float incl = seq_wave_scan(part, (int)lane);
+          float c = __shfl_up(incl, 1u, 64);             // the exclusive prefix of the scan itself: the CDF never steps back
+          if (lane == 0) c = 0.f;
+          if (lane == 63) sh.wsum[wave] = incl;
+          __syncthreads();
+          float total = 0.f;
+          for (uint32_t w = 0; w < nw; w++) {
+            const float ws = sh.wsum[w];
+            if (w < wave) c += ws;
+            total += ws;
+          }
+          const float dart = philox_uniform01(seed, sweep + s, row_id0 + off) * total;
+          uint32_t cnt = 0;
+          for (uint32_t k = kb; k < kb + chunk && k < K; k++) {
+            c += __builtin_amdgcn_exp2f((sh.sc[k] - m) * 1.44269504088896340736f);
+            cnt += c < dart ? 1u : 0u;
+          }
+          if (cnt) atomicAdd(&sh.below, cnt);
+          __syncthreads();
+          SEQ_STAMP(3);
+          g = sh.below < K ? sh.below : K - 1;
+        }
+        // ---- leave / join ----
+        seq_move(sh, feats, nfeat, K, kpad, g, ph == 0 ? -1 : 1, cnt_acc, cnt_u32, alpha, crp, ph == 0 ? nullptr : z + off);
+      }
+      SEQ_STAMP(4);
+    }
+    if (trace != nullptr && pos + 1 == nrows) {          // the row range's assignment after sweep s
+      for (uint64_t i = t; i < nrows; i += nt) trace[s * nrows + i] = z[i];
+      __syncthreads();
+    }
+  }
+#ifdef MSC_SEQ_PHASES
+  if (t == 0) {
+    for (int i = 0; i < 5; i++) atomicAdd(&g_seq_phase[i], ph_acc[i]);
+    atomicAdd(&g_seq_phase[5], (unsigned long long)(v1 - v0));
+  }
+#endif
+}
+
+int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
+                     uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *order, uint64_t v0, uint64_t v1,
+                     uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32, float alpha, float *crp,
+                     int32_t *trace) {
+  if (nfeat < 0 || nfeat > kSeqMaxFeat || K == 0 || K > kSeqMaxGroups) return -2;
+  hipLaunchKernelGGL(k_sweep_seq, dim3(1), dim3(kSeqThreads), 0, stream, feats_dev, nfeat, K, kpad, row0, nrows, row_id0,
+                     z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp, trace);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+MSC_DEFINE_BIND_ERROR_WORD(bind_error_word_seq)
+
+#ifdef MSC_SEQ_PHASES
+// cycles per phase (read, leave, score, draw, join) and visits since the last call; synchronises the device
+extern "C" int msc_seq_phase_cycles(unsigned long long *out6) {
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(out6, HIP_SYMBOL(g_seq_phase), 6 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  const unsigned long long zero[6] = {0, 0, 0, 0, 0, 0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_seq_phase), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
+}
+#endif
+
+}  // namespace msc

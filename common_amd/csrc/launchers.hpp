@@ -40,6 +40,7 @@ int launch_value_op(hipStream_t stream, void *mailbox_dev, uint32_t dim, int fam
 int bind_error_word_score(uint32_t *word_dev);
 int bind_error_word_sweep(uint32_t *word_dev);
 int bind_error_word_state(uint32_t *word_dev);
+int bind_error_word_seq(uint32_t *word_dev);
 
 // kernels_score.hip
 int launch_prepare(hipStream_t stream, const FeatDesc *feats_dev, uint32_t nfeat, uint32_t kpad, uint32_t value_slices);
@@ -167,6 +168,15 @@ int launch_sample_rows(hipStream_t stream, int num_cus, const float *scores, uin
                        uint64_t nrows, uint64_t row_id0, int32_t *z, const uint64_t *rng_dev);
 int launch_rng_set(hipStream_t stream, uint64_t *rng_dev, uint64_t seed, uint64_t sweep);
 int launch_rng_bump(hipStream_t stream, uint64_t *rng_dev);
+
+// kernels_seq.hip: visits [v0, v1) of the sequential sweep (msc_sweep_sequential), one workgroup; -2: shape not covered
+constexpr int kSeqThreads = 256;           // the workgroup: one wave a SIMD, room for prepare_group and the score paths
+constexpr uint32_t kSeqMaxGroups = 8192;   // the groups' scores sit in LDS (32 KiB)
+constexpr int kSeqMaxFeat = 256;           // features whose row values the workgroup stages
+int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
+                     uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *order, uint64_t v0, uint64_t v1,
+                     uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32, float alpha, float *crp,
+                     int32_t *trace);
 
 // kernels_niw.hip
 int launch_niw_prepare(hipStream_t stream, const FeatDesc *feats_dev, uint32_t f, uint32_t dim, uint32_t K,

@@ -453,6 +453,36 @@ class State(object):
                                                   row0 if row_id0 is None else row_id0,
                                                   C.c_void_p(z.data_ptr()), int(seed), int(sweep)))
 
+    def sweep_sequential(self, view, z, seed, sweep, nsweeps=1, order=None, trace=None, row0=0, nrows=None,
+                         row_id0=None, cols=None):
+        """nsweeps sequential collapsed Gibbs sweeps over the rows, each row scored against the tables the row before it
+        left (msc_sweep_sequential).  order: uint32 (or int32) device tensor of nrows offsets from row0, the visiting
+        order of every sweep (None: ascending); trace: int32 device tensor of nsweeps x nrows, z after every sweep."""
+        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
+        n = view.nrows - row0 if nrows is None else nrows
+        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
+            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+        if not 0 <= int(nsweeps) < (1 << 32):
+            raise ValueError("nsweeps must be in [0, 2^32)")
+        dev = self.ctx.torch_device
+        op = None
+        if order is not None:
+            if order.dtype not in (torch.int32, _TORCH_OF_TYPE.get(L.TYPE_U32, torch.int32)) or not order.is_contiguous() \
+                    or order.numel() < n or order.device != z.device:
+                raise ValueError("order must be a contiguous int32 / uint32 device tensor of nrows entries")
+            op = C.c_void_p(order.data_ptr())
+        tp = None
+        if trace is not None:
+            if trace.dtype != torch.int32 or not trace.is_contiguous() or trace.numel() < int(nsweeps) * n \
+                    or trace.device != z.device:
+                raise ValueError("trace must be a contiguous int32 device tensor of nsweeps x nrows entries")
+            tp = C.c_void_p(trace.data_ptr())
+        if z.device != dev:
+            raise ValueError("z must live on the context's device")
+        L.check(self.ctx.lib.msc_sweep_sequential(self._h, view._h, self._cols(cols), row0, n,
+                                                  row0 if row_id0 is None else row_id0, C.c_void_p(z.data_ptr()), op,
+                                                  int(nsweeps), int(seed), int(sweep), tp))
+
     def sweep_step_stats(self):
         """(steps run launch by launch, steps run as one graph launch)"""
         e, g = C.c_uint64(), C.c_uint64()

@@ -274,6 +274,20 @@ public:
     stale_ = true;      // the host partition follows when somebody looks at it: sweep after sweep costs the host nothing
   }
 
+  // nsweeps SEQUENTIAL Gibbs sweeps over all entities on the device (msc_sweep_sequential): the reference's own chain --
+  // each entity leaves its group, is scored against the tables as the entity before it left them (CRP prior, every
+  // free slot an empty group on offer), re-drawn with Philox(seed, sweep + s, entity) and joins -- in one call.  Entities
+  // not yet assigned are seated.  As gibbs_sweep, the host partition follows the assignment vector lazily (sync()).
+  // A non-conjugate component throws: free slots' parameters are drawn between sweeps only (refresh_free_slots), and a
+  // slot emptied mid-sweep would be offered with a stale one; niw and dm components throw as the library refuses them.
+  void gibbs_sweep_sequential(uint64_t seed, uint64_t sweep, common::rng_t &rng, uint32_t nsweeps = 1) {
+    (void)rng;                                          // (conjugate components only: nothing to draw on the host)
+    if (any_nonconj_) throw std::runtime_error("gibbs_sweep_sequential takes conjugate components only");
+    push_params(true);
+    check(msc_sweep_sequential(st_, view_, nullptr, 0, n_, 0, z_dev_, nullptr, nsweeps, seed, sweep, nullptr));
+    stale_ = true;
+  }
+
   // Posterior predictive draws for new, partly observed rows (downstream's sample_post_pred): each row of `rows` (the
   // state's column layout, with its mask) gets a group drawn from the CRP term plus the scores of its observed entries
   // against the tables as they stand, then its masked entries are drawn from that group's posterior predictive -- ONE

@@ -335,6 +335,35 @@ int msc_sweep_step_begin(msc_state *st, const msc_dataview *view, const uint32_t
 /* how many msc_sweep_step calls on this state ran launch by launch / as a graph launch */
 int msc_sweep_step_stats(const msc_state *st, uint64_t *eager_steps, uint64_t *graph_steps);
 
+/*
+ * nsweeps SEQUENTIAL collapsed Gibbs sweeps over rows [row0, row0+nrows): the reference's sampler (the
+ * per-entity moves of entity_state.hpp:57-89), in which row i+1 is scored against the tables row i has just changed.
+ * Each sweep visits the rows in the order order_dev (nullable: uint32[nrows] offsets from row0, the same for every
+ * sweep of the call; NULL = ascending).  For each visited row:
+ *   leave  if z_dev[offset] is in [0, ngroups) the row leaves that group (every feature's remove_value, the group
+ *          count); an id outside that range is unassigned and the row only joins -- a sweep from an all-unassigned z
+ *          is sequential CRP seating;
+ *   score  every slot: log pseudocount + sum over features of score_value, against the tables as they now stand (what
+ *          msc_score_value(..., MSC_SCORE_CRP_PRIOR) gives for the row; empty slots share alpha);
+ *   draw   util::sample_discrete_log semantics with philox_uniform01(seed, sweep + s, row_id0 + offset) in sweep s of
+ *          the call: the counter msc_sweep_step uses for that row, so a one-row call draws what msc_sweep_step draws;
+ *   join   the drawn group; z_dev[offset] is written.
+ * z_dev: int32[nrows] for the row range.  trace_dev (nullable): int32[nsweeps * nrows], receives z of the row range
+ * after every sweep.  Every table is current on return (additive sums, fields, score constants, CRP terms, as after
+ * msc_entity_op): msc_score_value, msc_score_data, msc_state_get_ss, msc_sweep_step and msc_sample_predictive may
+ * follow with nothing rebuilt.  Asynchronous; does not touch msc_sweep_step's device (seed, sweep) pair or its graph.
+ * Exactness: the chain is the collapsed CRP Gibbs sampler whenever an empty slot exists at every visit, which always
+ * holds when ngroups >= the rows in play; with every slot full it is the chain truncated to ngroups groups.
+ * Families: bb, gp, bnb, dd, nich and noop (masked entries honoured); at most 256 features and 8192 groups.  States
+ * that hold niw or dm features (prepare kernels of their own), or bbnc (a slot that empties mid-sweep would be offered
+ * with a stale p; free slots' p is drawn between sweeps) return MSC_EUNSUPPORTED.  MSC_EINVAL between
+ * msc_sweep_step_begin and msc_state_commit_reduce.  An order entry >= nrows skips that visit, and a leave from an
+ * empty group only joins; both surface as MSC_EDEVICE at the next call.
+ */
+int msc_sweep_sequential(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                         uint64_t row_id0, int32_t *z_dev, const uint32_t *order_dev, uint32_t nsweeps, uint64_t seed,
+                         uint64_t sweep, int32_t *trace_dev);
+
 /* ---- multi-GPU hook ---------------------------------------------------- */
 /*
  * The additive form of every table, ready for a sum all-reduce across row
