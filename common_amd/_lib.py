@@ -24,6 +24,10 @@ ABI_VERSION = 1
 HP_CLUSTER = 0xFFFFFFFF          # msc_hp_grid_create's feature index of the CRP concentration
 PRED_MASKED_ONLY = 0x1
 PRED_GROUP_KEY = 0xD1B54A32D192ED03   # msc_sample_predictive's group draw uses key = seed ^ this
+PRIOR_FLAT, PRIOR_EXPONENTIAL, PRIOR_NORMAL, PRIOR_NONINF_BETA = range(4)   # msc_slice_coord.prior
+SLICE_KEY = 0x2545F4914F6CDD1D        # msc_hp_slice / msc_theta_slice use key = seed ^ this
+SLICE_STEP_OUT = 64                   # m: the stepping-out limit of a slice update
+SLICE_SHRINK = 256                    # rejected proposals before an update keeps its value
 
 
 class MicroscopesHipError(RuntimeError):
@@ -38,6 +42,12 @@ class RuntimeType(C.Structure):
 
 class FeatureSpec(C.Structure):
     _fields_ = [("family", C.c_int32), ("dim", C.c_uint32)]
+
+
+class SliceCoord(C.Structure):
+    """msc_slice_coord"""
+    _fields_ = [("feature", C.c_uint32), ("coord", C.c_uint32), ("width", C.c_float), ("prior", C.c_uint32),
+                ("prior_a", C.c_float), ("prior_b", C.c_float), ("partner", C.c_uint32)]
 
 
 _SIGS = {
@@ -122,6 +132,10 @@ _SIGS = {
     "msc_hp_grid_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "msc_hp_grid_gibbs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                     C.c_void_p]),
+    "msc_hp_slice": (C.c_int, [C.c_void_p, C.POINTER(SliceCoord), C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64,
+                               C.c_void_p, C.c_void_p]),
+    "msc_theta_slice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64,
+                                  C.c_void_p]),
     "msc_sample_predictive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "msc_value_op_single": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int,

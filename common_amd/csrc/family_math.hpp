@@ -140,6 +140,17 @@ MSC_DEV double bbnc_score_data(const float *hp, uint32_t heads, uint32_t tails, 
   const double lbeta = lgamma(a) + lgamma(b) - lgamma(a + b);
   return (a - 1.0) * log(p) + (b - 1.0) * log(1.0 - p) - lbeta + (double)heads * log(p) + (double)tails * log(1.0 - p);
 }
+// the same for 0 < p < 1 with ln B(alpha, beta), the part that depends on the hp alone, given: what k_theta_slice
+// evaluates many times a lane.  (bbnc_score_data keeps its own copy of the expression so that the kernels that inline
+// it compile to the code they did before this split.)
+MSC_DEV double bbnc_lbeta(const float *hp) {
+  const double a = hp[0], b = hp[1];
+  return lgamma(a) + lgamma(b) - lgamma(a + b);
+}
+MSC_DEV double bbnc_score_data_lb(const float *hp, uint32_t heads, uint32_t tails, float pf, double lbeta) {
+  const double p = pf, a = hp[0], b = hp[1];
+  return (a - 1.0) * log(p) + (b - 1.0) * log(1.0 - p) - lbeta + (double)heads * log(p) + (double)tails * log(1.0 - p);
+}
 
 // ============================ Dirichlet-Discrete ============================
 // tab rows: i in [0, dim) -> log p(v = i)
@@ -506,6 +517,23 @@ MSC_DEV double nich_score_data(const float *hp, uint32_t count, float mean, floa
   return lgamma(0.5 * p.nu) - lgamma(0.5 * nu) + 0.5 * log(kappa / p.kappa) +
          0.5 * nu * log(nu * sigmasq) - 0.5 * p.nu * log(p.nu * p.sigmasq) -
          0.5 * (double)count * kLogPi;
+}
+
+// score_data of slot j of raw tables laid out as rows of `stride` words -- the family's u32 rows (su), then its f32 rows
+// (sf): a feature's device tables (stride kpad) or a block of them staged in LDS.  h: the scalar families' hp block;
+// dd / dm read theirs (hp, dim) in place.  (kernels_hp.hip scores grids with it, kernels_slice.hip slice targets.)
+MSC_DEV double hp_eval(int family, uint32_t dim, const float *h, const float *hp, const uint32_t *su, const float *sf,
+                       uint32_t j, uint32_t stride) {
+  switch (family) {
+    case MSC_BB: return bb_score_data(h, su[j], su[stride + j]);
+    case MSC_BBNC: return bbnc_score_data(h, su[j], su[stride + j], sf[j]);
+    case MSC_GP: return gp_score_data(h, su[j], su[stride + j], (double)sf[j]);
+    case MSC_BNB: return bnb_score_data(h, su[j], su[stride + j]);
+    case MSC_NICH: return nich_score_data(h, su[j], sf[j], sf[stride + j]);
+    case MSC_DD: return dd_score_data(hp, dim, su + stride + j, stride, su[j]);
+    case MSC_DM: return dm_score_data(hp, dim, su + j, stride, (double)sf[j]);
+    default: return 0.0;
+  }
 }
 
 // ============================ typed column loads ============================

@@ -4,9 +4,9 @@
 //   k_crp_grid_score  score_assignment(alpha) of the group counts for every alpha of a grid (group_manager.hpp:207-218)
 //   k_hp_grid_draw    one wave per grid: prior + likelihood, softmax, a Philox dart, the chosen block into the device hp
 // The hp is held PER LANE (lane <-> grid point) and the groups stream past as LDS broadcasts: the per-group formulas are
-// family_math.hpp's *_score_data, the ones k_score_data evaluates with one hp per feature.  Every sum runs in a fixed
-// order (slots in index order inside a block, blocks in order, lanes' chunks in lane order): no atomics, so two calls on
-// the same tables give the same bits, and so do the ranks of a sharded sweep.
+// family_math.hpp's *_score_data (through its hp_eval), the ones k_score_data evaluates with one hp per feature.  Every
+// sum runs in a fixed order (slots in index order inside a block, blocks in order, lanes' chunks in lane order): no
+// atomics, so two calls on the same tables give the same bits, and so do the ranks of a sharded sweep.
 #include "family_math.hpp"
 #include "launchers.hpp"
 #include "score_block.hpp"
@@ -16,21 +16,6 @@ namespace msc {
 constexpr int kHpPoints = 256;                     // grid points of a workgroup, one per lane
 constexpr int kHpSlots = 64;                       // group slots staged in LDS at a time
 constexpr int kHpRows = 1 + (int)kMaxDDDim;        // raw table rows a family has at most (dd: count_sum + 128 counts)
-
-// score_data of slot j of the staged block (rows of kHpSlots words: the family's u32 rows, then its f32 rows)
-MSC_DEV double hp_eval(int family, uint32_t dim, const float *h, const float *hp, const uint32_t *su, const float *sf,
-                       uint32_t j) {
-  switch (family) {
-    case MSC_BB: return bb_score_data(h, su[j], su[kHpSlots + j]);
-    case MSC_BBNC: return bbnc_score_data(h, su[j], su[kHpSlots + j], sf[j]);
-    case MSC_GP: return gp_score_data(h, su[j], su[kHpSlots + j], (double)sf[j]);
-    case MSC_BNB: return bnb_score_data(h, su[j], su[kHpSlots + j]);
-    case MSC_NICH: return nich_score_data(h, su[j], sf[j], sf[kHpSlots + j]);
-    case MSC_DD: return dd_score_data(hp, dim, su + kHpSlots + j, kHpSlots, su[j]);
-    case MSC_DM: return dm_score_data(hp, dim, su + j, kHpSlots, (double)sf[j]);
-    default: return 0.0;
-  }
-}
 
 // grid (point blocks, group blocks, grids).  Group block y covers slots [y * per_blk, (y + 1) * per_blk) of [0, K); a slot
 // counts when slots[k] != 0 (a caller's mask) or, without a mask, when its group count is not zero; no other slot is read.
@@ -73,7 +58,7 @@ __global__ __launch_bounds__(kHpPoints) void k_hp_grid_score(const HpJob *__rest
                                          : __float_as_uint(J.raw_f32[(size_t)(r - J.nu32) * kpad + k]);
     }
     __syncthreads();
-    for (uint32_t j = 0; j < n; j++) acc += hp_eval(family, J.dim, h, hp, su, sf, j);
+    for (uint32_t j = 0; j < n; j++) acc += hp_eval(family, J.dim, h, hp, su, sf, j, kHpSlots);
   }
   if (live) part[J.part_off + (size_t)blockIdx.y * G + p] = acc;
 }

@@ -229,6 +229,15 @@ int launch_crp_grid_score(hipStream_t stream, const HpJob *job_dev, uint32_t npo
                           double *out);
 int launch_hp_grid_draw(hipStream_t stream, const HpJob *jobs_dev, uint32_t njobs, const double *scores, uint64_t seed,
                         uint64_t sweep, uint32_t *chosen);
+// kernels_slice.hip (msc_hp_slice / msc_theta_slice): one workgroup per target; the theta kernel writes per (job, block of
+// 256 slots) the evaluations and the first slot left unchanged for a non-finite target (theta_slice_blocks(K) blocks a job)
+int launch_hp_slice(hipStream_t stream, const SliceTarget *targets_dev, uint32_t ntargets, const SliceCoord *coords_dev,
+                    uint32_t K, uint32_t kpad, const uint32_t *cnt, const uint8_t *slots, uint64_t key, uint64_t sweep,
+                    float *values, uint32_t *evals, uint32_t *status);
+inline uint32_t theta_slice_blocks(uint32_t K) { return (K + 255) / 256; }
+int launch_theta_slice(hipStream_t stream, const ThetaJob *jobs_dev, uint32_t njobs, uint32_t K, uint32_t kpad,
+                       const uint32_t *cnt, const uint8_t *slots, uint64_t key, uint64_t sweep,
+                       unsigned long long *evals_part, uint32_t *bad_part);
 int launch_unpack(hipStream_t stream, const uint8_t *records, const uint8_t *mask, uint64_t nrows,
                   uint32_t rowsize, uint32_t maskrowsize, const void *feats_dev, uint32_t nfeat);
 

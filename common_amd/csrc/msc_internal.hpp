@@ -232,6 +232,35 @@ struct HpJob {
   uint64_t stream;           // draw: Philox counter (msc_hp_grid_gibbs)
 };
 
+// msc_hp_slice as k_hp_slice reads it (kernels_slice.hip): one target a workgroup -- a feature's chain of coordinates,
+// entries [first, first + n) of the call's SliceCoord array in the caller's order, or the CRP concentration (family
+// kHpCluster, one entry).  Per entry the kernel writes the installed value, the evaluations it took and a status
+// (kSliceOk / kSliceNonFinite / kSliceStalled) at the entry's index; a feature's final block goes into hp.
+constexpr uint32_t kSliceOk = 0, kSliceNonFinite = 1, kSliceStalled = 2;
+struct SliceTarget {
+  int32_t family;            // or kHpCluster
+  uint32_t hpf;              // floats of the hp block (<= 4 for the families sliced)
+  uint32_t nu32, nf32;       // raw table rows of the family
+  const uint32_t *raw_u32;   // the feature's raw tables, rows of kpad
+  const float *raw_f32;
+  float *hp;                 // the feature's device hp block (null: alpha)
+  float alpha;               // kHpCluster: alpha at the call
+  uint32_t target;           // Philox counter word 0: the feature, or nfeatures for alpha
+  uint32_t first, n;
+};
+struct SliceCoord {
+  uint32_t coord, prior, partner;   // msc_slice_coord, as validated by msc_hp_slice
+  float width, prior_a, prior_b;
+};
+// msc_theta_slice: one bbnc feature of the call (a row of workgroups, one lane a slot)
+struct ThetaJob {
+  const uint32_t *raw_u32;   // heads, tails
+  float *raw_f32;            // p
+  const float *hp;           // the feature's device hp {alpha, beta}
+  float width;
+  uint32_t feature;
+};
+
 // One drawn feature of msc_sample_predictive as the kernels of kernels_pred.hip read it: where its hp and raw tables are,
 // the predictive parameters k_pred_prepare writes (par: [K][stride] doubles, pred_par_stride), and the columns a draw
 // reads (the bound view's column in the model's value type, its mask) and writes (out: nrows x count values).
@@ -573,6 +602,10 @@ struct msc_state {
   uint32_t *hp_chosen_dev = nullptr;
   size_t hp_jobs_cap = 0, hp_chosen_cap = 0;
   std::vector<msc::HpJob> hp_jobs_host;
+  // slice sampling (abi.cpp msc_hp_slice / msc_theta_slice): the call's targets and entries, then its outputs; grown on
+  // demand
+  unsigned char *slice_buf = nullptr;
+  size_t slice_cap = 0;
   // posterior predictive sampling (abi.cpp msc_sample_predictive): the drawn features' descriptors and parameters, and
   // the scratch assignment of a group draw, grown on demand
   msc::PredFeat *pred_feats_dev = nullptr;

@@ -10,6 +10,14 @@ synchronisation per step whatever the number of features); this module holds the
                                                    ("alpha", "beta") is called with the values in the tuple's order
   FeatureHpGibbs(state, descs, ...)               the grids of a state's features built once, .step(seed, sweep)
 
+and the slice sampler, downstream's `hp` kernel (State.hp_slice, msc_hp_slice: every coordinate's whole update loop in
+one kernel, one host synchronisation per step):
+
+  slice_prior(fn)                                 a scalar_functions prior -> (L.PRIOR_*, a, b)
+  slice_coords(desc, feature, hparams)            one feature's msc_slice_coord entries: {key or tuple of keys: (prior,
+                                                   width)}, default desc.default_hyperpriors() with width 1.0
+  FeatureHpSlice(state, descs, hparams, cparam)   the entries of a state's features (and alpha), .step(seed, sweep)
+
 A sharded sweep (common_amd.dist.ShardedSweep) calls .step after commit_reduce: every rank holds the same tables and
 draws with the same seed, so every rank installs the same points without exchanging anything.
 """
@@ -17,6 +25,7 @@ import numpy as np
 
 from . import _lib as L
 from .runtime import pack_hp
+from .scalar_functions import _log_noninformative_beta_prior, log_exponential, log_normal
 
 _FIELDS = {L.BB: ("alpha", "beta"), L.BBNC: ("alpha", "beta"), L.GP: ("alpha", "inv_beta"),
            L.BNB: ("alpha", "beta", "r"), L.NICH: ("mu", "kappa", "sigmasq", "nu")}
@@ -124,3 +133,92 @@ class FeatureHpGibbs(object):
         for g in self._grids:
             g.close()
         self._grids = []
+
+
+def slice_prior(fn):
+    """a prior of common_amd.scalar_functions -> (L.PRIOR_*, a, b) as msc_slice_coord carries it; None is flat"""
+    if fn is None:
+        return L.PRIOR_FLAT, 0.0, 0.0
+    if isinstance(fn, log_exponential):
+        return L.PRIOR_EXPONENTIAL, fn._lam, 0.0
+    if isinstance(fn, log_normal):
+        return L.PRIOR_NORMAL, fn._mu, fn._sigma2
+    if isinstance(fn, _log_noninformative_beta_prior):
+        return L.PRIOR_NONINF_BETA, 0.0, 0.0
+    raise TypeError("a slice-sampled prior is one of common_amd.scalar_functions' log_exponential, log_normal or "
+                    "log_noninformative_beta_prior, not %r" % (fn,))
+
+
+def slice_coords(desc, feature, hparams=None):
+    """the msc_slice_coord entries (State.hp_slice dicts) of state feature `feature` under `hparams` = {key or tuple of
+    keys: (prior, width)} (default: desc.default_hyperpriors(), width 1.0).  A tuple key takes the noninformative beta
+    prior and becomes one entry per key, each against the joint prior with the other as partner, in the tuple's order."""
+    if hparams is None:
+        hparams = {k: (fn, 1.0) for k, fn in desc.default_hyperpriors().items()}
+    if not hparams:
+        return []
+    fields = _FIELDS.get(desc.family)
+    if fields is None:
+        raise L.MicroscopesHipError(-4, "feature %d: the %s hyper-parameters are not slice-sampled" % (feature, desc.name()))
+    out = []
+    for key, (fn, w) in hparams.items():
+        kind, a, b = slice_prior(fn)
+        keys = key if isinstance(key, tuple) else (key,)
+        if (kind == L.PRIOR_NONINF_BETA) != (len(keys) == 2) or len(keys) > 2:
+            raise ValueError("feature %d: %r: the noninformative beta prior takes a pair of keys, every other prior one"
+                             % (feature, key))
+        for i, k in enumerate(keys):
+            if k not in fields:
+                raise ValueError("feature %d: %s has no hyper-parameter %r" % (feature, desc.name, k))
+            out.append({"feature": feature, "coord": fields.index(k), "width": float(w), "prior": kind, "a": a, "b": b,
+                        "partner": fields.index(keys[1 - i]) if len(keys) == 2 else 0})
+    return out
+
+
+class FeatureHpSlice(object):
+    """Slice steps over the hyper-parameters of a state's features (and, optionally, alpha): downstream's `hp` kernel.
+
+    hparams: None, or per feature (a list, or a dict keyed by feature) {key or tuple of keys: (prior, width)}, the
+    priors being common_amd.scalar_functions objects; a feature hparams does not name takes the descriptor's
+    default_hyperpriors() with width 1.0, and a feature with no prior (dd, dm, niw by default) is skipped.
+    cparam: None or {"alpha": (prior, width)}."""
+
+    def __init__(self, state, descs, hparams=None, cparam=None):
+        if len(descs) != len(state.features):
+            raise ValueError("one model descriptor per state feature expected")
+        self.state, self.descs = state, list(descs)
+        self.coords, self.features = [], []
+        for f, desc in enumerate(descs):
+            hp = None
+            if hparams is not None:
+                hp = hparams.get(f) if isinstance(hparams, dict) else hparams[f]
+            cs = slice_coords(desc, f, hp)
+            if not cs:
+                continue
+            if (desc.family, desc.dim) != tuple(state.features[f]):
+                raise ValueError("feature %d: descriptor does not match the state's feature" % f)
+            self.coords += cs
+            self.features.append(f)
+        self.has_alpha = False
+        if cparam is not None:
+            if set(cparam) != {"alpha"}:
+                raise ValueError("cparam takes one key, 'alpha'")
+            fn, w = cparam["alpha"]
+            kind, a, b = slice_prior(fn)
+            if kind == L.PRIOR_NONINF_BETA:
+                raise ValueError("alpha has no partner for the noninformative beta prior")
+            self.coords.append({"feature": "alpha", "coord": 0, "width": float(w), "prior": kind, "a": a, "b": b,
+                                "partner": 0})
+            self.has_alpha = True
+        self.last_evals = None
+
+    def step(self, seed, sweep, slots=None):
+        """one slice step of every coordinate -> {feature: the feature's hp dict now, "alpha": alpha now (if sliced)};
+        the evaluations each update took are in .last_evals"""
+        if not self.coords:
+            return {}
+        values, self.last_evals = self.state.hp_slice(self.coords, seed, sweep, slots=slots)
+        out = {f: unpack_hp(self.descs[f].family, self.state.get_hp(f), self.descs[f].dim) for f in self.features}
+        if self.has_alpha:
+            out["alpha"] = float(values[-1])
+        return out

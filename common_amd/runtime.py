@@ -545,6 +545,45 @@ class State(object):
                                                chosen.ctypes.data_as(C.c_void_p), sp))
         return (chosen, scores) if want_scores else chosen
 
+    # slice sampling (msc_hp_slice / msc_theta_slice; common_amd/hypers.py builds the coordinates upstream's way) -------
+    _PRIORS = {"flat": L.PRIOR_FLAT, "exponential": L.PRIOR_EXPONENTIAL, "normal": L.PRIOR_NORMAL,
+               "noninf_beta": L.PRIOR_NONINF_BETA}
+
+    def hp_slice(self, coords, seed, sweep, slots=None):
+        """one slice step of each entry of `coords` (msc_hp_slice; one host synchronisation).  An entry is a dict with
+        "feature" (a state feature, or "alpha" / L.HP_CLUSTER), "coord" (float index in the hp block; 0 for alpha),
+        "width", and optionally "prior" ("flat", "exponential", "normal", "noninf_beta" or an L.PRIOR_* value), "a"
+        (lambda | mu), "b" (sigma2) and "partner" (noninf_beta).  slots: uint8 device mask of the counted groups (default:
+        the non-empty ones).  -> (installed values float32, evaluations uint32), one per entry"""
+        coords = list(coords)
+        arr = (L.SliceCoord * max(1, len(coords)))()
+        for i, c in enumerate(coords):
+            f = c["feature"]
+            prior = c.get("prior", L.PRIOR_FLAT)
+            arr[i] = L.SliceCoord(L.HP_CLUSTER if f in ("alpha", L.HP_CLUSTER) else int(f), int(c.get("coord", 0)),
+                                  float(c["width"]), self._PRIORS.get(prior, prior) if isinstance(prior, str) else
+                                  int(prior), float(c.get("a", 0.0)), float(c.get("b", 0.0)), int(c.get("partner", 0)))
+        values = np.zeros(len(coords), dtype=np.float32)
+        evals = np.zeros(len(coords), dtype=np.uint32)
+        L.check(self.ctx.lib.msc_hp_slice(self._h, arr, len(coords), _slots_ptr(slots, self.K), int(seed), int(sweep),
+                                          values.ctypes.data_as(C.c_void_p), evals.ctypes.data_as(C.c_void_p)))
+        return values, evals
+
+    def theta_slice(self, tparams, seed, sweep, slots=None):
+        """one slice step of the p of every counted slot of the bbnc features in `tparams` = {feature: {"p": width}}, as
+        downstream's theta kernel takes it (msc_theta_slice; one host synchronisation).  -> {feature: evaluations}"""
+        feats = [int(f) for f in tparams]
+        for f in feats:
+            if set(tparams[f]) != {"p"}:
+                raise ValueError("feature %d: a bbnc group has one parameter, 'p'" % f)
+        fs = np.array(feats, dtype=np.uint32)
+        ws = np.array([tparams[f]["p"] for f in feats], dtype=np.float32)
+        evals = np.zeros(len(feats), dtype=np.uint64)
+        L.check(self.ctx.lib.msc_theta_slice(self._h, fs.ctypes.data_as(C.c_void_p), ws.ctypes.data_as(C.c_void_p),
+                                             len(feats), _slots_ptr(slots, self.K), int(seed), int(sweep),
+                                             evals.ctypes.data_as(C.c_void_p)))
+        return {f: int(e) for f, e in zip(feats, evals)}
+
     # posterior predictive sampling -------------------------------------------
     _PRED_DTYPES = {L.BB: torch.uint8, L.BBNC: torch.uint8, L.GP: torch.uint32, L.BNB: torch.uint32, L.DD: torch.int32,
                     L.NICH: torch.float32, L.NIW: torch.float32}

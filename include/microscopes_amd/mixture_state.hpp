@@ -254,6 +254,48 @@ public:
     return k;
   }
 
+  // Slice sampling (msc_hp_slice / msc_theta_slice): downstream's hp and theta kernels, one device call each.  The targets
+  // count every group the partition holds, empty ones included, as the grid steps do.
+  // one slice step of each of component c's coordinates, in order (`coords`: msc_slice_coord entries, their feature
+  // field ignored); the component's hypers object follows.  Returns the values installed, one per entry.
+  std::vector<float> slice_component_hp(size_t c, std::vector<msc_slice_coord> coords, uint64_t seed, uint64_t sweep) {
+    sync();
+    if (c >= hypers_.size()) throw std::runtime_error("invalid component");
+    if (coords.empty()) return {};
+    push_params();
+    for (auto &e : coords) e.feature = uint32_t(c);
+    std::vector<float> values(coords.size());
+    partition_slots slots(*this);
+    check(msc_hp_slice(st_, coords.data(), uint32_t(coords.size()), slots.p, seed, sweep, values.data(), nullptr));
+    std::vector<float> blk(hp_pushed_[c].size());
+    check(msc_state_get_hp(st_, uint32_t(c), blk.data(), blk.size()));
+    install_component_hp(c, blk);
+    return values;
+  }
+  // the same for the CRP concentration: prior MSC_PRIOR_* with parameters (a, b), width w; gm_'s alpha follows
+  float slice_cluster_hp(uint32_t prior, float a, float b, float w, uint64_t seed, uint64_t sweep) {
+    sync();
+    push_params(true);
+    msc_slice_coord e{MSC_HP_CLUSTER, 0, w, prior, a, b, 0};
+    float alpha = 0.f;
+    check(msc_hp_slice(st_, &e, 1, nullptr, seed, sweep, &alpha, nullptr));
+    gm_.get_hp_mutator("alpha").set<float>(alpha);
+    alpha_pushed_ = alpha;                               // (the device took it in the same call)
+    return alpha;
+  }
+  // one slice step of the p of every group of bbnc component c (width w); get_suffstats shows the new p.  Returns
+  // the evaluations the step took.
+  uint64_t slice_theta(size_t c, float w, uint64_t seed, uint64_t sweep) {
+    sync();
+    if (c >= hypers_.size()) throw std::runtime_error("invalid component");
+    push_params();
+    partition_slots slots(*this);
+    const uint32_t f = uint32_t(c);
+    uint64_t evals = 0;
+    check(msc_theta_slice(st_, &f, &w, 1, slots.p, seed, sweep, &evals));
+    return evals;
+  }
+
   // One synchronous Gibbs sweep over all entities on the device: every entity is scored leave-one-out against the
   // tables as they stand, with the CRP prior (every free slot is an empty group on offer and they share alpha,
   // which is the prior of "a new group" however many empty groups the host has created), re-drawn with the
@@ -433,28 +475,35 @@ private:
   }
   mutable bool stale_ = false;
 
+  // the device mask of the slots the partition holds (its groups, empty ones included)
+  struct partition_slots {
+    msc_context *ctx;
+    uint8_t *p = nullptr;
+    explicit partition_slots(mixture_state &s) : ctx(s.ctx_) {
+      std::vector<uint8_t> mask(s.kmax_, 0);
+      for (auto it = s.gm_.begin(); it != s.gm_.end(); ++it) mask[it->second.data_] = 1;
+      check(msc_device_alloc(ctx, mask.size(), reinterpret_cast<void **>(&p)));
+      check(msc_device_upload(ctx, p, mask.data(), mask.size()));
+    }
+    ~partition_slots() { msc_device_free(ctx, p); }
+    partition_slots(const partition_slots &) = delete;
+    partition_slots &operator=(const partition_slots &) = delete;
+  };
   // a grid of one call and the device mask of the slots the partition holds
   struct hp_grid {
-    msc_context *ctx;
     msc_hp_grid *h = nullptr;
-    uint8_t *slots = nullptr;
+    partition_slots mask;
+    uint8_t *slots;
     uint32_t npoints;
     hp_grid(mixture_state &s, uint32_t feature, const std::vector<float> &blocks, const std::vector<double> &logprior)
-        : ctx(s.ctx_) {
+        : mask(s), slots(mask.p) {
       const size_t nf = feature == MSC_HP_CLUSTER ? 1 : s.hp_pushed_.at(feature).size();
       if (!nf || blocks.empty() || blocks.size() % nf) throw std::runtime_error("grid blocks do not match the hp size");
       npoints = uint32_t(blocks.size() / nf);
       if (!logprior.empty() && logprior.size() != npoints) throw std::runtime_error("one log-prior value per point expected");
       check(msc_hp_grid_create(s.st_, feature, blocks.data(), nf, npoints, logprior.empty() ? nullptr : logprior.data(), &h));
-      std::vector<uint8_t> mask(s.kmax_, 0);
-      for (auto it = s.gm_.begin(); it != s.gm_.end(); ++it) mask[it->second.data_] = 1;
-      check(msc_device_alloc(ctx, mask.size(), reinterpret_cast<void **>(&slots)));
-      check(msc_device_upload(ctx, slots, mask.data(), mask.size()));
     }
-    ~hp_grid() {
-      msc_hp_grid_destroy(h);
-      msc_device_free(ctx, slots);
-    }
+    ~hp_grid() { msc_hp_grid_destroy(h); }
   };
   // the chosen block into the component's hypers object (its mutators), and what the device now holds
   void install_component_hp(size_t c, const std::vector<float> &blk) {
@@ -473,7 +522,7 @@ private:
         auto m = hypers_[c]->get_hp_mutator("alphas");
         for (size_t i = 0; i < blk.size(); i++) m.set<float>(blk[i], i);
       } break;
-      default: throw std::runtime_error("component has no hyper-parameter grid");
+      default: throw std::runtime_error("component has no hyper-parameter grid or slice");
     }
     if (keys)
       for (size_t i = 0; i < blk.size(); i++) hypers_[c]->get_hp_mutator(keys[i]).set<float>(blk[i]);

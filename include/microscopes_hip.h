@@ -451,6 +451,75 @@ int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, double *out_d
 int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint32_t n, const uint8_t *slots_dev, uint64_t seed,
                       uint64_t sweep, uint32_t *chosen_host, double *const *scores_dev);
 
+/* ---- slice sampling of hyper-parameters and bbnc group parameters (downstream's hp / theta kernels) ---- */
+/*
+ * Two kinds of target, each updated by one slice step:
+ *   hyper-parameter coordinate: one float of a feature's hp block (msc_state_set_hp layout), or the CRP alpha
+ *     (feature MSC_HP_CLUSTER, coord 0).  Target of a feature coordinate:
+ *       g(x) = sum over the counted slots k of score_data(hp with coordinate := x, group k) + prior(x)
+ *     the sum msc_hp_grid_score computes (in double, in a fixed order; counted: a non-zero group count, or with slots_dev
+ *     a non-zero byte; no other slot is read).  Target of alpha: score_assignment(alpha) of the device counts + prior.
+ *   group parameter: the p of a counted bbnc slot, target bbnc_score_data(hp, heads, tails, p) -- the Beta(alpha, beta)
+ *     prior plus the likelihood, so the stationary law of p is Beta(alpha + heads, beta + tails).
+ * Supports (a target is -inf outside and never evaluated there): bb / bbnc / bnb alpha, beta > 0; gp alpha, inv_beta > 0;
+ * nich mu any finite value, kappa, sigmasq, nu > 0; alpha > 0; bbnc p in (0, 1).  MSC_EUNSUPPORTED: bnb r (an integer),
+ * dd / dm alphas, niw (and noop).
+ * Priors, in double on the device: FLAT 0; EXPONENTIAL(lambda = prior_a) log lambda - lambda x (-inf for x < 0);
+ * NORMAL(mu = prior_a, sigma2 = prior_b) -0.5 log(2 pi sigma2) - 0.5 (x - mu)^2 / sigma2; NONINF_BETA -2.5 log(x + y)
+ * with y the feature's coordinate `partner` at its current value -- downstream's tuple key ('alpha', 'beta') is two
+ * entries, each against the joint prior with the other as partner.
+ * The step (Neal 2003, "Slice sampling", Fig. 3 stepping out with m = 64, Fig. 5 shrinkage), x0 the current value, w the
+ * width, u_b the uniforms below; the interval is kept in double and every point the target is evaluated at is first
+ * rounded to float32:
+ *   y = g(x0) + log u_0;  L = x0 - w u_1, R = L + w;  J = floor(m u_2), Kr = m - 1 - J
+ *   while J > 0 and y < g(L): L -= w, J--;   while Kr > 0 and y < g(R): R += w, Kr--
+ *   proposal j = 0, 1, ...: x1 = float(L + u_{3+j} (R - L)); accept if y < g(x1), else L = x1 if x1 < x0, R = x1 if not
+ *   after 256 rejected proposals x0 is kept (the update "stalls": floating point has collapsed the interval)
+ * The accepted float is installed.  The entries of one feature are updated one after another in the caller's order,
+ * each against the values installed before it; different features, alpha and different bbnc slots are independent.
+ * When g(x0) is not finite (e.g. the current value lies outside the prior's support) that entry (bbnc: that slot) keeps
+ * its value, every other target is still installed, and the call returns MSC_EINVAL naming it.
+ * Random numbers: Philox4x32-10, key = seed ^ 0x2545F4914F6CDD1D (a key no sweep, grid draw or predictive uses);
+ *   hyper-parameter entry: counter (target, entry, sweep & 0xffffffff, b), target = the feature or nfeatures for alpha,
+ *     entry = the entry's position among that target's entries in the call;
+ *   bbnc slot: counter (slot, 0x80000000 | feature, sweep & 0xffffffff, b);
+ *   u_b from block b, words a = w0, b = w1: ((a >> 5) 2^26 + (b >> 6) + 0.5) 2^-53, in (0, 1).
+ * Every sum runs in a fixed order with no atomics on values: the same tables and seed give the same bits, so every rank of
+ * a sharded sweep installs the same values after msc_state_commit_reduce without exchanging anything.  Both calls are
+ * synchronous with ONE host synchronisation, and return MSC_EINVAL between msc_sweep_step_begin and
+ * msc_state_commit_reduce.
+ */
+#define MSC_PRIOR_FLAT 0u
+#define MSC_PRIOR_EXPONENTIAL 1u
+#define MSC_PRIOR_NORMAL 2u
+#define MSC_PRIOR_NONINF_BETA 3u
+typedef struct {
+  uint32_t feature;  /* state feature, or MSC_HP_CLUSTER */
+  uint32_t coord;    /* float index in the feature's hp block; 0 for alpha */
+  float width;       /* w > 0 */
+  uint32_t prior;    /* MSC_PRIOR_* */
+  float prior_a;     /* EXPONENTIAL: lambda > 0; NORMAL: mu */
+  float prior_b;     /* NORMAL: sigma2 > 0 */
+  uint32_t partner;  /* NONINF_BETA: the other coordinate of the feature */
+} msc_slice_coord;
+/*
+ * One slice step of each of the n entries.  values_host[i] (nullable) = the value installed by entry i, evals_host[i]
+ * (nullable) = the evaluations of the target its update took (the one at x0 included; none outside the support).  The
+ * device hp, the host copy msc_state_get_hp reads, the score tables' staleness and alpha are left exactly as
+ * msc_state_set_hp / msc_state_set_alpha would leave them.  MSC_EINVAL (nothing installed) for a width that is not a
+ * positive finite float, a coordinate or partner outside the block, an unknown prior or a non-positive lambda / sigma2.
+ */
+int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev, uint64_t seed,
+                 uint64_t sweep, float *values_host, uint32_t *evals_host);
+/*
+ * One slice step of the p of every counted slot of each of the n bbnc features (features[i], widths[i] > 0): p is written
+ * into the slot's table and the feature's score tables go stale as after msc_state_set_ss (the next scoring call
+ * rebuilds them); slots that are not counted are not touched.  evals_host[i] (nullable) = the evaluations over all of
+ * feature i's slots.  MSC_EINVAL (nothing installed) for a feature that is not bbnc, twice in the call, or a bad width.
+ */
+int msc_theta_slice(msc_state *st, const uint32_t *features, const float *widths, uint32_t n, const uint8_t *slots_dev,
+                    uint64_t seed, uint64_t sweep, uint64_t *evals_host);
+
 /* ---- posterior predictive sampling (group::sample_value, base.hpp:29) ---- */
 #define MSC_PRED_MASKED_ONLY 0x1u /* draw masked entries only; observed ones are copied */
 /*
