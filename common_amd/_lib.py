@@ -28,6 +28,8 @@ PRIOR_FLAT, PRIOR_EXPONENTIAL, PRIOR_NORMAL, PRIOR_NONINF_BETA = range(4)   # ms
 SLICE_KEY = 0x2545F4914F6CDD1D        # msc_hp_slice / msc_theta_slice use key = seed ^ this
 SLICE_STEP_OUT = 64                   # m: the stepping-out limit of a slice update
 SLICE_SHRINK = 256                    # rejected proposals before an update keeps its value
+ZMATRIX_MAX_ROWS = 1 << 18            # msc_zmatrix_create: m at most
+ZMATRIX_MAX_LABELS = 1 << 16          # ... and nlabels at most
 
 
 class MicroscopesHipError(RuntimeError):
@@ -144,6 +146,13 @@ _SIGS = {
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64]),
     "msc_relation_blocks": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint64, C.c_void_p]),
+    "msc_zmatrix_create": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "msc_zmatrix_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64]),
+    "msc_zmatrix_nsamples": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "msc_zmatrix_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "msc_zmatrix_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "msc_zmatrix_reset": (C.c_int, [C.c_void_p]),
+    "msc_zmatrix_destroy": (C.c_int, [C.c_void_p]),
 }
 
 EXPORTS = tuple(sorted(_SIGS))

@@ -93,7 +93,8 @@ static int device_error_word(int device, volatile uint32_t **host_out) {
     h[0] = h[1] = 0;
     MSC_HIP(hipHostGetDevicePointer(&d, h, 0));
     uint32_t *w = static_cast<uint32_t *>(d);
-    if (bind_error_word_score(w) || bind_error_word_sweep(w) || bind_error_word_state(w) || bind_error_word_seq(w))
+    if (bind_error_word_score(w) || bind_error_word_sweep(w) || bind_error_word_state(w) || bind_error_word_seq(w) ||
+        bind_error_word_query(w))
       return fail(MSC_EHIP, "binding the device error word failed: %s", hipGetErrorString(hipGetLastError()));
     words[device] = h;
   }
@@ -114,7 +115,8 @@ static int device_error_check(msc_context *ctx) {
   if (code & 2u) add("msc_entity_op: leave from a group the row is not in / an empty group, or join of an assigned row (detail: group)");
   if (code & 4u) add("msc_relation_slice_scores: a block offset beyond the score row (detail: cell)");
   if (code & 8u) add("msc_sweep_sequential: an order entry >= nrows (visit skipped; detail: entry), or a leave from an empty group or counter (detail: group)");
-  if (code & ~15u) add("unknown device-side error");
+  if (code & 16u) add("msc_zmatrix_add: a label outside [0, nlabels) (that sample was skipped; detail: row of z)");
+  if (code & ~31u) add("unknown device-side error");
   return fail(MSC_EDEVICE, "reported by an earlier kernel on device %d: %s [detail of the first: %u]; rebuild the affected state's tables",
               ctx->device, what.c_str(), detail);
 }
@@ -3379,5 +3381,160 @@ extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, co
   if (launch_pred_sample(s, st->pred_feats_dev, pfs, st->K, row0, nrows, row_id0, z, z_out_dev,
                          (flags & MSC_PRED_MASKED_ONLY) != 0, seed, sweep))
     return fail(MSC_EHIP, "k_pred_sample launch failed");
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// z-matrix accumulator (microscopes.common.query.zmatrix; kernels_query.hip)
+// ---------------------------------------------------------------------------
+static void zmatrix_free(msc_zmatrix *zm) {
+  if (!zm) return;
+  for (void *p : {(void *)zm->rows_dev, (void *)zm->order_dev, (void *)zm->batch, (void *)zm->bad, (void *)zm->counts})
+    if (p) (void)hipFree(p);
+  delete zm;
+}
+
+static size_t zm_count_words(uint32_t nt) { return (size_t)nt * (nt + 1) / 2 * kZmTile * kZmTile; }
+
+// hipMalloc, MSC_ENOMEM (with the footprint) when the device has no room
+static int zm_alloc(void **p, size_t bytes, const char *what, uint32_t m) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess) return MSC_OK;
+  (void)hipGetLastError();
+  *p = nullptr;
+  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
+    return fail(MSC_ENOMEM, "msc_zmatrix_create: m = %u needs %zu bytes for the %s (include/microscopes_hip.h gives the "
+                "footprint); the device has no room", m, bytes, what);
+  return fail(MSC_EHIP, "hipMalloc of the %s failed: %s", what, hipGetErrorString(e));
+}
+
+extern "C" int msc_zmatrix_create(msc_context *ctx, uint64_t n, const uint32_t *host_rows, uint32_t m, uint32_t nlabels,
+                                  msc_zmatrix **out) {
+  MSC_REQUIRE(ctx && out, "null argument");
+  *out = nullptr;
+  MSC_REQUIRE(n > 0, "msc_zmatrix_create: n is 0");
+  MSC_REQUIRE(host_rows || (uint64_t)m == n, "msc_zmatrix_create: without rows m (%u) must equal n (%llu)", m,
+              (unsigned long long)n);
+  MSC_REQUIRE(m >= 1 && m <= kZmMaxRows, "msc_zmatrix_create: m = %u outside [1, %u]", m, kZmMaxRows);
+  MSC_REQUIRE(nlabels >= 1 && nlabels <= kZmMaxLabels, "msc_zmatrix_create: nlabels = %u outside [1, %u]", nlabels,
+              kZmMaxLabels);
+  std::vector<uint32_t> rows(m);
+  for (uint32_t a = 0; a < m; a++) {
+    rows[a] = host_rows ? host_rows[a] : a;
+    MSC_REQUIRE(rows[a] < n, "msc_zmatrix_create: rows[%u] = %u is not below n = %llu", a, rows[a], (unsigned long long)n);
+  }
+  MSC_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<msc_zmatrix, void (*)(msc_zmatrix *)> zm(new (std::nothrow) msc_zmatrix(), zmatrix_free);
+  if (!zm) return fail(MSC_ENOMEM, "out of host memory");
+  zm->ctx = ctx;
+  zm->n = n;
+  zm->m = m;
+  zm->nlabels = nlabels;
+  zm->nt = (m + kZmTile - 1) / kZmTile;
+  zm->wide = nlabels > 256;
+  const size_t batch_bytes = (size_t)zm->nt * kZmTile * kZmBatchWords * 4;
+  const size_t count_bytes = zm_count_words(zm->nt) * 4;
+  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->counts), count_bytes, "counts", m));
+  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->batch), batch_bytes, "sample batch", m));
+  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->bad), (kZmBatchMax + 1) * 4, "batch flags", m));
+  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->rows_dev), (size_t)m * 4, "rows", m));
+  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->order_dev), (size_t)m * 4, "order", m));
+  const hipStream_t s = ctx->stream;
+  MSC_HIP(hipMemsetAsync(zm->counts, 0, count_bytes, s));
+  MSC_HIP(hipMemsetAsync(zm->batch, 0, batch_bytes, s));
+  MSC_HIP(hipMemsetAsync(zm->bad, 0, (kZmBatchMax + 1) * 4, s));
+  MSC_HIP(hipMemcpyAsync(zm->rows_dev, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
+  MSC_HIP(hipStreamSynchronize(s));
+  *out = zm.release();
+  return MSC_OK;
+}
+
+// the staged samples into the counts, then an empty batch
+static int zmatrix_flush(msc_zmatrix *zm) {
+  if (zm->staged == 0) return MSC_OK;
+  const hipStream_t s = zm->ctx->stream;
+  if (launch_zm_count(s, zm->batch, zm->nt, zm->wide, zm->staged, zm->bad, zm->counts))
+    return fail(MSC_EHIP, "k_zm_count launch failed");
+  MSC_HIP(hipMemsetAsync(zm->batch, 0, (size_t)zm->nt * kZmTile * kZmBatchWords * 4, s));
+  MSC_HIP(hipMemsetAsync(zm->bad, 0, (kZmBatchMax + 1) * 4, s));
+  zm->staged = 0;
+  return MSC_OK;
+}
+
+extern "C" int msc_zmatrix_add(msc_zmatrix *zm, const int32_t *z_dev, uint32_t nsamples, uint64_t ld) {
+  MSC_REQUIRE(zm && z_dev, "null argument");
+  MSC_REQUIRE(ld >= zm->n, "msc_zmatrix_add: ld = %llu is below n = %llu", (unsigned long long)ld,
+              (unsigned long long)zm->n);
+  MSC_TRY(device_error_check(zm->ctx));
+  if (nsamples == 0) return MSC_OK;
+  MSC_HIP(hipSetDevice(zm->ctx->device));
+  const uint32_t cap = zm_batch_cap(zm->wide);
+  for (uint32_t done = 0; done < nsamples;) {
+    const uint32_t k = std::min(nsamples - done, cap - zm->staged);
+    if (launch_zm_stage(zm->ctx->stream, z_dev + (uint64_t)done * ld, ld, k, zm->rows_dev, zm->m, zm->nlabels, zm->wide,
+                        zm->staged, zm->bad, zm->batch))
+      return fail(MSC_EHIP, "k_zm_check / k_zm_pack launch failed");
+    zm->staged += k;
+    zm->nsamples += k;
+    done += k;
+    if (zm->staged == cap) MSC_TRY(zmatrix_flush(zm));
+  }
+  return MSC_OK;
+}
+
+extern "C" int msc_zmatrix_nsamples(const msc_zmatrix *zm, uint64_t *out) {
+  MSC_REQUIRE(zm && out, "null argument");
+  *out = zm->nsamples;
+  return MSC_OK;
+}
+
+static int zmatrix_write(msc_zmatrix *zm, const uint32_t *host_order, void *out_dev, uint64_t ld_out, bool norm) {
+  MSC_REQUIRE(zm && out_dev, "null argument");
+  MSC_REQUIRE(ld_out >= zm->m, "ld_out = %llu is below m = %u", (unsigned long long)ld_out, zm->m);
+  MSC_REQUIRE(!norm || zm->nsamples > 0, "msc_zmatrix_result: no sample has been added (empty assignments list)");
+  if (host_order) {
+    std::vector<uint8_t> seen(zm->m, 0);
+    for (uint32_t a = 0; a < zm->m; a++) {
+      MSC_REQUIRE(host_order[a] < zm->m && !seen[host_order[a]], "order is not a permutation of [0, %u): entry %u is %u",
+                  zm->m, a, host_order[a]);
+      seen[host_order[a]] = 1;
+    }
+  }
+  MSC_TRY(device_error_check(zm->ctx));
+  MSC_HIP(hipSetDevice(zm->ctx->device));
+  MSC_TRY(zmatrix_flush(zm));
+  const hipStream_t s = zm->ctx->stream;
+  if (host_order) MSC_HIP(hipMemcpyAsync(zm->order_dev, host_order, (size_t)zm->m * 4, hipMemcpyHostToDevice, s));
+  if (launch_zm_finish(s, zm->counts, zm->nt, zm->m, host_order ? zm->order_dev : nullptr, norm, (float)zm->nsamples,
+                       out_dev, ld_out))
+    return fail(MSC_EHIP, "k_zm_finish launch failed");
+  return MSC_OK;
+}
+
+extern "C" int msc_zmatrix_counts(msc_zmatrix *zm, const uint32_t *host_order, uint32_t *out_dev, uint64_t ld_out) {
+  return zmatrix_write(zm, host_order, out_dev, ld_out, false);
+}
+
+extern "C" int msc_zmatrix_result(msc_zmatrix *zm, const uint32_t *host_order, float *out_dev, uint64_t ld_out) {
+  return zmatrix_write(zm, host_order, out_dev, ld_out, true);
+}
+
+extern "C" int msc_zmatrix_reset(msc_zmatrix *zm) {
+  MSC_REQUIRE(zm, "null argument");
+  MSC_HIP(hipSetDevice(zm->ctx->device));
+  const hipStream_t s = zm->ctx->stream;
+  MSC_HIP(hipMemsetAsync(zm->counts, 0, zm_count_words(zm->nt) * 4, s));
+  MSC_HIP(hipMemsetAsync(zm->batch, 0, (size_t)zm->nt * kZmTile * kZmBatchWords * 4, s));
+  MSC_HIP(hipMemsetAsync(zm->bad, 0, (kZmBatchMax + 1) * 4, s));
+  zm->staged = 0;
+  zm->nsamples = 0;
+  return MSC_OK;
+}
+
+extern "C" int msc_zmatrix_destroy(msc_zmatrix *zm) {
+  if (!zm) return MSC_OK;
+  (void)hipSetDevice(zm->ctx->device);
+  (void)hipStreamSynchronize(zm->ctx->stream);
+  zmatrix_free(zm);
   return MSC_OK;
 }

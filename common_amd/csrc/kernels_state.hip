@@ -532,14 +532,15 @@ __global__ __launch_bounds__(256) void k_pack_look_idx(const LookIdxSrc *__restr
   }
   while (at < l4) rec[at++] = word, word = 0u;
 }
-static char g_last_kernel[2][160] = {"", ""};
+static char g_last_kernel[3][160] = {"", "", ""};
+static inline int kernel_slot(int slot) { return slot == 2 ? 2 : (slot & 1); }
 void note_kernel(int slot, const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_last_kernel[slot & 1], sizeof g_last_kernel[0], fmt, ap);
+  vsnprintf(g_last_kernel[kernel_slot(slot)], sizeof g_last_kernel[0], fmt, ap);
   va_end(ap);
 }
-const char *last_kernel(int slot) { return g_last_kernel[slot & 1]; }
+const char *last_kernel(int slot) { return g_last_kernel[kernel_slot(slot)]; }
 
 int launch_pack_look_idx(hipStream_t stream, const LookIdxSrc *src_dev, uint32_t nsrc, uint32_t l4, uint64_t n, uint32_t *out) {
   if (n == 0 || nsrc == 0) return 0;

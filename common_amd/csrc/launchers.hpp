@@ -41,6 +41,7 @@ int bind_error_word_score(uint32_t *word_dev);
 int bind_error_word_sweep(uint32_t *word_dev);
 int bind_error_word_state(uint32_t *word_dev);
 int bind_error_word_seq(uint32_t *word_dev);
+int bind_error_word_query(uint32_t *word_dev);
 
 // kernels_score.hip
 int launch_prepare(hipStream_t stream, const FeatDesc *feats_dev, uint32_t nfeat, uint32_t kpad, uint32_t value_slices);
@@ -121,7 +122,8 @@ int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan
                  uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z,
                  const float *own, const float *crp, float *out, uint64_t ld);
 
-// which kernel INSTANTIATION the library chose for the most recent scoring pass (slot 0) / fused assignment pass (slot 1),
+// which kernel INSTANTIATION the library chose for the most recent scoring pass (slot 0) / fused assignment pass (slot 1)
+// / z-matrix kernel (slot 2),
 // spelled as rocprofv3 spells it ("k_score_tile_roles<false, false, false>"): bench.py and tools/ key the committed
 // counter summaries by it (msc_last_kernel, include/microscopes_hip.h).  Process-wide, set by the launchers.
 void note_kernel(int slot, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -247,5 +249,21 @@ int launch_pred_prepare(hipStream_t stream, const PredFeat *pfs_dev, const std::
 int launch_pred_sample(hipStream_t stream, const PredFeat *pfs_dev, const std::vector<PredFeat> &pfs, uint32_t K,
                        uint64_t row0, uint64_t nrows, uint64_t row_id0, const int32_t *z, int32_t *z_out,
                        bool masked_only, uint64_t seed, uint64_t sweep);
+
+// kernels_query.hip (msc_zmatrix_*): counts live as upper-triangle tiles of kZmTile x kZmTile u32 (zm_tile_base); the
+// batch is [rows rounded up to kZmTile][kZmBatchWords] u32, four 8-bit or two 16-bit labels a word; `bad` holds a flag
+// per batch slot (kZmBatchMax of them) and then the number of flagged slots
+constexpr uint32_t kZmTile = 64;
+constexpr uint32_t kZmBatchWords = 256;
+constexpr uint32_t kZmBatchMax = 4 * kZmBatchWords;
+constexpr uint32_t kZmMaxRows = 1u << 18;
+constexpr uint32_t kZmMaxLabels = 1u << 16;
+inline uint32_t zm_batch_cap(bool wide) { return (wide ? 2u : 4u) * kZmBatchWords; }
+int launch_zm_stage(hipStream_t stream, const int32_t *z, uint64_t ld, uint32_t nsamples, const uint32_t *rows,
+                    uint32_t m, uint32_t nlabels, bool wide, uint32_t slot0, uint32_t *bad, uint32_t *batch);
+int launch_zm_count(hipStream_t stream, const uint32_t *batch, uint32_t nt, bool wide, uint32_t staged,
+                    const uint32_t *bad, uint32_t *counts);
+int launch_zm_finish(hipStream_t stream, const uint32_t *counts, uint32_t nt, uint32_t m, const uint32_t *order,
+                     bool norm, float S, void *out, uint64_t ld);
 
 }  // namespace msc

@@ -631,3 +631,18 @@ struct msc_hp_grid {
   msc::HpJob job;                     // the grid alone (part_off = out_off = 0)
   msc::HpJob *job_dev = nullptr;
 };
+
+// a z-matrix accumulator (abi.cpp msc_zmatrix_*, kernels_query.hip): m selected rows, counts as upper-triangle tiles
+struct msc_zmatrix {
+  msc_context *ctx = nullptr;
+  uint64_t n = 0;
+  uint32_t m = 0, nlabels = 0, nt = 0;     // nt: 64-row bands (m rounded up)
+  bool wide = false;                       // 16-bit labels (nlabels > 256)
+  uint32_t *rows_dev = nullptr;            // [m]
+  uint32_t *order_dev = nullptr;           // [m], the order of the most recent counts / result call
+  uint32_t *batch = nullptr;               // [64 nt][kZmBatchWords], zero where no sample is staged
+  uint32_t *bad = nullptr;                 // [kZmBatchMax + 1]: bad-sample flags of the batch's slots, then their number
+  uint32_t *counts = nullptr;              // [nt (nt + 1) / 2][64][64]
+  uint32_t staged = 0;                     // samples in the batch
+  uint64_t nsamples = 0;
+};

@@ -1,0 +1,158 @@
+"""Posterior summaries of assignment samples: the interface of the reference's ``microscopes.common.query``.
+
+``groups``, ``zmatrix``, ``zmatrix_reorder`` and ``zmatrix_heuristic_block_ordering`` take the same arguments, return the
+same values and raise the same ``ValueError``s.  Numpy input runs a vectorised numpy path.  Device tensors (or numpy input
+with ``ctx=``) build the z-matrix on the device (``ZMatrix``, ``msc_zmatrix_*``) and return a device tensor bit-equal to
+the numpy path.  The block ordering stays on the host: scipy's single linkage over the condensed upper triangle.
+"""
+import numpy as np
+import torch
+
+from ._lib import ZMATRIX_MAX_LABELS
+from .runtime import Context, ZMatrix
+
+_HOST_CHUNK_FLOATS = 1 << 23      # one-hot block of the numpy path: at most 64 MiB of float64
+
+
+def groups(avec, sort=False):
+    """The clustering of one assignment vector: a list of lists of row indices, one per distinct label, in the order the
+    labels first appear (``sort``: by descending size, ties in that order)."""
+    a = np.asarray(avec.cpu() if isinstance(avec, torch.Tensor) else avec)
+    if a.size == 0:
+        return []
+    a = a.reshape(-1)
+    _, first, inv = np.unique(a, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    rows = np.argsort(inv, kind="stable")              # rows of each label, ascending, label after label
+    sizes = np.bincount(inv, minlength=first.size)
+    parts = np.split(rows, np.cumsum(sizes)[:-1])
+    by_appearance = np.argsort(first, kind="stable")
+    if sort:
+        by_appearance = by_appearance[np.argsort(-sizes[by_appearance], kind="stable")]
+    return [parts[k].tolist() for k in by_appearance]
+
+
+def _is_device(x):
+    return isinstance(x, torch.Tensor) and x.device.type == "cuda"
+
+
+def _check_assignments(assignments):
+    if not len(assignments):
+        raise ValueError("empty assignments list")
+    if len(set(len(a) for a in assignments)) != 1:
+        raise ValueError("assignment vectors should all be same size")
+
+
+def _dense_labels(a):
+    """[S, n] of any labels -> the same partitions with labels in [0, K) per sample, and K"""
+    out = np.empty(a.shape, dtype=np.int32)
+    K = 1
+    for s in range(a.shape[0]):
+        u, inv = np.unique(a[s], return_inverse=True)
+        out[s] = inv.reshape(-1)
+        K = max(K, u.size)
+    return out, K
+
+
+def _zmatrix_host(a):
+    """float32 count / S: the counts as sums of one-hot products (exact in float64), a block of samples at a time"""
+    S, n = a.shape
+    dense, K = _dense_labels(a)
+    counts = np.zeros((n, n), dtype=np.float64)
+    step = max(1, _HOST_CHUNK_FLOATS // max(1, n * K))
+    eye = np.eye(K, dtype=np.float64)
+    for s0 in range(0, S, step):
+        blk = dense[s0:s0 + step]
+        H = eye[blk].transpose(1, 0, 2).reshape(n, -1)   # [n, samples x K]: row i's label of each sample, one-hot
+        counts += H @ H.T
+    return counts.astype(np.float32) / np.float32(S)
+
+
+def _zmatrix_device(a, ctx):
+    """a: int32 device tensor [S, n]"""
+    S, n = int(a.shape[0]), int(a.shape[1])
+    lo, hi = int(a.min()), int(a.max())
+    if lo < 0 or hi >= ZMATRIX_MAX_LABELS:
+        a = torch.stack([torch.unique(a[s], return_inverse=True)[1] for s in range(S)]).to(torch.int32)
+        hi = int(a.max())
+    zm = ZMatrix(ctx, n, hi + 1)
+    try:
+        zm.add(a.contiguous())
+        return zm.result()
+    finally:
+        zm.close()
+
+
+def zmatrix(assignments, ctx=None):
+    """Z[i, j] = the fraction of the assignment vectors in which rows i and j share a label (float32 [n, n]).
+
+    ``assignments``: a list (or [S, n] array) of assignment vectors of equal length.  Numpy input returns a numpy array;
+    a device tensor, a list of device tensors, or any input with ``ctx`` (a ``Context``) runs on the device and returns a
+    float32 device tensor with the same bits."""
+    _check_assignments(assignments)
+    on_device = ctx is not None or _is_device(assignments) or \
+        (not isinstance(assignments, (np.ndarray, torch.Tensor)) and any(_is_device(a) for a in assignments))
+    if not on_device:
+        a = np.asarray([np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in assignments])
+        return _zmatrix_host(a.reshape(len(assignments), -1))
+    if ctx is None:
+        dev = assignments.device if isinstance(assignments, torch.Tensor) else \
+            next(a.device for a in assignments if _is_device(a))
+        ctx = Context(device=dev.index if dev.index is not None else torch.cuda.current_device())
+    if isinstance(assignments, torch.Tensor):
+        a = assignments.to(device=ctx.torch_device)
+    else:
+        rows = []
+        for v in assignments:
+            if isinstance(v, torch.Tensor):
+                rows.append(v.to(device=ctx.torch_device).reshape(-1))
+            else:
+                rows.append(torch.from_numpy(np.asarray(v).reshape(-1).astype(np.int64)).to(ctx.torch_device))
+        a = torch.stack([r.to(torch.int64) for r in rows])
+    if a.dtype.is_floating_point or a.dtype == torch.bool:
+        raise ValueError("assignment vectors must hold integer labels")
+    if a.dtype != torch.int32:
+        a64 = a.to(torch.int64)
+        if int(a64.min()) < 0 or int(a64.max()) >= ZMATRIX_MAX_LABELS:
+            a64 = torch.stack([torch.unique(a64[s], return_inverse=True)[1] for s in range(a64.shape[0])])
+        a = a64.to(torch.int32)
+    return _zmatrix_device(a.reshape(a.shape[0], -1), ctx)
+
+
+def _is_square(z):
+    return len(z.shape) == 2 and z.shape[0] == z.shape[1]
+
+
+def _is_permutation(pi, n):
+    if len(pi.shape) != 1 or pi.shape[0] != n:
+        return False
+    if not np.issubdtype(pi.dtype, np.integer):
+        return False
+    return np.unique(pi).size == n
+
+
+def zmatrix_reorder(zmat, order):
+    """zmat with rows and columns permuted by ``order``: out[a, b] = zmat[order[a], order[b]].  A device tensor stays on
+    the device."""
+    o = np.asarray(order.cpu() if isinstance(order, torch.Tensor) else order)
+    if not _is_square(zmat):
+        raise ValueError("not a zmatrix")
+    if not _is_permutation(o, zmat.shape[0]):
+        raise ValueError("not a valid permutation")
+    if isinstance(zmat, torch.Tensor):
+        idx = torch.from_numpy(o.astype(np.int64)).to(zmat.device)
+        return zmat.index_select(0, idx).index_select(1, idx)
+    zmat = np.asarray(zmat)
+    return zmat[o][:, o]
+
+
+def zmatrix_heuristic_block_ordering(zmat):
+    """A permutation of the rows that puts co-clustered rows next to each other: the leaves of scipy's single linkage of
+    the distances 1 - Z over the condensed upper triangle."""
+    import scipy.cluster.hierarchy as hier
+    if not _is_square(zmat):
+        raise ValueError("not a zmat")
+    z = np.asarray(zmat.cpu() if isinstance(zmat, torch.Tensor) else zmat)
+    n = z.shape[0]
+    dist = 1. - np.array(z[np.triu_indices(n, k=1)])
+    return np.array(hier.leaves_list(hier.linkage(dist)))

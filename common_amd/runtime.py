@@ -87,9 +87,10 @@ class Context(object):
         return self.lib.msc_build_info().decode()
 
     def last_kernel(self, which="score"):
-        """the kernel instantiation of this process's most recent scoring ("score") or fused assignment ("sweep") pass, as
-        rocprofv3 spells it (msc_last_kernel): what bench.py keys the committed counter summaries by"""
-        return self.lib.msc_last_kernel(0 if which == "score" else 1).decode()
+        """the kernel instantiation of this process's most recent scoring ("score") or fused assignment ("sweep") pass, or
+        z-matrix kernel ("zmatrix"), as rocprofv3 spells it (msc_last_kernel): what bench.py keys the committed counter
+        summaries by"""
+        return self.lib.msc_last_kernel({"score": 0, "zmatrix": 2}.get(which, 1)).decode()
 
     def value_op(self, family, dim, op, hp, ss_record, value=None):
         """One group::{add_value, remove_value, score_value, score_data} call (base.hpp:25-28) as a batch
@@ -699,6 +700,113 @@ class HpGrid(object):
         if getattr(self, "_h", None):
             if getattr(self.state, "_h", None) and getattr(self.state.ctx, "_h", None):
                 self.state.ctx.lib.msc_hp_grid_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ZMatrix(object):
+    """Co-clustering counts of m chosen rows over assignment samples, accumulated on the device (msc_zmatrix_*): the
+    reference's query.zmatrix restricted to `rows` (None: all n, in order).  Every label must lie in [0, nlabels)."""
+
+    def __init__(self, ctx, n, nlabels, rows=None):
+        self.ctx, self.n, self.nlabels = ctx, int(n), int(nlabels)
+        rp = None
+        if rows is None:
+            self.m = self.n
+        else:
+            r = np.asarray(rows)
+            if r.ndim != 1 or not (np.issubdtype(r.dtype, np.integer) or r.size == 0):
+                raise ValueError("rows must be a 1-D array of row indices")
+            if r.size and (r.min() < 0 or r.max() >= self.n):
+                raise ValueError("rows must lie in [0, n)")
+            rp = np.ascontiguousarray(r, dtype=np.uint32)
+            self.m = int(rp.size)
+        self._rows = rp
+        h = C.c_void_p()
+        L.check(ctx.lib.msc_zmatrix_create(ctx._h, self.n, None if rp is None else rp.ctypes.data_as(C.c_void_p), self.m,
+                                           self.nlabels, C.byref(h)))
+        self._h = h
+
+    def _check_open(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("ZMatrix is closed")
+
+    def add(self, z):
+        """stage assignment vectors: an int32 device tensor [n] or [S, n] whose rows are contiguous (row stride >= n).
+        Asynchronous; z may be overwritten by the next work on the stream (msc_zmatrix_add)."""
+        self._check_open()
+        if not isinstance(z, torch.Tensor) or z.dtype != torch.int32 or z.device != self.ctx.torch_device:
+            raise ValueError("z must be an int32 tensor on %s" % self.ctx.torch_device)
+        if z.dim() == 1:
+            z2, S, ld = z, 1, self.n
+            if z.shape[0] != self.n or (self.n > 1 and z.stride(0) != 1):
+                raise ValueError("z must hold n = %d contiguous labels" % self.n)
+        elif z.dim() == 2:
+            z2, S, ld = z, int(z.shape[0]), int(z.stride(0)) if z.shape[0] > 1 else self.n
+            if z.shape[1] != self.n or (self.n > 1 and z.stride(1) != 1) or ld < self.n:
+                raise ValueError("z must be [S, n = %d] with contiguous rows" % self.n)
+        else:
+            raise ValueError("z must be [n] or [S, n]")
+        if S == 0:
+            return
+        L.check(self.ctx.lib.msc_zmatrix_add(self._h, C.c_void_p(z2.data_ptr()), S, ld))
+
+    @property
+    def nsamples(self):
+        self._check_open()
+        v = C.c_uint64()
+        L.check(self.ctx.lib.msc_zmatrix_nsamples(self._h, C.byref(v)))
+        return int(v.value)
+
+    def _out(self, out, dtype):
+        m = self.m
+        if out is None:
+            return torch.empty((m, m), dtype=dtype, device=self.ctx.torch_device)
+        if out.dtype != dtype or out.device != self.ctx.torch_device or out.dim() != 2 or out.shape[0] < m \
+                or out.shape[1] < m or (m > 1 and out.stride(1) != 1) or out.stride(0) < m:
+            raise ValueError("out must be a %s tensor on %s of at least [m, m] = [%d, %d] with contiguous rows"
+                             % (dtype, self.ctx.torch_device, m, m))
+        return out
+
+    def _order(self, order):
+        if order is None:
+            return None
+        o = np.asarray(order.cpu() if isinstance(order, torch.Tensor) else order)
+        if o.shape != (self.m,) or not np.issubdtype(o.dtype, np.integer) or \
+                (o.size and (o.min() < 0 or o.max() >= self.m)) or np.unique(o).size != self.m:
+            raise ValueError("not a valid permutation")
+        return np.ascontiguousarray(o, dtype=np.uint32)
+
+    def _write(self, fn, order, out, dtype):
+        self._check_open()
+        o = self._order(order)
+        out = self._out(out, dtype)
+        L.check(fn(self._h, None if o is None else o.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
+                   int(out.stride(0))))
+        return out[:self.m, :self.m] if out.shape != (self.m, self.m) else out
+
+    def counts(self, order=None, out=None):
+        """int32 [m, m] device tensor holding the exact u32 counts (optionally reordered: out[a, b] = C[order[a], order[b]])"""
+        return self._write(self.ctx.lib.msc_zmatrix_counts, order, out, torch.int32)
+
+    def result(self, order=None, out=None):
+        """float32 [m, m] device tensor: counts / nsamples, as the reference's zmatrix computes it"""
+        return self._write(self.ctx.lib.msc_zmatrix_result, order, out, torch.float32)
+
+    def reset(self):
+        self._check_open()
+        L.check(self.ctx.lib.msc_zmatrix_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            # (as DataView.close: a handle whose context is gone is not handed to the library)
+            if getattr(self.ctx, "_h", None):
+                self.ctx.lib.msc_zmatrix_destroy(self._h)
             self._h = None
 
     def __del__(self):

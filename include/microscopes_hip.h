@@ -87,7 +87,8 @@ const char *msc_last_error(void);
 const char *msc_build_info(void); /* "gfx950 hipcc <ver> ..." */
 /*
  * Which kernel INSTANTIATION the library chose for this process's most recent scoring pass (which = 0: msc_score_value)
- * or fused assignment pass (which = 1: msc_sweep_assign / msc_sweep_step), spelled as rocprofv3 spells it, e.g.
+ * or fused assignment pass (which = 1: msc_sweep_assign / msc_sweep_step), or the most recent kernel of the z-matrix
+ * accumulator (which = 2: msc_zmatrix_*), spelled as rocprofv3 spells it, e.g.
  * "k_score_tile_roles<false, false, false>" ("" before the first such call).  Measurement tooling only: bench.py keys the
  * committed counter summaries (profiles/ *_pmc.json) by it, so that a roofline figure is always the figure of the kernel
  * that ran.  Nothing comparable upstream (the reference has no kernels).
@@ -602,6 +603,47 @@ int msc_relation_slice_scores(msc_context *ctx, const float *scores_dev, uint64_
                               const uint64_t *shape, uint32_t dim, const uint32_t *seg_dev, const uint32_t *ids_dev,
                               const int32_t *off_dev, uint32_t ncand, uint32_t cand_stride, uint64_t nent,
                               float *out_dev, uint64_t ld_out);
+
+/* ---- posterior co-clustering (z-)matrix (replaces microscopes.common.query.zmatrix) ---- */
+/*
+ * An accumulator of the co-clustering counts of m chosen rows over S assignment samples: C[a][b] = the number of
+ * samples in which rows rows[a] and rows[b] share a label, and Z = C / S, the reference's zmatrix (query.py) restricted
+ * to those rows.  The handle belongs to its context, as a view or a state does.
+ * host_rows: m row indices into assignment vectors of n labels, in output order (repeats allowed, any order); NULL =
+ * every row (m must equal n).  An entry >= n is MSC_EINVAL.  1 <= m <= 262144.  nlabels (the state's K): every label
+ * must lie in [0, nlabels), 1 <= nlabels <= 65536.  Labels are packed 8 bits wide when nlabels <= 256, 16 bits otherwise.
+ * Device footprint: the counts as upper-triangle tiles of 64 x 64 u32, 8 T (T + 1) KiB with T = ceil(m / 64) (m =
+ * 16384: 514 MiB; m = 65536: 8 GiB), plus a batch of 64 T x 1 KiB (m = 16384: 16 MiB) and m u32 for the rows and as
+ * many for an order: MSC_ENOMEM when that cannot be allocated.  Synchronous.
+ */
+typedef struct msc_zmatrix msc_zmatrix;
+int msc_zmatrix_create(msc_context *ctx, uint64_t n, const uint32_t *host_rows, uint32_t m, uint32_t nlabels,
+                       msc_zmatrix **out);
+/*
+ * Stage nsamples assignment vectors: sample s is z_dev[s * ld .. s * ld + n) (ld >= n), int32 labels.  Asynchronous on
+ * the context's stream; the labels the matrix needs are packed before the call returns in stream order, so the caller
+ * may overwrite z_dev with the next work it enqueues (the next msc_sweep_step, a replayed step graph included).  Samples
+ * are gathered into a batch (1024 samples at 8 bits, 512 at 16) and the counts are updated when the batch fills; a call
+ * larger than the space left spreads over several updates.  A label outside [0, nlabels) is never used as an address:
+ * its sample adds nothing (it is still counted by msc_zmatrix_nsamples) and the failure surfaces as MSC_EDEVICE at the
+ * next synchronising or launching call (reset the accumulator then).
+ */
+int msc_zmatrix_add(msc_zmatrix *zm, const int32_t *z_dev, uint32_t nsamples, uint64_t ld);
+/* samples handed to msc_zmatrix_add since creation or the last reset (host bookkeeping, no synchronisation) */
+int msc_zmatrix_nsamples(const msc_zmatrix *zm, uint64_t *out);
+/*
+ * Update the counts with the staged samples, then write the full symmetric m x m matrix into out_dev (row a at
+ * out_dev + a * ld_out, ld_out >= m): msc_zmatrix_counts the exact u32 counts C, msc_zmatrix_result float(C) / float(S)
+ * with IEEE division (for S < 2^24 bit for bit the reference's float32 sum of ones divided by float(S)).  host_order
+ * (nullable): a permutation of [0, m); the matrix is written reordered, out[a][b] = Z[order[a]][order[b]] (MSC_EINVAL
+ * when it is not a permutation).  msc_zmatrix_result with no sample is MSC_EINVAL (the reference raises on an empty
+ * list).  Asynchronous on the context's stream; host_order is read before the call returns.
+ */
+int msc_zmatrix_counts(msc_zmatrix *zm, const uint32_t *host_order, uint32_t *out_dev, uint64_t ld_out);
+int msc_zmatrix_result(msc_zmatrix *zm, const uint32_t *host_order, float *out_dev, uint64_t ld_out);
+/* zero the counts and drop the staged samples (asynchronous); destroy frees everything the accumulator allocated */
+int msc_zmatrix_reset(msc_zmatrix *zm);
+int msc_zmatrix_destroy(msc_zmatrix *zm);
 
 #ifdef __cplusplus
 }
