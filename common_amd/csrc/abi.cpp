@@ -40,27 +40,11 @@ size_t primitive_size(int t) {
 
 static bool family_ok(int f) { return f >= MSC_BB && f <= MSC_DM; }
 
+// count elements (at least one), zero-filled
 template <typename T>
-static int dev_alloc(std::vector<void *> &owned, T **out, size_t count) {
-  void *p = nullptr;
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  MSC_HIP(hipMalloc(&p, bytes));
-  MSC_HIP(hipMemset(p, 0, bytes));
-  owned.push_back(p);
-  *out = static_cast<T *>(p);
-  return MSC_OK;
-}
-
-// a state's buffer that grows on demand to `n` elements.  No sync and no free: the old buffer stays in st->owned until
-// the state is destroyed, because a captured step graph may still use it (hp_reserve syncs and frees instead)
-template <typename T>
-static int grow(msc_state *st, T *&buf, size_t &cap, size_t n) {
-  if (cap >= n) return MSC_OK;
-  void *p = nullptr;
-  MSC_HIP(hipMalloc(&p, n * sizeof(T)));
-  st->owned.push_back(p);
-  buf = static_cast<T *>(p);
-  cap = n;
+static int alloc_zeroed(DevBuf<T> &buf, size_t count) {
+  MSC_HIP(buf.alloc(count, 1));
+  MSC_HIP(hipMemset(buf, 0, std::max<size_t>(count, 1) * sizeof(T)));
   return MSC_OK;
 }
 
@@ -141,23 +125,17 @@ extern "C" int msc_context_create(int device, void *stream, msc_context **out) {
   ctx->device = device;
   ctx->stream = static_cast<hipStream_t>(stream);
   ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  ctx->mailbox_bytes = 192 * 1024;       // niw at dim 128: a 66 KB record + a 66 KB hp block
-  MSC_HIP(hipHostMalloc(&ctx->mailbox_host, ctx->mailbox_bytes, hipHostMallocMapped));
+  MSC_HIP(ctx->mailbox_host.alloc(192 * 1024));   // niw at dim 128: a 66 KB record + a 66 KB hp block
   MSC_HIP(hipHostGetDevicePointer(&ctx->mailbox_dev, ctx->mailbox_host, 0));
   const char *sw = std::getenv("MSC_SYNC_WORD");           // 0: plain hipStreamSynchronize (A/B knob)
   if (sw && std::atoi(sw) == 0) ctx->sync_word_ok = false;
-  if (hipHostMalloc(reinterpret_cast<void **>(&ctx->sync_word_host), 64, hipHostMallocMapped) == hipSuccess) {
+  if (ctx->sync_word_host.alloc(16) == hipSuccess) {   // (64 bytes)
     *ctx->sync_word_host = 0;
     if (hipHostGetDevicePointer(&ctx->sync_word_dev, ctx->sync_word_host, 0) != hipSuccess) ctx->sync_word_ok = false;
   } else {
     (void)hipGetLastError();
-    ctx->sync_word_host = nullptr;
   }
-  if (const int rc = device_error_word(device, &ctx->err_host)) {      // (nothing pinned is left behind)
-    if (ctx->mailbox_host) (void)hipHostFree(ctx->mailbox_host);
-    if (ctx->sync_word_host) (void)hipHostFree(ctx->sync_word_host);
-    return rc;
-  }
+  MSC_TRY(device_error_word(device, &ctx->err_host));
   *out = ctx.release();
   return MSC_OK;
 }
@@ -169,8 +147,6 @@ extern "C" int msc_context_destroy(msc_context *ctx) {
   (void)hipSetDevice(ctx->device);
   for (auto &a : ctx->vmm) vmm_free(a);
   ctx->vmm.clear();
-  if (ctx->mailbox_host) (void)hipHostFree(ctx->mailbox_host);
-  if (ctx->sync_word_host) (void)hipHostFree(ctx->sync_word_host);
   if (ctx->record_stream) (void)hipStreamDestroy(ctx->record_stream);
   delete ctx;
   return MSC_OK;
@@ -523,11 +499,6 @@ static const msc_dataview *bound_view_of(msc_state *st) {
   return nullptr;
 }
 
-static void free_all(std::vector<void *> &owned) {
-  for (void *p : owned) (void)hipFree(p);
-  owned.clear();
-}
-
 extern "C" int msc_dataview_from_records(msc_context *ctx, const void *host_records,
                                          const uint8_t *host_mask, uint64_t nrows,
                                          const msc_runtime_type *types, uint32_t ntypes,
@@ -559,44 +530,39 @@ extern "C" int msc_dataview_from_records(msc_context *ctx, const void *host_reco
   v->ctx = ctx;
   v->serial = next_view_serial();
   v->nrows = nrows;
-  int rc = MSC_OK;
-  uint8_t *rec_dev = nullptr, *mask_dev = nullptr;
-  UnpackFeat *uf_dev = nullptr;
-  std::vector<void *> scratch;
-  auto cleanup = [&](int code) { free_all(scratch); if (code != MSC_OK) free_all(v->owned); return code; };
   for (uint32_t i = 0; i < ntypes; i++) {
-    uint8_t *col = nullptr;
-    rc = dev_alloc(v->owned, &col, (size_t)nrows * types[i].count * primitive_size(uf[i].dst_type));
-    if (rc) return cleanup(rc);
+    DevBuf<uint8_t> col, mask;
+    MSC_TRY(alloc_zeroed(col, (size_t)nrows * types[i].count * primitive_size(uf[i].dst_type)));
+    if (host_mask) MSC_TRY(alloc_zeroed(mask, (size_t)nrows * types[i].count));
     uf[i].dst = col;
-    uf[i].dst_mask = nullptr;
-    if (host_mask) {
-      rc = dev_alloc(v->owned, &uf[i].dst_mask, (size_t)nrows * types[i].count);
-      if (rc) return cleanup(rc);
-    }
+    uf[i].dst_mask = mask;
     v->cols.push_back(col);
-    v->masks.push_back(uf[i].dst_mask);
+    v->masks.push_back(mask);
     v->types.push_back(msc_runtime_type{uf[i].dst_type, types[i].count});
+    v->owned.push_back(std::move(col));
+    if (mask) v->owned.push_back(std::move(mask));
   }
   v->col_max.assign(ntypes, -1);
   v->dm_max.assign(ntypes, std::vector<uint32_t>());
-  v->dm_tot.assign(ntypes, nullptr);
   if (nrows > 0) {
-    if ((rc = dev_alloc(scratch, &rec_dev, (size_t)nrows * rowsize))) return cleanup(rc);
-    if ((rc = dev_alloc(scratch, &uf_dev, ntypes))) return cleanup(rc);
-    if (host_mask && (rc = dev_alloc(scratch, &mask_dev, (size_t)nrows * maskrowsize))) return cleanup(rc);
+    DevBuf<uint8_t> rec_dev, mask_dev;
+    DevBuf<UnpackFeat> uf_dev;
+    MSC_TRY(alloc_zeroed(rec_dev, (size_t)nrows * rowsize));
+    MSC_TRY(alloc_zeroed(uf_dev, ntypes));
+    if (host_mask) MSC_TRY(alloc_zeroed(mask_dev, (size_t)nrows * maskrowsize));
     hipError_t e = hipMemcpyAsync(rec_dev, host_records, (size_t)nrows * rowsize, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && host_mask)
       e = hipMemcpyAsync(mask_dev, host_mask, (size_t)nrows * maskrowsize, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(uf_dev, uf.data(), sizeof(UnpackFeat) * ntypes, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return cleanup(fail(MSC_EHIP, "upload failed: %s", hipGetErrorString(e)));
-    if (launch_unpack(ctx->stream, rec_dev, mask_dev, nrows, (uint32_t)rowsize, (uint32_t)maskrowsize, uf_dev, ntypes))
-      return cleanup(fail(MSC_EHIP, "k_unpack launch failed: %s", hipGetErrorString(hipGetLastError())));
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return cleanup(fail(MSC_EHIP, "k_unpack failed: %s", hipGetErrorString(e)));
+    int rc = e == hipSuccess ? MSC_OK : fail(MSC_EHIP, "upload failed: %s", hipGetErrorString(e));
+    if (rc == MSC_OK &&
+        launch_unpack(ctx->stream, rec_dev, mask_dev, nrows, (uint32_t)rowsize, (uint32_t)maskrowsize, uf_dev, ntypes))
+      rc = fail(MSC_EHIP, "k_unpack launch failed: %s", hipGetErrorString(hipGetLastError()));
+    e = hipStreamSynchronize(ctx->stream);              // (also before the staging buffers go on a failure)
+    if (rc == MSC_OK && e != hipSuccess) rc = fail(MSC_EHIP, "k_unpack failed: %s", hipGetErrorString(e));
+    MSC_TRY(rc);
   }
-  cleanup(MSC_OK);
   view_register(v->serial);
   *out = v.release();
   return MSC_OK;
@@ -626,7 +592,6 @@ extern "C" int msc_dataview_from_device_columns(msc_context *ctx, uint64_t nrows
   }
   v->col_max.assign(ntypes, -1);
   v->dm_max.assign(ntypes, std::vector<uint32_t>());
-  v->dm_tot.assign(ntypes, nullptr);
   view_register(v->serial);
   *out = v.release();
   return MSC_OK;
@@ -637,8 +602,6 @@ extern "C" int msc_dataview_destroy(msc_dataview *view) {
   view_unregister(view->serial);                          // (states that had it bound drop the binding: bound_view_of)
   (void)hipSetDevice(view->ctx->device);
   (void)hipStreamSynchronize(view->ctx->stream);
-  free_all(view->owned);
-  free_all(view->owned_lazy);
   delete view;
   return MSC_OK;
 }
@@ -655,15 +618,9 @@ extern "C" int msc_dataview_invalidate(msc_dataview *view) {
   MSC_HIP(hipSetDevice(view->ctx->device));
   MSC_HIP(hipStreamSynchronize(view->ctx->stream));
   view_unregister(view->serial);
-  free_all(view->owned_lazy);
-  view->converted.clear();
-  view->sentinels.clear();
-  view->packed_bits.clear();
-  view->nich_x.clear();
-  view->look_idx.clear();
+  view->copies.clear();
   view->col_max.assign(view->cols.size(), -1);
   view->dm_max.assign(view->cols.size(), std::vector<uint32_t>());
-  view->dm_tot.assign(view->cols.size(), nullptr);
   view->serial = next_view_serial();
   view_register(view->serial);
   return MSC_OK;
@@ -856,21 +813,36 @@ static PlanFacts plan_layout(std::vector<FeatDesc> &t, uint32_t split, const std
   return pf;
 }
 
+// The view's derived copies (msc_dataview::copies): the one of this kind and key, or null; and a new one.
+static const void *view_copy(const msc_dataview *view, msc_dataview::CopyKind kind, const std::vector<uint64_t> &key) {
+  for (const msc_dataview::Copy &e : view->copies)
+    if (e.kind == kind && e.key == key) return e.buf;
+  return nullptr;
+}
+static void *view_copy_add(const msc_dataview *view, msc_dataview::CopyKind kind, std::vector<uint64_t> key,
+                           DevBuf<uint8_t> &&buf) {
+  view->copies.push_back(msc_dataview::Copy{kind, std::move(key), std::move(buf)});
+  return view->copies.back().buf;
+}
+static size_t view_copies(const msc_dataview *view, msc_dataview::CopyKind kind) {
+  return (size_t)std::count_if(view->copies.begin(), view->copies.end(),
+                               [kind](const msc_dataview::Copy &e) { return e.kind == kind; });
+}
+static std::vector<uint64_t> pointer_key(const void *const *p, size_t n) {
+  std::vector<uint64_t> key(n);
+  for (size_t i = 0; i < n; i++) key[i] = reinterpret_cast<uintptr_t>(p[i]);
+  return key;
+}
+
 // the byte column holding the bits of m bool columns (kept by the view: every state that fuses the same columns shares it)
 static int packed_column(const msc_dataview *view, const void *const *cols, int m, uint32_t radix, const void **out) {
-  std::vector<const void *> key(cols, cols + m);
-  key.push_back(reinterpret_cast<const void *>((uintptr_t)radix));
-  for (const auto &e : view->packed_bits)
-    if (e.first == key) {
-      *out = e.second;
-      return MSC_OK;
-    }
-  void *dst = nullptr;
-  MSC_HIP(hipMalloc(&dst, std::max<size_t>(1, (size_t)view->nrows)));
-  view->owned_lazy.push_back(dst);
+  std::vector<uint64_t> key = pointer_key(cols, m);
+  key.push_back(radix);
+  if ((*out = view_copy(view, msc_dataview::kPackedBits, key))) return MSC_OK;
+  DevBuf<uint8_t> dst;
+  MSC_HIP(dst.alloc(view->nrows, 1));
   if (launch_pack_bits(view->ctx->stream, cols, m, radix, view->nrows, dst)) return fail(MSC_EHIP, "k_pack_bits launch failed");
-  view->packed_bits.emplace_back(key, dst);
-  *out = dst;
+  *out = view_copy_add(view, msc_dataview::kPackedBits, std::move(key), std::move(dst));
   return MSC_OK;
 }
 
@@ -882,31 +854,26 @@ static int packed_column(const msc_dataview *view, const void *const *cols, int 
 // the other need neither (the copies are an optimisation, never a reason for a call to fail).
 constexpr size_t kViewPackCap = 8;
 static bool nich_x_matrix(const msc_dataview *view, const std::vector<const void *> &cols, const float **out) {
-  for (const auto &e : view->nich_x)
-    if (e.first == cols) {
-      *out = e.second;
-      return true;
-    }
-  if (view->nich_x.size() >= kViewPackCap) return false;
+  std::vector<uint64_t> key = pointer_key(cols.data(), cols.size());
+  if ((*out = static_cast<const float *>(view_copy(view, msc_dataview::kNichX, key)))) return true;
+  if (view_copies(view, msc_dataview::kNichX) >= kViewPackCap) return false;
   const uint32_t n2 = (uint32_t)cols.size(), n2p = (n2 + 3u) & ~3u;
-  void *dst = nullptr, *ptrs = nullptr;
-  if (hipMalloc(&dst, std::max<size_t>(16, (size_t)view->nrows * n2p * sizeof(float))) != hipSuccess) {
+  DevBuf<uint8_t> dst;
+  if (dst.alloc((size_t)view->nrows * n2p * sizeof(float), 16) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
-  bool ok = hipMalloc(&ptrs, sizeof(void *) * n2) == hipSuccess;
+  DevBuf<const float *> ptrs;
+  bool ok = ptrs.alloc(n2) == hipSuccess;
   ok = ok && hipMemcpyAsync(ptrs, cols.data(), sizeof(void *) * n2, hipMemcpyHostToDevice, view->ctx->stream) == hipSuccess;
-  ok = ok && launch_pack_nich_x(view->ctx->stream, static_cast<const float *const *>(ptrs), n2, n2p, view->nrows, static_cast<float *>(dst)) == 0;
+  ok = ok && launch_pack_nich_x(view->ctx->stream, ptrs, n2, n2p, view->nrows, reinterpret_cast<float *>(dst.get())) == 0;
   ok = (hipStreamSynchronize(view->ctx->stream) == hipSuccess) && ok;      // (`cols` is the caller's, `ptrs` this function's)
-  if (ptrs != nullptr) (void)hipFree(ptrs);
+  ptrs.reset();
   if (!ok) {
     (void)hipGetLastError();
-    (void)hipFree(dst);
     return false;
   }
-  view->owned_lazy.push_back(dst);
-  view->nich_x.emplace_back(cols, static_cast<const float *>(dst));
-  *out = static_cast<const float *>(dst);
+  *out = static_cast<const float *>(view_copy_add(view, msc_dataview::kNichX, std::move(key), std::move(dst)));
   return true;
 }
 
@@ -933,31 +900,26 @@ static bool look_idx_matrix(const msc_dataview *view, std::vector<FeatDesc> &tf,
     f0 = f1;
   }
   *l4_out = l4;
-  for (const auto &e : view->look_idx)
-    if (e.first == key) {
-      *out = e.second;
-      return true;
-    }
-  if (view->look_idx.size() >= kViewPackCap || split == 0) return false;
-  void *dst = nullptr, *srcs = nullptr;
-  if (hipMalloc(&dst, ((size_t)view->nrows * l4 + 4u) * sizeof(uint32_t)) != hipSuccess) {
+  if ((*out = static_cast<const uint32_t *>(view_copy(view, msc_dataview::kLookIdx, key)))) return true;
+  if (view_copies(view, msc_dataview::kLookIdx) >= kViewPackCap || split == 0) return false;
+  DevBuf<uint8_t> dst;
+  if (dst.alloc(((size_t)view->nrows * l4 + 4u) * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
-  bool ok = hipMalloc(&srcs, sizeof(LookIdxSrc) * split) == hipSuccess;
+  uint32_t *const idx = reinterpret_cast<uint32_t *>(dst.get());
+  DevBuf<LookIdxSrc> srcs;
+  bool ok = srcs.alloc(split) == hipSuccess;
   ok = ok && hipMemcpyAsync(srcs, src.data(), sizeof(LookIdxSrc) * split, hipMemcpyHostToDevice, view->ctx->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(static_cast<uint32_t *>(dst) + (size_t)view->nrows * l4, 0, 4u * sizeof(uint32_t), view->ctx->stream) == hipSuccess;
-  ok = ok && launch_pack_look_idx(view->ctx->stream, static_cast<const LookIdxSrc *>(srcs), split, l4, view->nrows, static_cast<uint32_t *>(dst)) == 0;
+  ok = ok && hipMemsetAsync(idx + (size_t)view->nrows * l4, 0, 4u * sizeof(uint32_t), view->ctx->stream) == hipSuccess;
+  ok = ok && launch_pack_look_idx(view->ctx->stream, srcs, split, l4, view->nrows, idx) == 0;
   ok = (hipStreamSynchronize(view->ctx->stream) == hipSuccess) && ok;
-  if (srcs != nullptr) (void)hipFree(srcs);
+  srcs.reset();
   if (!ok) {
     (void)hipGetLastError();
-    (void)hipFree(dst);
     return false;
   }
-  view->owned_lazy.push_back(dst);
-  view->look_idx.emplace_back(key, static_cast<const uint32_t *>(dst));
-  *out = static_cast<const uint32_t *>(dst);
+  *out = static_cast<const uint32_t *>(view_copy_add(view, msc_dataview::kLookIdx, std::move(key), std::move(dst)));
   return true;
 }
 
@@ -1074,7 +1036,7 @@ static int plan_groups(msc_state *st) {
       left -= m;
     }
   }
-  MSC_TRY(grow(st, st->fuse_tab, st->fuse_tab_floats, quads.size() * 32 * (size_t)st->kpad));
+  MSC_HIP(grow_retained(st->retired, st->fuse_tab, quads.size() * 32 * (size_t)st->kpad));
   std::vector<bool> taken(n, false);
   for (size_t q = 0; q < quads.size(); q++) {
     const Fused &fq = quads[q];
@@ -1254,53 +1216,50 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
   st->n_f64 = n_f64;
   st->nich1 = nfeatures == 1 && st->feats[0].family == MSC_NICH;
   for (const msc_feature_host &h : st->feats) st->has_dm |= h.family == MSC_DM, st->n_niw += h.family == MSC_NIW;
-  int rc;
-  auto bail = [&](int code) { free_all(st->owned); return code; };
-  if ((rc = dev_alloc(st->owned, &st->red_i64, n_i64))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->red_f64, n_f64))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->cnt_u32, kpad))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->logpc, crp_floats(st->kpad)))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->desc_dev, nfeatures))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->desc_tile_dev, nfeatures))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->desc_fuse_dev, nfeatures))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->nich_info, nfeatures))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->rn_pos, (size_t)((nfeatures + 3u) & ~3u)))) return bail(rc);
+  MSC_TRY(alloc_zeroed(st->red_i64, n_i64));
+  MSC_TRY(alloc_zeroed(st->red_f64, n_f64));
+  MSC_TRY(alloc_zeroed(st->cnt_u32, kpad));
+  MSC_TRY(alloc_zeroed(st->logpc, crp_floats(st->kpad)));
+  MSC_TRY(alloc_zeroed(st->desc_dev, nfeatures));
+  MSC_TRY(alloc_zeroed(st->desc_tile_dev, nfeatures));
+  MSC_TRY(alloc_zeroed(st->desc_fuse_dev, nfeatures));
+  MSC_TRY(alloc_zeroed(st->nich_info, nfeatures));
+  MSC_TRY(alloc_zeroed(st->rn_pos, (size_t)((nfeatures + 3u) & ~3u)));
   {
     size_t nnich = 0;
     for (uint32_t f = 0; f < nfeatures; f++) nnich += features[f].family == MSC_NICH;
-    if ((rc = dev_alloc(st->owned, &st->rn_pack, (1 + kNichPackRows * nnich) * (size_t)kpad))) return bail(rc);
+    MSC_TRY(alloc_zeroed(st->rn_pack, (1 + kNichPackRows * nnich) * (size_t)kpad));
   }
-  if ((rc = dev_alloc(st->owned, &st->desc_acc_dev, nfeatures))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->rng_dev, 2))) return bail(rc);
-  if ((rc = dev_alloc(st->owned, &st->colmax_dev, 1))) return bail(rc);
+  MSC_TRY(alloc_zeroed(st->desc_acc_dev, nfeatures));
+  MSC_TRY(alloc_zeroed(st->rng_dev, 2));
+  MSC_TRY(alloc_zeroed(st->colmax_dev, 1));
   for (uint32_t f = 0; f < nfeatures; f++) {
     msc_feature_host &h = st->feats[f];
     default_hp(h.family, h.dim, h.hp);
-    if ((rc = dev_alloc(st->owned, &h.hp_dev, h.hp.size()))) return bail(rc);
-    if ((rc = dev_alloc(st->owned, &h.tab, (size_t)(tab_rows(h.family, h.dim) + 4) * kpad))) return bail(rc);   // +4: stage_table1 copies 4 rows per instruction
-    if ((rc = dev_alloc(st->owned, &h.raw_u32, (size_t)raw_u32_rows(h.family, h.dim) * kpad))) return bail(rc);
+    MSC_TRY(alloc_zeroed(h.hp_dev, h.hp.size()));
+    MSC_TRY(alloc_zeroed(h.tab, (size_t)(tab_rows(h.family, h.dim) + 4) * kpad));   // +4: stage_table1 copies 4 rows per instruction
+    MSC_TRY(alloc_zeroed(h.raw_u32, (size_t)raw_u32_rows(h.family, h.dim) * kpad));
     const size_t nf32 = h.family == MSC_NIW ? (size_t)ngroups * (h.dim + (size_t)h.dim * h.dim)
                                             : (size_t)raw_f32_rows(h.family) * kpad;
-    if ((rc = dev_alloc(st->owned, &h.raw_f32, nf32))) return bail(rc);
-    if (loo_rows(h.family) && (rc = dev_alloc(st->owned, &h.loo64, (size_t)loo_rows(h.family) * kpad))) return bail(rc);
-    if (loo_tab_rows(h.family, h.dim) &&
-        (rc = dev_alloc(st->owned, &h.loo_tab, (size_t)loo_tab_rows(h.family, h.dim) * kpad))) return bail(rc);
+    MSC_TRY(alloc_zeroed(h.raw_f32, nf32));
+    if (loo_rows(h.family)) MSC_TRY(alloc_zeroed(h.loo64, (size_t)loo_rows(h.family) * kpad));
+    if (loo_tab_rows(h.family, h.dim)) MSC_TRY(alloc_zeroed(h.loo_tab, (size_t)loo_tab_rows(h.family, h.dim) * kpad));
     if (h.family == MSC_DM) {
-      if ((rc = dev_alloc(st->owned, &h.dm_meta_dev, 2 * ((size_t)h.dim + 1)))) return bail(rc);
+      MSC_TRY(alloc_zeroed(h.dm_meta_dev, 2 * ((size_t)h.dim + 1)));
       h.dm_meta.assign(2 * ((size_t)h.dim + 1), 0u);
     }
     if (h.family == MSC_NIW) {
       if (h.dim <= (uint32_t)kNiwPad) {                    // operands of the f32 MFMA kernel (MSC_SCORE_NIW_F32), dim <= 32 only
-        if ((rc = dev_alloc(st->owned, &h.niw_w, (size_t)ngroups * kNiwPad * kNiwPad))) return bail(rc);
-        if ((rc = dev_alloc(st->owned, &h.niw_b, (size_t)ngroups * 2 * kNiwPad))) return bail(rc);
+        MSC_TRY(alloc_zeroed(h.niw_w, (size_t)ngroups * kNiwPad * kNiwPad));
+        MSC_TRY(alloc_zeroed(h.niw_b, (size_t)ngroups * 2 * kNiwPad));
       }
-      if ((rc = dev_alloc(st->owned, &h.niw_w64, (size_t)ngroups * niw_w_stream(h.dim)))) return bail(rc);
-      if ((rc = dev_alloc(st->owned, &h.niw_mu64, (size_t)ngroups * niw_b_stream(h.dim)))) return bail(rc);
-      if ((rc = dev_alloc(st->owned, &h.niw_c64, (size_t)ngroups * 8))) return bail(rc);
+      MSC_TRY(alloc_zeroed(h.niw_w64, (size_t)ngroups * niw_w_stream(h.dim)));
+      MSC_TRY(alloc_zeroed(h.niw_mu64, (size_t)ngroups * niw_b_stream(h.dim)));
+      MSC_TRY(alloc_zeroed(h.niw_c64, (size_t)ngroups * 8));
     }
     if (!h.hp.empty()) {
       hipError_t e = hipMemcpy(h.hp_dev, h.hp.data(), h.hp.size() * sizeof(float), hipMemcpyHostToDevice);
-      if (e != hipSuccess) return bail(fail(MSC_EHIP, "hp upload failed: %s", hipGetErrorString(e)));
+      if (e != hipSuccess) return fail(MSC_EHIP, "hp upload failed: %s", hipGetErrorString(e));
     }
     h.raw_valid = true;
     h.additive_valid = true;   // both all-zero
@@ -1329,24 +1288,19 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
     for (float a : h.hp) d.aux += h.family == MSC_DD || h.family == MSC_DM ? (double)a : 0.0;
   }
   st->cnt_additive_valid = true;
-  if ((rc = upload_desc(st.get()))) return bail(rc);
+  MSC_TRY(upload_desc(st.get()));
   hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return bail(fail(MSC_EHIP, "state init failed: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(MSC_EHIP, "state init failed: %s", hipGetErrorString(e));
   *out = st.release();
   return MSC_OK;
 }
-
-static void hp_state_release(msc_state *st);
-static void pred_state_release(msc_state *st);
 
 extern "C" int msc_state_destroy(msc_state *st) {
   if (!st) return MSC_OK;
   (void)hipSetDevice(st->ctx->device);
   (void)hipStreamSynchronize(st->ctx->stream);
   if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
-  hp_state_release(st);
-  pred_state_release(st);
-  free_all(st->owned);
+  if (st->pred_upload) (void)hipEventDestroy(st->pred_upload);
   delete st;
   return MSC_OK;
 }
@@ -1559,17 +1513,11 @@ static int column_as(const msc_dataview *view, uint32_t c, int want, bool make, 
     *out = view->cols[c];
     return MSC_OK;
   }
-  if (view->converted.size() < view->cols.size()) view->converted.resize(view->cols.size());
-  for (const auto &e : view->converted[c])
-    if (e.first == want) {
-      *out = e.second;
-      return MSC_OK;
-    }
-  if (!make) return MSC_OK;
+  std::vector<uint64_t> key{c, (uint64_t)want};
+  if ((*out = view_copy(view, msc_dataview::kConverted, key)) || !make) return MSC_OK;
   hipStream_t s = view->ctx->stream;
-  void *dst = nullptr;
-  MSC_HIP(hipMalloc(&dst, std::max<size_t>(1, (size_t)view->nrows * t.count * primitive_size(want))));
-  view->owned_lazy.push_back(dst);
+  DevBuf<uint8_t> dst;
+  MSC_HIP(dst.alloc((size_t)view->nrows * t.count * primitive_size(want), 1));
   if (view->nrows > 0) {
     UnpackFeat uf{};
     uf.dst = dst;
@@ -1579,18 +1527,17 @@ static int column_as(const msc_dataview *view, uint32_t c, int want, bool make, 
     uf.src_type = t.type;
     uf.dst_type = want;
     uf.count = t.count;
-    void *uf_dev = nullptr;
-    MSC_HIP(hipMalloc(&uf_dev, sizeof uf));
+    DevBuf<UnpackFeat> uf_dev;
+    MSC_HIP(uf_dev.alloc(1));
     hipError_t e = hipMemcpyAsync(uf_dev, &uf, sizeof uf, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && launch_unpack(s, static_cast<const uint8_t *>(view->cols[c]), nullptr, view->nrows,
                                          (uint32_t)(primitive_size(t.type) * t.count), 0, uf_dev, 1))
       e = hipErrorLaunchFailure;
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(uf_dev);
+    const hipError_t w = hipStreamSynchronize(s);       // (also before the buffers go on a failure)
+    if (e == hipSuccess) e = w;
     if (e != hipSuccess) return fail(MSC_EHIP, "column conversion failed: %s", hipGetErrorString(e));
   }
-  view->converted[c].emplace_back(want, dst);
-  *out = dst;
+  *out = view_copy_add(view, msc_dataview::kConverted, std::move(key), std::move(dst));
   return MSC_OK;
 }
 
@@ -1598,20 +1545,13 @@ static int column_as(const msc_dataview *view, uint32_t c, int want, bool make, 
 // column as the model's value type (column_as); made once per (column, element type, sentinel), kept with the view.
 static int sentinel_column(const msc_dataview *view, uint32_t c, const void *col, bool bytes, uint32_t sentinel, const void **out) {
   *out = nullptr;
-  if (view->sentinels.size() < view->cols.size()) view->sentinels.resize(view->cols.size());
-  const std::pair<int, uint32_t> key(bytes ? 1 : 4, sentinel);
-  for (const auto &e : view->sentinels[c])
-    if (e.first == key) {
-      *out = e.second;
-      return MSC_OK;
-    }
-  void *dst = nullptr;
-  MSC_HIP(hipMalloc(&dst, std::max<size_t>(1, (size_t)view->nrows * (bytes ? 1 : 4))));
-  view->owned_lazy.push_back(dst);
+  std::vector<uint64_t> key{c, bytes ? 1u : 4u, sentinel};
+  if ((*out = view_copy(view, msc_dataview::kSentinel, key))) return MSC_OK;
+  DevBuf<uint8_t> dst;
+  MSC_HIP(dst.alloc((size_t)view->nrows * (bytes ? 1 : 4), 1));
   if (launch_mask_sentinel(view->ctx->stream, col, static_cast<const uint8_t *>(view->masks[c]), view->nrows, bytes, sentinel, dst))
     return fail(MSC_EHIP, "k_mask_sentinel launch failed");
-  view->sentinels[c].emplace_back(key, dst);
-  *out = dst;
+  *out = view_copy_add(view, msc_dataview::kSentinel, std::move(key), std::move(dst));
   return MSC_OK;
 }
 
@@ -1623,22 +1563,25 @@ static int bind_dm_column(msc_state *st, uint32_t f, const msc_dataview *view, u
   if (view->dm_max[c].empty()) {
     std::vector<uint32_t> mx(nst, 0u);
     if (view->nrows > 0) {
-      void *tmp = nullptr, *tot = nullptr;
-      MSC_HIP(hipMalloc(&tmp, sizeof(uint32_t) * nst));
-      view->owned_lazy.push_back(tmp);
-      MSC_HIP(hipMalloc(&tot, sizeof(uint32_t) * view->nrows));
-      view->owned_lazy.push_back(tot);
-      view->dm_tot[c] = static_cast<uint32_t *>(tot);
-      MSC_HIP(hipMemsetAsync(tmp, 0, sizeof(uint32_t) * nst, s));
-      if (launch_dm_stats(s, static_cast<const uint32_t *>(d.col), view->nrows, h.dim,
-                          static_cast<uint32_t *>(tmp), view->dm_tot[c]))
-        return fail(MSC_EHIP, "k_dm_stats launch failed");
-      MSC_HIP(hipMemcpyAsync(mx.data(), tmp, sizeof(uint32_t) * nst, hipMemcpyDeviceToHost, s));
-      MSC_HIP(hipStreamSynchronize(s));
+      DevBuf<uint8_t> tmp, tot;
+      MSC_HIP(tmp.alloc(sizeof(uint32_t) * nst));
+      MSC_HIP(tot.alloc(sizeof(uint32_t) * view->nrows));
+      uint32_t *const tmp32 = reinterpret_cast<uint32_t *>(tmp.get()), *const tot32 = reinterpret_cast<uint32_t *>(tot.get());
+      hipError_t e = hipMemsetAsync(tmp32, 0, sizeof(uint32_t) * nst, s);
+      int rc = e == hipSuccess ? MSC_OK : fail(MSC_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+      if (rc == MSC_OK && launch_dm_stats(s, static_cast<const uint32_t *>(d.col), view->nrows, h.dim, tmp32, tot32))
+        rc = fail(MSC_EHIP, "k_dm_stats launch failed");
+      if (rc == MSC_OK && (e = hipMemcpyAsync(mx.data(), tmp32, sizeof(uint32_t) * nst, hipMemcpyDeviceToHost, s)))
+        rc = fail(MSC_EHIP, "hipMemcpyAsync: %s", hipGetErrorString(e));
+      e = hipStreamSynchronize(s);                      // (also before the buffers go on a failure)
+      if (rc == MSC_OK && e != hipSuccess) rc = fail(MSC_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+      MSC_TRY(rc);
+      view_copy_add(view, msc_dataview::kDmMax, {c}, std::move(tmp));
+      view_copy_add(view, msc_dataview::kDmTot, {c}, std::move(tot));
     }
     view->dm_max[c] = mx;
   }
-  d.dm_tot = view->dm_tot[c];
+  d.dm_tot = static_cast<const uint32_t *>(view_copy(view, msc_dataview::kDmTot, {c}));
   std::vector<uint32_t> meta(2 * (size_t)nst);
   uint32_t rows = 0;
   for (uint32_t i = 0; i < nst; i++) {
@@ -1649,18 +1592,16 @@ static int bind_dm_column(msc_state *st, uint32_t f, const msc_dataview *view, u
   }
   d.dm_rows = rows;
   if (meta != h.dm_meta || d.dm_meta == nullptr) {
-    if ((size_t)rows + 4 > h.tab_rows_cap || h.loo64 == nullptr) {   // grow the table buffers (the old ones stay owned until destroy)
-      float *t = nullptr;
-      MSC_TRY(dev_alloc(st->owned, &t, ((size_t)rows + 4) * st->kpad));
-      h.tab = t;
-      h.tab_rows_cap = (size_t)rows + 4;
-      d.tab = t;
+    // grow the table buffers, zeroed (rows is even: when the table grows, so does its twin below)
+    if (((size_t)rows + 4) * st->kpad > h.tab.size() || h.loo64 == nullptr) {
+      MSC_HIP(grow_retained(st->retired, h.tab, ((size_t)rows + 4) * st->kpad));
+      MSC_HIP(hipMemset(h.tab, 0, h.tab.size() * sizeof(float)));
+      d.tab = h.tab;
       // the leave-one-out twin of the tables ("count v against the group minus v"), one double per entry: read by
       // k_loo_own only, once per row and stage
-      double *l = nullptr;
-      MSC_TRY(dev_alloc(st->owned, &l, ((size_t)rows / 2 + 1) * st->kpad));
-      h.loo64 = l;
-      d.loo64 = l;
+      MSC_HIP(grow_retained(st->retired, h.loo64, ((size_t)rows / 2 + 1) * st->kpad));
+      MSC_HIP(hipMemset(h.loo64, 0, h.loo64.size() * sizeof(double)));
+      d.loo64 = h.loo64;
     }
     h.dm_meta = meta;
     MSC_HIP(hipMemcpyAsync(h.dm_meta_dev, h.dm_meta.data(), sizeof(uint32_t) * meta.size(), hipMemcpyHostToDevice, s));
@@ -1828,7 +1769,7 @@ static int tail_plan(msc_state *st, TailPlan &tp, bool exact = true) {
   tp.cost = st->plan_cost;
   tp.exact = exact;
   if (!st->tile_narrow_tail_ok || st->K - (st->kpad - kGroupTile) > kTailMaxGroups) return MSC_OK;
-  MSC_TRY(grow(st, st->tail_pack, st->tail_pack_floats, (size_t)st->tail_pack_rows * 64));
+  MSC_HIP(grow_retained(st->retired, st->tail_pack, (size_t)st->tail_pack_rows * 64));
   tp.ok = true;
   tp.masked_nich = st->tail_masked_nich;
   tp.dm = st->tail_dm;
@@ -1860,7 +1801,7 @@ static bool loo_needs_heavy(const msc_state *st) {
 
 // every row's leave-one-out value (its own group's score, the prior's when crp) into st->own
 static int run_loo_own(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z, bool crp) {
-  MSC_TRY(grow(st, st->own, st->own_cap, nrows));
+  MSC_HIP(grow_retained(st->retired, st->own, nrows));
   if (launch_loo_own(st->ctx->stream, st->ctx->num_cus, loo_needs_heavy(st), st->loo_staged != 0, st->desc_tile_dev, (int)st->nfeat,
                      st->K, st->kpad, row0, nrows, z, crp ? st->logpc : nullptr, st->own))
     return fail(MSC_EHIP, "k_loo_own launch failed");
@@ -1986,7 +1927,7 @@ static int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t
   }
   for (uint32_t f = 0; f < st->nfeat; f++) {
     if (st->feats[f].family != MSC_NIW) continue;
-    if (z_dev) MSC_TRY(grow(st, st->niw_qown, st->niw_qown_cap, nrows));   // leave-one-out: the score kernel parks q of the own group here
+    if (z_dev) MSC_HIP(grow_retained(st->retired, st->niw_qown, nrows));   // leave-one-out: the score kernel parks q of the own group here
     if (launch_niw_score(s, st->ctx->num_cus, st->desc_dev, f, st->feats[f].dim, st->K, st->kpad, row0, nrows, z_dev, written,
                          niw_f32, st->niw_qown, out_dev, ld_out))
       return fail(MSC_EHIP, "k_score_niw launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -2146,7 +2087,7 @@ static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32
     for (uint32_t f = 0; f < st->nfeat; f++) {
       if (st->feats[f].family != MSC_NIW) continue;
       MSC_REQUIRE(nrows < (1ull << 32), "niw accumulate takes at most 2^32 - 1 rows per call");
-      MSC_TRY(grow(st, st->niw_scratch, st->niw_scratch_len, 2 * (size_t)st->K + 1 + (size_t)nrows));
+      MSC_HIP(grow_retained(st->retired, st->niw_scratch, 2 * (size_t)st->K + 1 + (size_t)nrows));
       if (launch_niw_accumulate(s, st->ctx->num_cus, st->desc_dev, f, st->K, row0, nrows, z_dev,
                                 (flags & MSC_ACC_SUBTRACT) ? -1 : 1, st->niw_scratch, st->feats[f].dim))
         return fail(MSC_EHIP, "niw accumulate launch failed");
@@ -2182,7 +2123,7 @@ extern "C" int msc_entity_op(msc_state *st, const msc_dataview *view, const uint
   for (const auto &h : st->feats) scalar_only &= h.family != MSC_NIW && h.family != MSC_DM;
   if (!scalar_only) {
     // general path: the group travels through a one-entry assignment vector of the state's own
-    if (!st->one_z) MSC_TRY(dev_alloc(st->owned, &st->one_z, 1));
+    if (!st->one_z) MSC_TRY(alloc_zeroed(st->one_z, 1));
     if (launch_set_i32(s, st->one_z, (int32_t)group)) return fail(MSC_EHIP, "k_set_i32 launch failed");
     MSC_TRY(accumulate_impl(st, view, cols, row, 1, st->one_z, sign < 0 ? (uint32_t)MSC_ACC_SUBTRACT : 0u));
     if (z_dev && launch_set_i32(s, z_dev + row, sign > 0 ? (int32_t)group : -1)) return fail(MSC_EHIP, "k_set_i32 launch failed");
@@ -2330,8 +2271,8 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
   const int cus = st->ctx->num_cus;
   ZeroSpans zero;
   if (zeroed) {
-    zero.a = reinterpret_cast<unsigned long long *>(st->red_i64); zero.na = st->n_i64;
-    zero.b = reinterpret_cast<unsigned long long *>(st->red_f64); zero.nb = st->n_f64;
+    zero.a = reinterpret_cast<unsigned long long *>(st->red_i64.get()); zero.na = st->n_i64;
+    zero.b = reinterpret_cast<unsigned long long *>(st->red_f64.get()); zero.nb = st->n_f64;
   }
   const SweepRoute r = route_sweep(st);
   int rc = 0;
@@ -2342,7 +2283,7 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
       rc = launch_sweep_niw1(s, cus, st->feats[0].dim, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero);
       break;
     case SweepKind::nich1_rows:
-      MSC_TRY(grow(st, st->rows_table, st->rows_table_floats, sweep_nich1_rows_table_floats(st->kpad)));
+      MSC_HIP(grow_retained(st->retired, st->rows_table, sweep_nich1_rows_table_floats(st->kpad)));
       rc = launch_sweep_nich1_rows(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero, st->rows_table);
       break;
     case SweepKind::nich1:                                // (the single-nich kernel computes the own-group values itself)
@@ -2366,7 +2307,7 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
           rc = launch_sweep_rows(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0,
                                  z_dev, st->own, st->logpc, st->rng_dev, zero);
         } else {
-          MSC_TRY(grow(st, st->tail_scores, st->tail_floats, ((size_t)nrows + 16) * 128));
+          MSC_HIP(grow_retained(st->retired, st->tail_scores, ((size_t)nrows + 16) * 128));
           rc = launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, 0, row0, nrows,
                                  z_dev, st->own, st->logpc, st->tail_scores, 128);
           if (rc == 0) {
@@ -2381,7 +2322,7 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
     case SweepKind::roles_tail: {
       MSC_TRY(refresh_fused_tables(st));
       MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
-      MSC_TRY(grow(st, st->tail_scores, st->tail_floats, ((size_t)nrows + 16) * r.tail_ld));
+      MSC_HIP(grow_retained(st->retired, st->tail_scores, ((size_t)nrows + 16) * r.tail_ld));
       // (the kernel stores at out + row * ld + k: handing it tail_scores - 256 puts group 256 + j at column j; one sum per
       // group: nothing else scores these groups for a draw)
       TailPlan tail;
@@ -2417,7 +2358,7 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
     uint64_t chunk = ((forced_mib ? forced_mib : 4096ull) << 20) / (ld * sizeof(float));
     if (chunk == 0) chunk = 1;
     if (chunk > nrows) chunk = nrows;
-    MSC_TRY(grow(st, st->scratch, st->scratch_floats, chunk * ld));
+    MSC_HIP(grow_retained(st->retired, st->scratch, chunk * ld));
     for (uint64_t at = 0; at < nrows; at += chunk) {
       const uint64_t n = std::min<uint64_t>(chunk, nrows - at);
       MSC_TRY(run_score(st, row0 + at, n, z_dev + at, true, false, st->scratch, ld));
@@ -2691,7 +2632,7 @@ extern "C" int msc_state_reduce_buffers(msc_state *st, void **dev_i64, size_t *n
 extern "C" int msc_state_reduce_pack(msc_state *st, void **pack_dev, size_t *n_f64) {
   MSC_REQUIRE(st && pack_dev, "null argument");
   MSC_HIP(hipSetDevice(st->ctx->device));
-  if (!st->red_pack) MSC_TRY(dev_alloc(st->owned, &st->red_pack, st->n_i64 + st->n_f64));
+  if (!st->red_pack) MSC_TRY(alloc_zeroed(st->red_pack, st->n_i64 + st->n_f64));
   if (launch_pack64(st->ctx->stream, false, st->red_i64, st->n_i64, st->red_f64, st->n_f64, st->red_pack))
     return fail(MSC_EHIP, "k_pack64 launch failed");
   *pack_dev = st->red_pack;
@@ -2807,7 +2748,7 @@ extern "C" int msc_value_op_single(msc_context *ctx, int family, uint32_t dim, i
   hd.hp_off = 64;
   hd.ss_off = (uint32_t)up16(hd.hp_off + hp_bytes);
   hd.value_off = (uint32_t)up16(hd.ss_off + ss_bytes);
-  MSC_REQUIRE(hd.value_off + v_bytes <= ctx->mailbox_bytes, "record too large for the mailbox");
+  MSC_REQUIRE(hd.value_off + v_bytes <= ctx->mailbox_host.size(), "record too large for the mailbox");
   if (family == MSC_DD && host_value && op != MSC_OP_SCORE_DATA) {
     int32_t v;
     std::memcpy(&v, host_value, 4);
@@ -2841,44 +2782,11 @@ extern "C" int msc_value_op_single(msc_context *ctx, int family, uint32_t dim, i
 // ---------------------------------------------------------------------------
 // grid hyper-parameter inference (kernels_hp.hip)
 // ---------------------------------------------------------------------------
-static void hp_grid_free(msc_hp_grid *g) {
-  (void)hipFree(g->grid_dev);
-  (void)hipFree(g->logprior_dev);
-  (void)hipFree(g->job_dev);
-  delete g;
-}
-
-// a device buffer of at least n elements; a smaller one is freed first (after the stream is idle: an earlier
-// asynchronous call may still read it)
-template <typename T>
-static int hp_reserve(msc_state *st, T **buf, size_t &cap, size_t n) {
-  if (n <= cap && *buf) return MSC_OK;
-  MSC_HIP(hipStreamSynchronize(st->ctx->stream));
-  (void)hipFree(*buf);
-  *buf = nullptr;
-  cap = 0;
-  void *p = nullptr;
-  MSC_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-  *buf = static_cast<T *>(p);
-  cap = n;
-  return MSC_OK;
-}
-
 // group blocks of a score launch: enough workgroups for a few per CU, at least one LDS stage of slots per block
 static uint32_t hp_group_blocks(const msc_state *st, size_t point_blocks) {
   const uint32_t stages = (st->K + 63) / 64;
   const size_t want = (4 * (size_t)st->ctx->num_cus + point_blocks - 1) / point_blocks;
   return (uint32_t)std::max<size_t>(1, std::min<size_t>(stages, want));
-}
-
-static void hp_state_release(msc_state *st) {
-  for (msc_hp_grid *g : st->hp_grids) hp_grid_free(g);
-  st->hp_grids.clear();
-  (void)hipFree(st->hp_part);
-  (void)hipFree(st->hp_out);
-  (void)hipFree(st->hp_jobs_dev);
-  (void)hipFree(st->hp_chosen_dev);
-  (void)hipFree(st->slice_buf);
 }
 
 extern "C" int msc_hp_grid_create(msc_state *st, uint32_t feature, const float *host_blocks, size_t block_floats,
@@ -2912,26 +2820,26 @@ extern "C" int msc_hp_grid_create(msc_state *st, uint32_t feature, const float *
   job.hpf = (uint32_t)block_floats;
   job.npoints = npoints;
   MSC_HIP(hipSetDevice(st->ctx->device));
-  std::unique_ptr<msc_hp_grid, void (*)(msc_hp_grid *)> g(new (std::nothrow) msc_hp_grid(), hp_grid_free);
+  std::unique_ptr<msc_hp_grid> g(new (std::nothrow) msc_hp_grid());
   if (!g) return fail(MSC_ENOMEM, "out of host memory");
   g->st = st;
   g->feature = feature;
   g->blocks.assign(host_blocks, host_blocks + (size_t)npoints * block_floats);
   const hipStream_t s = st->ctx->stream;
-  MSC_HIP(hipMalloc(reinterpret_cast<void **>(&g->grid_dev), g->blocks.size() * sizeof(float)));
+  MSC_HIP(g->grid_dev.alloc(g->blocks.size()));
   MSC_HIP(hipMemcpyAsync(g->grid_dev, g->blocks.data(), g->blocks.size() * sizeof(float), hipMemcpyHostToDevice, s));
   if (host_logprior) {
-    MSC_HIP(hipMalloc(reinterpret_cast<void **>(&g->logprior_dev), (size_t)npoints * sizeof(double)));
+    MSC_HIP(g->logprior_dev.alloc(npoints));
     MSC_HIP(hipMemcpyAsync(g->logprior_dev, host_logprior, (size_t)npoints * sizeof(double), hipMemcpyHostToDevice, s));
   }
   job.grid = g->grid_dev;
   job.logprior = g->logprior_dev;
   g->job = job;
-  MSC_HIP(hipMalloc(reinterpret_cast<void **>(&g->job_dev), sizeof(HpJob)));
+  MSC_HIP(g->job_dev.alloc(1));
   MSC_HIP(hipMemcpyAsync(g->job_dev, &g->job, sizeof(HpJob), hipMemcpyHostToDevice, s));
   MSC_HIP(hipStreamSynchronize(s));
-  st->hp_grids.push_back(g.get());
-  *out = g.release();
+  *out = g.get();
+  st->hp_grids.push_back(std::move(g));
   return MSC_OK;
 }
 
@@ -2940,8 +2848,9 @@ extern "C" int msc_hp_grid_destroy(msc_hp_grid *grid) {
   msc_state *st = grid->st;
   (void)hipSetDevice(st->ctx->device);
   (void)hipStreamSynchronize(st->ctx->stream);
-  st->hp_grids.erase(std::remove(st->hp_grids.begin(), st->hp_grids.end(), grid), st->hp_grids.end());
-  hp_grid_free(grid);
+  st->hp_grids.erase(std::remove_if(st->hp_grids.begin(), st->hp_grids.end(),
+                                    [grid](const std::unique_ptr<msc_hp_grid> &g) { return g.get() == grid; }),
+                     st->hp_grids.end());   // (the state owns its grids: this deletes it)
   return MSC_OK;
 }
 
@@ -2959,7 +2868,7 @@ extern "C" int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, do
     return MSC_OK;
   }
   const uint32_t nblk = hp_group_blocks(st, (np + 255) / 256);
-  MSC_TRY(hp_reserve(st, &st->hp_part, st->hp_part_cap, (size_t)nblk * np));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_part, (size_t)nblk * np));
   if (launch_hp_grid_score(st->ctx->stream, grid->job_dev, 1, np, st->K, st->kpad, st->cnt_u32, slots_dev, nblk,
                            st->hp_part, out_dev))
     return fail(MSC_EHIP, "k_hp_grid_score launch failed");
@@ -3038,10 +2947,10 @@ extern "C" int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint3
   }
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(ensure_raw(st));
-  MSC_TRY(hp_reserve(st, &st->hp_part, st->hp_part_cap, part));
-  MSC_TRY(hp_reserve(st, &st->hp_out, st->hp_out_cap, out));
-  MSC_TRY(hp_reserve(st, &st->hp_jobs_dev, st->hp_jobs_cap, n));
-  MSC_TRY(hp_reserve(st, &st->hp_chosen_dev, st->hp_chosen_cap, n));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_part, part));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_out, out));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_jobs_dev, n));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_chosen_dev, n));
   const hipStream_t s = st->ctx->stream;
   MSC_HIP(hipMemcpyAsync(st->hp_jobs_dev, jobs.data(), n * sizeof(HpJob), hipMemcpyHostToDevice, s));
   if (nfj && launch_hp_grid_score(s, st->hp_jobs_dev, nfj, (uint32_t)max_np, st->K, st->kpad, st->cnt_u32, slots_dev, nblk,
@@ -3171,7 +3080,7 @@ extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32
   const size_t o_ev = o_val + slice_align(n * 4), o_stat = o_ev + slice_align(n * 4), total = o_stat + slice_align(n * 4);
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(ensure_raw(st));
-  MSC_TRY(hp_reserve(st, &st->slice_buf, st->slice_cap, total));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->slice_buf, total));
   std::vector<unsigned char> up(o_val);
   std::memcpy(up.data(), targets.data(), nt * sizeof(SliceTarget));
   std::memcpy(up.data() + o_coord, dc.data(), n * sizeof(SliceCoord));
@@ -3236,7 +3145,7 @@ extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const fl
   const size_t o_ev = slice_align(n * sizeof(ThetaJob)), o_bad = o_ev + np * 8, total = o_bad + slice_align(np * 4);
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(ensure_raw(st));
-  MSC_TRY(hp_reserve(st, &st->slice_buf, st->slice_cap, total));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->slice_buf, total));
   const hipStream_t s = st->ctx->stream;
   unsigned char *b = st->slice_buf;
   MSC_HIP(hipMemcpyAsync(b, jobs.data(), n * sizeof(ThetaJob), hipMemcpyHostToDevice, s));
@@ -3270,22 +3179,6 @@ extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const fl
 // posterior predictive sampling (group::sample_value, base.hpp:29, for a block of rows; kernels_pred.hip)
 // ---------------------------------------------------------------------------
 static constexpr uint64_t kPredGroupKey = 0xD1B54A32D192ED03ull;   // the group draw's key is seed ^ this
-
-static void pred_state_release(msc_state *st) {
-  (void)hipHostFree(st->pred_stage);
-  if (st->pred_upload) (void)hipEventDestroy(st->pred_upload);
-  st->pred_stage = nullptr;
-  st->pred_upload = nullptr;
-  st->pred_stage_cap = 0;
-  st->pred_feats_host.clear();
-  (void)hipFree(st->pred_feats_dev);
-  (void)hipFree(st->pred_par);
-  (void)hipFree(st->pred_z);
-  st->pred_feats_dev = nullptr;
-  st->pred_par = nullptr;
-  st->pred_z = nullptr;
-  st->pred_feats_cap = st->pred_par_cap = st->pred_z_cap = 0;
-}
 
 extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                                      uint64_t nrows, uint64_t row_id0, const int32_t *z_dev, int32_t *z_out_dev,
@@ -3333,23 +3226,19 @@ extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, co
     par_off.push_back(par_len);
     par_len += (size_t)p.stride * st->K;
   }
-  MSC_TRY(hp_reserve(st, &st->pred_par, st->pred_par_cap, par_len));
-  if (pfs.size() > st->pred_feats_cap || !st->pred_feats_dev) st->pred_feats_host.clear();   // (a new buffer holds nothing)
-  MSC_TRY(hp_reserve(st, &st->pred_feats_dev, st->pred_feats_cap, pfs.size()));
+  MSC_HIP(reserve_synced(st->ctx->stream, st->pred_par, par_len));
+  if (pfs.size() > st->pred_feats_dev.size() || !st->pred_feats_dev) st->pred_feats_host.clear();   // (a new buffer holds nothing)
+  MSC_HIP(reserve_synced(st->ctx->stream, st->pred_feats_dev, pfs.size()));
   for (size_t i = 0; i < pfs.size(); i++) pfs[i].par = st->pred_par + par_off[i];
   // the descriptors go up only when they changed (a loop of calls uploads nothing), from pinned staging memory: the copy
   // reads it when it runs, so the host waits -- for the previous upload only -- before it writes the staging again
   const size_t pbytes = pfs.size() * sizeof(PredFeat);
   if (pbytes && (st->pred_feats_host.size() != pfs.size() ||
                  std::memcmp(st->pred_feats_host.data(), pfs.data(), pbytes) != 0)) {
-    if (st->pred_stage_cap < pfs.size()) {
+    if (st->pred_stage.size() < pfs.size()) {
       if (st->pred_upload_pending) MSC_HIP(hipEventSynchronize(st->pred_upload));
       st->pred_upload_pending = false;
-      (void)hipHostFree(st->pred_stage);
-      st->pred_stage = nullptr;
-      st->pred_stage_cap = 0;
-      MSC_HIP(hipHostMalloc(reinterpret_cast<void **>(&st->pred_stage), pbytes, hipHostMallocDefault));
-      st->pred_stage_cap = pfs.size();
+      MSC_HIP(st->pred_stage.alloc(pfs.size()));   // (frees the smaller one first)
     }
     if (!st->pred_upload) MSC_HIP(hipEventCreateWithFlags(&st->pred_upload, hipEventDisableTiming));
     if (st->pred_upload_pending) MSC_HIP(hipEventSynchronize(st->pred_upload));
@@ -3364,7 +3253,7 @@ extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, co
   // sweep's (seed, sweep) pair on the device is put back afterwards
   const int32_t *z = z_dev;
   if (z == nullptr) {
-    MSC_TRY(hp_reserve(st, &st->pred_z, st->pred_z_cap, nrows));
+    MSC_HIP(reserve_synced(st->ctx->stream, st->pred_z, nrows));
     MSC_HIP(hipMemsetAsync(st->pred_z, 0xff, nrows * sizeof(int32_t), s));
     const bool had = st->rng_valid;
     const uint64_t had_seed = st->rng_seed, had_sweep = st->rng_sweep;
@@ -3387,25 +3276,17 @@ extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, co
 // ---------------------------------------------------------------------------
 // z-matrix accumulator (microscopes.common.query.zmatrix; kernels_query.hip)
 // ---------------------------------------------------------------------------
-static void zmatrix_free(msc_zmatrix *zm) {
-  if (!zm) return;
-  for (void *p : {(void *)zm->rows_dev, (void *)zm->order_dev, (void *)zm->batch, (void *)zm->bad, (void *)zm->counts})
-    if (p) (void)hipFree(p);
-  delete zm;
-}
-
 static size_t zm_count_words(uint32_t nt) { return (size_t)nt * (nt + 1) / 2 * kZmTile * kZmTile; }
 
-// hipMalloc, MSC_ENOMEM (with the footprint) when the device has no room
-static int zm_alloc(void **p, size_t bytes, const char *what, uint32_t m) {
-  const hipError_t e = hipMalloc(p, bytes);
+// the buffer's allocation, MSC_ENOMEM (with the footprint) when the device has no room
+static int zm_alloc(DevBuf<uint32_t> &buf, size_t bytes, const char *what, uint32_t m) {
+  const hipError_t e = buf.alloc(bytes / 4);
   if (e == hipSuccess) return MSC_OK;
   (void)hipGetLastError();
-  *p = nullptr;
   if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
     return fail(MSC_ENOMEM, "msc_zmatrix_create: m = %u needs %zu bytes for the %s (include/microscopes_hip.h gives the "
                 "footprint); the device has no room", m, bytes, what);
-  return fail(MSC_EHIP, "hipMalloc of the %s failed: %s", what, hipGetErrorString(e));
+  return fail(MSC_EHIP, "allocating the %s failed: %s", what, hipGetErrorString(e));
 }
 
 extern "C" int msc_zmatrix_create(msc_context *ctx, uint64_t n, const uint32_t *host_rows, uint32_t m, uint32_t nlabels,
@@ -3424,7 +3305,7 @@ extern "C" int msc_zmatrix_create(msc_context *ctx, uint64_t n, const uint32_t *
     MSC_REQUIRE(rows[a] < n, "msc_zmatrix_create: rows[%u] = %u is not below n = %llu", a, rows[a], (unsigned long long)n);
   }
   MSC_HIP(hipSetDevice(ctx->device));
-  std::unique_ptr<msc_zmatrix, void (*)(msc_zmatrix *)> zm(new (std::nothrow) msc_zmatrix(), zmatrix_free);
+  std::unique_ptr<msc_zmatrix> zm(new (std::nothrow) msc_zmatrix());
   if (!zm) return fail(MSC_ENOMEM, "out of host memory");
   zm->ctx = ctx;
   zm->n = n;
@@ -3434,11 +3315,11 @@ extern "C" int msc_zmatrix_create(msc_context *ctx, uint64_t n, const uint32_t *
   zm->wide = nlabels > 256;
   const size_t batch_bytes = (size_t)zm->nt * kZmTile * kZmBatchWords * 4;
   const size_t count_bytes = zm_count_words(zm->nt) * 4;
-  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->counts), count_bytes, "counts", m));
-  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->batch), batch_bytes, "sample batch", m));
-  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->bad), (kZmBatchMax + 1) * 4, "batch flags", m));
-  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->rows_dev), (size_t)m * 4, "rows", m));
-  MSC_TRY(zm_alloc(reinterpret_cast<void **>(&zm->order_dev), (size_t)m * 4, "order", m));
+  MSC_TRY(zm_alloc(zm->counts, count_bytes, "counts", m));
+  MSC_TRY(zm_alloc(zm->batch, batch_bytes, "sample batch", m));
+  MSC_TRY(zm_alloc(zm->bad, (kZmBatchMax + 1) * 4, "batch flags", m));
+  MSC_TRY(zm_alloc(zm->rows_dev, (size_t)m * 4, "rows", m));
+  MSC_TRY(zm_alloc(zm->order_dev, (size_t)m * 4, "order", m));
   const hipStream_t s = ctx->stream;
   MSC_HIP(hipMemsetAsync(zm->counts, 0, count_bytes, s));
   MSC_HIP(hipMemsetAsync(zm->batch, 0, batch_bytes, s));
@@ -3535,6 +3416,6 @@ extern "C" int msc_zmatrix_destroy(msc_zmatrix *zm) {
   if (!zm) return MSC_OK;
   (void)hipSetDevice(zm->ctx->device);
   (void)hipStreamSynchronize(zm->ctx->stream);
-  zmatrix_free(zm);
+  delete zm;
   return MSC_OK;
 }

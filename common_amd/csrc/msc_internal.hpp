@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/microscopes_hip.h"
+#include "dev_buf.hpp"
 
 namespace msc {
 
@@ -439,12 +440,11 @@ struct msc_context {
   std::vector<float> last_alloc_rates;
   uint32_t last_alloc_chosen = 0;
   // pinned, device-mapped mailbox for msc_value_op_single
-  void *mailbox_host = nullptr;
+  msc::MappedBuf<unsigned char> mailbox_host;
   void *mailbox_dev = nullptr;
-  size_t mailbox_bytes = 0;
   // msc_context_synchronize: a word of pinned memory the stream writes a sequence number into (hipStreamWriteValue32)
   // and the host watches, instead of sleeping in hipStreamSynchronize
-  uint32_t *sync_word_host = nullptr;
+  msc::MappedBuf<uint32_t> sync_word_host;
   void *sync_word_dev = nullptr;
   uint32_t sync_seq = 0;
   bool sync_word_ok = true;                // cleared when the stream operation is refused: plain stream waits from then on
@@ -459,51 +459,65 @@ struct msc_dataview {
   std::vector<msc_runtime_type> types;   // per feature, after conversion
   std::vector<void *> cols;              // device columns
   std::vector<void *> masks;             // device mask columns or null
-  std::vector<void *> owned;             // allocations to free
+  std::vector<msc::DevBuf<uint8_t>> owned;   // the columns and masks msc_dataview_from_records made
   mutable std::vector<long long> col_max;  // lazily computed maximum of uint32 columns (-1 = unknown)
   mutable std::vector<std::vector<uint32_t>> dm_max;  // dm columns: maxima of each category and of the row totals (lazy)
-  mutable std::vector<uint32_t *> dm_tot;             // dm columns: row totals (device, owned)
-  mutable std::vector<void *> owned_lazy;
-  // copies of a column converted to another primitive type with runtime_cast semantics, made the first time a state
-  // binds the column to a model whose value type differs (abi.cpp column_as): per column, (type, device copy)
-  mutable std::vector<std::vector<std::pair<int, const void *>>> converted;
-  // masked lookup columns with the mask folded in as a sentinel value (abi.cpp sentinel_column): per column,
-  // ((element type, sentinel), device copy)
-  mutable std::vector<std::vector<std::pair<std::pair<int, uint32_t>, const void *>>> sentinels;
-  // byte columns holding the bits of two to four bool columns (key: the member columns' device pointers), made when a
-  // state's plan fuses them (abi.cpp plan_groups, k_pack_bits)
-  mutable std::vector<std::pair<std::vector<const void *>, const void *>> packed_bits;
-  // float [nrows][n2p] of the columns in the key, position-major (msc::NichPos; abi.cpp nich_x_matrix)
-  mutable std::vector<std::pair<std::vector<const void *>, const float *>> nich_x;
-  // uint32 [nrows][l4] lookup index matrices (msc::FeatDesc::lk_idx; abi.cpp look_idx_matrix); key: per feature
-  // {column, kind, clamp, slot offset, byte} flattened
-  mutable std::vector<std::pair<std::vector<uint64_t>, const uint32_t *>> look_idx;
+  // what the library derives from the columns and keeps with the view until it is destroyed or invalidated (abi.cpp
+  // view_copy): one entry per (kind, key)
+  enum CopyKind : uint32_t {
+    kConverted,    // a column converted to another primitive type with runtime_cast semantics, made the first time a
+                   // state binds it to a model whose value type differs (column_as); key {column, type}
+    kSentinel,     // a masked lookup column with the mask folded in as a sentinel value (sentinel_column); key {column,
+                   // element bytes, sentinel}
+    kPackedBits,   // a byte column holding the bits of two to four bool columns, made when a state's plan fuses them
+                   // (plan_groups, k_pack_bits); key: the member columns' device pointers, then the radix
+    kNichX,        // float [nrows][n2p] of the columns in the key, position-major (msc::NichPos; nich_x_matrix)
+    kLookIdx,      // uint32 [nrows][l4] lookup index matrix (msc::FeatDesc::lk_idx; look_idx_matrix); key: per feature
+                   // {column, kind | clamp | slot offset, byte}
+    kDmTot,        // a dm column's row totals (uint32 [nrows]; bind_dm_column); key {column}
+    kDmMax,        // ... and the device scratch its maxima were found in; key {column}
+  };
+  struct Copy {
+    CopyKind kind;
+    std::vector<uint64_t> key;
+    msc::DevBuf<uint8_t> buf;
+  };
+  mutable std::vector<Copy> copies;
 };
 
 struct msc_feature_host {
   int family = 0;
   uint32_t dim = 0;
   std::vector<float> hp;
-  float *hp_dev = nullptr;
-  float *tab = nullptr;
-  uint32_t *raw_u32 = nullptr;
-  float *raw_f32 = nullptr;
-  float *niw_raw = nullptr;     // [K][d + d*d] float
-  double *loo64 = nullptr;      // nich: leave-one-out constants
-  float *loo_tab = nullptr;     // bb, gp, bnb, dd: leave-one-out tables
-  float *niw_w = nullptr, *niw_b = nullptr;
-  double *niw_w64 = nullptr, *niw_mu64 = nullptr, *niw_c64 = nullptr;
+  msc::DevBuf<float> hp_dev;
+  msc::DevBuf<float> tab;             // dm: (re)sized when a column is bound (bind_dm_column)
+  msc::DevBuf<uint32_t> raw_u32;
+  msc::DevBuf<float> raw_f32;
+  msc::DevBuf<double> loo64;          // nich: leave-one-out constants
+  msc::DevBuf<float> loo_tab;         // bb, gp, bnb, dd: leave-one-out tables
+  msc::DevBuf<float> niw_w, niw_b;
+  msc::DevBuf<double> niw_w64, niw_mu64, niw_c64;
   size_t i64_off = 0, i64_len = 0;   // slices of the state's reduce buffers (elements)
   size_t f64_off = 0, f64_len = 0;
-  size_t tab_rows_cap = 0;      // dm: rows (+4) the table buffer holds; it is (re)sized when a column is bound
-  uint32_t *dm_meta_dev = nullptr;   // dm: [dim+1][2] stage tables (FeatDesc::dm_meta)
+  msc::DevBuf<uint32_t> dm_meta_dev;  // dm: [dim+1][2] stage tables (FeatDesc::dm_meta)
   std::vector<uint32_t> dm_meta;     // host copy
   bool raw_valid = true;        // raw tables hold the truth
   bool additive_valid = false;  // additive tables are in sync with raw
   bool derived_valid = false;   // score tables are in sync with raw
 };
 
-struct msc_hp_grid;
+struct msc_state;
+// a grid of hyper-parameter points of one feature (or of alpha: feature == MSC_HP_CLUSTER), uploaded once
+struct msc_hp_grid {
+  msc_state *st = nullptr;
+  uint32_t feature = 0;
+  std::vector<float> blocks;          // [npoints][hpf], the host copy
+  msc::DevBuf<float> grid_dev;
+  msc::DevBuf<double> logprior_dev;   // null: no prior
+  msc::HpJob job;                     // the grid alone (part_off = out_off = 0)
+  msc::DevBuf<msc::HpJob> job_dev;
+};
+
 struct msc_state {
   msc_context *ctx = nullptr;
   uint32_t nfeat = 0, K = 0, kpad = 0;
@@ -511,46 +525,44 @@ struct msc_state {
   std::vector<msc_feature_host> feats;
   bool nich1 = false, has_dm = false;   // msc_state_create (no call changes the families): a single nich feature, any dm
   uint32_t n_niw = 0;                   // feature, how many niw features
-  long long *red_i64 = nullptr;   // [cnt[kpad] | feature slices]
-  double *red_f64 = nullptr;
+  msc::DevBuf<long long> red_i64;   // [cnt[kpad] | feature slices]
+  msc::DevBuf<double> red_f64;
   size_t n_i64 = 0, n_f64 = 0;
-  double *red_pack = nullptr;     // both tables as one float64 buffer (msc_state_reduce_pack), made at the first call
+  msc::DevBuf<double> red_pack;   // both tables as one float64 buffer (msc_state_reduce_pack), made at the first call
   uint64_t sweep_rows_hint = 0;   // msc_state_set_sweep_rows: the rows of the WHOLE a sharded sweep's kernel choice goes by
-  uint32_t *cnt_u32 = nullptr;    // group sizes (group_manager counts), [kpad]
-  float *logpc = nullptr;         // log pseudocount per group, [kpad] (+ loo variants, see prepare)
+  msc::DevBuf<uint32_t> cnt_u32;    // group sizes (group_manager counts), [kpad]
+  msc::DevBuf<float> logpc;         // log pseudocount per group, [kpad] (+ loo variants, see prepare)
   bool cnt_additive_valid = false;
   bool crp_valid = false;
-  msc::FeatDesc *desc_dev = nullptr;
+  msc::DevBuf<msc::FeatDesc> desc_dev;
   std::vector<msc::FeatDesc> desc_host;
   // the same descriptors in the order the tile kernels walk them (abi.cpp plan_groups): every feature but the
   // unmasked nich ones, in the caller's order, then the unmasked nich features (from index tile_split on)
-  msc::FeatDesc *desc_tile_dev = nullptr;
+  msc::DevBuf<msc::FeatDesc> desc_tile_dev;
   std::vector<msc::FeatDesc> desc_tile_host;
   uint32_t tile_split = 0;
   // the same plan with runs of unmasked bb / bbnc columns fused (FeatDesc::fuse_*): what the score / sweep kernels walk;
   // the leave-one-out pass keeps the plan above (its double sum over features stays term by term)
-  msc::FeatDesc *desc_fuse_dev = nullptr;
+  msc::DevBuf<msc::FeatDesc> desc_fuse_dev;
   std::vector<msc::FeatDesc> desc_fuse_host;
   uint32_t fuse_nfeat = 0, fuse_split = 0;
   bool fuse_any = false;
-  float *fuse_tab = nullptr;          // the fused tables, 32 rows of kpad floats a fused feature (16 or 27 used)
-  size_t fuse_tab_floats = 0;
+  msc::DevBuf<float> fuse_tab;        // the fused tables, 32 rows of kpad floats a fused feature (16 or 27 used)
   // what msc_accumulate walks: the fused bb features first (each feeds its members' tables from one byte column), then
   // every feature no fused one covers, as the caller gave it (masks and all)
-  msc::FeatDesc *desc_acc_dev = nullptr;
+  msc::DevBuf<msc::FeatDesc> desc_acc_dev;
   std::vector<msc::FeatDesc> desc_acc_host;
-  msc::NichPlanInfo *nich_info = nullptr;   // [nfeat]: per feature of the plans' second phase (FeatDesc::nich_info)
-  float *rn_pack = nullptr;                 // the role-split kernels' second phase (msc::NichPos): (1 + 5 nfeat) x kpad floats
-  msc::NichPos *rn_pos = nullptr;           // [nfeat rounded up to four]
+  msc::DevBuf<msc::NichPlanInfo> nich_info;   // [nfeat]: per feature of the plans' second phase (FeatDesc::nich_info)
+  msc::DevBuf<float> rn_pack;                 // the role-split kernels' second phase (msc::NichPos): (1 + 5 nfeat) x kpad floats
+  msc::DevBuf<msc::NichPos> rn_pos;           // [nfeat rounded up to four]
   bool nich_blocks_any = false;       // the plan has a nich block of two or more features
   const msc_dataview *bound_view = nullptr;
   uint64_t bound_serial = 0;
   std::vector<uint32_t> bound_cols;
-  std::vector<void *> owned;
-  float *scratch = nullptr;       // score chunk for the generic sweep path
-  float *tail_scores = nullptr;   // 64 floats per row: the groups beyond the first tile (k_score_tail_rows -> k_sweep_tile_roles<true>)
-  size_t tail_floats = 0;
-  float *own = nullptr;           // per-row leave-one-out values (k_loo_own)
+  msc::Retired retired;           // buffers grow_retained replaced: a captured step graph may still read them
+  msc::DevBuf<float> scratch;     // score chunk for the generic sweep path
+  msc::DevBuf<float> tail_scores;   // 64 floats per row: the groups beyond the first tile (k_score_tail_rows -> k_sweep_tile_roles<true>)
+  msc::DevBuf<float> own;         // per-row leave-one-out values (k_loo_own)
   // plan_groups: which tile kernels the plan takes -- TILE_ROLES: lookup runs only before tile_split, unmasked nich
   // features after it; NICH_PACK: no first phase at all (or a few lookups), two or more plain nich features
   // (k_score_nich_pack); LOOKUPS: staged lookup features and nothing else (k_score_lookups); else TILE
@@ -560,16 +572,12 @@ struct msc_state {
   uint32_t tail_max_rows = 0, tail_pack_rows = 0;   // the lookup tables of the tile plan's first phase: the largest, all together
   bool tail_masked_nich = false;      // ... and masked nich columns among them (evaluated in place, under the row's mask)
   bool tail_dm = false;               // ... or dm features with their tables staged whole
-  float *tail_pack = nullptr;         // k_tail_pack's output: tail_pack_rows x 64 floats (grown on demand)
-  size_t tail_pack_floats = 0;
+  msc::DevBuf<float> tail_pack;       // k_tail_pack's output: tail_pack_rows x 64 floats (grown on demand)
   uint32_t loo_staged = 0;        // plan_groups: features whose leave-one-out block k_loo_own_lds stages in LDS
-  float *rows_table = nullptr;    // k_sweep_nich1_rows: per-group constants as scalar operands (single nich, K > 1024)
-  size_t rows_table_floats = 0;
-  size_t own_cap = 0;
-  uint32_t *colmax_dev = nullptr;
-  size_t scratch_floats = 0;
+  msc::DevBuf<float> rows_table;  // k_sweep_nich1_rows: per-group constants as scalar operands (single nich, K > 1024)
+  msc::DevBuf<uint32_t> colmax_dev;
   // (seed, sweep index) of the sampling kernels, device-resident (kernels_sweep.hip); the host tracks what it holds
-  uint64_t *rng_dev = nullptr;
+  msc::DevBuf<uint64_t> rng_dev;
   uint64_t rng_seed = 0, rng_sweep = 0;
   bool rng_valid = false;
   bool rng_bump_pending = false;       // msc_sweep_step_begin left the increment of the sweep index to msc_state_commit_reduce
@@ -586,50 +594,29 @@ struct msc_state {
     bool disabled = false;
     uint64_t n_eager = 0, n_replayed = 0;   // steps run either way (msc_sweep_step_stats)
   } step_graph;
-  double *niw_qown = nullptr;        // q of every row's own group (niw leave-one-out), [niw_qown_cap]
-  size_t niw_qown_cap = 0;
-  int32_t *one_z = nullptr;          // a one-entry assignment vector (msc_entity_op's general path)
-  uint32_t *niw_scratch = nullptr;   // row bucketing for niw accumulate: 2 K + 1 + rows uint32
-  size_t niw_scratch_len = 0;
+  msc::DevBuf<double> niw_qown;      // q of every row's own group (niw leave-one-out), one a row
+  msc::DevBuf<int32_t> one_z;        // a one-entry assignment vector (msc_entity_op's general path)
+  msc::DevBuf<uint32_t> niw_scratch;   // row bucketing for niw accumulate: 2 K + 1 + rows uint32
   // grid hyper-parameter inference (abi.cpp msc_hp_grid_*): the live grids (destroyed with the state at the latest) and
   // the workspaces of the calls, grown on demand
-  std::vector<msc_hp_grid *> hp_grids;
-  double *hp_part = nullptr;          // per (group block, point) partial sums
-  size_t hp_part_cap = 0;
-  double *hp_out = nullptr;           // msc_hp_grid_gibbs: every grid's likelihoods
-  size_t hp_out_cap = 0;
-  msc::HpJob *hp_jobs_dev = nullptr;  // msc_hp_grid_gibbs: the grids of the call, then the indices drawn
-  uint32_t *hp_chosen_dev = nullptr;
-  size_t hp_jobs_cap = 0, hp_chosen_cap = 0;
+  std::vector<std::unique_ptr<msc_hp_grid>> hp_grids;
+  msc::DevBuf<double> hp_part;        // per (group block, point) partial sums
+  msc::DevBuf<double> hp_out;         // msc_hp_grid_gibbs: every grid's likelihoods
+  msc::DevBuf<msc::HpJob> hp_jobs_dev;   // msc_hp_grid_gibbs: the grids of the call, then the indices drawn
+  msc::DevBuf<uint32_t> hp_chosen_dev;
   std::vector<msc::HpJob> hp_jobs_host;
   // slice sampling (abi.cpp msc_hp_slice / msc_theta_slice): the call's targets and entries, then its outputs; grown on
   // demand
-  unsigned char *slice_buf = nullptr;
-  size_t slice_cap = 0;
+  msc::DevBuf<unsigned char> slice_buf;
   // posterior predictive sampling (abi.cpp msc_sample_predictive): the drawn features' descriptors and parameters, and
   // the scratch assignment of a group draw, grown on demand
-  msc::PredFeat *pred_feats_dev = nullptr;
-  size_t pred_feats_cap = 0;
-  double *pred_par = nullptr;
-  size_t pred_par_cap = 0;
-  int32_t *pred_z = nullptr;
-  size_t pred_z_cap = 0;
+  msc::DevBuf<msc::PredFeat> pred_feats_dev;
+  msc::DevBuf<double> pred_par;
+  msc::DevBuf<int32_t> pred_z;
   std::vector<msc::PredFeat> pred_feats_host;   // what pred_feats_dev holds
-  msc::PredFeat *pred_stage = nullptr;          // pinned staging of the upload, pred_stage_cap descriptors
-  size_t pred_stage_cap = 0;
+  msc::PinnedBuf<msc::PredFeat> pred_stage;     // pinned staging of the upload
   hipEvent_t pred_upload = nullptr;             // recorded after the upload from pred_stage
   bool pred_upload_pending = false;
-};
-
-// a grid of hyper-parameter points of one feature (or of alpha: feature == MSC_HP_CLUSTER), uploaded once
-struct msc_hp_grid {
-  msc_state *st = nullptr;
-  uint32_t feature = 0;
-  std::vector<float> blocks;          // [npoints][hpf], the host copy
-  float *grid_dev = nullptr;
-  double *logprior_dev = nullptr;     // null: no prior
-  msc::HpJob job;                     // the grid alone (part_off = out_off = 0)
-  msc::HpJob *job_dev = nullptr;
 };
 
 // a z-matrix accumulator (abi.cpp msc_zmatrix_*, kernels_query.hip): m selected rows, counts as upper-triangle tiles
@@ -638,11 +625,11 @@ struct msc_zmatrix {
   uint64_t n = 0;
   uint32_t m = 0, nlabels = 0, nt = 0;     // nt: 64-row bands (m rounded up)
   bool wide = false;                       // 16-bit labels (nlabels > 256)
-  uint32_t *rows_dev = nullptr;            // [m]
-  uint32_t *order_dev = nullptr;           // [m], the order of the most recent counts / result call
-  uint32_t *batch = nullptr;               // [64 nt][kZmBatchWords], zero where no sample is staged
-  uint32_t *bad = nullptr;                 // [kZmBatchMax + 1]: bad-sample flags of the batch's slots, then their number
-  uint32_t *counts = nullptr;              // [nt (nt + 1) / 2][64][64]
+  msc::DevBuf<uint32_t> rows_dev;          // [m]
+  msc::DevBuf<uint32_t> order_dev;         // [m], the order of the most recent counts / result call
+  msc::DevBuf<uint32_t> batch;             // [64 nt][kZmBatchWords], zero where no sample is staged
+  msc::DevBuf<uint32_t> bad;               // [kZmBatchMax + 1]: bad-sample flags of the batch's slots, then their number
+  msc::DevBuf<uint32_t> counts;            // [nt (nt + 1) / 2][64][64]
   uint32_t staged = 0;                     // samples in the batch
   uint64_t nsamples = 0;
 };

@@ -504,3 +504,48 @@ def test_columns_rewritten_in_place_need_invalidate(gpu_ctx, N):
     view.invalidate()
     b = check(feats2, "second_batch")
     assert np.abs(a - b).max() > 1e-2
+
+
+def test_a_full_lifecycle_returns_its_memory(gpu_ctx, monkeypatch):
+    """Every object the library makes owns its device memory and frees it when destroyed: a view over a million rows,
+    a state with bb, nich and dm features that has run a grid Gibbs step, a slice step, group draws of the posterior
+    predictive, a z-matrix and graph-captured sweep steps.  After a few rounds the free device memory stays put."""
+    import common_amd
+    monkeypatch.setenv("MSC_SWEEP_GRAPH", "1")
+    rng = np.random.default_rng(5)
+    N, K, D = 1 << 20, 64, 4
+    rec = np.zeros(N, dtype=[("f0", np.bool_), ("f1", np.float32), ("f2", np.int32, (D,))])
+    rec["f0"] = rng.random(N) < 0.3
+    rec["f1"] = rng.normal(0.0, 1.0, N).astype(np.float32)
+    rec["f2"] = rng.integers(0, 6, (N, D)).astype(np.int32)
+    z0 = torch.from_numpy(rng.integers(0, K, N).astype(np.int32)).to(gpu_ctx.torch_device)
+    specs = [(orc.BB, 0), (orc.NICH, 0), (orc.DM, D)]
+    free = []
+    for it in range(20):
+        view = common_amd.DataView.from_recarray(gpu_ctx, rec)
+        st = common_amd.State(gpu_ctx, specs, K)
+        st.set_alpha(1.0)
+        z = z0.clone()
+        st.accumulate(view, z)
+        grids = [st.hp_grid(0, [dict(alpha=a, beta=1.0) for a in (0.5, 1.0, 2.0)]), st.crp_grid([0.5, 1.0, 2.0])]
+        st.hp_gibbs(grids, seed=it, sweep=0)
+        st.hp_slice([{"feature": 1, "coord": 1, "width": 0.5}, {"feature": "alpha", "width": 0.5}], seed=it, sweep=1)
+        drawn, groups = st.sample_predictive(view, seed=it, sweep=2, features=[0, 1], nrows=1 << 16)
+        zm = common_amd.ZMatrix(gpu_ctx, N, K, rows=np.arange(0, N, 1024))
+        zm.add(z)
+        zm.result()
+        for sweep in range(4):                        # steps 0-1 eager, 2 captured, 3 replayed
+            st.sweep_step(view, z, seed=it, sweep=sweep)
+        assert st.sweep_step_stats()[1] > 0
+        gpu_ctx.synchronize()
+        del drawn, groups
+        zm.close()
+        for g in grids:
+            g.close()
+        st.close()
+        view.close()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        free.append(torch.cuda.mem_get_info()[0])
+    slack = 8 << 20
+    assert free[19] >= free[2] - slack, ["%.1f MiB" % ((f - free[2]) / 2.0 ** 20) for f in free]
