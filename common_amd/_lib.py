@@ -118,6 +118,8 @@ _SIGS = {
     "msc_state_reduce_pack": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "msc_state_reduce_unpack": (C.c_int, [C.c_void_p]),
     "msc_state_set_sweep_rows": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "msc_state_col_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "msc_state_set_col_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "msc_comm_unique_id_bytes": (C.c_size_t, []),
     "msc_comm_unique_id": (C.c_int, [C.c_void_p, C.c_size_t]),
     "msc_comm_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -1555,6 +1555,28 @@ static int sentinel_column(const msc_dataview *view, uint32_t c, const void *col
   return MSC_OK;
 }
 
+// The maxima the plan goes by: the view's own, raised to the whole dataset's where a sharded driver stated them
+// (msc_state_set_col_bounds), so that every shard plans -- tables, groups, kernels -- as the whole would
+static long long col_max_of(const msc_state *st, uint32_t f, const msc_dataview *view, uint32_t c) {
+  const long long own = view->col_max[c];
+  return f < st->col_bounds.size() && !st->col_bounds[f].empty() ? std::max(own, (long long)st->col_bounds[f][0]) : own;
+}
+// (i = dim: the row total's)
+static uint32_t dm_max_of(const msc_state *st, uint32_t f, const msc_dataview *view, uint32_t c, uint32_t i) {
+  const uint32_t own = view->dm_max[c][i];
+  return f < st->col_bounds.size() && !st->col_bounds[f].empty() ? std::max(own, st->col_bounds[f][i]) : own;
+}
+// how many bounds the state's features take (msc_state_col_bounds / msc_state_set_col_bounds)
+static size_t col_bound_count(const msc_state *st, uint32_t f) {
+  const int fam = st->feats[f].family;
+  return is_count_family(fam) ? 1 : fam == MSC_DM ? (size_t)st->feats[f].dim + 1 : 0;
+}
+static size_t col_bounds_size(const msc_state *st) {
+  size_t n = 0;
+  for (uint32_t f = 0; f < st->nfeat; f++) n += col_bound_count(st, f);
+  return n;
+}
+
 static int bind_dm_column(msc_state *st, uint32_t f, const msc_dataview *view, uint32_t c) {
   msc_feature_host &h = st->feats[f];
   FeatDesc &d = st->desc_host[f];
@@ -1585,7 +1607,7 @@ static int bind_dm_column(msc_state *st, uint32_t f, const msc_dataview *view, u
   std::vector<uint32_t> meta(2 * (size_t)nst);
   uint32_t rows = 0;
   for (uint32_t i = 0; i < nst; i++) {
-    const uint32_t vcap = (uint32_t)std::min<unsigned long long>((unsigned long long)view->dm_max[c][i] + 1ull, kGpMaxTable);
+    const uint32_t vcap = (uint32_t)std::min<unsigned long long>((unsigned long long)dm_max_of(st, f, view, c, i) + 1ull, kGpMaxTable);
     meta[2 * i] = rows;
     meta[2 * i + 1] = vcap;
     rows += 2 * vcap;                                   // (hi, lo) row pairs
@@ -1620,7 +1642,7 @@ static int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *co
               (unsigned long long)row0, (unsigned long long)(row0 + nrows),
               (unsigned long long)view->nrows);
   (void)bound_view_of(st);                                  // (a binding to a view that is gone, or was invalidated, is dropped first)
-  bool same = st->bound_view == view && st->bound_serial == view->serial && st->bound_cols.size() == st->nfeat;
+  bool same = !st->rebind && st->bound_view == view && st->bound_serial == view->serial && st->bound_cols.size() == st->nfeat;
   for (uint32_t f = 0; f < st->nfeat && same; f++) same = st->bound_cols[f] == (cols ? cols[f] : f);
   if (same) {
     for (uint32_t f = 0; f < st->nfeat && same; f++) {
@@ -1664,7 +1686,7 @@ static int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *co
         }
         view->col_max[c] = (long long)mx;
       }
-      const uint32_t vcap = (uint32_t)std::min<long long>(view->col_max[c] + 1, (long long)kGpMaxTable);
+      const uint32_t vcap = (uint32_t)std::min<long long>(col_max_of(st, f, view, c) + 1, (long long)kGpMaxTable);
       if (vcap != st->desc_host[f].vcap) {
         st->desc_host[f].vcap = vcap;
         st->feats[f].derived_valid = false;
@@ -1690,6 +1712,7 @@ static int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *co
   }
   st->bound_view = view;
   st->bound_serial = view->serial;
+  st->rebind = false;
   return upload_desc(st);
 }
 
@@ -1783,9 +1806,9 @@ static int tail_plan(msc_state *st, TailPlan &tp, bool exact = true) {
 static bool gp_beyond_table(const msc_state *st, uint32_t f) {
   if (!st->bound_view || f >= st->bound_cols.size()) return false;
   const uint32_t c = st->bound_cols[f];
-  if (is_count_family(st->feats[f].family)) return st->bound_view->col_max[c] >= (long long)kGpMaxTable;
+  if (is_count_family(st->feats[f].family)) return col_max_of(st, f, st->bound_view, c) >= (long long)kGpMaxTable;
   if (st->feats[f].family == MSC_DM)      // a row goes to the double path when its total is beyond the tables
-    return !st->bound_view->dm_max[c].empty() && st->bound_view->dm_max[c].back() >= kGpMaxTable;
+    return !st->bound_view->dm_max[c].empty() && dm_max_of(st, f, st->bound_view, c, st->feats[f].dim) >= kGpMaxTable;
   return false;
 }
 
@@ -2663,6 +2686,55 @@ extern "C" int msc_state_set_sweep_rows(msc_state *st, uint64_t global_rows) {
     st->step_graph.seen = 0;
   }
   st->sweep_rows_hint = global_rows;
+  return MSC_OK;
+}
+
+// The same for the kernels' TABLES: a count / dm feature's exact tables cover 0 .. the bound view's column maximum, and
+// that maximum decides the plan (table sizes, group packing, sentinel columns, lookup or generic kind, the kernel path,
+// the narrow and lane <-> row kernels, the generic sweep past kGpMaxTable).  A shard's maxima are not the whole's, so a
+// driver that gives every rank a view of its own reads each view's bounds (msc_state_col_bounds), takes the
+// elementwise MAX across ranks and installs it on every rank (msc_state_set_col_bounds): every shard then plans as the
+// whole does.  The state uses max(view's own, given) everywhere; NULL / 0 restores the view's alone.
+extern "C" int msc_state_col_bounds(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint32_t *out, size_t n) {
+  MSC_REQUIRE(st && view, "null argument");
+  const size_t want = col_bounds_size(st);
+  MSC_REQUIRE(n == want, "the state's features take %zu column bounds (got %zu)", want, n);
+  MSC_REQUIRE(out || n == 0, "null argument");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  MSC_TRY(bind_view(st, view, cols, 0, 0));              // (finds the maxima the binding needs, once per view)
+  size_t k = 0;
+  for (uint32_t f = 0; f < st->nfeat; f++) {
+    const uint32_t c = st->bound_cols[f];
+    if (is_count_family(st->feats[f].family)) out[k++] = (uint32_t)std::max(view->col_max[c], 0ll);
+    else if (st->feats[f].family == MSC_DM)
+      for (uint32_t i = 0; i <= st->feats[f].dim; i++) out[k++] = view->dm_max[c][i];
+  }
+  return MSC_OK;
+}
+
+extern "C" int msc_state_set_col_bounds(msc_state *st, const uint32_t *bounds, size_t n) {
+  MSC_REQUIRE(st, "null state");
+  const size_t want = col_bounds_size(st);
+  MSC_REQUIRE(n == 0 || n == want, "the state's features take %zu column bounds (got %zu)", want, n);
+  MSC_REQUIRE(bounds || n == 0, "null bounds");
+  std::vector<std::vector<uint32_t>> nb;
+  if (n != 0) {
+    nb.resize(st->nfeat);
+    for (uint32_t f = 0, k = 0; f < st->nfeat; f++) {
+      nb[f].assign(bounds + k, bounds + k + col_bound_count(st, f));
+      k += (uint32_t)col_bound_count(st, f);
+    }
+  }
+  if (nb == st->col_bounds) return MSC_OK;
+  if (st->step_graph.exec) {
+    // (a captured step holds the kernels and table sizes of the old plan: ADVICE r04, as for msc_state_set_sweep_rows)
+    (void)hipGraphExecDestroy(st->step_graph.exec);
+    st->step_graph.exec = nullptr;
+    st->step_graph.seen = 0;
+  }
+  st->col_bounds = std::move(nb);
+  st->rebind = true;
   return MSC_OK;
 }
 

@@ -9,6 +9,7 @@
 
 #include <cstdlib>
 #include <new>
+#include <vector>
 
 #include "msc_internal.hpp"
 
@@ -17,7 +18,7 @@ namespace {
 // the slice of rccl.h this file needs (layouts and enum values: /opt/rocm/include/rccl/rccl.h:40-43,448-470)
 struct rccl_unique_id { char internal[128]; };
 typedef void *rccl_comm_t;
-enum { kRcclSuccess = 0, kRcclSum = 0, kRcclInt64 = 4, kRcclFloat64 = 8 };
+enum { kRcclSuccess = 0, kRcclSum = 0, kRcclMax = 2, kRcclUint32 = 3, kRcclInt64 = 4, kRcclUint64 = 5, kRcclFloat64 = 8 };
 
 struct RcclApi {
   void *handle = nullptr;
@@ -166,10 +167,48 @@ extern "C" int msc_sweep_step_sharded(msc_state *st, const msc_dataview *view, c
   return msc_state_commit_reduce(st);
 }
 
-// suff-stats of the GLOBAL assignment: local accumulate, exchange, commit (what starts a sharded run)
+// what the kernels of a shard's sweeps are chosen by, made the whole dataset's: the views' column bounds (MAX) and row
+// counts (SUM) across the ranks, installed with msc_state_set_col_bounds / msc_state_set_sweep_rows (as
+// common_amd/dist.py ShardedSweep does over torch.distributed).  Synchronous: once, when a sharded run starts.
+static int exchange_plan_bounds(msc_state *st, const msc_dataview *view, const uint32_t *cols, msc_comm *comm) {
+  size_t nb = 0;                                       // (the layout of msc_state_col_bounds)
+  for (uint32_t f = 0; f < st->nfeat; f++) {
+    const int fam = st->feats[f].family;
+    nb += fam == MSC_GP || fam == MSC_BNB ? 1 : fam == MSC_DM ? (size_t)st->feats[f].dim + 1 : 0;
+  }
+  std::vector<uint32_t> bounds(nb);
+  MSC_TRY(msc_state_col_bounds(st, view, cols, bounds.data(), nb));
+  uint64_t rows = view->nrows;
+  DevBuf<uint32_t> bdev;
+  DevBuf<uint64_t> rdev;
+  MSC_HIP(bdev.alloc(nb, 1));
+  MSC_HIP(rdev.alloc(1));
+  hipStream_t s = st->ctx->stream;
+  if (nb) MSC_HIP(hipMemcpyAsync(bdev, bounds.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, s));
+  MSC_HIP(hipMemcpyAsync(rdev, &rows, sizeof rows, hipMemcpyHostToDevice, s));
+  MSC_RCCL(rccl().GroupStart());
+  int r1 = kRcclSuccess;
+  if (nb) r1 = rccl().AllReduce(bdev, bdev, nb, kRcclUint32, kRcclMax, comm->comm, s);
+  const int r2 = rccl().AllReduce(rdev, rdev, 1, kRcclUint64, kRcclSum, comm->comm, s);
+  const int r3 = rccl().GroupEnd();
+  if (r1 != kRcclSuccess) return fail(MSC_EHIP, "ncclAllReduce(uint32, max) failed: %s", rccl().GetErrorString(r1));
+  if (r2 != kRcclSuccess) return fail(MSC_EHIP, "ncclAllReduce(uint64) failed: %s", rccl().GetErrorString(r2));
+  if (r3 != kRcclSuccess) return fail(MSC_EHIP, "ncclGroupEnd failed: %s", rccl().GetErrorString(r3));
+  if (nb) MSC_HIP(hipMemcpyAsync(bounds.data(), bdev, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, s));
+  MSC_HIP(hipMemcpyAsync(&rows, rdev, sizeof rows, hipMemcpyDeviceToHost, s));
+  MSC_HIP(hipStreamSynchronize(s));
+  MSC_TRY(msc_state_set_col_bounds(st, bounds.data(), nb));
+  return msc_state_set_sweep_rows(st, rows);
+}
+
+// suff-stats of the GLOBAL assignment: local accumulate, exchange, commit (what starts a sharded run; with more than one
+// rank it first makes the plan the whole dataset's: exchange_plan_bounds)
 extern "C" int msc_accumulate_sharded(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                                       uint64_t nrows, const int32_t *z_dev, msc_comm *comm) {
-  MSC_REQUIRE(st && comm, "null argument");
+  MSC_REQUIRE(st && view && comm, "null argument");
+  MSC_REQUIRE(comm->ctx->device == st->ctx->device, "communicator and state live on different devices");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  if (comm->nranks > 1) MSC_TRY(exchange_plan_bounds(st, view, cols, comm));
   MSC_TRY(msc_accumulate(st, view, cols, row0, nrows, z_dev, MSC_ACC_RESET | MSC_ACC_NO_COMMIT));
   MSC_TRY(msc_state_allreduce(st, comm));
   return msc_state_commit_reduce(st);

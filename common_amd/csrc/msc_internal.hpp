@@ -530,6 +530,10 @@ struct msc_state {
   size_t n_i64 = 0, n_f64 = 0;
   msc::DevBuf<double> red_pack;   // both tables as one float64 buffer (msc_state_reduce_pack), made at the first call
   uint64_t sweep_rows_hint = 0;   // msc_state_set_sweep_rows: the rows of the WHOLE a sharded sweep's kernel choice goes by
+  // msc_state_set_col_bounds: the WHOLE dataset's column maxima per feature (gp / bnb: one value; dm: each category's,
+  // then the row total's; other families none) -- the plan goes by max(bound view's, these).  Empty: the view's alone.
+  std::vector<std::vector<uint32_t>> col_bounds;
+  bool rebind = false;            // the bounds changed: the next call binds its view afresh (and so re-plans)
   msc::DevBuf<uint32_t> cnt_u32;    // group sizes (group_manager counts), [kpad]
   msc::DevBuf<float> logpc;         // log pseudocount per group, [kpad] (+ loo variants, see prepare)
   bool cnt_additive_valid = false;

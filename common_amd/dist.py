@@ -13,6 +13,7 @@ the same points.
 """
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -60,22 +61,38 @@ class ShardedSweep(object):
 
     The exchange is pack (one launch of the library: both tables into one float64 buffer) -> ONE all_reduce -> unpack
     (one launch) -> commit: the launch count of the C / C++ driver (msc_sweep_step_sharded) plus the two copies a
-    one-dtype collective needs.  The kernels a sweep takes are chosen by the rows of the WHOLE dataset (the shards'
-    sum, told to the state once), so that the shards draw what an unsharded sweep draws."""
+    one-dtype collective needs.
 
-    def __init__(self, state, view, z, first_global_row, group=None, global_rows=None):
+    Every rank's view holds its shard only, and a sweep's kernels are chosen by what the view holds: its row count and
+    its column maxima (a count feature's tables cover 0 .. the column's maximum; the maxima size the tables, pack the
+    features into groups and pick tile, narrow, lane <-> row or generic kernels, which add a row's scores in different
+    orders).  So the state is told the WHOLE dataset's once, here: the rows (the shards' sum, State.set_sweep_rows) and
+    the column bounds (the elementwise MAX of every rank's State.col_bounds, State.set_col_bounds).  Then every shard
+    draws what an unsharded sweep draws.  global_rows / col_bounds: the whole's, when the caller knows them already
+    (nothing is exchanged for them then).  A single rank needs no bounds: its view is the whole."""
+
+    def __init__(self, state, view, z, first_global_row, group=None, global_rows=None, col_bounds=None):
         self.state, self.view, self.z = state, view, z
         self.row_id0 = int(first_global_row)
         self.group = group
         self.red_i64, self.red_f64 = state.reduce_buffers()
+        many = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
         if global_rows is None:
             global_rows = int(view.nrows)
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            if many:
                 t = torch.tensor([global_rows], dtype=torch.int64, device=self.red_f64.device)
                 dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
                 global_rows = int(t.item())
         self.global_rows = int(global_rows)
         state.set_sweep_rows(self.global_rows)
+        if col_bounds is None and many:
+            local = np.asarray(state.col_bounds(view), dtype=np.int64)
+            t = torch.from_numpy(local).to(self.red_f64.device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+            col_bounds = t.cpu().numpy()
+        self.col_bounds = None if col_bounds is None else np.asarray(col_bounds, dtype=np.uint32)
+        if self.col_bounds is not None:
+            state.set_col_bounds(self.col_bounds)
 
     def _exchange(self):
         pack = self.state.reduce_pack()

@@ -515,6 +515,28 @@ class State(object):
         """rows of the WHOLE dataset when this state sweeps a shard through a view of its own (msc_state_set_sweep_rows)"""
         L.check(self.ctx.lib.msc_state_set_sweep_rows(self._h, int(global_rows)))
 
+    def col_bound_count(self):
+        """how many column bounds the features take: gp / bnb one, dm dim + 1, every other family none"""
+        return sum(1 if fam in (L.GP, L.BNB) else dim + 1 if fam == L.DM else 0 for fam, dim in self.features)
+
+    def col_bounds(self, view, cols=None):
+        """this view's column bounds for the state's features, in feature order (msc_state_col_bounds): uint32 array of
+        col_bound_count() values -- a gp / bnb column's maximum; a dm column's category maxima, then its largest row total"""
+        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
+        out = np.zeros(self.col_bound_count(), dtype=np.uint32)
+        L.check(self.ctx.lib.msc_state_col_bounds(self._h, view._h, self._cols(cols), out.ctypes.data_as(C.c_void_p),
+                                                  out.size))
+        return out
+
+    def set_col_bounds(self, bounds):
+        """the WHOLE dataset's column bounds (the elementwise max of every shard view's col_bounds) when this state sweeps
+        a shard through a view of its own (msc_state_set_col_bounds); None restores the view's own"""
+        if bounds is None:
+            L.check(self.ctx.lib.msc_state_set_col_bounds(self._h, None, 0))
+            return
+        b = np.ascontiguousarray(np.asarray(bounds), dtype=np.uint32)
+        L.check(self.ctx.lib.msc_state_set_col_bounds(self._h, b.ctypes.data_as(C.c_void_p), b.size))
+
     # grid hyper-parameter inference (msc_hp_grid_*; common_amd/hypers.py builds the grids upstream's way) -----------
     def hp_grid(self, f, blocks, logprior=None):
         """an HpGrid of feature f: `blocks` = [npoints, msc_hp_floats] floats (or a list of hp dicts, packed with

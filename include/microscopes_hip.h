@@ -389,6 +389,22 @@ int msc_state_reduce_unpack(msc_state *st);
  * bound view's row count); 0 restores that default.
  */
 int msc_state_set_sweep_rows(msc_state *st, uint64_t global_rows);
+/*
+ * The column bounds of the WHOLE dataset, for the same states.  A count feature's exact tables cover 0 .. its column's
+ * maximum, and the maxima decide the plan: table sizes, how features pack into groups, masked columns' sentinels, which
+ * tile / narrow / lane <-> row kernel runs, and (a count >= 1024) the generic sweep.  A shard's maxima are not the
+ * whole's, so it must plan with the whole's or it may add a row's scores in another order and draw other bits.
+ *   msc_state_col_bounds      this view's bounds for the state's features, in feature order: gp / bnb one value (the
+ *                             column's maximum), dm dim + 1 (each category's maximum, then the largest row total), other
+ *                             families none.  n must be that count (MSC_EINVAL naming it).  Binds the view if needed.
+ *   msc_state_set_col_bounds  the whole dataset's bounds (the elementwise MAX of every rank's msc_state_col_bounds), in the
+ *                             same layout; from then on the state plans with max(view's own, given) (capped at the table
+ *                             limit as before).  NULL / 0 restores the view's alone.  A change re-plans at the next call
+ *                             and drops a captured step graph.
+ * Row ranges of ONE view need neither; msc_accumulate_sharded installs both these and the rows when nranks > 1.
+ */
+int msc_state_col_bounds(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint32_t *out, size_t n);
+int msc_state_set_col_bounds(msc_state *st, const uint32_t *bounds, size_t n);
 int msc_state_commit_reduce(msc_state *st);
 
 /*
@@ -398,7 +414,10 @@ int msc_state_commit_reduce(msc_state *st);
  * msc_comm_adopt wraps an ncclComm_t the caller already has.  librccl is resolved at the first of these calls.
  *   msc_state_allreduce      sums both additive tables in place across the ranks (one RCCL group, context's stream)
  *   msc_sweep_step_sharded   msc_sweep_step_begin + that + msc_state_commit_reduce: a whole sharded sweep step
- *   msc_accumulate_sharded   suff-stats of the GLOBAL assignment: local accumulate, exchange, commit
+ *   msc_accumulate_sharded   suff-stats of the GLOBAL assignment: local accumulate, exchange, commit.  What starts a
+ *                            sharded run: with nranks > 1 it also exchanges the views' column bounds (RCCL MAX) and row
+ *                            counts (RCCL SUM) and installs them (msc_state_set_col_bounds, msc_state_set_sweep_rows), so
+ *                            that every rank's sweeps take the kernels of the unsharded sweep.  Synchronous.
  * With one rank these are msc_sweep_step / msc_accumulate.  Asynchronous (msc_comm_create / destroy are not).
  */
 typedef struct msc_comm msc_comm;

@@ -28,6 +28,26 @@ def dataset(dev, spec, N, K, seed):
     return make_columns(_Ctx, spec, N, K, seed)
 
 
+def skewed(dev, N, K, seed):
+    """bb, gp, dm(4), nich with small counts everywhere but on the second half of the rows (rank 1 of two): one gp count
+    of 700 and one dm row totalling 210 there -- each rank's view alone would plan other tables and kernels than the
+    whole (the ranks must install the whole's column bounds)"""
+    rng = np.random.default_rng(seed)
+    zn = rng.integers(0, K, N)
+    p = rng.random(K)
+    bb = rng.random(N) < p[zn]
+    gp = np.minimum(rng.poisson(rng.gamma(2.0, 2.0, K)[zn]), 60).astype(np.int32)
+    dm = rng.poisson((rng.random((K, 4)) * 2.0 + 0.2)[zn]).clip(0, 3).astype(np.int32)
+    nich = (rng.normal(0, 10, K)[zn] + rng.normal(0, 1, N)).astype(np.float32)
+    gp[N * 3 // 4] = 700
+    dm[N * 3 // 4 + 5] = [60, 50, 50, 50]
+    gpt = torch.from_numpy(gp).to(dev)
+    cols = [torch.from_numpy(bb).to(dev), gpt.view(torch.uint32) if hasattr(torch, "uint32") else gpt,
+            torch.from_numpy(dm).to(dev), torch.from_numpy(nich).to(dev)]
+    z = torch.from_numpy(rng.integers(0, K, N).astype(np.int32)).to(dev)
+    return [c.contiguous() for c in cols], z
+
+
 def main():
     out_path, which = sys.argv[1], sys.argv[2]
     N, K, nsweeps = int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
@@ -42,9 +62,13 @@ def main():
     ctx = common_amd.Context(device=local)
     dev = ctx.torch_device
     spec = {"nich": [(common_amd.NICH, 0)],
-            "mixed": [(common_amd.BB, 0), (common_amd.GP, 0), (common_amd.DD, 5), (common_amd.NICH, 0)]}[which]
+            "mixed": [(common_amd.BB, 0), (common_amd.GP, 0), (common_amd.DD, 5), (common_amd.NICH, 0)],
+            "skewed": [(common_amd.BB, 0), (common_amd.GP, 0), (common_amd.DM, 4), (common_amd.NICH, 0)]}[which]
     torch.manual_seed(1234)                                 # (make_columns draws the gp rates from the global generator)
-    cols, z_all = dataset(dev, spec, N, K, 7)               # same seeds on every rank: the same global dataset
+    if which == "skewed":
+        cols, z_all = skewed(dev, N, K, 7)
+    else:
+        cols, z_all = dataset(dev, spec, N, K, 7)           # same seeds on every rank: the same global dataset
     lo, n = shard_rows(N, world, rank)
     shard_cols = [c[lo:lo + n].contiguous() for c in cols]
     view = common_amd.DataView.from_tensors(ctx, shard_cols)
@@ -80,6 +104,8 @@ def main():
             same.append(float((z1.cpu().numpy() == z_sharded[s]).mean()))
         zf = z_sharded[-1]
         res = {"world": world, "ranks_seen": int(seen.item()), "backend": backend, "N": N, "K": K, "which": which,
+               "col_bounds_installed": None if drv.col_bounds is None else drv.col_bounds.tolist(),
+               "col_bounds_whole": st1.col_bounds(view1).tolist(),
                "same_fraction_per_sweep": same,
                "counts_equal_bincount": bool(np.array_equal(counts, np.bincount(zf, minlength=K))),
                "counts_equal_unsharded": bool(np.array_equal(counts, st1.get_group_counts())),

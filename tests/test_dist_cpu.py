@@ -1,6 +1,7 @@
 """CPU, world_size 2 over gloo: the N>1 path of a sweep -- shard the rows, build the additive
 tables per rank, sum all-reduce (the product's own allreduce_tables), compare with the oracle's
 suff-stats of the whole data.  (The kernels themselves need a GPU; this covers the collective.)"""
+import json
 import os
 
 import numpy as np
@@ -66,3 +67,75 @@ def test_allreduce_is_a_noop_without_a_process_group():
     a, b = torch.arange(4), torch.ones(3, dtype=torch.float64)
     allreduce_tables(a, b)
     assert a.tolist() == [0, 1, 2, 3] and b.tolist() == [1.0, 1.0, 1.0]
+
+
+class _StubState(object):
+    """what ShardedSweep asks of a state, on the host: this rank's column bounds, and a record of what it was told"""
+
+    def __init__(self, bounds):
+        self.bounds, self.calls = np.asarray(bounds, dtype=np.uint32), []
+
+    def reduce_buffers(self):
+        return torch.zeros(3, dtype=torch.int64), torch.zeros(2, dtype=torch.float64)
+
+    def set_sweep_rows(self, n):
+        self.calls.append(("set_sweep_rows", int(n)))
+
+    def col_bounds(self, view):
+        self.calls.append(("col_bounds",))
+        return self.bounds
+
+    def set_col_bounds(self, b):
+        self.calls.append(("set_col_bounds", None if b is None else [int(v) for v in b]))
+
+
+class _StubView(object):
+    def __init__(self, nrows):
+        self.nrows = nrows
+
+
+# every rank's own bounds: a gp maximum, a dm feature's three category maxima and its largest row total, a bnb maximum
+# (one rank holds a value beyond 2^31: the MAX travels as int64 and comes back exact)
+_RANK_BOUNDS = [[17, 3, 0, 9, 12, 1500], [700, 2, 5, 4, 210, 4], [60, 8, 1, 2**32 - 5, 11, 0]]
+
+
+def _bounds_worker(rank, world, port, out):
+    from common_amd.dist import ShardedSweep
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    st = _StubState(_RANK_BOUNDS[rank])
+    drv = ShardedSweep(st, _StubView(1000 + rank), torch.zeros(1000 + rank, dtype=torch.int32), first_global_row=0)
+    with open(out + "_%d.json" % rank, "w") as fh:
+        json.dump({"calls": st.calls, "installed": drv.col_bounds.tolist()}, fh)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_sharded_sweep_installs_the_max_of_every_ranks_column_bounds(tmp_path):
+    """ShardedSweep over gloo, three ranks: every rank reads its view's bounds, the elementwise MAX across ranks is
+    installed on every rank (with the rows of the whole), exactly once"""
+    world = len(_RANK_BOUNDS)
+    out = str(tmp_path / "bounds")
+    port = 29500 + int(np.random.default_rng(1).integers(2000, 4000))
+    mp.spawn(_bounds_worker, args=(world, port, out), nprocs=world, join=True)
+    want = [int(v) for v in np.max(np.array(_RANK_BOUNDS, dtype=np.int64), axis=0)]
+    assert want == [700, 8, 5, 2**32 - 5, 210, 1500]
+    for r in range(world):
+        with open(out + "_%d.json" % r) as fh:
+            got = json.load(fh)
+        assert got["installed"] == want
+        assert got["calls"] == [["set_sweep_rows", 3003], ["col_bounds"], ["set_col_bounds", want]], (r, got)
+
+
+def test_single_rank_sharded_sweep_installs_no_bounds():
+    """one rank (no process group): its view is the whole -- no bounds are read or installed, so sweep() stays the
+    one-call graph-replayed step; bounds the caller gives are installed as given"""
+    from common_amd.dist import ShardedSweep
+    st = _StubState([5, 6])
+    drv = ShardedSweep(st, _StubView(10), torch.zeros(10, dtype=torch.int32), first_global_row=0)
+    assert st.calls == [("set_sweep_rows", 10)] and drv.col_bounds is None
+    st = _StubState([5, 6])
+    ShardedSweep(st, _StubView(10), torch.zeros(10, dtype=torch.int32), first_global_row=0, global_rows=30,
+                 col_bounds=[9, 1])
+    assert st.calls == [("set_sweep_rows", 30), ("set_col_bounds", [9, 1])]

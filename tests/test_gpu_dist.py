@@ -73,6 +73,20 @@ def test_two_ranks_choose_the_kernels_the_whole_would(gpu_ctx, tmp_path, K):
     _check(_launch(tmp_path, "mixed", 24_000, K, 2, MSC_TAIL_MIN_ROWS="16000"))
 
 
+@pytest.mark.parametrize("K,tail_min", [(100, None), (48, "16000")])
+def test_two_ranks_with_skewed_column_maxima_equal_the_unsharded_run(gpu_ctx, tmp_path, K, tail_min):
+    """bb + gp + dm(4) + nich whose one large gp count (700) and one large dm row (total 210) sit on rank 1 only: rank 0's
+    view alone would plan lookup gp tables and staged dm tables (k_score_tail_rows<.., DMF> where the lane <-> row
+    kernels are allowed), the whole generic gp and unstaged dm.  ShardedSweep all-reduces the views' column bounds (MAX)
+    and installs them: the ranks draw what the whole draws, from the first sweep on."""
+    extra = {} if tail_min is None else {"MSC_TAIL_MIN_ROWS": tail_min}
+    r = _launch(tmp_path, "skewed", 24_000, K, 3, **extra)
+    _check(r)
+    assert min(r["same_fraction_per_sweep"][:1]) == 1.0
+    assert r["col_bounds_installed"] == r["col_bounds_whole"]
+    assert r["col_bounds_whole"][0] == 700 and r["col_bounds_whole"][-1] == 210
+
+
 def test_one_rank_over_nccl_runs_the_exchange_path_on_rccl(gpu_ctx, tmp_path):
     """the nccl (= RCCL) branch on the box's one GPU: a single rank forced through msc_sweep_step_begin -> all_reduce
     (RCCL, on the library's own reduce buffers) -> msc_state_commit_reduce must equal msc_sweep_step"""

@@ -560,9 +560,18 @@ def _nich_block_state(gpu_ctx, specs, N, K, rng, hp_of=None, z_of=None, edit=Non
     return feats, fs, z, view, st
 
 
-def _gate_on_sum(got, feats, fs, rows, z=None, prior=None):
-    """|got - sum_f twin_f| <= 1e-6 sum_f max(1, |twin_f|) (+ the prior's magnitude): the per-feature tolerances add"""
-    tw = [F.score_matrix(ss64, f["values"][rows], None if z is None else z[rows]) for f, (F, ss64, _) in zip(feats, fs)]
+def _gate_on_sum(got, feats, fs, rows, z=None, prior=None, masks=None):
+    """|got - sum_f twin_f| <= 1e-6 sum_f max(1, |twin_f|) (+ the prior's magnitude): the per-feature tolerances add.
+    masks: {feature: bool [N]} -- a masked (row, feature) adds nothing (and is not in its group's tables)"""
+    masks = masks or {}
+    tw = []
+    for i, (f, (F, ss64, _)) in enumerate(zip(feats, fs)):
+        m = masks.get(i)
+        zz = None if z is None else (z[rows] if m is None else np.where(m[rows], -1, z[rows]).astype(np.int32))
+        t = F.score_matrix(ss64, f["values"][rows], zz)
+        if m is not None:
+            t[m[rows]] = 0.0
+        tw.append(t)
     total = sum(tw) + (0.0 if prior is None else prior)
     mag = sum(np.maximum(1.0, np.abs(t)) for t in tw) + (0.0 if prior is None else np.maximum(1.0, np.abs(prior)))
     return (np.abs(got - total) / np.maximum(mag, np.abs(total))).max()
