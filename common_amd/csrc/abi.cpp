@@ -40,6 +40,26 @@ size_t primitive_size(int t) {
 
 static bool family_ok(int f) { return f >= MSC_BB && f <= MSC_DM; }
 
+// What the library reads from the environment, all of it here (INTEGRATION.md "Environment" says what each switch does):
+// read afresh by every call that plans, routes or allocates, so that a test may set a switch between two calls.
+struct Switches {
+  bool tail_forced = false, no_narrow_tail = false, no_bb_fuse = false, sweep_graph = false;
+  uint64_t tail_min_rows = 0;                           // (tail_forced)
+  int loo_lds = -1, sweep_nich1 = 0, alloc_candidates = 12;
+  float alloc_accept_gbps = 6650.f;
+};
+static Switches read_switches() {
+  Switches sw;
+  if (const char *e = std::getenv("MSC_TAIL_MIN_ROWS")) sw.tail_forced = true, sw.tail_min_rows = (uint64_t)std::atoll(e);
+  sw.no_narrow_tail = std::getenv("MSC_NO_NARROW_TAIL") != nullptr, sw.no_bb_fuse = std::getenv("MSC_NO_BB_FUSE") != nullptr;
+  if (const char *e = std::getenv("MSC_LOO_LDS")) sw.loo_lds = std::atoi(e);
+  if (const char *e = std::getenv("MSC_SWEEP_NICH1")) sw.sweep_nich1 = std::atoi(e);
+  if (const char *g = std::getenv("MSC_SWEEP_GRAPH")) sw.sweep_graph = g[0] != '0' && g[0] != 0;
+  if (const char *e = std::getenv("MSC_ALLOC_CANDIDATES")) sw.alloc_candidates = std::atoi(e);
+  if (const char *e = std::getenv("MSC_ALLOC_ACCEPT_GBPS")) sw.alloc_accept_gbps = (float)std::atof(e);
+  return sw;
+}
+
 // count elements (at least one), zero-filled
 template <typename T>
 static int alloc_zeroed(DevBuf<T> &buf, size_t count) {
@@ -127,8 +147,6 @@ extern "C" int msc_context_create(int device, void *stream, msc_context **out) {
   ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   MSC_HIP(ctx->mailbox_host.alloc(192 * 1024));   // niw at dim 128: a 66 KB record + a 66 KB hp block
   MSC_HIP(hipHostGetDevicePointer(&ctx->mailbox_dev, ctx->mailbox_host, 0));
-  const char *sw = std::getenv("MSC_SYNC_WORD");           // 0: plain hipStreamSynchronize (A/B knob)
-  if (sw && std::atoi(sw) == 0) ctx->sync_word_ok = false;
   if (ctx->sync_word_host.alloc(16) == hipSuccess) {   // (64 bytes)
     *ctx->sync_word_host = 0;
     if (hipHostGetDevicePointer(&ctx->sync_word_dev, ctx->sync_word_host, 0) != hipSuccess) ctx->sync_word_ok = false;
@@ -254,7 +272,6 @@ static void vmm_free(msc_context::VmmAlloc &a) {
 // candidate and GB).
 static int alloc_placed(msc_context *ctx, size_t nbytes, uint32_t max_candidates, float accept_gbps, uint32_t flat_after,
                         void **out, float *rates_gbps, uint32_t *chosen) {
-  static const bool no_vmm = std::getenv("MSC_ALLOC_NO_VMM") != nullptr;       // (A/B knob: plain hipMalloc candidates)
   struct Cand { void *p; bool vmm; msc_context::VmmAlloc v; };
   std::vector<Cand> bufs;
   std::vector<float> rate;
@@ -269,7 +286,7 @@ static int alloc_placed(msc_context *ctx, size_t nbytes, uint32_t max_candidates
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(MSC_EHIP, "hipEventCreate failed");
   int rc = MSC_OK;
   const int reps = nbytes >= (256u << 20) ? 5 : 8;
-  const bool want_vmm = !no_vmm && nbytes >= (64u << 20);                      // small buffers: not worth 32 MiB chunks
+  const bool want_vmm = nbytes >= (64u << 20);                      // small buffers: not worth 32 MiB chunks
   size_t free_at_start = 0;
   {
     size_t total_b = 0;
@@ -356,13 +373,12 @@ extern "C" int msc_device_alloc(msc_context *ctx, size_t nbytes, void **out) {
   // Candidates held side by side walk through physical memory, and where the fast stretches lie differs from box to
   // box: one box offered one within six candidates in ten processes of ten, another none within twelve in one process
   // of twelve (profiles/r03_alloc_distribution.jsonl), the round-3 driver's none within 24
-  static const int cand = std::getenv("MSC_ALLOC_CANDIDATES") ? std::atoi(std::getenv("MSC_ALLOC_CANDIDATES")) : 12;
-  static const float accept = std::getenv("MSC_ALLOC_ACCEPT_GBPS") ? (float)std::atof(std::getenv("MSC_ALLOC_ACCEPT_GBPS")) : 6650.f;
+  const Switches sw = read_switches();
   constexpr int flat = 6;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   const bool capturing = hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-  if (nbytes >= (64u << 20) && cand >= 1 && !capturing)
-    return alloc_placed(ctx, nbytes, (uint32_t)std::min(cand, 64), accept, (uint32_t)std::max(flat, 2), out, nullptr, nullptr);
+  if (nbytes >= (64u << 20) && sw.alloc_candidates >= 1 && !capturing)
+    return alloc_placed(ctx, nbytes, (uint32_t)std::min(sw.alloc_candidates, 64), sw.alloc_accept_gbps, (uint32_t)std::max(flat, 2), out, nullptr, nullptr);
   void *p = nullptr;
   MSC_HIP(hipMalloc(&p, nbytes ? nbytes : 1));
   const hipError_t e = hipMemsetAsync(p, 0, nbytes ? nbytes : 1, ctx->stream);
@@ -708,7 +724,7 @@ static bool stages_nich(ScorePath path) { return path == MSC_PATH_TILE_ROLES || 
 
 // group packing, lookup kinds and runs of a plan `t` whose first `split` entries are the first phase (`extra`: one more
 // table row for a masked lookup column's zero row)
-static PlanFacts plan_layout(std::vector<FeatDesc> &t, uint32_t split, const std::vector<uint32_t> &extra) {
+static PlanFacts plan_layout(std::vector<FeatDesc> &t, uint32_t split, const std::vector<uint32_t> &extra, const Switches &sw) {
   auto rows_of = [](const FeatDesc &d) -> uint32_t {
     if (d.fuse_n >= 2) {
       uint32_t rows = 1;
@@ -776,16 +792,15 @@ static PlanFacts plan_layout(std::vector<FeatDesc> &t, uint32_t split, const std
   // or a first phase of at most kPackMaxLookups lookup features beside at least twice as many nich features (the lookups
   // are gathered from L2 there, ~0.03 ms a feature and million rows: 8 bb + 8 nich sweep 0.81 -> 0.70 ms, 2 gp + 12 nich
   // 0.99 -> 0.86; with 16 bb + 4 nich -- four fused lookups, four nich -- the role-split kernels are as good or better)
-  const bool nich_only = (split == 0 && n >= 2) || (roles_ok && !has_dm && split <= (uint32_t)kPackMaxLookups && n - split >= 2 * split &&
-                                                    std::getenv("MSC_NO_PACK_LOOKUPS") == nullptr);
+  const bool nich_only = (split == 0 && n >= 2) || (roles_ok && !has_dm && split <= (uint32_t)kPackMaxLookups && n - split >= 2 * split);
   // staged lookup features and nothing else: k_score_lookups / k_sweep_lookups (sixteen lookup waves of 16 sums)
-  bool lookups_only = split == n && n > 0 && !has_dm && std::getenv("MSC_NO_LOOKUPS_KERNEL") == nullptr;
+  bool lookups_only = split == n && n > 0 && !has_dm;
   for (uint32_t i = 0; i < n; i++) lookups_only &= t[i].kind != MSC_KIND_GENERIC;
   // (roles_ok needs split < n and lookups_only split == n; nich_only wins over roles_ok)
   pf.path = nich_only ? MSC_PATH_NICH_PACK : roles_ok ? MSC_PATH_TILE_ROLES : lookups_only ? MSC_PATH_LOOKUPS : MSC_PATH_TILE;
   // the lane <-> row kernel for a partly filled last tile (k_score_tail_rows): lookup features only in the first phase
   // (what it implements), whatever the second holds of plain nich features
-  pf.tail_ok = std::getenv("MSC_NO_NARROW_TAIL") == nullptr;
+  pf.tail_ok = !sw.no_narrow_tail;
   // (a masked nich column among them is evaluated like the second phase's features, under the row's mask; a dm feature
   // whose dim + 1 tables are staged whole -- small counts: no row of the bound column is beyond them -- is dim + 1 lookups
   // of (hi, lo) pairs, round 5; the kernel has one instantiation for either, none for both)
@@ -925,6 +940,7 @@ static bool look_idx_matrix(const msc_dataview *view, std::vector<FeatDesc> &tf,
 
 static int plan_groups(msc_state *st) {
   const msc_dataview *const bview = bound_view_of(st);    // (null: no column pointer survives in desc_host either)
+  const Switches sw = read_switches();
   auto nich_tail = [](const FeatDesc &d) { return d.family == MSC_NICH && d.mask == nullptr && d.col != nullptr; };
   std::vector<FeatDesc> &t = st->desc_tile_host;
   t.clear();
@@ -941,13 +957,12 @@ static int plan_groups(msc_state *st) {
     std::vector<uint32_t> tail;
     for (uint32_t i = 0; i < st->nfeat; i++) if (nich_tail(st->desc_host[i])) tail.push_back(i);
     auto nu_bits = [&](uint32_t i) { uint32_t b; std::memcpy(&b, &st->feats[i].hp[3], 4); return b; };
-    static const bool no_blocks = std::getenv("MSC_NO_NICH_BLOCKS") != nullptr;       // (A/B knob: every feature on its own)
     std::stable_sort(tail.begin(), tail.end(), [&](uint32_t a, uint32_t b) { return nu_bits(a) < nu_bits(b); });
     st->nich_blocks_any = false;
     for (size_t a = 0; a < tail.size();) {
       size_t b = a + 1;
       while (b < tail.size() && nu_bits(tail[b]) == nu_bits(tail[a])) b++;
-      const size_t n = b - a, nb = no_blocks ? n : (n + kNichBlock - 1) / kNichBlock, base = n / nb, rem = n % nb;
+      const size_t n = b - a, nb = (n + kNichBlock - 1) / kNichBlock, base = n / nb, rem = n % nb;
       for (size_t blk = 0, at = a; blk < nb; blk++) {
         const size_t len = base + (blk < rem ? 1 : 0);
         for (size_t j = 0; j < len; j++) {
@@ -976,7 +991,7 @@ static int plan_groups(msc_state *st) {
     }
   }
   const uint32_t n = st->nfeat, split = st->tile_split;
-  PlanFacts facts = plan_layout(t, split, extra);
+  PlanFacts facts = plan_layout(t, split, extra, sw);
   // The leave-one-out pass (k_loo_own_lds) stages what a row gathers per feature -- the lookup families' "value against
   // the group minus one" tables, nich's twelve doubles per group -- for ALL kpad groups (a row's own group is any of
   // them): consecutive features share the 64 KiB slot while their blocks fit; a feature whose block does not fit, or
@@ -1014,7 +1029,7 @@ static int plan_groups(msc_state *st) {
   // re-plans -- fuses nothing and holds no column; the next call that brings a view binds and plans again)
   if (!st->nich_blocks_any)                                     // (no block of two or more: no records, no head-kernel work, no far rows)
     for (FeatDesc &d : t) d.nich_info = nullptr;
-  const bool may_fuse = bview != nullptr && std::getenv("MSC_NO_BB_FUSE") == nullptr;
+  const bool may_fuse = bview != nullptr && !sw.no_bb_fuse;
   // (columns with a mask: their mask-folded copies, three states a value -- 0, 1, masked = the member's zero row --,
   // three at a time against 27 rows)
   std::vector<uint32_t> members[2];                        // [0] unmasked, [1] masked: the fusable features, in plan order
@@ -1095,14 +1110,13 @@ static int plan_groups(msc_state *st) {
     tf[i].blk_first -= n - st->fuse_nfeat;
     tf[i].blk_end -= n - st->fuse_nfeat;
   }
-  if (st->fuse_any) facts = plan_layout(tf, st->fuse_split, extra_f);
+  if (st->fuse_any) facts = plan_layout(tf, st->fuse_split, extra_f, sw);
   // what the role-split kernels' nich waves read (msc::NichPos): positions, the pack (k_fuse_tables fills it at the head
   // of every call), the x matrix -- the last needs the view; without it (a plan made while no view is bound) the plan
   // does not take those kernels, and the next call with a view plans again
   for (FeatDesc &d : tf) d.rn_pack = nullptr, d.rn_pos = nullptr, d.rn_x = nullptr, d.rn_n2 = d.rn_n2p = 0;
   for (FeatDesc &d : t) d.rn_pack = nullptr, d.rn_pos = nullptr, d.rn_x = nullptr, d.rn_n2 = d.rn_n2p = 0;
-  static const bool no_roles_pack = std::getenv("MSC_NO_ROLES") != nullptr;      // (A/B knob: the kernels that run the phases one after the other)
-  if (stages_nich(facts.path) && (bview == nullptr || no_roles_pack)) facts.path = MSC_PATH_TILE;
+  if (stages_nich(facts.path) && bview == nullptr) facts.path = MSC_PATH_TILE;
   if (stages_nich(facts.path)) {
     const uint32_t s0 = st->fuse_split, n2 = st->fuse_nfeat - s0, n2p = (n2 + 3u) & ~3u;
     std::vector<NichPos> pos(n2p);
@@ -1785,15 +1799,20 @@ static int refresh_fused_tables(msc_state *st) {
   return MSC_OK;
 }
 
-// what the narrow kernels of a partly filled last tile need (launchers.hpp): a last tile of at most kTailMaxGroups groups
-// on a plan they take; the packed-table scratch grows on demand
+// Can k_score_tail_rows take this plan's partly filled last tile?  A plan it takes (plan_groups), at most kTailMaxGroups
+// groups there, and the largest staged table beside the second phase's block (64 floats a nich feature) in 64 KiB of LDS.
+static bool narrow_tail_fits(const msc_state *st) {
+  const size_t nich_bytes = (size_t)(st->fuse_nfeat - st->fuse_split) * 64 * sizeof(float);
+  return st->tile_narrow_tail_ok && st->K - (st->kpad - kGroupTile) <= kTailMaxGroups &&
+         nich_bytes + (size_t)std::max<uint32_t>(1u, st->tail_max_rows) * kTailStride * sizeof(float) <= 64u * 1024u;
+}
+
+// what the narrow kernels of a partly filled last tile need (launchers.hpp); the packed-table scratch grows on demand
 static int tail_plan(msc_state *st, TailPlan &tp, bool exact = true) {
   tp = TailPlan();
-  tp.cost = st->plan_cost;
   tp.exact = exact;
-  if (!st->tile_narrow_tail_ok || st->K - (st->kpad - kGroupTile) > kTailMaxGroups) return MSC_OK;
+  if (!(tp.ok = narrow_tail_fits(st))) return MSC_OK;
   MSC_HIP(grow_retained(st->retired, st->tail_pack, (size_t)st->tail_pack_rows * 64));
-  tp.ok = true;
   tp.masked_nich = st->tail_masked_nich;
   tp.dm = st->tail_dm;
   tp.max_rows = st->tail_max_rows;
@@ -1822,25 +1841,34 @@ static bool loo_needs_heavy(const msc_state *st) {
   return false;
 }
 
-// every row's leave-one-out value (its own group's score, the prior's when crp) into st->own
+// every row's leave-one-out value (its own group's score, the prior's when crp) into st->own.  The staged kernel (a plan
+// with leave-one-out blocks in LDS, plan_groups) pays once the rows nearly fill the chip -- C3, 1M rows: 140 us staged, 196
+// gathered; a 131k-row chunk: 0.33 ms against 0.03.  Both give a row the same bits (test_gpu_score.py::
+// test_both_leave_one_out_kernels_give_a_row_the_same_bits), so the CALL's rows choose.
 static int run_loo_own(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z, bool crp) {
+  const int lds = read_switches().loo_lds;
+  const bool staged = st->loo_staged != 0 && (lds < 0 ? nrows >= (uint64_t)kLooRows * kLooThreads * st->ctx->num_cus * 3 / 4 : lds != 0);
   MSC_HIP(grow_retained(st->retired, st->own, nrows));
-  if (launch_loo_own(st->ctx->stream, st->ctx->num_cus, loo_needs_heavy(st), st->loo_staged != 0, st->desc_tile_dev, (int)st->nfeat,
-                     st->K, st->kpad, row0, nrows, z, crp ? st->logpc : nullptr, st->own))
+  if (launch_loo_own(st->ctx->stream, loo_needs_heavy(st), staged, st->desc_tile_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z,
+                     crp ? st->logpc : nullptr, st->own))
     return fail(MSC_EHIP, "k_loo_own launch failed");
   return MSC_OK;
 }
 
+// PAIR mode of the role-split / nich-only / lookups-only kernels: one k-tile of at most 128 groups
+static bool pair_path(ScorePath path, uint32_t K) {
+  return (path == MSC_PATH_TILE_ROLES || path == MSC_PATH_NICH_PACK || path == MSC_PATH_LOOKUPS) && K <= 128;
+}
+
 // K <= 64 and nothing but scalar families whose tables all fit 64 KiB of LDS at 4 L groups per row: the narrow tiling
 // (kernels_sweep.hip k_narrow).  Returns L = lanes per row (4 / 8 / 16) or 0, and the table rows to stage.
-static int narrow_lanes(const msc_state *st, uint32_t *table_rows) {
-  static const bool off = std::getenv("MSC_NO_NARROW") != nullptr;        // (A/B knob; the tests run both tilings)
+static int narrow_lanes(const msc_state *st, const Switches &sw, uint32_t *table_rows) {
   // (32 lanes per row for K <= 128 was measured and loses to the 256-group tiling: 8 bb at K = 100, 0.52 against 0.20 ms)
-  if (off || st->K > 64) return 0;
-  // Views of many rows leave it to the lane <-> row kernel (round 3's; by view_rows: route_sweep's shard rule).  At a million rows that kernel is 1.3-2.7x the faster one (tools/scans/k_monotone.sh, MSC_NO_NARROW:
+  if (st->K > 64) return 0;
+  // Views of many rows leave it to the lane <-> row kernel (round 3's; by view_rows: route_sweep's shard rule).  At a million rows that kernel is 1.3-2.7x the faster one (tools/scans/k_monotone.sh:
   // sixteen dd32 columns at K = 32 0.34 -> 0.13 ms, 8 bb + 8 nich at K = 64 0.48 -> 0.26, sixteen nich at K = 32 0.30 -> 0.18);
   // this tiling is for the small problems it was made for (C1: 10k rows, 8 us a pass): views below kNarrowMaxRows rows.
-  if (view_rows(st) >= kNarrowMaxRows && st->tile_narrow_tail_ok && std::getenv("MSC_TAIL_MIN_ROWS") == nullptr) return 0;
+  if (view_rows(st) >= kNarrowMaxRows && st->tile_narrow_tail_ok && !sw.tail_forced) return 0;
   const int L = st->K <= 16 ? 4 : st->K <= 32 ? 8 : 16;
   uint32_t rows = 0;
   for (uint32_t f = 0; f < st->nfeat; f++) {
@@ -1872,22 +1900,11 @@ static int narrow_lanes(const msc_state *st, uint32_t *table_rows) {
       us += fam == MSC_BB || fam == MSC_BBNC ? 30.0 : fam == MSC_NICH ? 60.0 : fam == MSC_NOOP ? 0.0 : 50.0;
     }
     us *= std::max(L, 8) / 16.0;
-    const bool pair = pair_mode_ok(st->tile_path, st->K, false);
-    const double tile = st->plan_cost.tile_round_us * (1.0e6 / 128.0 / st->ctx->num_cus) * (pair ? kPairTileShare : 1.0);
+    const double tile = st->plan_cost.tile_round_us * (1.0e6 / 128.0 / st->ctx->num_cus) * (pair_path(st->tile_path, st->K) ? kPairTileShare : 1.0);
     if (us > 1.25 * tile) return 0;
   }
   *table_rows = rows;
   return L;
-}
-
-// Which kernels score a state (by the plan and view_rows: route_sweep's shard rule): k_narrow when `lanes` is set
-// (lanes, table_rows: narrow_lanes), else the scalar features' pass on `path`; then every niw feature's own pass
-struct ScoreRoute { int lanes = 0; uint32_t table_rows = 0; ScorePath path = MSC_PATH_TILE; };
-static ScoreRoute route_score(const msc_state *st) {
-  ScoreRoute r;
-  r.lanes = narrow_lanes(st, &r.table_rows);
-  r.path = st->nich1 ? MSC_PATH_NICH1 : st->has_dm ? MSC_PATH_TILE_DM : st->tile_path;
-  return r;
 }
 
 // k_score_nich1's launch shape for a pass of `nrows` x K into `out`: what msc_score_tune remembered for this very
@@ -1899,7 +1916,6 @@ static int nich1_shape_for(msc_context *ctx, const void *out, uint64_t nrows, ui
   int plain = 1;
   for (const msc_context::Placed &p : ctx->placed)
     if (out >= p.base && static_cast<const char *>(out) < static_cast<const char *>(p.base) + p.size) plain = p.nt_fast ? 0 : 1;
-  static const int fixed = [] { const char *e = std::getenv("MSC_NICH1_SHAPE"); return e ? std::atoi(e) : -1; }();
   int shape = -1, by_size = -1;
   for (const msc_context::ShapeEntry &e : ctx->nich1_shapes) {
     if (e.nrows != nrows || e.K != K) continue;
@@ -1911,8 +1927,44 @@ static int nich1_shape_for(msc_context *ctx, const void *out, uint64_t nrows, ui
     if (by_size < 0) by_size = e.shape;
   }
   if (shape < 0) shape = by_size < 0 ? 0 : by_size;
-  if (fixed >= 0 && fixed < kNich1NumShapes) shape = fixed;
   return shape | (plain ? 0x100 : 0);
+}
+
+// Which kernels score `nrows` rows into `out`: k_narrow when `lanes` is set (narrow_lanes: by view_rows), else the scalar
+// features' pass on `path` as `shape` says -- by the call's rows: every shape gives the tile kernels' bits --, then niw's.
+struct ScoreRoute { int lanes = 0; uint32_t table_rows = 0; ScorePath path = MSC_PATH_TILE; ScoreShape shape; };
+static ScoreRoute route_score(const msc_state *st, uint64_t nrows, const void *out) {
+  const Switches sw = read_switches();
+  ScoreRoute r;
+  r.lanes = narrow_lanes(st, sw, &r.table_rows);
+  r.path = st->nich1 ? MSC_PATH_NICH1 : st->has_dm ? MSC_PATH_TILE_DM : st->tile_path;
+  if (r.lanes) return r;
+  if (r.path == MSC_PATH_NICH1) {
+    r.shape.nich1 = nich1_shape_for(st->ctx, out, nrows, st->K);
+    return r;
+  }
+  // few rows: the chunks -- serial chains, feature after feature -- spread over the chip in ONE round at 4 or 2 rows a
+  // wave (4 only while the 64-row workgroups fit one round: 20000 rows made 313 of them, 0.113 ms, where 157 of 128 take one)
+  const int cus = st->ctx->num_cus;
+  const uint32_t ktiles = st->kpad / kGroupTile, last_groups = st->K - (ktiles - 1) * kGroupTile;
+  const uint64_t round = (uint64_t)cus / ktiles;
+  const bool small4 = r.path != MSC_PATH_TILE_DM && (nrows + 63) / 64 <= round, small2 = small4 && (nrows + 31) / 32 <= round;
+  r.shape.wave_rows = small2 ? 2 : small4 ? 4 : 8;
+  r.shape.pair = !small4 && pair_path(r.path, st->K);
+  // a LAST tile of 65 .. 128 groups beyond full ones on the role-split kernels: PAIR mode at that tile (round 5), ~0.62 of a
+  // full tile's price where the lane <-> row kernel takes two or three launches
+  // else the last tile on the lane <-> row kernel when the plan allows and the rows are many (few -- a per-entity call's one
+  // -- are better off with lanes as groups): whichever the cost model of launchers.hpp prices lower for these rows
+  if (ktiles > 1 && r.path == MSC_PATH_TILE_ROLES && !small4 && last_groups > 64 && last_groups <= 128) r.shape.last = LastTile::pair;
+  if (r.shape.last == LastTile::pair || !narrow_tail_fits(st)) return r;
+  const PlanCost &pc = st->plan_cost;
+  const uint64_t c128 = (nrows + 127) / 128;
+  const double tile_us = (r.shape.pair ? kPairTileShare : 1.0) *
+                         (tile_rounds_us(c128 * ktiles, cus, false, pc) - (ktiles > 1 ? tile_rounds_us(c128 * (ktiles - 1), cus, false, pc) : 0.0));
+  const bool many_rows = sw.tail_forced ? nrows >= sw.tail_min_rows
+                                        : nrows >= kTailMinRows && tail_rows_us(last_groups, true, nrows, cus, pc) < tile_us;
+  if (many_rows) r.shape.last = LastTile::rows;
+  return r;
 }
 
 static int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z_dev, bool crp,
@@ -1920,12 +1972,10 @@ static int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t
   hipStream_t s = st->ctx->stream;
   const float *prior = crp ? st->logpc : nullptr;
   if (z_dev) MSC_TRY(run_loo_own(st, row0, nrows, z_dev, crp));
-  const ScoreRoute r = route_score(st);
+  const ScoreRoute r = route_score(st, nrows, out_dev);
   if (r.lanes) {
-    if (launch_narrow(s, st->ctx->num_cus, r.lanes, r.table_rows, false, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows,
-                      z_dev, st->own, prior, out_dev, ld_out, 0, nullptr, nullptr, ZeroSpans()))
-      return fail(MSC_EHIP, "k_narrow launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return MSC_OK;
+    return launch_narrow(s, st->ctx->num_cus, r.lanes, r.table_rows, false, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows,
+                         z_dev, st->own, prior, out_dev, ld_out, 0, nullptr, nullptr, ZeroSpans());
   }
   bool written = false;
   if (st->n_niw < st->nfeat || crp) {
@@ -1935,13 +1985,8 @@ static int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t
       MSC_TRY(tail_plan(st, tail));
       MSC_TRY(refresh_fused_tables(st));
     }
-    // The single-nich pass is bound by the HBM write stream; its launch shape (rows per visit, visits per wave =
-    // write fronts) is the default (4 rows, 2 visits) unless msc_score_tune settled another one for passes like this
-    // (same buffer first, else same size), or MSC_NICH1_SHAPE fixes it.  Nothing here waits for the device.
-    const int shape = nich1 ? nich1_shape_for(st->ctx, out_dev, nrows, st->K) : 0;
-    if (launch_score(s, st->ctx->num_cus, r.path, tail, shape, nich1 ? st->desc_dev : st->desc_fuse_dev, (int)st->fuse_nfeat,
-                     (int)st->fuse_split, st->K, st->kpad, row0, nrows, z_dev, st->own, prior, out_dev, ld_out))
-      return fail(MSC_EHIP, "score kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    MSC_TRY(launch_score(s, st->ctx->num_cus, r.path, tail, r.shape, nich1 ? st->desc_dev : st->desc_fuse_dev, (int)st->fuse_nfeat,
+                         (int)st->fuse_split, st->K, st->kpad, row0, nrows, z_dev, st->own, prior, out_dev, ld_out));
     written = true;
     for (uint32_t f = 0; f < st->nfeat; f++)
       if (gp_beyond_table(st, f) &&
@@ -1988,15 +2033,15 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
   if (ms_out) *ms_out = 0.f;
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  const ScoreRoute r = route_score(st);
+  const ScoreRoute r = route_score(st, nrows, out_dev);
   if (r.lanes || r.path != MSC_PATH_NICH1 || nrows == 0) return MSC_OK;
   MSC_TRY(ensure_derived(st));
   hipStream_t s = st->ctx->stream;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
     return fail(MSC_EINVAL, "msc_score_tune waits for the device: not on a capturing stream");
-  auto launch = [&](int shape) {
-    return launch_score(s, st->ctx->num_cus, MSC_PATH_NICH1, TailPlan(), shape, st->desc_dev, 1, (int)st->tile_split, st->K, st->kpad, row0,
+  auto launch = [&](int code) {
+    return launch_score(s, st->ctx->num_cus, MSC_PATH_NICH1, TailPlan(), ScoreShape{8, false, LastTile::tiles, code}, st->desc_dev, 1, (int)st->tile_split, st->K, st->kpad, row0,
                         nrows, nullptr, nullptr, nullptr, out_dev, ld_out);
   };
   hipEvent_t e0, e1;
@@ -2005,7 +2050,7 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
   float best = 0.f;
   int shape = -1, rc = MSC_OK;
   for (int cand = 0; cand < kNich1NumShapes && rc == MSC_OK; cand++) {
-    if (launch(cand)) { rc = fail(MSC_EHIP, "score kernel launch failed: %s", hipGetErrorString(hipGetLastError())); break; }
+    if ((rc = launch(cand)) != MSC_OK) break;
     hipError_t e = hipEventRecord(e0, s);
     for (int r = 0; r < 6 && e == hipSuccess; r++) (void)launch(cand);
     if (e == hipSuccess) e = hipEventRecord(e1, s);
@@ -2024,7 +2069,7 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
     float ms_kind[2] = {0.f, 0.f};
     for (int kind = 0; kind < 2 && rc == MSC_OK; kind++) {
       const int code = shape | (kind ? 0x100 : 0);
-      if (launch(code)) { rc = fail(MSC_EHIP, "score kernel launch failed: %s", hipGetErrorString(hipGetLastError())); break; }
+      if ((rc = launch(code)) != MSC_OK) break;
       hipError_t e = hipEventRecord(e0, s);
       for (int r = 0; r < 6 && e == hipSuccess; r++) (void)launch(code);
       if (e == hipSuccess) e = hipEventRecord(e1, s);
@@ -2199,11 +2244,11 @@ static bool sweep_is_niw1(const msc_state *st) {
 // PAIR mode of the role-split sweep kernel (at most 128 groups; kernels_sweep.hip): its draw associates a row's entries
 // differently from the other tile kernels'
 static bool sweep_pair_mode(const msc_state *st) {
-  return view_rows(st) >= kTailMinRows && pair_mode_ok(st->tile_path, st->K, false);
+  return view_rows(st) >= kTailMinRows && pair_path(st->tile_path, st->K);
 }
-static bool sweep_rows_pays(const msc_state *st, uint32_t groups) {
+static bool sweep_rows_pays(const msc_state *st, const Switches &sw, uint32_t groups) {
   const uint64_t rows = view_rows(st);
-  if (const char *forced = std::getenv("MSC_TAIL_MIN_ROWS")) return rows >= (uint64_t)std::atoll(forced);
+  if (sw.tail_forced) return rows >= sw.tail_min_rows;
   if (rows < kTailMinRows) return false;
   const int cus = st->ctx->num_cus;
   const uint64_t c128 = (rows + 127) / 128;
@@ -2236,39 +2281,60 @@ static bool sweep_is_fused(const msc_state *st) {
   return st->nich1 ? st->K <= sweep_nich1_rows_max_groups() : st->K <= 256;
 }
 
-// How a sweep assigns a state's rows: the kind sweep_assign_impl switches on, and what that kind needs.
+// How a sweep assigns a state's rows: the kind sweep_assign_impl switches on, and what that kind needs -- every kernel the
+// sweep launches, decided here (the launchers take it as it is).
 // THE SHARD RULE: some kernels add a row's terms in a different order from others, so the choice depends only on the plan
 // and on view_rows (the bound view's, or the whole's a sharded driver announced), never on the call's rows: that is what
-// makes a shard draw the same bits as the whole.  Recomputed on every call (the bound view, the hint and the knobs read
-// here change between calls).  A launcher may still decline a call by its geometry: the caller then falls back.
+// makes a shard draw the same bits as the whole.  (A launch shape that draws the same bits at every row count may follow
+// the call's rows; the test that holds it so is named where it is chosen.)  Recomputed on every call (the bound view, the hint and the switches read
+// here change between calls).
 // (rows: K <= 64, the lane <-> row kernel draws its own row; rows_sampler: up to 128 groups, its scores into 128 floats a
-// row, then the row sampler; roles_tail: 256 < K <= 384, the groups beyond the tile from the narrow kernel into tail_ld
-// floats a row, then the fused kernel over the tile draws over both; generic: chunks scored into scratch, then sampled)
+// row, then the row sampler; roles_tail: 256 < K <= 384, the groups beyond the tile from the narrow kernel -- or, 65 .. 128
+// of them on a role-split plan, the role-split kernel in PAIR mode (tail_pair) -- into tail_ld floats a row, then the fused
+// kernel over the tile draws over both; generic: chunks scored into scratch, then sampled)
 enum class SweepKind { niw1, nich1, nich1_rows, narrow, rows, rows_sampler, mixed, roles_tail, generic };
 struct SweepRoute {
   SweepKind kind = SweepKind::generic;
   int lanes = 0; uint32_t table_rows = 0;   // narrow (narrow_lanes)
-  bool pair = false;                        // rows, rows_sampler, mixed: PAIR mode of the tile kernels (sweep_pair_mode)
+  bool transposed = false;                  // nich1: k_sweep_nich1_t
+  ScoreShape shape;                         // mixed: PAIR mode of the tile kernels (sweep_pair_mode), rows a wave
   uint64_t tail_ld = 0;                     // roles_tail
+  bool tail_pair = false;                   // roles_tail
 };
-static SweepRoute route_sweep(const msc_state *st) {
+static SweepRoute route_sweep(const msc_state *st, uint64_t nrows) {
+  const Switches sw = read_switches();
+  const uint64_t cus = (uint64_t)st->ctx->num_cus;
   SweepRoute r;
   if (sweep_is_niw1(st)) {
     r.kind = SweepKind::niw1;
   } else if (sweep_is_fused(st)) {
-    if (st->nich1) r.kind = st->K > 1024 ? SweepKind::nich1_rows : SweepKind::nich1;
-    else if ((r.lanes = narrow_lanes(st, &r.table_rows)) != 0) r.kind = SweepKind::narrow;
-    else {
-      r.pair = sweep_pair_mode(st);
+    if (st->nich1) {
+      r.kind = st->K > 1024 ? SweepKind::nich1_rows : SweepKind::nich1;
+      // enough rows for a 32-row chunk per wave over most of the chip: the transposed draw (k_sweep_nich1_t; measured ahead
+      // from ~16 k rows on at K = 256 and at K = 1024 alike -- 4 k rows: 15 vs 11 us, 16 k: 15 vs 18, 64 k: 19 vs 30,
+      // 512 k: 74 vs 120).  The two kernels draw different bits: by view_rows.
+      r.transposed = sw.sweep_nich1 == 2 || (sw.sweep_nich1 != 1 && view_rows(st) >= cus * 64);
+    } else if ((r.lanes = narrow_lanes(st, sw, &r.table_rows)) != 0) {
+      r.kind = SweepKind::narrow;
+    } else if (narrow_tail_fits(st) && st->K <= kTailMaxGroups && sweep_rows_pays(st, sw, st->K)) {
+      r.kind = st->K <= 64 ? SweepKind::rows : SweepKind::rows_sampler;
+    } else {
       r.kind = SweepKind::mixed;
-      if (st->tile_narrow_tail_ok && st->K <= kTailMaxGroups && std::getenv("MSC_NO_SWEEP_ROWS") == nullptr && sweep_rows_pays(st, st->K))
-        r.kind = st->K <= 64 ? SweepKind::rows : SweepKind::rows_sampler;
+      r.shape.pair = sweep_pair_mode(st);
+      // Few rows: R = 2 or 4 rows a wave (not 8) spread the chunks over the chip in one round.  k_sweep_tile<R, 16> then
+      // takes the place of a plan's own non-PAIR kernel: by view_rows.  R follows the call's rows: the same bits at every R
+      // (test_gpu_shard_views.py _kernels).
+      const bool small = (nrows + 63) / 64 <= cus, view_small = (view_rows(st) + 63) / 64 <= cus;
+      const int R = small ? ((nrows + 31) / 32 > cus ? 4 : 2) : view_small ? 4 : 8;
+      if (!st->has_dm && (view_small || st->tile_path == MSC_PATH_TILE)) r.shape.wave_rows = R;
     }
   } else if (!st->nich1 && !st->has_dm && st->tile_path != MSC_PATH_TILE && st->tile_narrow_tail_ok && st->K > 256 &&
-             st->K <= (uint32_t)kGroupTile + kTailMaxGroups && std::getenv("MSC_NO_FUSED_TAIL") == nullptr &&
-             sweep_rows_pays(st, st->K - kGroupTile) && sweep_plain(st)) {
-    r.kind = SweepKind::roles_tail;
+             st->K <= (uint32_t)kGroupTile + kTailMaxGroups && sweep_rows_pays(st, sw, st->K - kGroupTile) && sweep_plain(st)) {
     r.tail_ld = st->K <= (uint32_t)kGroupTile + 64 ? 64 : 128;
+    // (65 .. 128 groups beyond the tile on a role-split plan: ONE pass of the role-split kernel in PAIR mode at tile 1
+    // instead of three launches of the lane <-> row kernel -- round 5)
+    r.tail_pair = st->tile_path == MSC_PATH_TILE_ROLES && r.tail_ld == 128;
+    if (r.tail_pair || narrow_tail_fits(st)) r.kind = SweepKind::roles_tail;
   }
   return r;
 }
@@ -2297,51 +2363,47 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
     zero.a = reinterpret_cast<unsigned long long *>(st->red_i64.get()); zero.na = st->n_i64;
     zero.b = reinterpret_cast<unsigned long long *>(st->red_f64.get()); zero.nb = st->n_f64;
   }
-  const SweepRoute r = route_sweep(st);
-  int rc = 0;
+  const SweepRoute r = route_sweep(st, nrows);
   bool zeroes = true;                                   // the kernel emptied the additive tables on its way (with `zeroed`)
-  bool generic = r.kind == SweepKind::generic;          // (or a launcher declined this call: see below)
-  switch (r.kind) {
+  switch (r.kind) {                                     // (the launchers report their own failures)
     case SweepKind::niw1:
-      rc = launch_sweep_niw1(s, cus, st->feats[0].dim, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero);
+      MSC_TRY(launch_sweep_niw1(s, cus, st->feats[0].dim, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero));
       break;
     case SweepKind::nich1_rows:
       MSC_HIP(grow_retained(st->retired, st->rows_table, sweep_nich1_rows_table_floats(st->kpad)));
-      rc = launch_sweep_nich1_rows(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero, st->rows_table);
+      MSC_TRY(launch_sweep_nich1_rows(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->logpc, st->rng_dev, zero, st->rows_table));
       break;
     case SweepKind::nich1:                                // (the single-nich kernel computes the own-group values itself)
-      rc = launch_sweep_nich1(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero);
+      MSC_TRY(launch_sweep_nich1(s, cus, r.transposed, st->desc_dev, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero));
       break;
     case SweepKind::narrow:
       MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
-      rc = launch_narrow(s, cus, r.lanes, r.table_rows, true, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z_dev,
-                         st->own, st->logpc, nullptr, 0, row_id0, z_dev, st->rng_dev, zero);
+      MSC_TRY(launch_narrow(s, cus, r.lanes, r.table_rows, true, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z_dev,
+                            st->own, st->logpc, nullptr, 0, row_id0, z_dev, st->rng_dev, zero));
       break;
-    case SweepKind::rows:
-    case SweepKind::rows_sampler:
     case SweepKind::mixed:
       MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
       MSC_TRY(refresh_fused_tables(st));                  // (these walk the fused plan)
-      rc = 1;
-      if (r.kind != SweepKind::mixed) {
-        TailPlan tail;
-        MSC_TRY(tail_plan(st, tail, false));
-        if (r.kind == SweepKind::rows) {
-          rc = launch_sweep_rows(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0,
-                                 z_dev, st->own, st->logpc, st->rng_dev, zero);
-        } else {
-          MSC_HIP(grow_retained(st->retired, st->tail_scores, ((size_t)nrows + 16) * 128));
-          rc = launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, 0, row0, nrows,
-                                 z_dev, st->own, st->logpc, st->tail_scores, 128);
-          if (rc == 0) {
-            rc = launch_sample_rows(s, cus, st->tail_scores, 128, st->K, nrows, row_id0, z_dev, st->rng_dev);
-            zeroes = false;                               // (nothing emptied the additive tables on the way)
-          }
-        }
-      }
-      if (rc == 1)                                        // (mixed, or the lane <-> row kernel declined this call's rows)
-        rc = launch_sweep_mixed(s, cus, st->has_dm, st->tile_path, r.pair, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero);
+      MSC_TRY(launch_sweep_mixed(s, cus, st->has_dm, st->tile_path, r.shape, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero));
       break;
+    case SweepKind::rows:
+    case SweepKind::rows_sampler: {
+      MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
+      MSC_TRY(refresh_fused_tables(st));
+      TailPlan tail;
+      MSC_TRY(tail_plan(st, tail, false));
+      if (r.kind == SweepKind::rows) {
+        MSC_TRY(launch_sweep_rows(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0,
+                                  z_dev, st->own, st->logpc, st->rng_dev, zero));
+        break;
+      }
+      MSC_HIP(grow_retained(st->retired, st->tail_scores, ((size_t)nrows + 16) * 128));
+      MSC_TRY(launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, 0, row0, nrows,
+                                z_dev, st->own, st->logpc, st->tail_scores, 128));
+      if (launch_sample_rows(s, cus, st->tail_scores, 128, st->K, nrows, row_id0, z_dev, st->rng_dev)) return fail(MSC_EHIP, "k_sample_rows launch failed");
+      zeroes = false;                                     // (nothing emptied the additive tables on the way)
+      break;
+    }
     case SweepKind::roles_tail: {
       MSC_TRY(refresh_fused_tables(st));
       MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
@@ -2350,48 +2412,36 @@ static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint
       // group: nothing else scores these groups for a draw)
       TailPlan tail;
       MSC_TRY(tail_plan(st, tail, false));
-      // (65 .. 128 groups beyond the tile on a role-split plan: ONE pass of the role-split kernel in PAIR mode at tile 1
-      // instead of three launches of the lane <-> row kernel -- round 5)
-      int tail_rc = -2;
-      if (st->tile_path == MSC_PATH_TILE_ROLES && r.tail_ld == 128 && std::getenv("MSC_NO_PAIR") == nullptr)
-        tail_rc = launch_score_pair_tail(s, cus, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
-                                         z_dev, st->own, st->logpc, st->tail_scores, r.tail_ld);
-      if (tail_rc == -2)
-        tail_rc = launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad,
-                                    kGroupTile, row0, nrows, z_dev, st->own, st->logpc, st->tail_scores - kGroupTile, r.tail_ld);
-      if (tail_rc == 0)
-        rc = launch_sweep_roles_tail(s, cus, st->tile_path, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
-                                     row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero, st->tail_scores);
-      else generic = true;                                 // (the tail kernels declined this call's rows)
+      MSC_TRY(r.tail_pair ? launch_score_pair_tail(s, cus, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
+                                                   z_dev, st->own, st->logpc, st->tail_scores, r.tail_ld)
+                          : launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad,
+                                              kGroupTile, row0, nrows, z_dev, st->own, st->logpc, st->tail_scores - kGroupTile, r.tail_ld));
+      MSC_TRY(launch_sweep_roles_tail(s, cus, st->tile_path, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
+                                      row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero, st->tail_scores));
       break;
     }
-    case SweepKind::generic: break;
-  }
-  if (generic || rc == -2) {                             // (-2: launch_sweep_niw1 / _nich1 / _mixed, launch_narrow declined)
-    // score a chunk of rows (leave-one-out + prior) into scratch, then sample it
-    // (rows of K rounded up to 64 floats, not of the padded table width: at K = 300 the chunk is 320 wide, not 512 --
-    // neither the score kernels nor the sampler touch a row beyond K)
-    const uint64_t ld = std::min<uint64_t>(st->kpad, ((uint64_t)st->K + 63) & ~63ull);
-    // Up to 4 GiB of scores per chunk (288 GB of HBM: the scratch is not what runs out): fewer and larger launches beat
-    // keeping the chunk cache-resident (single nich, 1M rows x 300 groups, 32 / 64 / 128 / 256 / 512 MiB: 1.88 / 1.55 /
-    // 1.28 / 1.13 / 1.05 ms), a state with niw features wants >= 4 waves per SIMD on its MFMA kernel, and the
-    // leave-one-out pass takes its staged kernel only when the rows fill the chip -- C3's columns at K = 512, 1M rows:
-    // 5.39 ms a sweep step with 256 MiB chunks (eight of them), 4.95 with 1 GiB, 4.63 with the whole 2 GiB at once
-    static const uint64_t forced_mib = std::getenv("MSC_SWEEP_CHUNK_MIB") ? std::strtoull(std::getenv("MSC_SWEEP_CHUNK_MIB"), nullptr, 10) : 0;
-    uint64_t chunk = ((forced_mib ? forced_mib : 4096ull) << 20) / (ld * sizeof(float));
-    if (chunk == 0) chunk = 1;
-    if (chunk > nrows) chunk = nrows;
-    MSC_HIP(grow_retained(st->retired, st->scratch, chunk * ld));
-    for (uint64_t at = 0; at < nrows; at += chunk) {
-      const uint64_t n = std::min<uint64_t>(chunk, nrows - at);
-      MSC_TRY(run_score(st, row0 + at, n, z_dev + at, true, false, st->scratch, ld));
-      if (launch_sample_rows(s, cus, st->scratch, ld, st->K, n, row_id0 + at, z_dev + at, st->rng_dev))
-        return fail(MSC_EHIP, "k_sample_rows launch failed");
+    case SweepKind::generic: {
+      // score a chunk of rows (leave-one-out + prior) into scratch, then sample it
+      // (rows of K rounded up to 64 floats, not of the padded table width: at K = 300 the chunk is 320 wide, not 512 --
+      // neither the score kernels nor the sampler touch a row beyond K)
+      const uint64_t ld = std::min<uint64_t>(st->kpad, ((uint64_t)st->K + 63) & ~63ull);
+      // Up to 4 GiB of scores per chunk (288 GB of HBM: the scratch is not what runs out): fewer and larger launches beat
+      // keeping the chunk cache-resident (single nich, 1M rows x 300 groups, 32 / 64 / 128 / 256 / 512 MiB: 1.88 / 1.55 /
+      // 1.28 / 1.13 / 1.05 ms), a state with niw features wants >= 4 waves per SIMD on its MFMA kernel, and the
+      // leave-one-out pass takes its staged kernel only when the rows fill the chip -- C3's columns at K = 512, 1M rows:
+      // 5.39 ms a sweep step with 256 MiB chunks (eight of them), 4.95 with 1 GiB, 4.63 with the whole 2 GiB at once
+      const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((4096ull << 20) / (ld * sizeof(float)), nrows));
+      MSC_HIP(grow_retained(st->retired, st->scratch, chunk * ld));
+      for (uint64_t at = 0; at < nrows; at += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, nrows - at);
+        MSC_TRY(run_score(st, row0 + at, n, z_dev + at, true, false, st->scratch, ld));
+        if (launch_sample_rows(s, cus, st->scratch, ld, st->K, n, row_id0 + at, z_dev + at, st->rng_dev))
+          return fail(MSC_EHIP, "k_sample_rows launch failed");
+      }
+      zeroes = false;
+      break;
     }
-    rc = 0;
-    zeroes = false;
   }
-  if (rc) return fail(MSC_EHIP, "sweep kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
   if (zeroed) {
     *zeroed = zeroes;
     return MSC_OK;
@@ -2459,8 +2509,7 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
   msc_state::StepGraph &g = st->step_graph;
   // Replay is opt-in: on ROCm 7.2 / MI355X a graph launch of the step's 3-5 kernels measured 4-5 us SLOWER than
   // launching them (27 -> 32 us at N = 10k), and instantiation costs milliseconds (sweep step).
-  const char *gv = std::getenv("MSC_SWEEP_GRAPH");
-  const bool no_graph = gv == nullptr || gv[0] == '0' || gv[0] == 0;
+  const bool no_graph = !read_switches().sweep_graph;
   if (nrows == 0) return accumulate_impl(st, view, cols, row0, 0, z_dev, MSC_ACC_RESET);   // (no row draws anything)
   if (no_graph || g.disabled) return eager();
   std::vector<uint32_t> colv(st->nfeat);

@@ -337,7 +337,6 @@ __global__ __launch_bounds__(256) void k_loo_own(const FeatDesc *__restrict__ fe
 // 128 KiB slot): the block copy is coalesced, the per-row reads are LDS reads at the lane's own address.  (Two workgroups
 // of 512 threads with 64 KiB each, covering each other's copies: 149 us on C3 against 140 -- twice the stages.)  Same terms, same order of the double sum as k_loo_own: same bits.
 // ---------------------------------------------------------------------------
-constexpr int kLooRows = 4, kLooThreads = 1024;      // (kLooStageFeats: msc_internal.hpp)
 template <bool HEAVY>
 __global__ __launch_bounds__(kLooThreads) void k_loo_own_lds(const FeatDesc *__restrict__ feats,
                                                               int nfeat, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows,
@@ -489,8 +488,7 @@ __global__ __launch_bounds__(256) void k_score_nich1(const FeatDesc *__restrict_
   const float *xcol = reinterpret_cast<const float *>(fd.col) + row0;
   // everything the wave's rows need, fetched at once: lane i holds row r = i % Q of visit k = i / Q
   // (a spread launch order -- the resident waves writing S windows far apart instead of one dense one -- and the stores'
-  // cache policies were measured in round 4 and are kept as a patch: tools/microbench/r04_store_policy_experiment.patch,
-  // profiles/r04_spread_store.txt, r04_store_policy.txt)
+  // cache policies were measured in round 4 and not kept: profiles/r04_spread_store.txt, r04_store_policy.txt)
   const uint64_t nblocks = (nrows + Q - 1) / Q;
   const uint32_t nvis = (uint32_t)((nblocks + nslots - 1) / nslots);      // <= 64 / Q (launcher)
   const uint32_t vk = (uint32_t)lane / Q, vr = (uint32_t)lane % Q;
@@ -1068,17 +1066,9 @@ int launch_crp_prepare(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_loo_own(hipStream_t stream, int num_cus, bool heavy, bool staged, const FeatDesc *feats_dev, int nfeat, uint32_t K,
+int launch_loo_own(hipStream_t stream, bool heavy, bool staged, const FeatDesc *feats_dev, int nfeat, uint32_t K,
                    uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z, const float *crp, float *own) {
-  // staged: the plan has features whose leave-one-out blocks fit the LDS slot (abi.cpp plan_groups).  A workgroup of the
-  // staged kernel takes as long for its 4096 rows as the plan has stages (~10 us each) however many workgroups run, so it
-  // pays once the rows (nearly) fill the chip -- C3, 1M rows: 140 us staged, 196 us gathered; below about three quarters
-  // of a workgroup per CU the gather kernel's time, which falls with the rows, is the shorter one (a 131k-row chunk:
-  // 0.33 ms staged against 0.03 ms gathered)
-  const char *knob = std::getenv("MSC_LOO_LDS");            // 0 / 1: A/B knob, read per call (the tests pin either kernel)
-  const int lds_mode = knob ? std::atoi(knob) : -1;
-  const bool use_lds = staged && (lds_mode < 0 ? nrows >= (uint64_t)kLooRows * kLooThreads * (uint64_t)num_cus * 3 / 4 : lds_mode != 0);
-  if (use_lds) {
+  if (staged) {
     static unsigned long long attr_devices = 0;
     if (first_use_on_device(attr_devices)) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_loo_own_lds<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLooSlotFloats * 4);
@@ -1112,14 +1102,6 @@ int launch_gp_large_fix(hipStream_t stream, int num_cus, const FeatDesc *feats_d
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// PAIR mode of the role-split kernels: one k-tile of at most 128 groups, rows enough for the role-split kernels at all
-// (the A/B switch between these kernels and the ones that run the phases one after the other is the plan's: MSC_NO_ROLES,
-// abi.cpp plan_groups)
-bool pair_mode_ok(ScorePath path, uint32_t K, bool few_rows) {
-  static const bool off = std::getenv("MSC_NO_PAIR") != nullptr;     // (A/B knob)
-  return !off && (path == MSC_PATH_TILE_ROLES || path == MSC_PATH_NICH_PACK || path == MSC_PATH_LOOKUPS) && K <= 128 && !few_rows;
-}
-
 // (blocks of one row, like a memset's, lose in this kernel although they win as a bare fill: a wave that visits only a few
 // rows does not pay for loading the group constants, and with many visits the fronts are too many)
 const Nich1Shape kNich1Shapes[kNich1NumShapes] = {{4, 2}, {4, 1}, {4, 4}, {4, 6}, {4, 3}, {4, 8}, {4, 5}, {4, 12}};
@@ -1140,8 +1122,7 @@ const Nich1Shape kNich1Shapes[kNich1NumShapes] = {{4, 2}, {4, 1}, {4, 4}, {4, 6}
 // so a shard reproduces the whole.  (Round 3's first version had the lanes as (row slot, group quad) with the row values
 // broadcast by shuffles: 1.08 ms for C3's tail of 44 groups; this one 0.46 ms -- tools/microbench/README.md.)
 // ---------------------------------------------------------------------------
-constexpr int kTailRowsWaves = 8;                     // 512 rows per workgroup visit
-constexpr uint32_t kTailStride = 65;                   // floats per staged table row (64 groups + 1)
+constexpr int kTailRowsWaves = 8;                     // 512 rows per workgroup visit (kTailStride: launchers.hpp)
 
 // table rows a first-phase feature brings to the slot: a lookup feature's selectable rows; none for a masked nich column
 // (the one generic kind the plan admits there: evaluated like the second phase's, under the row's mask)
@@ -1505,14 +1486,13 @@ static void launch_tail_rows_t(hipStream_t stream, unsigned grid, size_t lds, in
   else launch_tail_rows_m<TGP, SPLIT, DRAW, false, EST>(stream, grid, lds, feats_dev, nfeat, nsplit, K, kpad, k0, row0, nrows, z, own, crp, out, ld, pack, cap_rows, kend, rng, row_id0, zero);
 }
 
-// the geometry the launches of one pass share; false: not for this kernel
+// the geometry the launches of one pass share; false: the plan is not for this kernel (abi.cpp never routes it here)
 static bool tail_rows_geometry(const TailPlan &tp, int num_cus, int nfeat, int nsplit, uint64_t nrows, uint32_t &cap_rows, size_t &lds,
                                unsigned &grid) {
   if (!tp.ok || (tp.pack_rows > 0 && tp.pack == nullptr)) return false;
   // the slot: up to 200 table rows (52 KiB) in what 64 KiB leave beside the second phase's block (64 floats a nich
-  // feature) -- two workgroups a CU; it must hold the largest table
+  // feature) -- two workgroups a CU; it holds the largest table (abi.cpp narrow_tail_fits)
   const size_t nich_bytes = (size_t)(nfeat - nsplit) * 64 * sizeof(float);
-  if (nich_bytes + (size_t)std::max<uint32_t>(1u, tp.max_rows) * kTailStride * sizeof(float) > 64u * 1024u) return false;
   const uint32_t fit = (uint32_t)((64u * 1024u - nich_bytes) / (kTailStride * sizeof(float)));
   cap_rows = std::max<uint32_t>(1u, std::min<uint32_t>(tp.pack_rows, std::min<uint32_t>(200u, fit)));
   lds = (size_t)cap_rows * kTailStride * sizeof(float) + nich_bytes;
@@ -1523,14 +1503,14 @@ static bool tail_rows_geometry(const TailPlan &tp, int num_cus, int nfeat, int n
 }
 
 // a state of at most 64 groups: leave-one-out + prior scores and the draw in one launch of the lane <-> row kernel (own from
-// launch_loo_own; zero: the additive tables a sweep step wants emptied).  -> 0: launched; 1: not for this kernel
+// launch_loo_own; zero: the additive tables a sweep step wants emptied)
 int launch_sweep_rows(hipStream_t stream, int num_cus, const TailPlan &tp, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,
                       uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z, const float *own, const float *crp,
                       const uint64_t *rng, ZeroSpans zero) {
   uint32_t cap_rows = 0;
   size_t lds = 0;
   unsigned grid = 0;
-  if (K > 64 || crp == nullptr || !tail_rows_geometry(tp, num_cus, nfeat, nsplit, nrows, cap_rows, lds, grid)) return 1;
+  if (K > 64 || crp == nullptr || !tail_rows_geometry(tp, num_cus, nfeat, nsplit, nrows, cap_rows, lds, grid)) return fail(MSC_EHIP, "launch_sweep_rows: K = %u", K);
   if (nsplit > 0) hipLaunchKernelGGL(k_tail_pack, dim3((unsigned)nsplit), dim3(256), 0, stream, feats_dev, kpad, 0u, tp.pack);
   const uint32_t tgp = (K + 15u) / 16u * 16u;
 #define MSC_SWEEP_ROWS(T) launch_tail_rows_t<T, false, true, true>(stream, grid, lds, tp.dm ? 2 : tp.masked_nich ? 1 : 0, feats_dev, nfeat, nsplit, K, kpad, 0u, row0, nrows, z, own, crp, nullptr, 0, tp.pack, cap_rows, K, rng, row_id0, zero)
@@ -1540,10 +1520,9 @@ int launch_sweep_rows(hipStream_t stream, int num_cus, const TailPlan &tp, const
   else if (tgp == 48) MSC_SWEEP_ROWS(48);
   else MSC_SWEEP_ROWS(64);
 #undef MSC_SWEEP_ROWS
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("k_score_tail_rows");
 }
 
-// -> 0: launched; 1: the groups are not for this kernel (the caller's tile kernels take them)
 int launch_score_tail(hipStream_t stream, int num_cus, const TailPlan &tp, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,
                       uint32_t kpad, uint32_t k0, uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp,
                       float *out, uint64_t ld) {
@@ -1552,7 +1531,7 @@ int launch_score_tail(hipStream_t stream, int num_cus, const TailPlan &tp, const
   uint32_t cap_rows = 0;
   size_t lds = 0;
   unsigned grid = 0;
-  if (K <= k0 || K - k0 > kTailMaxGroups || !tail_rows_geometry(tp, num_cus, nfeat, nsplit, nrows, cap_rows, lds, grid)) return 1;
+  if (K <= k0 || K - k0 > kTailMaxGroups || !tail_rows_geometry(tp, num_cus, nfeat, nsplit, nrows, cap_rows, lds, grid)) return fail(MSC_EHIP, "launch_score_tail: K = %u", K);
   if (nrows == 0) return 0;
   // launches of equal width; with two sums a group (exact) at most 32 groups a launch -- the 48-group instantiation holds 96
   // sums a lane and costs a light plan 2.8x a 32-group launch (8 bb columns, 1M rows: K = 48 0.22 ms, K = 64 = 32 + 32 0.16;
@@ -1576,11 +1555,11 @@ int launch_score_tail(hipStream_t stream, int num_cus, const TailPlan &tp, const
     }
 #undef MSC_TAIL_ROWS
   }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("k_score_tail_rows");
 }
 
 template <bool LOO, bool CRP>
-static void launch_score_t(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, int nich1_shape, const FeatDesc *feats_dev,
+static int launch_score_t(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, const ScoreShape &shape, const FeatDesc *feats_dev,
                            int nfeat, int nsplit, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows,
                            const int32_t *z, const float *own, const float *crp, float *out, uint64_t ld) {
   const uint32_t ktiles = kpad / kGroupTile;
@@ -1590,9 +1569,9 @@ static void launch_score_t(hipStream_t stream, int num_cus, ScorePath path, cons
     // Which (Q, visits) suits the HBM write stream depends on the box and on where the score buffer landed
     // (profiles/r01_nich1_variants.txt); abi.cpp run_score times the shapes of kNich1Shapes at the first large
     // pass of a context and passes the winner's index here (0 = the default).
-    // (nich1_shape: the shape's index; bit 8: plain stores instead of non-temporal ones -- abi.cpp nich1_shape_for)
-    const bool plain_stores = (nich1_shape & 0x100) != 0;
-    nich1_shape &= 0xff;
+    // (shape.nich1: the shape's index; bit 8: plain stores instead of non-temporal ones -- abi.cpp nich1_shape_for)
+    const bool plain_stores = (shape.nich1 & 0x100) != 0;
+    const int nich1_shape = shape.nich1 & 0xff;
     const Nich1Shape sh = kNich1Shapes[nich1_shape >= 0 && nich1_shape < kNich1NumShapes ? nich1_shape : 0];
     const uint64_t nvisits_all = (nrows + sh.q - 1) / sh.q;
     const uint64_t max_slots = ((uint64_t)1 << 32) / ktiles;          // keeps grid.x below 2^30 workgroups
@@ -1611,47 +1590,19 @@ static void launch_score_t(hipStream_t stream, int num_cus, ScorePath path, cons
     // one workgroup per CU (2 x 64 KiB of LDS), 128 rows per workgroup, two tilings:
     // 16 waves x 8 rows (4 waves/SIMD, default) or 8 waves x 16 rows (2 waves/SIMD)
     // states with a dm feature: 8 waves x 8 rows (64 rows per workgroup, 256-register budget for the hi/lo sums)
-    // few rows: a chunk is a serial chain (feature after feature, the code fetched once), so what counts is that
-    // the chunks spread over the chip in ONE round: 4 or 2 rows per wave while that still fits
     const bool dm = path == MSC_PATH_TILE_DM;
-    const uint64_t round = (uint64_t)num_cus / ktiles;
-    constexpr uint64_t rounds4 = 1;
-    // (4 rows per wave only while the 64-row workgroups themselves fit one round: 20000 rows made 313 of them -- two
-    // rounds, 0.113 ms -- where 157 workgroups of 128 rows take one)
-    const bool small4 = !dm && (nrows + 63) / 64 <= round * rounds4, small2 = small4 && (nrows + 31) / 32 <= round;
-    const uint64_t rows_per_wg = dm ? 64 : small2 ? 32 : small4 ? 64 : 128;
-    const uint64_t nchunks = (nrows + rows_per_wg - 1) / rows_per_wg;
-    uint64_t gx = nchunks;
-    const uint64_t cap = (uint64_t)num_cus * 4;
-    if (gx > cap) gx = cap;
-    if (gx == 0) gx = 1;
-    // the last tile alone on the lane <-> row kernel when it is partly filled and the plan allows (flag from abi.cpp) and
-    // the rows are many: its bits are the tile kernels', so the choice is free; few rows (a per-entity call's one) are
-    // better off with lanes as groups.  A state of at most kTailMaxGroups groups is all "last tile".
-    // (it fills the chip from ~260k rows on, 512 a workgroup, where the tile kernels run in rounds of 128 rows a CU:
-    // whichever the cost model of launchers.hpp prices lower for these rows -- the last tile's share of the tile pass
-    // against the launches of the lane <-> row kernel)
-    const char *forced = std::getenv("MSC_TAIL_MIN_ROWS");          // (tests: the kernel on a few thousand rows)
-    const uint64_t c128 = (nrows + 127) / 128;
-    // (a state of at most 128 groups on the role-split kernels: PAIR mode, 256 rows a workgroup at about the price of 128)
-    const bool pair = pair_mode_ok(path, K, small4);
-    const double tile_us = (pair ? kPairTileShare : 1.0) *
-                           (tile_rounds_us(c128 * ktiles, num_cus, false, narrow_tail.cost) - (ktiles > 1 ? tile_rounds_us(c128 * (ktiles - 1), num_cus, false, narrow_tail.cost) : 0.0));
-    const bool many_rows = forced ? nrows >= (uint64_t)std::atoll(forced)
-                                  : nrows >= kTailMinRows && tail_rows_us(K - (ktiles - 1) * kGroupTile, true, nrows, num_cus, narrow_tail.cost) < tile_us;
-    // a LAST tile of 65 .. 128 groups beyond full ones on the role-split kernels: PAIR mode at that tile (round 5) -- about
-    // 0.62 of a full tile's price, the tile kernels' own bits, where the lane <-> row kernel takes two or three launches
-    const uint32_t last_groups = K - (ktiles - 1) * kGroupTile;
-    bool tail = false;
-    if (ktiles > 1 && path == MSC_PATH_TILE_ROLES && !small4 && last_groups > 64 && last_groups <= 128 && pair_mode_ok(path, last_groups, false)) {
+    const bool small4 = shape.wave_rows < 8, small2 = shape.wave_rows == 2, pair = shape.pair;
+    const uint64_t rows_per_wg = dm ? 64 : 16 * (uint64_t)shape.wave_rows, cap = (uint64_t)num_cus * 4;
+    const uint64_t gx = std::max<uint64_t>(1, std::min<uint64_t>((nrows + rows_per_wg - 1) / rows_per_wg, cap));
+    const bool tail = shape.last != LastTile::tiles;
+    if (shape.last == LastTile::pair) {
       hipLaunchKernelGGL((k_score_tile_roles<LOO, CRP, true>), (note_kernel(0, "k_score_tile_roles<%s, %s, true>", tf(LOO), tf(CRP)), dim3((unsigned)std::min<uint64_t>((nrows + 255) / 256, cap), 1)), dim3(1024), 0, stream,
                          feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out + (size_t)(ktiles - 1) * kGroupTile, ld, ktiles - 1);
-      tail = true;
+    } else if (shape.last == LastTile::rows) {
+      MSC_TRY(launch_score_tail(stream, num_cus, narrow_tail, feats_dev, nfeat, nsplit, K, kpad, (ktiles - 1) * kGroupTile, row0, nrows, z, own,
+                                crp, out, ld));
     }
-    if (!tail)
-      tail = many_rows && launch_score_tail(stream, num_cus, narrow_tail, feats_dev, nfeat, nsplit, K, kpad,
-                                            (ktiles - 1) * kGroupTile, row0, nrows, z, own, crp, out, ld) == 0;
-    if (tail && ktiles == 1) return;
+    if (tail && ktiles == 1) return 0;
     const dim3 grid((unsigned)gx, tail ? ktiles - 1 : ktiles);
     if (path == MSC_PATH_TILE_DM)
       hipLaunchKernelGGL((k_score_tile<8, 8, LOO, CRP, true>), (note_kernel(0, "k_score_tile<8, 8, %s, %s, true>", tf(LOO), tf(CRP)), grid), dim3(512), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0,
@@ -1694,6 +1645,7 @@ static void launch_score_t(hipStream_t stream, int num_cus, ScorePath path, cons
       hipLaunchKernelGGL((k_score_tile<8, 16, LOO, CRP, false>), (note_kernel(0, "k_score_tile<8, 16, %s, %s, false>", tf(LOO), tf(CRP)), grid), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0,
                          nrows, z, own, crp, out, ld);
   }
+  return launch_status("score kernel");
 }
 
 // The groups 256 .. K - 1 (65 .. 128 of them) of a role-split plan, leave-one-out value and prior included, into
@@ -1701,23 +1653,22 @@ static void launch_score_t(hipStream_t stream, int num_cus, ScorePath path, cons
 // full tile's price where the lane <-> row kernel took three launches of up to 48 groups.  The tile kernels' sums.
 int launch_score_pair_tail(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K, uint32_t kpad,
                            uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp, float *tail, uint64_t ld) {
-  if (K <= (uint32_t)kGroupTile + 64u || K > (uint32_t)kGroupTile + 128u || z == nullptr || crp == nullptr) return -2;
+  if (K <= (uint32_t)kGroupTile + 64u || K > (uint32_t)kGroupTile + 128u || z == nullptr || crp == nullptr) return fail(MSC_EHIP, "launch_score_pair_tail: K = %u", K);
   const uint64_t cap = (uint64_t)num_cus * 4;
   hipLaunchKernelGGL((k_score_tile_roles<true, true, true>), (note_kernel(0, "k_score_tile_roles<true, true, true>"), dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nrows + 255) / 256, cap)), 1)),
                      dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, tail, ld, 1u);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("k_score_tile_roles");
 }
 
 // own: per-row leave-one-out values from launch_loo_own (required when z != null)
-int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, int nich1_shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
+int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, const ScoreShape &shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
                  uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z,
                  const float *own, const float *crp, float *out, uint64_t ld) {
   const bool loo = z != nullptr, pri = crp != nullptr;
-  if (loo && pri) launch_score_t<true, true>(stream, num_cus, path, narrow_tail, nich1_shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
-  else if (loo) launch_score_t<true, false>(stream, num_cus, path, narrow_tail, nich1_shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
-  else if (pri) launch_score_t<false, true>(stream, num_cus, path, narrow_tail, nich1_shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
-  else launch_score_t<false, false>(stream, num_cus, path, narrow_tail, nich1_shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  if (loo && pri) return launch_score_t<true, true>(stream, num_cus, path, narrow_tail, shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
+  if (loo) return launch_score_t<true, false>(stream, num_cus, path, narrow_tail, shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
+  if (pri) return launch_score_t<false, true>(stream, num_cus, path, narrow_tail, shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
+  return launch_score_t<false, false>(stream, num_cus, path, narrow_tail, shape, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, z, own, crp, out, ld);
 }
 
 }  // namespace msc

@@ -949,7 +949,7 @@ MSC_DEFINE_BIND_ERROR_WORD(bind_error_word_sweep)
 int launch_sweep_niw1(hipStream_t stream, int num_cus, uint32_t dim, const FeatDesc *feats_dev, uint32_t K, uint32_t kpad,
                       uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z, const float *crp, const uint64_t *rng,
                       ZeroSpans zero) {
-  if ((int)K > sweep_niw1_max_groups(dim)) return -2;
+  if ((int)K > sweep_niw1_max_groups(dim)) return fail(MSC_EHIP, "launch_sweep_niw1: K = %u at dim %u was routed here", K, dim);
 #define MSC_NIW1(Dv, Gv) launch_sweep_niw1_t<Dv, Gv>(stream, num_cus, feats_dev, K, kpad, row0, nrows, row_id0, z, crp, rng, zero)
 #define MSC_NIW1_G(Dv)                \
   if (K <= 64) MSC_NIW1(Dv, 1);       \
@@ -967,11 +967,11 @@ int launch_sweep_niw1(hipStream_t stream, int num_cus, uint32_t dim, const FeatD
     case 6: MSC_NIW1(6, 1); break;
     case 7: MSC_NIW1(7, 1); break;
     case 8: MSC_NIW1(8, 1); break;
-    default: return -2;
+    default: return fail(MSC_EHIP, "launch_sweep_niw1: dim %u was routed here", dim);
   }
 #undef MSC_NIW1_G
 #undef MSC_NIW1
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("k_sweep_niw1");
 }
 
 // ---------------------------------------------------------------------------
@@ -1603,20 +1603,18 @@ __global__ __launch_bounds__(256) void k_narrow(const FeatDesc *__restrict__ fea
   }
 }
 
-static size_t g_narrow_lds_limit = 64 * 1024;
 template <int L, int S, bool SWEEP>
 static int launch_narrow_s(hipStream_t stream, uint64_t gx, size_t lds_bytes, const FeatDesc *feats_dev, int nfeat, uint32_t K,
                            uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp,
                            float *out, uint64_t ld, uint64_t row_id0, int32_t *z_out, const uint64_t *rng, ZeroSpans zero) {
   hipLaunchKernelGGL((k_narrow<L, S, SWEEP>), dim3((unsigned)(gx ? gx : 1)), dim3(256), lds_bytes, stream, feats_dev, nfeat, K, kpad,
                      row0, nrows, z, own, crp, out, ld, row_id0, z_out, rng, zero);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("k_narrow");
 }
 template <int L, bool SWEEP>
 static int launch_narrow_t(hipStream_t stream, int num_cus, size_t lds_bytes, const FeatDesc *feats_dev, int nfeat, uint32_t K,
                            uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp,
                            float *out, uint64_t ld, uint64_t row_id0, int32_t *z_out, const uint64_t *rng, ZeroSpans zero) {
-  if (lds_bytes > g_narrow_lds_limit) return -2;
   const uint64_t steps = (nrows + 64 / L - 1) / (64 / L);
   const uint64_t cap = (uint64_t)num_cus * 8;
   // 8 steps per wave visit once that still leaves ~4 waves per SIMD of work; few rows: one step each, spread out
@@ -1629,7 +1627,7 @@ static int launch_narrow_t(hipStream_t stream, int num_cus, size_t lds_bytes, co
   if (gx > cap) gx = cap;
   return launch_narrow_s<L, 1, SWEEP>(stream, gx, lds_bytes, feats_dev, nfeat, K, kpad, row0, nrows, z, own, crp, out, ld, row_id0, z_out, rng, zero);
 }
-// lanes_per_row: 4, 8 or 16 (abi.cpp narrow_lanes); table_rows: sum over features of narrow_table_rows
+// lanes_per_row: 4, 8 or 16; table_rows: sum over features of narrow_table_rows (abi.cpp narrow_lanes: within 64 KiB)
 int launch_narrow(hipStream_t stream, int num_cus, int lanes_per_row, uint32_t table_rows, bool sweep, const FeatDesc *feats_dev,
                   int nfeat, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z, const float *own,
                   const float *crp, float *out, uint64_t ld, uint64_t row_id0, int32_t *z_out, const uint64_t *rng,
@@ -1820,20 +1818,14 @@ int launch_sweep_nich1_rows(hipStream_t stream, int num_cus, const FeatDesc *fea
   if (gx == 0) gx = 1;
   hipLaunchKernelGGL(k_sweep_nich1_rows, dim3((unsigned)gx), dim3(128), 0, stream, feats_dev, K, kpad, row0, nrows, row_id0,
                      z, crp, rng, zero, table, g.B, g.nb);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("k_sweep_nich1_rows");
 }
 
-int launch_sweep_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, uint32_t K,
+int launch_sweep_nich1(hipStream_t stream, int num_cus, bool transposed, const FeatDesc *feats_dev, uint32_t K,
                        uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z,
                        const float *own, const float *crp, const uint64_t *rng, ZeroSpans zero) {
-  // enough rows for a 32-row chunk per wave over most of the chip: the transposed draw (k_sweep_nich1_t)
-  // MSC_SWEEP_NICH1 = 1 / 2 pins the row-at-a-time / the transposed kernel whatever the size (tests, A/B timing)
-  const char *pin = std::getenv("MSC_SWEEP_NICH1");
-  const int which = pin ? std::atoi(pin) : 0;
-  // (measured: the transposed kernel is ahead from ~16 k rows on at K = 256 and at K = 1024 alike -- 4 k rows: 15 vs 11 us,
-  // 16 k: 15 vs 18, 64 k: 19 vs 30, 512 k: 74 vs 120)
-  const bool transposed = which == 2 || (which != 1 && nrows >= (uint64_t)num_cus * 64);
-  if (transposed && K <= 1024) {
+  if (K > 1024) return fail(MSC_EHIP, "launch_sweep_nich1: K = %u was routed here", K);
+  if (transposed) {
     // one wave per slot the registers leave (4 / 3 / 2 a SIMD for G <= 4 / 8 / 16): the waves split the rows evenly
     const uint64_t gxt = grid_for((nrows + kTRows - 1) / kTRows, num_cus, K <= 256 ? 16 : K <= 512 ? 12 : 8);
     const dim3 gridt((unsigned)gxt), blockt(256);
@@ -1847,7 +1839,7 @@ int launch_sweep_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_de
       hipLaunchKernelGGL(k_sweep_nich1_t<8>, (note_kernel(1, "k_sweep_nich1_t<8>"), gridt), blockt, 0, stream, feats_dev, K, kpad, row0, nrows, row_id0, z, crp, rng, zero);
     else
       hipLaunchKernelGGL(k_sweep_nich1_t<16>, (note_kernel(1, "k_sweep_nich1_t<16>"), gridt), blockt, 0, stream, feats_dev, K, kpad, row0, nrows, row_id0, z, crp, rng, zero);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_status("k_sweep_nich1_t");
   }
   // 64 rows per wave visit once there are enough rows for ~8 waves per SIMD; fewer rows: halve the visit down to 4
   int chunk_rows = 64;
@@ -1862,11 +1854,9 @@ int launch_sweep_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_de
     hipLaunchKernelGGL(k_sweep_nich1<4>, (note_kernel(1, "k_sweep_nich1<4>"), grid), block, 0, stream, feats_dev, K, kpad, row0, nrows, row_id0, z, own, crp, rng, chunk_rows, zero);
   else if (K <= 512)
     hipLaunchKernelGGL(k_sweep_nich1<8>, (note_kernel(1, "k_sweep_nich1<8>"), grid), block, 0, stream, feats_dev, K, kpad, row0, nrows, row_id0, z, own, crp, rng, chunk_rows, zero);
-  else if (K <= 1024)
-    hipLaunchKernelGGL(k_sweep_nich1<16>, (note_kernel(1, "k_sweep_nich1<16>"), grid), block, 0, stream, feats_dev, K, kpad, row0, nrows, row_id0, z, own, crp, rng, chunk_rows, zero);
   else
-    return -2;
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+    hipLaunchKernelGGL(k_sweep_nich1<16>, (note_kernel(1, "k_sweep_nich1<16>"), grid), block, 0, stream, feats_dev, K, kpad, row0, nrows, row_id0, z, own, crp, rng, chunk_rows, zero);
+  return launch_status("k_sweep_nich1");
 }
 
 // one workgroup for every `rows_per_wg` rows, at least one and at most `cap`
@@ -1875,27 +1865,23 @@ static dim3 rows_grid(uint64_t nrows, uint64_t rows_per_wg, uint64_t cap) {
 }
 
 // (path: the state's tile plan, msc_state::tile_path; has_dm overrides it)
-int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath path, bool pair, const FeatDesc *feats_dev, int nfeat, int nsplit,
+int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath path, const ScoreShape &shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
                        uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z,
                        const float *own, const float *crp, const uint64_t *rng, ZeroSpans zero) {
-  if (K > 256) return -2;
-  // few rows: 2 rows per wave instead of 8, so that the chunks -- each a serial chain of feature lookups and R
-  // draws -- spread over the chip instead of queueing in a quarter of it (N = 10k, 12 features: 26 -> ? us)
-  // (and 4 rows per wave only while the 64-row workgroups fit one round themselves)
-  const bool small = !has_dm && (nrows + 63) / 64 <= (uint64_t)num_cus;
-  const bool small4 = small && (nrows + 31) / 32 > (uint64_t)num_cus;      // (2 rows per wave would need a second round)
+  if (K > 256 || (shape.pair && K > 128)) return fail(MSC_EHIP, "launch_sweep_mixed: K = %u was routed here", K);
+  const bool pair = shape.pair, small = shape.wave_rows < 8, small4 = shape.wave_rows == 4;
   const uint64_t cap = (uint64_t)num_cus * 4;
   const dim3 grid = rows_grid(nrows, has_dm ? 64 : small4 ? 64 : small ? 32 : 128, cap);
   if (has_dm)
     hipLaunchKernelGGL((k_sweep_tile<8, 8, true>), (note_kernel(1, "k_sweep_tile<8, 8, true>"), grid), dim3(512), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows,
                        row_id0, z, own, crp, rng, zero);
-  else if (path == MSC_PATH_LOOKUPS && pair && K <= 128)
+  else if (path == MSC_PATH_LOOKUPS && pair)
     hipLaunchKernelGGL((k_sweep_lookups<true>), (note_kernel(1, "k_sweep_lookups<true, 0>"), rows_grid(nrows, 512, cap)), dim3(1024), 0, stream,
                        feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
   else if (path == MSC_PATH_LOOKUPS && !small && !pair)
     hipLaunchKernelGGL((k_sweep_lookups<false>), (note_kernel(1, "k_sweep_lookups<false, 0>"), rows_grid(nrows, 256, cap)), dim3(1024), 0, stream,
                        feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
-  else if (path == MSC_PATH_NICH_PACK && pair && K <= 128)
+  else if (path == MSC_PATH_NICH_PACK && pair)
   {
     const dim3 g = rows_grid(nrows, 32 * kNichPackWaves, cap * (16 / kNichPackWaves));
     if (nsplit > 0)
@@ -1911,7 +1897,7 @@ int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath p
     else
       hipLaunchKernelGGL((k_sweep_nich_pack<false, false>), (note_kernel(1, "k_sweep_nich_pack<false, false, 0>"), g), dim3(kNichPackWaves * 64), 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
   }
-  else if (pair && path == MSC_PATH_TILE_ROLES && K <= 128)
+  else if (pair && path == MSC_PATH_TILE_ROLES)
     // PAIR mode (its draw sums a row's entries two to a lane where the other tile kernels sum four: abi.cpp route_sweep)
     hipLaunchKernelGGL((k_sweep_tile_roles<0, true>), (note_kernel(1, "k_sweep_tile_roles<0, true>"), rows_grid(nrows, 256, cap)), dim3(1024), 0,
                        stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, static_cast<const float *>(nullptr));
@@ -1927,7 +1913,7 @@ int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath p
   else
     hipLaunchKernelGGL((k_sweep_tile<8, 16, false>), (note_kernel(1, "k_sweep_tile<8, 16, false>"), grid), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows,
                        row_id0, z, own, crp, rng, zero);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("sweep kernel");
 }
 
 // 256 < K <= 384 (abi.cpp route_sweep): the kernel of the plan's path over the full tile -- TILE_ROLES the role-split
@@ -1942,7 +1928,7 @@ int launch_sweep_roles_tail(hipStream_t stream, int num_cus, ScorePath path, con
     const dim3 g = rows_grid(nrows, 256, cap);
     if (!wide) hipLaunchKernelGGL((k_sweep_lookups<false, 1>), (note_kernel(1, "k_sweep_lookups<false, 1>"), g), dim3(1024), 0, stream, feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, tail);
     else hipLaunchKernelGGL((k_sweep_lookups<false, 2>), (note_kernel(1, "k_sweep_lookups<false, 2>"), g), dim3(1024), 0, stream, feats_dev, nfeat, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, tail);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_status("sweep kernel");
   }
   if (path == MSC_PATH_NICH_PACK) {
     const dim3 g = rows_grid(nrows, 16 * kNichPackWaves, cap * (16 / kNichPackWaves));
@@ -1954,7 +1940,7 @@ int launch_sweep_roles_tail(hipStream_t stream, int num_cus, ScorePath path, con
       if (!wide) hipLaunchKernelGGL((k_sweep_nich_pack<false, false, 1>), (note_kernel(1, "k_sweep_nich_pack<false, false, 1>"), g), b, 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, tail);
       else hipLaunchKernelGGL((k_sweep_nich_pack<false, false, 2>), (note_kernel(1, "k_sweep_nich_pack<false, false, 2>"), g), b, 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, tail);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_status("sweep kernel");
   }
   if (!wide)
     hipLaunchKernelGGL(k_sweep_tile_roles<1>, (note_kernel(1, "k_sweep_tile_roles<1, false>"), rows_grid(nrows, 128, cap)), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad,
@@ -1962,7 +1948,7 @@ int launch_sweep_roles_tail(hipStream_t stream, int num_cus, ScorePath path, con
   else
     hipLaunchKernelGGL(k_sweep_tile_roles<2>, (note_kernel(1, "k_sweep_tile_roles<2, false>"), rows_grid(nrows, 128, cap)), dim3(1024), 0, stream, feats_dev, nfeat, nsplit, K, kpad,
                        row0, nrows, row_id0, z, own, crp, rng, zero, tail);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launch_status("sweep kernel");
 }
 
 int launch_sample_rows(hipStream_t stream, int num_cus, const float *scores, uint64_t ld, uint32_t K,

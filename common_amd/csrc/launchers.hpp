@@ -51,7 +51,8 @@ int launch_crp_prepare(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint
 int launch_entity_op(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row,
                      uint32_t group, int sign, long long *cnt_acc, uint32_t *cnt_u32, float alpha, float *crp, int32_t *z_slot);
 int launch_set_i32(hipStream_t stream, int32_t *dst, int32_t value);
-int launch_loo_own(hipStream_t stream, int num_cus, bool heavy, bool staged, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
+constexpr int kLooRows = 4, kLooThreads = 1024;      // k_loo_own_lds: rows a thread, threads a workgroup (staged = true)
+int launch_loo_own(hipStream_t stream, bool heavy, bool staged, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
                    uint64_t nrows, const int32_t *z, const float *crp, float *own);
 int launch_gp_large_fix(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, int f, uint32_t K,
                         uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z, float *out, uint64_t ld);
@@ -63,6 +64,7 @@ constexpr uint32_t kTailMaxGroups = 128;
 constexpr uint64_t kNarrowMaxRows = 65536;   // views from this many rows on do not take the K <= 64 narrow tiling (abi.cpp narrow_lanes:
                                              // at 100k rows its sweeps already cost 2.5x the lane <-> row kernel's, at 20k they are level)
 constexpr uint64_t kTailMinRows = 16384;     // fewer rows always stay with the tile kernels (lanes as groups)
+constexpr uint32_t kTailStride = 65;         // floats per table row k_score_tail_rows stages (64 groups + 1)
 // What a pass over `nrows` rows costs, in microseconds, on either kind of kernel -- only to choose between them.  The
 // prices follow the PLAN (abi.cpp plan_cost; measured on one MI355X, 1M rows: tools/scans/c3_pieces.py --spec=...,
 // tail_threshold.py, small_n.py, n_scan.py) -- with C3's prices for every plan (round 3) a state of lookup features only took the
@@ -87,11 +89,10 @@ inline double tail_rows_us(uint32_t groups, bool exact, uint64_t nrows, int num_
   const double rounds = frac >= 1.0 ? frac : std::max(0.6, 0.4 + 0.6 * frac);      // (100k rows, 0.38 of a round: 0.75 of its price)
   return (double)nblk * (pc.tail_fixed_us + pc.tail_group_us * per) * rounds;
 }
-// narrow_tail: score a partly filled last tile (<= kTailMaxGroups groups) with the narrow kernel, k_score_tail_rows (abi.cpp: the plan's
-// first phase is lookup features only, the second plain nich features).  ok = false: no.
+// what k_score_tail_rows needs to score a partly filled last tile (<= kTailMaxGroups groups; abi.cpp: the plan's first
+// phase is lookup features only, the second plain nich features).  ok = false: the plan is not for it.
 struct TailPlan {
-  PlanCost cost;              // the plan's prices (set whether or not the narrow kernel may take the plan)
-  bool ok = false;
+  bool ok = false;            // (abi.cpp narrow_tail_fits: the plan, the tile and the LDS the staged tables need)
   bool exact = true;          // the tile kernels' bits (two sums per group: score passes, where the row count picks the kernel);
                               // false: one sum per group, faster (sweeps: the choice of kernel follows the bound view's row count, not the call's)
   bool masked_nich = false;   // the first phase holds masked nich columns (the kernel's instantiation that evaluates them)
@@ -100,7 +101,7 @@ struct TailPlan {
   uint32_t pack_rows = 0;     // all lookup tables together
   float *pack = nullptr;      // scratch of pack_rows x 64 floats (the tail groups' tables, k_tail_pack), owned by the state
 };
-// the narrow kernel alone: groups [k0, K) of every row
+// the narrow kernel alone: groups [k0, K) of every row (k0 < K <= k0 + kTailMaxGroups, tp.ok)
 int launch_score_tail(hipStream_t stream, int num_cus, const TailPlan &tp, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,
                       uint32_t kpad, uint32_t k0, uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp,
                       float *out, uint64_t ld);
@@ -112,13 +113,17 @@ struct ZeroSpans {
   unsigned long long *b = nullptr;
   size_t nb = 0;
 };
-// (kernels_score.hip: the lane <-> row kernel with the draw in it)
+// (kernels_score.hip: the lane <-> row kernel with the draw in it; K <= 64, tp.ok)
 int launch_sweep_rows(hipStream_t stream, int num_cus, const TailPlan &tp, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,
                       uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z, const float *own, const float *crp,
                       const uint64_t *rng, ZeroSpans zero);
 int launch_score_pair_tail(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K, uint32_t kpad,
                            uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp, float *tail, uint64_t ld);
-int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, int nich1_shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
+// How a pass runs (abi.cpp route_score): rows a wave of k_score_tile<R, 16> takes, PAIR mode, what scores a partly filled
+// last tile (the tile kernels, k_score_tail_rows, k_score_tile_roles in PAIR mode), k_score_nich1's code (nich1_shape_for)
+enum class LastTile { tiles, rows, pair };
+struct ScoreShape { int wave_rows = 8; bool pair = false; LastTile last = LastTile::tiles; int nich1 = 0; };
+int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, const ScoreShape &shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
                  uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z,
                  const float *own, const float *crp, float *out, uint64_t ld);
 
@@ -129,12 +134,16 @@ int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan
 void note_kernel(int slot, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 const char *last_kernel(int slot);
 inline const char *tf(bool b) { return b ? "true" : "false"; }
+// what the routed launchers return: 0, or MSC_EHIP with the launch's HIP error (or the shape no route sends) reported
+inline int launch_status(const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(MSC_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
+}
 
-// kernels_sweep.hip  (return -2: shape not covered by this kernel)
-int launch_sweep_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, uint32_t K,
+// kernels_sweep.hip (launchers launch what abi.cpp route_sweep chose: a shape it never sends is MSC_EHIP, reported)
+int launch_sweep_nich1(hipStream_t stream, int num_cus, bool transposed, const FeatDesc *feats_dev, uint32_t K,
                        uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z,
                        const float *own, const float *crp, const uint64_t *rng_dev, ZeroSpans zero);
-bool pair_mode_ok(ScorePath path, uint32_t K, bool few_rows);
 #ifndef MSC_NICH_PACK_WAVES
 #define MSC_NICH_PACK_WAVES 8
 #endif
@@ -145,7 +154,7 @@ constexpr int kNichPackWaves = MSC_NICH_PACK_WAVES;   // waves a workgroup of th
 constexpr int kPackMaxLookups = 4;                      // lookup features (after fusing the bool columns) a plan may hold and still take the nich-only kernels
 constexpr int kNichPackNC = MSC_NICH_PACK_NC;          // groups of the lane a block part of the nich-only kernels takes (256 registers a wave there)
 constexpr double kPairTileShare = 0.62;     // what a pass of the role-split kernels costs in PAIR mode (<= 128 groups), of a full tile pass
-int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath path, bool pair, const FeatDesc *feats_dev, int nfeat, int nsplit,
+int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath path, const ScoreShape &shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
                        uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z,
                        const float *own, const float *crp, const uint64_t *rng, ZeroSpans zero);
 int launch_sweep_roles_tail(hipStream_t stream, int num_cus, ScorePath path, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,

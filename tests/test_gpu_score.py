@@ -608,8 +608,8 @@ def test_nich_blocks_follow_the_nu_prior_and_the_counts_the_suffstats_hold(gpu_c
     """What makes a block: the same nu prior (the host's plan) AND, per group, the same count (the head kernel looks at the
     c1 the suff-stats produced).  Columns 2-5 share nu = 1 but column 4's suff-stats come from ANOTHER assignment (set
     feature by feature, as msc_state_set_ss allows): its block is scored feature by feature; columns 6, 7 have nu = 3.5 and
-    form a block of their own; column 8's nu is its own.  Against the twin, and -- for the features that fell back -- the
-    bits of a plan without blocks (MSC_NO_NICH_BLOCKS)."""
+    form a block of their own; column 8's nu is its own.  Against the twin, and the tile kernels on few rows give the
+    same bits."""
     import common_amd
     monkeypatch.setenv("MSC_TAIL_MIN_ROWS", "16384")
     K, N = 200, 30_000

@@ -324,6 +324,31 @@ def test_narrow_tiling_on_one_shard_only(gpu_ctx, K):
     _shard_case(gpu_ctx, feats, K, R, seed=160 + K, hot=hot)
 
 
+@pytest.mark.parametrize("R", [2, 3])
+def test_single_nich_sweep_kernel_follows_the_whole(gpu_ctx, R):
+    """one nich feature, K = 256, 24 000 rows: the whole takes the transposed single-nich sweep (k_sweep_nich1_t, from 64
+    rows a CU on); its shards of 12 000 or 8 000 rows alone would take the row-at-a-time kernel, which draws other bits"""
+    rng = np.random.default_rng(800 + R)
+    N, K = 24_000, 256
+    feats = [make_feature(orc.NICH, N, K, rng)]
+    names = _shard_case(gpu_ctx, feats, K, R, seed=180 + R)
+    assert names["whole"][1].startswith("k_sweep_nich1_t<"), names
+
+
+@pytest.mark.parametrize("R", [2, 3])
+@pytest.mark.parametrize("plan", ["roles", "lookups"])
+def test_small_shards_of_a_large_whole_keep_the_plans_sweep_kernel(gpu_ctx, plan, R):
+    """K = 200 (no PAIR mode), 24 000 rows: the whole sweeps on its plan's own kernel (role-split or lookups-only); its
+    shards of 12 000 or 8 000 rows alone would be few enough rows for k_sweep_tile<2 | 4, 16>"""
+    rng = np.random.default_rng(850 + R + (10 if plan == "roles" else 0))
+    N, K = 24_000, 200
+    specs = {"roles": [(orc.BB, 0), (orc.BB, 0), (orc.DD, 5), (orc.NICH, 0), (orc.NICH, 0)],
+             "lookups": [(orc.BB, 0), (orc.BB, 0), (orc.DD, 5), (orc.DD, 3)]}[plan]
+    feats = [make_feature(f, N, K, rng, d) for f, d in specs]
+    names = _shard_case(gpu_ctx, feats, K, R, seed=190 + R)
+    assert not names["whole"][1].startswith("k_sweep_tile<"), names
+
+
 FUZZ_FAMILIES = [orc.BB, orc.BBNC, orc.GP, orc.BNB, orc.DD, orc.DM, orc.NICH]
 
 

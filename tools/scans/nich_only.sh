@@ -8,6 +8,3 @@ for lib in "" common_amd/lib/variants/*.so; do
     echo "== K $K no lane<->row kernel"; MSC_TAIL_MIN_ROWS=100000000 python tools/scans/c3_pieces.py $K --family=nich 2>&1 | grep -v amdgpu
   done
 done
-echo "#### no pack (MSC_NO_ROLES)"
-unset MSC_LIB_PATH
-for K in 256 128; do echo "== K $K"; MSC_NO_ROLES=1 python tools/scans/c3_pieces.py $K --family=nich 2>&1 | grep -v amdgpu; done

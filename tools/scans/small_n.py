@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""C3's columns on SMALL row counts: sweep step and score pass, default against the A/B switches (each state planned under its
+"""C3's columns on SMALL row counts: sweep step and score pass, default against the test hooks (each state planned under its
 own environment).  usage: tools/scans/small_n.py [N ...]"""
 import os
 import sys
@@ -18,8 +18,7 @@ for N in Ns:
         cols, z = make_columns(ctx, spec, N, K, 73)
         view = common_amd.DataView.from_tensors(ctx, cols)
         row = {}
-        for name, env in (("default", {}), ("no_bb_fuse", {"MSC_NO_BB_FUSE": "1"}), ("no_fused_tail", {"MSC_NO_FUSED_TAIL": "1"}),
-                          ("rows_forced", {"MSC_TAIL_MIN_ROWS": "1"})):
+        for name, env in (("default", {}), ("no_bb_fuse", {"MSC_NO_BB_FUSE": "1"}), ("rows_forced", {"MSC_TAIL_MIN_ROWS": "1"})):
             os.environ.update(env)
             st = common_amd.State(ctx, spec, K)
             st.set_alpha(1.0)
