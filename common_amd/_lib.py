@@ -93,6 +93,7 @@ _SIGS = {
     "msc_state_set_ss": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     "msc_state_get_ss": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     "msc_state_set_alpha": (C.c_int, [C.c_void_p, C.c_float]),
+    "msc_state_get_alpha": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "msc_state_set_group_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "msc_state_get_group_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "msc_score_value": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
@@ -142,6 +143,8 @@ _SIGS = {
                                   C.c_void_p]),
     "msc_sample_predictive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "msc_score_marginal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "msc_value_op_single": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "msc_relation_slice_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,

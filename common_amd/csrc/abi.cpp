@@ -46,6 +46,8 @@ struct Switches {
   bool tail_forced = false, no_narrow_tail = false, no_bb_fuse = false, sweep_graph = false;
   uint64_t tail_min_rows = 0;                           // (tail_forced)
   int loo_lds = -1, sweep_nich1 = 0, alloc_candidates = 12;
+  int marginal_tile = -1;                               // MSC_MARGINAL_TILE: 1 / 0 = the fused tile kernel for every plan it takes / for none
+
   float alloc_accept_gbps = 6650.f;
 };
 static Switches read_switches() {
@@ -54,6 +56,7 @@ static Switches read_switches() {
   sw.no_narrow_tail = std::getenv("MSC_NO_NARROW_TAIL") != nullptr, sw.no_bb_fuse = std::getenv("MSC_NO_BB_FUSE") != nullptr;
   if (const char *e = std::getenv("MSC_LOO_LDS")) sw.loo_lds = std::atoi(e);
   if (const char *e = std::getenv("MSC_SWEEP_NICH1")) sw.sweep_nich1 = std::atoi(e);
+  if (const char *e = std::getenv("MSC_MARGINAL_TILE")) sw.marginal_tile = std::atoi(e);
   if (const char *g = std::getenv("MSC_SWEEP_GRAPH")) sw.sweep_graph = g[0] != '0' && g[0] != 0;
   if (const char *e = std::getenv("MSC_ALLOC_CANDIDATES")) sw.alloc_candidates = std::atoi(e);
   if (const char *e = std::getenv("MSC_ALLOC_ACCEPT_GBPS")) sw.alloc_accept_gbps = (float)std::atof(e);
@@ -1485,6 +1488,12 @@ extern "C" int msc_state_set_alpha(msc_state *st, float alpha) {
   MSC_REQUIRE(alpha > 0.f, "alpha must be positive (group_manager.hpp:78)");
   st->alpha = alpha;
   st->crp_valid = false;
+  return MSC_OK;
+}
+
+extern "C" int msc_state_get_alpha(const msc_state *st, float *alpha) {
+  MSC_REQUIRE(st && alpha, "null argument");
+  *alpha = st->alpha;
   return MSC_OK;
 }
 
@@ -3294,6 +3303,77 @@ extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const fl
                 features[i], first_bad);
   }
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// row predictive log-density (kernels_marginal.hip): a row's K totals -- what msc_score_value with the prior defines --
+// reduced to their log-sum-exp, arg-max and the arg-max's log responsibility
+// ---------------------------------------------------------------------------
+// Which kernels reduce a state's rows.  By the state and view_rows alone (THE SHARD RULE of route_sweep): the fused
+// kernels and the score kernels add a row's terms in different orders, so a call over a sub-range must take what the
+// whole call takes.
+//   nich1    a single nich feature (masked or not) up to 1024 groups: k_marginal_nich1, the own-group values computed inside
+//   tile     scalar features within the tables (no niw, no dm, no count beyond a table), K <= 256, a view of at least
+//            kTailMinRows rows (fewer rows do not fill the chip with 128-row workgroups: the score pass has shapes for
+//            them), on plans whose SCORE pass is the plain tile kernel too (tile_path == MSC_PATH_TILE): k_loo_own, then
+//            k_marginal_tile over the fused plan.  A plan with kernels of its own (role-split, nich-only, lookups-only)
+//            goes the generic way: its score pass plus k_row_lse beats the plain tile form (C3, 10^6 x 256: DESIGN.md 6g)
+//            until a fused form of those kernels exists.  MSC_MARGINAL_TILE=1 / 0 sends every such plan / none to the tile
+//            kernel (how the two were measured against each other).
+//   generic  everything else: run_score (leave-one-out + prior) into the scratch chunk, then k_row_lse over it
+enum class MarginalKind { nich1, tile, generic };
+static MarginalKind route_marginal(const msc_state *st) {
+  if (!sweep_plain(st)) return MarginalKind::generic;
+  if (st->nich1) return st->K <= 1024 ? MarginalKind::nich1 : MarginalKind::generic;
+  if (!st->has_dm && st->K <= 256 && view_rows(st) >= kTailMinRows) {
+    const int forced = read_switches().marginal_tile;
+    if (forced >= 0 ? forced != 0 : st->tile_path == MSC_PATH_TILE) return MarginalKind::tile;
+  }
+  return MarginalKind::generic;
+}
+
+extern "C" int msc_score_marginal(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                  const int32_t *z_dev, uint32_t flags, float *logp_dev, int32_t *map_dev,
+                                  float *map_logresp_dev) {
+  MSC_REQUIRE(st && (logp_dev || nrows == 0), "null argument");
+  MSC_REQUIRE(flags == 0, "unknown flags 0x%x", flags);
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_score_marginal between msc_sweep_step_begin and msc_state_commit_reduce: the "
+              "tables hold one rank's uncommitted sums");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  if (nrows == 0) return MSC_OK;
+  MSC_TRY(ensure_derived(st));
+  MSC_TRY(ensure_crp(st));
+  hipStream_t s = st->ctx->stream;
+  const int cus = st->ctx->num_cus;
+  MSC_HIP(grow_retained(st->retired, st->marg_norm, 2));
+  MSC_TRY(launch_marginal_norm(s, st->cnt_u32, st->K, st->alpha, st->marg_norm));
+  switch (route_marginal(st)) {                           // (the launchers report their own failures)
+    case MarginalKind::nich1:
+      return launch_marginal_nich1(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, z_dev, st->logpc, st->marg_norm, logp_dev,
+                                   map_dev, map_logresp_dev);
+    case MarginalKind::tile:
+      if (z_dev) MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
+      MSC_TRY(refresh_fused_tables(st));                  // (the kernel walks the fused plan)
+      return launch_marginal_tile(s, cus, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
+                                  z_dev, st->own, st->logpc, st->marg_norm, logp_dev, map_dev, map_logresp_dev);
+    case MarginalKind::generic: {
+      // (the chunk of SweepKind::generic: rows of K rounded up to 64 floats; the scratch is the state's and stays with it,
+      // grown to what the largest call asked for, at most 4 GiB of scores)
+      const uint64_t ld = std::min<uint64_t>(st->kpad, ((uint64_t)st->K + 63) & ~63ull);
+      const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((4096ull << 20) / (ld * sizeof(float)), nrows));
+      MSC_HIP(grow_retained(st->retired, st->scratch, chunk * ld));
+      for (uint64_t at = 0; at < nrows; at += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, nrows - at);
+        MSC_TRY(run_score(st, row0 + at, n, z_dev ? z_dev + at : nullptr, true, false, st->scratch, ld));
+        MSC_TRY(launch_row_lse(s, cus, st->scratch, ld, st->K, n, z_dev ? z_dev + at : nullptr, st->marg_norm, logp_dev + at,
+                               map_dev ? map_dev + at : nullptr, map_logresp_dev ? map_logresp_dev + at : nullptr));
+      }
+      return MSC_OK;
+    }
+  }
+  return MSC_OK;
 }
 
 // ---------------------------------------------------------------------------

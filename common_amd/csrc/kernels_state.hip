@@ -532,8 +532,8 @@ __global__ __launch_bounds__(256) void k_pack_look_idx(const LookIdxSrc *__restr
   }
   while (at < l4) rec[at++] = word, word = 0u;
 }
-static char g_last_kernel[3][160] = {"", "", ""};
-static inline int kernel_slot(int slot) { return slot == 2 ? 2 : (slot & 1); }
+static char g_last_kernel[4][160] = {"", "", "", ""};   // 0 score, 1 sweep, 2 zmatrix, 3 marginal
+static inline int kernel_slot(int slot) { return slot == 2 || slot == 3 ? slot : (slot & 1); }
 void note_kernel(int slot, const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);

@@ -128,7 +128,7 @@ int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan
                  const float *own, const float *crp, float *out, uint64_t ld);
 
 // which kernel INSTANTIATION the library chose for the most recent scoring pass (slot 0) / fused assignment pass (slot 1)
-// / z-matrix kernel (slot 2),
+// / z-matrix kernel (slot 2) / row predictive pass (slot 3: the kernel that reduced the rows),
 // spelled as rocprofv3 spells it ("k_score_tile_roles<false, false, false>"): bench.py and tools/ key the committed
 // counter summaries by it (msc_last_kernel, include/microscopes_hip.h).  Process-wide, set by the launchers.
 void note_kernel(int slot, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -258,6 +258,18 @@ int launch_pred_prepare(hipStream_t stream, const PredFeat *pfs_dev, const std::
 int launch_pred_sample(hipStream_t stream, const PredFeat *pfs_dev, const std::vector<PredFeat> &pfs, uint32_t K,
                        uint64_t row0, uint64_t nrows, uint64_t row_id0, const int32_t *z, int32_t *z_out,
                        bool masked_only, uint64_t seed, uint64_t sweep);
+
+// kernels_marginal.hip (msc_score_marginal; abi.cpp route_marginal chooses): norm = {log(n + alpha), log(n - 1 + alpha)} on the
+// device; z null = no leave-one-out; map / logresp null = not wanted
+int launch_marginal_norm(hipStream_t stream, const uint32_t *cnt, uint32_t K, float alpha, double *norm);
+int launch_marginal_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, uint32_t K, uint32_t kpad, uint64_t row0,
+                          uint64_t nrows, const int32_t *z, const float *crp, const double *norm, float *logp, int32_t *map,
+                          float *logresp);
+int launch_marginal_tile(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,
+                         uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp,
+                         const double *norm, float *logp, int32_t *map, float *logresp);
+int launch_row_lse(hipStream_t stream, int num_cus, const float *scores, uint64_t ld, uint32_t K, uint64_t nrows,
+                   const int32_t *z, const double *norm, float *logp, int32_t *map, float *logresp);
 
 // kernels_query.hip (msc_zmatrix_*): counts live as upper-triangle tiles of kZmTile x kZmTile u32 (zm_tile_base); the
 // batch is [rows rounded up to kZmTile][kZmBatchWords] u32, four 8-bit or two 16-bit labels a word; `bad` holds a flag

@@ -578,6 +578,7 @@ struct msc_state {
   bool tail_dm = false;               // ... or dm features with their tables staged whole
   msc::DevBuf<float> tail_pack;       // k_tail_pack's output: tail_pack_rows x 64 floats (grown on demand)
   uint32_t loo_staged = 0;        // plan_groups: features whose leave-one-out block k_loo_own_lds stages in LDS
+  msc::DevBuf<double> marg_norm;  // msc_score_marginal: {log(n + alpha), log(n - 1 + alpha)}, rewritten by every call
   msc::DevBuf<float> rows_table;  // k_sweep_nich1_rows: per-group constants as scalar operands (single nich, K > 1024)
   msc::DevBuf<uint32_t> colmax_dev;
   // (seed, sweep index) of the sampling kernels, device-resident (kernels_sweep.hip); the host tracks what it holds

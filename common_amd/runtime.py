@@ -90,7 +90,7 @@ class Context(object):
         """the kernel instantiation of this process's most recent scoring ("score") or fused assignment ("sweep") pass, or
         z-matrix kernel ("zmatrix"), as rocprofv3 spells it (msc_last_kernel): what bench.py keys the committed counter
         summaries by"""
-        return self.lib.msc_last_kernel({"score": 0, "zmatrix": 2}.get(which, 1)).decode()
+        return self.lib.msc_last_kernel({"score": 0, "zmatrix": 2, "marginal": 3}.get(which, 1)).decode()
 
     def value_op(self, family, dim, op, hp, ss_record, value=None):
         """One group::{add_value, remove_value, score_value, score_data} call (base.hpp:25-28) as a batch
@@ -324,6 +324,7 @@ class State(object):
 
     # hypers -----------------------------------------------------------------
     def set_hp(self, f, hp):
+        self._drop_subsets()
         fam, dim = self.features[f]
         a = pack_hp(fam, hp, dim)
         L.check(self.ctx.lib.msc_state_set_hp(self._h, f, a.ctypes.data_as(C.c_void_p), a.size))
@@ -336,6 +337,7 @@ class State(object):
 
     # suff-stats -------------------------------------------------------------
     def set_ss(self, f, records, first_group=0):
+        self._drop_subsets()
         fam, dim = self.features[f]
         r = np.ascontiguousarray(records, dtype=ss_dtype(fam, dim))
         L.check(self.ctx.lib.msc_state_set_ss(self._h, f, first_group, r.shape[0],
@@ -349,11 +351,18 @@ class State(object):
         return r
 
     def set_alpha(self, alpha):
+        self._drop_subsets()
         L.check(self.ctx.lib.msc_state_set_alpha(self._h, float(alpha)))
 
     def set_group_counts(self, counts):
+        self._drop_subsets()
         c = np.ascontiguousarray(counts, dtype=np.uint32)
         L.check(self.ctx.lib.msc_state_set_group_counts(self._h, c.ctypes.data_as(C.c_void_p), c.size))
+
+    def get_alpha(self):
+        a = C.c_float()
+        L.check(self.ctx.lib.msc_state_get_alpha(self._h, C.byref(a)))
+        return a.value
 
     def get_group_counts(self):
         c = np.zeros(self.K, dtype=np.uint32)
@@ -400,6 +409,7 @@ class State(object):
         return shape.value, ms.value
 
     def accumulate(self, view, z, row0=0, nrows=None, reset=True, subtract=False, commit=True, cols=None):
+        self._drop_subsets()
         self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
         n = view.nrows - row0 if nrows is None else nrows
         if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
@@ -411,6 +421,7 @@ class State(object):
 
     def entity_op(self, view, row, group, join=True, z=None, cols=None):
         """one entity joins / leaves one group, the group by value (msc_entity_op): every table stays current"""
+        self._drop_subsets()
         self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
         zp = None
         if z is not None:
@@ -436,6 +447,7 @@ class State(object):
 
     def sweep_step(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
         """sweep_assign + accumulate(reset) in one call; repeated steps replay as a HIP graph (msc_sweep_step)."""
+        self._drop_subsets()
         self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
         n = view.nrows - row0 if nrows is None else nrows
         if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
@@ -446,6 +458,7 @@ class State(object):
 
     def sweep_step_begin(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
         """the sharded step up to the exchange: follow with all-reduce of reduce_buffers() and commit_reduce()"""
+        self._drop_subsets()
         self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
         n = view.nrows - row0 if nrows is None else nrows
         if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
@@ -459,6 +472,7 @@ class State(object):
         """nsweeps sequential collapsed Gibbs sweeps over the rows, each row scored against the tables the row before it
         left (msc_sweep_sequential).  order: uint32 (or int32) device tensor of nrows offsets from row0, the visiting
         order of every sweep (None: ascending); trace: int32 device tensor of nsweeps x nrows, z after every sweep."""
+        self._drop_subsets()
         self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
         n = view.nrows - row0 if nrows is None else nrows
         if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
@@ -499,6 +513,7 @@ class State(object):
                 _alias_tensor(pf.value, nf.value, torch.float64, self.ctx.torch_device))
 
     def commit_reduce(self):
+        self._drop_subsets()
         L.check(self.ctx.lib.msc_state_commit_reduce(self._h))
 
     def reduce_pack(self):
@@ -509,6 +524,7 @@ class State(object):
         return _alias_tensor(p.value, n.value, torch.float64, self.ctx.torch_device)
 
     def reduce_unpack(self):
+        self._drop_subsets()
         L.check(self.ctx.lib.msc_state_reduce_unpack(self._h))
 
     def set_sweep_rows(self, global_rows):
@@ -554,6 +570,7 @@ class State(object):
         """one grid Gibbs step over `grids` (at most one per feature, one crp_grid): score, add the prior, draw, install
         (msc_hp_grid_gibbs; one host synchronisation).  -> chosen indices (numpy uint32, one per grid), and with
         want_scores the float64 tensors of prior + likelihood per grid"""
+        self._drop_subsets()
         grids = list(grids)
         for g in grids:
             if g.state is not self or not g._h:
@@ -578,6 +595,7 @@ class State(object):
         "width", and optionally "prior" ("flat", "exponential", "normal", "noninf_beta" or an L.PRIOR_* value), "a"
         (lambda | mu), "b" (sigma2) and "partner" (noninf_beta).  slots: uint8 device mask of the counted groups (default:
         the non-empty ones).  -> (installed values float32, evaluations uint32), one per entry"""
+        self._drop_subsets()
         coords = list(coords)
         arr = (L.SliceCoord * max(1, len(coords)))()
         for i, c in enumerate(coords):
@@ -595,6 +613,7 @@ class State(object):
     def theta_slice(self, tparams, seed, sweep, slots=None):
         """one slice step of the p of every counted slot of the bbnc features in `tparams` = {feature: {"p": width}}, as
         downstream's theta kernel takes it (msc_theta_slice; one host synchronisation).  -> {feature: evaluations}"""
+        self._drop_subsets()
         feats = [int(f) for f in tparams]
         for f in feats:
             if set(tparams[f]) != {"p"}:
@@ -610,6 +629,74 @@ class State(object):
     # posterior predictive sampling -------------------------------------------
     _PRED_DTYPES = {L.BB: torch.uint8, L.BBNC: torch.uint8, L.GP: torch.uint32, L.BNB: torch.uint32, L.DD: torch.int32,
                     L.NICH: torch.float32, L.NIW: torch.float32}
+
+    # row predictive log-density (msc_score_marginal) ---------------------------------------------------------------
+    def predictive_logp(self, view, z=None, row0=0, nrows=None, cols=None, out=None, want_map=False, given=None):
+        """log p(x_r | state) of rows [row0, row0 + nrows): the log-sum-exp over the groups of log pseudocount + the
+        row's summed score_value, minus log(n_r + alpha) -- float32 device tensor of nrows entries (msc_score_marginal;
+        the [nrows, K] matrix is not written where a fused kernel takes the state).  z (int32 device tensor): leave-one-out,
+        an id outside [0, K) is unassigned.  want_map: -> (logp, map, map_logresp), the arg-max group of every row (lowest
+        index among exact ties) and its log responsibility.
+        given=[f, ...]: the CONDITIONAL log density of the row's other observed entries given features f, ..., as
+        logp(all) - logp(subset(given)); the subset state is kept until a table of this state changes.  cols then has to
+        be None or list every feature's column (the subset reads the given features' entries of it)."""
+        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
+        n = view.nrows - row0 if nrows is None else nrows
+        dev = self.ctx.torch_device
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=dev)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n:
+            raise ValueError("out must be a contiguous float32 tensor of nrows entries")
+        zp = None
+        if z is not None:
+            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
+                raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+            zp = C.c_void_p(z.data_ptr())
+        mp = lr = None
+        if want_map:
+            mp = torch.empty(n, dtype=torch.int32, device=dev)
+            lr = torch.empty(n, dtype=torch.float32, device=dev)
+        L.check(self.ctx.lib.msc_score_marginal(self._h, view._h, self._cols(cols), row0, n, zp, 0,
+                                                C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(mp.data_ptr()) if want_map else None,
+                                                C.c_void_p(lr.data_ptr()) if want_map else None))
+        if given is not None:
+            given = [int(f) for f in given]
+            sub = self._subset_cached(given)
+            all_cols = list(range(len(self.features))) if cols is None else [int(c) for c in cols]
+            denom = sub.predictive_logp(view, z=z, row0=row0, nrows=n, cols=[all_cols[f] for f in given])
+            out[:n] -= denom
+        return (out, mp, lr) if want_map else out
+
+    def subset(self, features):
+        """a new State of the same K holding only `features` (indices into this state's, in the order given), with their
+        hp, suff-stats (bbnc's p included: it is a field of the record), the group counts and alpha copied (a host round
+        trip of K records a feature)"""
+        feats = [int(f) for f in features]
+        for f in feats:
+            if not 0 <= f < len(self.features):
+                raise ValueError("feature %d outside the state (%d features)" % (f, len(self.features)))
+        sub = State(self.ctx, [self.features[f] for f in feats], self.K)
+        for i, f in enumerate(feats):
+            a = self.get_hp(f)
+            L.check(self.ctx.lib.msc_state_set_hp(sub._h, i, a.ctypes.data_as(C.c_void_p), a.size))
+            sub.set_ss(i, self.get_ss(f))
+        sub.set_group_counts(self.get_group_counts())
+        sub.set_alpha(self.get_alpha())
+        return sub
+
+    def _subset_cached(self, feats):
+        cache = self.__dict__.setdefault("_subsets", {})
+        key = tuple(feats)
+        if key not in cache:
+            cache[key] = self.subset(feats)
+        return cache[key]
+
+    def _drop_subsets(self):
+        """every method that changes a table (hp, suff-stats, counts, alpha) calls this first: the subset states that
+        predictive_logp(given=) keeps were copies of the tables as they stood"""
+        for sub in self.__dict__.pop("_subsets", {}).values():
+            sub.close()
 
     def sample_predictive(self, view, z=None, seed=0, sweep=0, masked_only=False, features=None, row0=0, nrows=None,
                           row_id0=None, cols=None, out=None):
@@ -660,6 +747,7 @@ class State(object):
         return self.sample_predictive(view, z=z, seed=seed, sweep=sweep, masked_only=True, **kw)
 
     def close(self):
+        self._drop_subsets()                            # (the subset states predictive_logp(given=) kept)
         if getattr(self, "_h", None):
             for g in list(getattr(self, "_grids", ())):  # (the library frees a state's grids with it)
                 g._h = None
@@ -681,6 +769,7 @@ def _slots_ptr(slots, K):
             and slots.numel() >= K):
         raise ValueError("slots must be a contiguous uint8 device tensor of ngroups entries")
     return C.c_void_p(slots.data_ptr())
+
 
 
 class HpGrid(object):

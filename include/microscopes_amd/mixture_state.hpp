@@ -398,6 +398,40 @@ public:
     return out;
   }
 
+  // The log posterior predictive density of new rows under the state (downstream's held-out log-likelihood and, as a
+  // difference of two such numbers, its conditional queries): log sum over the slots of pseudocount / (n + alpha) times the
+  // product of the observed entries' predictive densities -- ONE msc_score_marginal call (no leave-one-out: the rows are
+  // not the state's entities); a masked entry contributes nothing, free slots share alpha as empty groups do.
+  // map_slots (nullable) receives every row's MAP slot (slot_of(gid) maps a group to its slot; the lowest slot among
+  // exact ties), map_logresp (nullable) the log responsibility of that slot (<= 0).
+  std::vector<float> log_post_pred(const common::recarray::row_major_dataview &rows, std::vector<int32_t> *map_slots = nullptr,
+                                   std::vector<float> *map_logresp = nullptr) {
+    if (rows.types().size() != specs_.size()) throw std::runtime_error("one column per component model expected");
+    const size_t n = rows.size();
+    std::vector<float> out(n);
+    if (map_slots) map_slots->assign(n, -1);
+    if (map_logresp) map_logresp->assign(n, 0.f);
+    if (n == 0) return out;
+    push_params(true);
+    msc_dataview *v = rows.to_device(ctx_, &col_types_);
+    float *logp = nullptr, *lr = nullptr;
+    int32_t *mp = nullptr;
+    int rc = msc_device_alloc(ctx_, 4 * n, reinterpret_cast<void **>(&logp));
+    if (rc == MSC_OK && map_slots) rc = msc_device_alloc(ctx_, 4 * n, reinterpret_cast<void **>(&mp));
+    if (rc == MSC_OK && map_logresp) rc = msc_device_alloc(ctx_, 4 * n, reinterpret_cast<void **>(&lr));
+    if (rc == MSC_OK) rc = msc_score_marginal(st_, v, nullptr, 0, n, nullptr, 0, logp, mp, lr);
+    if (rc == MSC_OK) rc = msc_device_download(ctx_, out.data(), logp, 4 * n);
+    if (rc == MSC_OK && mp) rc = msc_device_download(ctx_, map_slots->data(), mp, 4 * n);
+    if (rc == MSC_OK && lr) rc = msc_device_download(ctx_, map_logresp->data(), lr, 4 * n);
+    const std::string err = rc == MSC_OK ? std::string() : std::string(msc_last_error());
+    if (logp) msc_device_free(ctx_, logp);
+    if (mp) msc_device_free(ctx_, mp);
+    if (lr) msc_device_free(ctx_, lr);
+    msc_dataview_destroy(v);
+    if (rc != MSC_OK) throw std::runtime_error(err);
+    return out;
+  }
+
   // the device handles, for callers that mix in calls of microscopes_hip.h
   msc_state *device_state() const { return st_; }
   msc_dataview *device_view() const { return view_; }

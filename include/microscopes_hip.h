@@ -88,7 +88,8 @@ const char *msc_build_info(void); /* "gfx950 hipcc <ver> ..." */
 /*
  * Which kernel INSTANTIATION the library chose for this process's most recent scoring pass (which = 0: msc_score_value)
  * or fused assignment pass (which = 1: msc_sweep_assign / msc_sweep_step), or the most recent kernel of the z-matrix
- * accumulator (which = 2: msc_zmatrix_*), spelled as rocprofv3 spells it, e.g.
+ * accumulator (which = 2: msc_zmatrix_*), or the kernel that reduced the rows of the most recent row predictive pass
+ * (which = 3: msc_score_marginal), spelled as rocprofv3 spells it, e.g.
  * "k_score_tile_roles<false, false, false>" ("" before the first such call).  Measurement tooling only: bench.py keys the
  * committed counter summaries (profiles/ *_pmc.json) by it, so that a roofline figure is always the figure of the kernel
  * that ran.  Nothing comparable upstream (the reference has no kernels).
@@ -225,6 +226,8 @@ int msc_state_get_ss(msc_state *st, uint32_t feature, uint32_t first_group, uint
 
 /* group_manager: alpha (get_hp_mutator("alpha"), group_manager.hpp:124-130) and counts */
 int msc_state_set_alpha(msc_state *st, float alpha);
+/* the CRP concentration the state holds (msc_state_set_alpha, or what a hyper-parameter move installed) */
+int msc_state_get_alpha(const msc_state *st, float *alpha);
 int msc_state_set_group_counts(msc_state *st, const uint32_t *host_counts, uint32_t ngroups);
 int msc_state_get_group_counts(msc_state *st, uint32_t *host_counts, uint32_t ngroups);
 
@@ -576,6 +579,32 @@ int msc_theta_slice(msc_state *st, const uint32_t *features, const float *widths
 int msc_sample_predictive(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                           uint64_t row_id0, const int32_t *z_dev, int32_t *z_out_dev, uint32_t flags, uint64_t seed,
                           uint64_t sweep, void *const *out_dev);
+
+/*
+ * The log posterior predictive density of rows [row0, row0+nrows) under the state, reduced over the groups on chip:
+ *   log p(x_r | state) = log sum_k pseudocount(k) / (n_r + alpha) * prod_f p_f(x_rf | group k).
+ * For row r and slot k let t[r][k] be exactly what msc_score_value(st, view, cols, row0, nrows, z_dev,
+ * MSC_SCORE_CRP_PRIOR, ...) defines: log pseudocount (empty slots share alpha) + the sum over features of score_value,
+ * masked entries contributing nothing, leave-one-out when z_dev is given (int32[nrows], indexed from row0; an id < 0 or
+ * >= ngroups is unassigned).  Then, indexed from row0,
+ *   logp_dev[r]        = logsumexp_k t[r][k] - log(n_r + alpha), n_r = the sum of the group counts, minus one when the
+ *                        row is assigned under leave-one-out.  With at least one empty slot this is the exact CRP
+ *                        predictive; with every slot full it is the chain truncated to ngroups groups
+ *                        (msc_sweep_sequential);
+ *   map_dev[r]         (nullable) = the lowest k at which t[r][k] is the row's maximum: the hard (MAP) assignment;
+ *   map_logresp_dev[r] (nullable) = t[r][map] - logsumexp_k t[r][k] (<= 0): the log responsibility of that group.
+ * The [nrows, ngroups] matrix is never written where a fused kernel takes the state (a single nich feature up to 1024
+ * groups; scalar features up to 256 groups on plans the plain tile kernel scores); every other state is scored chunk by
+ * chunk into the state's scratch and reduced from there -- min(nrows, 4 GiB / row) x ngroups floats that stay allocated
+ * with the state (the buffer msc_sweep_assign's materialised route uses).  All eight families and noop are taken.  flags is reserved: 0.
+ * A row's results do not depend on the rows around it: a call over a sub-range gives the bits the whole call gives
+ * for those rows (the kernels are chosen from the state and the view's rows, never the call's).
+ * The state is read-only: tables, counts, alpha, hp, the sweeps' device (seed, sweep) pair and a captured step graph
+ * are left as they were.  MSC_EINVAL for bad arguments and between msc_sweep_step_begin and msc_state_commit_reduce.
+ * Asynchronous on the context's stream.  msc_last_kernel(3) names the kernel that reduced the rows.
+ */
+int msc_score_marginal(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                       const int32_t *z_dev, uint32_t flags, float *logp_dev, int32_t *map_dev, float *map_logresp_dev);
 
 /* ---- per-value entry (the virtual group API, base.hpp:25-28) ----------- */
 typedef enum msc_value_op {
