@@ -30,6 +30,7 @@ SLICE_STEP_OUT = 64                   # m: the stepping-out limit of a slice upd
 SLICE_SHRINK = 256                    # rejected proposals before an update keeps its value
 ZMATRIX_MAX_ROWS = 1 << 18            # msc_zmatrix_create: m at most
 ZMATRIX_MAX_LABELS = 1 << 16          # ... and nlabels at most
+LINKAGE_MAX_N = 1 << 16               # msc_linkage_single: n at most
 
 
 class MicroscopesHipError(RuntimeError):
@@ -158,6 +159,7 @@ _SIGS = {
     "msc_zmatrix_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "msc_zmatrix_reset": (C.c_int, [C.c_void_p]),
     "msc_zmatrix_destroy": (C.c_int, [C.c_void_p]),
+    "msc_linkage_single": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(sorted(_SIGS))

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "launchers.hpp"
+#include "linkage_host.hpp"
 
 namespace msc {
 
@@ -3618,5 +3619,38 @@ extern "C" int msc_zmatrix_destroy(msc_zmatrix *zm) {
   (void)hipSetDevice(zm->ctx->device);
   (void)hipStreamSynchronize(zm->ctx->stream);
   delete zm;
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// single linkage of a dense z-matrix (scipy.cluster.hierarchy.linkage of 1 - Z; kernels_linkage.hip, linkage_host.hpp)
+// ---------------------------------------------------------------------------
+extern "C" int msc_linkage_single(msc_context *ctx, const float *z_dev, uint64_t ld, uint32_t n, uint32_t flags,
+                                  double *host_linkage, uint32_t *host_order) {
+  MSC_REQUIRE(ctx && z_dev, "null argument");
+  MSC_REQUIRE(flags == 0, "msc_linkage_single: flags = %u (none is defined)", flags);
+  MSC_REQUIRE(n >= 2, "msc_linkage_single: n = %u (a linkage needs two points)", n);
+  MSC_REQUIRE(ld >= n, "msc_linkage_single: ld = %llu is below n = %u", (unsigned long long)ld, n);
+  if (n > linkage::kMaxN)
+    return fail(MSC_EUNSUPPORTED, "msc_linkage_single: n = %u is above %u (one workgroup holds the chain's distances in "
+                "registers)", n, linkage::kMaxN);
+  MSC_TRY(device_error_check(ctx));
+  MSC_HIP(hipSetDevice(ctx->device));
+  const hipStream_t s = ctx->stream;
+  const size_t nvals = 3 * (size_t)(n - 1);
+  {
+    const hipError_t e = reserve_synced(s, ctx->linkage_edges, nvals);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "msc_linkage_single: the edge list of %zu bytes: %s",
+                  nvals * sizeof(double), hipGetErrorString(e));
+    }
+  }
+  if (launch_linkage_prim(s, z_dev, ld, n, ctx->linkage_edges)) return fail(MSC_EHIP, "k_linkage_prim launch failed");
+  std::vector<double> edges(nvals);
+  MSC_HIP(hipMemcpyAsync(edges.data(), ctx->linkage_edges, nvals * sizeof(double), hipMemcpyDeviceToHost, s));
+  MSC_HIP(hipStreamSynchronize(s));
+  MSC_TRY(device_error_check(ctx));
+  if (host_linkage || host_order) linkage::finish(edges.data(), n, host_linkage, host_order);
   return MSC_OK;
 }

@@ -287,4 +287,8 @@ int launch_zm_count(hipStream_t stream, const uint32_t *batch, uint32_t nt, bool
 int launch_zm_finish(hipStream_t stream, const uint32_t *counts, uint32_t nt, uint32_t m, const uint32_t *order,
                      bool norm, float S, void *out, uint64_t ld);
 
+// kernels_linkage.hip (msc_linkage_single): Prim's chain over the dense n x n matrix z (row stride ld), one workgroup
+// of linkage::shape_for(n) (linkage_host.hpp); edges[3 i ..] = (x, y, distance) of step i.  -2: n outside [2, 65536]
+int launch_linkage_prim(hipStream_t stream, const float *z, uint64_t ld, uint32_t n, double *edges);
+
 }  // namespace msc

@@ -450,6 +450,8 @@ struct msc_context {
   bool sync_word_ok = true;                // cleared when the stream operation is refused: plain stream waits from then on
   // the device's error word {code, detail} (device_error.hpp), pinned and shared by every context on the device
   volatile uint32_t *err_host = nullptr;
+  // msc_linkage_single: the chain's edges, 3 (n - 1) doubles, kept between calls
+  msc::DevBuf<double> linkage_edges;
 };
 
 struct msc_dataview {

@@ -3,12 +3,15 @@
 ``groups``, ``zmatrix``, ``zmatrix_reorder`` and ``zmatrix_heuristic_block_ordering`` take the same arguments, return the
 same values and raise the same ``ValueError``s.  Numpy input runs a vectorised numpy path.  Device tensors (or numpy input
 with ``ctx=``) build the z-matrix on the device (``ZMatrix``, ``msc_zmatrix_*``) and return a device tensor bit-equal to
-the numpy path.  The block ordering stays on the host: scipy's single linkage over the condensed upper triangle.
+the numpy path.  The block ordering is the leaf order of scipy's single linkage over the condensed upper triangle: scipy
+itself for numpy input, ``msc_linkage_single`` for a float32 device tensor (the same dendrogram, bit for bit).
+``zmatrix_linkage`` returns that dendrogram and ``zmatrix_clusters`` cuts a consensus partition out of it; the reference
+exposes neither.
 """
 import numpy as np
 import torch
 
-from ._lib import ZMATRIX_MAX_LABELS
+from ._lib import LINKAGE_MAX_N, ZMATRIX_MAX_LABELS
 from .runtime import Context, ZMatrix
 
 _HOST_CHUNK_FLOATS = 1 << 23      # one-hot block of the numpy path: at most 64 MiB of float64
@@ -146,13 +149,87 @@ def zmatrix_reorder(zmat, order):
     return zmat[o][:, o]
 
 
-def zmatrix_heuristic_block_ordering(zmat):
-    """A permutation of the rows that puts co-clustered rows next to each other: the leaves of scipy's single linkage of
-    the distances 1 - Z over the condensed upper triangle."""
+_NONFINITE = "The condensed distance matrix must contain only finite values."     # scipy's linkage says so
+_contexts = {}
+
+
+def _context_of(zmat, ctx):
+    """the caller's context, or one kept per device that follows torch's current stream"""
+    if ctx is not None:
+        return ctx
+    index = zmat.device.index if zmat.device.index is not None else torch.cuda.current_device()
+    c = _contexts.get(index)
+    if c is None or not getattr(c, "_h", None):
+        c = _contexts[index] = Context(device=index)
+    else:
+        c.set_stream(torch.cuda.current_stream(index))
+    return c
+
+
+def _device_linkage(zmat, ctx, linkage, order):
+    """(linkage, order) of a float32 device tensor by msc_linkage_single, or None where the tensor goes the host way.
+    The reference looks at the strict upper triangle alone; the kernel reads whole rows of a symmetric matrix, so a
+    tensor that is not symmetric is replaced by the mirror image of its upper triangle."""
+    if not (_is_device(zmat) and zmat.dtype == torch.float32):
+        return None
+    n = int(zmat.shape[0])
+    if n < 2 or n > LINKAGE_MAX_N:
+        return None
+    ctx = _context_of(zmat, ctx)
+    z = zmat.to(ctx.torch_device)
+    if not (bool(torch.isfinite(z).all()) and torch.equal(z, z.T)):
+        upper = torch.triu(z, diagonal=1)            # (zeros elsewhere, whatever was there)
+        if not bool(torch.isfinite(upper).all()):
+            raise ValueError(_NONFINITE)
+        z = upper + upper.T
+        del upper
+    if z.stride(1) != 1 or z.stride(0) < n:
+        z = z.contiguous()
+    return ctx.linkage_single(z, linkage=linkage, order=order)
+
+
+def _condensed_distances(zmat):
+    z = np.asarray(zmat.cpu() if isinstance(zmat, torch.Tensor) else zmat)
+    return 1. - np.array(z[np.triu_indices(z.shape[0], k=1)])
+
+
+def zmatrix_linkage(zmat, ctx=None):
+    """scipy's single linkage of the distances 1 - Z over the condensed upper triangle: the float64 [n - 1, 4] matrix
+    ``scipy.cluster.hierarchy.linkage(1. - zmat[np.triu_indices(n, 1)])`` returns.  A float32 device tensor of 2 <= n <=
+    65536 rows is linked on the device (msc_linkage_single: the same matrix, bit for bit); a view with contiguous rows
+    is read in place.  Everything else takes scipy on the host."""
     import scipy.cluster.hierarchy as hier
     if not _is_square(zmat):
         raise ValueError("not a zmat")
-    z = np.asarray(zmat.cpu() if isinstance(zmat, torch.Tensor) else zmat)
-    n = z.shape[0]
-    dist = 1. - np.array(z[np.triu_indices(n, k=1)])
-    return np.array(hier.leaves_list(hier.linkage(dist)))
+    got = _device_linkage(zmat, ctx, True, False)
+    if got is not None:
+        return got[0]
+    return hier.linkage(_condensed_distances(zmat))
+
+
+def zmatrix_heuristic_block_ordering(zmat, ctx=None):
+    """A permutation of the rows that puts co-clustered rows next to each other: the leaves of scipy's single linkage of
+    the distances 1 - Z over the condensed upper triangle.  A float32 device tensor stays on the device (see
+    ``zmatrix_linkage``); the permutation is a numpy array either way."""
+    import scipy.cluster.hierarchy as hier
+    if not _is_square(zmat):
+        raise ValueError("not a zmat")
+    got = _device_linkage(zmat, ctx, True, True)
+    if got is not None:
+        if (got[0][:, 2] < 0).any():                  # (an entry above 1: scipy's leaves_list refuses such a linkage)
+            raise ValueError("Linkage 'Z' contains negative distances.")
+        return got[1]
+    return np.array(hier.leaves_list(hier.linkage(_condensed_distances(zmat))))
+
+
+def zmatrix_clusters(zmat, threshold, ctx=None):
+    """The consensus partition at ``threshold``: rows i and j share a label when a chain of pairs with Z >= threshold
+    (1 - Z <= 1 - threshold) leads from one to the other -- the single linkage cut at the distance 1 - threshold,
+    ``fcluster(zmatrix_linkage(zmat), 1 - threshold, 'distance')`` as a partition.  Returns an integer array of n labels,
+    numbered from 0 in the order of their first row."""
+    import scipy.cluster.hierarchy as hier
+    flat = hier.fcluster(zmatrix_linkage(zmat, ctx=ctx), 1. - threshold, criterion="distance")
+    _, first, inv = np.unique(flat, return_index=True, return_inverse=True)
+    rank = np.empty(first.size, dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(first.size)
+    return rank[inv.reshape(-1)]

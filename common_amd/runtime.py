@@ -88,9 +88,28 @@ class Context(object):
 
     def last_kernel(self, which="score"):
         """the kernel instantiation of this process's most recent scoring ("score") or fused assignment ("sweep") pass, or
-        z-matrix kernel ("zmatrix"), as rocprofv3 spells it (msc_last_kernel): what bench.py keys the committed counter
+        z-matrix or linkage kernel ("zmatrix"), as rocprofv3 spells it (msc_last_kernel): what bench.py keys the committed counter
         summaries by"""
         return self.lib.msc_last_kernel({"score": 0, "zmatrix": 2, "marginal": 3}.get(which, 1)).decode()
+
+    def linkage_single(self, z, linkage=True, order=True):
+        """scipy's single linkage of the distances 1 - z and / or its leaf order (msc_linkage_single): z a float32
+        [n, n] tensor on this device, 2 <= n, with contiguous rows (any row stride >= n), SYMMETRIC and finite off the
+        diagonal (the diagonal's value is never used).  Returns (float64 [n - 1, 4] or None, int32 [n] or None).  Synchronous."""
+        if not isinstance(z, torch.Tensor) or z.dtype != torch.float32 or z.device != self.torch_device or z.dim() != 2 \
+                or z.shape[0] != z.shape[1] or z.stride(1) != 1 or z.stride(0) < z.shape[0]:
+            raise ValueError("z must be a square float32 tensor on %s with contiguous rows" % self.torch_device)
+        n = int(z.shape[0])
+        # rows that start on 16 bytes are read 16 bytes a lane, up to 3 floats past column n - 1 inside the row's ld: a
+        # view whose storage ends before that in its last row (as_strided can make one) is copied first
+        if (n - 1) * int(z.stride(0)) + (n + 3) // 4 * 4 > z.untyped_storage().nbytes() // 4 - int(z.storage_offset()):
+            z = z.contiguous()
+        lk = np.empty((max(n - 1, 0), 4), dtype=np.float64) if linkage else None
+        od = np.empty(n, dtype=np.uint32) if order else None
+        L.check(self.lib.msc_linkage_single(self._h, C.c_void_p(z.data_ptr()), int(z.stride(0)), n, 0,
+                                            None if lk is None else lk.ctypes.data_as(C.c_void_p),
+                                            None if od is None else od.ctypes.data_as(C.c_void_p)))
+        return lk, (None if od is None else od.astype(np.int32))
 
     def value_op(self, family, dim, op, hp, ss_record, value=None):
         """One group::{add_value, remove_value, score_value, score_data} call (base.hpp:25-28) as a batch
@@ -908,6 +927,19 @@ class ZMatrix(object):
     def result(self, order=None, out=None):
         """float32 [m, m] device tensor: counts / nsamples, as the reference's zmatrix computes it"""
         return self._write(self.ctx.lib.msc_zmatrix_result, order, out, torch.float32)
+
+    def linkage(self):
+        """scipy's single linkage of 1 - result() (query.zmatrix_linkage), float64 [m - 1, 4].  result() is materialised
+        into a temporary first: m x m floats on top of the accumulator's tiles."""
+        from . import query
+        return query.zmatrix_linkage(self.result(), ctx=self.ctx)
+
+    def block_ordering(self):
+        """query.zmatrix_heuristic_block_ordering of result(): result(order=zm.block_ordering()) is the matrix in block
+        order, with nothing quadratic crossing to the host.  result() is materialised into a temporary first: m x m
+        floats on top of the accumulator's tiles."""
+        from . import query
+        return query.zmatrix_heuristic_block_ordering(self.result(), ctx=self.ctx)
 
     def reset(self):
         self._check_open()

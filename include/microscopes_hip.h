@@ -88,7 +88,7 @@ const char *msc_build_info(void); /* "gfx950 hipcc <ver> ..." */
 /*
  * Which kernel INSTANTIATION the library chose for this process's most recent scoring pass (which = 0: msc_score_value)
  * or fused assignment pass (which = 1: msc_sweep_assign / msc_sweep_step), or the most recent kernel of the z-matrix
- * accumulator (which = 2: msc_zmatrix_*), or the kernel that reduced the rows of the most recent row predictive pass
+ * accumulator or of its linkage (which = 2: msc_zmatrix_*, msc_linkage_single), or the kernel that reduced the rows of the most recent row predictive pass
  * (which = 3: msc_score_marginal), spelled as rocprofv3 spells it, e.g.
  * "k_score_tile_roles<false, false, false>" ("" before the first such call).  Measurement tooling only: bench.py keys the
  * committed counter summaries (profiles/ *_pmc.json) by it, so that a roofline figure is always the figure of the kernel
@@ -691,6 +691,30 @@ int msc_zmatrix_result(msc_zmatrix *zm, const uint32_t *host_order, float *out_d
 /* zero the counts and drop the staged samples (asynchronous); destroy frees everything the accumulator allocated */
 int msc_zmatrix_reset(msc_zmatrix *zm);
 int msc_zmatrix_destroy(msc_zmatrix *zm);
+
+/* ---- single linkage of a z-matrix (replaces scipy's linkage in microscopes.common.query.zmatrix_heuristic_block_ordering) ---- */
+/*
+ * scipy.cluster.hierarchy.linkage(y, 'single') and leaves_list of it, for y the condensed distances 1 - Z of a dense
+ * float32 matrix on the device: z_dev[i * ld + j], 0 <= i, j < n, ld >= n (read only; a row of a strided view may start
+ * at any multiple of 4 bytes).  When z_dev and ld * 4 are multiples of 16 (of 8 for 1024 < n <= 2048) a row of n > 1024
+ * is read 16 (8) bytes a lane: up to 3 floats past column n - 1, inside the row's ld floats, which must then be readable
+ * in the last row too; their values are never used.  Otherwise one float at a time and nothing outside columns [0, n).
+ * The distance of i and j is 1.0f - Z[i][j] in float, as the reference forms it, widened to double in the output.
+ * Tie rule (it decides the tree: a z-matrix holds multiples of 1 / S): Prim's chain from point 0; every step moves to the
+ * unmerged point of the lowest (distance so far, index) in lexicographic order, i.e. the lowest index among equal
+ * distances; the n - 1 edges are then sorted by distance with a stable sort and relabelled by union-find, row i joining
+ * (min(root, root), max(root, root)) into node n + i.  Bit for bit scipy's matrix and scipy's leaf order (pre-order from
+ * node 2 n - 2, column 0 first) whenever every distance is finite.
+ * Precondition: Z is symmetric.  Step x reads row x alone, never column x, and the diagonal's value is never used (it may
+ * hold anything, NaN included).  A caller whose matrix is not symmetric passes a symmetrised copy (common_amd.query does).
+ * host_linkage (nullable): [n - 1][4] doubles (node, node, distance, size).  host_order (nullable): the n leaves.
+ * The chain runs in ONE workgroup whose threads hold its n distances in registers (msc_last_kernel(2) names the
+ * instantiation: columns a thread, wide loads or not): n <= 65536, MSC_EUNSUPPORTED above, before anything is launched.
+ * MSC_EINVAL for n < 2, ld < n, a null z_dev, or flags != 0 (none is defined).  Synchronous: the kernel, a copy of the
+ * 3 (n - 1) edge values, then the sort and the relabelling on the host.
+ */
+int msc_linkage_single(msc_context *ctx, const float *z_dev, uint64_t ld, uint32_t n, uint32_t flags,
+                       double *host_linkage, uint32_t *host_order);
 
 #ifdef __cplusplus
 }
