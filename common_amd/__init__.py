@@ -9,8 +9,9 @@ loudly when the HIP library or a gfx950 device is missing (there is no CPU path)
 from ._lib import (ACC_NO_COMMIT, ACC_RESET, ACC_SUBTRACT, BB, BBNC, BNB, DD, DM, GP, NICH, NIW, NOOP,
                    HP_CLUSTER, LINKAGE_MAX_N, PRED_MASKED_ONLY, SCORE_CRP_PRIOR, MicroscopesHipError, EXPORTS, LIB_PATH, load)
 from .runtime import Context, DataView, HpGrid, RelationView, SparseRelationView, State, ZMatrix, pack_hp, runtime_types_of, ss_dtype, type_of_numpy
-from . import dist, hypers, models, query
+from .chains import ChainEnsemble
+from . import chains, dist, hypers, models, query
 
-__all__ = ["Context", "DataView", "HpGrid", "hypers", "RelationView", "SparseRelationView", "State", "ZMatrix", "query", "BNB", "DM", "models", "dist", "load", "MicroscopesHipError", "BB", "BBNC", "GP", "DD",
+__all__ = ["ChainEnsemble", "chains", "Context", "DataView", "HpGrid", "hypers", "RelationView", "SparseRelationView", "State", "ZMatrix", "query", "BNB", "DM", "models", "dist", "load", "MicroscopesHipError", "BB", "BBNC", "GP", "DD",
            "NICH", "NIW", "NOOP", "pack_hp", "ss_dtype", "runtime_types_of", "type_of_numpy",
            "EXPORTS", "LIB_PATH", "HP_CLUSTER", "LINKAGE_MAX_N", "PRED_MASKED_ONLY", "SCORE_CRP_PRIOR", "ACC_RESET", "ACC_SUBTRACT", "ACC_NO_COMMIT"]

@@ -114,6 +114,14 @@ _SIGS = {
     "msc_sweep_step_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msc_sweep_sequential": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "msc_chains_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "msc_chains_destroy": (C.c_int, [C.c_void_p]),
+    "msc_chains_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    # (ch, view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, nsweeps, host_seeds, sweep, trace_every,
+    #  trace_dev, occupied_dev)
+    "msc_chains_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                   C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64,
+                                   C.c_uint32, C.c_void_p, C.c_void_p]),
     "msc_state_reduce_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "msc_state_commit_reduce": (C.c_int, [C.c_void_p]),

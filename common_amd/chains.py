@@ -1,0 +1,190 @@
+"""Many independent sequential Gibbs chains swept in one launch, a workgroup each (msc_chains_*, include/microscopes_hip.h).
+
+A ChainEnsemble owns nchains State objects of one shape and their assignment vectors.  Chain c of a sweep does exactly what
+State.sweep_sequential does on ens.states[c] with the same seed and arguments; the ensemble only runs them side by side.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .runtime import State
+
+_U64 = (1 << 64) - 1
+
+
+def trace_shape(nsweeps, trace_every, nchains, nrows):
+    """shape of the thinned trace of a sweep call: [nchains, nsweeps // trace_every, nrows] -- sample j of a chain is its z
+    after sweep (j + 1) * trace_every - 1 of the call; sweeps beyond the last whole multiple leave no sample"""
+    nsweeps, trace_every, nchains, nrows = int(nsweeps), int(trace_every), int(nchains), int(nrows)
+    if trace_every < 1:
+        raise ValueError("trace_every must be >= 1")
+    if nsweeps < 0 or nchains < 0 or nrows < 0:
+        raise ValueError("nsweeps, nchains and nrows must be >= 0")
+    return (nchains, nsweeps // trace_every, nrows)
+
+
+def chain_seeds(seed, nchains):
+    """the Philox key of every chain: an int gives chain c the key seed + c (mod 2^64); a sequence gives its entries"""
+    nchains = int(nchains)
+    if isinstance(seed, (int, np.integer)):
+        return [(int(seed) + c) & _U64 for c in range(nchains)]
+    seeds = [int(s) for s in seed]
+    if len(seeds) != nchains:
+        raise ValueError("seed must be an int or a sequence of nchains = %d ints (got %d)" % (nchains, len(seeds)))
+    for s in seeds:
+        if not 0 <= s <= _U64:
+            raise ValueError("every seed must lie in [0, 2^64)")
+    return seeds
+
+
+def _per_chain(what, value, nchains, is_one):
+    """one value for all chains, or a sequence of one per chain -> list of nchains"""
+    if value is None:
+        return [None] * nchains
+    if is_one(value):
+        return [value] * nchains
+    value = list(value)
+    if len(value) != nchains:
+        raise ValueError("%s must be one value or one per chain (%d chains, got %d)" % (what, nchains, len(value)))
+    return value
+
+
+class ChainEnsemble(object):
+    """nchains states of the same features and ngroups, swept together.
+
+    alpha: one float or nchains floats.  hps: one list with an hp (dict or packed array) per feature, used by every chain,
+    or nchains such lists.  ens.states[c] is an ordinary State: get_ss, hp_slice, predictive_logp, set_hp, ... work on it
+    between sweeps.  ens.z: int32 [nchains, nrows] on the device once assign() / seat() has run."""
+
+    def __init__(self, ctx, features, ngroups, nchains, alpha=None, hps=None):
+        nchains = int(nchains)
+        if nchains < 1:
+            raise ValueError("nchains must be >= 1")
+        self.ctx, self.nchains, self.K = ctx, nchains, int(ngroups)
+        self.states, self._h, self.z = [], None, None
+        alphas = _per_chain("alpha", alpha, nchains, lambda a: isinstance(a, (int, float, np.floating, np.integer)))
+        hpsets = _per_chain("hps", hps, nchains, lambda h: len(h) > 0 and isinstance(h[0], (dict, np.ndarray)))
+        try:
+            for c in range(nchains):
+                st = State(ctx, features, ngroups)
+                self.states.append(st)
+                if hpsets[c] is not None:
+                    if len(hpsets[c]) != len(st.features):
+                        raise ValueError("hps needs one entry per feature (%d, got %d)" % (len(st.features), len(hpsets[c])))
+                    for f, hp in enumerate(hpsets[c]):
+                        st.set_hp(f, hp)
+                if alphas[c] is not None:
+                    st.set_alpha(alphas[c])
+            self._h = _create(ctx, self.states)
+        except Exception:
+            self.close()
+            raise
+        self.features = self.states[0].features
+
+    # the assignment -----------------------------------------------------------
+    def assign(self, view, z):
+        """start every chain from z (int32 [nchains, nrows] or [nrows] for all, host or device; ids outside [0, ngroups)
+        are unassigned): ens.z becomes a copy and every state's tables are accumulated from its row"""
+        self._check_open()
+        n = int(view.nrows)
+        zt = torch.as_tensor(z)
+        if zt.dtype != torch.int32 or zt.dim() not in (1, 2) or zt.shape[-1] != n or (zt.dim() == 2 and zt.shape[0] != self.nchains):
+            raise ValueError("z must be int32 [nchains = %d, nrows = %d] or [nrows]" % (self.nchains, n))
+        zt = zt.to(self.ctx.torch_device)
+        self.z = (zt.expand(self.nchains, n) if zt.dim() == 1 else zt).contiguous().clone()
+        for c, st in enumerate(self.states):
+            st.accumulate(view, self.z[c])
+        self._view = view
+
+    def seat(self, view, seed=None, sweep=0):
+        """every row of every chain unassigned and the tables empty; the first sweep that follows is then sequential CRP
+        seating.  With a seed that sweep is run here (keys as in sweep(), sweep index `sweep`), so ens.z holds groups on return"""
+        self.assign(view, torch.full((int(view.nrows),), -1, dtype=torch.int32))
+        if seed is not None:
+            self.sweep(view, 1, seed, sweep=sweep)
+
+    # the sweep ----------------------------------------------------------------
+    def sweep(self, view, nsweeps, seed, sweep=0, order=None, trace_every=None, zmatrix=None, want_occupied=False, row0=0,
+              nrows=None, row_id0=None, cols=None):
+        """nsweeps sequential sweeps of every chain over rows [row0, row0 + nrows) (msc_chains_sweep; asynchronous).
+        seed: an int (chain c takes seed + c) or nchains ints; sweep: the counter's sweep index of the first sweep.
+        order: uint32 / int32 device tensor [nrows] (all chains) or [nchains, nrows] of offsets from row0.
+        trace_every = e: -> the int32 device tensor [nchains, nsweeps // e, nrows] holding z of the row range after every
+        e-th sweep; with want_occupied -> (trace, occupied), occupied int32 [nchains, nsweeps // e] the groups in use at
+        those moments.  zmatrix: a ZMatrix over the nrows rows that takes the whole trace in one add (trace_every
+        defaults to 1 then).  Without any of the three -> None."""
+        self._check_open()
+        if self.z is None:
+            raise ValueError("no assignment yet: call assign() or seat() first")
+        dev = self.ctx.torch_device
+        row0 = int(row0)
+        n = int(view.nrows) - row0 if nrows is None else int(nrows)
+        if row0 < 0 or n < 0 or row0 + n > self.z.shape[1] or self.z.shape[1] != view.nrows:
+            raise ValueError("rows [%d, %d) outside the assignment (%d rows)" % (row0, row0 + n, self.z.shape[1]))
+        nsweeps = int(nsweeps)
+        if not 0 <= nsweeps < (1 << 32):
+            raise ValueError("nsweeps must be in [0, 2^32)")
+        seeds = chain_seeds(seed, self.nchains)
+        op, ld_order = None, 0
+        if order is not None:
+            if not isinstance(order, torch.Tensor) or order.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
+                    or not order.is_contiguous() or order.device != dev \
+                    or tuple(order.shape) not in ((n,), (self.nchains, n)):
+                raise ValueError("order must be a contiguous int32 / uint32 tensor on %s of [nrows] or [nchains, nrows] "
+                                 "entries" % dev)
+            op, ld_order = C.c_void_p(order.data_ptr()), (n if order.dim() == 2 else 0)
+        if (zmatrix is not None or want_occupied) and trace_every is None:
+            trace_every = 1
+        trace = occupied = None
+        if trace_every is not None:
+            shape = trace_shape(nsweeps, trace_every, self.nchains, n)
+            if zmatrix is not None and (zmatrix.n != n or zmatrix.ctx is not self.ctx):
+                raise ValueError("zmatrix must be over the %d rows of the sweep, on the ensemble's context" % n)
+            trace = torch.empty(shape, dtype=torch.int32, device=dev)
+            if want_occupied:
+                occupied = torch.empty(shape[:2], dtype=torch.int32, device=dev)
+        for st in self.states:
+            st._drop_subsets()
+            st._bound_view = view        # (the library keeps no reference to a view: the states do, for the last one bound)
+        zp = self.z.data_ptr() + 4 * row0
+        L.check(self.ctx.lib.msc_chains_sweep(
+            self._h, view._h, self.states[0]._cols(cols), row0, n, row0 if row_id0 is None else int(row_id0),
+            C.c_void_p(zp), int(self.z.stride(0)), op, ld_order, nsweeps, (C.c_uint64 * self.nchains)(*seeds), int(sweep),
+            0 if trace_every is None else int(trace_every),
+            C.c_void_p(trace.data_ptr()) if trace is not None and trace.numel() else None,
+            C.c_void_p(occupied.data_ptr()) if occupied is not None and occupied.numel() else None))
+        if zmatrix is not None and trace.shape[1] > 0:
+            zmatrix.add(trace.view(-1, n))
+        if trace is None:
+            return None
+        return (trace, occupied) if want_occupied else trace
+
+    # lifetime -----------------------------------------------------------------
+    def _check_open(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("ChainEnsemble is closed")
+
+    def close(self):
+        """the handle first (a member state cannot be destroyed while it lives), then the states"""
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                self.ctx.lib.msc_chains_destroy(self._h)
+            self._h = None
+        for st in getattr(self, "states", ()):
+            st.close()
+        self.states = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _create(ctx, states):
+    hs = (C.c_void_p * len(states))(*[st._h.value for st in states])
+    h = C.c_void_p()
+    L.check(ctx.lib.msc_chains_create(hs, len(states), C.byref(h)))
+    return h

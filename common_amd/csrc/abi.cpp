@@ -1315,6 +1315,8 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
 
 extern "C" int msc_state_destroy(msc_state *st) {
   if (!st) return MSC_OK;
+  MSC_REQUIRE(st->chain_members == 0, "msc_state_destroy: the state is a member of %u live msc_chains handle(s), whose "
+                                      "table holds its buffers; destroy those first (msc_chains_destroy)", st->chain_members);
   (void)hipSetDevice(st->ctx->device);
   (void)hipStreamSynchronize(st->ctx->stream);
   if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
@@ -2696,6 +2698,169 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
   for (auto &h : st->feats) { h.raw_valid = true; h.additive_valid = true; h.derived_valid = true; }
   st->cnt_additive_valid = true;
   st->crp_valid = true;
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Many sequential chains in one launch (k_sweep_seq_chains): workgroup c carries the chain of member state c.
+// ---------------------------------------------------------------------------
+struct msc_chains {
+  msc_context *ctx = nullptr;
+  std::vector<msc_state *> states;
+  // the per-chain table of a call: filled on the host in one of two pinned areas, taken in turn, and copied to table_dev
+  // on the stream.  uploaded[i] is recorded after the copy out of area i; the host waits for it before it refills area i,
+  // so no pending copy reads an area that is being written.  table_dev itself is ordered by the stream: the copy of
+  // a call queues behind the launches of the call before it.
+  msc::PinnedBuf<msc::SeqChain> stage[2];
+  hipEvent_t uploaded[2] = {nullptr, nullptr};
+  bool pending[2] = {false, false};
+  int next = 0;
+  msc::DevBuf<msc::SeqChain> table_dev;   // [nchains]
+};
+
+extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc_chains **out) {
+  MSC_REQUIRE(states && out, "null argument");
+  *out = nullptr;
+  MSC_REQUIRE(nchains >= 1, "msc_chains_create: at least one state");
+  for (uint32_t c = 0; c < nchains; c++) {
+    const msc_state *st = states[c];
+    MSC_REQUIRE(st, "msc_chains_create: state %u is null", c);
+    MSC_REQUIRE(st->ctx == states[0]->ctx, "msc_chains_create: state %u lives on another context than state 0", c);
+    for (uint32_t b = 0; b < c; b++)
+      MSC_REQUIRE(states[b] != st, "msc_chains_create: state %u is state %u again (two workgroups on one state's tables "
+                                   "would race)", c, b);
+    MSC_REQUIRE(st->K == states[0]->K, "msc_chains_create: state %u has %u groups, state 0 has %u", c, st->K, states[0]->K);
+    MSC_REQUIRE(st->nfeat == states[0]->nfeat, "msc_chains_create: state %u has %u features, state 0 has %u", c, st->nfeat,
+                states[0]->nfeat);
+    for (uint32_t f = 0; f < st->nfeat; f++)
+      MSC_REQUIRE(st->feats[f].family == states[0]->feats[f].family && st->feats[f].dim == states[0]->feats[f].dim,
+                  "msc_chains_create: feature %u of state %u (family %d, dim %u) differs from state 0's (family %d, dim %u)",
+                  f, c, st->feats[f].family, st->feats[f].dim, states[0]->feats[f].family, states[0]->feats[f].dim);
+  }
+  const SeqRoute route = route_sequential(states[0]);      // (equal feature lists and K: one answer for all)
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  msc_context *ctx = states[0]->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<msc_chains> ch(new (std::nothrow) msc_chains());
+  if (!ch) return fail(MSC_ENOMEM, "out of host memory");
+  ch->ctx = ctx;
+  ch->states.assign(states, states + nchains);
+  hipError_t e = ch->table_dev.alloc(nchains);
+  for (int i = 0; i < 2 && e == hipSuccess; i++) {
+    e = ch->stage[i].alloc(nchains);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ch->uploaded[i], hipEventDisableTiming);
+  }
+  if (e != hipSuccess) {
+    for (hipEvent_t ev : ch->uploaded) if (ev) (void)hipEventDestroy(ev);
+    return fail(MSC_EHIP, "msc_chains_create: %s", hipGetErrorString(e));
+  }
+  for (msc_state *st : ch->states) st->chain_members++;
+  *out = ch.release();
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_destroy(msc_chains *ch) {
+  if (!ch) return MSC_OK;
+  (void)hipSetDevice(ch->ctx->device);
+  (void)hipStreamSynchronize(ch->ctx->stream);             // (a launch may still read the table)
+  for (int i = 0; i < 2; i++) {
+    if (ch->pending[i]) (void)hipEventSynchronize(ch->uploaded[i]);
+    if (ch->uploaded[i]) (void)hipEventDestroy(ch->uploaded[i]);
+  }
+  for (msc_state *st : ch->states) st->chain_members--;
+  delete ch;
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_size(const msc_chains *ch, uint32_t *nchains) {
+  MSC_REQUIRE(ch && nchains, "null argument");
+  *nchains = (uint32_t)ch->states.size();
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                                uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep, uint32_t trace_every,
+                                int32_t *trace_dev, uint32_t *occupied_dev) {
+  MSC_REQUIRE(ch && view, "null argument");
+  const uint32_t n = (uint32_t)ch->states.size();
+  if (n == 0) return MSC_OK;
+  MSC_REQUIRE((z_dev && host_seeds) || nrows == 0 || nsweeps == 0, "null argument");
+  MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
+  MSC_REQUIRE(ld_z >= nrows, "msc_chains_sweep: ld_z %llu < nrows %llu", (unsigned long long)ld_z, (unsigned long long)nrows);
+  MSC_REQUIRE(!order_dev || ld_order == 0 || ld_order >= nrows, "msc_chains_sweep: ld_order %llu is neither 0 (one order "
+              "for all chains) nor >= nrows %llu", (unsigned long long)ld_order, (unsigned long long)nrows);
+  const bool tracing = trace_dev != nullptr || occupied_dev != nullptr;
+  MSC_REQUIRE(!tracing || trace_every >= 1, "msc_chains_sweep: trace_every must be >= 1 with a trace or an occupied array");
+  for (uint32_t c = 0; c < n; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_sweep: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  if (nrows == 0 || nsweeps == 0) return MSC_OK;
+  // every table of every member current before, as msc_sweep_sequential
+  hipStream_t s = ctx->stream;
+  double visit_us = 0.0;
+  for (msc_state *st : ch->states) {
+    MSC_TRY(ensure_raw(st));
+    for (uint32_t f = 0; f < st->nfeat; f++)
+      if (!st->feats[f].additive_valid && launch_lift(s, st->desc_dev + f, 1, st->kpad, st->red_i64, st->cnt_u32, 0))
+        return fail(MSC_EHIP, "k_lift launch failed");
+    if (!st->cnt_additive_valid && launch_lift(s, st->desc_dev, 0, st->kpad, st->red_i64, st->cnt_u32, 1))
+      return fail(MSC_EHIP, "k_lift launch failed");
+    for (auto &h : st->feats) h.additive_valid = true;
+    st->cnt_additive_valid = true;
+    MSC_TRY(ensure_derived(st));
+    MSC_TRY(ensure_crp(st));
+    visit_us = std::max(visit_us, seq_visit_us(st));
+  }
+  // the table of this call (pointers and alpha may have changed since the last one), through the pinned area whose turn it is
+  const uint64_t ntrace = tracing ? nsweeps / trace_every : 0;
+  const int a = ch->next;
+  ch->next ^= 1;
+  if (ch->pending[a]) MSC_HIP(hipEventSynchronize(ch->uploaded[a]));
+  ch->pending[a] = false;
+  SeqChain *tab = ch->stage[a];
+  for (uint32_t c = 0; c < n; c++) {
+    const msc_state *st = ch->states[c];
+    SeqChain &e = tab[c];
+    e.feats = st->desc_dev;
+    e.cnt_acc = st->red_i64;
+    e.cnt_u32 = st->cnt_u32;
+    e.crp = st->logpc;
+    e.z = z_dev + (size_t)c * ld_z;
+    e.order = order_dev ? order_dev + (size_t)c * ld_order : nullptr;
+    e.trace = trace_dev && ntrace ? trace_dev + (size_t)c * ntrace * nrows : nullptr;
+    e.occupied = occupied_dev && ntrace ? occupied_dev + (size_t)c * ntrace : nullptr;
+    e.seed = host_seeds[c];
+    e.alpha = st->alpha;
+    e.pad = 0;
+  }
+  MSC_HIP(hipMemcpyAsync(ch->table_dev, tab, sizeof(SeqChain) * n, hipMemcpyHostToDevice, s));
+  MSC_HIP(hipEventRecord(ch->uploaded[a], s));
+  ch->pending[a] = true;
+  // a launch's visits: what one chain may take in the launch's time (as msc_sweep_sequential, by the costliest member),
+  // divided by the rounds the grid runs in -- at this kernel's register count one workgroup is resident per CU
+  const msc_state *st0 = ch->states[0];
+  const uint64_t visits = (uint64_t)nsweeps * nrows;
+  const double one = std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / visit_us));
+  const uint64_t rounds = (n + (uint32_t)std::max(1, ctx->num_cus) - 1) / (uint32_t)std::max(1, ctx->num_cus);
+  const uint64_t per_launch = std::max<uint64_t>(1, (uint64_t)one / rounds);
+  for (uint64_t v0 = 0; v0 < visits; v0 += per_launch) {
+    const uint64_t v1 = std::min(visits, v0 + per_launch);
+    const int rc = launch_sweep_seq_chains(s, ch->table_dev, n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows, row_id0, v0,
+                                           v1, sweep, tracing ? trace_every : 1u);
+    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq_chains does not take this shape");
+    if (rc) return fail(MSC_EHIP, "k_sweep_seq_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  // the kernel kept every table of every member current: additive sums, fields, constants, counts and CRP terms
+  for (msc_state *st : ch->states) {
+    for (auto &h : st->feats) { h.raw_valid = true; h.additive_valid = true; h.derived_valid = true; }
+    st->cnt_additive_valid = true;
+    st->crp_valid = true;
+  }
   return MSC_OK;
 }
 

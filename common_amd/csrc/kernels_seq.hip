@@ -15,6 +15,8 @@
 //                 empty slots lives in LDS for the launch.  The score tables are read from global memory (L2 at these
 //                 sizes).  A launch takes the visits that fit a time budget (abi.cpp seq_visit_us); the state carries over in
 //                 global memory.
+//   k_sweep_seq_chains   a grid of such workgroups, one independent chain each (msc_chains_sweep): what differs per chain
+//                 is a SeqChain entry of a device table; also a thinned trace and the occupied-slot count per sample.
 #include "commit_ops.hpp"
 #include "device_error.hpp"
 #include "family_math.hpp"
@@ -162,15 +164,17 @@ static __device__ unsigned long long g_seq_phase[6];
 #define SEQ_STAMP(i) do {} while (0)
 #endif
 
-// visits [v0, v1) of the call's nsweeps x nrows: visit v is sweep v / nrows, position v % nrows of the order.
+// The chain's workgroup, whichever kernel launched it: both kernels below are this function and nothing else, so a chain
+// of k_sweep_seq_chains performs exactly the arithmetic of a k_sweep_seq launch with the same arguments.
+// Visits [v0, v1) of the call's nsweeps x nrows: visit v is sweep v / nrows, position v % nrows of the order.
 // Scoring: K >= the block, thread t sums every feature for groups t, t + 256, ...; fewer groups, the block is nq = 256 / K
 // slices of K threads and slice q sums features q, q + nq, ... (partials summed in slice order: the same bits every run)
-__global__ __launch_bounds__(kSeqThreads) void k_sweep_seq(const FeatDesc *__restrict__ feats, int nfeat, uint32_t K,
-                                                           uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
-                                                           int32_t *z, const uint32_t *__restrict__ order, uint64_t v0,
-                                                           uint64_t v1, uint64_t seed, uint64_t sweep, long long *cnt_acc,
-                                                           uint32_t *cnt_u32, float alpha, float *crp, int32_t *trace) {
-  __shared__ SeqShared sh;
+// trace (nullable): after sweep s of the call, when (s + 1) % trace_every == 0, z of the row range goes to sample
+// (s + 1) / trace_every - 1; occupied (nullable): K - the empty slots at the same moments.
+MSC_DEV void seq_visits(SeqShared &sh, const FeatDesc *__restrict__ feats, int nfeat, uint32_t K, uint32_t kpad,
+                        uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *__restrict__ order,
+                        uint64_t v0, uint64_t v1, uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32,
+                        float alpha, float *crp, int32_t *trace, uint32_t trace_every, uint32_t *occupied) {
   const uint32_t t = threadIdx.x, nt = kSeqThreads, lane = t & 63u, wave = t >> 6, nw = kSeqThreads / 64;
   if (t == 0) sh.nempty = 0;
   __syncthreads();
@@ -286,8 +290,11 @@ __global__ __launch_bounds__(kSeqThreads) void k_sweep_seq(const FeatDesc *__res
       }
       SEQ_STAMP(4);
     }
-    if (trace != nullptr && pos + 1 == nrows) {          // the row range's assignment after sweep s
-      for (uint64_t i = t; i < nrows; i += nt) trace[s * nrows + i] = z[i];
+    if ((trace != nullptr || occupied != nullptr) && pos + 1 == nrows && (s + 1) % trace_every == 0) {
+      const uint64_t j = (s + 1) / trace_every - 1;      // the row range's assignment after sweep s
+      if (trace != nullptr)
+        for (uint64_t i = t; i < nrows; i += nt) trace[j * nrows + i] = z[i];
+      if (occupied != nullptr && t == 0) occupied[j] = K - sh.nempty;
       __syncthreads();
     }
   }
@@ -299,6 +306,37 @@ __global__ __launch_bounds__(kSeqThreads) void k_sweep_seq(const FeatDesc *__res
 #endif
 }
 
+// visits [v0, v1) of the call's nsweeps x nrows: visit v is sweep v / nrows, position v % nrows of the order.
+__global__ __launch_bounds__(kSeqThreads) void k_sweep_seq(const FeatDesc *__restrict__ feats, int nfeat, uint32_t K,
+                                                           uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
+                                                           int32_t *z, const uint32_t *__restrict__ order, uint64_t v0,
+                                                           uint64_t v1, uint64_t seed, uint64_t sweep, long long *cnt_acc,
+                                                           uint32_t *cnt_u32, float alpha, float *crp, int32_t *trace) {
+  __shared__ SeqShared sh;
+  seq_visits(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp,
+             trace, 1u, nullptr);
+}
+
+// the same visits of gridDim.x independent chains (msc_chains_sweep): workgroup c carries chain c, whose state, z, order,
+// key and outputs come from chains[c]; the fields are read once, into what k_sweep_seq has as arguments
+__global__ __launch_bounds__(kSeqThreads) void k_sweep_seq_chains(const SeqChain *__restrict__ chains, int nfeat, uint32_t K,
+                                                                  uint32_t kpad, uint64_t row0, uint64_t nrows,
+                                                                  uint64_t row_id0, uint64_t v0, uint64_t v1, uint64_t sweep,
+                                                                  uint32_t trace_every) {
+  __shared__ SeqShared sh;
+  const SeqChain &c = chains[blockIdx.x];
+  const FeatDesc *feats = c.feats;
+  int32_t *z = c.z, *trace = c.trace;
+  long long *cnt_acc = c.cnt_acc;
+  uint32_t *cnt_u32 = c.cnt_u32, *occupied = c.occupied;
+  float *crp = c.crp;
+  const uint32_t *order = c.order;
+  const float alpha = c.alpha;
+  const uint64_t seed = c.seed;
+  seq_visits(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp,
+             trace, trace_every, occupied);
+}
+
 int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
                      uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *order, uint64_t v0, uint64_t v1,
                      uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32, float alpha, float *crp,
@@ -306,6 +344,15 @@ int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, u
   if (nfeat < 0 || nfeat > kSeqMaxFeat || K == 0 || K > kSeqMaxGroups) return -2;
   hipLaunchKernelGGL(k_sweep_seq, dim3(1), dim3(kSeqThreads), 0, stream, feats_dev, nfeat, K, kpad, row0, nrows, row_id0,
                      z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp, trace);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_sweep_seq_chains(hipStream_t stream, const SeqChain *chains_dev, uint32_t nchains, int nfeat, uint32_t K,
+                            uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t v0, uint64_t v1,
+                            uint64_t sweep, uint32_t trace_every) {
+  if (nfeat < 0 || nfeat > kSeqMaxFeat || K == 0 || K > kSeqMaxGroups || nchains == 0 || trace_every == 0) return -2;
+  hipLaunchKernelGGL(k_sweep_seq_chains, dim3(nchains), dim3(kSeqThreads), 0, stream, chains_dev, nfeat, K, kpad, row0,
+                     nrows, row_id0, v0, v1, sweep, trace_every);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -188,6 +188,24 @@ int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, u
                      uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *order, uint64_t v0, uint64_t v1,
                      uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32, float alpha, float *crp,
                      int32_t *trace);
+// ... and of nchains independent chains, one workgroup each (msc_chains_sweep): what differs per chain
+struct SeqChain {
+  const FeatDesc *feats;   // the chain's state: descriptors, counts (additive, u32), CRP terms
+  long long *cnt_acc;
+  uint32_t *cnt_u32;
+  float *crp;
+  int32_t *z;              // int32 [nrows] of the row range
+  const uint32_t *order;   // uint32 [nrows] or null (ascending)
+  int32_t *trace;          // int32 [ntrace][nrows] or null
+  uint32_t *occupied;      // uint32 [ntrace] or null
+  uint64_t seed;           // the chain's Philox key
+  float alpha;
+  uint32_t pad;
+};
+// trace_every >= 1: sample (s + 1) / trace_every - 1 is written after sweep s of the call when (s + 1) % trace_every == 0
+int launch_sweep_seq_chains(hipStream_t stream, const SeqChain *chains_dev, uint32_t nchains, int nfeat, uint32_t K,
+                            uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t v0, uint64_t v1,
+                            uint64_t sweep, uint32_t trace_every);
 
 // kernels_niw.hip
 int launch_niw_prepare(hipStream_t stream, const FeatDesc *feats_dev, uint32_t f, uint32_t dim, uint32_t K,

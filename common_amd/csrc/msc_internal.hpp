@@ -624,6 +624,7 @@ struct msc_state {
   msc::PinnedBuf<msc::PredFeat> pred_stage;     // pinned staging of the upload
   hipEvent_t pred_upload = nullptr;             // recorded after the upload from pred_stage
   bool pred_upload_pending = false;
+  uint32_t chain_members = 0;                   // live msc_chains handles that hold this state: it cannot be destroyed meanwhile
 };
 
 // a z-matrix accumulator (abi.cpp msc_zmatrix_*, kernels_query.hip): m selected rows, counts as upper-triangle tiles

@@ -768,10 +768,11 @@ class State(object):
     def close(self):
         self._drop_subsets()                            # (the subset states predictive_logp(given=) kept)
         if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):           # (see DataView.close)
+                # (refused while the state is a member of a live ChainEnsemble's handle: the state stays open)
+                L.check(self.ctx.lib.msc_state_destroy(self._h))
             for g in list(getattr(self, "_grids", ())):  # (the library frees a state's grids with it)
                 g._h = None
-            if getattr(self.ctx, "_h", None):           # (see DataView.close)
-                self.ctx.lib.msc_state_destroy(self._h)
             self._h = None
 
     def __del__(self):

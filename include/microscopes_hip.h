@@ -190,6 +190,7 @@ int msc_dataview_column(const msc_dataview *view, uint32_t feature, void **dev_p
  */
 int msc_state_create(msc_context *ctx, const msc_feature_spec *features, uint32_t nfeatures,
                      uint32_t ngroups, msc_state **out);
+/* MSC_EINVAL, and the state lives on, while it is a member of an msc_chains handle (destroy the handle first) */
 int msc_state_destroy(msc_state *st);
 int msc_state_shape(const msc_state *st, uint32_t *nfeatures, uint32_t *ngroups);
 
@@ -366,6 +367,58 @@ int msc_sweep_step_stats(const msc_state *st, uint64_t *eager_steps, uint64_t *g
 int msc_sweep_sequential(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                          uint64_t row_id0, int32_t *z_dev, const uint32_t *order_dev, uint32_t nsweeps, uint64_t seed,
                          uint64_t sweep, int32_t *trace_dev);
+
+/*
+ * MANY sequential chains in one launch.  An msc_chains handle groups nchains states of one context; msc_chains_sweep
+ * runs msc_sweep_sequential's sweeps on all of them at once, a workgroup (one compute unit) per chain, where a single
+ * call occupies one compute unit of the card.  The chains need nothing from each other.
+ * msc_chains_create: at least one state; all on one context; pairwise distinct (two workgroups on one state's tables
+ * would race); equal ngroups and equal feature lists (family and dim) -- hyper-parameters, suff-stats and alpha may
+ * differ per chain.  A violation is MSC_EINVAL and names the offending index.  The families and limits are
+ * msc_sweep_sequential's (niw, dm, bbnc: MSC_EUNSUPPORTED; at most 256 features and 8192 groups), checked here once
+ * since no call changes them.  While the handle lives its member states cannot be destroyed: msc_state_destroy
+ * returns MSC_EINVAL (destroy the handle first); every other call on a member state keeps working between sweeps.
+ * msc_chains_destroy waits for the context's stream.  msc_chains_size: the number of chains.
+ *
+ * msc_chains_sweep: chain c performs exactly what
+ *   msc_sweep_sequential(states[c], view, cols, row0, nrows, row_id0, z_dev + c * ld_z, order of c, nsweeps,
+ *                        host_seeds[c], sweep, ...)
+ * performs -- the same arithmetic in the same order, so the same bits in z, the tables and the trace.  That is the
+ * contract.  Layout:
+ *   z_dev         int32, chain c's row range at z_dev + c * ld_z, ld_z >= nrows;
+ *   order_dev     nullable; uint32 offsets from row0; ld_order == 0: one order of nrows entries shared by all chains,
+ *                 else chain c's at order_dev + c * ld_order, ld_order >= nrows;
+ *   host_seeds    uint64[nchains] on the host: the Philox key of each chain.  The counter of the draw at a row in sweep
+ *                 s of the call stays (row_id0 + offset, sweep + s), whatever the chain;
+ *   trace_dev     nullable; int32 [nchains][ntrace][nrows], contiguous, ntrace = nsweeps / trace_every: after sweep s of
+ *                 the call, when (s + 1) % trace_every == 0, chain c's z of the row range goes to sample
+ *                 (s + 1) / trace_every - 1.  As [nchains * ntrace][nrows] it is what msc_zmatrix_add takes;
+ *   occupied_dev  nullable; uint32 [nchains][ntrace]: the chain's occupied slots (ngroups - its empty slots) at the same
+ *                 moments;
+ *   trace_every   ignored when both are null, otherwise >= 1 (a trace_every > nsweeps writes no sample).
+ * On return (asynchronously) every table of every member state is current, as after msc_sweep_sequential.  nrows == 0
+ * or nsweeps == 0 changes nothing and returns MSC_OK.  The per-chain table (pointers, keys, alpha: read afresh from the
+ * states at every call) reaches the device through a buffer the handle owns; the host fills one of TWO pinned staging
+ * areas, taken in turn, each with an event recorded after the copy out of it, and waits for that event before it fills
+ * the area again, so a call never writes under a pending copy; the device buffer is ordered by the stream (calls on one
+ * handle go to one stream, or the caller orders them).  A launch takes max(1, V / R) visits of every chain, V the
+ * visits msc_sweep_sequential would give the costliest member and R = ceil(nchains / compute units) the rounds a grid
+ * beyond the compute units runs in (one workgroup is resident per compute unit), so a launch stays inside its time
+ * budget on a shared card.
+ * Errors: MSC_EINVAL for a null argument, nrows >= 2^32, ld_z < nrows, ld_order neither 0 nor >= nrows, trace_every
+ * == 0 with a trace or an occupied array, rows outside the view, a column that does not fit a feature, or a member
+ * between msc_sweep_step_begin and msc_state_commit_reduce (the index is named); MSC_EDEVICE when an earlier kernel
+ * reported an error.  An order entry >= nrows skips that visit and a leave from an empty group only joins, in any
+ * chain; both surface as MSC_EDEVICE at the next call (one error word serves all chains).
+ */
+typedef struct msc_chains msc_chains;
+int msc_chains_create(msc_state *const *states, uint32_t nchains, msc_chains **out);
+int msc_chains_destroy(msc_chains *ch);
+int msc_chains_size(const msc_chains *ch, uint32_t *nchains);
+int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                     uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                     uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep,
+                     uint32_t trace_every, int32_t *trace_dev, uint32_t *occupied_dev);
 
 /* ---- multi-GPU hook ---------------------------------------------------- */
 /*

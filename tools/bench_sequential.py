@@ -8,7 +8,14 @@ With --phases (and MSC_LIB_PATH naming the experiment build `make -C common_amd/
 EXTRA=-DMSC_SEQ_PHASES`): the kernel's own s_memtime stamps split the timed sweeps' visits into read / leave / score / draw /
 join, reported as shares and as microseconds of the measured visit.  Prints one JSON line per shape.
 
+With --chains C[,C...]: ChainEnsemble.sweep (msc_chains_sweep, a workgroup per chain) instead, one sweep of C chains
+timed warm with device events around the call, on one nich column and on the C3 mix at D = 64, K = 256; beside it the
+route without the ensemble, back-to-back State.sweep_sequential calls on the same states (timed on --loop-chains of them
+and scaled to C: the calls run one after another, one compute unit each).  Writes microseconds per visit per chain,
+aggregate visits per second and the ratio to that loop into --out, with the date and the commit.
+
     python tools/bench_sequential.py [--rows 10000] [--steps 3] [--route-rows 300] [--posterior] [--phases]
+    python tools/bench_sequential.py --chains 1,16,64,256,512 [--sweep-rows 10000] [--out profiles/chains.txt]
 """
 import argparse
 import ctypes as C
@@ -125,8 +132,63 @@ def posterior(ctx, sweeps_seq=200000, sweeps_batched=20000):
     return res
 
 
+def chains(ctx, mix, N, K, counts, steps, sweep_rows, loop_chains):
+    """one result per chain count: a timed sweep of rows [0, sweep_rows) by every chain of an ensemble, and by a loop of
+    single-chain calls over the same states"""
+    spec = MIXES[mix]
+    cols, z = make_columns(ctx, spec, N, K, seed=K + len(spec))
+    view = common_amd.DataView.from_tensors(ctx, cols)
+    R = min(sweep_rows, N)
+
+    def timed(fn):
+        ms = []
+        for s in range(steps + 1):                        # (the first is the warm-up)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn(s)
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        return min(ms[1:])
+
+    res = []
+    for nc in counts:
+        ens = common_amd.ChainEnsemble(ctx, spec, K, nc, alpha=1.0)
+        ens.assign(view, z)
+        torch.cuda.synchronize()
+        ens_ms = timed(lambda s: ens.sweep(view, 1, 1000, sweep=s, nrows=R))
+        L = min(nc, loop_chains)
+
+        def loop(s):
+            for c in range(L):
+                ens.states[c].sweep_sequential(view, ens.z[c], 1000 + c, 100 + s, nrows=R)
+        loop_ms = timed(loop) * nc / L
+        ens.close()
+        res.append(dict(mix=mix, K=K, N=N, features=len(spec), chains=nc, rows_swept=R,
+                        us_per_visit_per_chain=round(ens_ms * 1e3 / R, 3),
+                        visits_per_s=round(nc * R / (ens_ms * 1e-3)),
+                        loop_us_per_visit=round(loop_ms * 1e3 / (nc * R), 3), loop_states_timed=L,
+                        ratio_to_loop=round(loop_ms / ens_ms, 2)))
+        print(json.dumps(res[-1]), flush=True)
+    return res
+
+
+def commit_id():
+    import subprocess
+    try:
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL,
+                                       text=True).strip()
+    except Exception:
+        return "unknown"
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", default=None, help="chain counts, e.g. 1,16,64,256,512: time ChainEnsemble.sweep instead")
+    ap.add_argument("--sweep-rows", type=int, default=10000, help="--chains: rows of the N a timed sweep visits")
+    ap.add_argument("--loop-chains", type=int, default=16, help="--chains: states the single-chain loop is timed on")
+    ap.add_argument("--commit", default=None, help="--chains: the commit the figures belong to (default: git's HEAD)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "chains.txt"))
     ap.add_argument("--rows", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--route-rows", type=int, default=300)
@@ -134,6 +196,21 @@ def main():
     ap.add_argument("--phases", action="store_true")
     a = ap.parse_args()
     ctx = common_amd.Context(device=0)
+    if a.chains:
+        import datetime
+        counts = [int(c) for c in a.chains.split(",")]
+        lines = ["# Many sequential chains in one launch (msc_chains_sweep, k_sweep_seq_chains): %s, %s, commit %s"
+                 % (torch.cuda.get_device_name(0), datetime.date.today().isoformat(), a.commit or commit_id()),
+                 "# one sweep of rows_swept rows by every chain, best of %d warm calls, device events around the call;"
+                 % a.steps,
+                 "# loop: back-to-back State.sweep_sequential calls on the same states, timed on loop_states_timed of "
+                 "them and scaled to `chains`"]
+        for mix in ("nich1", "c3_d64"):
+            lines += [json.dumps(r) for r in chains(ctx, mix, a.rows, 256, counts, a.steps, a.sweep_rows, a.loop_chains)]
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        return
     for mix in ("nich1", "bb16", "c3_d64"):
         for K in (16, 64, 256, 1024):
             print(json.dumps(shape(ctx, mix, a.rows, K, a.steps, a.route_rows, a.phases)), flush=True)
