@@ -114,6 +114,13 @@ _SIGS = {
     "msc_sweep_step_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msc_sweep_sequential": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "msc_blocked_draw": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "msc_blocked_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32)]),
+    "msc_blocked_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                     C.c_uint64, C.c_uint64]),
+    "msc_sweep_blocked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                    C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "msc_chains_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
     "msc_chains_destroy": (C.c_int, [C.c_void_p]),
     "msc_chains_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

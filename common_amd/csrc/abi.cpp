@@ -9,6 +9,7 @@
 #include <mutex>
 #include <new>
 
+#include "blocked_post.hpp"
 #include "launchers.hpp"
 #include "linkage_host.hpp"
 
@@ -1339,6 +1340,7 @@ extern "C" int msc_state_set_hp(msc_state *st, uint32_t feature, const float *ho
   MSC_REQUIRE(nfloats == h.hp.size(), "feature %u: hp block has %zu floats, expected %zu", feature,
               nfloats, h.hp.size());
   std::copy(host_hp, host_hp + nfloats, h.hp.begin());
+  st->blk_drawn = false;
   if (nfloats) {
     MSC_HIP(hipMemcpyAsync(h.hp_dev, h.hp.data(), nfloats * sizeof(float), hipMemcpyHostToDevice, st->ctx->stream));
     MSC_HIP(hipStreamSynchronize(st->ctx->stream));
@@ -1364,6 +1366,7 @@ extern "C" int msc_state_get_hp(const msc_state *st, uint32_t feature, float *ho
 }
 
 static int launch_commit_all(msc_state *st) {
+  st->blk_drawn = false;                                   // (the fields change: a blocked draw made from them is stale)
   if (launch_commit(st->ctx->stream, st->desc_dev, (int)st->nfeat, st->kpad, st->red_i64, st->cnt_u32))
     return fail(MSC_EHIP, "k_commit launch failed");
   for (uint32_t f = 0; f < st->nfeat; f++)
@@ -1400,6 +1403,7 @@ extern "C" int msc_state_set_ss(msc_state *st, uint32_t feature, uint32_t first_
   MSC_REQUIRE(nbytes == rec * ngroups, "expected %zu bytes of records, got %zu", rec * ngroups, nbytes);
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(ensure_raw(st));
+  st->blk_drawn = false;
   if (h.family == MSC_NIW) {
     // record = {u32 count, f32 sum_x[d], f32 sum_xxT[d*d]}; device keeps count as a row and the
     // float block group-major
@@ -1491,6 +1495,7 @@ extern "C" int msc_state_set_alpha(msc_state *st, float alpha) {
   MSC_REQUIRE(alpha > 0.f, "alpha must be positive (group_manager.hpp:78)");
   st->alpha = alpha;
   st->crp_valid = false;
+  st->blk_drawn = false;
   return MSC_OK;
 }
 
@@ -1509,6 +1514,7 @@ extern "C" int msc_state_set_group_counts(msc_state *st, const uint32_t *host_co
   MSC_HIP(hipStreamSynchronize(st->ctx->stream));
   st->cnt_additive_valid = false;
   st->crp_valid = false;
+  st->blk_drawn = false;
   return MSC_OK;
 }
 
@@ -2119,6 +2125,7 @@ enum : uint32_t { kAccZeroed = 0x100, kAccThenPrepare = 0x200 };
 
 static int commit_and_prepare(msc_state *st, bool bump_rng = true) {
   hipStream_t s = st->ctx->stream;
+  st->blk_drawn = false;
   if (launch_commit_prepare(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, st->red_i64, st->cnt_u32, st->alpha,
                             st->logpc, bump_rng ? st->rng_dev : nullptr, prepare_value_slices(st)))
     return fail(MSC_EHIP, "k_commit_prepare launch failed");
@@ -2140,6 +2147,7 @@ static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32
                            uint64_t nrows, const int32_t *z_dev, uint32_t flags) {
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   hipStream_t s = st->ctx->stream;
+  st->blk_drawn = false;
   if (flags & MSC_ACC_RESET) {
     if (!(flags & kAccZeroed) && launch_zero64(s, st->red_i64, st->n_i64, st->red_f64, st->n_f64))
       return fail(MSC_EHIP, "k_zero64 launch failed");
@@ -2220,6 +2228,7 @@ extern "C" int msc_entity_op(msc_state *st, const msc_dataview *view, const uint
   st->cnt_additive_valid = true;
   MSC_TRY(ensure_derived(st));
   MSC_TRY(ensure_crp(st));
+  st->blk_drawn = false;
   if (launch_entity_op(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row, group, sign > 0 ? 1 : -1, st->red_i64, st->cnt_u32,
                        st->alpha, st->logpc, z_dev ? z_dev + row : nullptr))
     return fail(MSC_EHIP, "k_entity_op launch failed");
@@ -2506,6 +2515,7 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
   hipStream_t s = st->ctx->stream;
+  st->blk_drawn = false;                                  // (a replayed graph passes none of the functions that say so)
   auto eager = [&]() -> int {
     st->step_graph.n_eager++;
     bool zeroed = false;
@@ -2673,6 +2683,7 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   if (nrows == 0 || nsweeps == 0) return MSC_OK;
+  st->blk_drawn = false;
   // every table current before (as msc_entity_op): the reference's fields, the additive sums, score constants, CRP terms
   hipStream_t s = st->ctx->stream;
   MSC_TRY(ensure_raw(st));
@@ -2698,6 +2709,171 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
   for (auto &h : st->feats) { h.raw_valid = true; h.additive_valid = true; h.derived_valid = true; }
   st->cnt_additive_valid = true;
   st->crp_valid = true;
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The blocked (uncollapsed) Gibbs sampler (kernels_blocked.hip, blocked_post.hpp): draw every slot's parameters and the
+// stick weights from the tables, then every row's slot independently under them.
+// ---------------------------------------------------------------------------
+// Which assign kernel a state takes, and whether the sampler takes it at all.  By the state alone: every kernel adds a
+// row's terms in the same order (blk_tile_scores), so a sub-range draws what the whole draws whichever is chosen.
+//   nich1   a single nich column: the row's value in a register, no LDS
+//   staged  up to 256 features: the workgroup's row values staged in LDS once, [feature][row] -- 256 rows a workgroup up
+//           to 32 features, 128 up to 64, 64 beyond (32 KiB at most, 64 KiB from 129 features on)
+//   global  more features than that: the values re-read from the columns for every eight slots
+struct BlockedRoute { int rc = MSC_OK; const char *why = ""; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
+static BlockedRoute route_blocked(const msc_state *st, uint64_t nrows) {
+  BlockedRoute r;
+  (void)nrows;
+  for (const auto &h : st->feats)
+    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
+      r.rc = MSC_EUNSUPPORTED;
+      r.why = "the blocked sweep takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
+      return r;
+    }
+  if (st->nfeat >= blocked::kStickTag) {
+    r.rc = MSC_EUNSUPPORTED;
+    r.why = "the blocked sweep takes fewer than 32767 features";
+    return r;
+  }
+  if (st->nfeat == 1 && st->feats[0].family == MSC_NICH) r.kernel = BlockedKernel::nich1;
+  else if (st->nfeat <= 256) {                          // (at most 32 KiB of LDS a workgroup: several a compute unit)
+    r.kernel = BlockedKernel::staged;
+    r.block = st->nfeat <= 32 ? 256 : st->nfeat <= 64 ? 128 : 64;
+  }
+  return r;
+}
+
+// the parameter table and the features as the kernels read them (columns from the current binding, if any)
+static int blocked_setup(msc_state *st) {
+  if (!st->blk_tab) {
+    uint32_t rows = 1;
+    for (const auto &h : st->feats) rows += blocked_slices(h.family, h.dim);
+    MSC_TRY(alloc_zeroed(st->blk_tab, (size_t)rows * st->kpad));
+    MSC_TRY(alloc_zeroed(st->blk_work, 2 * (size_t)st->K));
+    MSC_TRY(alloc_zeroed(st->blk_feats_dev, std::max<size_t>(1, st->nfeat)));
+    st->blk_rows = rows;
+  }
+  std::vector<BlkFeat> fs(st->nfeat);
+  uint32_t row = 1;
+  for (uint32_t f = 0; f < st->nfeat; f++) {
+    const msc_feature_host &h = st->feats[f];
+    const FeatDesc &d = st->desc_host[f];
+    BlkFeat &b = fs[f];
+    std::memset(&b, 0, sizeof(b));
+    switch (h.family) {
+      case MSC_BB: b.kind = MSC_BLK_SELECT; break;
+      case MSC_GP:
+      case MSC_BNB: b.kind = MSC_BLK_LINEAR; break;
+      case MSC_DD: b.kind = MSC_BLK_GATHER; break;
+      case MSC_NICH: b.kind = MSC_BLK_NICH; break;
+      default: b.kind = MSC_BLK_NOOP; break;
+    }
+    b.slice0 = row;
+    b.nslices = blocked_slices(h.family, h.dim);
+    row += b.nslices;
+    b.family = h.family;
+    b.dim = h.dim;
+    b.tag = f;
+    b.col = d.col;
+    b.mask = d.mask;
+    b.hp = h.hp_dev;
+    b.raw_u32 = h.raw_u32;
+    b.raw_f32 = h.raw_f32;
+  }
+  if (fs.size() != st->blk_feats_host.size() ||
+      (!fs.empty() && std::memcmp(fs.data(), st->blk_feats_host.data(), fs.size() * sizeof(BlkFeat)) != 0)) {
+    if (!fs.empty()) {
+      MSC_HIP(hipMemcpyAsync(st->blk_feats_dev, fs.data(), fs.size() * sizeof(BlkFeat), hipMemcpyHostToDevice, st->ctx->stream));
+      MSC_HIP(hipStreamSynchronize(st->ctx->stream));
+    }
+    st->blk_feats_host = std::move(fs);
+  }
+  return MSC_OK;
+}
+
+static int blocked_draw_impl(msc_state *st, uint64_t seed, uint64_t sweep) {
+  // the draw reads the reference's fields and the group counts: both current before (the additive sums and the score
+  // constants it does not read are left as they are)
+  MSC_TRY(ensure_raw(st));
+  MSC_TRY(blocked_setup(st));
+  if (launch_blocked_draw(st->ctx->stream, st->blk_feats_dev, st->nfeat, st->K, st->kpad, st->cnt_u32, st->alpha, seed, sweep,
+                          st->blk_work, st->blk_tab))
+    return MSC_EHIP;
+  st->blk_drawn = true;
+  return MSC_OK;
+}
+
+static int blocked_assign_impl(msc_state *st, const BlockedRoute &route, const msc_dataview *view, const uint32_t *cols,
+                               uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
+  MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  MSC_REQUIRE(st->blk_drawn, "msc_blocked_assign: no parameter draw made from the tables as they stand (msc_blocked_draw "
+                             "first; whatever changes tables, hyper-parameters, alpha or group counts makes a draw stale)");
+  MSC_TRY(blocked_setup(st));
+  if (launch_blocked_assign(st->ctx->stream, route.kernel, route.block, st->blk_feats_dev, (int)st->nfeat, st->blk_tab, st->K,
+                            st->kpad, row0, nrows, row_id0, z_dev, seed, sweep))
+    return MSC_EHIP;
+  return MSC_OK;
+}
+
+extern "C" int msc_blocked_draw(msc_state *st, uint64_t seed, uint64_t sweep) {
+  MSC_REQUIRE(st, "null state");
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_blocked_draw between msc_sweep_step_begin and msc_state_commit_reduce: the "
+                                     "additive tables hold uncommitted sums");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  const BlockedRoute route = route_blocked(st, 0);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  return blocked_draw_impl(st, seed, sweep);
+}
+
+extern "C" int msc_blocked_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
+  MSC_REQUIRE(st, "null state");
+  MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  const BlockedRoute route = route_blocked(st, 0);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  MSC_TRY(blocked_setup(st));
+  const bool w = feature == UINT32_MAX;
+  if (dev) *dev = st->blk_tab + (w ? 0 : (size_t)st->blk_feats_host[feature].slice0 * st->kpad);
+  if (nslices) *nslices = w ? 1u : st->blk_feats_host[feature].nslices;
+  if (ld) *ld = st->kpad;
+  return MSC_OK;
+}
+
+extern "C" int msc_blocked_assign(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                  uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
+  MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_blocked_assign between msc_sweep_step_begin and msc_state_commit_reduce: the "
+                                     "additive tables hold uncommitted sums");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  const BlockedRoute route = route_blocked(st, nrows);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  return blocked_assign_impl(st, route, view, cols, row0, nrows, row_id0, z_dev, seed, sweep);
+}
+
+extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                 uint64_t row_id0, int32_t *z_dev, uint32_t nsweeps, uint64_t seed, uint64_t sweep,
+                                 int32_t *trace_dev, uint32_t *top_slot_dev) {
+  MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_sweep_blocked between msc_sweep_step_begin and msc_state_commit_reduce: the "
+                                     "additive tables hold uncommitted sums");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  const BlockedRoute route = route_blocked(st, nrows);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  hipStream_t s = st->ctx->stream;
+  for (uint32_t i = 0; i < nsweeps; i++) {
+    MSC_TRY(blocked_draw_impl(st, seed, sweep + i));
+    MSC_TRY(blocked_assign_impl(st, route, view, cols, row0, nrows, row_id0, z_dev, seed, sweep + i));
+    MSC_TRY(accumulate_impl(st, view, cols, row0, nrows, z_dev, MSC_ACC_RESET));
+    if (trace_dev && nrows)
+      MSC_HIP(hipMemcpyAsync(trace_dev + (size_t)i * nrows, z_dev, nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (top_slot_dev && launch_blocked_top_slot(s, st->cnt_u32, st->K, top_slot_dev + i)) return MSC_EHIP;
+  }
   return MSC_OK;
 }
 
@@ -2857,6 +3033,7 @@ extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const 
   }
   // the kernel kept every table of every member current: additive sums, fields, constants, counts and CRP terms
   for (msc_state *st : ch->states) {
+    st->blk_drawn = false;
     for (auto &h : st->feats) { h.raw_valid = true; h.additive_valid = true; h.derived_valid = true; }
     st->cnt_additive_valid = true;
     st->crp_valid = true;
@@ -2888,6 +3065,7 @@ extern "C" int msc_state_reduce_pack(msc_state *st, void **pack_dev, size_t *n_f
 }
 extern "C" int msc_state_reduce_unpack(msc_state *st) {
   MSC_REQUIRE(st, "null state");
+  st->blk_drawn = false;
   MSC_REQUIRE(st->red_pack, "msc_state_reduce_unpack before msc_state_reduce_pack");
   MSC_HIP(hipSetDevice(st->ctx->device));
   if (launch_pack64(st->ctx->stream, true, st->red_i64, st->n_i64, st->red_f64, st->n_f64, st->red_pack))
@@ -3178,6 +3356,7 @@ static void hp_installed(msc_state *st, uint32_t feature, const float *blk) {
   msc_feature_host &h = st->feats[feature];
   std::copy(blk, blk + h.hp.size(), h.hp.begin());
   h.derived_valid = false;
+  st->blk_drawn = false;
   if (h.family == MSC_DD || h.family == MSC_DM) {
     double asum = 0;
     for (float a : h.hp) asum += (double)a;
@@ -3189,6 +3368,7 @@ static void hp_installed(msc_state *st, uint32_t feature, const float *blk) {
 }
 // the same for alpha, which the device takes from the host at the next call that reads it (msc_state_set_alpha)
 static void alpha_installed(msc_state *st, float alpha) {
+  st->blk_drawn = false;
   st->alpha = alpha;
   st->crp_valid = false;
 }

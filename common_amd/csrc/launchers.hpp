@@ -207,6 +207,15 @@ int launch_sweep_seq_chains(hipStream_t stream, const SeqChain *chains_dev, uint
                             uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t v0, uint64_t v1,
                             uint64_t sweep, uint32_t trace_every);
 
+// kernels_blocked.hip: the blocked Gibbs sampler (msc_blocked_*; abi.cpp route_blocked chooses the assign kernel)
+enum class BlockedKernel { nich1, staged, global };
+int launch_blocked_draw(hipStream_t stream, const BlkFeat *fs_dev, uint32_t nfeat, uint32_t K, uint32_t kpad,
+                        const uint32_t *cnt, float alpha, uint64_t seed, uint64_t sweep, double *work, float *tab);
+int launch_blocked_assign(hipStream_t stream, BlockedKernel kernel, uint32_t block, const BlkFeat *fs_dev, int nfeat,
+                          const float *tab, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
+                          int32_t *z, uint64_t seed, uint64_t sweep);
+int launch_blocked_top_slot(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint32_t *out);
+
 // kernels_niw.hip
 int launch_niw_prepare(hipStream_t stream, const FeatDesc *feats_dev, uint32_t f, uint32_t dim, uint32_t K,
                        uint32_t kpad);

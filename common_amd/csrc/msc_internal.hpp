@@ -294,6 +294,34 @@ inline uint32_t pred_par_stride(int family, uint32_t dim) {
   }
 }
 
+// One feature of the blocked Gibbs sampler as the kernels of kernels_blocked.hip read it (msc_blocked_*): where the draw
+// finds hp and the slot's suff-stats, where its slices sit in the state's parameter table (row 0 of the table holds the
+// log weights; blocked_post.hpp lists the slices), and the bound column the assign kernels score.
+enum BlkKind : uint32_t { MSC_BLK_NOOP = 0, MSC_BLK_SELECT = 1, MSC_BLK_LINEAR = 2, MSC_BLK_GATHER = 3, MSC_BLK_NICH = 4 };
+struct BlkFeat {
+  uint32_t kind;             // BlkKind: how a value meets the slices
+  uint32_t slice0;           // first table row of the feature's slices
+  uint32_t nslices;
+  int32_t family;
+  uint32_t dim;
+  uint32_t tag;              // the feature's index: the Philox stream of its draws
+  const void *col;           // bound column in the model's value type (null until a view is bound)
+  const uint8_t *mask;
+  const float *hp;
+  const uint32_t *raw_u32;
+  const float *raw_f32;
+};
+inline uint32_t blocked_slices(int family, uint32_t dim) {
+  switch (family) {
+    case MSC_BB:
+    case MSC_GP:
+    case MSC_BNB: return 2;
+    case MSC_NICH: return 3;
+    case MSC_DD: return dim;
+    default: return 0;
+  }
+}
+
 // one feature of the index matrix as k_pack_look_idx reads it
 struct LookIdxSrc {
   const void *col;
@@ -624,6 +652,15 @@ struct msc_state {
   msc::PinnedBuf<msc::PredFeat> pred_stage;     // pinned staging of the upload
   hipEvent_t pred_upload = nullptr;             // recorded after the upload from pred_stage
   bool pred_upload_pending = false;
+  // the blocked Gibbs sampler (abi.cpp msc_blocked_*): the parameter table -- (1 + sum of the features' slices) rows of
+  // kpad floats, row 0 the log stick weights -- the features as the kernels read them, the stick kernel's scratch
+  // (log V, log(1 - V): 2 K doubles), and whether the table was drawn from the tables as they stand
+  msc::DevBuf<float> blk_tab;
+  msc::DevBuf<msc::BlkFeat> blk_feats_dev;
+  std::vector<msc::BlkFeat> blk_feats_host;
+  msc::DevBuf<double> blk_work;
+  uint32_t blk_rows = 0;
+  bool blk_drawn = false;
   uint32_t chain_members = 0;                   // live msc_chains handles that hold this state: it cannot be destroyed meanwhile
 };
 

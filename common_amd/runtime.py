@@ -517,6 +517,66 @@ class State(object):
                                                   row0 if row_id0 is None else row_id0, C.c_void_p(z.data_ptr()), op,
                                                   int(nsweeps), int(seed), int(sweep), tp))
 
+    # the blocked (uncollapsed) Gibbs sampler ---------------------------------
+    def blocked_draw(self, seed, sweep):
+        """draw every slot's parameters and the stick weights from the tables as they stand (msc_blocked_draw)"""
+        L.check(self.ctx.lib.msc_blocked_draw(self._h, int(seed), int(sweep)))
+
+    def blocked_tables(self):
+        """{"logw": float32[K], feature index: float32[nslices, K]}: views onto the device tables of the latest draw
+        (msc_blocked_tables; the slices per family are listed in include/microscopes_hip.h)"""
+        out = {}
+        for f in [None] + list(range(len(self.features))):
+            p, ns, ld = C.c_void_p(), C.c_uint32(), C.c_uint32()
+            L.check(self.ctx.lib.msc_blocked_tables(self._h, 0xffffffff if f is None else f, C.byref(p), C.byref(ns),
+                                                    C.byref(ld)))
+            if ns.value == 0:
+                t = torch.empty((0, self.K), dtype=torch.float32, device=self.ctx.torch_device)
+            else:
+                t = _alias_tensor(p.value, ns.value * ld.value, torch.float32, self.ctx.torch_device,
+                                  self).view(ns.value, ld.value)[:, :self.K]
+            out["logw" if f is None else f] = t[0] if f is None else t
+        return out
+
+    def blocked_assign(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
+        """every row's slot drawn independently under the parameters of the latest blocked_draw (msc_blocked_assign)"""
+        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
+        n = view.nrows - row0 if nrows is None else nrows
+        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
+            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+        L.check(self.ctx.lib.msc_blocked_assign(self._h, view._h, self._cols(cols), row0, n,
+                                                row0 if row_id0 is None else row_id0,
+                                                C.c_void_p(z.data_ptr()), int(seed), int(sweep)))
+
+    def sweep_blocked(self, view, z, seed, sweep, nsweeps=1, trace=None, top_slot=None, row0=0, nrows=None,
+                      row_id0=None, cols=None):
+        """nsweeps blocked Gibbs sweeps: draw the parameters, draw every row's slot, accumulate (msc_sweep_blocked).
+        trace: int32 device tensor of nsweeps x nrows, z after every sweep; top_slot: int32 / uint32 device tensor of
+        nsweeps entries, the highest occupied slot after every sweep (K - 1: raise K)."""
+        self._drop_subsets()
+        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
+        n = view.nrows - row0 if nrows is None else nrows
+        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
+            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+        if not 0 <= int(nsweeps) < (1 << 32):
+            raise ValueError("nsweeps must be in [0, 2^32)")
+        if z.device != self.ctx.torch_device:
+            raise ValueError("z must live on the context's device")
+        tp = sp = None
+        if trace is not None:
+            if trace.dtype != torch.int32 or not trace.is_contiguous() or trace.numel() < int(nsweeps) * n \
+                    or trace.device != z.device:
+                raise ValueError("trace must be a contiguous int32 device tensor of nsweeps x nrows entries")
+            tp = C.c_void_p(trace.data_ptr())
+        if top_slot is not None:
+            if top_slot.element_size() != 4 or top_slot.is_floating_point() or not top_slot.is_contiguous() \
+                    or top_slot.numel() < int(nsweeps) or top_slot.device != z.device:
+                raise ValueError("top_slot must be a contiguous 32-bit integer device tensor of nsweeps entries")
+            sp = C.c_void_p(top_slot.data_ptr())
+        L.check(self.ctx.lib.msc_sweep_blocked(self._h, view._h, self._cols(cols), row0, n,
+                                               row0 if row_id0 is None else row_id0, C.c_void_p(z.data_ptr()),
+                                               int(nsweeps), int(seed), int(sweep), tp, sp))
+
     def sweep_step_stats(self):
         """(steps run launch by launch, steps run as one graph launch)"""
         e, g = C.c_uint64(), C.c_uint64()

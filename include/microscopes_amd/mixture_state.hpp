@@ -330,6 +330,22 @@ public:
     stale_ = true;
   }
 
+  // nsweeps BLOCKED Gibbs sweeps over all entities on the device (msc_sweep_blocked): the truncated stick-breaking
+  // sampler -- every slot's parameters and the stick weights drawn from the tables, then every entity's slot drawn
+  // independently under them, the tables rebuilt -- exact up to the truncation at the state's slot count and parallel
+  // over entities.  The first draw conditions on the tables as they stand; as gibbs_sweep, the host partition follows the
+  // assignment vector lazily (sync()).  Non-conjugate (bbnc), niw and dm components throw: the library refuses them.
+  void gibbs_sweep_blocked(uint64_t seed, uint64_t sweep, common::rng_t &rng, uint32_t nsweeps = 1) {
+    (void)rng;                                          // (every draw is the device's)
+    if (any_nonconj_) throw std::runtime_error("gibbs_sweep_blocked takes conjugate components only");
+    for (const auto &s : specs_)
+      if (s.family == MSC_NIW || s.family == MSC_DM)
+        throw std::runtime_error("gibbs_sweep_blocked does not take niw or dm components");
+    push_params(true);
+    check(msc_sweep_blocked(st_, view_, nullptr, 0, n_, 0, z_dev_, nsweeps, seed, sweep, nullptr, nullptr));
+    stale_ = true;
+  }
+
   // Posterior predictive draws for new, partly observed rows (downstream's sample_post_pred): each row of `rows` (the
   // state's column layout, with its mask) gets a group drawn from the CRP term plus the scores of its observed entries
   // against the tables as they stand, then its masked entries are drawn from that group's posterior predictive -- ONE

@@ -420,6 +420,65 @@ int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *c
                      uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep,
                      uint32_t trace_every, int32_t *trace_dev, uint32_t *occupied_dev);
 
+/*
+ * The BLOCKED (uncollapsed) Gibbs sampler for the truncated stick-breaking Dirichlet process mixture (Ishwaran & James,
+ * JASA 2001): an exact sampler that is parallel over rows.  With ngroups = K slots a sweep draws, given the tables,
+ * every slot's component parameters from their conjugate posteriors and the mixture weights from the stick-breaking
+ * posterior, and then every row's slot INDEPENDENTLY from pi_k f(x | theta_k): rows do not depend on each other, so
+ * nothing is stale.  Against the CRP posterior the only error is the truncation: the L1 distance of the marginal
+ * density is at most 4 N exp(-(K - 1) / alpha) (N rows) -- 1e-12 at K = 32, alpha = 1, N = 6.
+ *
+ * msc_blocked_draw: makes the reference's fields and the group counts current, then draws, for every slot k < K (an
+ * empty slot draws from the prior)
+ *   V_k ~ Beta(1 + n_k, alpha + sum_{l > k} n_l) for k < K - 1, V_{K-1} = 1;
+ *   log pi_k = log V_k + sum_{l < k} log(1 - V_l), summed in slot order in double;
+ * and the parameters of every feature into a state-owned float32 table of slices, [slice][ld] with the slot minor:
+ *
+ *   family  posterior draw (hp + the slot's suff-stats)                      slices                   log-lik. of value v
+ *   bb      p ~ Beta(alpha + heads, beta + tails)                            log(1 - p), log p        slice v
+ *   gp      lambda ~ Gamma(alpha + sum, rate inv_beta + count)               -lambda, log lambda      s0 + v s1
+ *   bnb     p ~ Beta(alpha + r count, beta + sum)                            r log p, log(1 - p)      s0 + v s1
+ *   dd      theta ~ Dirichlet(alpha_i + c_i): dim gammas from one stream     log theta_i, i < dim     slice v
+ *           in value order, normalised in double
+ *   nich    sigma^2 = nu' sigma'^2 / chi2(nu'), mu ~ N(mu', sigma^2/kappa')  -log(2 pi sigma^2) / 2,  s0 + s2 (v - s1)^2
+ *           (kappa' = kappa + n, nu' = nu + n, mu' = (kappa mu + n mean) /   mu, -1 / (2 sigma^2)
+ *           kappa', nu' sigma'^2 = nu sigma^2 + ctv + n kappa (mu-mean)^2 / kappa')
+ *   noop    --                                                               none                     0
+ *
+ * (terms that do not depend on the slot -- lgamma(v + 1) and the like -- are dropped: they cancel in the draw).  Draws
+ * are made in double and stored as floats; every stored value is finite (the log of 0 is stored as -1e28).  The Philox
+ * key is seed ^ 0x9FB21C651E98DF25; the stream of (slot, feature) is that of msc_sample_predictive's entries with the
+ * slot as the row (counter words: slot, slot >> 32, sweep, 0x80000000 | feature << 16 | block), the stick weights take
+ * feature 0x7fff.  Nothing else enters a counter: two states with equal tables -- the ranks of a row-sharded run after the
+ * all-reduce -- draw bit-identical tables.
+ *
+ * msc_blocked_tables: the table of one feature (*dev = float[*nslices][*ld], the slot minor) or, feature == UINT32_MAX,
+ * the log weights (one slice).  The pointers stay valid for the state's life.
+ *
+ * msc_blocked_assign: for every row of [row0, row0 + nrows): s_k = log pi_k + sum over features of the log-likelihood
+ * of the row's value under slot k (masked entries skipped; dd values clamped into [0, dim)), over all K slots, then
+ * z_dev[r] by util::sample_discrete_log semantics with the dart philox_uniform01(seed, sweep, row_id0 + r) -- the
+ * counter msc_sweep_step uses.  Reads the drawn table only; no table of the state is touched.  MSC_EINVAL when no draw
+ * was made, when anything that changes tables, hyper-parameters, alpha or group counts ran since the draw (the draw is
+ * stale), and between msc_sweep_step_begin and msc_state_commit_reduce.
+ *
+ * msc_sweep_blocked: sweep s of nsweeps does msc_blocked_draw(seed, sweep + s), msc_blocked_assign(seed, sweep + s),
+ * msc_accumulate(MSC_ACC_RESET) of the same rows (commit included).  The first draw conditions on the state's tables as
+ * they stand at the call (z_dev's content is not read).  trace_dev (nullable): int32[nsweeps * nrows], z after every
+ * sweep; top_slot_dev (nullable): uint32[nsweeps], the highest occupied slot after every sweep -- K - 1 means the
+ * truncation binds and K should be raised.  Asynchronous; the reference's fields, the additive sums and the group
+ * counts are current on return, and msc_sweep_step's device (seed, sweep) pair and graph are untouched.
+ *
+ * Families: bb, gp, bnb, dd, nich and noop.  States with niw, dm or bbnc features: MSC_EUNSUPPORTED from all four.
+ */
+int msc_blocked_draw(msc_state *st, uint64_t seed, uint64_t sweep);
+int msc_blocked_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld);
+int msc_blocked_assign(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                       uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep);
+int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                      uint64_t row_id0, int32_t *z_dev, uint32_t nsweeps, uint64_t seed, uint64_t sweep,
+                      int32_t *trace_dev, uint32_t *top_slot_dev);
+
 /* ---- multi-GPU hook ---------------------------------------------------- */
 /*
  * The additive form of every table, ready for a sum all-reduce across row
