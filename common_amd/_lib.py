@@ -26,6 +26,8 @@ PRED_MASKED_ONLY = 0x1
 PRED_GROUP_KEY = 0xD1B54A32D192ED03   # msc_sample_predictive's group draw uses key = seed ^ this
 PRIOR_FLAT, PRIOR_EXPONENTIAL, PRIOR_NORMAL, PRIOR_NONINF_BETA = range(4)   # msc_slice_coord.prior
 SLICE_KEY = 0x2545F4914F6CDD1D        # msc_hp_slice / msc_theta_slice use key = seed ^ this
+SPLIT_MERGE_KEY = 0xA0761D6478BD642F  # msc_split_merge's streams: key = (seed ^ this) + stream * SPLIT_MERGE_STREAM_STRIDE
+SPLIT_MERGE_STREAM_STRIDE = 0x9E3779B97F4A7C15
 SLICE_STEP_OUT = 64                   # m: the stepping-out limit of a slice update
 SLICE_SHRINK = 256                    # rejected proposals before an update keeps its value
 ZMATRIX_MAX_ROWS = 1 << 18            # msc_zmatrix_create: m at most
@@ -121,6 +123,13 @@ _SIGS = {
                                      C.c_uint64, C.c_uint64]),
     "msc_sweep_blocked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                     C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    # (st, view, cols, row0, nrows, row_id0, z_dev, nproposals, launch_iters, seed, sweep, log_dev, trace_dev,
+    #  proposed_dev, counters_dev)
+    "msc_split_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                  C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "msc_split_merge_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32)]),
     "msc_chains_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
     "msc_chains_destroy": (C.c_int, [C.c_void_p]),
     "msc_chains_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

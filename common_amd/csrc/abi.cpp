@@ -12,6 +12,7 @@
 #include "blocked_post.hpp"
 #include "launchers.hpp"
 #include "linkage_host.hpp"
+#include "splitmerge_math.hpp"
 
 namespace msc {
 
@@ -1322,6 +1323,7 @@ extern "C" int msc_state_destroy(msc_state *st) {
   (void)hipStreamSynchronize(st->ctx->stream);
   if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
   if (st->pred_upload) (void)hipEventDestroy(st->pred_upload);
+  if (st->sm_pair) (void)msc_state_destroy(st->sm_pair);
   delete st;
   return MSC_OK;
 }
@@ -2874,6 +2876,138 @@ extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const 
       MSC_HIP(hipMemcpyAsync(trace_dev + (size_t)i * nrows, z_dev, nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (top_slot_dev && launch_blocked_top_slot(s, st->cnt_u32, st->K, top_slot_dev + i)) return MSC_EHIP;
   }
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The split-merge move (kernels_splitmerge.hip, splitmerge_math.hpp): Metropolis-Hastings proposals that split one group
+// in two or merge two groups, the launch state reached by restricted BLOCKED Gibbs passes over the rows of the two groups.
+// ---------------------------------------------------------------------------
+// Which assign kernel a state takes, and whether the move takes it at all: the families and the shapes of route_blocked
+// (every kernel adds a row's terms in the same order, so the choice never changes a bit).
+struct SplitMergeRoute { int rc = MSC_OK; const char *why = ""; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
+static SplitMergeRoute route_splitmerge(const msc_state *st, uint64_t nrows) {
+  SplitMergeRoute r;
+  (void)nrows;
+  for (const auto &h : st->feats)
+    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
+      r.rc = MSC_EUNSUPPORTED;
+      r.why = "split-merge takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
+      return r;
+    }
+  if (st->nfeat >= blocked::kStickTag) {
+    r.rc = MSC_EUNSUPPORTED;
+    r.why = "split-merge takes fewer than 32767 features";
+    return r;
+  }
+  if (st->nfeat == 1 && st->feats[0].family == MSC_NICH) r.kernel = BlockedKernel::nich1;
+  else if (st->nfeat < 256) {                           // (the codes and the waves' sums within 64 KiB of LDS a workgroup)
+    r.kernel = BlockedKernel::staged;
+    r.block = st->nfeat <= 32 ? 256 : st->nfeat <= 64 ? 128 : 64;
+  }
+  return r;
+}
+
+// the pair state (three slots: the pair's two, and their union for score_data), created at the first call; its
+// hyper-parameters and alpha follow the state's before every call
+constexpr uint32_t kSmSlots = 3;
+static int sm_setup(msc_state *st) {
+  if (!st->sm_pair) {
+    std::vector<msc_feature_spec> specs(st->nfeat);
+    for (uint32_t f = 0; f < st->nfeat; f++) {
+      specs[f].family = st->feats[f].family;
+      specs[f].dim = st->feats[f].dim;
+    }
+    MSC_TRY(alloc_zeroed(st->sm_prop, 1));
+    MSC_TRY(alloc_zeroed(st->sm_sd, (size_t)st->nfeat * kSmSlots));
+    MSC_TRY(msc_state_create(st->ctx, specs.data(), st->nfeat, kSmSlots, &st->sm_pair));
+  }
+  msc_state *pair = st->sm_pair;
+  for (uint32_t f = 0; f < st->nfeat; f++)
+    if (pair->feats[f].hp != st->feats[f].hp)
+      MSC_TRY(msc_state_set_hp(pair, f, st->feats[f].hp.data(), st->feats[f].hp.size()));
+  pair->alpha = st->alpha;
+  return MSC_OK;
+}
+
+extern "C" int msc_split_merge(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                               uint64_t row_id0, int32_t *z_dev, uint32_t nproposals, uint32_t launch_iters, uint64_t seed,
+                               uint64_t sweep, double *log_dev, int32_t *trace_dev, int32_t *proposed_dev,
+                               uint64_t *counters_dev) {
+  MSC_REQUIRE(st && view && z_dev, "null argument");
+  MSC_REQUIRE(!st->rng_bump_pending, "msc_split_merge between msc_sweep_step_begin and msc_state_commit_reduce: the "
+                                     "additive tables hold uncommitted sums");
+  MSC_REQUIRE(launch_iters <= 1024, "launch_iters %u beyond 1024", launch_iters);
+  MSC_REQUIRE(nrows < (1ull << 48), "msc_split_merge takes fewer than 2^48 rows");
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  const SplitMergeRoute route = route_splitmerge(st, nrows);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  MSC_TRY(ensure_raw(st));                                 // (the group sizes: where a split finds its empty slot)
+  MSC_TRY(sm_setup(st));
+  msc_state *pair = st->sm_pair;
+  hipStream_t s = st->ctx->stream;
+  const uint32_t nparts = sm_assign_blocks(nrows, route.block);
+  MSC_HIP(reserve_synced(s, st->sm_ell, (size_t)std::max<uint64_t>(nrows, 1)));
+  MSC_HIP(reserve_synced(s, st->sm_part, nparts));
+  ZeroSpans zero;
+  zero.a = reinterpret_cast<unsigned long long *>(pair->red_i64.get());
+  zero.na = pair->n_i64;
+  zero.b = reinterpret_cast<unsigned long long *>(pair->red_f64.get());
+  zero.nb = pair->n_f64;
+  // the proposals move the group sizes on the device (k_sm_relabel); everything else is rebuilt at the end
+  st->cnt_additive_valid = false;
+  st->crp_valid = false;
+  st->blk_drawn = false;
+  for (uint32_t p = 0; p < nproposals; p++) {
+    const uint64_t sw = sweep + p;
+    if (launch_sm_begin(s, z_dev, nrows, row_id0, st->cnt_u32, st->K, seed, sw, st->sm_prop, st->sm_ell, zero)) return MSC_EHIP;
+    for (uint32_t t = 0; t <= launch_iters; t++) {
+      // the pair slots' suff-stats from the labels, their parameters and the K = 2 stick, then the rows' labels
+      MSC_TRY(accumulate_impl(pair, view, cols, row0, nrows, st->sm_ell, MSC_ACC_RESET | kAccZeroed));
+      MSC_TRY(blocked_setup(pair));
+      if (launch_blocked_draw(s, pair->blk_feats_dev, pair->nfeat, 2, pair->kpad, pair->cnt_u32, st->alpha,
+                              sm::stream_key(seed, sm::kStreamPass0 + t) ^ blocked::kKey, sw, pair->blk_work, pair->blk_tab))
+        return MSC_EHIP;
+      if (launch_sm_assign(s, route.kernel, route.block, t == launch_iters, t, pair->blk_feats_dev, (int)pair->nfeat,
+                           pair->blk_tab, pair->kpad, row0, nrows, row_id0, z_dev, st->sm_ell, st->sm_prop, seed, sw,
+                           st->sm_part, zero))
+        return MSC_EHIP;
+    }
+    if (proposed_dev && nrows)
+      MSC_HIP(hipMemcpyAsync(proposed_dev + (size_t)p * nrows, st->sm_ell, nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    // score_data of the two blocks and of their union (slot 2 = the sum of the additive tables of slots 0 and 1)
+    MSC_TRY(accumulate_impl(pair, view, cols, row0, nrows, st->sm_ell, MSC_ACC_RESET | kAccZeroed | MSC_ACC_NO_COMMIT));
+    if (launch_sm_merge_slots(s, pair->red_i64, (uint32_t)(pair->n_i64 / pair->kpad), pair->red_f64,
+                              (uint32_t)(pair->n_f64 / pair->kpad), pair->kpad))
+      return MSC_EHIP;
+    MSC_TRY(commit(pair));
+    if (launch_score_data(s, pair->desc_dev, (int)pair->nfeat, kSmSlots, pair->kpad, st->sm_sd))
+      return fail(MSC_EHIP, "k_score_data launch failed");
+    if (launch_sm_decide(s, st->sm_prop, st->sm_part, nparts, st->sm_sd, st->nfeat, pair->cnt_u32, st->alpha, seed, sw,
+                         log_dev ? log_dev + (size_t)p * 8 : nullptr, reinterpret_cast<unsigned long long *>(counters_dev)))
+      return MSC_EHIP;
+    if (launch_sm_relabel(s, nrows, z_dev, st->sm_ell, st->sm_prop, pair->cnt_u32, st->cnt_u32)) return MSC_EHIP;
+    if (trace_dev && nrows)
+      MSC_HIP(hipMemcpyAsync(trace_dev + (size_t)p * nrows, z_dev, nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  }
+  return accumulate_impl(st, view, cols, row0, nrows, z_dev, MSC_ACC_RESET);
+}
+
+extern "C" int msc_split_merge_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
+  MSC_REQUIRE(st, "null state");
+  MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  const SplitMergeRoute route = route_splitmerge(st, 0);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  MSC_TRY(sm_setup(st));
+  msc_state *pair = st->sm_pair;
+  MSC_TRY(blocked_setup(pair));
+  const bool w = feature == UINT32_MAX;
+  if (dev) *dev = pair->blk_tab + (w ? 0 : (size_t)pair->blk_feats_host[feature].slice0 * pair->kpad);
+  if (nslices) *nslices = w ? 1u : pair->blk_feats_host[feature].nslices;
+  if (ld) *ld = pair->kpad;
   return MSC_OK;
 }
 

@@ -216,6 +216,23 @@ int launch_blocked_assign(hipStream_t stream, BlockedKernel kernel, uint32_t blo
                           int32_t *z, uint64_t seed, uint64_t sweep);
 int launch_blocked_top_slot(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint32_t *out);
 
+// kernels_splitmerge.hip: the split-merge move (msc_split_merge; abi.cpp route_splitmerge chooses the assign kernel).
+// seed is the caller's: the launchers form the streams' keys (splitmerge_math.hpp).  `zero`: the pair state's additive
+// tables, emptied on the way for the accumulate pass that follows.
+int launch_sm_begin(hipStream_t stream, const int32_t *z, uint64_t nrows, uint64_t row_id0, const uint32_t *cnt, uint32_t K,
+                    uint64_t seed, uint64_t sweep, SmProp *prop, int32_t *ell, ZeroSpans zero);
+uint32_t sm_assign_blocks(uint64_t nrows, uint32_t block);   // workgroups (= partials) of an assign pass
+int launch_sm_assign(hipStream_t stream, BlockedKernel kernel, uint32_t block, bool final, uint32_t pass, const BlkFeat *fs_dev,
+                     int nfeat, const float *tab, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
+                     const int32_t *z, int32_t *ell, const SmProp *prop, uint64_t seed, uint64_t sweep, double *part,
+                     ZeroSpans zero);
+int launch_sm_merge_slots(hipStream_t stream, long long *i64, uint32_t rows_i, double *f64, uint32_t rows_f, uint32_t kpad);
+int launch_sm_decide(hipStream_t stream, SmProp *prop, const double *part, uint32_t nparts, const float *sd, uint32_t nfeat,
+                     const uint32_t *pair_cnt, float alpha, uint64_t seed, uint64_t sweep, double *log_row,
+                     unsigned long long *counters);
+int launch_sm_relabel(hipStream_t stream, uint64_t nrows, int32_t *z, const int32_t *ell, const SmProp *prop,
+                      const uint32_t *pair_cnt, uint32_t *cnt);
+
 // kernels_niw.hip
 int launch_niw_prepare(hipStream_t stream, const FeatDesc *feats_dev, uint32_t f, uint32_t dim, uint32_t K,
                        uint32_t kpad);

@@ -322,6 +322,18 @@ inline uint32_t blocked_slices(int family, uint32_t dim) {
   }
 }
 
+// One split-merge proposal as the kernels of kernels_splitmerge.hip hand it on (msc_split_merge): written by
+// k_sm_anchors, `accepted` by k_sm_decide.  A void proposal (an unassigned anchor, no empty slot for a split, fewer than
+// two rows) makes every later kernel of the proposal a no-op.
+struct SmProp {
+  int32_t gi, gj;            // the anchors' groups
+  uint32_t kind;             // sm::kSplit / kMerge / kVoid (splitmerge_math.hpp)
+  int32_t target;            // where the label-1 rows go when accepted: a split's lowest empty slot, a merge's gi
+  uint64_t i, j;             // the anchors, as offsets from the call's first row
+  uint32_t accepted;
+  uint32_t pad;
+};
+
 // one feature of the index matrix as k_pack_look_idx reads it
 struct LookIdxSrc {
   const void *col;
@@ -661,6 +673,14 @@ struct msc_state {
   msc::DevBuf<double> blk_work;
   uint32_t blk_rows = 0;
   bool blk_drawn = false;
+  // the split-merge move (abi.cpp msc_split_merge): an internal three-slot state of the same features -- pair slots 0
+  // and 1, slot 2 their union -- created at the first call and destroyed with this one; the pair labels of the call's
+  // rows, the assign kernel's per-workgroup partials, the proposal descriptor and the pair state's score_data
+  msc_state *sm_pair = nullptr;
+  msc::DevBuf<int32_t> sm_ell;
+  msc::DevBuf<double> sm_part;
+  msc::DevBuf<msc::SmProp> sm_prop;
+  msc::DevBuf<float> sm_sd;
   uint32_t chain_members = 0;                   // live msc_chains handles that hold this state: it cannot be destroyed meanwhile
 };
 

@@ -577,6 +577,63 @@ class State(object):
                                                row0 if row_id0 is None else row_id0, C.c_void_p(z.data_ptr()),
                                                int(nsweeps), int(seed), int(sweep), tp, sp))
 
+    # split-merge Metropolis-Hastings proposals --------------------------------
+    def split_merge(self, view, z, seed, sweep, nproposals=1, launch_iters=2, log=None, trace=None, proposed=None,
+                    counters=None, row0=0, nrows=None, row_id0=None, cols=None):
+        """nproposals split-merge proposals on the device, proposal p with the sweep counter sweep + p
+        (msc_split_merge).  All outputs are optional device tensors: log float64 [nproposals, 8] = {i, j, kind (0 split,
+        1 merge, 2 void), n_0, n_1, log q, log A, accepted}; trace int32 [nproposals, nrows], z after every proposal;
+        proposed int32 [nproposals, nrows], the proposed pair labels (-1 outside the two groups); counters 64-bit integer
+        [5] = {splits proposed, accepted, merges proposed, accepted, void}, added to."""
+        self._drop_subsets()
+        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
+        n = view.nrows - row0 if nrows is None else nrows
+        if z is None:
+            zp = None
+        else:
+            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
+                raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+            if z.device != self.ctx.torch_device:
+                raise ValueError("z must live on the context's device")
+            zp = C.c_void_p(z.data_ptr())
+        if not 0 <= int(nproposals) < (1 << 32) or not 0 <= int(launch_iters) < (1 << 32):
+            raise ValueError("nproposals and launch_iters must be in [0, 2^32)")
+
+        def ptr(t, dtype, numel, what):
+            if t is None:
+                return None
+            if t.dtype != dtype or not t.is_contiguous() or t.numel() < numel or t.device != self.ctx.torch_device:
+                raise ValueError("%s must be a contiguous %s device tensor of at least %d entries" % (what, dtype, numel))
+            return C.c_void_p(t.data_ptr())
+
+        cp = None
+        if counters is not None:
+            if counters.element_size() != 8 or counters.is_floating_point() or not counters.is_contiguous() \
+                    or counters.numel() < 5 or counters.device != self.ctx.torch_device:
+                raise ValueError("counters must be a contiguous 64-bit integer device tensor of 5 entries")
+            cp = C.c_void_p(counters.data_ptr())
+        L.check(self.ctx.lib.msc_split_merge(self._h, view._h, self._cols(cols), row0, n,
+                                             row0 if row_id0 is None else row_id0, zp, int(nproposals), int(launch_iters),
+                                             int(seed), int(sweep), ptr(log, torch.float64, 8 * int(nproposals), "log"),
+                                             ptr(trace, torch.int32, int(nproposals) * n, "trace"),
+                                             ptr(proposed, torch.int32, int(nproposals) * n, "proposed"), cp))
+
+    def split_merge_tables(self):
+        """{"logw": float32[2], feature index: float32[nslices, 2]}: views onto theta* of the last proposal made -- the
+        two pair slots' log weights and slices (msc_split_merge_tables; the slices are blocked_tables()'s)"""
+        out = {}
+        for f in [None] + list(range(len(self.features))):
+            p, ns, ld = C.c_void_p(), C.c_uint32(), C.c_uint32()
+            L.check(self.ctx.lib.msc_split_merge_tables(self._h, 0xffffffff if f is None else f, C.byref(p), C.byref(ns),
+                                                        C.byref(ld)))
+            if ns.value == 0:
+                t = torch.empty((0, 2), dtype=torch.float32, device=self.ctx.torch_device)
+            else:
+                t = _alias_tensor(p.value, ns.value * ld.value, torch.float32, self.ctx.torch_device,
+                                  self).view(ns.value, ld.value)[:, :2]
+            out["logw" if f is None else f] = t[0] if f is None else t
+        return out
+
     def sweep_step_stats(self):
         """(steps run launch by launch, steps run as one graph launch)"""
         e, g = C.c_uint64(), C.c_uint64()

@@ -346,6 +346,37 @@ public:
     stale_ = true;
   }
 
+  // nproposals SPLIT-MERGE Metropolis-Hastings proposals over all entities on the device (msc_split_merge): each picks
+  // two entities, proposes to split their group in two (into the lowest free slot) or to merge their two groups, from a
+  // launch state reached by launch_iters restricted blocked Gibbs passes, and accepts or rejects on the device.  Proposal
+  // p uses the sweep counter sweep + p.  Returns what was proposed and accepted; as gibbs_sweep, the host partition
+  // follows the assignment vector lazily (sync()).  Non-conjugate (bbnc), niw and dm components throw.
+  struct split_merge_counts {
+    uint64_t splits = 0, splits_accepted = 0, merges = 0, merges_accepted = 0, voids = 0;
+  };
+  split_merge_counts split_merge(uint64_t seed, uint64_t sweep, common::rng_t &rng, uint32_t nproposals = 1,
+                                 uint32_t launch_iters = 2) {
+    (void)rng;                                          // (every draw is the device's)
+    if (any_nonconj_) throw std::runtime_error("split_merge takes conjugate components only");
+    for (const auto &s : specs_)
+      if (s.family == MSC_NIW || s.family == MSC_DM) throw std::runtime_error("split_merge does not take niw or dm components");
+    push_params(true);
+    uint64_t c[5] = {0, 0, 0, 0, 0};
+    uint64_t *c_dev = nullptr;
+    check(msc_device_alloc(ctx_, sizeof c, reinterpret_cast<void **>(&c_dev)));
+    int rc = msc_device_upload(ctx_, c_dev, c, sizeof c);
+    if (rc == MSC_OK)
+      rc = msc_split_merge(st_, view_, nullptr, 0, n_, 0, z_dev_, nproposals, launch_iters, seed, sweep, nullptr, nullptr,
+                           nullptr, c_dev);
+    if (rc == MSC_OK) rc = msc_device_download(ctx_, c, c_dev, sizeof c);
+    msc_device_free(ctx_, c_dev);
+    check(rc);
+    stale_ = true;
+    split_merge_counts out;
+    out.splits = c[0], out.splits_accepted = c[1], out.merges = c[2], out.merges_accepted = c[3], out.voids = c[4];
+    return out;
+  }
+
   // Posterior predictive draws for new, partly observed rows (downstream's sample_post_pred): each row of `rows` (the
   // state's column layout, with its mask) gets a group drawn from the CRP term plus the scores of its observed entries
   // against the tables as they stand, then its masked entries are drawn from that group's posterior predictive -- ONE

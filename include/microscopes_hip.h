@@ -479,6 +479,58 @@ int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const uint32_t *c
                       uint64_t row_id0, int32_t *z_dev, uint32_t nsweeps, uint64_t seed, uint64_t sweep,
                       int32_t *trace_dev, uint32_t *top_slot_dev);
 
+/*
+ * SPLIT-MERGE Metropolis-Hastings proposals (Jain & Neal 2004 / 2007, with an uncollapsed launch): moves that split one
+ * group in two or merge two groups in one step, which no chain of single-row moves makes.  One call runs nproposals
+ * proposals back to back without a host synchronisation; proposal p uses the sweep counter sweep + p.
+ *
+ *   1. anchors: an ordered pair of distinct rows (i, j), uniform over the call's nrows rows.  An unassigned anchor (z
+ *      outside [0, K)) makes the proposal VOID; so does nrows < 2.
+ *   2. S = the rows of the call with z in {z_i, z_j}; z_i = z_j: a SPLIT (void when no slot is empty), else a MERGE.  A
+ *      void proposal changes nothing and is counted.
+ *   3. launch -- a function of (S, i, j, data, hyper-parameters, alpha, streams) only, never of how S is divided now:
+ *      pair labels l_i = 0, l_j = 1, a coin for every other row of S; then launch_iters times: the two pair slots'
+ *      suff-stats from l, their parameters from the conjugate posteriors (msc_blocked_draw's draws) and the weights as
+ *      the K = 2 stick V_0 ~ Beta(1 + n_0, alpha + n_1), and every free row (not an anchor) redraws l_r with
+ *      P(l_r = s) ~ pi_s prod_f lik_f(x_rf | theta_s), masked entries adding nothing.  One more accumulate and draw give
+ *      theta*.
+ *   4. final labels l': a split draws them under theta* for the free rows, a merge takes l'_r = [z_r = z_j]; either way
+ *      log q = sum over free rows of log P(l'_r | theta*), added in double in a fixed order (lanes, waves, workgroups).
+ *   5. with n_0, n_1 the sizes under l' and sd(.) the sum over features of score_data of a block:
+ *        log A_split = log alpha + lgamma(n_0) + lgamma(n_1) - lgamma(n_0 + n_1) + sd(0) + sd(1) - sd(S) - log q
+ *        log A_merge = -(the same without log q) + log q
+ *      accepted when log u < log A; the decision is made on the device in double.
+ *   6. apply: a split moves the rows with l' = 1 to the lowest-numbered empty slot, a merge the rows of z_j's group to
+ *      z_i's.  Rows outside S are never written.
+ *
+ * Random numbers: Philox4x32-10 under keys made from seed ^ 0xA0761D6478BD642F (a key no sweep, grid draw, slice step,
+ * predictive or blocked draw uses): stream s has key (seed ^ that) + s 0x9E3779B97F4A7C15; s = 0 the proposal's darts
+ * (counters 0 .. 4: anchor i from two darts, anchor j from two, the acceptance), s = 1 the coins (counter: the row's
+ * global id row_id0 + offset), s = 2 + t pass t of the launch (parameters: msc_blocked_draw's streams under this key;
+ * labels: the row's global id).  common_amd/csrc/splitmerge_math.hpp states every stream and the arithmetic.
+ *
+ * Outputs, all nullable, all device memory:
+ *   log_dev       double[nproposals][8] = {i, j, kind (0 split, 1 merge, 2 void), n_0, n_1, log q, log A, accepted};
+ *                 i and j are offsets from the call's first row
+ *   trace_dev     int32[nproposals][nrows], z after each proposal
+ *   proposed_dev  int32[nproposals][nrows], l' of each proposal, -1 outside S
+ *   counters_dev  uint64[5] = {splits proposed, splits accepted, merges proposed, merges accepted, void}, added to
+ *
+ * The group sizes must be current at the call (they say which slots are empty) and follow the proposals on the device.
+ * On return the reference's fields, the additive sums and the group counts are those of msc_accumulate(MSC_ACC_RESET) of
+ * the call's rows under the final z (one accumulate at the end of the call); a blocked draw made before is stale.
+ * Asynchronous.  MSC_EINVAL between msc_sweep_step_begin and msc_state_commit_reduce; MSC_EUNSUPPORTED for states with
+ * niw, dm or bbnc features.
+ *
+ * msc_split_merge_tables: theta* of the last proposal made, as msc_blocked_tables gives the blocked sweep's table: one
+ * feature's slices (*dev = float[*nslices][*ld], pair slots 0 and 1 the first two of a row) or, feature == UINT32_MAX,
+ * the two log weights.
+ */
+int msc_split_merge(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                    uint64_t row_id0, int32_t *z_dev, uint32_t nproposals, uint32_t launch_iters, uint64_t seed,
+                    uint64_t sweep, double *log_dev, int32_t *trace_dev, int32_t *proposed_dev, uint64_t *counters_dev);
+int msc_split_merge_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld);
+
 /* ---- multi-GPU hook ---------------------------------------------------- */
 /*
  * The additive form of every table, ready for a sum all-reduce across row
