@@ -181,6 +181,9 @@ _SIGS = {
     "msc_zmatrix_nsamples": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "msc_zmatrix_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "msc_zmatrix_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "msc_zmatrix_partition_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "msc_zmatrix_partition_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
     "msc_zmatrix_reset": (C.c_int, [C.c_void_p]),
     "msc_zmatrix_destroy": (C.c_int, [C.c_void_p]),
     "msc_linkage_single": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

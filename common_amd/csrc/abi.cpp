@@ -4081,6 +4081,95 @@ extern "C" int msc_zmatrix_result(msc_zmatrix *zm, const uint32_t *host_order, f
   return zmatrix_write(zm, host_order, out_dev, ld_out, true);
 }
 
+// candidate partitions against the counts (kernels_partition.hip): the checks both entries share, the flush, and the
+// label buffer of one chunk of candidates
+static int zm_partition_begin(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld, const char *who) {
+  MSC_REQUIRE(zm && cand_dev, "null argument");
+  MSC_REQUIRE(zm->nsamples > 0, "%s: no sample has been added", who);
+  MSC_REQUIRE(ncand > 0, "%s: ncand is 0", who);
+  MSC_REQUIRE(ld >= zm->n, "%s: ld = %llu is below n = %llu", who, (unsigned long long)ld, (unsigned long long)zm->n);
+  MSC_TRY(device_error_check(zm->ctx));
+  MSC_HIP(hipSetDevice(zm->ctx->device));
+  MSC_TRY(zmatrix_flush(zm));
+  return MSC_OK;
+}
+
+template <typename T>
+static int zm_partition_reserve(msc_zmatrix *zm, DevBuf<T> &buf, size_t n, const char *who, const char *what) {
+  const hipError_t e = reserve_synced(zm->ctx->stream, buf, n);
+  if (e == hipSuccess) return MSC_OK;
+  (void)hipGetLastError();
+  return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "%s: the %s of %zu bytes: %s", who, what, n * sizeof(T),
+              hipGetErrorString(e));
+}
+
+// w / size (either may be null) of candidates [0, k) at cand_dev into [k][m] arrays
+static int zm_partition_chunk_sums(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t k, uint64_t ld, uint64_t *w_dev,
+                                   uint32_t *size_dev) {
+  const hipStream_t s = zm->ctx->stream;
+  if (launch_zm_partition_gather(s, cand_dev, ld, k, zm->rows_dev, zm->m, zm->nt, zm->part_lab))
+    return fail(MSC_EHIP, "k_zm_partition_gather launch failed");
+  if (launch_zm_partition_sums(s, zm->counts, zm->nt, zm->m, zm->nsamples < kZmPartPackedMax, zm->part_lab, k, w_dev,
+                               size_dev))
+    return fail(MSC_EHIP, "k_zm_partition_sums launch failed");
+  return MSC_OK;
+}
+
+extern "C" int msc_zmatrix_partition_sums(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
+                                          uint64_t *w_dev, uint32_t *size_dev) {
+  const char *who = "msc_zmatrix_partition_sums";
+  MSC_TRY(zm_partition_begin(zm, cand_dev, ncand, ld, who));
+  if (!w_dev && !size_dev) return MSC_OK;
+  const uint32_t chunk = zm_partition_chunk(zm->nt);
+  MSC_TRY(zm_partition_reserve(zm, zm->part_lab, (size_t)chunk * zm->nt * kZmTile, who, "label buffer"));
+  for (uint32_t c0 = 0; c0 < ncand; c0 += chunk) {
+    const size_t o = (size_t)c0 * zm->m;
+    MSC_TRY(zm_partition_chunk_sums(zm, cand_dev + (uint64_t)c0 * ld, std::min(chunk, ncand - c0), ld,
+                                    w_dev ? w_dev + o : nullptr, size_dev ? size_dev + o : nullptr));
+  }
+  return MSC_OK;
+}
+
+extern "C" int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
+                                          int64_t *binder_num_dev, double *vi_lb_dev, uint64_t *valid_dev) {
+  const char *who = "msc_zmatrix_partition_loss";
+  MSC_REQUIRE(zm && cand_dev, "null argument");
+  {
+    // binder_num <= V m (m - 1) / 2 must fit an int64
+    const unsigned __int128 pairs = (unsigned __int128)zm->m * (zm->m - 1) / 2;
+    if (zm->nsamples > 0 && pairs * zm->nsamples >= ((unsigned __int128)1 << 63))
+      return fail(MSC_EUNSUPPORTED, "%s: m (m - 1) / 2 x nsamples = %u (%u - 1) / 2 x %llu does not fit 63 bits", who, zm->m,
+                  zm->m, (unsigned long long)zm->nsamples);
+  }
+  MSC_TRY(zm_partition_begin(zm, cand_dev, ncand, ld, who));
+  if (!binder_num_dev && !vi_lb_dev && !valid_dev) return MSC_OK;
+  const uint32_t chunk = zm_partition_chunk(zm->nt);
+  const size_t mpad = (size_t)zm->nt * kZmTile;
+  MSC_TRY(zm_partition_reserve(zm, zm->part_lab, chunk * mpad, who, "label buffer"));
+  MSC_TRY(zm_partition_reserve(zm, zm->part_w, (size_t)chunk * zm->m, who, "workspace of row sums"));
+  MSC_TRY(zm_partition_reserve(zm, zm->part_size, (size_t)chunk * zm->m, who, "workspace of cluster sizes"));
+  MSC_TRY(zm_partition_reserve(zm, zm->part_T, 1, who, "pair total"));
+  const hipStream_t s = zm->ctx->stream;
+  // T (and V): the loss of all rows in one cluster
+  MSC_HIP(hipMemsetAsync(zm->part_lab, 0, mpad * 4, s));
+  if (launch_zm_partition_sums(s, zm->counts, zm->nt, zm->m, zm->nsamples < kZmPartPackedMax, zm->part_lab, 1,
+                               zm->part_w, zm->part_size))
+    return fail(MSC_EHIP, "k_zm_partition_sums launch failed");
+  if (launch_zm_partition_loss(s, zm->counts, zm->part_w, zm->part_size, zm->m, 1, true, zm->part_T, nullptr, nullptr,
+                               valid_dev))
+    return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
+  if (!binder_num_dev && !vi_lb_dev) return MSC_OK;
+  for (uint32_t c0 = 0; c0 < ncand; c0 += chunk) {
+    const uint32_t k = std::min(chunk, ncand - c0);
+    MSC_TRY(zm_partition_chunk_sums(zm, cand_dev + (uint64_t)c0 * ld, k, ld, zm->part_w, zm->part_size));
+    if (launch_zm_partition_loss(s, zm->counts, zm->part_w, zm->part_size, zm->m, k, false, zm->part_T,
+                                 binder_num_dev ? binder_num_dev + c0 : nullptr, vi_lb_dev ? vi_lb_dev + c0 : nullptr,
+                                 nullptr))
+      return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
+  }
+  return MSC_OK;
+}
+
 extern "C" int msc_zmatrix_reset(msc_zmatrix *zm) {
   MSC_REQUIRE(zm, "null argument");
   MSC_HIP(hipSetDevice(zm->ctx->device));

@@ -331,6 +331,23 @@ int launch_zm_count(hipStream_t stream, const uint32_t *batch, uint32_t nt, bool
 int launch_zm_finish(hipStream_t stream, const uint32_t *counts, uint32_t nt, uint32_t m, const uint32_t *order,
                      bool norm, float S, void *out, uint64_t ld);
 
+// kernels_partition.hip (msc_zmatrix_partition_*): candidates are gathered to lab[candidate][64 nt] (the selected rows'
+// labels, 0 in the padding) a chunk of zm_partition_chunk(nt) at a time (a multiple of kZmPartBatch; the label buffer
+// stays within 32 MiB up to m = 131072).  packed: every count is below kZmPartPackedMax (the kernel file's head says why
+// that matters); the sums kernel takes kZmPartBatch candidates a workgroup then, half as many otherwise.
+// launch_zm_partition_loss: tmode = the one candidate is the all-in-one partition and *T_io receives T (and *valid V);
+// otherwise *T_io is read.  -2: a shape the launcher does not take
+constexpr int kZmPartBatch = 64;
+constexpr uint64_t kZmPartPackedMax = 1ull << 20;
+uint32_t zm_partition_chunk(uint32_t nt);
+int launch_zm_partition_gather(hipStream_t stream, const int32_t *cand, uint64_t ld, uint32_t ncand, const uint32_t *rows,
+                               uint32_t m, uint32_t nt, int32_t *lab);
+int launch_zm_partition_sums(hipStream_t stream, const uint32_t *counts, uint32_t nt, uint32_t m, bool packed,
+                             const int32_t *lab, uint32_t ncand, uint64_t *w_out, uint32_t *size_out);
+int launch_zm_partition_loss(hipStream_t stream, const uint32_t *counts, const uint64_t *w, const uint32_t *size,
+                             uint32_t m, uint32_t ncand, bool tmode, uint64_t *T_io, int64_t *binder, double *vi,
+                             uint64_t *valid);
+
 // kernels_linkage.hip (msc_linkage_single): Prim's chain over the dense n x n matrix z (row stride ld), one workgroup
 // of linkage::shape_for(n) (linkage_host.hpp); edges[3 i ..] = (x, y, distance) of step i.  -2: n outside [2, 65536]
 int launch_linkage_prim(hipStream_t stream, const float *z, uint64_t ld, uint32_t n, double *edges);

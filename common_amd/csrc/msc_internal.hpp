@@ -697,4 +697,10 @@ struct msc_zmatrix {
   msc::DevBuf<uint32_t> counts;            // [nt (nt + 1) / 2][64][64]
   uint32_t staged = 0;                     // samples in the batch
   uint64_t nsamples = 0;
+  // msc_zmatrix_partition_* (kernels_partition.hip), allocated at the first call: a chunk of gathered candidate labels
+  // [chunk][64 nt], the chunk's sums for the loss ([chunk][m] w, then [chunk][m] size), and T
+  msc::DevBuf<int32_t> part_lab;
+  msc::DevBuf<uint64_t> part_w;
+  msc::DevBuf<uint32_t> part_size;
+  msc::DevBuf<uint64_t> part_T;
 };

@@ -6,8 +6,13 @@ with ``ctx=``) build the z-matrix on the device (``ZMatrix``, ``msc_zmatrix_*``)
 the numpy path.  The block ordering is the leaf order of scipy's single linkage over the condensed upper triangle: scipy
 itself for numpy input, ``msc_linkage_single`` for a float32 device tensor (the same dendrogram, bit for bit).
 ``zmatrix_linkage`` returns that dendrogram and ``zmatrix_clusters`` cuts a consensus partition out of it; the reference
-exposes neither.
+exposes neither.  ``partition_sums``, ``partition_loss`` and ``point_estimate`` choose ONE clustering by posterior expected
+loss (Binder's loss, which is Dahl's least-squares clustering, or the variation-of-information lower bound of Wade and
+Ghahramani) among candidate partitions, from exact integer sums over the co-clustering counts: numpy on the host,
+``msc_zmatrix_partition_*`` on the device, the same integers on both.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -57,8 +62,8 @@ def _dense_labels(a):
     return out, K
 
 
-def _zmatrix_host(a):
-    """float32 count / S: the counts as sums of one-hot products (exact in float64), a block of samples at a time"""
+def _counts_host(a):
+    """float64 [n, n] co-clustering counts: sums of one-hot products (exact in float64), a block of samples at a time"""
     S, n = a.shape
     dense, K = _dense_labels(a)
     counts = np.zeros((n, n), dtype=np.float64)
@@ -68,36 +73,52 @@ def _zmatrix_host(a):
         blk = dense[s0:s0 + step]
         H = eye[blk].transpose(1, 0, 2).reshape(n, -1)   # [n, samples x K]: row i's label of each sample, one-hot
         counts += H @ H.T
-    return counts.astype(np.float32) / np.float32(S)
+    return counts
 
 
-def _zmatrix_device(a, ctx):
-    """a: int32 device tensor [S, n]"""
+def _zmatrix_host(a):
+    """float32 count / S"""
+    return _counts_host(a).astype(np.float32) / np.float32(a.shape[0])
+
+
+def _open_zmatrix(a, ctx):
+    """a: int32 device tensor [S, n] -> (an accumulator holding the samples, the samples as it took them)"""
     S, n = int(a.shape[0]), int(a.shape[1])
     lo, hi = int(a.min()), int(a.max())
     if lo < 0 or hi >= ZMATRIX_MAX_LABELS:
         a = torch.stack([torch.unique(a[s], return_inverse=True)[1] for s in range(S)]).to(torch.int32)
         hi = int(a.max())
+    a = a.contiguous()
     zm = ZMatrix(ctx, n, hi + 1)
     try:
-        zm.add(a.contiguous())
+        zm.add(a)
+    except Exception:
+        zm.close()
+        raise
+    return zm, a
+
+
+def _zmatrix_device(a, ctx):
+    """a: int32 device tensor [S, n]"""
+    zm, _ = _open_zmatrix(a, ctx)
+    try:
         return zm.result()
     finally:
         zm.close()
 
 
-def zmatrix(assignments, ctx=None):
-    """Z[i, j] = the fraction of the assignment vectors in which rows i and j share a label (float32 [n, n]).
+def _host_samples(assignments):
+    a = np.asarray([np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in assignments])
+    return a.reshape(len(assignments), -1)
 
-    ``assignments``: a list (or [S, n] array) of assignment vectors of equal length.  Numpy input returns a numpy array;
-    a device tensor, a list of device tensors, or any input with ``ctx`` (a ``Context``) runs on the device and returns a
-    float32 device tensor with the same bits."""
-    _check_assignments(assignments)
-    on_device = ctx is not None or _is_device(assignments) or \
+
+def _on_device(assignments, ctx):
+    return ctx is not None or _is_device(assignments) or \
         (not isinstance(assignments, (np.ndarray, torch.Tensor)) and any(_is_device(a) for a in assignments))
-    if not on_device:
-        a = np.asarray([np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in assignments])
-        return _zmatrix_host(a.reshape(len(assignments), -1))
+
+
+def _device_samples(assignments, ctx):
+    """(int32 device tensor [S, n], context) of assignment vectors given as zmatrix takes them"""
     if ctx is None:
         dev = assignments.device if isinstance(assignments, torch.Tensor) else \
             next(a.device for a in assignments if _is_device(a))
@@ -119,7 +140,19 @@ def zmatrix(assignments, ctx=None):
         if int(a64.min()) < 0 or int(a64.max()) >= ZMATRIX_MAX_LABELS:
             a64 = torch.stack([torch.unique(a64[s], return_inverse=True)[1] for s in range(a64.shape[0])])
         a = a64.to(torch.int32)
-    return _zmatrix_device(a.reshape(a.shape[0], -1), ctx)
+    return a.reshape(a.shape[0], -1), ctx
+
+
+def zmatrix(assignments, ctx=None):
+    """Z[i, j] = the fraction of the assignment vectors in which rows i and j share a label (float32 [n, n]).
+
+    ``assignments``: a list (or [S, n] array) of assignment vectors of equal length.  Numpy input returns a numpy array;
+    a device tensor, a list of device tensors, or any input with ``ctx`` (a ``Context``) runs on the device and returns a
+    float32 device tensor with the same bits."""
+    _check_assignments(assignments)
+    if not _on_device(assignments, ctx):
+        return _zmatrix_host(_host_samples(assignments))
+    return _zmatrix_device(*_device_samples(assignments, ctx))
 
 
 def _is_square(z):
@@ -233,3 +266,198 @@ def zmatrix_clusters(zmat, threshold, ctx=None):
     rank = np.empty(first.size, dtype=np.int64)
     rank[np.argsort(first, kind="stable")] = np.arange(first.size)
     return rank[inv.reshape(-1)]
+
+
+# ---- one clustering out of the samples: posterior expected loss of candidate partitions ----------------------------
+PointEstimate = collections.namedtuple("PointEstimate", ["labels", "index", "losses", "confidence"])
+_LOSSES = ("binder", "vi")
+
+
+def _renumber(labels):
+    """the same partition, numbered from 0 in the order of each label's first row (as zmatrix_clusters numbers)"""
+    _, first, inv = np.unique(np.asarray(labels), return_index=True, return_inverse=True)
+    rank = np.empty(first.size, dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(first.size)
+    return rank[inv.reshape(-1)]
+
+
+def _host_candidates(candidates, n):
+    c = np.asarray(candidates.cpu() if isinstance(candidates, torch.Tensor) else candidates)
+    if c.ndim == 1:
+        c = c.reshape(1, -1)
+    if c.ndim != 2 or c.shape[0] == 0:
+        raise ValueError("empty candidates list")
+    if c.shape[1] != n:
+        raise ValueError("candidate vectors should be the size of the assignment vectors")
+    if not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("candidate vectors must hold integer labels")
+    return c
+
+
+def _sums_of_counts(C, c):
+    """C: int64 [m, m] counts; c: [ncand, m] labels -> (w int64 [ncand, m], size int32 [ncand, m])"""
+    nc, m = c.shape
+    w = np.empty((nc, m), dtype=np.int64)
+    size = np.empty((nc, m), dtype=np.int32)
+    for k in range(nc):
+        _, inv = np.unique(c[k], return_inverse=True)
+        inv = inv.reshape(-1)
+        by_label = np.argsort(inv, kind="stable")
+        sizes = np.bincount(inv)
+        starts = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+        per_label = np.add.reduceat(C[:, by_label], starts, axis=1)     # [m, labels]: row a's counts over each cluster
+        w[k] = per_label[np.arange(m), inv]
+        size[k] = sizes[inv]
+    return w, size
+
+
+def _loss_of_sums(C, w, size):
+    """(binder_num int64 [ncand], vi_lb float64 [ncand], V) by the definitions of msc_zmatrix_partition_loss"""
+    m = C.shape[0]
+    V = int(C[0, 0])
+    T = (int(C.sum()) - int(np.trace(C))) // 2
+    P = (size.astype(np.int64) - 1).sum(axis=1) // 2
+    Q2 = (w - V).sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vi = (np.log2(size.astype(np.float64)) - 2. * np.log2(w.astype(np.float64))).sum(axis=1) / m + 2. * np.log2(float(V))
+    return T + V * P - Q2, vi, V
+
+
+def _host_counts_of(assignments):
+    _check_assignments(assignments)
+    a = _host_samples(assignments)
+    return a, np.rint(_counts_host(a)).astype(np.int64)
+
+
+def partition_sums(assignments, candidates):
+    """The integer sums behind both losses, on the host (the yardstick of ``ZMatrix.partition_sums``).  With C the
+    co-clustering counts of the assignment vectors, for every candidate c and row a: ``size[c, a]`` = the rows that c puts
+    with a (a itself included), ``w[c, a]`` = the sum of C[a, b] over those rows.  Only equality of labels is used.
+    Returns ``(w int64 [ncand, n], size int32 [ncand, n])``."""
+    a, C = _host_counts_of(assignments)
+    return _sums_of_counts(C, _host_candidates(candidates, a.shape[1]))
+
+
+def _device_candidates(candidates, ctx, n):
+    """an int32 tensor [ncand, n] on the context's device; labels that do not fit an int32 are renumbered row by row"""
+    if isinstance(candidates, torch.Tensor):
+        c = candidates.to(ctx.torch_device)
+        if c.dtype.is_floating_point or c.dtype == torch.bool:
+            raise ValueError("candidate vectors must hold integer labels")
+        c = c.reshape(1, -1) if c.dim() == 1 else c
+        if c.dim() != 2 or c.shape[0] == 0:
+            raise ValueError("empty candidates list")
+        if c.shape[1] != n:
+            raise ValueError("candidate vectors should be the size of the assignment vectors")
+        if c.dtype != torch.int32:
+            c64 = c.to(torch.int64)
+            if int(c64.min()) < -2 ** 31 or int(c64.max()) >= 2 ** 31:
+                c64 = torch.stack([torch.unique(c64[k], return_inverse=True)[1] for k in range(c64.shape[0])])
+            c = c64.to(torch.int32)
+        return c.contiguous()
+    if not isinstance(candidates, np.ndarray):
+        candidates = [np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in candidates]
+    c = _host_candidates(candidates, n)
+    if c.size and (c.min() < -2 ** 31 or c.max() >= 2 ** 31):
+        c = _dense_labels(c)[0]
+    return torch.from_numpy(np.ascontiguousarray(c, dtype=np.int32)).to(ctx.torch_device)
+
+
+class _Scorer(object):
+    """candidates against one set of samples, on the host (C: int64 counts) or on the device (zm: a ZMatrix)"""
+
+    def __init__(self, assignments, ctx):
+        self.zm = self.C = self.samples = None
+        self.owned = False
+        if isinstance(assignments, ZMatrix):
+            if ctx is not None and ctx is not assignments.ctx:
+                raise ValueError("ctx is not the accumulator's context")
+            self.zm, self.n = assignments, assignments.n
+            return
+        _check_assignments(assignments)
+        if _on_device(assignments, ctx):
+            a, ctx = _device_samples(assignments, ctx)
+            self.zm, self.samples = _open_zmatrix(a, ctx)
+            self.owned, self.n = True, self.zm.n
+        else:
+            self.samples, self.C = _host_counts_of(assignments)
+            self.n = self.samples.shape[1]
+
+    def candidates(self, candidates):
+        if candidates is None:
+            if self.samples is None:
+                raise ValueError("an accumulator keeps no samples: candidates must be given")
+            return self.samples
+        if self.zm is not None:
+            return _device_candidates(candidates, self.zm.ctx, self.n)
+        return _host_candidates(candidates, self.n)
+
+    def loss(self, c):
+        if self.zm is not None:
+            return self.zm.partition_loss(c)
+        return _loss_of_sums(self.C, *_sums_of_counts(self.C, c))
+
+    def sums(self, c):
+        """(w, size) as numpy arrays"""
+        if self.zm is not None:
+            w, size = self.zm.partition_sums(c)
+            return w.cpu().numpy(), size.cpu().numpy()
+        return _sums_of_counts(self.C, c)
+
+    def selected(self, labels):
+        """a candidate's labels over the rows the sums run over"""
+        labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+        if self.zm is not None and self.zm._rows is not None:
+            return labels[self.zm._rows.astype(np.int64)]
+        return labels
+
+    def close(self):
+        if self.owned:
+            self.zm.close()
+
+
+def partition_loss(assignments, candidates, ctx=None):
+    """Posterior expected losses of candidate partitions: ``(binder_num int64 [ncand], vi_lb float64 [ncand], valid)``.
+
+    ``binder_num[c] = valid * sum_{a<b} |[c puts a with b] - Z[a, b]|``, an exact integer: ``binder_num / valid`` is the
+    expected number of mis-paired pairs under Binder's loss.  Dahl's least-squares criterion ``sum_{a<b} ([..] - Z)^2``
+    differs from it by a term that does not depend on the candidate, so both have the same argmin.  ``vi_lb[c] =
+    (1 / m) sum_a (log2 size_c[a] - 2 log2 w_c[a]) + 2 log2 valid`` is Wade and Ghahramani's lower bound on the expected
+    variation of information less its candidate-independent term ``(1 / m) sum_a E[log2 size_sample(a)]``, which the
+    counts do not determine; it is 0 for all singletons.  ``valid`` is the number of samples counted.
+
+    ``assignments`` as for ``zmatrix``, or an open ``ZMatrix`` (the sums then run over its selected rows, the candidates
+    are vectors of its n labels).  Numpy input without ``ctx`` runs on the host and returns numpy arrays; device tensors,
+    ``ctx=`` or a ``ZMatrix`` run on the device (``msc_zmatrix_partition_loss``) and return device tensors holding the same
+    integers."""
+    sc = _Scorer(assignments, ctx)
+    try:
+        return sc.loss(sc.candidates(candidates))
+    finally:
+        sc.close()
+
+
+def point_estimate(assignments, loss="binder", candidates=None, ctx=None):
+    """ONE clustering out of posterior samples: the candidate of the lowest posterior expected loss.
+
+    ``loss``: ``"binder"`` (Binder's loss: Dahl's least-squares clustering) or ``"vi"`` (the variation-of-information lower
+    bound); see ``partition_loss``.  ``candidates``: the partitions to choose among, ``None`` for the samples themselves
+    (an open ``ZMatrix`` keeps none, so it needs them).  Runs where ``partition_loss`` would.  Returns a named tuple of
+    numpy values: ``labels`` (the winner over the rows scored, numbered from 0 in the order of first row), ``index`` (the
+    winner; the lowest index among equal losses), ``losses`` (``binder_num`` int64 or ``vi_lb`` float64 of every
+    candidate) and ``confidence`` (float64: ``w[a] / (valid * size[a])``, the mean posterior probability that row a is
+    with a row of its own cluster, itself included; in (0, 1])."""
+    if loss not in _LOSSES:
+        raise ValueError("loss must be one of %s" % (_LOSSES,))
+    sc = _Scorer(assignments, ctx)
+    try:
+        c = sc.candidates(candidates)
+        binder, vi, valid = sc.loss(c)
+        losses = binder if loss == "binder" else vi
+        losses = losses.cpu().numpy() if isinstance(losses, torch.Tensor) else np.asarray(losses)
+        index = int(np.argmin(losses))
+        w, size = sc.sums(c[index:index + 1])
+        confidence = w[0].astype(np.float64) / (float(valid) * size[0].astype(np.float64))
+        return PointEstimate(_renumber(sc.selected(c[index])), index, losses, confidence)
+    finally:
+        sc.close()

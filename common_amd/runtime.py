@@ -984,9 +984,8 @@ class ZMatrix(object):
         if not getattr(self, "_h", None):
             raise ValueError("ZMatrix is closed")
 
-    def add(self, z):
-        """stage assignment vectors: an int32 device tensor [n] or [S, n] whose rows are contiguous (row stride >= n).
-        Asynchronous; z may be overwritten by the next work on the stream (msc_zmatrix_add)."""
+    def _vectors(self, z):
+        """(tensor, S, ld) of assignment vectors given as add takes them"""
         self._check_open()
         if not isinstance(z, torch.Tensor) or z.dtype != torch.int32 or z.device != self.ctx.torch_device:
             raise ValueError("z must be an int32 tensor on %s" % self.ctx.torch_device)
@@ -1000,9 +999,45 @@ class ZMatrix(object):
                 raise ValueError("z must be [S, n = %d] with contiguous rows" % self.n)
         else:
             raise ValueError("z must be [n] or [S, n]")
+        return z2, S, ld
+
+    def add(self, z):
+        """stage assignment vectors: an int32 device tensor [n] or [S, n] whose rows are contiguous (row stride >= n).
+        Asynchronous; z may be overwritten by the next work on the stream (msc_zmatrix_add)."""
+        z2, S, ld = self._vectors(z)
         if S == 0:
             return
         L.check(self.ctx.lib.msc_zmatrix_add(self._h, C.c_void_p(z2.data_ptr()), S, ld))
+
+    def partition_sums(self, cands):
+        """Candidate partitions against the counts (msc_zmatrix_partition_sums).  cands: an int32 device tensor [n] or
+        [ncand, n] laid out as add takes samples; only equality of labels matters, any int32 value is a label.  Returns
+        (w int64 [ncand, m], size int32 [ncand, m]): size[c, a] = the selected rows that c puts with row a (a included),
+        w[c, a] = the sum of counts()[a, b] over those rows.  Exact; flushes the staged samples first."""
+        c2, nc, ld = self._vectors(cands)
+        dev = self.ctx.torch_device
+        w = torch.empty((nc, self.m), dtype=torch.int64, device=dev)
+        size = torch.empty((nc, self.m), dtype=torch.int32, device=dev)
+        L.check(self.ctx.lib.msc_zmatrix_partition_sums(self._h, C.c_void_p(c2.data_ptr()), nc, ld,
+                                                        C.c_void_p(w.data_ptr()), C.c_void_p(size.data_ptr())))
+        return w, size
+
+    def partition_loss(self, cands):
+        """Posterior expected losses of candidate partitions (msc_zmatrix_partition_loss; cands as for partition_sums).
+        Returns (binder_num int64 [ncand], vi_lb float64 [ncand], valid): binder_num / valid is the expected number of
+        mis-paired pairs under Binder's loss (the argmin is Dahl's least-squares clustering); vi_lb is Wade and
+        Ghahramani's lower bound on the expected variation of information less its candidate-independent term, which
+        counts do not determine; valid is the number of valid samples, counts()[0, 0].  Synchronises to read valid."""
+        c2, nc, ld = self._vectors(cands)
+        dev = self.ctx.torch_device
+        binder = torch.empty(nc, dtype=torch.int64, device=dev)
+        vi = torch.empty(nc, dtype=torch.float64, device=dev)
+        valid = torch.empty(1, dtype=torch.int64, device=dev)
+        L.check(self.ctx.lib.msc_zmatrix_partition_loss(self._h, C.c_void_p(c2.data_ptr()), nc, ld,
+                                                        C.c_void_p(binder.data_ptr()), C.c_void_p(vi.data_ptr()),
+                                                        C.c_void_p(valid.data_ptr())))
+        self.ctx.synchronize()
+        return binder, vi, int(valid.item())
 
     @property
     def nsamples(self):

@@ -852,6 +852,37 @@ int msc_zmatrix_nsamples(const msc_zmatrix *zm, uint64_t *out);
  */
 int msc_zmatrix_counts(msc_zmatrix *zm, const uint32_t *host_order, uint32_t *out_dev, uint64_t ld_out);
 int msc_zmatrix_result(msc_zmatrix *zm, const uint32_t *host_order, float *out_dev, uint64_t ld_out);
+/*
+ * Candidate partitions scored against the counts: the sums behind a decision-theoretic point estimate (Binder's loss,
+ * i.e. Dahl's least squares, and Wade & Ghahramani's lower bound on the variation of information).  With C what
+ * msc_zmatrix_counts writes (no order) and V = C[0][0], the valid samples, a candidate c is an assignment vector of n
+ * int32 labels laid out as for msc_zmatrix_add (candidate c at cand_dev + c * ld, ld >= n); position a carries
+ * l_c(a) = cand[c][rows[a]].  Only equality of labels is used: any int32 value is a label and there is no range check.
+ *   size_c[a] = #{ b < m : l_c(b) == l_c(a) }   (b = a included)
+ *   w_c[a]    = the sum of C[a][b] over those b  (>= V)
+ *   binder_num[c] = T + V P_c - 2 Q_c,  P_c = sum_a (size_c[a] - 1) / 2,  Q_c = sum_a (w_c[a] - V) / 2,
+ *                   T = sum_{a<b} C[a][b]:  V * sum_{a<b} |[l_c(a) == l_c(b)] - C[a][b] / V|, an exact int64 >= 0;
+ *                   binder_num / V is the posterior expected number of mis-paired pairs, and Dahl's
+ *                   sum_{a<b} ([..] - Z)^2 differs from it by a term that does not depend on c (same argmin)
+ *   vi_lb[c]      = (1 / m) sum_a (log2 size_c[a] - 2 log2 w_c[a]) + 2 log2 V  in float64: the lower bound on the
+ *                   expected VI less its candidate-independent term (1 / m) sum_a E[log2 size_sample(a)], which the
+ *                   counts do not determine; 0 for all singletons.  The sum runs in a fixed order: the same arguments
+ *                   give the same bits.
+ * Both calls first update the counts with the staged samples (as msc_zmatrix_counts does) and otherwise leave the
+ * accumulator as it was; both are asynchronous on the context's stream.  Outputs are device pointers, each nullable:
+ * w_dev [ncand][m] uint64 and size_dev [ncand][m] uint32; binder_num_dev [ncand], vi_lb_dev [ncand], valid_dev [1] (V).
+ * Every sum is an exact integer for every m and number of samples the accumulator takes.  Candidates are processed a
+ * chunk at a time over buffers the accumulator owns, allocated at the first call: a chunk of 64 .. 512 candidates (8 Mi
+ * labels over 64 ceil(m / 64), rounded down to 64) holds chunk x 64 ceil(m / 64) int32 labels and, for
+ * msc_zmatrix_partition_loss, chunk x m x 12 bytes of sums (m = 16384: 32 MiB + 96 MiB).  MSC_EINVAL: no sample yet,
+ * ncand == 0, ld < n, a null handle or a null cand_dev.  msc_zmatrix_partition_loss returns MSC_EUNSUPPORTED, before
+ * anything is launched, when m (m - 1) / 2 x nsamples does not fit 63 bits.  msc_last_kernel(2) names the
+ * instantiation of the sums kernel (packed 24 + 8 bit partial sums while nsamples < 2^20, 64-bit sums after).
+ */
+int msc_zmatrix_partition_sums(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
+                               uint64_t *w_dev, uint32_t *size_dev);
+int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
+                               int64_t *binder_num_dev, double *vi_lb_dev, uint64_t *valid_dev);
 /* zero the counts and drop the staged samples (asynchronous); destroy frees everything the accumulator allocated */
 int msc_zmatrix_reset(msc_zmatrix *zm);
 int msc_zmatrix_destroy(msc_zmatrix *zm);
