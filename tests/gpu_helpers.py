@@ -89,6 +89,80 @@ def make_feature(family, N, K, rng, dim=0, hp=None):
     return dict(family=family, dim=dim, hp=hp, values=vals, np_dtype=dt)
 
 
+# the state of several features that the hyperparameter tests run, feature j on distinct_hp(.., i=j)
+MIXED = [(orc.BB, 0), (orc.BB, 0), (orc.GP, 0), (orc.GP, 0), (orc.DD, 7), (orc.DD, 33), (orc.NICH, 0), (orc.NICH, 0),
+         (orc.NICH, 0), (orc.BNB, 0), (orc.DM, 4), (orc.BBNC, 0), (orc.NIW, 3)]
+
+
+def distinct_hp(family, dim=0, i=0):
+    """A hyperparameter block in which no two fields can stand in for each other: every value a dyadic rational (the
+    float block the device is given and the double twin see the same number), the fields of a block different from each
+    other and from 1, mu away from 0, psi dense.  make_feature's defaults (all ones, mu = 0, psi = I) cannot tell alpha
+    from beta, inv_beta from beta, one alphas index from another, kappa from nu, or a dropped kappa mu mu^T / nu sigmasq
+    / ln det psi term from a kept one.  i: the variant for the i-th feature of a state (every positive scalar + i / 8,
+    mu - i / 2, alphas rotated by i places, r = 4 + i % 3), so that reading another feature's block shows as well.
+    (alphas cycle with period 7 and niw's mu[j] = ((5 j) % 7 - 3) / 2 passes through 0 at j = 2 mod 7: vectors longer
+    than that repeat values, neighbours still differ.  "Different from each other and from 1" holds at i = 0 and for
+    feature j of MIXED at i = j -- the variants the tests use, asserted in test_hypers_cpu.py -- not for every i: nich
+    at i = 5 has kappa = 1.)"""
+    s = 0.125 * i
+    if family in (orc.BB, orc.BBNC):
+        return dict(alpha=0.75 + s, beta=2.5 + s)
+    if family == orc.GP:
+        return dict(alpha=2.5 + s, inv_beta=0.375 + s)
+    if family == orc.BNB:
+        return dict(alpha=2.5 + s, beta=0.75 + s, r=4 + i % 3)
+    if family in (orc.DD, orc.DM):
+        base = [0.25 + 0.5 * ((3 * j) % 7) for j in range(dim)]
+        return dict(alphas=[float(a) + s for a in np.roll(base, i)])
+    if family == orc.NICH:
+        return dict(mu=-1.25 - 0.5 * i, kappa=0.375 + s, sigmasq=2.5 + s, nu=3.5 + s)
+    if family == orc.NIW:
+        B = np.random.default_rng(1000 + dim).standard_normal((dim, dim))
+        psi = (B @ B.T / dim + 1.5 * np.eye(dim)).astype(np.float32).astype(np.float64)
+        psi = np.tril(psi) + np.tril(psi, -1).T          # (the device reads the lower triangle: exactly symmetric)
+        mu = np.array([((5 * j) % 7 - 3) / 2.0 for j in range(dim)]) - 0.5 * i
+        return dict(mu=mu, kappa=0.75 + s, psi=psi, nu=dim + 2.5 + s)
+    raise ValueError(family)
+
+
+def random_hp(family, dim, hrng):
+    """A block drawn from hrng (the fuzzers' hyperparameter stream -- a generator of its own, so the shapes, data and masks
+    a seed draws stay what they were): positive scalars log-uniform in [0.25, 4], mu uniform in [-3, 3], niw a dense
+    symmetric psi with a random diagonal load and nu = dim + U(0.5, 4); bnb's r stays 3 (make_feature draws the data
+    with it).  Every value is rounded to float: the device's block and the twin's hold the same numbers."""
+    def pos(size=None):
+        return np.asarray(np.exp(hrng.uniform(np.log(0.25), np.log(4.0), size))).astype(np.float32).astype(np.float64)
+
+    def loc(size=None):
+        return np.asarray(hrng.uniform(-3.0, 3.0, size)).astype(np.float32).astype(np.float64)
+    if family in (orc.BB, orc.BBNC):
+        return dict(alpha=float(pos()), beta=float(pos()))
+    if family == orc.GP:
+        return dict(alpha=float(pos()), inv_beta=float(pos()))
+    if family == orc.BNB:
+        return dict(alpha=float(pos()), beta=float(pos()), r=3)
+    if family in (orc.DD, orc.DM):
+        return dict(alphas=[float(a) for a in pos(dim)])
+    if family == orc.NICH:
+        return dict(mu=float(loc()), kappa=float(pos()), sigmasq=float(pos()), nu=float(pos()))
+    if family == orc.NIW:
+        B = hrng.standard_normal((dim, dim))
+        psi = (B @ B.T / dim + np.diag(hrng.uniform(0.5, 2.5, dim))).astype(np.float32).astype(np.float64)
+        psi = np.tril(psi) + np.tril(psi, -1).T
+        return dict(mu=loc(dim), kappa=float(pos()), psi=psi, nu=float(np.float32(dim + hrng.uniform(0.5, 4.0))))
+    raise ValueError(family)
+
+
+def edge_assignment(N, K, rng):
+    """-> z with the edge state every hyperparameter test wants: the last group empty, the one before it a singleton
+    (row 3: leaving it empties the group, its leave-one-out score is the prior's alone), row 5 unassigned"""
+    z = rng.integers(0, K - 2, N).astype(np.int32)
+    z[3] = K - 2
+    z[5] = -1
+    return z
+
+
 def recarray_of(features):
     dt = np.dtype([("f%d" % i, f["np_dtype"]) for i, f in enumerate(features)])
     arr = np.zeros(len(features[0]["values"]), dtype=dt)

@@ -7,11 +7,18 @@ import pytest
 import torch
 
 from oracle import oracle as orc
-from tests.gpu_helpers import TOL, audit, crp_prior_matrix, load_state, make_feature, rel_err
+from tests.gpu_helpers import TOL, audit, crp_prior_matrix, load_state, make_feature, random_hp, rel_err
 
 pytestmark = pytest.mark.gpu
 
 FAMS = [orc.BB, orc.BBNC, orc.GP, orc.BNB, orc.DD, orc.NICH, orc.NIW, orc.DM]
+
+
+def _hp_stream(seed):
+    """hp_of(j, family, dim) drawing feature after feature from a generator of its own, default_rng((7919, seed)): the
+    seed's shapes, data and masks -- the other generator's draws -- are what they were under the all-one blocks"""
+    hrng = np.random.default_rng((7919, seed))
+    return lambda j, family, dim: random_hp(family, dim, hrng)
 
 
 def _random_spec(rng):
@@ -41,6 +48,8 @@ def test_random_feature_lists_match_the_oracle(gpu_ctx, seed):
     N = int(rng.choice([1, 5, 64, 127, 129, 300, 777]))
     K = int(rng.choice([1, 3, 16, 20, 33, 64, 255, 256, 257, 300]))
     feats = [make_feature(f, N, K, rng, d) for f, d in spec]
+    hp_of = _hp_stream(seed)
+    feats = [dict(f, hp=hp_of(j, f["family"], f["dim"])) for j, f in enumerate(feats)]
     if rng.random() < 0.3:                                       # gp counts beyond what a feature stages / tables hold
         for f in feats:
             if f["family"] == orc.GP and N > 2:
@@ -118,7 +127,8 @@ def test_random_sweeps_draw_the_oracles_assignments(gpu_ctx, seed):
     spec = _random_spec(rng)
     N = int(rng.choice([64, 300, 1000]))
     K = int(rng.choice([2, 17, 40, 64, 256, 300]))
-    got, want, scores, _ = _run(gpu_ctx, spec, N, K, seed=300 + seed, sweep_idx=seed % 5, alpha=0.9, empty=min(2, K - 1))
+    got, want, scores, _ = _run(gpu_ctx, spec, N, K, seed=300 + seed, sweep_idx=seed % 5, alpha=0.9, empty=min(2, K - 1),
+                                hp_of=_hp_stream(seed))
     _check_agreement(got, want, scores, 300 + seed, seed % 5, 0.98)
 
 
@@ -151,6 +161,8 @@ def test_random_scalar_feature_lists_on_many_rows(gpu_ctx, seed):
     K = int(rng.choice([40, 64, 100, 128, 200, 256, 300, 384])) - int(rng.integers(0, 3))
     feats = [make_feature(f, N, K, rng, d) for f, d in spec]
     feats = [dict(f, values=(f["values"] // 5).astype(np.int32)) if f["family"] == orc.DM else f for f in feats]
+    hp_of = _hp_stream(seed)
+    feats = [dict(f, hp=hp_of(j, f["family"], f["dim"])) for j, f in enumerate(feats)]
     z = rng.integers(0, K, N).astype(np.int32)
     z[7] = -1
     # (masked lookup columns keep the fast kernels; now and then a masked nich column: the one-phase-after-the-other kernels)
@@ -227,5 +239,5 @@ def test_random_sweeps_on_many_rows_draw_the_oracles_assignments(gpu_ctx, seed):
     N = 33_000 + int(rng.integers(0, 7000))
     K = int(rng.choice([40, 64, 100, 128, 200, 256, 300, 384])) - int(rng.integers(0, 3))
     empty = int(rng.integers(0, max(1, K // 8)))
-    got, want, scores, z = _run(gpu_ctx, spec, N, K, seed=900 + seed, sweep_idx=3, alpha=0.9, empty=empty)
+    got, want, scores, z = _run(gpu_ctx, spec, N, K, seed=900 + seed, sweep_idx=3, alpha=0.9, empty=empty, hp_of=_hp_stream(seed))
     _check_agreement(got, want, scores, 900 + seed, 3, 0.995)

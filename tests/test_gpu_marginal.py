@@ -25,11 +25,15 @@ MIX = [(orc.BB, 0), (orc.GP, 0), (orc.DD, 5), (orc.NICH, 0)]
 
 
 class Case(object):
-    def __init__(self, ctx, specs, N, K, seed, alpha=1.5, used=None, masked=()):
+    def __init__(self, ctx, specs, N, K, seed, alpha=1.5, used=None, masked=(), hp_of=None):
+        """hp_of(j, family, dim) -> feature j's hyperparameter block, or None for make_feature's (set after the values are
+        drawn: the data of a seed does not depend on it)"""
         rng = np.random.default_rng(seed)
         used = K if used is None else used
         self.N, self.K, self.alpha, self.specs = N, K, alpha, specs
         self.feats = [make_feature(fam, N, max(used, 1), rng, dim) for fam, dim in specs]
+        if hp_of is not None:
+            self.feats = [dict(f, hp=hp_of(j, f["family"], f["dim"]) or f["hp"]) for j, f in enumerate(self.feats)]
         z = rng.integers(0, max(used, 1), N).astype(np.int32)
         if used < K:                                  # a singleton group: it empties when its row leaves
             z[N // 2] = used

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.gpu_helpers import random_hp
 from tests.test_gpu_marginal import Case, check_case
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,9 @@ def test_random_scalar_feature_lists(gpu_ctx, seed):
     specs = [POOL[i] for i in rng.integers(0, len(POOL), int(rng.integers(1, 9)))]
     K = int(rng.integers(38, 385))
     N = int(rng.integers(33000, 70001))
-    c = Case(gpu_ctx, specs, N, K, seed=seed, alpha=float(rng.choice([0.5, 1.5, 4.0])), used=K - int(rng.integers(1, 6)))
+    hrng = np.random.default_rng((7919, seed))       # the hyperparameters' own stream: the seed's shapes and data stay
+    c = Case(gpu_ctx, specs, N, K, seed=seed, alpha=float(rng.choice([0.5, 1.5, 4.0])), used=K - int(rng.integers(1, 6)),
+             hp_of=lambda j, family, dim: random_hp(family, dim, hrng))
     name = "fuzz_%d" % seed
     check_case(c, name, nsample=1024)
     check_case(c, name, z=c.loo_z(seed), nsample=1024)

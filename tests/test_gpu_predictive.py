@@ -103,10 +103,11 @@ def test_group_draw_is_the_sweeps_draw_of_an_unassigned_row_under_its_own_key(gp
     assert (inverse_cdf(probs, u_sweep)[0] == g).mean() < 0.9
 
 
-def group_state(ctx, family, dim, K, n_per, seed, hp=None):
+def group_state(ctx, family, dim, K, n_per, seed, hp=None, empty=0):
+    """K groups of n_per rows each; the last `empty` of them hold no row (their draws are the prior predictive's)"""
     rng = np.random.default_rng(seed)
-    f = make_feature(family, K * n_per, K, rng, dim=dim, hp=hp)
-    z = np.repeat(np.arange(K), n_per).astype(np.int32)
+    f = make_feature(family, (K - empty) * n_per, K, rng, dim=dim, hp=hp)
+    z = np.repeat(np.arange(K - empty), n_per).astype(np.int32)
     fs = state_from_assignment([f], K, z)
     st = common_amd.State(ctx, [(family, dim)], K)
     load_state(st, fs)
