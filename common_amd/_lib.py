@@ -32,6 +32,8 @@ SLICE_STEP_OUT = 64                   # m: the stepping-out limit of a slice upd
 SLICE_SHRINK = 256                    # rejected proposals before an update keeps its value
 ZMATRIX_MAX_ROWS = 1 << 18            # msc_zmatrix_create: m at most
 ZMATRIX_MAX_LABELS = 1 << 16          # ... and nlabels at most
+ZMATRIX_REFINE_MAX_ROWS = 1 << 15     # msc_zmatrix_partition_refine: m at most
+ZMATRIX_REFINE_MAX_CLUSTERS = 1 << 10 # ... and max_clusters at most
 LINKAGE_MAX_N = 1 << 16               # msc_linkage_single: n at most
 
 
@@ -184,6 +186,8 @@ _SIGS = {
     "msc_zmatrix_partition_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
     "msc_zmatrix_partition_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
+    "msc_zmatrix_partition_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "msc_zmatrix_reset": (C.c_int, [C.c_void_p]),
     "msc_zmatrix_destroy": (C.c_int, [C.c_void_p]),
     "msc_linkage_single": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

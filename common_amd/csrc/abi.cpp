@@ -104,7 +104,7 @@ static int device_error_word(int device, volatile uint32_t **host_out) {
     MSC_HIP(hipHostGetDevicePointer(&d, h, 0));
     uint32_t *w = static_cast<uint32_t *>(d);
     if (bind_error_word_score(w) || bind_error_word_sweep(w) || bind_error_word_state(w) || bind_error_word_seq(w) ||
-        bind_error_word_query(w))
+        bind_error_word_query(w) || bind_error_word_refine(w))
       return fail(MSC_EHIP, "binding the device error word failed: %s", hipGetErrorString(hipGetLastError()));
     words[device] = h;
   }
@@ -126,7 +126,8 @@ static int device_error_check(msc_context *ctx) {
   if (code & 4u) add("msc_relation_slice_scores: a block offset beyond the score row (detail: cell)");
   if (code & 8u) add("msc_sweep_sequential: an order entry >= nrows (visit skipped; detail: entry), or a leave from an empty group or counter (detail: group)");
   if (code & 16u) add("msc_zmatrix_add: a label outside [0, nlabels) (that sample was skipped; detail: row of z)");
-  if (code & ~31u) add("unknown device-side error");
+  if (code & 32u) add("msc_zmatrix_partition_refine: a start with more than max_clusters clusters (its outputs mean nothing; detail: start of its chunk)");
+  if (code & ~63u) add("unknown device-side error");
   return fail(MSC_EDEVICE, "reported by an earlier kernel on device %d: %s [detail of the first: %u]; rebuild the affected state's tables",
               ctx->device, what.c_str(), detail);
 }
@@ -4130,27 +4131,23 @@ extern "C" int msc_zmatrix_partition_sums(msc_zmatrix *zm, const int32_t *cand_d
   return MSC_OK;
 }
 
-extern "C" int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
-                                          int64_t *binder_num_dev, double *vi_lb_dev, uint64_t *valid_dev) {
-  const char *who = "msc_zmatrix_partition_loss";
-  MSC_REQUIRE(zm && cand_dev, "null argument");
-  {
-    // binder_num <= V m (m - 1) / 2 must fit an int64
-    const unsigned __int128 pairs = (unsigned __int128)zm->m * (zm->m - 1) / 2;
-    if (zm->nsamples > 0 && pairs * zm->nsamples >= ((unsigned __int128)1 << 63))
-      return fail(MSC_EUNSUPPORTED, "%s: m (m - 1) / 2 x nsamples = %u (%u - 1) / 2 x %llu does not fit 63 bits", who, zm->m,
-                  zm->m, (unsigned long long)zm->nsamples);
-  }
-  MSC_TRY(zm_partition_begin(zm, cand_dev, ncand, ld, who));
-  if (!binder_num_dev && !vi_lb_dev && !valid_dev) return MSC_OK;
-  const uint32_t chunk = zm_partition_chunk(zm->nt);
+// binder_num <= V m (m - 1) / 2 must fit an int64
+static int zm_partition_fits(const msc_zmatrix *zm, const char *who) {
+  const unsigned __int128 pairs = (unsigned __int128)zm->m * (zm->m - 1) / 2;
+  if (zm->nsamples > 0 && pairs * zm->nsamples >= ((unsigned __int128)1 << 63))
+    return fail(MSC_EUNSUPPORTED, "%s: m (m - 1) / 2 x nsamples = %u (%u - 1) / 2 x %llu does not fit 63 bits", who, zm->m,
+                zm->m, (unsigned long long)zm->nsamples);
+  return MSC_OK;
+}
+
+// the loss workspaces of one chunk, and T (and V into valid_dev, nullable): the loss of all rows in one cluster
+static int zm_partition_total(msc_zmatrix *zm, uint32_t chunk, uint64_t *valid_dev, const char *who) {
   const size_t mpad = (size_t)zm->nt * kZmTile;
   MSC_TRY(zm_partition_reserve(zm, zm->part_lab, chunk * mpad, who, "label buffer"));
   MSC_TRY(zm_partition_reserve(zm, zm->part_w, (size_t)chunk * zm->m, who, "workspace of row sums"));
   MSC_TRY(zm_partition_reserve(zm, zm->part_size, (size_t)chunk * zm->m, who, "workspace of cluster sizes"));
   MSC_TRY(zm_partition_reserve(zm, zm->part_T, 1, who, "pair total"));
   const hipStream_t s = zm->ctx->stream;
-  // T (and V): the loss of all rows in one cluster
   MSC_HIP(hipMemsetAsync(zm->part_lab, 0, mpad * 4, s));
   if (launch_zm_partition_sums(s, zm->counts, zm->nt, zm->m, zm->nsamples < kZmPartPackedMax, zm->part_lab, 1,
                                zm->part_w, zm->part_size))
@@ -4158,6 +4155,19 @@ extern "C" int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_d
   if (launch_zm_partition_loss(s, zm->counts, zm->part_w, zm->part_size, zm->m, 1, true, zm->part_T, nullptr, nullptr,
                                valid_dev))
     return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
+  return MSC_OK;
+}
+
+extern "C" int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
+                                          int64_t *binder_num_dev, double *vi_lb_dev, uint64_t *valid_dev) {
+  const char *who = "msc_zmatrix_partition_loss";
+  MSC_REQUIRE(zm && cand_dev, "null argument");
+  MSC_TRY(zm_partition_fits(zm, who));
+  MSC_TRY(zm_partition_begin(zm, cand_dev, ncand, ld, who));
+  if (!binder_num_dev && !vi_lb_dev && !valid_dev) return MSC_OK;
+  const uint32_t chunk = zm_partition_chunk(zm->nt);
+  MSC_TRY(zm_partition_total(zm, chunk, valid_dev, who));
+  const hipStream_t s = zm->ctx->stream;
   if (!binder_num_dev && !vi_lb_dev) return MSC_OK;
   for (uint32_t c0 = 0; c0 < ncand; c0 += chunk) {
     const uint32_t k = std::min(chunk, ncand - c0);
@@ -4166,6 +4176,79 @@ extern "C" int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_d
                                  binder_num_dev ? binder_num_dev + c0 : nullptr, vi_lb_dev ? vi_lb_dev + c0 : nullptr,
                                  nullptr))
       return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
+  }
+  return MSC_OK;
+}
+
+// greedy row moves from given starts (kernels_refine.hip)
+extern "C" int msc_zmatrix_partition_refine(msc_zmatrix *zm, const int32_t *start_dev, uint32_t nstarts, uint64_t ld,
+                                            uint32_t max_sweeps, uint32_t max_clusters, const uint32_t *host_order,
+                                            int32_t *labels_dev, int64_t *binder_num_dev, uint32_t *sweeps_dev,
+                                            uint64_t *moves_dev) {
+  const char *who = "msc_zmatrix_partition_refine";
+  MSC_REQUIRE(zm && start_dev, "null argument");
+  const uint32_t m = zm->m;
+  MSC_REQUIRE(max_clusters >= 1 && max_clusters <= m, "%s: max_clusters = %u outside [1, m = %u]", who, max_clusters, m);
+  if (host_order) {
+    std::vector<uint8_t> seen(m, 0);
+    for (uint32_t a = 0; a < m; a++) {
+      MSC_REQUIRE(host_order[a] < m && !seen[host_order[a]], "%s: order is not a permutation of [0, %u): entry %u is %u",
+                  who, m, a, host_order[a]);
+      seen[host_order[a]] = 1;
+    }
+  }
+  MSC_REQUIRE(zm->nsamples > 0, "%s: no sample has been added", who);
+  MSC_REQUIRE(nstarts > 0, "%s: nstarts is 0", who);
+  MSC_REQUIRE(ld >= zm->n, "%s: ld = %llu is below n = %llu", who, (unsigned long long)ld, (unsigned long long)zm->n);
+  if (m > kZmRefineMaxRows || max_clusters > kZmRefineMaxClusters)
+    return fail(MSC_EUNSUPPORTED, "%s: m = %u, max_clusters = %u: at most %u positions and %u clusters", who, m,
+                max_clusters, kZmRefineMaxRows, kZmRefineMaxClusters);
+  MSC_TRY(zm_partition_fits(zm, who));
+  MSC_TRY(zm_partition_begin(zm, start_dev, nstarts, ld, who));
+  if (!labels_dev && !binder_num_dev && !sweeps_dev && !moves_dev) return MSC_OK;
+  const uint32_t chunk = zm_partition_chunk(zm->nt);
+  const uint64_t ldd = ((uint64_t)m + 3u) & ~(uint64_t)3u;
+  const uint32_t mpad = zm->nt * kZmTile;
+  MSC_TRY(zm_partition_total(zm, chunk, nullptr, who));
+  MSC_TRY(zm_partition_reserve(zm, zm->ref_dense, (size_t)m * ldd, who, "dense copy of the counts"));
+  MSC_TRY(zm_partition_reserve(zm, zm->ref_ids, (size_t)chunk * ldd, who, "cluster ids"));
+  MSC_TRY(zm_partition_reserve(zm, zm->ref_st, chunk, who, "running totals"));
+  MSC_TRY(zm_partition_reserve(zm, zm->ref_binder, chunk, who, "losses of the starts"));
+  const hipStream_t s = zm->ctx->stream;
+  if (host_order) MSC_HIP(hipMemcpyAsync(zm->order_dev, host_order, (size_t)m * 4, hipMemcpyHostToDevice, s));
+  if (launch_zm_finish(s, zm->counts, zm->nt, m, nullptr, false, (float)zm->nsamples, zm->ref_dense, ldd))
+    return fail(MSC_EHIP, "k_zm_finish launch failed");
+  const bool narrow = zm->nsamples * (uint64_t)m < (1ull << 32);      // s_k <= V (m - 1), V <= nsamples
+  std::vector<RefineStart> st_host;
+  for (uint32_t c0 = 0; c0 < nstarts; c0 += chunk) {
+    const uint32_t k = std::min(chunk, nstarts - c0);
+    MSC_TRY(zm_partition_chunk_sums(zm, start_dev + (uint64_t)c0 * ld, k, ld, zm->part_w, zm->part_size));
+    if (launch_zm_partition_loss(s, zm->counts, zm->part_w, zm->part_size, m, k, false, zm->part_T, zm->ref_binder, nullptr,
+                                 nullptr))
+      return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
+    if (launch_zm_refine_init(s, zm->part_lab, mpad, m, max_clusters, k, zm->ref_ids, ldd, zm->ref_st))
+      return fail(MSC_EHIP, "k_zm_refine_init launch failed");
+    for (uint32_t sweep = 0; sweep < max_sweeps; sweep++) {
+      // every sweep is a launch and the stream is not waited for -- up to kRefineBlindSweeps of them; a caller who
+      // allows more pays one wait per kRefineBlindSweeps further ones, so that the launches end when the starts have
+      constexpr uint32_t kRefineBlindSweeps = 64;
+      if (sweep >= kRefineBlindSweeps && sweep % kRefineBlindSweeps == 0) {
+        st_host.resize(k);
+        MSC_HIP(hipMemcpyAsync(st_host.data(), zm->ref_st, (size_t)k * sizeof(RefineStart), hipMemcpyDeviceToHost, s));
+        MSC_HIP(hipStreamSynchronize(s));
+        bool any = false;
+        for (uint32_t i = 0; i < k; i++) any = any || st_host[i].active != 0u;
+        if (!any) break;
+      }
+      if (launch_zm_refine_sweep(s, zm->ref_dense, ldd, m, max_clusters, host_order ? zm->order_dev : nullptr, narrow, k,
+                                 zm->ref_ids, zm->ref_st))
+        return fail(MSC_EHIP, "k_zm_refine_sweep launch failed");
+    }
+    if (launch_zm_refine_finish(s, zm->ref_ids, ldd, m, max_clusters, k, zm->ref_st, zm->ref_binder,
+                                labels_dev ? labels_dev + (uint64_t)c0 * m : nullptr,
+                                binder_num_dev ? binder_num_dev + c0 : nullptr, sweeps_dev ? sweeps_dev + c0 : nullptr,
+                                moves_dev ? moves_dev + c0 : nullptr))
+      return fail(MSC_EHIP, "k_zm_refine_finish launch failed");
   }
   return MSC_OK;
 }

@@ -17,6 +17,7 @@ enum : uint32_t {
   MSC_DEVERR_SEQ_SWEEP = 8u,         // k_sweep_seq: an order entry >= nrows (visit skipped; detail = entry), a leave from an
                                      // empty group (the row only joins) or from an empty counter of a feature (detail = group)
   MSC_DEVERR_ZMATRIX_LABEL = 16u,    // k_zm_check: a label outside [0, nlabels) (the sample is skipped); detail = row of z
+  MSC_DEVERR_REFINE_CLUSTERS = 32u,  // k_zm_refine_init: a start with more than max_clusters clusters (it is not refined); detail = start
 };
 
 static __device__ uint32_t *g_dev_error = nullptr;

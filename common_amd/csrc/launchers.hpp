@@ -348,6 +348,23 @@ int launch_zm_partition_loss(hipStream_t stream, const uint32_t *counts, const u
                              uint32_t m, uint32_t ncand, bool tmode, uint64_t *T_io, int64_t *binder, double *vi,
                              uint64_t *valid);
 
+// kernels_refine.hip (msc_zmatrix_partition_refine): greedy row moves over a dense [m][ldd] u32 copy of the counts (ldd =
+// m rounded up to 4), a workgroup per start.  ids: [nstarts][ldd] 16-bit cluster ids of the positions; st: a start's
+// running totals.  init turns gathered labels (launch_zm_partition_gather's lab, row stride mpad) into ids and reports
+// MSC_DEVERR_REFINE_CLUSTERS for a start with more than max_clusters labels; one sweep launch is one sweep of every
+// start that is still active (narrow: nsamples x m < 2^32, so 32-bit bins hold every s_k); finish writes the outputs
+// (each nullable).  -2: a shape beyond the caps
+constexpr uint32_t kZmRefineMaxRows = 1u << 15;
+constexpr uint32_t kZmRefineMaxClusters = 1u << 10;
+int bind_error_word_refine(uint32_t *word_dev);
+int launch_zm_refine_init(hipStream_t stream, const int32_t *lab, uint32_t mpad, uint32_t m, uint32_t max_clusters,
+                          uint32_t nstarts, uint16_t *ids, uint64_t ldi, RefineStart *st);
+int launch_zm_refine_sweep(hipStream_t stream, const uint32_t *dense, uint64_t ldd, uint32_t m, uint32_t max_clusters,
+                           const uint32_t *order, bool narrow, uint32_t nstarts, uint16_t *ids, RefineStart *st);
+int launch_zm_refine_finish(hipStream_t stream, const uint16_t *ids, uint64_t ldi, uint32_t m, uint32_t max_clusters,
+                            uint32_t nstarts, const RefineStart *st, const int64_t *binder0, int32_t *labels,
+                            int64_t *binder, uint32_t *sweeps, uint64_t *moves);
+
 // kernels_linkage.hip (msc_linkage_single): Prim's chain over the dense n x n matrix z (row stride ld), one workgroup
 // of linkage::shape_for(n) (linkage_host.hpp); edges[3 i ..] = (x, y, distance) of step i.  -2: n outside [2, 65536]
 int launch_linkage_prim(hipStream_t stream, const float *z, uint64_t ld, uint32_t n, double *edges);

@@ -322,6 +322,14 @@ inline uint32_t blocked_slices(int family, uint32_t dim) {
   }
 }
 
+// One start of msc_zmatrix_partition_refine (kernels_refine.hip): its running totals over the sweeps
+struct RefineStart {
+  int64_t dec;        // binder_num of the start less binder_num now
+  uint64_t moves;
+  uint32_t sweeps;
+  uint32_t active;    // the last sweep moved a row (or none has run): the next one has work
+};
+
 // One split-merge proposal as the kernels of kernels_splitmerge.hip hand it on (msc_split_merge): written by
 // k_sm_anchors, `accepted` by k_sm_decide.  A void proposal (an unassigned anchor, no empty slot for a split, fewer than
 // two rows) makes every later kernel of the proposal a no-op.
@@ -703,4 +711,11 @@ struct msc_zmatrix {
   msc::DevBuf<uint64_t> part_w;
   msc::DevBuf<uint32_t> part_size;
   msc::DevBuf<uint64_t> part_T;
+  // msc_zmatrix_partition_refine (kernels_refine.hip), allocated at the first call: the dense [m][m rounded up to 4] copy
+  // of the counts, and of one chunk of starts the 16-bit ids [chunk][m rounded up to 4], the running totals and the
+  // starts' own binder_num
+  msc::DevBuf<uint32_t> ref_dense;
+  msc::DevBuf<uint16_t> ref_ids;
+  msc::DevBuf<msc::RefineStart> ref_st;
+  msc::DevBuf<int64_t> ref_binder;
 };

@@ -9,14 +9,16 @@ itself for numpy input, ``msc_linkage_single`` for a float32 device tensor (the 
 exposes neither.  ``partition_sums``, ``partition_loss`` and ``point_estimate`` choose ONE clustering by posterior expected
 loss (Binder's loss, which is Dahl's least-squares clustering, or the variation-of-information lower bound of Wade and
 Ghahramani) among candidate partitions, from exact integer sums over the co-clustering counts: numpy on the host,
-``msc_zmatrix_partition_*`` on the device, the same integers on both.
+``msc_zmatrix_partition_*`` on the device, the same integers on both.  ``refine_partition`` takes partitions further by
+greedy row moves under Binder's loss until no single move helps (``msc_zmatrix_partition_refine`` on the device, plain
+numpy on the host, the same trajectory bit for bit), and ``point_estimate(refine=...)`` refines the best candidates.
 """
 import collections
 
 import numpy as np
 import torch
 
-from ._lib import LINKAGE_MAX_N, ZMATRIX_MAX_LABELS
+from ._lib import LINKAGE_MAX_N, ZMATRIX_MAX_LABELS, ZMATRIX_REFINE_MAX_CLUSTERS
 from .runtime import Context, ZMatrix
 
 _HOST_CHUNK_FLOATS = 1 << 23      # one-hot block of the numpy path: at most 64 MiB of float64
@@ -404,6 +406,28 @@ class _Scorer(object):
             return w.cpu().numpy(), size.cpu().numpy()
         return _sums_of_counts(self.C, c)
 
+    def refine(self, starts, max_sweeps, max_clusters, order):
+        """(labels, binder_num, sweeps, moves) of starts given as candidates are"""
+        if self.zm is not None:
+            return self.zm.partition_refine(starts, max_sweeps, max_clusters, order)
+        m = self.C.shape[0]
+        return _refine_host(self.C, starts, max_sweeps, m if max_clusters is None else max_clusters, order)
+
+    def sums_of_positions(self, labels):
+        """(w, size) as numpy arrays of one partition given over the rows the sums run over"""
+        labels = np.asarray(labels).reshape(-1)
+        if self.zm is None:
+            return _sums_of_counts(self.C, labels[None])
+        full = np.zeros(self.n, dtype=np.int32)
+        if self.zm._rows is None:
+            full[:] = labels
+        else:
+            rows = self.zm._rows.astype(np.int64)
+            full[rows] = labels
+            if not np.array_equal(full[rows], labels):
+                raise ValueError("a row selected twice ended in two clusters: no vector of n labels holds this partition")
+        return self.sums(torch.from_numpy(full).to(self.zm.ctx.torch_device)[None])
+
     def selected(self, labels):
         """a candidate's labels over the rows the sums run over"""
         labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
@@ -437,7 +461,113 @@ def partition_loss(assignments, candidates, ctx=None):
         sc.close()
 
 
-def point_estimate(assignments, loss="binder", candidates=None, ctx=None):
+# ---- greedy refinement under Binder's loss ---------------------------------------------------------------------------
+RefinedPartitions = collections.namedtuple("RefinedPartitions", ["labels", "binder_num", "sweeps", "moves", "valid"])
+_INT64_MIN = np.iinfo(np.int64).min
+
+
+def _row_sums(C_row, ids, K, exact_in_float):
+    """s_k = the sum of C_row over the positions with id k, int64 [K]"""
+    if exact_in_float:
+        return np.bincount(ids, weights=C_row, minlength=K).astype(np.int64)
+    s = np.zeros(K, dtype=np.int64)
+    np.add.at(s, ids, C_row)
+    return s
+
+
+def _refine_host(C, starts, max_sweeps, max_clusters, order):
+    """The rule of msc_zmatrix_partition_refine (include/microscopes_hip.h) in plain numpy over the int64 counts C:
+    starts [nstarts, m] over the positions -> (labels int32 [nstarts, m], binder_num int64, sweeps int32, moves int64)"""
+    starts = np.asarray(starts)
+    ns, m = starts.shape
+    K = int(max_clusters)
+    if K < 1 or K > m:
+        raise ValueError("max_clusters must lie in [1, m = %d]" % m)
+    if int(max_sweeps) < 0:
+        raise ValueError("max_sweeps must not be negative")
+    visit = np.arange(m) if order is None else np.asarray(order).astype(np.int64)
+    if order is not None and not _is_permutation(np.asarray(order), m):
+        raise ValueError("not a valid permutation")
+    V = int(C[0, 0])
+    exact_in_float = V * m < 2 ** 53                   # bincount adds in float64
+    Cf = C.astype(np.float64) if exact_in_float else C
+    binder0 = _loss_of_sums(C, *_sums_of_counts(C, starts))[0]
+    labels = np.empty((ns, m), dtype=np.int32)
+    binder = np.empty(ns, dtype=np.int64)
+    sweeps = np.zeros(ns, dtype=np.int32)
+    moves = np.zeros(ns, dtype=np.int64)
+    for i in range(ns):
+        ids = _renumber(starts[i]).astype(np.int64)
+        if int(ids.max()) + 1 > K:
+            raise ValueError("a start holds %d clusters, more than max_clusters = %d" % (int(ids.max()) + 1, K))
+        n = np.bincount(ids, minlength=K).astype(np.int64)
+        dec = 0
+        for _ in range(int(max_sweeps)):
+            moved = 0
+            for a in visit:
+                c = int(ids[a])
+                s = _row_sums(Cf[a], ids, K, exact_in_float)
+                s[c] -= int(C[a, a])
+                n[c] -= 1                              # n' from here on
+                g = 2 * s - V * n
+                g_cur = int(g[c]) if n[c] > 0 else 0
+                k = int(np.argmax(np.where(n > 0, g, _INT64_MIN)))      # the first of the largest: the lowest id
+                target, gain = -1, 0
+                if n[k] > 0 and int(g[k]) > g_cur:
+                    target, gain = k, int(g[k])
+                elif n[c] > 0 and 0 > g_cur:
+                    free = np.flatnonzero(n == 0)      # (n[c] > 0 here: c is not among them)
+                    if free.size:
+                        target = int(free[0])
+                if target < 0:
+                    n[c] += 1
+                    continue
+                n[target] += 1
+                ids[a] = target
+                dec += gain - g_cur
+                moved += 1
+            sweeps[i] += 1
+            moves[i] += moved
+            if moved == 0:
+                break
+        labels[i] = _renumber(ids)
+        binder[i] = int(binder0[i]) - dec
+    return labels, binder, sweeps, moves
+
+
+def refine_partition(assignments, starts, max_sweeps=20, max_clusters=None, order=None, ctx=None):
+    """Partitions taken to a local optimum of Binder's posterior expected loss by greedy row moves.
+
+    From each start, rows are visited in ascending order (or in ``order``, a permutation of the rows scored) and each
+    moves to the cluster -- or alone into a new one -- that lowers ``binder_num`` most; a row stays on a tie, and an
+    existing cluster is preferred to a new one at equal gain.  Sweeps repeat until one moves nothing or ``max_sweeps``
+    have run (include/microscopes_hip.h states the rule in full under msc_zmatrix_partition_refine).  Every move lowers
+    ``binder_num`` strictly, so the result is never worse than its start, and a result with ``sweeps < max_sweeps`` is a
+    local optimum: no single row move lowers it.  ``max_clusters``: the most clusters a partition may hold on the way
+    (``None``: the number of rows scored, at most %d on the device); a start that holds more raises ``ValueError``.
+
+    ``assignments`` and ``starts`` as ``partition_loss`` takes assignments and candidates.  Returns a named tuple
+    ``(labels [nstarts, m] int32, numbered from 0 in the order of first row; binder_num int64 [nstarts]; sweeps int32
+    [nstarts], the last one that moved nothing included; moves int64 [nstarts]; valid)``.  Numpy input without ``ctx``
+    runs the host implementation, plain numpy over the int64 counts; device tensors, ``ctx=`` or an open ``ZMatrix`` run
+    ``msc_zmatrix_partition_refine`` and return device tensors holding the same integers, bit for bit.  The
+    variation-of-information bound is not refined.""" % ZMATRIX_REFINE_MAX_CLUSTERS
+    sc = _Scorer(assignments, ctx)
+    try:
+        c = sc.candidates(starts)
+        if sc.zm is not None:
+            out = sc.refine(c, max_sweeps, max_clusters, order)
+            sc.zm.ctx.synchronize()
+            valid = sc.zm.partition_loss(c[:1])[2]
+        else:
+            out = sc.refine(c, max_sweeps, max_clusters, order)
+            valid = int(sc.C[0, 0])
+        return RefinedPartitions(out[0], out[1], out[2], out[3], valid)
+    finally:
+        sc.close()
+
+
+def point_estimate(assignments, loss="binder", candidates=None, ctx=None, refine=0, starts=8):
     """ONE clustering out of posterior samples: the candidate of the lowest posterior expected loss.
 
     ``loss``: ``"binder"`` (Binder's loss: Dahl's least-squares clustering) or ``"vi"`` (the variation-of-information lower
@@ -446,15 +576,41 @@ def point_estimate(assignments, loss="binder", candidates=None, ctx=None):
     numpy values: ``labels`` (the winner over the rows scored, numbered from 0 in the order of first row), ``index`` (the
     winner; the lowest index among equal losses), ``losses`` (``binder_num`` int64 or ``vi_lb`` float64 of every
     candidate) and ``confidence`` (float64: ``w[a] / (valid * size[a])``, the mean posterior probability that row a is
-    with a row of its own cluster, itself included; in (0, 1])."""
+    with a row of its own cluster, itself included; in (0, 1]).
+
+    ``refine > 0`` (Binder's loss only; ``"vi"`` raises ``ValueError``): the ``starts`` candidates of lowest loss (ties
+    to the lowest index) are each refined by greedy row moves for at most ``refine`` sweeps (``refine_partition``) and
+    the best refined partition is returned (ties to the better-ranked start): ``labels`` and ``confidence`` are its own,
+    ``index`` is the candidate it grew from, ``losses`` stay the candidates' own."""
     if loss not in _LOSSES:
         raise ValueError("loss must be one of %s" % (_LOSSES,))
+    refine, starts = int(refine), int(starts)
+    if refine < 0 or starts < 1:
+        raise ValueError("refine must not be negative and starts must be at least 1")
+    if refine > 0 and loss != "binder":
+        raise ValueError("refine > 0 needs loss='binder': the variation-of-information bound is not refined")
     sc = _Scorer(assignments, ctx)
     try:
         c = sc.candidates(candidates)
         binder, vi, valid = sc.loss(c)
         losses = binder if loss == "binder" else vi
         losses = losses.cpu().numpy() if isinstance(losses, torch.Tensor) else np.asarray(losses)
+        if refine > 0:
+            top = np.argsort(losses, kind="stable")[:starts]
+            if isinstance(c, torch.Tensor):
+                picked = c[torch.from_numpy(top).to(c.device)]
+            else:
+                picked = c[top]
+            m = sc.zm.m if sc.zm is not None else sc.C.shape[0]
+            cap = min(m, ZMATRIX_REFINE_MAX_CLUSTERS) if sc.zm is not None else m
+            got = sc.refine(picked, refine, cap, None)
+            rb = got[1].cpu().numpy() if isinstance(got[1], torch.Tensor) else got[1]
+            best = int(np.argmin(rb))
+            labels = got[0][best]
+            labels = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else labels
+            w, size = sc.sums_of_positions(labels)
+            confidence = w[0].astype(np.float64) / (float(valid) * size[0].astype(np.float64))
+            return PointEstimate(_renumber(labels), int(top[best]), losses, confidence)
         index = int(np.argmin(losses))
         w, size = sc.sums(c[index:index + 1])
         confidence = w[0].astype(np.float64) / (float(valid) * size[0].astype(np.float64))

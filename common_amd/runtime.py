@@ -1039,6 +1039,43 @@ class ZMatrix(object):
         self.ctx.synchronize()
         return binder, vi, int(valid.item())
 
+    def partition_refine(self, starts, max_sweeps=20, max_clusters=None, order=None):
+        """Greedy refinement of partitions under Binder's loss (msc_zmatrix_partition_refine; starts as partition_sums
+        takes candidates).  From each start rows move one at a time to the cluster, or into a new one, that lowers
+        binder_num most, sweep after sweep (positions ascending, or in `order`, a permutation of [0, m)), until a sweep
+        moves nothing or max_sweeps have run.  max_clusters: the most clusters a partition may hold on the way (None:
+        min(m, ZMATRIX_REFINE_MAX_CLUSTERS)); a start that holds more raises ValueError.  Returns device tensors (labels
+        int32 [nstarts, m] over the selected rows, numbered by first row; binder_num int64 [nstarts]; sweeps int32
+        [nstarts], the last one that moved nothing included; moves int64 [nstarts]), bit-equal to
+        query.refine_partition on the host.  Asynchronous; flushes the staged samples first."""
+        s2, ns, ld = self._vectors(starts)
+        if max_clusters is None:
+            max_clusters = min(self.m, L.ZMATRIX_REFINE_MAX_CLUSTERS)
+        max_sweeps, max_clusters = int(max_sweeps), int(max_clusters)
+        if max_sweeps < 0 or max_sweeps >= 2 ** 32:
+            raise ValueError("max_sweeps must lie in [0, 2^32)")
+        if max_clusters < 1 or max_clusters > self.m:
+            raise ValueError("max_clusters must lie in [1, m = %d]" % self.m)
+        o = self._order(order)
+        dev = self.ctx.torch_device
+        if ns and self.m <= L.ZMATRIX_REFINE_MAX_ROWS and max_clusters <= L.ZMATRIX_REFINE_MAX_CLUSTERS:
+            # the clusters of every start over the selected rows, counted before anything is launched
+            sel = s2.reshape(ns, -1) if self._rows is None else \
+                s2.reshape(ns, -1)[:, torch.from_numpy(self._rows.astype(np.int64)).to(dev)]
+            srt = torch.sort(sel, dim=1).values
+            most = int(((srt[:, 1:] != srt[:, :-1]).sum(dim=1) + 1).max())
+            if most > max_clusters:
+                raise ValueError("a start holds %d clusters, more than max_clusters = %d" % (most, max_clusters))
+        labels = torch.empty((ns, self.m), dtype=torch.int32, device=dev)
+        binder = torch.empty(ns, dtype=torch.int64, device=dev)
+        sweeps = torch.empty(ns, dtype=torch.int32, device=dev)
+        moves = torch.empty(ns, dtype=torch.int64, device=dev)
+        L.check(self.ctx.lib.msc_zmatrix_partition_refine(
+            self._h, C.c_void_p(s2.data_ptr()), ns, ld, max_sweeps, max_clusters,
+            None if o is None else o.ctypes.data_as(C.c_void_p), C.c_void_p(labels.data_ptr()),
+            C.c_void_p(binder.data_ptr()), C.c_void_p(sweeps.data_ptr()), C.c_void_p(moves.data_ptr())))
+        return labels, binder, sweeps, moves
+
     @property
     def nsamples(self):
         self._check_open()

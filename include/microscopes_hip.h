@@ -883,6 +883,46 @@ int msc_zmatrix_partition_sums(msc_zmatrix *zm, const int32_t *cand_dev, uint32_
                                uint64_t *w_dev, uint32_t *size_dev);
 int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
                                int64_t *binder_num_dev, double *vi_lb_dev, uint64_t *valid_dev);
+/*
+ * Greedy refinement of partitions under Binder's loss: from each start, rows move one at a time to the cluster (or to a
+ * new one) that lowers binder_num most, sweep after sweep, until a sweep moves nothing.  With C, V and the layout of a
+ * candidate as above, a start is start_dev + s * ld (ld >= n), position a carrying start[s][rows[a]]; only equality of
+ * labels is used.  The rule (the device and common_amd.query's host path implement exactly this; all integer):
+ *   ids      a start's labels over the positions are renumbered from 0 in the order of each label's first position;
+ *            1 <= max_clusters <= m is the id capacity and n_k the number of positions with id k.
+ *   a sweep  visits the positions in ascending order, or in host_order (nullable: a permutation of [0, m), read before
+ *            the call returns).  For position a with id c:  n'_k = n_k - [k == c],  s_k = the sum of C[a][b] over the
+ *            b != a with id k (uint64),  g_k = 2 s_k - V n'_k (int64) for every k with n'_k > 0,  g_cur = g_c if
+ *            n'_c > 0 and 0 otherwise (a is alone already).
+ *   target   (1) the existing cluster k (n'_k > 0) of the largest g_k, the lowest id among equals, if g_k > g_cur
+ *            strictly: gain g_k;  (2) else, if n'_c > 0, 0 > g_cur and some id f < max_clusters has n_f == 0, a moves
+ *            alone into the lowest such f: gain 0;  (3) else a stays.  Ties keep a row where it is, and an existing
+ *            cluster is preferred to a new one at equal gain.
+ *   a move   lowers binder_num by exactly gain - g_cur > 0, so the process ends.  Sweeps repeat until one makes no move
+ *            or max_sweeps have run (0 is allowed: the outputs describe the start).
+ * Outputs, device pointers, each nullable: labels_dev [nstarts][m] int32 over the positions, numbered from 0 in the order
+ * of first position; binder_num_dev [nstarts], the start's value less the decreases (what msc_zmatrix_partition_loss
+ * gives for the output labels); sweeps_dev [nstarts], the sweeps run, the last one that moved nothing included;
+ * moves_dev [nstarts], all moves.  Starts are independent: any split of them over calls gives the same outputs.
+ * Like msc_zmatrix_partition_loss the call first updates the counts with the staged samples, otherwise leaves the
+ * accumulator as it was, and is asynchronous on the context's stream: one launch per sweep (one workgroup per start; a
+ * start that has converged returns at once) with no wait in between up to 64 sweeps; beyond 64 the host waits once per
+ * 64 further sweeps to see whether any start still moves.  Caps: m <= 32768 and max_clusters <= 1024 (16-bit ids, sizes
+ * and bins of s_k in LDS); beyond them MSC_EUNSUPPORTED before anything is launched, as when m (m - 1) / 2 x
+ * nsamples does not fit 63 bits.  MSC_EINVAL: no sample yet, nstarts == 0, ld < n, a null handle or start_dev,
+ * host_order not a permutation, max_clusters 0 or above m.  A start with more than max_clusters clusters is found on
+ * the device after the gather: it is not refined, its outputs mean nothing, and the failure surfaces as MSC_EDEVICE at
+ * the next synchronising or launching call (the accumulator itself stays good).  Workspaces the accumulator owns,
+ * allocated at the first call, beside those of msc_zmatrix_partition_loss: a dense copy of the counts, m x 4 ceil(m / 4)
+ * u32 (m = 16384: 1 GiB; m = 32768: 4 GiB), written once per call, and chunk x 4 ceil(m / 4) 16-bit ids: MSC_ENOMEM
+ * when they cannot be allocated.  msc_last_kernel(2) names the instantiation of the sweep kernel (its LDS id capacity, the 16-byte loads a thread has in
+ * flight, and whether nsamples x m < 2^32 let it keep s_k in 32-bit bins instead of 64-bit ones).
+ * The variation-of-information bound is not refined: its gains are floats, and a tie decided in the last ulp would
+ * change the trajectory.
+ */
+int msc_zmatrix_partition_refine(msc_zmatrix *zm, const int32_t *start_dev, uint32_t nstarts, uint64_t ld,
+                                 uint32_t max_sweeps, uint32_t max_clusters, const uint32_t *host_order,
+                                 int32_t *labels_dev, int64_t *binder_num_dev, uint32_t *sweeps_dev, uint64_t *moves_dev);
 /* zero the counts and drop the staged samples (asynchronous); destroy frees everything the accumulator allocated */
 int msc_zmatrix_reset(msc_zmatrix *zm);
 int msc_zmatrix_destroy(msc_zmatrix *zm);
