@@ -35,6 +35,9 @@ ZMATRIX_MAX_LABELS = 1 << 16          # ... and nlabels at most
 ZMATRIX_REFINE_MAX_ROWS = 1 << 15     # msc_zmatrix_partition_refine: m at most
 ZMATRIX_REFINE_MAX_CLUSTERS = 1 << 10 # ... and max_clusters at most
 LINKAGE_MAX_N = 1 << 16               # msc_linkage_single: n at most
+DISTANCES_MAX_ROWS = 1 << 15          # msc_partition_distances: m at most
+DISTANCES_MAX_CLUSTERS = 1 << 10      # ... and clusters a partition at most
+DISTANCES_LDS_CELLS = 15 * 1024       # ... and the cells K_a x K_b of a pair whose table stays in LDS
 
 
 class MicroscopesHipError(RuntimeError):
@@ -191,6 +194,8 @@ _SIGS = {
     "msc_zmatrix_reset": (C.c_int, [C.c_void_p]),
     "msc_zmatrix_destroy": (C.c_int, [C.c_void_p]),
     "msc_linkage_single": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "msc_partition_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
+                                          C.c_uint32, C.c_uint32] + [C.c_void_p] * 8),
 }
 
 EXPORTS = tuple(sorted(_SIGS))

@@ -104,7 +104,7 @@ static int device_error_word(int device, volatile uint32_t **host_out) {
     MSC_HIP(hipHostGetDevicePointer(&d, h, 0));
     uint32_t *w = static_cast<uint32_t *>(d);
     if (bind_error_word_score(w) || bind_error_word_sweep(w) || bind_error_word_state(w) || bind_error_word_seq(w) ||
-        bind_error_word_query(w) || bind_error_word_refine(w))
+        bind_error_word_query(w) || bind_error_word_refine(w) || bind_error_word_distance(w))
       return fail(MSC_EHIP, "binding the device error word failed: %s", hipGetErrorString(hipGetLastError()));
     words[device] = h;
   }
@@ -127,7 +127,8 @@ static int device_error_check(msc_context *ctx) {
   if (code & 8u) add("msc_sweep_sequential: an order entry >= nrows (visit skipped; detail: entry), or a leave from an empty group or counter (detail: group)");
   if (code & 16u) add("msc_zmatrix_add: a label outside [0, nlabels) (that sample was skipped; detail: row of z)");
   if (code & 32u) add("msc_zmatrix_partition_refine: a start with more than max_clusters clusters (its outputs mean nothing; detail: start of its chunk)");
-  if (code & ~63u) add("unknown device-side error");
+  if (code & 64u) add("msc_partition_distances: a partition with more than 1024 clusters (every output it takes part in is -1 or NaN; detail: its index in its set)");
+  if (code & ~127u) add("unknown device-side error");
   return fail(MSC_EDEVICE, "reported by an earlier kernel on device %d: %s [detail of the first: %u]; rebuild the affected state's tables",
               ctx->device, what.c_str(), detail);
 }
@@ -4303,5 +4304,106 @@ extern "C" int msc_linkage_single(msc_context *ctx, const float *z_dev, uint64_t
   MSC_HIP(hipStreamSynchronize(s));
   MSC_TRY(device_error_check(ctx));
   if (host_linkage || host_order) linkage::finish(edges.data(), n, host_linkage, host_order);
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// distances between partitions (kernels_distance.hip)
+// ---------------------------------------------------------------------------
+template <typename T>
+static int pd_reserve(msc_context *ctx, DevBuf<T> &buf, size_t n, const char *what) {
+  const hipError_t e = reserve_synced(ctx->stream, buf, n);
+  if (e == hipSuccess) return MSC_OK;
+  (void)hipGetLastError();
+  return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "msc_partition_distances: the %s of %zu bytes: %s", what,
+              n * sizeof(T), hipGetErrorString(e));
+}
+
+// which launches a block of partitions with cluster counts ka[0..na) x kb[0..nb) needs (route_pd_table decides per pair)
+static void pd_block_routes(const uint32_t *ka, uint32_t na, const uint32_t *kb, uint32_t nb, bool *lds, bool *global) {
+  uint32_t lo_a = kPdBad, hi_a = 0, lo_b = kPdBad, hi_b = 0;
+  bool bad = false;
+  for (uint32_t i = 0; i < na; i++)
+    if (ka[i] == kPdBad) bad = true; else lo_a = std::min(lo_a, ka[i]), hi_a = std::max(hi_a, ka[i]);
+  for (uint32_t j = 0; j < nb; j++)
+    if (kb[j] == kPdBad) bad = true; else lo_b = std::min(lo_b, kb[j]), hi_b = std::max(hi_b, kb[j]);
+  const bool any = hi_a != 0 && hi_b != 0;                  // a pair of two good partitions
+  *lds = bad || (any && route_pd_table(lo_a, lo_b) == PdRoute::lds);
+  *global = any && route_pd_table(hi_a, hi_b) == PdRoute::global;
+}
+
+extern "C" int msc_partition_distances(msc_context *ctx, const int32_t *a_dev, uint64_t lda, uint32_t na,
+                                       const int32_t *b_dev, uint64_t ldb, uint32_t nb, uint32_t m, uint32_t flags,
+                                       int64_t *pairs_ab_dev, double *nlogn_ab_dev, int64_t *pairs_a_dev,
+                                       double *nlogn_a_dev, uint32_t *nclusters_a_dev, int64_t *pairs_b_dev,
+                                       double *nlogn_b_dev, uint32_t *nclusters_b_dev) {
+  const char *who = "msc_partition_distances";
+  MSC_REQUIRE(ctx && a_dev, "%s: null argument", who);
+  MSC_REQUIRE(flags == 0, "%s: flags = %u (none is defined)", who, flags);
+  const bool mirror = b_dev == nullptr;
+  if (mirror) b_dev = a_dev, ldb = lda, nb = na;
+  MSC_REQUIRE(na > 0 && nb > 0 && m > 0, "%s: na = %u, nb = %u, m = %u: none may be 0", who, na, nb, m);
+  MSC_REQUIRE(lda >= m && ldb >= m, "%s: lda = %llu, ldb = %llu below m = %u", who, (unsigned long long)lda,
+              (unsigned long long)ldb, m);
+  if (m > kPdMaxRows)
+    return fail(MSC_EUNSUPPORTED, "%s: m = %u: at most %u rows (16-bit ids; up to %u clusters a partition)", who, m,
+                kPdMaxRows, kPdMaxClusters);
+  MSC_TRY(device_error_check(ctx));
+  MSC_HIP(hipSetDevice(ctx->device));
+  const hipStream_t s = ctx->stream;
+  const uint64_t ldi = ((uint64_t)m + 3u) & ~(uint64_t)3u;
+  MSC_TRY(pd_reserve(ctx, ctx->pd_ids, 2 * (size_t)kPdChunk * ldi, "cluster ids"));
+  MSC_TRY(pd_reserve(ctx, ctx->pd_k, 2 * (size_t)kPdChunk, "cluster counts"));
+  if (ctx->pd_log2_n < m || !ctx->pd_log2) {
+    ctx->pd_log2_n = 0;
+    MSC_TRY(pd_reserve(ctx, ctx->pd_log2, (size_t)m + 1, "table of log2 n"));
+    if (launch_pd_log2(s, ctx->pd_log2, m)) return fail(MSC_EHIP, "k_pd_log2 launch failed");
+    ctx->pd_log2_n = m;
+  }
+  uint16_t *ids_a = ctx->pd_ids, *ids_b = ids_a + (size_t)kPdChunk * ldi;
+  uint32_t *k_a = ctx->pd_k, *k_b = k_a + kPdChunk;
+  // the cluster counts come back to the host, a chunk at a time (one wait each): they say which launches a block needs
+  std::vector<uint32_t> ka_host(kPdChunk), kb_host(nb);
+  for (uint32_t a0 = 0; a0 < na; a0 += kPdChunk) {
+    const uint32_t nac = std::min(kPdChunk, na - a0);
+    if (launch_pd_canon(s, a_dev + (uint64_t)a0 * lda, lda, m, nac, ctx->pd_log2, a0, ids_a, ldi, k_a,
+                        pairs_a_dev ? pairs_a_dev + a0 : nullptr, nlogn_a_dev ? nlogn_a_dev + a0 : nullptr,
+                        nclusters_a_dev ? nclusters_a_dev + a0 : nullptr))
+      return fail(MSC_EHIP, "k_pd_canon launch failed");
+    MSC_HIP(hipMemcpyAsync(ka_host.data(), k_a, (size_t)nac * 4, hipMemcpyDeviceToHost, s));
+    MSC_HIP(hipStreamSynchronize(s));
+    for (uint32_t b0 = 0; b0 < nb; b0 += kPdChunk) {
+      const uint32_t nbc = std::min(kPdChunk, nb - b0);
+      const bool first = a0 == 0;                            // of this chunk of b: its own outputs are written now
+      if (mirror && !first && b0 + nbc <= a0) continue;      // (every pair of the block is another block's mirror image)
+      if (launch_pd_canon(s, b_dev + (uint64_t)b0 * ldb, ldb, m, nbc, ctx->pd_log2, b0, ids_b, ldi, k_b,
+                          first && pairs_b_dev ? pairs_b_dev + b0 : nullptr,
+                          first && nlogn_b_dev ? nlogn_b_dev + b0 : nullptr,
+                          first && nclusters_b_dev ? nclusters_b_dev + b0 : nullptr))
+        return fail(MSC_EHIP, "k_pd_canon launch failed");
+      if (first) {
+        MSC_HIP(hipMemcpyAsync(kb_host.data() + b0, k_b, (size_t)nbc * 4, hipMemcpyDeviceToHost, s));
+        MSC_HIP(hipStreamSynchronize(s));
+      }
+      if (!pairs_ab_dev && !nlogn_ab_dev) continue;
+      if (mirror && b0 + nbc <= a0) continue;
+      bool lds = false, global = false;
+      pd_block_routes(ka_host.data(), nac, kb_host.data() + b0, nbc, &lds, &global);
+      PdPairArgs p;
+      p.ids_a = ids_a, p.ids_b = ids_b, p.ldi = ldi, p.k_a = k_a, p.k_b = k_b;
+      p.m = m, p.na = nac, p.nb = nbc, p.a0 = a0, p.b0 = b0, p.ldo = nb, p.mirror = mirror ? 1u : 0u;
+      p.log2tab = ctx->pd_log2, p.table = nullptr, p.pairs_ab = pairs_ab_dev, p.nlogn_ab = nlogn_ab_dev;
+      if (global) {
+        if (!ctx->pd_table) {
+          const size_t cells = (size_t)kPdSlices * kPdSliceCells;
+          MSC_TRY(pd_reserve(ctx, ctx->pd_table, cells, "contingency tables"));
+          MSC_HIP(hipMemsetAsync(ctx->pd_table, 0, cells * 4, s));
+        }
+        p.table = ctx->pd_table;
+        if (launch_pd_pairs(s, ctx->num_cus, PdRoute::global, p)) return fail(MSC_EHIP, "k_pd_pairs launch failed");
+      }
+      if (lds && launch_pd_pairs(s, ctx->num_cus, PdRoute::lds, p)) return fail(MSC_EHIP, "k_pd_pairs launch failed");
+    }
+  }
   return MSC_OK;
 }

@@ -18,6 +18,7 @@ enum : uint32_t {
                                      // empty group (the row only joins) or from an empty counter of a feature (detail = group)
   MSC_DEVERR_ZMATRIX_LABEL = 16u,    // k_zm_check: a label outside [0, nlabels) (the sample is skipped); detail = row of z
   MSC_DEVERR_REFINE_CLUSTERS = 32u,  // k_zm_refine_init: a start with more than max_clusters clusters (it is not refined); detail = start
+  MSC_DEVERR_DISTANCE_CLUSTERS = 64u, // k_pd_canon: a partition with more than 1024 clusters (its outputs are -1 / NaN); detail = its index in its set
 };
 
 static __device__ uint32_t *g_dev_error = nullptr;

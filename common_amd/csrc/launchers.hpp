@@ -369,4 +369,43 @@ int launch_zm_refine_finish(hipStream_t stream, const uint16_t *ids, uint64_t ld
 // of linkage::shape_for(n) (linkage_host.hpp); edges[3 i ..] = (x, y, distance) of step i.  -2: n outside [2, 65536]
 int launch_linkage_prim(hipStream_t stream, const float *z, uint64_t ld, uint32_t n, double *edges);
 
+// kernels_distance.hip (msc_partition_distances): partitions are canonicalised a chunk of kPdChunk at a time into 16-bit
+// ids [chunk][ldi] (ldi = m rounded up to 4) and cluster counts k (kPdBad: more than kPdMaxClusters, reported as
+// MSC_DEVERR_DISTANCE_CLUSTERS); the pair kernel then takes a block of a chunk of a against a chunk of b.  A pair's
+// contingency table lives where route_pd_table says -- the one place that picks: in LDS while K_a K_b cells fit, else in
+// the workgroup's slice of a global workspace of kPdSlices x kPdSliceCells u32 (zeroed when allocated; the kernel leaves
+// it zero).  launch_pd_pairs(route) computes the pairs of the block that take `route` and leaves the others alone; the
+// LDS launch also writes -1 / NaN for the pairs of a kPdBad partition.  -2: a shape the launcher does not take
+constexpr uint32_t kPdMaxRows = kZmRefineMaxRows;
+constexpr uint32_t kPdMaxClusters = kZmRefineMaxClusters;
+constexpr uint32_t kPdBad = 0xFFFFFFFFu;
+constexpr uint32_t kPdChunk = 256;
+constexpr uint32_t kPdTile = 8;                              // b's a work item of the pair kernel takes
+constexpr uint32_t kPdLdsCells = 15u * 1024u;                // 60 KiB of the 64 a workgroup declares; the rest holds the partial sums
+constexpr uint32_t kPdSliceCells = kPdMaxClusters * kPdMaxClusters;
+constexpr uint32_t kPdSlices = 128;
+enum class PdRoute { lds, global };
+__host__ __device__ inline PdRoute route_pd_table(uint32_t ka, uint32_t kb) {
+  return (uint64_t)ka * kb <= kPdLdsCells ? PdRoute::lds : PdRoute::global;
+}
+struct PdPairArgs {
+  const uint16_t *ids_a, *ids_b;   // [na][ldi], [nb][ldi]
+  uint64_t ldi;
+  const uint32_t *k_a, *k_b;       // cluster counts of the block's partitions
+  uint32_t m, na, nb;              // rows; partitions of the block
+  uint32_t a0, b0;                 // the block's first partitions in their sets
+  uint64_t ldo;                    // row stride of the outputs: the whole nb
+  uint32_t mirror;                 // b is a: pairs with b0 + j < a0 + i are left out, the others are written twice
+  const double *log2tab;           // [m + 1]
+  uint32_t *table;                 // the global workspace (null on the LDS route)
+  int64_t *pairs_ab;               // [.][ldo], nullable
+  double *nlogn_ab;
+};
+int bind_error_word_distance(uint32_t *word_dev);
+int launch_pd_log2(hipStream_t stream, double *tab, uint32_t n);
+int launch_pd_canon(hipStream_t stream, const int32_t *lab, uint64_t ld, uint32_t m, uint32_t nparts, const double *log2tab,
+                    uint32_t part0, uint16_t *ids, uint64_t ldi, uint32_t *k, int64_t *pairs, double *nlogn,
+                    uint32_t *nclusters);
+int launch_pd_pairs(hipStream_t stream, int num_cus, PdRoute route, const PdPairArgs &p);
+
 }  // namespace msc

@@ -500,6 +500,13 @@ struct msc_context {
   volatile uint32_t *err_host = nullptr;
   // msc_linkage_single: the chain's edges, 3 (n - 1) doubles, kept between calls
   msc::DevBuf<double> linkage_edges;
+  // msc_partition_distances, kept between calls: the ids and cluster counts of a chunk of a and a chunk of b, log2 n for
+  // n <= pd_log2_n, and the contingency tables of the pairs that do not fit LDS (zeroed once; the kernel leaves them zero)
+  msc::DevBuf<uint16_t> pd_ids;
+  msc::DevBuf<uint32_t> pd_k;
+  msc::DevBuf<double> pd_log2;
+  uint32_t pd_log2_n = 0;
+  msc::DevBuf<uint32_t> pd_table;
 };
 
 struct msc_dataview {

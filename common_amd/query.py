@@ -12,13 +12,19 @@ Ghahramani) among candidate partitions, from exact integer sums over the co-clus
 ``msc_zmatrix_partition_*`` on the device, the same integers on both.  ``refine_partition`` takes partitions further by
 greedy row moves under Binder's loss until no single move helps (``msc_zmatrix_partition_refine`` on the device, plain
 numpy on the host, the same trajectory bit for bit), and ``point_estimate(refine=...)`` refines the best candidates.
+``partition_distances`` is what the counts cannot give: Binder's distance and the variation of information between every
+partition of one set and every partition of another (``msc_partition_distances`` on the device, ``np.unique`` and a
+contingency table per pair on the host, the same integers on both).  ``adjusted_rand``, ``expected_loss`` (the EXACT
+posterior expected VI of candidates, where ``partition_loss`` has a bound), ``vi_estimate`` and ``credible_ball`` (Wade and
+Ghahramani's credible ball around an estimate) are built on it; they take the samples themselves.
 """
+import math
 import collections
 
 import numpy as np
 import torch
 
-from ._lib import LINKAGE_MAX_N, ZMATRIX_MAX_LABELS, ZMATRIX_REFINE_MAX_CLUSTERS
+from ._lib import DISTANCES_MAX_CLUSTERS, LINKAGE_MAX_N, ZMATRIX_MAX_LABELS, ZMATRIX_REFINE_MAX_CLUSTERS
 from .runtime import Context, ZMatrix
 
 _HOST_CHUNK_FLOATS = 1 << 23      # one-hot block of the numpy path: at most 64 MiB of float64
@@ -617,3 +623,250 @@ def point_estimate(assignments, loss="binder", candidates=None, ctx=None, refine
         return PointEstimate(_renumber(sc.selected(c[index])), index, losses, confidence)
     finally:
         sc.close()
+
+
+# ---- distances between partitions: the exact expected VI, credible balls, adjusted Rand ---------------------------------
+PartitionDistances = collections.namedtuple("PartitionDistances", ["binder", "vi", "pairs_ab", "nclusters_a", "nclusters_b"])
+ExpectedLoss = collections.namedtuple("ExpectedLoss", ["binder_num", "vi", "valid"])
+CredibleBall = collections.namedtuple("CredibleBall", ["distances", "radius", "members", "horizontal", "upper", "lower",
+                                                       "nclusters"])
+_METRICS = ("vi", "binder")
+_HOST_TABLE_CELLS = 1 << 16       # a pair's contingency table is a bincount up to this many cells (or 8 m), np.unique beyond
+
+
+def _host_partitions(p, name="partitions"):
+    """an integer array [count, m], neither 0, of partitions given as a vector, a list of vectors or an array"""
+    if not isinstance(p, (np.ndarray, torch.Tensor)):
+        p = [np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in p]
+    p = np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p)
+    if p.ndim == 1:
+        p = p.reshape(1, -1)
+    if p.ndim != 2 or p.shape[0] == 0 or p.shape[1] == 0:
+        raise ValueError("empty %s" % name)
+    if not np.issubdtype(p.dtype, np.integer):
+        raise ValueError("%s must hold integer labels" % name)
+    return p
+
+
+def _nlogn(counts):
+    """sum n log2 n over positive counts, ascending: the same bits for a pair and for the pair the other way round"""
+    c = np.sort(counts).astype(np.float64)
+    return float(np.sum(c * np.log2(c)))
+
+
+def _pairs(counts):
+    c = counts.astype(np.int64)
+    return int(np.sum(c * (c - 1) // 2))
+
+
+def _canon_host(p):
+    """per partition: (ids int64 [m], K, pairs, nlogn)"""
+    out = []
+    for row in p:
+        u, inv = np.unique(row, return_inverse=True)
+        inv = inv.reshape(-1).astype(np.int64)
+        sizes = np.bincount(inv, minlength=u.size)
+        out.append((inv, int(u.size), _pairs(sizes), _nlogn(sizes)))
+    return out
+
+
+def _sums_host(a, b):
+    """the outputs of msc_partition_distances in plain numpy (b None: a against itself); no cap on clusters or rows"""
+    ca = _canon_host(a)
+    cb = ca if b is None else _canon_host(b)
+    m = a.shape[1]
+    pairs_ab = np.empty((len(ca), len(cb)), dtype=np.int64)
+    nlogn_ab = np.empty((len(ca), len(cb)), dtype=np.float64)
+    for i, (ia, ka, _, _) in enumerate(ca):
+        for j, (ib, kb, _, _) in enumerate(cb):
+            if b is None and j < i:
+                pairs_ab[i, j], nlogn_ab[i, j] = pairs_ab[j, i], nlogn_ab[j, i]
+                continue
+            key = ia * kb + ib
+            if ka * kb <= max(_HOST_TABLE_CELLS, 8 * m):
+                cells = np.bincount(key, minlength=ka * kb)
+                cells = cells[cells > 0]
+            else:
+                cells = np.unique(key, return_counts=True)[1]
+            pairs_ab[i, j], nlogn_ab[i, j] = _pairs(cells), _nlogn(cells)
+    per = lambda c: (np.array([x[2] for x in c], dtype=np.int64), np.array([x[3] for x in c], dtype=np.float64),
+                     np.array([x[1] for x in c], dtype=np.int32))
+    return (pairs_ab, nlogn_ab) + per(ca) + per(cb)
+
+
+def _distance_sums(a, b, ctx):
+    """(the eight outputs of msc_partition_distances, m, on the device?) of partitions given as partition_distances takes
+    them"""
+    device = ctx is not None or _is_device(a) or _is_device(b) or \
+        any(not isinstance(x, (np.ndarray, torch.Tensor)) and x is not None and any(_is_device(v) for v in x) for x in (a, b))
+    if not device:
+        a = _host_partitions(a)
+        if b is not None:
+            b = _host_partitions(b)
+            if b.shape[1] != a.shape[1]:
+                raise ValueError("partitions of different numbers of rows: %d and %d" % (a.shape[1], b.shape[1]))
+        return _sums_host(a, b), a.shape[1], False
+    if ctx is None:
+        first = next(x for x in (a, b) if x is not None and (_is_device(x) or not isinstance(x, (np.ndarray, torch.Tensor))))
+        t = first if isinstance(first, torch.Tensor) else next(v for v in first if _is_device(v))
+        ctx = _context_of(t, None)
+    m = int(a.shape[-1]) if isinstance(a, (np.ndarray, torch.Tensor)) else len(a[0])
+    da = _device_candidates(a, ctx, m)
+    db = None
+    if b is not None:
+        mb = int(b.shape[-1]) if isinstance(b, (np.ndarray, torch.Tensor)) else len(b[0])
+        if mb != m:
+            raise ValueError("partitions of different numbers of rows: %d and %d" % (m, mb))
+        db = _device_candidates(b, ctx, m)
+    return ctx.partition_distances(da, db), m, True
+
+
+def _binder_vi(sums, m):
+    pairs_ab, nlogn_ab, pairs_a, nlogn_a, _, pairs_b, nlogn_b, _ = sums
+    binder = pairs_a[:, None] + pairs_b[None, :] - 2 * pairs_ab
+    vi = (nlogn_a[:, None] + nlogn_b[None, :] - 2. * nlogn_ab) / float(m)
+    return binder, vi
+
+
+def partition_distances(a, b=None, ctx=None):
+    """Distances between every partition of ``a`` and every partition of ``b`` (``None``: of ``a`` again), all labelling
+    the same m rows: vectors, lists of vectors or [count, m] arrays of integer labels; only equality of labels is used.
+
+    With n_ij the contingency counts of a pair, a_i and b_j the cluster sizes and C(n, 2) = n (n - 1) / 2:
+    ``pairs_ab = sum C(n_ij, 2)``; ``binder = sum C(a_i, 2) + sum C(b_j, 2) - 2 pairs_ab``, the row pairs that one
+    partition joins and the other separates, an exact integer; ``vi = (sum a_i log2 a_i + sum b_j log2 b_j -
+    2 sum n_ij log2 n_ij) / m``, the variation of information in bits, a metric, 0 iff the partitions are equal.
+    Returns a named tuple ``(binder int64 [na, nb], vi float64 [na, nb], pairs_ab int64 [na, nb], nclusters_a int32 [na],
+    nclusters_b int32 [nb])``.
+
+    Numpy input without ``ctx`` runs on the host -- ``np.unique`` per partition and a contingency table per pair, no cap
+    on clusters or rows -- and returns numpy arrays.  Device tensors, or ``ctx=``, run ``msc_partition_distances`` (at most
+    %d clusters a partition, more raise ``ValueError``; at most 32768 rows) and return device tensors: the same integers,
+    ``vi`` within rounding of the host's (the sum of m terms log2 n, each within an ulp)."""
+    sums, m, _ = _distance_sums(a, b, ctx)
+    binder, vi = _binder_vi(sums, m)
+    return PartitionDistances(binder, vi, sums[0], sums[4], sums[7])
+
+
+partition_distances.__doc__ %= DISTANCES_MAX_CLUSTERS
+
+
+def adjusted_rand(a, b=None, ctx=None):
+    """The adjusted Rand index of every partition of ``a`` against every partition of ``b`` (as ``partition_distances``
+    takes them; typically ``b`` is one known labelling): float64 [na, nb], ``(pairs_ab - E) / ((pairs_a + pairs_b) / 2 -
+    E)`` with ``E = pairs_a pairs_b / C(m, 2)``, in float64 from the exact integers of ``partition_distances``; 1.0 where
+    the denominator is 0 (both partitions all-in-one, or both all singletons).  1 for equal partitions, about 0 for
+    independent ones."""
+    sums, m, device = _distance_sums(a, b, ctx)
+    pairs_ab, pairs_a, pairs_b = sums[0], sums[2], sums[5]
+    total = m * (m - 1) // 2
+    if device:
+        f = lambda x: x.to(torch.float64)
+        where, full = torch.where, torch.ones_like(f(pairs_ab))
+    else:
+        f = lambda x: x.astype(np.float64)
+        where, full = np.where, np.ones(pairs_ab.shape, dtype=np.float64)
+    pa, pb = f(pairs_a)[:, None], f(pairs_b)[None, :]
+    E = pa * pb / float(total) if total > 0 else 0. * pa * pb
+    den = (pa + pb) / 2. - E
+    safe = where(den == 0, full, den)
+    return where(den == 0, full, (f(pairs_ab) - E) / safe)
+
+
+def _samples_for_distances(assignments, ctx):
+    """(samples [S, m], the context or None) of assignment vectors given as zmatrix takes them"""
+    if isinstance(assignments, ZMatrix):
+        raise ValueError("a ZMatrix keeps counts, not samples: the exact expected losses need the assignment vectors")
+    _check_assignments(assignments)
+    if _on_device(assignments, ctx):
+        if ctx is None:
+            t = assignments if isinstance(assignments, torch.Tensor) else next(a for a in assignments if _is_device(a))
+            ctx = _context_of(t, None)
+        return _device_samples(assignments, ctx)
+    a = _host_samples(assignments)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("assignment vectors must hold integer labels")
+    return a, None
+
+
+def _expected(samples, cands, ctx):
+    """ExpectedLoss of candidates against samples, both already where they run"""
+    S = int(samples.shape[0])
+    d = partition_distances(cands, None if cands is samples else samples, ctx=ctx)
+    if ctx is None:
+        return ExpectedLoss(d.binder.sum(axis=1), np.cumsum(d.vi, axis=1)[:, -1] / float(S), S)
+    # the sum over the samples in sample order, as the host adds: a running sum in float64 (a device scan has its own tree)
+    vi = np.cumsum(d.vi.cpu().numpy(), axis=1)[:, -1] / float(S)
+    return ExpectedLoss(d.binder.sum(dim=1), torch.from_numpy(vi).to(d.vi.device), S)
+
+
+def expected_loss(assignments, candidates=None, ctx=None):
+    """The EXACT posterior expected losses of candidate partitions, from the samples themselves: a named tuple
+    ``(binder_num int64 [ncand], vi float64 [ncand], valid)``.
+
+    ``binder_num[c] = sum_s binder(c, s)`` -- the integer ``partition_loss`` gives, from another direction -- and ``vi[c] =
+    (1 / S) sum_s vi(c, s)``, the posterior expected variation of information in bits (``partition_loss`` has only its
+    Jensen bound ``vi_lb``: ``vi[c] >= vi_lb[c] + (1 / (m S)) sum_s sum_i s_i log2 s_i`` over the samples' cluster sizes).
+    The sum over the samples runs in sample order and the division by S = ``valid`` last, in float64.
+    ``assignments`` as for ``zmatrix`` (an open ``ZMatrix`` keeps no samples and raises ``ValueError``); ``candidates``
+    as for ``partition_loss``, ``None`` for the samples themselves.  Runs and returns where ``partition_distances`` would."""
+    samples, ctx = _samples_for_distances(assignments, ctx)
+    m = int(samples.shape[1])
+    if candidates is None:
+        cands = samples
+    else:
+        cands = _device_candidates(candidates, ctx, m) if ctx is not None else _host_candidates(candidates, m)
+    return _expected(samples, cands, ctx)
+
+
+def vi_estimate(assignments, candidates=None, ctx=None):
+    """ONE clustering out of posterior samples by the exact expected variation of information: ``point_estimate`` with
+    ``expected_loss``'s ``vi`` where ``loss="vi"`` has the bound.  Returns the same ``PointEstimate`` tuple of numpy
+    values: ``labels`` of the winner (numbered by first row), ``index`` (the lowest among equal losses), ``losses`` (the
+    expected VI of every candidate, bits) and ``confidence`` as ``point_estimate`` computes it."""
+    samples, ctx = _samples_for_distances(assignments, ctx)
+    sc = _Scorer(samples, ctx)
+    try:
+        c = sc.candidates(candidates)
+        vi = _expected(samples, c, ctx).vi
+        losses = vi.cpu().numpy() if isinstance(vi, torch.Tensor) else np.asarray(vi)
+        index = int(np.argmin(losses))
+        w, size = sc.sums(c[index:index + 1])
+        valid = int(samples.shape[0])
+        confidence = w[0].astype(np.float64) / (float(valid) * size[0].astype(np.float64))
+        return PointEstimate(_renumber(sc.selected(c[index])), index, losses, confidence)
+    finally:
+        sc.close()
+
+
+def credible_ball(assignments, estimate, level=0.95, metric="vi", ctx=None):
+    """Wade and Ghahramani's credible ball around ``estimate`` (``mcclust.ext::credibleball``): the smallest ball, in the
+    ``metric`` (``"vi"`` in bits or ``"binder"`` in row pairs), that holds at least ``level`` of the samples.
+
+    With ``d[s]`` the distance from ``estimate`` to sample s: ``radius`` is the ceil(level S)-th smallest ``d`` (1-based);
+    ``members`` is ``d <= radius``; ``horizontal`` the members at the largest distance; ``upper`` the members with the
+    fewest clusters and, among those, the largest distance; ``lower`` the members with the most clusters and, among
+    those, the largest distance -- each an ascending array of sample indices.  Returns a named tuple of numpy values
+    ``(distances [S], radius, members bool [S], horizontal, upper, lower, nclusters int32 [S])``.  ``assignments`` as for
+    ``expected_loss``; ``estimate``: one vector of m labels.  Runs where ``partition_distances`` would."""
+    if metric not in _METRICS:
+        raise ValueError("metric must be one of %s" % (_METRICS,))
+    level = float(level)
+    if not (0. < level <= 1.):
+        raise ValueError("level must lie in (0, 1]")
+    samples, ctx = _samples_for_distances(assignments, ctx)
+    m, S = int(samples.shape[1]), int(samples.shape[0])
+    est = _device_candidates(estimate, ctx, m) if ctx is not None else _host_candidates(estimate, m)
+    if est.shape[0] != 1:
+        raise ValueError("estimate must be one vector of labels")
+    got = partition_distances(est, samples, ctx=ctx)
+    d, k = (got.vi if metric == "vi" else got.binder)[0], got.nclusters_b
+    d = d.cpu().numpy() if isinstance(d, torch.Tensor) else np.asarray(d)
+    k = k.cpu().numpy() if isinstance(k, torch.Tensor) else np.asarray(k)
+    rank = min(S, max(1, int(math.ceil(level * S))))
+    radius = np.sort(d)[rank - 1]
+    members = d <= radius
+    idx = np.flatnonzero(members)
+    farthest = lambda sel: sel[d[sel] == d[sel].max()]
+    return CredibleBall(d, radius, members, farthest(idx), farthest(idx[k[idx] == k[idx].min()]),
+                        farthest(idx[k[idx] == k[idx].max()]), k)

@@ -88,7 +88,7 @@ class Context(object):
 
     def last_kernel(self, which="score"):
         """the kernel instantiation of this process's most recent scoring ("score") or fused assignment ("sweep") pass, or
-        z-matrix or linkage kernel ("zmatrix"), as rocprofv3 spells it (msc_last_kernel): what bench.py keys the committed counter
+        z-matrix, linkage or partition-distance kernel ("zmatrix"), as rocprofv3 spells it (msc_last_kernel): what bench.py keys the committed counter
         summaries by"""
         return self.lib.msc_last_kernel({"score": 0, "zmatrix": 2, "marginal": 3}.get(which, 1)).decode()
 
@@ -110,6 +110,54 @@ class Context(object):
                                             None if lk is None else lk.ctypes.data_as(C.c_void_p),
                                             None if od is None else od.ctypes.data_as(C.c_void_p)))
         return lk, (None if od is None else od.astype(np.int32))
+
+    def _partitions(self, p, name):
+        """(tensor, count, ld, m) of partitions given as an int32 tensor [m] or [count, m] with contiguous rows"""
+        if not isinstance(p, torch.Tensor) or p.dtype != torch.int32 or p.device != self.torch_device:
+            raise ValueError("%s must be an int32 tensor on %s" % (name, self.torch_device))
+        if p.dim() == 1:
+            p = p.reshape(1, -1)
+        if p.dim() != 2 or p.shape[0] == 0 or p.shape[1] == 0:
+            raise ValueError("%s must be [m] or [count, m], neither 0" % name)
+        m = int(p.shape[1])
+        ld = int(p.stride(0)) if p.shape[0] > 1 else m
+        if (m > 1 and p.stride(1) != 1) or ld < m:
+            raise ValueError("%s must have contiguous rows (row stride >= m)" % name)
+        return p, int(p.shape[0]), ld, m
+
+    def partition_distances(self, a, b=None):
+        """The contingency sums of every partition of a against every partition of b (msc_partition_distances): int32
+        tensors [m] or [count, m] on this device whose rows are contiguous (any row stride >= m); any int32 value is a
+        label.  b None: a against itself.  Returns device tensors (pairs_ab int64 [na, nb], nlogn_ab float64 [na, nb],
+        pairs_a int64 [na], nlogn_a float64 [na], nclusters_a int32 [na], pairs_b, nlogn_b, nclusters_b), as
+        include/microscopes_hip.h defines them; common_amd.query makes Binder's distance, the variation of information
+        and the adjusted Rand index of them.  At most %d clusters a partition: counted before anything is launched, more
+        raise ValueError.  More than %d rows: MicroscopesHipError (MSC_EUNSUPPORTED)."""
+        a2, na, lda, m = self._partitions(a, "a")
+        if b is None:
+            b2, nb, ldb = None, na, lda
+        else:
+            b2, nb, ldb, mb = self._partitions(b, "b")
+            if mb != m:
+                raise ValueError("a and b must label the same rows: m = %d and %d" % (m, mb))
+        if m <= L.DISTANCES_MAX_ROWS:
+            for p in (a2,) if b2 is None else (a2, b2):
+                srt = torch.sort(p, dim=1).values
+                most = int(((srt[:, 1:] != srt[:, :-1]).sum(dim=1) + 1).max())
+                if most > L.DISTANCES_MAX_CLUSTERS:
+                    raise ValueError("a partition holds %d clusters, more than %d" % (most, L.DISTANCES_MAX_CLUSTERS))
+        dev = self.torch_device
+        pairs_ab = torch.empty((na, nb), dtype=torch.int64, device=dev)
+        nlogn_ab = torch.empty((na, nb), dtype=torch.float64, device=dev)
+        per = []
+        for n in (na, nb):
+            per += [torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                    torch.empty(n, dtype=torch.int32, device=dev)]
+        L.check(self.lib.msc_partition_distances(
+            self._h, C.c_void_p(a2.data_ptr()), lda, na, None if b2 is None else C.c_void_p(b2.data_ptr()), ldb, nb, m, 0,
+            C.c_void_p(pairs_ab.data_ptr()), C.c_void_p(nlogn_ab.data_ptr()), *[C.c_void_p(t.data_ptr()) for t in per]))
+        return (pairs_ab, nlogn_ab) + tuple(per)
+    partition_distances.__doc__ %= (L.DISTANCES_MAX_CLUSTERS, L.DISTANCES_MAX_ROWS)
 
     def value_op(self, family, dim, op, hp, ss_record, value=None):
         """One group::{add_value, remove_value, score_value, score_data} call (base.hpp:25-28) as a batch

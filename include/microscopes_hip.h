@@ -88,7 +88,8 @@ const char *msc_build_info(void); /* "gfx950 hipcc <ver> ..." */
 /*
  * Which kernel INSTANTIATION the library chose for this process's most recent scoring pass (which = 0: msc_score_value)
  * or fused assignment pass (which = 1: msc_sweep_assign / msc_sweep_step), or the most recent kernel of the z-matrix
- * accumulator or of its linkage (which = 2: msc_zmatrix_*, msc_linkage_single), or the kernel that reduced the rows of the most recent row predictive pass
+ * accumulator, of its linkage or of the partition distances (which = 2: msc_zmatrix_*, msc_linkage_single,
+ * msc_partition_distances' pair kernel), or the kernel that reduced the rows of the most recent row predictive pass
  * (which = 3: msc_score_marginal), spelled as rocprofv3 spells it, e.g.
  * "k_score_tile_roles<false, false, false>" ("" before the first such call).  Measurement tooling only: bench.py keys the
  * committed counter summaries (profiles/ *_pmc.json) by it, so that a roofline figure is always the figure of the kernel
@@ -950,6 +951,47 @@ int msc_zmatrix_destroy(msc_zmatrix *zm);
  */
 int msc_linkage_single(msc_context *ctx, const float *z_dev, uint64_t ld, uint32_t n, uint32_t flags,
                        double *host_linkage, uint32_t *host_order);
+
+/* ---- distances between partitions: what the exact expected VI, credible balls and the adjusted Rand index are made of ---- */
+/*
+ * Every partition of one set against every partition of another.  Partition i of a is a_dev + i * lda, partition j of b is
+ * b_dev + j * ldb (lda, ldb >= m): int32 labels of the same m rows; only equality of labels is used, any int32 value is a
+ * label.  b_dev == NULL: a against itself (ldb and nb are ignored, nb = na, and the b outputs repeat the a outputs).
+ * For partitions a and b write n_ij for the contingency counts (rows with label i in a and label j in b), a_i and b_j for
+ * the cluster sizes, C(n, 2) = n (n - 1) / 2.  The call writes
+ *   pairs_ab = sum_ij C(n_ij, 2),  pairs_a = sum_i C(a_i, 2),  pairs_b likewise            exact int64
+ *   nlogn_ab = sum_ij n_ij log2 n_ij,  nlogn_a = sum_i a_i log2 a_i,  nlogn_b likewise     float64
+ *   nclusters_a, nclusters_b                                                               the numbers of clusters
+ * from which (common_amd.query does this arithmetic)
+ *   binder(a, b) = pairs_a + pairs_b - 2 pairs_ab: the row pairs that one partition joins and the other separates, an
+ *                  exact integer;
+ *   vi(a, b)     = (nlogn_a + nlogn_b - 2 nlogn_ab) / m: the variation of information in bits, a metric, 0 iff a = b;
+ *   ari(a, b)    = (pairs_ab - E) / ((pairs_a + pairs_b) / 2 - E),  E = pairs_a pairs_b / C(m, 2), in float64 from the
+ *                  integers, defined as 1.0 where the denominator is 0.
+ * With n(r) the count of row r's own cell, sum_r (n(r) - 1) = 2 pairs_ab and sum_r log2 n(r) = nlogn_ab: the kernel counts
+ * the rows into a table, lets every row read its own cell back and never walks the cells.  nlogn_ab is that sum of m terms
+ * log2 n(r) (each within an ulp), in an order and a reduction tree that m alone fixes: the same arguments give the same
+ * bits; any split of a or of b over calls gives the same bits; (a, b) and (b, a) give the same bits; and so do the two
+ * places the table may live in (LDS while K_a K_b <= 15360 cells, else a global workspace; msc_last_kernel(2) names the
+ * pair kernel that ran last: threads, steps of four rows a thread, LDS or not).  nlogn_a is summed over the clusters in
+ * the order of their first rows.
+ * Outputs are device pointers: pairs_ab_dev, nlogn_ab_dev [na][nb] (either may be NULL; both NULL: no pair is computed);
+ * pairs_a_dev, nlogn_a_dev, nclusters_a_dev [na] and the same three for b [nb], each nullable.
+ * Caps: m <= 32768, MSC_EUNSUPPORTED above, before anything is launched; at most 1024 clusters a partition.  A partition
+ * with more is found on the device: every output it takes part in is written as -1 (uint32: all ones) or NaN and the
+ * failure surfaces as MSC_EDEVICE at the next synchronising or launching call.  MSC_EINVAL: a null ctx or a_dev, na, nb or
+ * m equal to 0, lda or ldb below m, flags != 0 (none is defined).
+ * The outputs are written asynchronously on the context's stream.  Partitions are taken 256 of a against 256 of b at a
+ * time; the host waits once for the cluster counts of each chunk (4 bytes a partition), which say which of the two
+ * kernels a block needs.  Workspaces the context owns, allocated at first use and kept: 2 x 256 x 4 ceil(m / 4) 16-bit
+ * ids, m + 1 doubles of log2 n, and -- from the first pair that does not fit LDS -- 128 tables of 4 MiB, zeroed once
+ * (the kernel leaves them zero).  MSC_ENOMEM when they cannot be allocated.
+ */
+int msc_partition_distances(msc_context *ctx, const int32_t *a_dev, uint64_t lda, uint32_t na,
+                            const int32_t *b_dev, uint64_t ldb, uint32_t nb, uint32_t m, uint32_t flags,
+                            int64_t *pairs_ab_dev, double *nlogn_ab_dev,
+                            int64_t *pairs_a_dev, double *nlogn_a_dev, uint32_t *nclusters_a_dev,
+                            int64_t *pairs_b_dev, double *nlogn_b_dev, uint32_t *nclusters_b_dev);
 
 #ifdef __cplusplus
 }
