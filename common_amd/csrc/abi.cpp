@@ -1283,9 +1283,6 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
       hipError_t e = hipMemcpy(h.hp_dev, h.hp.data(), h.hp.size() * sizeof(float), hipMemcpyHostToDevice);
       if (e != hipSuccess) return fail(MSC_EHIP, "hp upload failed: %s", hipGetErrorString(e));
     }
-    h.raw_valid = true;
-    h.additive_valid = true;   // both all-zero
-    h.derived_valid = false;
     FeatDesc &d = st->desc_host[f];
     std::memset(&d, 0, sizeof d);
     d.family = h.family;
@@ -1309,7 +1306,7 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
     d.aux = 0.0;
     for (float a : h.hp) d.aux += h.family == MSC_DD || h.family == MSC_DM ? (double)a : 0.0;
   }
-  st->cnt_additive_valid = true;
+  st->valid.created(nfeatures);       // (raw and additive both all-zero)
   MSC_TRY(upload_desc(st.get()));
   hipError_t e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) return fail(MSC_EHIP, "state init failed: %s", hipGetErrorString(e));
@@ -1337,6 +1334,21 @@ extern "C" int msc_state_shape(const msc_state *st, uint32_t *nfeatures, uint32_
   return MSC_OK;
 }
 
+// dd / dm: the sum of the feature's alphas (FeatDesc::aux) follows its host hp block, in every host copy of the
+// descriptor; whether the family carries one.  The device side is the caller's: msc_state_set_hp uploads, hp_installed
+// does not (the kernel wrote it).
+static bool refresh_alpha_sum(msc_state *st, uint32_t feature) {
+  const msc_feature_host &h = st->feats[feature];
+  if (h.family != MSC_DD && h.family != MSC_DM) return false;
+  double asum = 0;
+  for (float a : h.hp) asum += (double)a;
+  st->desc_host[feature].aux = asum;
+  for (auto *v : {&st->desc_tile_host, &st->desc_fuse_host, &st->desc_acc_host})
+    for (FeatDesc &d : *v)
+      if (d.hp == h.hp_dev) d.aux = asum;
+  return true;
+}
+
 extern "C" int msc_state_set_hp(msc_state *st, uint32_t feature, const float *host_hp, size_t nfloats) {
   MSC_REQUIRE(st && host_hp, "null argument");
   MSC_REQUIRE(feature < st->nfeat, "feature %u out of range", feature);
@@ -1344,18 +1356,12 @@ extern "C" int msc_state_set_hp(msc_state *st, uint32_t feature, const float *ho
   MSC_REQUIRE(nfloats == h.hp.size(), "feature %u: hp block has %zu floats, expected %zu", feature,
               nfloats, h.hp.size());
   std::copy(host_hp, host_hp + nfloats, h.hp.begin());
-  st->blk_drawn = false;
+  st->valid.hp_changed(feature);
   if (nfloats) {
     MSC_HIP(hipMemcpyAsync(h.hp_dev, h.hp.data(), nfloats * sizeof(float), hipMemcpyHostToDevice, st->ctx->stream));
     MSC_HIP(hipStreamSynchronize(st->ctx->stream));
   }
-  h.derived_valid = false;
-  if (h.family == MSC_DD || h.family == MSC_DM) {
-    double asum = 0;
-    for (float a : h.hp) asum += (double)a;
-    st->desc_host[feature].aux = asum;
-    MSC_TRY(upload_desc(st));
-  }
+  if (refresh_alpha_sum(st, feature)) MSC_TRY(upload_desc(st));
   return MSC_OK;
 }
 
@@ -1370,7 +1376,6 @@ extern "C" int msc_state_get_hp(const msc_state *st, uint32_t feature, float *ho
 }
 
 static int launch_commit_all(msc_state *st) {
-  st->blk_drawn = false;                                   // (the fields change: a blocked draw made from them is stale)
   if (launch_commit(st->ctx->stream, st->desc_dev, (int)st->nfeat, st->kpad, st->red_i64, st->cnt_u32))
     return fail(MSC_EHIP, "k_commit launch failed");
   for (uint32_t f = 0; f < st->nfeat; f++)
@@ -1381,12 +1386,16 @@ static int launch_commit_all(msc_state *st) {
 }
 
 static int ensure_raw(msc_state *st) {
-  bool any = false;
-  for (auto &h : st->feats) any |= !h.raw_valid;
-  if (!any) return MSC_OK;
+  if (!st->valid.any_raw_stale()) return MSC_OK;
   MSC_TRY(launch_commit_all(st));
-  for (auto &h : st->feats) { h.raw_valid = true; h.derived_valid = false; }
-  st->crp_valid = false;
+  st->valid.committed();
+  return MSC_OK;
+}
+
+// refuses a call between msc_sweep_step_begin and msc_state_commit_reduce
+static int refuse_mid_step(const msc_state *st, const char *entry) {
+  MSC_REQUIRE(!st->rng_bump_pending, "%s between msc_sweep_step_begin and msc_state_commit_reduce: the additive tables "
+                                     "hold one rank's uncommitted sums", entry);
   return MSC_OK;
 }
 
@@ -1407,7 +1416,7 @@ extern "C" int msc_state_set_ss(msc_state *st, uint32_t feature, uint32_t first_
   MSC_REQUIRE(nbytes == rec * ngroups, "expected %zu bytes of records, got %zu", rec * ngroups, nbytes);
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(ensure_raw(st));
-  st->blk_drawn = false;
+  st->valid.fields_written(feature);
   if (h.family == MSC_NIW) {
     // record = {u32 count, f32 sum_x[d], f32 sum_xxT[d*d]}; device keeps count as a row and the
     // float block group-major
@@ -1422,8 +1431,6 @@ extern "C" int msc_state_set_ss(msc_state *st, uint32_t feature, uint32_t first_
     MSC_HIP(hipMemcpyAsync(h.raw_u32 + first_group, cnt.data(), 4 * (size_t)ngroups, hipMemcpyHostToDevice, st->ctx->stream));
     MSC_HIP(hipMemcpyAsync(h.raw_f32 + nf * first_group, blk.data(), 4 * nf * ngroups, hipMemcpyHostToDevice, st->ctx->stream));
     MSC_HIP(hipStreamSynchronize(st->ctx->stream));
-    h.additive_valid = false;
-    h.derived_valid = false;
     return MSC_OK;
   }
   uint32_t nu32, nf32;
@@ -1444,8 +1451,6 @@ extern "C" int msc_state_set_ss(msc_state *st, uint32_t feature, uint32_t first_
     MSC_HIP(hipMemcpyAsync(h.raw_f32 + (size_t)i * st->kpad + first_group, &sf[(size_t)i * ngroups],
                            4 * (size_t)ngroups, hipMemcpyHostToDevice, st->ctx->stream));
   MSC_HIP(hipStreamSynchronize(st->ctx->stream));
-  h.additive_valid = false;
-  h.derived_valid = false;
   return MSC_OK;
 }
 
@@ -1498,8 +1503,7 @@ extern "C" int msc_state_set_alpha(msc_state *st, float alpha) {
   MSC_REQUIRE(st, "null state");
   MSC_REQUIRE(alpha > 0.f, "alpha must be positive (group_manager.hpp:78)");
   st->alpha = alpha;
-  st->crp_valid = false;
-  st->blk_drawn = false;
+  st->valid.alpha_changed();
   return MSC_OK;
 }
 
@@ -1516,9 +1520,7 @@ extern "C" int msc_state_set_group_counts(msc_state *st, const uint32_t *host_co
   MSC_TRY(ensure_raw(st));
   MSC_HIP(hipMemcpyAsync(st->cnt_u32, host_counts, 4 * (size_t)ngroups, hipMemcpyHostToDevice, st->ctx->stream));
   MSC_HIP(hipStreamSynchronize(st->ctx->stream));
-  st->cnt_additive_valid = false;
-  st->crp_valid = false;
-  st->blk_drawn = false;
+  st->valid.counts_changed();
   return MSC_OK;
 }
 
@@ -1665,7 +1667,7 @@ static int bind_dm_column(msc_state *st, uint32_t f, const msc_dataview *view, u
     MSC_HIP(hipMemcpyAsync(h.dm_meta_dev, h.dm_meta.data(), sizeof(uint32_t) * meta.size(), hipMemcpyHostToDevice, s));
     MSC_HIP(hipStreamSynchronize(s));
     d.dm_meta = h.dm_meta_dev;
-    h.derived_valid = false;
+    st->valid.derived_dropped(f);
   }
   return MSC_OK;
 }
@@ -1725,7 +1727,7 @@ static int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *co
       const uint32_t vcap = (uint32_t)std::min<long long>(col_max_of(st, f, view, c) + 1, (long long)kGpMaxTable);
       if (vcap != st->desc_host[f].vcap) {
         st->desc_host[f].vcap = vcap;
-        st->feats[f].derived_valid = false;
+        st->valid.derived_dropped(f);
       }
     }
     if (h.family == MSC_DM) MSC_TRY(bind_dm_column(st, f, view, c));
@@ -1771,30 +1773,53 @@ static uint32_t prepare_value_slices(const msc_state *st) {
 
 static int ensure_derived(msc_state *st) {
   MSC_TRY(ensure_raw(st));
-  bool any = false;
-  for (auto &h : st->feats) any |= !h.derived_valid;
-  if (!any) return MSC_OK;
+  if (!st->valid.any_derived_stale()) return MSC_OK;
   if (launch_prepare(st->ctx->stream, st->desc_dev, st->nfeat, st->kpad, prepare_value_slices(st)))
     return fail(MSC_EHIP, "k_prepare launch failed");
   for (uint32_t f = 0; f < st->nfeat; f++)
-    if (st->feats[f].family == MSC_NIW && !st->feats[f].derived_valid &&
+    if (st->feats[f].family == MSC_NIW && st->valid.derived_stale(f) &&
         launch_niw_prepare(st->ctx->stream, st->desc_dev, f, st->feats[f].dim, st->K, st->kpad))
       return fail(MSC_EHIP, "k_niw_prepare launch failed");
   for (uint32_t f = 0; f < st->nfeat; f++)
-    if (st->feats[f].family == MSC_DM && !st->feats[f].derived_valid && st->desc_host[f].dm_meta != nullptr &&
+    if (st->feats[f].family == MSC_DM && st->valid.derived_stale(f) && st->desc_host[f].dm_meta != nullptr &&
         launch_dm_prepare(st->ctx->stream, st->desc_dev, (int)f, st->feats[f].dim, st->kpad, dm_value_slices(st->feats[f])))
       return fail(MSC_EHIP, "k_dm_prepare launch failed");
-  for (auto &h : st->feats) h.derived_valid = true;
+  st->valid.prepared();
   return MSC_OK;
 }
 
 static int ensure_crp(msc_state *st) {
   MSC_TRY(ensure_raw(st));
-  if (st->crp_valid) return MSC_OK;
+  if (!st->valid.crp_stale()) return MSC_OK;
   if (launch_crp_prepare(st->ctx->stream, st->cnt_u32, st->K, st->kpad, st->alpha, st->logpc))
     return fail(MSC_EHIP, "k_crp_prepare launch failed");
-  st->crp_valid = true;
+  st->valid.crp_prepared();
   return MSC_OK;
+}
+
+// the raw tables lifted into the additive ones where those are stale: the features in their order, then the counts
+// (niw lifts through its commit kernel run backwards)
+static int ensure_additive(msc_state *st) {
+  MSC_TRY(ensure_raw(st));
+  hipStream_t s = st->ctx->stream;
+  for (uint32_t f = 0; f < st->nfeat; f++)
+    if (st->valid.additive_stale(f)) {
+      const int rc = st->feats[f].family == MSC_NIW
+                         ? launch_niw_commit(s, st->desc_dev, f, st->feats[f].dim, st->K, st->kpad, 0)
+                         : launch_lift(s, st->desc_dev + f, 1, st->kpad, st->red_i64, st->cnt_u32, 0);
+      if (rc) return fail(MSC_EHIP, "k_lift launch failed");
+    }
+  if (st->valid.counts_additive_stale() && launch_lift(s, st->desc_dev, 0, st->kpad, st->red_i64, st->cnt_u32, 1))
+    return fail(MSC_EHIP, "k_lift launch failed");
+  st->valid.additive_lifted();
+  return MSC_OK;
+}
+
+// every table current: the reference's fields, the additive sums, the score constants, the CRP terms
+static int ensure_all_current(msc_state *st) {
+  MSC_TRY(ensure_additive(st));
+  MSC_TRY(ensure_derived(st));
+  return ensure_crp(st);
 }
 
 // ---------------------------------------------------------------------------
@@ -2118,8 +2143,7 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
 
 static int commit(msc_state *st) {
   MSC_TRY(launch_commit_all(st));
-  for (auto &h : st->feats) { h.raw_valid = true; h.derived_valid = false; }
-  st->crp_valid = false;
+  st->valid.committed();
   return MSC_OK;
 }
 
@@ -2129,7 +2153,6 @@ enum : uint32_t { kAccZeroed = 0x100, kAccThenPrepare = 0x200 };
 
 static int commit_and_prepare(msc_state *st, bool bump_rng = true) {
   hipStream_t s = st->ctx->stream;
-  st->blk_drawn = false;
   if (launch_commit_prepare(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, st->red_i64, st->cnt_u32, st->alpha,
                             st->logpc, bump_rng ? st->rng_dev : nullptr, prepare_value_slices(st)))
     return fail(MSC_EHIP, "k_commit_prepare launch failed");
@@ -2142,8 +2165,7 @@ static int commit_and_prepare(msc_state *st, bool bump_rng = true) {
         launch_dm_prepare(s, st->desc_dev, (int)f, h.dim, st->kpad, dm_value_slices(h)))
       return fail(MSC_EHIP, "k_dm_prepare launch failed");
   }
-  for (auto &h : st->feats) { h.raw_valid = true; h.derived_valid = true; }
-  st->crp_valid = true;
+  st->valid.committed_and_prepared();
   return MSC_OK;
 }
 
@@ -2151,25 +2173,13 @@ static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32
                            uint64_t nrows, const int32_t *z_dev, uint32_t flags) {
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   hipStream_t s = st->ctx->stream;
-  st->blk_drawn = false;
   if (flags & MSC_ACC_RESET) {
     if (!(flags & kAccZeroed) && launch_zero64(s, st->red_i64, st->n_i64, st->red_f64, st->n_f64))
       return fail(MSC_EHIP, "k_zero64 launch failed");
+    st->valid.additive_lifted();                            // (zeroed: what this call sums into)
   } else {
-    MSC_TRY(ensure_raw(st));
-    for (uint32_t f = 0; f < st->nfeat; f++)
-      if (!st->feats[f].additive_valid) {
-        const int rc = st->feats[f].family == MSC_NIW
-                           ? launch_niw_commit(s, st->desc_dev, f, st->feats[f].dim, st->K, st->kpad, 0)
-                           : launch_lift(s, st->desc_dev + f, 1, st->kpad, st->red_i64, st->cnt_u32, 0);
-        if (rc) return fail(MSC_EHIP, "k_lift launch failed");
-      }
-    if (!st->cnt_additive_valid)
-      if (launch_lift(s, st->desc_dev, 0, st->kpad, st->red_i64, st->cnt_u32, 1))
-        return fail(MSC_EHIP, "k_lift launch failed");
+    MSC_TRY(ensure_additive(st));
   }
-  for (auto &h : st->feats) h.additive_valid = true;
-  st->cnt_additive_valid = true;
   if (nrows > 0) {
     const int rc = launch_accumulate(s, st->ctx->num_cus, st->desc_acc_dev, st->desc_acc_host.data(), (int)st->desc_acc_host.size(),
                                      st->K, st->kpad, row0, nrows, z_dev,
@@ -2185,7 +2195,7 @@ static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32
         return fail(MSC_EHIP, "niw accumulate launch failed");
     }
   }
-  for (auto &h : st->feats) h.raw_valid = false;
+  st->valid.accumulated();
   if (flags & kAccThenPrepare) return commit_and_prepare(st);
   if (!(flags & MSC_ACC_NO_COMMIT)) MSC_TRY(commit(st));
   return MSC_OK;
@@ -2205,8 +2215,7 @@ extern "C" int msc_entity_op(msc_state *st, const msc_dataview *view, const uint
   MSC_REQUIRE(st && view, "null argument");
   MSC_REQUIRE(sign != 0, "sign must be +1 (join) or -1 (leave)");
   MSC_REQUIRE(group < st->K, "group %u outside [0,%u)", group, st->K);
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_entity_op between msc_sweep_step_begin and msc_state_commit_reduce: the additive "
-                                     "tables hold uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_entity_op"));
   MSC_TRY(device_error_check(st->ctx));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(bind_view(st, view, cols, row, 1));
@@ -2222,20 +2231,11 @@ extern "C" int msc_entity_op(msc_state *st, const msc_dataview *view, const uint
     return MSC_OK;
   }
   // every table current before, every table current after
-  MSC_TRY(ensure_raw(st));
-  for (uint32_t f = 0; f < st->nfeat; f++)
-    if (!st->feats[f].additive_valid && launch_lift(s, st->desc_dev + f, 1, st->kpad, st->red_i64, st->cnt_u32, 0))
-      return fail(MSC_EHIP, "k_lift launch failed");
-  if (!st->cnt_additive_valid && launch_lift(s, st->desc_dev, 0, st->kpad, st->red_i64, st->cnt_u32, 1))
-    return fail(MSC_EHIP, "k_lift launch failed");
-  for (auto &h : st->feats) h.additive_valid = true;
-  st->cnt_additive_valid = true;
-  MSC_TRY(ensure_derived(st));
-  MSC_TRY(ensure_crp(st));
-  st->blk_drawn = false;
+  MSC_TRY(ensure_all_current(st));
   if (launch_entity_op(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row, group, sign > 0 ? 1 : -1, st->red_i64, st->cnt_u32,
                        st->alpha, st->logpc, z_dev ? z_dev + row : nullptr))
     return fail(MSC_EHIP, "k_entity_op launch failed");
+  st->valid.kept_current();
   return MSC_OK;
 }
 
@@ -2494,32 +2494,13 @@ extern "C" int msc_sweep_assign(msc_state *st, const msc_dataview *view, const u
 static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                            uint64_t nrows, const int32_t *z_dev, uint32_t flags);
 
-// everything the host tracks about which device tables are current; a captured step must leave it as it found it
-typedef std::vector<uint8_t> StepFlags;
-static StepFlags save_flags(const msc_state *st) {
-  StepFlags f;
-  for (auto &h : st->feats) f.push_back((uint8_t)(h.raw_valid | (h.additive_valid << 1) | (h.derived_valid << 2)));
-  f.push_back((uint8_t)(st->cnt_additive_valid | (st->crp_valid << 1) | (st->rng_valid << 2)));
-  return f;
-}
-static void restore_flags(msc_state *st, const StepFlags &f) {
-  for (size_t i = 0; i < st->feats.size(); i++) {
-    st->feats[i].raw_valid = f[i] & 1;
-    st->feats[i].additive_valid = (f[i] >> 1) & 1;
-    st->feats[i].derived_valid = (f[i] >> 2) & 1;
-  }
-  st->cnt_additive_valid = f.back() & 1;
-  st->crp_valid = (f.back() >> 1) & 1;
-  st->rng_valid = (f.back() >> 2) & 1;
-}
-
 extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                               uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
   MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
   hipStream_t s = st->ctx->stream;
-  st->blk_drawn = false;                                  // (a replayed graph passes none of the functions that say so)
+  st->valid.step_began();
   auto eager = [&]() -> int {
     st->step_graph.n_eager++;
     bool zeroed = false;
@@ -2549,7 +2530,9 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
     g.seen = 0;
   }
   const bool next_sweep = st->rng_valid && st->rng_seed == seed && st->rng_sweep == sweep;
-  const StepFlags entry = save_flags(st);
+  // (which device tables are current, and the random stream's pair: a captured step must leave both as it found them)
+  const TableValidity::Snapshot entry = st->valid.snapshot();
+  const bool rng_was_valid = st->rng_valid;
   if (g.exec) {
     if (!next_sweep || entry != g.flags) return eager();
     MSC_HIP(hipGraphLaunch(g.exec, s));
@@ -2580,7 +2563,8 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
   g.n_eager--;                      // (recorded, not run)
   hipGraph_t graph = nullptr;
   const hipError_t ec = hipStreamEndCapture(ctx->record_stream, &graph);
-  bool ok = rc == MSC_OK && ec == hipSuccess && graph != nullptr && save_flags(st) == entry;
+  bool ok = rc == MSC_OK && ec == hipSuccess && graph != nullptr && st->valid.snapshot() == entry &&
+            st->rng_valid == rng_was_valid;
   if (ok && hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
     g.exec = nullptr;
     ok = false;
@@ -2591,7 +2575,8 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
     (void)hipGetLastError();
     if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
     g.disabled = true;
-    restore_flags(st, entry);
+    st->valid.restore(entry);
+    st->rng_valid = rng_was_valid;
     st->rng_sweep = sweep_before;
     return eager();
   }
@@ -2679,27 +2664,16 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
                                     uint32_t nsweeps, uint64_t seed, uint64_t sweep, int32_t *trace_dev) {
   MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
   MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_sweep_sequential between msc_sweep_step_begin and msc_state_commit_reduce: the "
-                                     "additive tables hold uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_sweep_sequential"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
   const SeqRoute route = route_sequential(st);
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   if (nrows == 0 || nsweeps == 0) return MSC_OK;
-  st->blk_drawn = false;
-  // every table current before (as msc_entity_op): the reference's fields, the additive sums, score constants, CRP terms
+  // every table current before (as msc_entity_op)
   hipStream_t s = st->ctx->stream;
-  MSC_TRY(ensure_raw(st));
-  for (uint32_t f = 0; f < st->nfeat; f++)
-    if (!st->feats[f].additive_valid && launch_lift(s, st->desc_dev + f, 1, st->kpad, st->red_i64, st->cnt_u32, 0))
-      return fail(MSC_EHIP, "k_lift launch failed");
-  if (!st->cnt_additive_valid && launch_lift(s, st->desc_dev, 0, st->kpad, st->red_i64, st->cnt_u32, 1))
-    return fail(MSC_EHIP, "k_lift launch failed");
-  for (auto &h : st->feats) h.additive_valid = true;
-  st->cnt_additive_valid = true;
-  MSC_TRY(ensure_derived(st));
-  MSC_TRY(ensure_crp(st));
+  MSC_TRY(ensure_all_current(st));
   const uint64_t visits = (uint64_t)nsweeps * nrows;
   const uint64_t per_launch = (uint64_t)std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / seq_visit_us(st)));
   for (uint64_t v0 = 0; v0 < visits; v0 += per_launch) {
@@ -2710,9 +2684,7 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
     if (rc) return fail(MSC_EHIP, "k_sweep_seq launch failed: %s", hipGetErrorString(hipGetLastError()));
   }
   // the kernel kept every table current: additive sums, fields, constants, counts and CRP terms
-  for (auto &h : st->feats) { h.raw_valid = true; h.additive_valid = true; h.derived_valid = true; }
-  st->cnt_additive_valid = true;
-  st->crp_valid = true;
+  st->valid.kept_current();
   return MSC_OK;
 }
 
@@ -2726,27 +2698,41 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
 //   staged  up to 256 features: the workgroup's row values staged in LDS once, [feature][row] -- 256 rows a workgroup up
 //           to 32 features, 128 up to 64, 64 beyond (32 KiB at most, 64 KiB from 129 features on)
 //   global  more features than that: the values re-read from the columns for every eight slots
-struct BlockedRoute { int rc = MSC_OK; const char *why = ""; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
-static BlockedRoute route_blocked(const msc_state *st, uint64_t nrows) {
+// The split-merge move takes the same families and shapes (every kernel adds a row's terms in the same order, so the
+// choice never changes a bit); its staged kernel holds one feature fewer.  who: the caller, as the message names it.
+struct BlockedRoute { int rc = MSC_OK; std::string why; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
+constexpr uint32_t kBlockedStagedMax = 256;             // (at most 32 KiB of LDS a workgroup: several a compute unit)
+constexpr uint32_t kSplitMergeStagedMax = 255;          // (the codes and the waves' sums within 64 KiB of LDS a workgroup)
+static BlockedRoute route_blocked(const msc_state *st, const char *who, uint32_t staged_max) {
   BlockedRoute r;
-  (void)nrows;
   for (const auto &h : st->feats)
     if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
       r.rc = MSC_EUNSUPPORTED;
-      r.why = "the blocked sweep takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
+      r.why = std::string(who) + " takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
       return r;
     }
   if (st->nfeat >= blocked::kStickTag) {
     r.rc = MSC_EUNSUPPORTED;
-    r.why = "the blocked sweep takes fewer than 32767 features";
+    r.why = std::string(who) + " takes fewer than 32767 features";
     return r;
   }
   if (st->nfeat == 1 && st->feats[0].family == MSC_NICH) r.kernel = BlockedKernel::nich1;
-  else if (st->nfeat <= 256) {                          // (at most 32 KiB of LDS a workgroup: several a compute unit)
+  else if (st->nfeat <= staged_max) {
     r.kernel = BlockedKernel::staged;
     r.block = st->nfeat <= 32 ? 256 : st->nfeat <= 64 ? 128 : 64;
   }
   return r;
+}
+static BlockedRoute route_sweep_blocked(const msc_state *st) { return route_blocked(st, "the blocked sweep", kBlockedStagedMax); }
+static BlockedRoute route_splitmerge(const msc_state *st) { return route_blocked(st, "split-merge", kSplitMergeStagedMax); }
+
+// a feature's slices in a state's parameter table (UINT32_MAX: row 0, the log weights), as msc_blocked_tables and
+// msc_split_merge_tables hand them out
+static void blocked_table_slices(const msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
+  const bool w = feature == UINT32_MAX;
+  if (dev) *dev = st->blk_tab + (w ? 0 : (size_t)st->blk_feats_host[feature].slice0 * st->kpad);
+  if (nslices) *nslices = w ? 1u : st->blk_feats_host[feature].nslices;
+  if (ld) *ld = st->kpad;
 }
 
 // the parameter table and the features as the kernels read them (columns from the current binding, if any)
@@ -2805,15 +2791,15 @@ static int blocked_draw_impl(msc_state *st, uint64_t seed, uint64_t sweep) {
   if (launch_blocked_draw(st->ctx->stream, st->blk_feats_dev, st->nfeat, st->K, st->kpad, st->cnt_u32, st->alpha, seed, sweep,
                           st->blk_work, st->blk_tab))
     return MSC_EHIP;
-  st->blk_drawn = true;
+  st->valid.drawn();
   return MSC_OK;
 }
 
 static int blocked_assign_impl(msc_state *st, const BlockedRoute &route, const msc_dataview *view, const uint32_t *cols,
                                uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  MSC_REQUIRE(st->blk_drawn, "msc_blocked_assign: no parameter draw made from the tables as they stand (msc_blocked_draw "
-                             "first; whatever changes tables, hyper-parameters, alpha or group counts makes a draw stale)");
+  MSC_REQUIRE(st->valid.draw_current(), "msc_blocked_assign: no parameter draw made from the tables as they stand (msc_blocked_draw "
+                                        "first; whatever changes tables, hyper-parameters, alpha or group counts makes a draw stale)");
   MSC_TRY(blocked_setup(st));
   if (launch_blocked_assign(st->ctx->stream, route.kernel, route.block, st->blk_feats_dev, (int)st->nfeat, st->blk_tab, st->K,
                             st->kpad, row0, nrows, row_id0, z_dev, seed, sweep))
@@ -2823,12 +2809,11 @@ static int blocked_assign_impl(msc_state *st, const BlockedRoute &route, const m
 
 extern "C" int msc_blocked_draw(msc_state *st, uint64_t seed, uint64_t sweep) {
   MSC_REQUIRE(st, "null state");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_blocked_draw between msc_sweep_step_begin and msc_state_commit_reduce: the "
-                                     "additive tables hold uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_blocked_draw"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_blocked(st, 0);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  const BlockedRoute route = route_sweep_blocked(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   return blocked_draw_impl(st, seed, sweep);
 }
 
@@ -2836,25 +2821,21 @@ extern "C" int msc_blocked_tables(msc_state *st, uint32_t feature, const float *
   MSC_REQUIRE(st, "null state");
   MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
   MSC_HIP(hipSetDevice(st->ctx->device));
-  const BlockedRoute route = route_blocked(st, 0);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  const BlockedRoute route = route_sweep_blocked(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(blocked_setup(st));
-  const bool w = feature == UINT32_MAX;
-  if (dev) *dev = st->blk_tab + (w ? 0 : (size_t)st->blk_feats_host[feature].slice0 * st->kpad);
-  if (nslices) *nslices = w ? 1u : st->blk_feats_host[feature].nslices;
-  if (ld) *ld = st->kpad;
+  blocked_table_slices(st, feature, dev, nslices, ld);
   return MSC_OK;
 }
 
 extern "C" int msc_blocked_assign(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                                   uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
   MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_blocked_assign between msc_sweep_step_begin and msc_state_commit_reduce: the "
-                                     "additive tables hold uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_blocked_assign"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_blocked(st, nrows);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  const BlockedRoute route = route_sweep_blocked(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   return blocked_assign_impl(st, route, view, cols, row0, nrows, row_id0, z_dev, seed, sweep);
 }
 
@@ -2862,12 +2843,11 @@ extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const 
                                  uint64_t row_id0, int32_t *z_dev, uint32_t nsweeps, uint64_t seed, uint64_t sweep,
                                  int32_t *trace_dev, uint32_t *top_slot_dev) {
   MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_sweep_blocked between msc_sweep_step_begin and msc_state_commit_reduce: the "
-                                     "additive tables hold uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_sweep_blocked"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_blocked(st, nrows);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  const BlockedRoute route = route_sweep_blocked(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   hipStream_t s = st->ctx->stream;
   for (uint32_t i = 0; i < nsweeps; i++) {
@@ -2885,32 +2865,8 @@ extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const 
 // The split-merge move (kernels_splitmerge.hip, splitmerge_math.hpp): Metropolis-Hastings proposals that split one group
 // in two or merge two groups, the launch state reached by restricted BLOCKED Gibbs passes over the rows of the two groups.
 // ---------------------------------------------------------------------------
-// Which assign kernel a state takes, and whether the move takes it at all: the families and the shapes of route_blocked
-// (every kernel adds a row's terms in the same order, so the choice never changes a bit).
-struct SplitMergeRoute { int rc = MSC_OK; const char *why = ""; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
-static SplitMergeRoute route_splitmerge(const msc_state *st, uint64_t nrows) {
-  SplitMergeRoute r;
-  (void)nrows;
-  for (const auto &h : st->feats)
-    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
-      r.rc = MSC_EUNSUPPORTED;
-      r.why = "split-merge takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
-      return r;
-    }
-  if (st->nfeat >= blocked::kStickTag) {
-    r.rc = MSC_EUNSUPPORTED;
-    r.why = "split-merge takes fewer than 32767 features";
-    return r;
-  }
-  if (st->nfeat == 1 && st->feats[0].family == MSC_NICH) r.kernel = BlockedKernel::nich1;
-  else if (st->nfeat < 256) {                           // (the codes and the waves' sums within 64 KiB of LDS a workgroup)
-    r.kernel = BlockedKernel::staged;
-    r.block = st->nfeat <= 32 ? 256 : st->nfeat <= 64 ? 128 : 64;
-  }
-  return r;
-}
-
-// the pair state (three slots: the pair's two, and their union for score_data), created at the first call; its
+// (Which assign kernel a state takes, and whether the move takes it at all: route_splitmerge, next to route_blocked.)
+// The pair state (three slots: the pair's two, and their union for score_data), created at the first call; its
 // hyper-parameters and alpha follow the state's before every call
 constexpr uint32_t kSmSlots = 3;
 static int sm_setup(msc_state *st) {
@@ -2937,14 +2893,13 @@ extern "C" int msc_split_merge(msc_state *st, const msc_dataview *view, const ui
                                uint64_t sweep, double *log_dev, int32_t *trace_dev, int32_t *proposed_dev,
                                uint64_t *counters_dev) {
   MSC_REQUIRE(st && view && z_dev, "null argument");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_split_merge between msc_sweep_step_begin and msc_state_commit_reduce: the "
-                                     "additive tables hold uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_split_merge"));
   MSC_REQUIRE(launch_iters <= 1024, "launch_iters %u beyond 1024", launch_iters);
   MSC_REQUIRE(nrows < (1ull << 48), "msc_split_merge takes fewer than 2^48 rows");
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const SplitMergeRoute route = route_splitmerge(st, nrows);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  const BlockedRoute route = route_splitmerge(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   MSC_TRY(ensure_raw(st));                                 // (the group sizes: where a split finds its empty slot)
   MSC_TRY(sm_setup(st));
@@ -2959,9 +2914,7 @@ extern "C" int msc_split_merge(msc_state *st, const msc_dataview *view, const ui
   zero.b = reinterpret_cast<unsigned long long *>(pair->red_f64.get());
   zero.nb = pair->n_f64;
   // the proposals move the group sizes on the device (k_sm_relabel); everything else is rebuilt at the end
-  st->cnt_additive_valid = false;
-  st->crp_valid = false;
-  st->blk_drawn = false;
+  st->valid.counts_changed();
   for (uint32_t p = 0; p < nproposals; p++) {
     const uint64_t sw = sweep + p;
     if (launch_sm_begin(s, z_dev, nrows, row_id0, st->cnt_u32, st->K, seed, sw, st->sm_prop, st->sm_ell, zero)) return MSC_EHIP;
@@ -3001,15 +2954,12 @@ extern "C" int msc_split_merge_tables(msc_state *st, uint32_t feature, const flo
   MSC_REQUIRE(st, "null state");
   MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
   MSC_HIP(hipSetDevice(st->ctx->device));
-  const SplitMergeRoute route = route_splitmerge(st, 0);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  const BlockedRoute route = route_splitmerge(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(sm_setup(st));
   msc_state *pair = st->sm_pair;
   MSC_TRY(blocked_setup(pair));
-  const bool w = feature == UINT32_MAX;
-  if (dev) *dev = pair->blk_tab + (w ? 0 : (size_t)pair->blk_feats_host[feature].slice0 * pair->kpad);
-  if (nslices) *nslices = w ? 1u : pair->blk_feats_host[feature].nslices;
-  if (ld) *ld = pair->kpad;
+  blocked_table_slices(pair, feature, dev, nslices, ld);
   return MSC_OK;
 }
 
@@ -3116,16 +3066,7 @@ extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const 
   hipStream_t s = ctx->stream;
   double visit_us = 0.0;
   for (msc_state *st : ch->states) {
-    MSC_TRY(ensure_raw(st));
-    for (uint32_t f = 0; f < st->nfeat; f++)
-      if (!st->feats[f].additive_valid && launch_lift(s, st->desc_dev + f, 1, st->kpad, st->red_i64, st->cnt_u32, 0))
-        return fail(MSC_EHIP, "k_lift launch failed");
-    if (!st->cnt_additive_valid && launch_lift(s, st->desc_dev, 0, st->kpad, st->red_i64, st->cnt_u32, 1))
-      return fail(MSC_EHIP, "k_lift launch failed");
-    for (auto &h : st->feats) h.additive_valid = true;
-    st->cnt_additive_valid = true;
-    MSC_TRY(ensure_derived(st));
-    MSC_TRY(ensure_crp(st));
+    MSC_TRY(ensure_all_current(st));
     visit_us = std::max(visit_us, seq_visit_us(st));
   }
   // the table of this call (pointers and alpha may have changed since the last one), through the pinned area whose turn it is
@@ -3168,12 +3109,7 @@ extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const 
     if (rc) return fail(MSC_EHIP, "k_sweep_seq_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
   }
   // the kernel kept every table of every member current: additive sums, fields, constants, counts and CRP terms
-  for (msc_state *st : ch->states) {
-    st->blk_drawn = false;
-    for (auto &h : st->feats) { h.raw_valid = true; h.additive_valid = true; h.derived_valid = true; }
-    st->cnt_additive_valid = true;
-    st->crp_valid = true;
-  }
+  for (msc_state *st : ch->states) st->valid.kept_current();
   return MSC_OK;
 }
 
@@ -3201,7 +3137,7 @@ extern "C" int msc_state_reduce_pack(msc_state *st, void **pack_dev, size_t *n_f
 }
 extern "C" int msc_state_reduce_unpack(msc_state *st) {
   MSC_REQUIRE(st, "null state");
-  st->blk_drawn = false;
+  st->valid.additive_rewritten();
   MSC_REQUIRE(st->red_pack, "msc_state_reduce_unpack before msc_state_reduce_pack");
   MSC_HIP(hipSetDevice(st->ctx->device));
   if (launch_pack64(st->ctx->stream, true, st->red_i64, st->n_i64, st->red_f64, st->n_f64, st->red_pack))
@@ -3467,8 +3403,7 @@ extern "C" int msc_hp_grid_destroy(msc_hp_grid *grid) {
 extern "C" int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, double *out_dev) {
   MSC_REQUIRE(grid && out_dev, "null argument");
   msc_state *st = grid->st;
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_hp_grid_score between msc_sweep_step_begin and msc_state_commit_reduce: the "
-              "tables hold one rank's uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_hp_grid_score"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(ensure_raw(st));
   const uint32_t np = grid->job.npoints;
@@ -3491,30 +3426,20 @@ extern "C" int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, do
 static void hp_installed(msc_state *st, uint32_t feature, const float *blk) {
   msc_feature_host &h = st->feats[feature];
   std::copy(blk, blk + h.hp.size(), h.hp.begin());
-  h.derived_valid = false;
-  st->blk_drawn = false;
-  if (h.family == MSC_DD || h.family == MSC_DM) {
-    double asum = 0;
-    for (float a : h.hp) asum += (double)a;
-    st->desc_host[feature].aux = asum;
-    for (auto *v : {&st->desc_tile_host, &st->desc_fuse_host, &st->desc_acc_host})
-      for (FeatDesc &d : *v)
-        if (d.hp == h.hp_dev) d.aux = asum;
-  }
+  st->valid.hp_changed(feature);
+  (void)refresh_alpha_sum(st, feature);
 }
 // the same for alpha, which the device takes from the host at the next call that reads it (msc_state_set_alpha)
 static void alpha_installed(msc_state *st, float alpha) {
-  st->blk_drawn = false;
   st->alpha = alpha;
-  st->crp_valid = false;
+  st->valid.alpha_changed();
 }
 
 extern "C" int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint32_t n, const uint8_t *slots_dev,
                                  uint64_t seed, uint64_t sweep, uint32_t *chosen_host, double *const *scores_dev) {
   MSC_REQUIRE(st && grids && chosen_host, "null argument");
   MSC_REQUIRE(n > 0, "no grids");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_hp_grid_gibbs between msc_sweep_step_begin and msc_state_commit_reduce: the "
-              "tables hold one rank's uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_hp_grid_gibbs"));
   // the feature grids first (one score launch), the alpha grid last; order[j] = the caller's index of job j
   std::vector<uint32_t> order;
   std::vector<bool> seen(st->nfeat + 1, false);
@@ -3615,8 +3540,7 @@ extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32
                             uint64_t seed, uint64_t sweep, float *values_host, uint32_t *evals_host) {
   MSC_REQUIRE(st && coords, "null argument");
   MSC_REQUIRE(n > 0, "no coordinates");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_hp_slice between msc_sweep_step_begin and msc_state_commit_reduce: the tables "
-              "hold one rank's uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_hp_slice"));
   // the targets in order of first appearance (slot nfeat = alpha), each with its entries in the caller's order
   std::vector<int32_t> tix(st->nfeat + 1, -1);
   std::vector<std::vector<uint32_t>> members;
@@ -3737,8 +3661,7 @@ extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const fl
                                const uint8_t *slots_dev, uint64_t seed, uint64_t sweep, uint64_t *evals_host) {
   MSC_REQUIRE(st && features && widths, "null argument");
   MSC_REQUIRE(n > 0, "no features");
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_theta_slice between msc_sweep_step_begin and msc_state_commit_reduce: the "
-              "tables hold one rank's uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_theta_slice"));
   std::vector<bool> seen(st->nfeat, false);
   std::vector<ThetaJob> jobs(n);
   for (uint32_t i = 0; i < n; i++) {
@@ -3772,7 +3695,7 @@ extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const fl
   const uint32_t *bad = reinterpret_cast<const uint32_t *>(down.data() + np * 8);
   int rc = MSC_OK;
   for (uint32_t i = 0; i < n; i++) {
-    st->feats[features[i]].derived_valid = false;     // (p is read by the bbnc prepare and the fused bool tables)
+    st->valid.hp_changed(features[i]);                // (p is read by the bbnc prepare and the fused bool tables)
     uint64_t t = 0;
     uint32_t first_bad = 0xffffffffu;
     for (uint32_t x = 0; x < nb; x++) {
@@ -3819,8 +3742,7 @@ extern "C" int msc_score_marginal(msc_state *st, const msc_dataview *view, const
                                   float *map_logresp_dev) {
   MSC_REQUIRE(st && (logp_dev || nrows == 0), "null argument");
   MSC_REQUIRE(flags == 0, "unknown flags 0x%x", flags);
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_score_marginal between msc_sweep_step_begin and msc_state_commit_reduce: the "
-              "tables hold one rank's uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_score_marginal"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
@@ -3868,8 +3790,7 @@ extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, co
                                      uint32_t flags, uint64_t seed, uint64_t sweep, void *const *out_dev) {
   MSC_REQUIRE(st && view && out_dev, "null argument");
   MSC_REQUIRE((flags & ~MSC_PRED_MASKED_ONLY) == 0, "unknown flags 0x%x", flags);
-  MSC_REQUIRE(!st->rng_bump_pending, "msc_sample_predictive between msc_sweep_step_begin and msc_state_commit_reduce: the "
-              "tables hold one rank's uncommitted sums");
+  MSC_TRY(refuse_mid_step(st, "msc_sample_predictive"));
   for (uint32_t f = 0; f < st->nfeat; f++) {
     if (out_dev[f] == nullptr) continue;
     const int fam = st->feats[f].family;

@@ -13,6 +13,7 @@
 
 #include "../../include/microscopes_hip.h"
 #include "dev_buf.hpp"
+#include "table_validity.hpp"
 
 namespace msc {
 
@@ -558,9 +559,6 @@ struct msc_feature_host {
   size_t f64_off = 0, f64_len = 0;
   msc::DevBuf<uint32_t> dm_meta_dev;  // dm: [dim+1][2] stage tables (FeatDesc::dm_meta)
   std::vector<uint32_t> dm_meta;     // host copy
-  bool raw_valid = true;        // raw tables hold the truth
-  bool additive_valid = false;  // additive tables are in sync with raw
-  bool derived_valid = false;   // score tables are in sync with raw
 };
 
 struct msc_state;
@@ -593,8 +591,7 @@ struct msc_state {
   bool rebind = false;            // the bounds changed: the next call binds its view afresh (and so re-plans)
   msc::DevBuf<uint32_t> cnt_u32;    // group sizes (group_manager counts), [kpad]
   msc::DevBuf<float> logpc;         // log pseudocount per group, [kpad] (+ loo variants, see prepare)
-  bool cnt_additive_valid = false;
-  bool crp_valid = false;
+  msc::TableValidity valid;         // which of the tables above and below are current (table_validity.hpp)
   msc::DevBuf<msc::FeatDesc> desc_dev;
   std::vector<msc::FeatDesc> desc_host;
   // the same descriptors in the order the tile kernels walk them (abi.cpp plan_groups): every feature but the
@@ -651,7 +648,7 @@ struct msc_state {
     uint64_t view_serial = 0, row0 = 0, nrows = 0, row_id0 = 0;
     float alpha = 0.f;
     std::vector<uint32_t> cols;
-    std::vector<uint8_t> flags;        // validity flags of the state at step entry
+    msc::TableValidity::Snapshot flags;   // validity flags of the state at step entry
     int seen = 0;                      // eager steps with this key so far
     bool disabled = false;
     uint64_t n_eager = 0, n_replayed = 0;   // steps run either way (msc_sweep_step_stats)
@@ -681,13 +678,12 @@ struct msc_state {
   bool pred_upload_pending = false;
   // the blocked Gibbs sampler (abi.cpp msc_blocked_*): the parameter table -- (1 + sum of the features' slices) rows of
   // kpad floats, row 0 the log stick weights -- the features as the kernels read them, the stick kernel's scratch
-  // (log V, log(1 - V): 2 K doubles), and whether the table was drawn from the tables as they stand
+  // (log V, log(1 - V): 2 K doubles); whether the table was drawn from the tables as they stand: valid.draw_current()
   msc::DevBuf<float> blk_tab;
   msc::DevBuf<msc::BlkFeat> blk_feats_dev;
   std::vector<msc::BlkFeat> blk_feats_host;
   msc::DevBuf<double> blk_work;
   uint32_t blk_rows = 0;
-  bool blk_drawn = false;
   // the split-merge move (abi.cpp msc_split_merge): an internal three-slot state of the same features -- pair slots 0
   // and 1, slot 2 their union -- created at the first call and destroyed with this one; the pair labels of the call's
   // rows, the assign kernel's per-workgroup partials, the proposal descriptor and the pair state's score_data
