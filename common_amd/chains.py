@@ -8,8 +8,9 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
-from .runtime import State
+from .runtime import _I32_U32, State
 
 _U64 = (1 << 64) - 1
 
@@ -119,9 +120,8 @@ class ChainEnsemble(object):
         if self.z is None:
             raise ValueError("no assignment yet: call assign() or seat() first")
         dev = self.ctx.torch_device
-        row0 = int(row0)
-        n = int(view.nrows) - row0 if nrows is None else int(nrows)
-        if row0 < 0 or n < 0 or row0 + n > self.z.shape[1] or self.z.shape[1] != view.nrows:
+        row0, n = A.rows(int(view.nrows), row0, nrows)
+        if row0 + n > self.z.shape[1] or self.z.shape[1] != view.nrows:      # (the trace is sized before the call)
             raise ValueError("rows [%d, %d) outside the assignment (%d rows)" % (row0, row0 + n, self.z.shape[1]))
         nsweeps = int(nsweeps)
         if not 0 <= nsweeps < (1 << 32):
@@ -129,12 +129,9 @@ class ChainEnsemble(object):
         seeds = chain_seeds(seed, self.nchains)
         op, ld_order = None, 0
         if order is not None:
-            if not isinstance(order, torch.Tensor) or order.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
-                    or not order.is_contiguous() or order.device != dev \
-                    or tuple(order.shape) not in ((n,), (self.nchains, n)):
-                raise ValueError("order must be a contiguous int32 / uint32 tensor on %s of [nrows] or [nchains, nrows] "
-                                 "entries" % dev)
-            op, ld_order = C.c_void_p(order.data_ptr()), (n if order.dim() == 2 else 0)
+            op, ld_order = A.flat(order, _I32_U32, n, dev, "order"), (n if order.dim() == 2 else 0)
+            if tuple(order.shape) not in ((n,), (self.nchains, n)):
+                raise ValueError("order must hold [nrows] or [nchains, nrows] entries")
         if (zmatrix is not None or want_occupied) and trace_every is None:
             trace_every = 1
         trace = occupied = None
@@ -148,13 +145,13 @@ class ChainEnsemble(object):
         for st in self.states:
             st._drop_subsets()
             st._bound_view = view        # (the library keeps no reference to a view: the states do, for the last one bound)
-        zp = self.z.data_ptr() + 4 * row0
+        zp = self.z.data_ptr() + 4 * row0            # (self.z is the ensemble's own tensor: assign() made it)
         L.check(self.ctx.lib.msc_chains_sweep(
             self._h, view._h, self.states[0]._cols(cols), row0, n, row0 if row_id0 is None else int(row_id0),
             C.c_void_p(zp), int(self.z.stride(0)), op, ld_order, nsweeps, (C.c_uint64 * self.nchains)(*seeds), int(sweep),
             0 if trace_every is None else int(trace_every),
-            C.c_void_p(trace.data_ptr()) if trace is not None and trace.numel() else None,
-            C.c_void_p(occupied.data_ptr()) if occupied is not None and occupied.numel() else None))
+            A.ptr(trace) if trace is not None and trace.numel() else None,
+            A.ptr(occupied) if occupied is not None and occupied.numel() else None))
         if zmatrix is not None and trace.shape[1] > 0:
             zmatrix.add(trace.view(-1, n))
         if trace is None:

@@ -12,6 +12,7 @@
 #include "blocked_post.hpp"
 #include "launchers.hpp"
 #include "linkage_host.hpp"
+#include "row_range.hpp"
 #include "splitmerge_math.hpp"
 
 namespace msc {
@@ -1676,7 +1677,7 @@ static int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *co
                      uint64_t nrows) {
   MSC_REQUIRE(view, "null dataview");
   MSC_REQUIRE(view->ctx->device == st->ctx->device, "dataview and state live on different devices");
-  MSC_REQUIRE(row0 + nrows <= view->nrows, "rows [%llu,%llu) outside the view (%llu rows)",
+  MSC_REQUIRE(msc::rows_within(row0, nrows, view->nrows), "rows [%llu,%llu) outside the view (%llu rows)",
               (unsigned long long)row0, (unsigned long long)(row0 + nrows),
               (unsigned long long)view->nrows);
   (void)bound_view_of(st);                                  // (a binding to a view that is gone, or was invalidated, is dropped first)

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 _NP_OF_TYPE = {L.TYPE_B: np.bool_, L.TYPE_I8: np.int8, L.TYPE_U8: np.uint8, L.TYPE_I16: np.int16,
@@ -25,6 +26,8 @@ for _n, _t in (("uint16", L.TYPE_U16), ("uint32", L.TYPE_U32), ("uint64", L.TYPE
     if hasattr(torch, _n):
         _TYPE_OF_TORCH[getattr(torch, _n)] = _t
         _TORCH_OF_TYPE[_t] = getattr(torch, _n)
+
+_I32_U32 = (torch.int32, _TORCH_OF_TYPE.get(L.TYPE_U32, torch.int32))      # what an `order` tensor may hold
 
 VALUE_TYPE = {L.BB: L.TYPE_B, L.BBNC: L.TYPE_B, L.GP: L.TYPE_U32, L.DD: L.TYPE_I32, L.NICH: L.TYPE_F32,
               L.NIW: L.TYPE_F32, L.NOOP: L.TYPE_B, L.BNB: L.TYPE_U32, L.DM: L.TYPE_I32}
@@ -96,34 +99,21 @@ class Context(object):
         """scipy's single linkage of the distances 1 - z and / or its leaf order (msc_linkage_single): z a float32
         [n, n] tensor on this device, 2 <= n, with contiguous rows (any row stride >= n), SYMMETRIC and finite off the
         diagonal (the diagonal's value is never used).  Returns (float64 [n - 1, 4] or None, int32 [n] or None).  Synchronous."""
-        if not isinstance(z, torch.Tensor) or z.dtype != torch.float32 or z.device != self.torch_device or z.dim() != 2 \
-                or z.shape[0] != z.shape[1] or z.stride(1) != 1 or z.stride(0) < z.shape[0]:
+        if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[0] != z.shape[1]:
             raise ValueError("z must be a square float32 tensor on %s with contiguous rows" % self.torch_device)
         n = int(z.shape[0])
+        zp, ld = A.matrix(z, torch.float32, n, n, self.torch_device, "z")
         # rows that start on 16 bytes are read 16 bytes a lane, up to 3 floats past column n - 1 inside the row's ld: a
         # view whose storage ends before that in its last row (as_strided can make one) is copied first
         if (n - 1) * int(z.stride(0)) + (n + 3) // 4 * 4 > z.untyped_storage().nbytes() // 4 - int(z.storage_offset()):
             z = z.contiguous()
+            zp, ld = A.ptr(z), n
         lk = np.empty((max(n - 1, 0), 4), dtype=np.float64) if linkage else None
         od = np.empty(n, dtype=np.uint32) if order else None
-        L.check(self.lib.msc_linkage_single(self._h, C.c_void_p(z.data_ptr()), int(z.stride(0)), n, 0,
+        L.check(self.lib.msc_linkage_single(self._h, zp, ld, n, 0,
                                             None if lk is None else lk.ctypes.data_as(C.c_void_p),
                                             None if od is None else od.ctypes.data_as(C.c_void_p)))
         return lk, (None if od is None else od.astype(np.int32))
-
-    def _partitions(self, p, name):
-        """(tensor, count, ld, m) of partitions given as an int32 tensor [m] or [count, m] with contiguous rows"""
-        if not isinstance(p, torch.Tensor) or p.dtype != torch.int32 or p.device != self.torch_device:
-            raise ValueError("%s must be an int32 tensor on %s" % (name, self.torch_device))
-        if p.dim() == 1:
-            p = p.reshape(1, -1)
-        if p.dim() != 2 or p.shape[0] == 0 or p.shape[1] == 0:
-            raise ValueError("%s must be [m] or [count, m], neither 0" % name)
-        m = int(p.shape[1])
-        ld = int(p.stride(0)) if p.shape[0] > 1 else m
-        if (m > 1 and p.stride(1) != 1) or ld < m:
-            raise ValueError("%s must have contiguous rows (row stride >= m)" % name)
-        return p, int(p.shape[0]), ld, m
 
     def partition_distances(self, a, b=None):
         """The contingency sums of every partition of a against every partition of b (msc_partition_distances): int32
@@ -133,16 +123,17 @@ class Context(object):
         include/microscopes_hip.h defines them; common_amd.query makes Binder's distance, the variation of information
         and the adjusted Rand index of them.  At most %d clusters a partition: counted before anything is launched, more
         raise ValueError.  More than %d rows: MicroscopesHipError (MSC_EUNSUPPORTED)."""
-        a2, na, lda, m = self._partitions(a, "a")
+        a2, na, lda = A.vectors(a, self.torch_device, "a")
+        m = int(a2.shape[-1])
         if b is None:
             b2, nb, ldb = None, na, lda
         else:
-            b2, nb, ldb, mb = self._partitions(b, "b")
-            if mb != m:
-                raise ValueError("a and b must label the same rows: m = %d and %d" % (m, mb))
+            b2, nb, ldb = A.vectors(b, self.torch_device, "b")
+            if b2.shape[-1] != m:
+                raise ValueError("a and b must label the same rows: m = %d and %d" % (m, b2.shape[-1]))
         if m <= L.DISTANCES_MAX_ROWS:
             for p in (a2,) if b2 is None else (a2, b2):
-                srt = torch.sort(p, dim=1).values
+                srt = torch.sort(p.reshape(-1, m), dim=1).values
                 most = int(((srt[:, 1:] != srt[:, :-1]).sum(dim=1) + 1).max())
                 if most > L.DISTANCES_MAX_CLUSTERS:
                     raise ValueError("a partition holds %d clusters, more than %d" % (most, L.DISTANCES_MAX_CLUSTERS))
@@ -154,8 +145,8 @@ class Context(object):
             per += [torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
                     torch.empty(n, dtype=torch.int32, device=dev)]
         L.check(self.lib.msc_partition_distances(
-            self._h, C.c_void_p(a2.data_ptr()), lda, na, None if b2 is None else C.c_void_p(b2.data_ptr()), ldb, nb, m, 0,
-            C.c_void_p(pairs_ab.data_ptr()), C.c_void_p(nlogn_ab.data_ptr()), *[C.c_void_p(t.data_ptr()) for t in per]))
+            self._h, A.ptr(a2), lda, na, None if b2 is None else A.ptr(b2), ldb, nb, m, 0, A.ptr(pairs_ab), A.ptr(nlogn_ab),
+            *[A.ptr(t) for t in per]))
         return (pairs_ab, nlogn_ab) + tuple(per)
     partition_distances.__doc__ %= (L.DISTANCES_MAX_CLUSTERS, L.DISTANCES_MAX_ROWS)
 
@@ -266,11 +257,8 @@ class DataView(object):
     @classmethod
     def from_tensors(cls, ctx, columns, masks=None):
         """Adopt device tensors as columns (no copy).  [N] scalars or [N, d] vector features."""
-        cols = []
-        for c in columns:
-            if c.device != ctx.torch_device or not c.is_contiguous():
-                raise ValueError("columns must be contiguous tensors on %s" % ctx.torch_device)
-            cols.append(c)
+        cols, dev = list(columns), ctx.torch_device
+        ptrs = (C.c_void_p * len(cols))(*[A.flat(c, tuple(_TYPE_OF_TORCH), 0, dev, "a column") for c in cols])
         n = cols[0].shape[0]
         types = []
         for c in cols:
@@ -278,10 +266,13 @@ class DataView(object):
                 raise ValueError("column shapes must be [N] or [N, d] with one N")
             types.append((_TYPE_OF_TORCH[c.dtype], 1 if c.dim() == 1 else int(c.shape[1])))
         rt = (L.RuntimeType * len(types))(*[L.RuntimeType(t, k) for t, k in types])
-        ptrs = (C.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
         mptr = None
         if masks is not None:
-            mptr = (C.c_void_p * len(cols))(*[(m.data_ptr() if m is not None else None) for m in masks])
+            masks = list(masks)
+            if len(masks) != len(cols):
+                raise ValueError("masks must hold one entry (a tensor or None) per column")
+            mptr = (C.c_void_p * len(cols))(*[A.flat(m, (torch.uint8, torch.bool), n * k, dev, "a mask", True)
+                                              for m, (_, k) in zip(masks, types)])
         h = C.c_void_p()
         L.check(ctx.lib.msc_dataview_from_device_columns(ctx._h, n, rt, len(types), ptrs, mptr, C.byref(h)))
         return cls(ctx, h, keepalive=(cols, masks))
@@ -442,97 +433,80 @@ class State(object):
             return None
         return (C.c_uint32 * len(cols))(*[int(c) for c in cols])
 
+    def _slots(self, slots):
+        return A.flat(slots, torch.uint8, self.K, self.ctx.torch_device, "slots", True)
+
+    def _bind(self, view, row0, nrows, z, optional=False):
+        """what every call over a view's rows starts with -> (row0, n, z's pointer).  The library keeps no reference to a
+        view: this object does, for the last one bound."""
+        self._bound_view = view
+        row0, n = A.rows(view.nrows, row0, nrows)
+        return row0, n, A.flat(z, torch.int32, n, self.ctx.torch_device, "z", optional)
+
     def score_value(self, view, out=None, row0=0, nrows=None, z=None, crp_prior=False, cols=None,
                     niw_f32=False):
         """[nrows, K] float32 device tensor of summed score_value (see msc_score_value)."""
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
+        row0, n, zp = self._bind(view, row0, nrows, z, True)
         if out is None:
             out = torch.empty((n, self.K), dtype=torch.float32, device=self.ctx.torch_device)
-        if out.dtype != torch.float32 or out.stride(-1) != 1 or out.shape[0] < n:
-            raise ValueError("out must be a row-major float32 [nrows, >=K] tensor")
-        ld = out.stride(0) if out.dim() == 2 else self.K
-        zp = None
-        if z is not None:
-            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-                raise ValueError("z must be a contiguous int32 tensor of nrows entries")
-            zp = C.c_void_p(z.data_ptr())
+        op, ld = A.matrix(out, torch.float32, n, self.K, self.ctx.torch_device, "out")
         L.check(self.ctx.lib.msc_score_value(self._h, view._h, self._cols(cols), row0, n, zp,
                                              (L.SCORE_CRP_PRIOR if crp_prior else 0) |
-                                             (L.SCORE_NIW_F32 if niw_f32 else 0),
-                                             C.c_void_p(out.data_ptr()), ld))
+                                             (L.SCORE_NIW_F32 if niw_f32 else 0), op, ld))
         return out
 
     def score_tune(self, view, out, row0=0, nrows=None, cols=None):
         """Settle the single-nich pass's launch shape for passes like this one (synchronous, ~10 ms; msc_score_tune).
         -> (shape index or -1, ms per pass)."""
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if out.dtype != torch.float32 or out.stride(-1) != 1 or out.shape[0] < n:
-            raise ValueError("out must be a row-major float32 [nrows, >=K] tensor")
+        row0, n, _ = self._bind(view, row0, nrows, None, True)
+        op, ld = A.matrix(out, torch.float32, n, self.K, self.ctx.torch_device, "out")
         shape, ms = C.c_int(-1), C.c_float(0)
-        L.check(self.ctx.lib.msc_score_tune(self._h, view._h, self._cols(cols), row0, n, C.c_void_p(out.data_ptr()),
-                                            out.stride(0) if out.dim() == 2 else self.K, C.byref(shape), C.byref(ms)))
+        L.check(self.ctx.lib.msc_score_tune(self._h, view._h, self._cols(cols), row0, n, op, ld, C.byref(shape),
+                                            C.byref(ms)))
         return shape.value, ms.value
 
     def accumulate(self, view, z, row0=0, nrows=None, reset=True, subtract=False, commit=True, cols=None):
         self._drop_subsets()
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+        row0, n, zp = self._bind(view, row0, nrows, z)
         flags = (L.ACC_RESET if reset else 0) | (L.ACC_SUBTRACT if subtract else 0) | \
                 (0 if commit else L.ACC_NO_COMMIT)
-        L.check(self.ctx.lib.msc_accumulate(self._h, view._h, self._cols(cols), row0, n,
-                                            C.c_void_p(z.data_ptr()), flags))
+        L.check(self.ctx.lib.msc_accumulate(self._h, view._h, self._cols(cols), row0, n, zp, flags))
 
     def entity_op(self, view, row, group, join=True, z=None, cols=None):
         """one entity joins / leaves one group, the group by value (msc_entity_op): every table stays current"""
         self._drop_subsets()
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        zp = None
-        if z is not None:
-            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] <= row:
-                raise ValueError("z must be a contiguous int32 tensor covering the row")
-            zp = C.c_void_p(z.data_ptr())
-        L.check(self.ctx.lib.msc_entity_op(self._h, view._h, self._cols(cols), int(row), int(group), 1 if join else -1, zp))
+        self._bound_view = view          # (as _bind)
+        row, _ = A.rows(view.nrows, row, 1)
+        zp = A.flat(z, torch.int32, row + 1, self.ctx.torch_device, "z", True)
+        L.check(self.ctx.lib.msc_entity_op(self._h, view._h, self._cols(cols), row, int(group), 1 if join else -1, zp))
 
     def score_data(self, out=None):
         if out is None:
             out = torch.empty((len(self.features), self.K), dtype=torch.float32, device=self.ctx.torch_device)
-        L.check(self.ctx.lib.msc_score_data(self._h, C.c_void_p(out.data_ptr())))
+        op, ld = A.matrix(out, torch.float32, len(self.features), self.K, self.ctx.torch_device, "out")
+        if ld != self.K:
+            raise ValueError("out must be a contiguous [nfeatures, K] tensor: msc_score_data takes no row stride")
+        L.check(self.ctx.lib.msc_score_data(self._h, op))
         return out
 
+    def _rows_call(self, fn, view, z, seed, sweep, row0, nrows, row_id0, cols):
+        """the calls that take (view, cols, row0, nrows, row_id0, z, seed, sweep) and nothing else"""
+        row0, n, zp = self._bind(view, row0, nrows, z)
+        L.check(fn(self._h, view._h, self._cols(cols), row0, n, row0 if row_id0 is None else row_id0, zp, int(seed),
+                   int(sweep)))
+
     def sweep_assign(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
-        L.check(self.ctx.lib.msc_sweep_assign(self._h, view._h, self._cols(cols), row0, n,
-                                              row0 if row_id0 is None else row_id0,
-                                              C.c_void_p(z.data_ptr()), int(seed), int(sweep)))
+        self._rows_call(self.ctx.lib.msc_sweep_assign, view, z, seed, sweep, row0, nrows, row_id0, cols)
 
     def sweep_step(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
         """sweep_assign + accumulate(reset) in one call; repeated steps replay as a HIP graph (msc_sweep_step)."""
         self._drop_subsets()
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
-        L.check(self.ctx.lib.msc_sweep_step(self._h, view._h, self._cols(cols), row0, n,
-                                            row0 if row_id0 is None else row_id0,
-                                            C.c_void_p(z.data_ptr()), int(seed), int(sweep)))
+        self._rows_call(self.ctx.lib.msc_sweep_step, view, z, seed, sweep, row0, nrows, row_id0, cols)
 
     def sweep_step_begin(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
         """the sharded step up to the exchange: follow with all-reduce of reduce_buffers() and commit_reduce()"""
         self._drop_subsets()
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
-        L.check(self.ctx.lib.msc_sweep_step_begin(self._h, view._h, self._cols(cols), row0, n,
-                                                  row0 if row_id0 is None else row_id0,
-                                                  C.c_void_p(z.data_ptr()), int(seed), int(sweep)))
+        self._rows_call(self.ctx.lib.msc_sweep_step_begin, view, z, seed, sweep, row0, nrows, row_id0, cols)
 
     def sweep_sequential(self, view, z, seed, sweep, nsweeps=1, order=None, trace=None, row0=0, nrows=None,
                          row_id0=None, cols=None):
@@ -540,29 +514,14 @@ class State(object):
         left (msc_sweep_sequential).  order: uint32 (or int32) device tensor of nrows offsets from row0, the visiting
         order of every sweep (None: ascending); trace: int32 device tensor of nsweeps x nrows, z after every sweep."""
         self._drop_subsets()
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+        row0, n, zp = self._bind(view, row0, nrows, z)
         if not 0 <= int(nsweeps) < (1 << 32):
             raise ValueError("nsweeps must be in [0, 2^32)")
         dev = self.ctx.torch_device
-        op = None
-        if order is not None:
-            if order.dtype not in (torch.int32, _TORCH_OF_TYPE.get(L.TYPE_U32, torch.int32)) or not order.is_contiguous() \
-                    or order.numel() < n or order.device != z.device:
-                raise ValueError("order must be a contiguous int32 / uint32 device tensor of nrows entries")
-            op = C.c_void_p(order.data_ptr())
-        tp = None
-        if trace is not None:
-            if trace.dtype != torch.int32 or not trace.is_contiguous() or trace.numel() < int(nsweeps) * n \
-                    or trace.device != z.device:
-                raise ValueError("trace must be a contiguous int32 device tensor of nsweeps x nrows entries")
-            tp = C.c_void_p(trace.data_ptr())
-        if z.device != dev:
-            raise ValueError("z must live on the context's device")
+        op = A.flat(order, _I32_U32, n, dev, "order", True)
+        tp = A.flat(trace, torch.int32, int(nsweeps) * n, dev, "trace", True)
         L.check(self.ctx.lib.msc_sweep_sequential(self._h, view._h, self._cols(cols), row0, n,
-                                                  row0 if row_id0 is None else row_id0, C.c_void_p(z.data_ptr()), op,
+                                                  row0 if row_id0 is None else row_id0, zp, op,
                                                   int(nsweeps), int(seed), int(sweep), tp))
 
     # the blocked (uncollapsed) Gibbs sampler ---------------------------------
@@ -570,31 +529,28 @@ class State(object):
         """draw every slot's parameters and the stick weights from the tables as they stand (msc_blocked_draw)"""
         L.check(self.ctx.lib.msc_blocked_draw(self._h, int(seed), int(sweep)))
 
-    def blocked_tables(self):
-        """{"logw": float32[K], feature index: float32[nslices, K]}: views onto the device tables of the latest draw
-        (msc_blocked_tables; the slices per family are listed in include/microscopes_hip.h)"""
+    def _tables(self, fn, ncols):
+        """{"logw": float32[ncols], feature index: float32[nslices, ncols]}: views onto the device tables fn describes"""
         out = {}
         for f in [None] + list(range(len(self.features))):
             p, ns, ld = C.c_void_p(), C.c_uint32(), C.c_uint32()
-            L.check(self.ctx.lib.msc_blocked_tables(self._h, 0xffffffff if f is None else f, C.byref(p), C.byref(ns),
-                                                    C.byref(ld)))
+            L.check(fn(self._h, 0xffffffff if f is None else f, C.byref(p), C.byref(ns), C.byref(ld)))
             if ns.value == 0:
-                t = torch.empty((0, self.K), dtype=torch.float32, device=self.ctx.torch_device)
+                t = torch.empty((0, ncols), dtype=torch.float32, device=self.ctx.torch_device)
             else:
                 t = _alias_tensor(p.value, ns.value * ld.value, torch.float32, self.ctx.torch_device,
-                                  self).view(ns.value, ld.value)[:, :self.K]
+                                  self).view(ns.value, ld.value)[:, :ncols]
             out["logw" if f is None else f] = t[0] if f is None else t
         return out
 
+    def blocked_tables(self):
+        """{"logw": float32[K], feature index: float32[nslices, K]}: views onto the device tables of the latest draw
+        (msc_blocked_tables; the slices per family are listed in include/microscopes_hip.h)"""
+        return self._tables(self.ctx.lib.msc_blocked_tables, self.K)
+
     def blocked_assign(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
         """every row's slot drawn independently under the parameters of the latest blocked_draw (msc_blocked_assign)"""
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
-        L.check(self.ctx.lib.msc_blocked_assign(self._h, view._h, self._cols(cols), row0, n,
-                                                row0 if row_id0 is None else row_id0,
-                                                C.c_void_p(z.data_ptr()), int(seed), int(sweep)))
+        self._rows_call(self.ctx.lib.msc_blocked_assign, view, z, seed, sweep, row0, nrows, row_id0, cols)
 
     def sweep_blocked(self, view, z, seed, sweep, nsweeps=1, trace=None, top_slot=None, row0=0, nrows=None,
                       row_id0=None, cols=None):
@@ -602,27 +558,14 @@ class State(object):
         trace: int32 device tensor of nsweeps x nrows, z after every sweep; top_slot: int32 / uint32 device tensor of
         nsweeps entries, the highest occupied slot after every sweep (K - 1: raise K)."""
         self._drop_subsets()
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-            raise ValueError("z must be a contiguous int32 tensor of nrows entries")
+        row0, n, zp = self._bind(view, row0, nrows, z)
         if not 0 <= int(nsweeps) < (1 << 32):
             raise ValueError("nsweeps must be in [0, 2^32)")
-        if z.device != self.ctx.torch_device:
-            raise ValueError("z must live on the context's device")
-        tp = sp = None
-        if trace is not None:
-            if trace.dtype != torch.int32 or not trace.is_contiguous() or trace.numel() < int(nsweeps) * n \
-                    or trace.device != z.device:
-                raise ValueError("trace must be a contiguous int32 device tensor of nsweeps x nrows entries")
-            tp = C.c_void_p(trace.data_ptr())
-        if top_slot is not None:
-            if top_slot.element_size() != 4 or top_slot.is_floating_point() or not top_slot.is_contiguous() \
-                    or top_slot.numel() < int(nsweeps) or top_slot.device != z.device:
-                raise ValueError("top_slot must be a contiguous 32-bit integer device tensor of nsweeps entries")
-            sp = C.c_void_p(top_slot.data_ptr())
+        dev = self.ctx.torch_device
+        tp = A.flat(trace, torch.int32, int(nsweeps) * n, dev, "trace", True)
+        sp = A.flat(top_slot, 4, int(nsweeps), dev, "top_slot", True)
         L.check(self.ctx.lib.msc_sweep_blocked(self._h, view._h, self._cols(cols), row0, n,
-                                               row0 if row_id0 is None else row_id0, C.c_void_p(z.data_ptr()),
+                                               row0 if row_id0 is None else row_id0, zp,
                                                int(nsweeps), int(seed), int(sweep), tp, sp))
 
     # split-merge Metropolis-Hastings proposals --------------------------------
@@ -634,53 +577,21 @@ class State(object):
         proposed int32 [nproposals, nrows], the proposed pair labels (-1 outside the two groups); counters 64-bit integer
         [5] = {splits proposed, accepted, merges proposed, accepted, void}, added to."""
         self._drop_subsets()
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
-        if z is None:
-            zp = None
-        else:
-            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-                raise ValueError("z must be a contiguous int32 tensor of nrows entries")
-            if z.device != self.ctx.torch_device:
-                raise ValueError("z must live on the context's device")
-            zp = C.c_void_p(z.data_ptr())
+        row0, n, zp = self._bind(view, row0, nrows, z, True)      # (a null z is the library's to refuse)
         if not 0 <= int(nproposals) < (1 << 32) or not 0 <= int(launch_iters) < (1 << 32):
             raise ValueError("nproposals and launch_iters must be in [0, 2^32)")
-
-        def ptr(t, dtype, numel, what):
-            if t is None:
-                return None
-            if t.dtype != dtype or not t.is_contiguous() or t.numel() < numel or t.device != self.ctx.torch_device:
-                raise ValueError("%s must be a contiguous %s device tensor of at least %d entries" % (what, dtype, numel))
-            return C.c_void_p(t.data_ptr())
-
-        cp = None
-        if counters is not None:
-            if counters.element_size() != 8 or counters.is_floating_point() or not counters.is_contiguous() \
-                    or counters.numel() < 5 or counters.device != self.ctx.torch_device:
-                raise ValueError("counters must be a contiguous 64-bit integer device tensor of 5 entries")
-            cp = C.c_void_p(counters.data_ptr())
+        dev, np_ = self.ctx.torch_device, int(nproposals)
         L.check(self.ctx.lib.msc_split_merge(self._h, view._h, self._cols(cols), row0, n,
-                                             row0 if row_id0 is None else row_id0, zp, int(nproposals), int(launch_iters),
-                                             int(seed), int(sweep), ptr(log, torch.float64, 8 * int(nproposals), "log"),
-                                             ptr(trace, torch.int32, int(nproposals) * n, "trace"),
-                                             ptr(proposed, torch.int32, int(nproposals) * n, "proposed"), cp))
+                                             row0 if row_id0 is None else row_id0, zp, np_, int(launch_iters),
+                                             int(seed), int(sweep), A.flat(log, torch.float64, 8 * np_, dev, "log", True),
+                                             A.flat(trace, torch.int32, np_ * n, dev, "trace", True),
+                                             A.flat(proposed, torch.int32, np_ * n, dev, "proposed", True),
+                                             A.flat(counters, 8, 5, dev, "counters", True)))
 
     def split_merge_tables(self):
         """{"logw": float32[2], feature index: float32[nslices, 2]}: views onto theta* of the last proposal made -- the
         two pair slots' log weights and slices (msc_split_merge_tables; the slices are blocked_tables()'s)"""
-        out = {}
-        for f in [None] + list(range(len(self.features))):
-            p, ns, ld = C.c_void_p(), C.c_uint32(), C.c_uint32()
-            L.check(self.ctx.lib.msc_split_merge_tables(self._h, 0xffffffff if f is None else f, C.byref(p), C.byref(ns),
-                                                        C.byref(ld)))
-            if ns.value == 0:
-                t = torch.empty((0, 2), dtype=torch.float32, device=self.ctx.torch_device)
-            else:
-                t = _alias_tensor(p.value, ns.value * ld.value, torch.float32, self.ctx.torch_device,
-                                  self).view(ns.value, ld.value)[:, :2]
-            out["logw" if f is None else f] = t[0] if f is None else t
-        return out
+        return self._tables(self.ctx.lib.msc_split_merge_tables, 2)
 
     def sweep_step_stats(self):
         """(steps run launch by launch, steps run as one graph launch)"""
@@ -765,7 +676,7 @@ class State(object):
         if want_scores:
             scores = [torch.empty(g.npoints, dtype=torch.float64, device=self.ctx.torch_device) for g in grids]
             sp = (C.c_void_p * len(grids))(*[t.data_ptr() for t in scores])
-        L.check(self.ctx.lib.msc_hp_grid_gibbs(self._h, hs, len(grids), _slots_ptr(slots, self.K), int(seed), int(sweep),
+        L.check(self.ctx.lib.msc_hp_grid_gibbs(self._h, hs, len(grids), self._slots(slots), int(seed), int(sweep),
                                                chosen.ctypes.data_as(C.c_void_p), sp))
         return (chosen, scores) if want_scores else chosen
 
@@ -790,7 +701,7 @@ class State(object):
                                   int(prior), float(c.get("a", 0.0)), float(c.get("b", 0.0)), int(c.get("partner", 0)))
         values = np.zeros(len(coords), dtype=np.float32)
         evals = np.zeros(len(coords), dtype=np.uint32)
-        L.check(self.ctx.lib.msc_hp_slice(self._h, arr, len(coords), _slots_ptr(slots, self.K), int(seed), int(sweep),
+        L.check(self.ctx.lib.msc_hp_slice(self._h, arr, len(coords), self._slots(slots), int(seed), int(sweep),
                                           values.ctypes.data_as(C.c_void_p), evals.ctypes.data_as(C.c_void_p)))
         return values, evals
 
@@ -806,7 +717,7 @@ class State(object):
         ws = np.array([tparams[f]["p"] for f in feats], dtype=np.float32)
         evals = np.zeros(len(feats), dtype=np.uint64)
         L.check(self.ctx.lib.msc_theta_slice(self._h, fs.ctypes.data_as(C.c_void_p), ws.ctypes.data_as(C.c_void_p),
-                                             len(feats), _slots_ptr(slots, self.K), int(seed), int(sweep),
+                                             len(feats), self._slots(slots), int(seed), int(sweep),
                                              evals.ctypes.data_as(C.c_void_p)))
         return {f: int(e) for f, e in zip(feats, evals)}
 
@@ -824,26 +735,17 @@ class State(object):
         given=[f, ...]: the CONDITIONAL log density of the row's other observed entries given features f, ..., as
         logp(all) - logp(subset(given)); the subset state is kept until a table of this state changes.  cols then has to
         be None or list every feature's column (the subset reads the given features' entries of it)."""
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else nrows
+        row0, n, zp = self._bind(view, row0, nrows, z, True)
         dev = self.ctx.torch_device
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=dev)
-        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n:
-            raise ValueError("out must be a contiguous float32 tensor of nrows entries")
-        zp = None
-        if z is not None:
-            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n:
-                raise ValueError("z must be a contiguous int32 tensor of nrows entries")
-            zp = C.c_void_p(z.data_ptr())
+        op = A.flat(out, torch.float32, n, dev, "out")
         mp = lr = None
         if want_map:
             mp = torch.empty(n, dtype=torch.int32, device=dev)
             lr = torch.empty(n, dtype=torch.float32, device=dev)
-        L.check(self.ctx.lib.msc_score_marginal(self._h, view._h, self._cols(cols), row0, n, zp, 0,
-                                                C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(mp.data_ptr()) if want_map else None,
-                                                C.c_void_p(lr.data_ptr()) if want_map else None))
+        L.check(self.ctx.lib.msc_score_marginal(self._h, view._h, self._cols(cols), row0, n, zp, 0, op,
+                                                A.ptr(mp) if want_map else None, A.ptr(lr) if want_map else None))
         if given is not None:
             given = [int(f) for f in given]
             sub = self._subset_cached(given)
@@ -879,8 +781,10 @@ class State(object):
     def _drop_subsets(self):
         """every method that changes a table (hp, suff-stats, counts, alpha) calls this first: the subset states that
         predictive_logp(given=) keeps were copies of the tables as they stood"""
-        for sub in self.__dict__.pop("_subsets", {}).values():
-            sub.close()
+        subs = self.__dict__.pop("_subsets", None)
+        if subs:
+            for sub in subs.values():
+                sub.close()
 
     def sample_predictive(self, view, z=None, seed=0, sweep=0, masked_only=False, features=None, row0=0, nrows=None,
                           row_id0=None, cols=None, out=None):
@@ -889,9 +793,8 @@ class State(object):
         its observed entries.  features: state feature indices to draw (default: all).  out: optional dict feature ->
         device tensor to write into (rows that are skipped keep what it held).  -> (dict feature -> device tensor of
         nrows values -- [nrows, dim] for niw --, int32 device tensor of the groups used)."""
-        self._bound_view = view          # (the library keeps no reference to a view: this object does, for the last one bound)
-        n = view.nrows - row0 if nrows is None else int(nrows)
-        if row0 < 0 or n < 0 or row0 + n > view.nrows:
+        row0, n, zp = self._bind(view, row0, nrows, z, True)
+        if row0 + n > view.nrows:                      # (outputs are sized before the call: not left to the library)
             raise ValueError("rows [%d, %d) outside the view (%d rows)" % (row0, row0 + n, view.nrows))
         feats = list(range(len(self.features))) if features is None else [int(f) for f in features]
         for f in feats:
@@ -901,11 +804,6 @@ class State(object):
                 raise L.MicroscopesHipError(-4, "feature %d: dm has no sample_value upstream" % f)
             if self.features[f][0] not in self._PRED_DTYPES:
                 raise L.MicroscopesHipError(-4, "feature %d: the family has no values to draw" % f)
-        zp = None
-        if z is not None:
-            if z.dtype != torch.int32 or not z.is_contiguous() or z.shape[0] < n or z.device != self.ctx.torch_device:
-                raise ValueError("z must be a contiguous int32 device tensor of nrows entries")
-            zp = C.c_void_p(z.data_ptr())
         out = dict(out or {})
         ptrs = (C.c_void_p * len(self.features))()
         for f in feats:
@@ -915,14 +813,14 @@ class State(object):
             t = out.get(f)
             if t is None:
                 t = torch.empty(shape, dtype=dt, device=self.ctx.torch_device)
-            elif t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.ctx.torch_device:
+            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
                 raise ValueError("out[%d] must be a contiguous %s device tensor of shape %s" % (f, dt, shape))
             out[f] = t
-            ptrs[f] = t.data_ptr() if n else None
+            ptrs[f] = A.flat(t, dt, 0, self.ctx.torch_device, "out[%d]" % f) if n else None
         groups = torch.full((n,), -1, dtype=torch.int32, device=self.ctx.torch_device)
-        L.check(self.ctx.lib.msc_sample_predictive(self._h, view._h, self._cols(cols), int(row0), n,
+        L.check(self.ctx.lib.msc_sample_predictive(self._h, view._h, self._cols(cols), row0, n,
                                                    int(row0 if row_id0 is None else row_id0), zp,
-                                                   C.c_void_p(groups.data_ptr()) if n else None,
+                                                   A.ptr(groups) if n else None,
                                                    L.PRED_MASKED_ONLY if masked_only else 0, int(seed), int(sweep), ptrs))
         return {f: out[f] for f in feats}, groups
 
@@ -945,16 +843,6 @@ class State(object):
             self.close()
         except Exception:
             pass
-
-
-def _slots_ptr(slots, K):
-    if slots is None:
-        return None
-    if not (torch.is_tensor(slots) and slots.dtype == torch.uint8 and slots.is_cuda and slots.is_contiguous()
-            and slots.numel() >= K):
-        raise ValueError("slots must be a contiguous uint8 device tensor of ngroups entries")
-    return C.c_void_p(slots.data_ptr())
-
 
 
 class HpGrid(object):
@@ -987,9 +875,8 @@ class HpGrid(object):
             raise ValueError("grid is closed")
         if out is None:
             out = torch.empty(self.npoints, dtype=torch.float64, device=self.state.ctx.torch_device)
-        if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < self.npoints:
-            raise ValueError("out must be a contiguous float64 tensor of npoints entries")
-        L.check(self.state.ctx.lib.msc_hp_grid_score(self._h, _slots_ptr(slots, self.state.K), C.c_void_p(out.data_ptr())))
+        op = A.flat(out, torch.float64, self.npoints, self.state.ctx.torch_device, "out")
+        L.check(self.state.ctx.lib.msc_hp_grid_score(self._h, self.state._slots(slots), op))
         return out
 
     def close(self):
@@ -1032,22 +919,10 @@ class ZMatrix(object):
         if not getattr(self, "_h", None):
             raise ValueError("ZMatrix is closed")
 
-    def _vectors(self, z):
+    def _vectors(self, z, name="z"):
         """(tensor, S, ld) of assignment vectors given as add takes them"""
         self._check_open()
-        if not isinstance(z, torch.Tensor) or z.dtype != torch.int32 or z.device != self.ctx.torch_device:
-            raise ValueError("z must be an int32 tensor on %s" % self.ctx.torch_device)
-        if z.dim() == 1:
-            z2, S, ld = z, 1, self.n
-            if z.shape[0] != self.n or (self.n > 1 and z.stride(0) != 1):
-                raise ValueError("z must hold n = %d contiguous labels" % self.n)
-        elif z.dim() == 2:
-            z2, S, ld = z, int(z.shape[0]), int(z.stride(0)) if z.shape[0] > 1 else self.n
-            if z.shape[1] != self.n or (self.n > 1 and z.stride(1) != 1) or ld < self.n:
-                raise ValueError("z must be [S, n = %d] with contiguous rows" % self.n)
-        else:
-            raise ValueError("z must be [n] or [S, n]")
-        return z2, S, ld
+        return A.vectors(z, self.ctx.torch_device, name, self.n)
 
     def add(self, z):
         """stage assignment vectors: an int32 device tensor [n] or [S, n] whose rows are contiguous (row stride >= n).
@@ -1055,19 +930,18 @@ class ZMatrix(object):
         z2, S, ld = self._vectors(z)
         if S == 0:
             return
-        L.check(self.ctx.lib.msc_zmatrix_add(self._h, C.c_void_p(z2.data_ptr()), S, ld))
+        L.check(self.ctx.lib.msc_zmatrix_add(self._h, A.ptr(z2), S, ld))
 
     def partition_sums(self, cands):
         """Candidate partitions against the counts (msc_zmatrix_partition_sums).  cands: an int32 device tensor [n] or
         [ncand, n] laid out as add takes samples; only equality of labels matters, any int32 value is a label.  Returns
         (w int64 [ncand, m], size int32 [ncand, m]): size[c, a] = the selected rows that c puts with row a (a included),
         w[c, a] = the sum of counts()[a, b] over those rows.  Exact; flushes the staged samples first."""
-        c2, nc, ld = self._vectors(cands)
+        c2, nc, ld = self._vectors(cands, "cands")
         dev = self.ctx.torch_device
         w = torch.empty((nc, self.m), dtype=torch.int64, device=dev)
         size = torch.empty((nc, self.m), dtype=torch.int32, device=dev)
-        L.check(self.ctx.lib.msc_zmatrix_partition_sums(self._h, C.c_void_p(c2.data_ptr()), nc, ld,
-                                                        C.c_void_p(w.data_ptr()), C.c_void_p(size.data_ptr())))
+        L.check(self.ctx.lib.msc_zmatrix_partition_sums(self._h, A.ptr(c2), nc, ld, A.ptr(w), A.ptr(size)))
         return w, size
 
     def partition_loss(self, cands):
@@ -1076,14 +950,13 @@ class ZMatrix(object):
         mis-paired pairs under Binder's loss (the argmin is Dahl's least-squares clustering); vi_lb is Wade and
         Ghahramani's lower bound on the expected variation of information less its candidate-independent term, which
         counts do not determine; valid is the number of valid samples, counts()[0, 0].  Synchronises to read valid."""
-        c2, nc, ld = self._vectors(cands)
+        c2, nc, ld = self._vectors(cands, "cands")
         dev = self.ctx.torch_device
         binder = torch.empty(nc, dtype=torch.int64, device=dev)
         vi = torch.empty(nc, dtype=torch.float64, device=dev)
         valid = torch.empty(1, dtype=torch.int64, device=dev)
-        L.check(self.ctx.lib.msc_zmatrix_partition_loss(self._h, C.c_void_p(c2.data_ptr()), nc, ld,
-                                                        C.c_void_p(binder.data_ptr()), C.c_void_p(vi.data_ptr()),
-                                                        C.c_void_p(valid.data_ptr())))
+        L.check(self.ctx.lib.msc_zmatrix_partition_loss(self._h, A.ptr(c2), nc, ld, A.ptr(binder), A.ptr(vi),
+                                                        A.ptr(valid)))
         self.ctx.synchronize()
         return binder, vi, int(valid.item())
 
@@ -1096,7 +969,7 @@ class ZMatrix(object):
         int32 [nstarts, m] over the selected rows, numbered by first row; binder_num int64 [nstarts]; sweeps int32
         [nstarts], the last one that moved nothing included; moves int64 [nstarts]), bit-equal to
         query.refine_partition on the host.  Asynchronous; flushes the staged samples first."""
-        s2, ns, ld = self._vectors(starts)
+        s2, ns, ld = self._vectors(starts, "starts")
         if max_clusters is None:
             max_clusters = min(self.m, L.ZMATRIX_REFINE_MAX_CLUSTERS)
         max_sweeps, max_clusters = int(max_sweeps), int(max_clusters)
@@ -1119,9 +992,8 @@ class ZMatrix(object):
         sweeps = torch.empty(ns, dtype=torch.int32, device=dev)
         moves = torch.empty(ns, dtype=torch.int64, device=dev)
         L.check(self.ctx.lib.msc_zmatrix_partition_refine(
-            self._h, C.c_void_p(s2.data_ptr()), ns, ld, max_sweeps, max_clusters,
-            None if o is None else o.ctypes.data_as(C.c_void_p), C.c_void_p(labels.data_ptr()),
-            C.c_void_p(binder.data_ptr()), C.c_void_p(sweeps.data_ptr()), C.c_void_p(moves.data_ptr())))
+            self._h, A.ptr(s2), ns, ld, max_sweeps, max_clusters, None if o is None else o.ctypes.data_as(C.c_void_p),
+            A.ptr(labels), A.ptr(binder), A.ptr(sweeps), A.ptr(moves)))
         return labels, binder, sweeps, moves
 
     @property
@@ -1130,16 +1002,6 @@ class ZMatrix(object):
         v = C.c_uint64()
         L.check(self.ctx.lib.msc_zmatrix_nsamples(self._h, C.byref(v)))
         return int(v.value)
-
-    def _out(self, out, dtype):
-        m = self.m
-        if out is None:
-            return torch.empty((m, m), dtype=dtype, device=self.ctx.torch_device)
-        if out.dtype != dtype or out.device != self.ctx.torch_device or out.dim() != 2 or out.shape[0] < m \
-                or out.shape[1] < m or (m > 1 and out.stride(1) != 1) or out.stride(0) < m:
-            raise ValueError("out must be a %s tensor on %s of at least [m, m] = [%d, %d] with contiguous rows"
-                             % (dtype, self.ctx.torch_device, m, m))
-        return out
 
     def _order(self, order):
         if order is None:
@@ -1153,10 +1015,14 @@ class ZMatrix(object):
     def _write(self, fn, order, out, dtype):
         self._check_open()
         o = self._order(order)
-        out = self._out(out, dtype)
-        L.check(fn(self._h, None if o is None else o.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
-                   int(out.stride(0))))
-        return out[:self.m, :self.m] if out.shape != (self.m, self.m) else out
+        m = self.m
+        if out is None:
+            out = torch.empty((m, m), dtype=dtype, device=self.ctx.torch_device)
+        elif not isinstance(out, torch.Tensor) or out.dim() != 2:
+            raise ValueError("out must be a 2-D tensor of at least [m, m] = [%d, %d]" % (m, m))
+        op, ld = A.matrix(out, dtype, m, m, self.ctx.torch_device, "out")
+        L.check(fn(self._h, None if o is None else o.ctypes.data_as(C.c_void_p), op, ld))
+        return out[:m, :m] if out.shape != (m, m) else out
 
     def counts(self, order=None, out=None):
         """int32 [m, m] device tensor holding the exact u32 counts (optionally reordered: out[a, b] = C[order[a], order[b]])"""
@@ -1228,17 +1094,37 @@ def _alias_tensor(ptr, n, dtype, device, owner=None):
     return torch.as_tensor(_CudaArrayView(ptr, n, typestr, owner), device=device)
 
 
-def _check_slice_args(scores, dim, ngroups, nd):
-    """a slice reduction indexes score columns up to prod(ngroups): the matrix must have them all (the kernel skips and
-    reports an offset past the row, MSC_EDEVICE, but a consistent caller never gets there)"""
+def _relation_blocks(ctx, shape, zs, ngroups, pos, ncells):
+    """msc_relation_blocks for both relation views: pos None = dense"""
+    nd = len(shape)
+    if len(zs) != nd or len(ngroups) != nd:
+        raise ValueError("one assignment vector and one cluster count per dimension")
+    zp = (C.c_void_p * nd)(*[A.flat(z, torch.int32, n, ctx.torch_device, "an assignment vector") for z, n in zip(zs, shape)])
+    out = torch.empty(max(ncells, 1), dtype=torch.int32, device=ctx.torch_device)
+    L.check(ctx.lib.msc_relation_blocks(ctx._h, nd, (C.c_uint64 * nd)(*shape), zp, (C.c_uint32 * nd)(*[int(k) for k in ngroups]),
+                                        None if pos is None else A.ptr(pos), ncells, A.ptr(out)))
+    return out[:ncells]
+
+
+def _relation_slice_scores(ctx, shape, scores, off, dim, ngroups, ncells, seg, ids):
+    """msc_relation_slice_scores for both relation views: seg = ids = None = dense.  A slice reduction indexes score
+    columns up to prod(ngroups): the matrix must have them all (the kernel skips and reports an offset past the row,
+    MSC_EDEVICE, but a consistent caller never gets there)"""
+    nd, dev = len(shape), ctx.torch_device
     if len(ngroups) != nd or not 0 <= int(dim) < nd:
         raise ValueError("one cluster count per dimension and a dimension inside the relation")
-    nblocks = 1
-    for k in ngroups:
+    nblocks = stride = 1
+    for d, k in enumerate(ngroups):
         nblocks *= int(k)
-    if scores.dim() != 2 or scores.shape[1] < nblocks:
-        raise ValueError("scores has %d columns but the cluster counts %s make %d blocks" %
-                         (scores.shape[1] if scores.dim() == 2 else -1, list(ngroups), nblocks))
+        if d > dim:
+            stride *= int(k)
+    sp, ld = A.matrix(scores, torch.float32, ncells, nblocks, dev, "scores")
+    op = A.flat(off, torch.int32, ncells, dev, "off")
+    out = torch.empty((shape[dim], int(ngroups[dim])), dtype=torch.float32, device=dev)
+    L.check(ctx.lib.msc_relation_slice_scores(ctx._h, sp, ld, nd, (C.c_uint64 * nd)(*shape), dim,
+                                              None if seg is None else A.ptr(seg), None if ids is None else A.ptr(ids), op,
+                                              int(ngroups[dim]), stride, shape[dim], A.ptr(out), out.stride(0)))
+    return out
 
 
 class RelationView(object):
@@ -1264,19 +1150,7 @@ class RelationView(object):
 
     def blocks(self, zs, ngroups):
         """zs: one int32 device tensor per dimension; ngroups: clusters per dimension -> int32 [ncells]"""
-        if len(zs) != len(self.shape) or len(ngroups) != len(self.shape):
-            raise ValueError("one assignment vector and one cluster count per dimension")
-        for z, n in zip(zs, self.shape):
-            if z.dtype != torch.int32 or z.numel() != n or not z.is_contiguous():
-                raise ValueError("assignments must be contiguous int32 tensors of the dimension's length")
-        nd = len(self.shape)
-        out = torch.empty(self.cells.nrows, dtype=torch.int32, device=self.ctx.torch_device)
-        shape = (C.c_uint64 * nd)(*self.shape)
-        zp = (C.c_void_p * nd)(*[z.data_ptr() for z in zs])
-        kg = (C.c_uint32 * nd)(*[int(k) for k in ngroups])
-        L.check(self.ctx.lib.msc_relation_blocks(self.ctx._h, nd, shape, zp, kg, None, self.cells.nrows,
-                                                 C.c_void_p(out.data_ptr())))
-        return out
+        return _relation_blocks(self.ctx, self.shape, zs, ngroups, None, self.cells.nrows)
 
     def slice_offsets(self, zs, ngroups, dim):
         """block index of every cell with dimension `dim`'s cluster taken as 0 (-1 where another entity of the cell is
@@ -1289,21 +1163,7 @@ class RelationView(object):
         """irm's slice reduction (msc_relation_slice_scores): out[e, g] = sum over the cells of slice (dim, e) of the
         cell's score against block (g, the cell's other clusters).  scores: [ncells, >= prod(ngroups)] from
         State.score_value on self.cells; off: slice_offsets(...).  -> float32 [shape[dim], ngroups[dim]]"""
-        nd = len(self.shape)
-        _check_slice_args(scores, dim, ngroups, nd)
-        if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[0] != self.cells.nrows:
-            raise ValueError("scores must be a row-major float32 [ncells, nblocks] tensor")
-        if off.dtype != torch.int32 or off.numel() != self.cells.nrows or not off.is_contiguous():
-            raise ValueError("off must be a contiguous int32 tensor of ncells entries")
-        stride = 1
-        for k in ngroups[dim + 1:]:
-            stride *= int(k)
-        out = torch.empty((self.shape[dim], int(ngroups[dim])), dtype=torch.float32, device=self.ctx.torch_device)
-        shape = (C.c_uint64 * nd)(*self.shape)
-        L.check(self.ctx.lib.msc_relation_slice_scores(self.ctx._h, C.c_void_p(scores.data_ptr()), scores.stride(0), nd, shape, dim,
-                                                       None, None, C.c_void_p(off.data_ptr()), int(ngroups[dim]), stride,
-                                                       self.shape[dim], C.c_void_p(out.data_ptr()), out.stride(0)))
-        return out
+        return _relation_slice_scores(self.ctx, self.shape, scores, off, dim, ngroups, self.cells.nrows, None, None)
 
 
 class SparseRelationView(object):
@@ -1341,18 +1201,7 @@ class SparseRelationView(object):
         return int(self._csr.nnz)
 
     def blocks(self, zs, ngroups):
-        if len(zs) != 2 or len(ngroups) != 2:
-            raise ValueError("one assignment vector and one cluster count per dimension")
-        for z, n in zip(zs, self.shape):
-            if z.dtype != torch.int32 or z.numel() != n or not z.is_contiguous():
-                raise ValueError("assignments must be contiguous int32 tensors of the dimension's length")
-        out = torch.empty(max(self.nnz(), 1), dtype=torch.int32, device=self.ctx.torch_device)
-        shape = (C.c_uint64 * 2)(*self.shape)
-        zp = (C.c_void_p * 2)(*[z.data_ptr() for z in zs])
-        kg = (C.c_uint32 * 2)(*[int(k) for k in ngroups])
-        L.check(self.ctx.lib.msc_relation_blocks(self.ctx._h, 2, shape, zp, kg, C.c_void_p(self._pos.data_ptr()), self.nnz(),
-                                                 C.c_void_p(out.data_ptr())))
-        return out[:self.nnz()]
+        return _relation_blocks(self.ctx, self.shape, zs, ngroups, self._pos, self.nnz())
 
     def slice_offsets(self, zs, ngroups, dim):
         zs = list(zs)
@@ -1362,16 +1211,5 @@ class SparseRelationView(object):
     def slice_scores(self, scores, off, dim, ngroups):
         """out[e, g] = sum over the stored cells of row / column e of the cell's score against block (g, the other
         entity's cluster) -- msc_relation_slice_scores with the CSR rows (dim 0) or the transpose's (dim 1)"""
-        _check_slice_args(scores, dim, ngroups, 2)
-        if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[0] != self.nnz():
-            raise ValueError("scores must be a row-major float32 [nnz, nblocks] tensor")
-        if off.dtype != torch.int32 or off.numel() != self.nnz() or not off.is_contiguous():
-            raise ValueError("off must be a contiguous int32 tensor of nnz entries")
-        stride = int(ngroups[1]) if dim == 0 else 1
-        out = torch.empty((self.shape[dim], int(ngroups[dim])), dtype=torch.float32, device=self.ctx.torch_device)
-        shape = (C.c_uint64 * 2)(*self.shape)
-        L.check(self.ctx.lib.msc_relation_slice_scores(
-            self.ctx._h, C.c_void_p(scores.data_ptr()), scores.stride(0), 2, shape, dim, C.c_void_p(self._seg[dim].data_ptr()),
-            C.c_void_p(self._ids[dim].data_ptr()), C.c_void_p(off.data_ptr()), int(ngroups[dim]), stride, self.shape[dim],
-            C.c_void_p(out.data_ptr()), out.stride(0)))
-        return out
+        return _relation_slice_scores(self.ctx, self.shape, scores, off, dim, ngroups, self.nnz(), self._seg[dim],
+                                      self._ids[dim])
