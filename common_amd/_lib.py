@@ -38,6 +38,10 @@ LINKAGE_MAX_N = 1 << 16               # msc_linkage_single: n at most
 DISTANCES_MAX_ROWS = 1 << 15          # msc_partition_distances: m at most
 DISTANCES_MAX_CLUSTERS = 1 << 10      # ... and clusters a partition at most
 DISTANCES_LDS_CELLS = 15 * 1024       # ... and the cells K_a x K_b of a pair whose table stays in LDS
+REFINE_VI_MAX_ROWS = 1 << 15          # msc_partition_refine_vi: m at most
+REFINE_VI_MAX_SAMPLES = 1 << 16       # ... samples at most
+REFINE_VI_MAX_CLUSTERS = 1 << 10      # ... and max_clusters, and the clusters of a sample, at most
+VI_TABLE_SCALE = 1 << 24              # msc_vi_table: F(n) = rint(n log2 n VI_TABLE_SCALE)
 
 
 class MicroscopesHipError(RuntimeError):
@@ -196,6 +200,10 @@ _SIGS = {
     "msc_linkage_single": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "msc_partition_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
                                           C.c_uint32, C.c_uint32] + [C.c_void_p] * 8),
+    "msc_vi_table": (C.c_int, [C.c_uint32, C.c_void_p]),
+    "msc_partition_refine_vi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32] +
+                                [C.c_void_p] * 4),
 }
 
 EXPORTS = tuple(sorted(_SIGS))

@@ -105,7 +105,8 @@ static int device_error_word(int device, volatile uint32_t **host_out) {
     MSC_HIP(hipHostGetDevicePointer(&d, h, 0));
     uint32_t *w = static_cast<uint32_t *>(d);
     if (bind_error_word_score(w) || bind_error_word_sweep(w) || bind_error_word_state(w) || bind_error_word_seq(w) ||
-        bind_error_word_query(w) || bind_error_word_refine(w) || bind_error_word_distance(w))
+        bind_error_word_query(w) || bind_error_word_refine(w) || bind_error_word_distance(w) ||
+        bind_error_word_refine_vi(w))
       return fail(MSC_EHIP, "binding the device error word failed: %s", hipGetErrorString(hipGetLastError()));
     words[device] = h;
   }
@@ -129,7 +130,8 @@ static int device_error_check(msc_context *ctx) {
   if (code & 16u) add("msc_zmatrix_add: a label outside [0, nlabels) (that sample was skipped; detail: row of z)");
   if (code & 32u) add("msc_zmatrix_partition_refine: a start with more than max_clusters clusters (its outputs mean nothing; detail: start of its chunk)");
   if (code & 64u) add("msc_partition_distances: a partition with more than 1024 clusters (every output it takes part in is -1 or NaN; detail: its index in its set)");
-  if (code & ~127u) add("unknown device-side error");
+  if (code & 128u) add("msc_partition_refine_vi: a sample with more than 1024 clusters or a start with more than max_clusters (its outputs mean nothing; detail: its index)");
+  if (code & ~255u) add("unknown device-side error");
   return fail(MSC_EDEVICE, "reported by an earlier kernel on device %d: %s [detail of the first: %u]; rebuild the affected state's tables",
               ctx->device, what.c_str(), detail);
 }
@@ -4326,6 +4328,143 @@ extern "C" int msc_partition_distances(msc_context *ctx, const int32_t *a_dev, u
       }
       if (lds && launch_pd_pairs(s, ctx->num_cus, PdRoute::lds, p)) return fail(MSC_EHIP, "k_pd_pairs launch failed");
     }
+  }
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// greedy refinement under the exact expected variation of information (kernels_refine_vi.hip)
+// ---------------------------------------------------------------------------
+extern "C" int msc_vi_table(uint32_t m, int64_t *host_F) {
+  MSC_REQUIRE(host_F != nullptr, "msc_vi_table: host_F is null");
+  host_F[0] = 0;
+  for (uint32_t n = 1; n <= m; n++) host_F[n] = (int64_t)std::rint((double)n * std::log2((double)n) * 16777216.0);
+  return MSC_OK;
+}
+
+template <typename T>
+static int vi_reserve(msc_context *ctx, DevBuf<T> &buf, size_t n, const char *what) {
+  const hipError_t e = reserve_synced(ctx->stream, buf, n);
+  if (e == hipSuccess) return MSC_OK;
+  (void)hipGetLastError();
+  return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "msc_partition_refine_vi: the %s of %zu bytes: %s", what,
+              n * sizeof(T), hipGetErrorString(e));
+}
+
+extern "C" int msc_partition_refine_vi(msc_context *ctx, const int32_t *samples_dev, uint64_t lds, uint32_t nsamples,
+                                       uint32_t m, const int32_t *start_dev, uint64_t ld, uint32_t nstarts,
+                                       uint32_t max_sweeps, uint32_t max_clusters, const uint32_t *host_order,
+                                       size_t workspace_bytes, uint32_t flags, int32_t *labels_dev, int64_t *decrease_dev,
+                                       uint32_t *sweeps_dev, uint64_t *moves_dev) {
+  const char *who = "msc_partition_refine_vi";
+  MSC_REQUIRE(ctx && samples_dev && start_dev, "%s: null argument", who);
+  MSC_REQUIRE(flags == 0, "%s: flags = %u (none is defined)", who, flags);
+  MSC_REQUIRE(nsamples > 0 && nstarts > 0 && m > 0, "%s: nsamples = %u, nstarts = %u, m = %u: none may be 0", who, nsamples,
+              nstarts, m);
+  MSC_REQUIRE(lds >= m && ld >= m, "%s: lds = %llu, ld = %llu below m = %u", who, (unsigned long long)lds,
+              (unsigned long long)ld, m);
+  MSC_REQUIRE(max_clusters >= 1 && max_clusters <= m, "%s: max_clusters = %u outside [1, m = %u]", who, max_clusters, m);
+  if (host_order) {
+    std::vector<uint8_t> seen(m, 0);
+    for (uint32_t a = 0; a < m; a++) {
+      MSC_REQUIRE(host_order[a] < m && !seen[host_order[a]], "%s: order is not a permutation of [0, %u): entry %u is %u",
+                  who, m, a, host_order[a]);
+      seen[host_order[a]] = 1;
+    }
+  }
+  if (m > kViMaxRows || nsamples > kViMaxSamples || max_clusters > kViMaxClusters)
+    return fail(MSC_EUNSUPPORTED, "%s: m = %u, nsamples = %u, max_clusters = %u: at most %u rows, %u samples and %u clusters",
+                who, m, nsamples, max_clusters, kViMaxRows, kViMaxSamples, kViMaxClusters);
+  // the table, and the widths of everything made of it: |D| <= 3 S G_max and decrease <= 2 S F(m) stay under 2^62
+  if (ctx->vi_G_m != m || ctx->vi_G_host.size() != m) {
+    std::vector<int64_t> F((size_t)m + 1);
+    MSC_TRY(msc_vi_table(m, F.data()));
+    ctx->vi_G_m = 0;
+    ctx->vi_G_host.resize(m);
+    for (uint32_t n = 0; n < m; n++) ctx->vi_G_host[n] = F[n + 1] - F[n];
+  }
+  {
+    const long double lim = 4611686018427387904.0L;                 // 2^62
+    long double fm = 0.0L, gmax = 0.0L;
+    for (uint32_t n = 0; n < m; n++) fm += (long double)ctx->vi_G_host[n], gmax = std::max(gmax, (long double)ctx->vi_G_host[n]);
+    if (3.0L * nsamples * gmax >= lim || 2.0L * nsamples * fm >= lim)
+      return fail(MSC_EUNSUPPORTED, "%s: nsamples = %u, m = %u: a gain or the decrease may pass 62 bits", who, nsamples, m);
+  }
+  MSC_TRY(device_error_check(ctx));
+  MSC_HIP(hipSetDevice(ctx->device));
+  if (!labels_dev && !decrease_dev && !sweeps_dev && !moves_dev) return MSC_OK;
+  const hipStream_t s = ctx->stream;
+  const uint64_t ldi = ((uint64_t)m + 3u) & ~(uint64_t)3u;
+  const uint32_t S = nsamples, kcap = round_up(max_clusters, kViCellPad);
+  const size_t budget = workspace_bytes ? workspace_bytes : (size_t)2 << 30;
+  uint32_t chunk = std::min<uint32_t>(nstarts, 4096);
+  uint64_t cells_per_start = 0;
+  if (max_sweeps > 0) {
+    // the samples: ids, cluster counts, their running sums and the rows' stretch indices.  The host waits once, for the
+    // total of the cluster counts: it is what a start's cells, and so the chunk of starts, are sized by
+    MSC_TRY(vi_reserve(ctx, ctx->vi_sample_ids, (size_t)S * ldi, "ids of the samples"));
+    MSC_TRY(vi_reserve(ctx, ctx->vi_L, S, "cluster counts of the samples"));
+    MSC_TRY(vi_reserve(ctx, ctx->vi_off, (size_t)S + 1, "running sums of the cluster counts"));
+    MSC_TRY(vi_reserve(ctx, ctx->vi_row, (size_t)m * S, "stretch indices of the rows"));
+    if (launch_vi_canon(s, samples_dev, lds, m, kViMaxClusters, S, 0, ctx->vi_sample_ids, ldi, ctx->vi_L, nullptr))
+      return fail(MSC_EHIP, "k_vi_canon launch failed");
+    if (launch_vi_rows(s, ctx->vi_sample_ids, ldi, ctx->vi_L, S, m, ctx->vi_off, ctx->vi_row))
+      return fail(MSC_EHIP, "k_vi_offsets / k_vi_transpose launch failed");
+    uint32_t stretches = 0;
+    MSC_HIP(hipMemcpyAsync(&stretches, ctx->vi_off + S, 4, hipMemcpyDeviceToHost, s));
+    MSC_HIP(hipStreamSynchronize(s));
+    cells_per_start = (uint64_t)stretches * kcap;
+    const uint64_t bytes = cells_per_start * 2u;
+    if (bytes > budget)
+      return fail(MSC_EUNSUPPORTED, "%s: the contingency cells of one start take %llu bytes (%u stretches of %u cells of 2 "
+                  "bytes), workspace_bytes allows %zu", who, (unsigned long long)bytes, stretches, kcap, budget);
+    chunk = (uint32_t)std::min<uint64_t>(chunk, budget / bytes);
+    MSC_TRY(vi_reserve(ctx, ctx->vi_cells, (size_t)chunk * cells_per_start, "contingency cells"));
+    if (!ctx->vi_G || ctx->vi_G_m != m) {
+      ctx->vi_G_m = 0;
+      MSC_TRY(vi_reserve(ctx, ctx->vi_G, m, "table of G"));
+      MSC_HIP(hipMemcpyAsync(ctx->vi_G, ctx->vi_G_host.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+      MSC_HIP(hipStreamSynchronize(s));
+      ctx->vi_G_m = m;
+    }
+    if (host_order) {
+      MSC_TRY(vi_reserve(ctx, ctx->vi_order, m, "visiting order"));
+      MSC_HIP(hipMemcpyAsync(ctx->vi_order, host_order, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    }
+  }
+  MSC_TRY(vi_reserve(ctx, ctx->vi_ids, (size_t)chunk * ldi, "cluster ids"));
+  MSC_TRY(vi_reserve(ctx, ctx->vi_st, chunk, "running totals"));
+  ViSweepArgs p;
+  p.row = ctx->vi_row, p.S = S, p.m = m, p.max_clusters = max_clusters, p.kcap = kcap;
+  p.order = host_order ? ctx->vi_order.get() : nullptr, p.G = ctx->vi_G, p.ids = ctx->vi_ids, p.ldi = ldi;
+  p.cells = ctx->vi_cells, p.cells_per_start = cells_per_start, p.st = ctx->vi_st;
+  std::vector<RefineStart> st_host;
+  for (uint32_t c0 = 0; c0 < nstarts; c0 += chunk) {
+    const uint32_t k = std::min(chunk, nstarts - c0);
+    if (launch_vi_canon(s, start_dev + (uint64_t)c0 * ld, ld, m, max_clusters, k, c0, ctx->vi_ids, ldi, nullptr, ctx->vi_st))
+      return fail(MSC_EHIP, "k_vi_canon launch failed");
+    if (max_sweeps > 0) {
+      MSC_HIP(hipMemsetAsync(ctx->vi_cells, 0, (size_t)k * cells_per_start * 2u, s));
+      if (launch_vi_count(s, ctx->num_cus, p, k)) return fail(MSC_EHIP, "k_vi_count launch failed");
+    }
+    for (uint32_t sweep = 0; sweep < max_sweeps; sweep++) {
+      // every sweep is a launch and the stream is not waited for -- up to kViBlindSweeps of them; a caller who allows
+      // more pays one wait per kViBlindSweeps further ones, so that the launches end when the starts have
+      constexpr uint32_t kViBlindSweeps = 64;
+      if (sweep >= kViBlindSweeps && sweep % kViBlindSweeps == 0) {
+        st_host.resize(k);
+        MSC_HIP(hipMemcpyAsync(st_host.data(), ctx->vi_st, (size_t)k * sizeof(RefineStart), hipMemcpyDeviceToHost, s));
+        MSC_HIP(hipStreamSynchronize(s));
+        bool any = false;
+        for (uint32_t i = 0; i < k; i++) any = any || st_host[i].active != 0u;
+        if (!any) break;
+      }
+      if (launch_vi_sweep(s, p, k)) return fail(MSC_EHIP, "k_vi_sweep launch failed");
+    }
+    if (launch_vi_finish(s, ctx->vi_ids, ldi, m, max_clusters, k, ctx->vi_st,
+                         labels_dev ? labels_dev + (uint64_t)c0 * m : nullptr, decrease_dev ? decrease_dev + c0 : nullptr,
+                         sweeps_dev ? sweeps_dev + c0 : nullptr, moves_dev ? moves_dev + c0 : nullptr))
+      return fail(MSC_EHIP, "k_vi_finish launch failed");
   }
   return MSC_OK;
 }

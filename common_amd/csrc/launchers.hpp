@@ -408,4 +408,44 @@ int launch_pd_canon(hipStream_t stream, const int32_t *lab, uint64_t ld, uint32_
                     uint32_t *nclusters);
 int launch_pd_pairs(hipStream_t stream, int num_cus, PdRoute route, const PdPairArgs &p);
 
+// kernels_refine_vi.hip (msc_partition_refine_vi): greedy row moves under the exact expected VI, a workgroup per start.
+// launch_vi_canon turns samples (cap = kViMaxClusters; count receives the cluster counts L) or starts (cap =
+// max_clusters; st receives the running totals) into 16-bit ids [n][ldi] and reports MSC_DEVERR_VI_CLUSTERS for one with
+// more clusters than cap; launch_vi_rows makes off[S + 1] (the running sum of L) and row[m][S] = off[s] + id_s[a];
+// launch_vi_count fills the zeroed u16 cells [nstarts][off[S] kcap] of the starts; one launch_vi_sweep is one sweep of
+// every start that is still active; launch_vi_finish writes the outputs (each nullable).  -2: a shape beyond the caps
+constexpr uint32_t kViMaxRows = kZmRefineMaxRows;
+constexpr uint32_t kViMaxClusters = kZmRefineMaxClusters;
+constexpr uint32_t kViMaxSamples = 1u << 16;
+constexpr uint32_t kViCellPad = 32;                          // ids a block of cells; kcap: max_clusters rounded up to it
+struct ViSweepArgs {
+  const uint32_t *row;             // [m][S]
+  uint32_t S, m, max_clusters, kcap;
+  const uint32_t *order;           // nullable
+  const int64_t *G;                // [m]: G(n) = F(n + 1) - F(n) of msc_vi_table
+  uint16_t *ids;                   // [nstarts][ldi]
+  uint64_t ldi;
+  uint16_t *cells;                 // [nstarts][cells_per_start]
+  uint64_t cells_per_start;
+  RefineStart *st;
+};
+// the one place that picks the sweep kernel's instantiation: the 64-id slots a thread keeps sums for in one pass over
+// the samples, 1, 2, 4 or 8 (sixteen would not fit the 128 registers of a thread of sixteen waves: past 512 ids in use
+// the kernel makes two passes)
+inline int route_vi_refine(uint32_t kcap) {
+  int nk = 1;
+  while (nk < 8 && (uint32_t)nk * 64u < kcap) nk *= 2;
+  return nk;
+}
+int bind_error_word_refine_vi(uint32_t *word_dev);
+int launch_vi_canon(hipStream_t stream, const int32_t *lab, uint64_t ld, uint32_t m, uint32_t cap, uint32_t nparts,
+                    uint32_t part0, uint16_t *ids, uint64_t ldi, uint32_t *count, RefineStart *st);
+int launch_vi_rows(hipStream_t stream, const uint16_t *ids, uint64_t ldi, const uint32_t *L, uint32_t S, uint32_t m,
+                   uint32_t *off, uint32_t *row);
+int launch_vi_count(hipStream_t stream, int num_cus, const ViSweepArgs &p, uint32_t nstarts);
+int launch_vi_sweep(hipStream_t stream, const ViSweepArgs &p, uint32_t nstarts);
+int launch_vi_finish(hipStream_t stream, const uint16_t *ids, uint64_t ldi, uint32_t m, uint32_t max_clusters,
+                     uint32_t nstarts, const RefineStart *st, int32_t *labels, int64_t *decrease, uint32_t *sweeps,
+                     uint64_t *moves);
+
 }  // namespace msc

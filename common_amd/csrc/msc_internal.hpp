@@ -508,6 +508,18 @@ struct msc_context {
   msc::DevBuf<double> pd_log2;
   uint32_t pd_log2_n = 0;
   msc::DevBuf<uint32_t> pd_table;
+  // msc_partition_refine_vi (kernels_refine_vi.hip), allocated at first use and kept: the samples' ids [S][ldi], their
+  // cluster counts and running sums, the stretch indices [m][S], G of msc_vi_table for m = vi_G_m rows (0: none; the
+  // host copy is what the upload reads), the visiting order, and a chunk of starts' ids, totals and contingency cells
+  msc::DevBuf<uint16_t> vi_sample_ids;
+  msc::DevBuf<uint32_t> vi_L, vi_off, vi_row;
+  msc::DevBuf<int64_t> vi_G;
+  std::vector<int64_t> vi_G_host;
+  uint32_t vi_G_m = 0;
+  msc::DevBuf<uint32_t> vi_order;
+  msc::DevBuf<uint16_t> vi_ids;
+  msc::DevBuf<msc::RefineStart> vi_st;
+  msc::DevBuf<uint16_t> vi_cells;
 };
 
 struct msc_dataview {

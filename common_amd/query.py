@@ -12,6 +12,8 @@ Ghahramani) among candidate partitions, from exact integer sums over the co-clus
 ``msc_zmatrix_partition_*`` on the device, the same integers on both.  ``refine_partition`` takes partitions further by
 greedy row moves under Binder's loss until no single move helps (``msc_zmatrix_partition_refine`` on the device, plain
 numpy on the host, the same trajectory bit for bit), and ``point_estimate(refine=...)`` refines the best candidates.
+``refine_partition_vi`` and ``vi_estimate(refine=...)`` do the same under the exact expected variation of information,
+with integer gains from a fixed-point table of n log2 n (``vi_table``, ``msc_partition_refine_vi``).
 ``partition_distances`` is what the counts cannot give: Binder's distance and the variation of information between every
 partition of one set and every partition of another (``msc_partition_distances`` on the device, ``np.unique`` and a
 contingency table per pair on the host, the same integers on both).  ``adjusted_rand``, ``expected_loss`` (the EXACT
@@ -24,7 +26,9 @@ import collections
 import numpy as np
 import torch
 
-from ._lib import DISTANCES_MAX_CLUSTERS, LINKAGE_MAX_N, ZMATRIX_MAX_LABELS, ZMATRIX_REFINE_MAX_CLUSTERS
+from . import _lib
+from ._lib import (DISTANCES_MAX_CLUSTERS, LINKAGE_MAX_N, REFINE_VI_MAX_CLUSTERS, VI_TABLE_SCALE, ZMATRIX_MAX_LABELS,
+                   ZMATRIX_REFINE_MAX_CLUSTERS)
 from .runtime import Context, ZMatrix
 
 _HOST_CHUNK_FLOATS = 1 << 23      # one-hot block of the numpy path: at most 64 MiB of float64
@@ -819,24 +823,175 @@ def expected_loss(assignments, candidates=None, ctx=None):
     return _expected(samples, cands, ctx)
 
 
-def vi_estimate(assignments, candidates=None, ctx=None):
+def vi_estimate(assignments, candidates=None, ctx=None, refine=0, starts=8):
     """ONE clustering out of posterior samples by the exact expected variation of information: ``point_estimate`` with
     ``expected_loss``'s ``vi`` where ``loss="vi"`` has the bound.  Returns the same ``PointEstimate`` tuple of numpy
     values: ``labels`` of the winner (numbered by first row), ``index`` (the lowest among equal losses), ``losses`` (the
-    expected VI of every candidate, bits) and ``confidence`` as ``point_estimate`` computes it."""
+    expected VI of every candidate, bits) and ``confidence`` as ``point_estimate`` computes it.
+
+    ``refine > 0``: the ``starts`` candidates of lowest expected VI (ties to the lowest index) are each refined by greedy
+    row moves for at most ``refine`` sweeps (``refine_partition_vi``) and the best refined partition by its exact float64
+    expected VI is returned (ties to the better-ranked start): ``labels`` and ``confidence`` are its own, ``index`` is the
+    candidate it grew from, ``losses`` stay the candidates' own."""
+    refine, starts = int(refine), int(starts)
+    if refine < 0 or starts < 1:
+        raise ValueError("refine must not be negative and starts must be at least 1")
     samples, ctx = _samples_for_distances(assignments, ctx)
     sc = _Scorer(samples, ctx)
     try:
         c = sc.candidates(candidates)
         vi = _expected(samples, c, ctx).vi
         losses = vi.cpu().numpy() if isinstance(vi, torch.Tensor) else np.asarray(vi)
+        valid = int(samples.shape[0])
+        if refine > 0:
+            top = np.argsort(losses, kind="stable")[:starts]
+            picked = c[torch.from_numpy(top).to(c.device)] if isinstance(c, torch.Tensor) else c[top]
+            got = _refine_vi(samples, picked, refine, None, None, ctx)
+            rvi = _expected(samples, got[0], ctx).vi
+            rvi = rvi.cpu().numpy() if isinstance(rvi, torch.Tensor) else np.asarray(rvi)
+            best = int(np.argmin(rvi))
+            labels = got[0][best]
+            labels = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else labels
+            w, size = sc.sums_of_positions(labels)
+            confidence = w[0].astype(np.float64) / (float(valid) * size[0].astype(np.float64))
+            return PointEstimate(_renumber(labels), int(top[best]), losses, confidence)
         index = int(np.argmin(losses))
         w, size = sc.sums(c[index:index + 1])
-        valid = int(samples.shape[0])
         confidence = w[0].astype(np.float64) / (float(valid) * size[0].astype(np.float64))
         return PointEstimate(_renumber(sc.selected(c[index])), index, losses, confidence)
     finally:
         sc.close()
+
+
+# ---- greedy refinement under the exact expected VI --------------------------------------------------------------------
+RefinedVI = collections.namedtuple("RefinedVI", ["labels", "vi", "vi_start", "decrease", "sweeps", "moves", "valid"])
+_INT64_MAX = np.iinfo(np.int64).max
+
+
+def vi_table(m):
+    """``F[0..m]`` of ``msc_vi_table``: int64, ``F(0) = 0`` and ``F(n) = rint(n log2(n) 2^24)``, computed by the library on
+    the host (no GPU is needed).  The one table that the host path and the kernels of ``refine_partition_vi`` share."""
+    m = int(m)
+    if m < 0 or m >= 2 ** 32:
+        raise ValueError("m must lie in [0, 2^32)")
+    F = np.empty(m + 1, dtype=np.int64)
+    _lib.check(_lib.load().msc_vi_table(m, F.ctypes.data))
+    return F
+
+
+def _refine_vi_host(samples, starts, max_sweeps, max_clusters, order):
+    """The rule of msc_partition_refine_vi (include/microscopes_hip.h) in plain numpy, all int64: samples [S, m], starts
+    [nstarts, m] -> (labels int32 [nstarts, m], decrease int64, sweeps int32, moves int64)"""
+    samples, starts = np.asarray(samples), np.asarray(starts)
+    S, m = samples.shape
+    ns = starts.shape[0]
+    K = int(max_clusters)
+    if K < 1 or K > m:
+        raise ValueError("max_clusters must lie in [1, m = %d]" % m)
+    if int(max_sweeps) < 0:
+        raise ValueError("max_sweeps must not be negative")
+    if order is not None and not _is_permutation(np.asarray(order), m):
+        raise ValueError("not a valid permutation")
+    visit = np.arange(m) if order is None else np.asarray(order).astype(np.int64)
+    G = np.diff(vi_table(m))                           # G[n] = F(n + 1) - F(n), 0 <= n < m
+    sid, _ = _dense_labels(samples)                    # per sample, ids in [0, L_s)
+    L = sid.max(axis=1).astype(np.int64) + 1
+    off = np.concatenate(([0], np.cumsum(L)[:-1]))
+    stretch = off[:, None] + sid                       # [S, m]: the row of cells that row a touches in sample s
+    labels = np.empty((ns, m), dtype=np.int32)
+    decrease = np.zeros(ns, dtype=np.int64)
+    sweeps = np.zeros(ns, dtype=np.int32)
+    moves = np.zeros(ns, dtype=np.int64)
+    for i in range(ns):
+        ids = _renumber(starts[i]).astype(np.int64)
+        if int(ids.max()) + 1 > K:
+            raise ValueError("a start holds %d clusters, more than max_clusters = %d" % (int(ids.max()) + 1, K))
+        n = np.bincount(ids, minlength=K).astype(np.int64)
+        N = np.zeros((int(L.sum()), K), dtype=np.int64)
+        np.add.at(N, (stretch, np.broadcast_to(ids, (S, m))), 1)
+        dec = 0
+        for _ in range(int(max_sweeps)):
+            moved = 0
+            for a in visit:
+                c = int(ids[a])
+                r = stretch[:, a]
+                n[c] -= 1                              # n' from here on
+                N[r, c] -= 1
+                D = S * G[n] - 2 * G[N[r]].sum(axis=0)
+                there = n > 0
+                d_cur = int(D[c]) if there[c] else 0
+                target, d_target = -1, 0
+                if there.any():
+                    target = int(np.argmin(np.where(there, D, _INT64_MAX)))     # the first of the smallest: the lowest id
+                    d_target = int(D[target])
+                    if there[c] and d_target > 0:
+                        free = np.flatnonzero(n == 0)
+                        if free.size:
+                            target, d_target = int(free[0]), 0
+                if target < 0 or not d_target < d_cur:
+                    target = c
+                else:
+                    dec += d_cur - d_target
+                    moved += 1
+                n[target] += 1
+                N[r, target] += 1
+                ids[a] = target
+            sweeps[i] += 1
+            moves[i] += moved
+            if moved == 0:
+                break
+        labels[i] = _renumber(ids)
+        decrease[i] = dec
+    return labels, decrease, sweeps, moves
+
+
+def _refine_vi(samples, starts, max_sweeps, max_clusters, order, ctx):
+    """(labels, decrease, sweeps, moves) of starts against samples, both already where they run"""
+    m = int(samples.shape[1])
+    if max_clusters is None:
+        max_clusters = min(m, REFINE_VI_MAX_CLUSTERS)
+    if ctx is None:
+        return _refine_vi_host(samples, starts, max_sweeps, max_clusters, order)
+    return ctx.partition_refine_vi(samples.contiguous(), starts.contiguous(), max_sweeps, max_clusters, order)
+
+
+def refine_partition_vi(assignments, starts=None, nstarts=8, max_sweeps=20, max_clusters=None, order=None, ctx=None):
+    """Partitions taken to a local optimum of the EXACT posterior expected variation of information by greedy row moves.
+
+    From each start, rows are visited in ascending order (or in ``order``, a permutation of the rows) and each moves to
+    the cluster -- or alone into a new one -- that lowers the expected VI most; a row stays on a tie, and an existing
+    cluster is preferred to a new one at equal gain.  Sweeps repeat until one moves nothing or ``max_sweeps`` have run.
+    The gains are integers, read from ``vi_table`` (n log2 n in fixed point, scale 2^%d), which the host path and the
+    kernel share (include/microscopes_hip.h states the rule in full under msc_partition_refine_vi): ``decrease /
+    (valid m 2^%d)`` is the expected VI lost, in bits, up to the table's rounding.  Every move lowers the integer
+    objective strictly, and a result with ``sweeps < max_sweeps`` is a local optimum of it: no single row move lowers it.
+
+    ``assignments`` as for ``expected_loss`` (an open ``ZMatrix`` keeps no samples and raises ``ValueError``); ``starts``
+    as ``partition_loss`` takes candidates, ``None`` for the ``nstarts`` samples of lowest exact expected VI (ties to the
+    lowest index).  ``max_clusters``: the most clusters a partition may hold on the way (``None``: ``min(m, %d)``); a start
+    that holds more raises ``ValueError``.  Returns a named tuple ``(labels [nstarts, m] int32, numbered from 0 in the
+    order of first row; vi float64 [nstarts], the exact expected VI of the results, and vi_start, of the starts, both from
+    expected_loss; decrease int64 [nstarts]; sweeps int32 [nstarts], the last one that moved nothing included; moves
+    int64 [nstarts]; valid)``.  Numpy input without ``ctx`` runs the host implementation, plain numpy; device tensors or
+    ``ctx=`` run ``msc_partition_refine_vi`` and return device tensors holding the same integers, bit for bit."""
+    samples, ctx = _samples_for_distances(assignments, ctx)
+    m, S = int(samples.shape[1]), int(samples.shape[0])
+    if starts is None:
+        nstarts = int(nstarts)
+        if nstarts < 1:
+            raise ValueError("nstarts must be at least 1")
+        vi_all = _expected(samples, samples, ctx).vi
+        vi_all = vi_all.cpu().numpy() if isinstance(vi_all, torch.Tensor) else np.asarray(vi_all)
+        top = np.argsort(vi_all, kind="stable")[:nstarts]
+        c = samples[torch.from_numpy(top).to(samples.device)] if isinstance(samples, torch.Tensor) else samples[top]
+    else:
+        c = _device_candidates(starts, ctx, m) if ctx is not None else _host_candidates(starts, m)
+    labels, decrease, sweeps, moves = _refine_vi(samples, c, max_sweeps, max_clusters, order, ctx)
+    return RefinedVI(labels, _expected(samples, labels, ctx).vi, _expected(samples, c, ctx).vi, decrease, sweeps, moves, S)
+
+
+refine_partition_vi.__doc__ %= (24, 24, REFINE_VI_MAX_CLUSTERS)
+assert VI_TABLE_SCALE == 1 << 24
 
 
 def credible_ball(assignments, estimate, level=0.95, metric="vi", ctx=None):

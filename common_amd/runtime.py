@@ -150,6 +150,58 @@ class Context(object):
         return (pairs_ab, nlogn_ab) + tuple(per)
     partition_distances.__doc__ %= (L.DISTANCES_MAX_CLUSTERS, L.DISTANCES_MAX_ROWS)
 
+    def partition_refine_vi(self, samples, starts, max_sweeps=20, max_clusters=None, order=None, workspace_bytes=0):
+        """Greedy refinement of partitions under the exact posterior expected variation of information
+        (msc_partition_refine_vi; include/microscopes_hip.h states the rule).  samples, starts: int32 tensors [m] or
+        [count, m] on this device whose rows are contiguous (any row stride >= m); any int32 value is a label.  From each
+        start rows move one at a time to the cluster, or into a new one, that lowers the expected VI most, sweep after
+        sweep (rows ascending, or in `order`, a permutation of [0, m)), until a sweep moves nothing or max_sweeps have
+        run.  max_clusters: the most clusters a partition may hold on the way (None: min(m, %d)).  The clusters are
+        counted before anything is launched: a start with more than max_clusters, or a sample with more than %d, raises
+        ValueError.  workspace_bytes (0: 2 GiB) bounds the contingency cells of the starts refined at a time; the outputs
+        do not depend on it.  Returns device tensors (labels int32 [nstarts, m], numbered by first row; decrease int64
+        [nstarts], in units of 1 / (S m 2^24) bits; sweeps int32 [nstarts], the last one that moved nothing included;
+        moves int64 [nstarts]), bit-equal to common_amd.query's host path.  Asynchronous after one wait."""
+        dev = self.torch_device
+        s2, S, lds = A.vectors(samples, dev, "samples")
+        m = int(s2.shape[-1])
+        c2, ns, ld = A.vectors(starts, dev, "starts", m)
+        if ns == 0:
+            raise ValueError("starts must be [m] or [count, m], neither 0")
+        if max_clusters is None:
+            max_clusters = min(m, L.REFINE_VI_MAX_CLUSTERS)
+        max_sweeps, max_clusters, workspace_bytes = int(max_sweeps), int(max_clusters), int(workspace_bytes)
+        if max_sweeps < 0 or max_sweeps >= 2 ** 32:
+            raise ValueError("max_sweeps must lie in [0, 2^32)")
+        if max_clusters < 1 or max_clusters > m:
+            raise ValueError("max_clusters must lie in [1, m = %d]" % m)
+        if workspace_bytes < 0:
+            raise ValueError("workspace_bytes must not be negative")
+        o = None
+        if order is not None:
+            o = np.asarray(order.cpu() if isinstance(order, torch.Tensor) else order)
+            if o.shape != (m,) or not np.issubdtype(o.dtype, np.integer) or (o.min() < 0 or o.max() >= m) or \
+                    np.unique(o).size != m:
+                raise ValueError("not a valid permutation")
+            o = np.ascontiguousarray(o, dtype=np.uint32)
+        if m <= L.REFINE_VI_MAX_ROWS and S <= L.REFINE_VI_MAX_SAMPLES and max_clusters <= L.REFINE_VI_MAX_CLUSTERS:
+            for p, cap, what in ((s2, L.REFINE_VI_MAX_CLUSTERS, "sample"), (c2, max_clusters, "start")):
+                srt = torch.sort(p.reshape(-1, m), dim=1).values
+                most = int(((srt[:, 1:] != srt[:, :-1]).sum(dim=1) + 1).max())
+                if most > cap:
+                    raise ValueError("a %s holds %d clusters, more than %d" % (what, most, cap))
+        labels = torch.empty((ns, m), dtype=torch.int32, device=dev)
+        decrease = torch.empty(ns, dtype=torch.int64, device=dev)
+        sweeps = torch.empty(ns, dtype=torch.int32, device=dev)
+        moves = torch.empty(ns, dtype=torch.int64, device=dev)
+        L.check(self.lib.msc_partition_refine_vi(
+            self._h, A.ptr(s2), lds, S, m, A.ptr(c2), ld, ns, max_sweeps, max_clusters,
+            None if o is None else o.ctypes.data_as(C.c_void_p), workspace_bytes, 0,
+            A.flat(labels, torch.int32, ns * m, dev, "labels"), A.flat(decrease, torch.int64, ns, dev, "decrease"),
+            A.flat(sweeps, torch.int32, ns, dev, "sweeps"), A.flat(moves, torch.int64, ns, dev, "moves")))
+        return labels, decrease, sweeps, moves
+    partition_refine_vi.__doc__ %= (L.REFINE_VI_MAX_CLUSTERS, L.REFINE_VI_MAX_CLUSTERS)
+
     def value_op(self, family, dim, op, hp, ss_record, value=None):
         """One group::{add_value, remove_value, score_value, score_data} call (base.hpp:25-28) as a batch
         of one on the device.  op: "add" | "remove" | "score_value" | "score_data".  `ss_record` is a

@@ -993,6 +993,67 @@ int msc_partition_distances(msc_context *ctx, const int32_t *a_dev, uint64_t lda
                             int64_t *pairs_a_dev, double *nlogn_a_dev, uint32_t *nclusters_a_dev,
                             int64_t *pairs_b_dev, double *nlogn_b_dev, uint32_t *nclusters_b_dev);
 
+/* ---- greedy refinement of partitions under the exact posterior expected variation of information ---- */
+/*
+ * msc_vi_table: F[0..m] on the host, F(0) = 0 and F(n) = rint(n log2(n) 2^24) for 1 <= n <= m, computed in double.  It
+ * needs no context and no device.  Everything that needs the table -- the kernels below, common_amd.query's host path --
+ * takes it from this one function, so no libm difference can separate the two.  G(n) = F(n + 1) - F(n), 0 <= n < m.
+ * MSC_EINVAL: host_F null.
+ *
+ * msc_partition_refine_vi: from each start, rows move one at a time to the cluster (or to a new one) that lowers the
+ * posterior expected VI most, sweep after sweep, until a sweep moves nothing.  Sample s is samples_dev + s * lds, a start
+ * is start_dev + i * ld (lds, ld >= m): int32 labels of the same m rows; any int32 value is a label and only equality is
+ * used.  The rule (the device and common_amd.query's host path implement exactly this; all integer):
+ *   objective  a partition c has sizes n_k; n^s_{k,l} counts the rows with id k in c and label l in sample s;
+ *              J(c) = S sum_k F(n_k) - 2 sum_s sum_{k,l} F(n^s_{k,l}).  J / (S m 2^24) is the posterior expected VI in
+ *              bits less its candidate-independent term, up to the table's rounding.  J is never formed, only differences.
+ *   ids        a start's labels are renumbered from 0 in the order of each label's first row; 1 <= max_clusters <= m is
+ *              the id capacity.
+ *   a sweep    visits the rows in ascending order, or in host_order (nullable: a permutation of [0, m), read before the
+ *              call returns).  For row a with id c and sample labels l_s:
+ *              (1) take a out: n'_k = n_k - [k == c], and n'^s likewise;
+ *              (2) for every k with n'_k > 0:  D_k = S G(n'_k) - 2 sum_s G(n'^s_{k, l_s}), an int64: J with a in k is J
+ *                  without a, plus D_k;
+ *              (3) D_cur = D_c if n'_c > 0, else 0 (a is alone already);
+ *              (4) the target is the existing cluster (n'_k > 0) of the smallest D_k, the lowest id among equals;
+ *              (5) a new cluster is taken instead in one case only, when all three hold: n'_c > 0; some id below
+ *                  max_clusters is empty; and that smallest D_k is strictly above 0.  Then a goes alone into the lowest
+ *                  empty id, with D = 0.  An existing cluster is preferred to a new one at equal D;
+ *              (6) a moves only if the target's D is strictly below D_cur; otherwise a stays;
+ *              (7) a move lowers J by exactly D_cur - D_target > 0, so the process ends, and the running int64
+ *                  `decrease` needs no second pass.
+ *   Sweeps repeat until one moves nothing or max_sweeps have run (0 is allowed: the outputs describe the start).
+ *   widths     G < 17 2^24 for m <= 32768, |D| <= 3 S G_max and decrease <= 2 S F(m): under 2^62 within the caps.  The
+ *              host checks these bounds before any launch: MSC_EUNSUPPORTED if they fail.
+ * Outputs, device pointers, each nullable (all null: nothing is done): labels_dev [nstarts][m] int32, numbered from 0 in
+ * the order of first row; decrease_dev [nstarts], J of the start less J of the output; sweeps_dev [nstarts], the sweeps
+ * run, the last one that moved nothing included; moves_dev [nstarts], all moves.  Starts are independent: any split of
+ * them over calls, and any workspace_bytes, gives the same outputs.
+ * The call is asynchronous on the context's stream but for one wait: the samples are canonicalised first (16-bit ids by
+ * first row, their cluster counts L_s) and the host waits for the sum of the L_s, which sizes the cells; max_sweeps == 0
+ * does not need them and waits for nothing.  Then, a chunk of starts at a time: the starts' ids, their contingency cells
+ * (u16, sum L_s x max_clusters rounded up to 32 a start, in blocks of 32 ids so that the ids in use lie together; counted
+ * once), one launch per sweep (one workgroup per start; a
+ * start that has converged returns at once) with no wait in between up to 64 sweeps; beyond 64 the host waits once per
+ * 64 further sweeps to see whether any start still moves.  msc_last_kernel(2) names the sweep kernel's instantiation.
+ * workspace_bytes (0: 2 GiB) bounds the cells of one chunk; a single start whose cells do not fit returns
+ * MSC_EUNSUPPORTED, naming the bytes it needs, with no output written.
+ * Caps: m <= 32768, nsamples <= 65536, max_clusters <= 1024: MSC_EUNSUPPORTED before anything is launched.  At most 1024
+ * clusters a sample, max_clusters a start: one with more is found on the device after canonicalisation; such a start is
+ * not refined, the outputs of a call with such a sample mean nothing, and the failure surfaces as MSC_EDEVICE at the next
+ * synchronising or launching call (the context stays good).  MSC_EINVAL: a null ctx, samples_dev or start_dev; nsamples,
+ * nstarts or m equal to 0; lds or ld below m; host_order not a permutation; max_clusters 0 or above m; flags != 0 (none is
+ * defined).  Workspaces the context owns, allocated at first use and kept: the samples' ids (S x 4 ceil(m / 4) x 2 bytes),
+ * the rows' stretch indices (m x S x 4 bytes), G (m x 8 bytes), and a chunk's ids, totals and cells: MSC_ENOMEM when they
+ * cannot be allocated.
+ */
+int msc_vi_table(uint32_t m, int64_t *host_F);
+int msc_partition_refine_vi(msc_context *ctx, const int32_t *samples_dev, uint64_t lds, uint32_t nsamples, uint32_t m,
+                            const int32_t *start_dev, uint64_t ld, uint32_t nstarts,
+                            uint32_t max_sweeps, uint32_t max_clusters, const uint32_t *host_order,
+                            size_t workspace_bytes, uint32_t flags,
+                            int32_t *labels_dev, int64_t *decrease_dev, uint32_t *sweeps_dev, uint64_t *moves_dev);
+
 #ifdef __cplusplus
 }
 #endif
