@@ -147,6 +147,13 @@ _SIGS = {
     "msc_chains_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                    C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64,
                                    C.c_uint32, C.c_void_p, C.c_void_p]),
+    # (ch, view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, pos0, npos, host_seeds, sweep, logw_dev,
+    #  visit_logp_dev, ld_logp)
+    "msc_chains_visit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                   C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
+    # (ch, host_ancestors, z_dev, ld_z, nrows)
+    "msc_chains_clone": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.c_uint64]),
     "msc_state_reduce_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "msc_state_commit_reduce": (C.c_int, [C.c_void_p]),

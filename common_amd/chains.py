@@ -10,6 +10,7 @@ import torch
 
 from . import _args as A
 from . import _lib as L
+from . import smc as S
 from .runtime import _I32_U32, State
 
 _U64 = (1 << 64) - 1
@@ -57,14 +58,15 @@ class ChainEnsemble(object):
 
     alpha: one float or nchains floats.  hps: one list with an hp (dict or packed array) per feature, used by every chain,
     or nchains such lists.  ens.states[c] is an ordinary State: get_ss, hp_slice, predictive_logp, set_hp, ... work on it
-    between sweeps.  ens.z: int32 [nchains, nrows] on the device once assign() / seat() has run."""
+    between sweeps.  ens.z: int32 [nchains, nrows] on the device once assign() / seat() has run; ens.logw: float64
+    [nchains] on the device, zeroed there, the log weights visit() adds the visits' log predictives to."""
 
     def __init__(self, ctx, features, ngroups, nchains, alpha=None, hps=None):
         nchains = int(nchains)
         if nchains < 1:
             raise ValueError("nchains must be >= 1")
         self.ctx, self.nchains, self.K = ctx, nchains, int(ngroups)
-        self.states, self._h, self.z = [], None, None
+        self.states, self._h, self.z, self.logw = [], None, None, None
         alphas = _per_chain("alpha", alpha, nchains, lambda a: isinstance(a, (int, float, np.floating, np.integer)))
         hpsets = _per_chain("hps", hps, nchains, lambda h: len(h) > 0 and isinstance(h[0], (dict, np.ndarray)))
         try:
@@ -95,6 +97,7 @@ class ChainEnsemble(object):
             raise ValueError("z must be int32 [nchains = %d, nrows = %d] or [nrows]" % (self.nchains, n))
         zt = zt.to(self.ctx.torch_device)
         self.z = (zt.expand(self.nchains, n) if zt.dim() == 1 else zt).contiguous().clone()
+        self.logw = torch.zeros(self.nchains, dtype=torch.float64, device=self.ctx.torch_device)
         for c, st in enumerate(self.states):
             st.accumulate(view, self.z[c])
         self._view = view
@@ -105,6 +108,11 @@ class ChainEnsemble(object):
         self.assign(view, torch.full((int(view.nrows),), -1, dtype=torch.int32))
         if seed is not None:
             self.sweep(view, 1, seed, sweep=sweep)
+
+    def _z_at(self, row0):
+        """pointer to column row0 of chain 0's row of self.z (the ensemble's own tensor: assign() made it)"""
+        zp = self.z.data_ptr() + 4 * row0
+        return C.c_void_p(zp)
 
     # the sweep ----------------------------------------------------------------
     def sweep(self, view, nsweeps, seed, sweep=0, order=None, trace_every=None, zmatrix=None, want_occupied=False, row0=0,
@@ -145,10 +153,9 @@ class ChainEnsemble(object):
         for st in self.states:
             st._drop_subsets()
             st._bound_view = view        # (the library keeps no reference to a view: the states do, for the last one bound)
-        zp = self.z.data_ptr() + 4 * row0            # (self.z is the ensemble's own tensor: assign() made it)
         L.check(self.ctx.lib.msc_chains_sweep(
             self._h, view._h, self.states[0]._cols(cols), row0, n, row0 if row_id0 is None else int(row_id0),
-            C.c_void_p(zp), int(self.z.stride(0)), op, ld_order, nsweeps, (C.c_uint64 * self.nchains)(*seeds), int(sweep),
+            self._z_at(row0), int(self.z.stride(0)), op, ld_order, nsweeps, (C.c_uint64 * self.nchains)(*seeds), int(sweep),
             0 if trace_every is None else int(trace_every),
             A.ptr(trace) if trace is not None and trace.numel() else None,
             A.ptr(occupied) if occupied is not None and occupied.numel() else None))
@@ -157,6 +164,134 @@ class ChainEnsemble(object):
         if trace is None:
             return None
         return (trace, occupied) if want_occupied else trace
+
+    # part of a sweep, with the visits' log predictives --------------------------
+    def _order(self, order, n):
+        if order is None:
+            return None, 0
+        op = A.flat(order, _I32_U32, n, self.ctx.torch_device, "order")
+        if tuple(order.shape) not in ((n,), (self.nchains, n)):
+            raise ValueError("order must hold [nrows] or [nchains, nrows] entries")
+        return op, (n if order.dim() == 2 else 0)
+
+    def visit(self, view, pos0, npos, seed, sweep=0, order=None, want_logp=False, row0=0, nrows=None, row_id0=None,
+              cols=None):
+        """positions [pos0, pos0 + npos) of the order of ONE sweep of every chain over rows [row0, row0 + nrows)
+        (msc_chains_visit; asynchronous): the visits sweep(view, 1, seed, sweep=sweep, order=order) makes at those
+        positions, bit for bit, so calls over [0, a), [a, b), ... [y, nrows) together are that sweep.  Every visit's log
+        predictive -- log p(row | the rows seated at that moment), from the draw's own max and sum -- is added to
+        ens.logw[c] in double, in visit order.  want_logp: -> float32 device tensor [nchains, nrows] of those increments
+        by order POSITION, NaN where this call made no visit; otherwise -> None."""
+        self._check_open()
+        if self.z is None:
+            raise ValueError("no assignment yet: call assign() or seat() first")
+        dev = self.ctx.torch_device
+        row0, n = A.rows(int(view.nrows), row0, nrows)
+        if row0 + n > self.z.shape[1] or self.z.shape[1] != view.nrows:
+            raise ValueError("rows [%d, %d) outside the assignment (%d rows)" % (row0, row0 + n, self.z.shape[1]))
+        pos0, npos = int(pos0), int(npos)
+        if pos0 < 0 or npos < 0 or pos0 + npos > n:
+            raise ValueError("positions [%d, %d) outside the order (%d rows)" % (pos0, pos0 + npos, n))
+        seeds = chain_seeds(seed, self.nchains)
+        op, ld_order = self._order(order, n)
+        logp = torch.full((self.nchains, n), float("nan"), dtype=torch.float32, device=dev) if want_logp else None
+        for st in self.states:
+            st._drop_subsets()
+            st._bound_view = view
+        L.check(self.ctx.lib.msc_chains_visit(
+            self._h, view._h, self.states[0]._cols(cols), row0, n, row0 if row_id0 is None else int(row_id0),
+            self._z_at(row0), int(self.z.stride(0)), op, ld_order, pos0, npos, (C.c_uint64 * self.nchains)(*seeds), int(sweep),
+            A.ptr(self.logw), A.ptr(logp) if logp is not None and logp.numel() else None, n))
+        return logp
+
+    def clone(self, ancestors):
+        """chain c becomes chain ancestors[c] wherever the two differ (msc_chains_clone; asynchronous, one launch): its z
+        row and its state's sums are the ancestor's bits; hyper-parameters, alpha and ens.logw are left alone.
+        ancestors: nchains ints with ancestors[ancestors[c]] == ancestors[c] (a source survives in place:
+        smc.systematic_ancestors arranges them so); anything else is a ValueError and changes nothing."""
+        self._check_open()
+        if self.z is None:
+            raise ValueError("no assignment yet: call assign() or seat() first")
+        anc = [int(a) for a in np.asarray(ancestors).ravel()]
+        if len(anc) != self.nchains:
+            raise ValueError("ancestors must hold nchains = %d entries (got %d)" % (self.nchains, len(anc)))
+        for c, a in enumerate(anc):
+            if not 0 <= a < self.nchains:
+                raise ValueError("ancestor %d of chain %d is not a chain (%d chains)" % (a, c, self.nchains))
+            if anc[a] != a:
+                raise ValueError("chain %d copies chain %d, which is itself overwritten: a source must survive in place"
+                                 % (c, a))
+        for c, a in enumerate(anc):
+            if a != c:
+                self.states[c]._drop_subsets()
+        L.check(self.ctx.lib.msc_chains_clone(self._h, (C.c_uint32 * self.nchains)(*anc), A.ptr(self.z),
+                                              int(self.z.stride(0)), int(self.z.shape[1])))
+
+    def smc(self, view, seed, order=None, block=None, ess_threshold=0.5, resample_seed=None, final_resample=False, sweep=0):
+        """A particle filter over the rows, the chains as particles -> smc.SMCResult, whose log_evidence estimates
+        log p(X | hp, alpha), the marginal likelihood of the mixture.
+
+        Every particle is seated from all-unassigned (seat(view)) and visits the order in blocks of `block` positions
+        (default max(1, nrows // 64)); a row's incremental weight is its predictive density given the rows seated before
+        it (visit()).  After every block but the last comes a checkpoint: the nchains log weights are copied to the host
+        -- the ONE synchronisation with the device per checkpoint -- and the effective sample size is computed there.  If
+        ess < ess_threshold * nchains the particles are resampled: log_mean_exp(logw) is added to the estimate,
+        smc.systematic_ancestors(logw, u) chooses the ancestors, clone() copies them and ens.logw is zeroed.
+        ess_threshold = 0 never resamples (plain sequential importance sampling); float("inf") always does.  u comes from
+        numpy.random.Generator(numpy.random.Philox(key=resample_seed)), resample_seed defaulting to the first chain's
+        key; one random() is drawn per checkpoint whether or not it is used, so a run is reproducible from its arguments.
+        exp(log_evidence) is unbiased for p(X) whatever the threshold, provided all chains share hyper-parameters and alpha.
+
+        final_resample: one more resampling after the last block, so that the particles end equally weighted: ens.z can go
+        straight into a ZMatrix and ens.sweep can continue from them.
+
+        result.truncated: during seating rows only join, so the occupied slots never decrease; a particle that ends with
+        an empty slot had one at every visit and the estimate is for the exact CRP.  If a particle ends with all ngroups
+        slots occupied, a new group may have been refused somewhere, and the estimate is for the mixture truncated to
+        ngroups slots: truncated is True then."""
+        self._check_open()
+        n, P = int(view.nrows), self.nchains
+        seeds = chain_seeds(seed, P)
+        block = max(1, n // 64) if block is None else int(block)
+        if block < 1:
+            raise ValueError("block must be >= 1")
+        ess_threshold = float(ess_threshold)
+        if not ess_threshold >= 0.0:
+            raise ValueError("ess_threshold must be >= 0")
+        rng = np.random.Generator(np.random.Philox(key=seeds[0] if resample_seed is None else int(resample_seed)))
+        self.seat(view)
+        log_z, ess_list, resampled_at, ancestors = 0.0, [], [], []
+
+        def resample(pos, logw, u):
+            a = S.systematic_ancestors(logw, u)
+            self.clone(a)
+            self.logw.zero_()
+            resampled_at.append(pos)
+            ancestors.append(a)
+
+        for pos0 in range(0, n, block):
+            npos = min(block, n - pos0)
+            self.visit(view, pos0, npos, seeds, sweep=sweep, order=order)
+            if pos0 + npos == n:
+                break
+            logw = self.logw.cpu().numpy()               # the checkpoint's one synchronisation
+            u = rng.random()                             # (drawn whether or not it is used)
+            ess_list.append(S.ess(logw))
+            if ess_list[-1] < ess_threshold * P:
+                log_z += S.log_mean_exp(logw)
+                resample(pos0 + npos, logw, u)
+        logw = self.logw.cpu().numpy()
+        ess_list.append(S.ess(logw))
+        log_evidence = log_z + S.log_mean_exp(logw)
+        if final_resample:
+            resample(n, logw, rng.random())
+            logw = np.zeros(P)
+        # occupied slots of every particle, from its z row (every seated row holds a slot id)
+        seen = torch.zeros((P, self.K + 1), dtype=torch.int32, device=self.ctx.torch_device)
+        seen.scatter_(1, (self.z.clamp(-1, self.K - 1) + 1).long(), 1)
+        truncated = bool((seen[:, 1:].sum(1) >= self.K).any().item()) if n else False
+        return S.SMCResult(log_evidence=log_evidence, log_weights=logw, weights=S.normalised_weights(logw), ess=ess_list,
+                           resampled_at=resampled_at, ancestors=ancestors, truncated=truncated)
 
     # lifetime -----------------------------------------------------------------
     def _check_open(self):

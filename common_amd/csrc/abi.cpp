@@ -2981,7 +2981,24 @@ struct msc_chains {
   bool pending[2] = {false, false};
   int next = 0;
   msc::DevBuf<msc::SeqChain> table_dev;   // [nchains]
+  msc::DevBuf<msc::ClonePair> pairs_dev;  // [nchains]: the pairs of a msc_chains_clone, staged through the same two areas
 };
+static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
+
+// the pinned staging area whose turn it is, once no pending copy reads it; chains_staged records the copy out of it
+static int chains_stage(msc_chains *ch, int *area) {
+  const int a = ch->next;
+  ch->next ^= 1;
+  if (ch->pending[a]) MSC_HIP(hipEventSynchronize(ch->uploaded[a]));
+  ch->pending[a] = false;
+  *area = a;
+  return MSC_OK;
+}
+static int chains_staged(msc_chains *ch, int area, hipStream_t s) {
+  MSC_HIP(hipEventRecord(ch->uploaded[area], s));
+  ch->pending[area] = true;
+  return MSC_OK;
+}
 
 extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc_chains **out) {
   MSC_REQUIRE(states && out, "null argument");
@@ -3011,6 +3028,7 @@ extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc
   ch->ctx = ctx;
   ch->states.assign(states, states + nchains);
   hipError_t e = ch->table_dev.alloc(nchains);
+  if (e == hipSuccess) e = ch->pairs_dev.alloc(nchains);
   for (int i = 0; i < 2 && e == hipSuccess; i++) {
     e = ch->stage[i].alloc(nchains);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ch->uploaded[i], hipEventDisableTiming);
@@ -3043,28 +3061,35 @@ extern "C" int msc_chains_size(const msc_chains *ch, uint32_t *nchains) {
   return MSC_OK;
 }
 
-extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
-                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
-                                uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep, uint32_t trace_every,
-                                int32_t *trace_dev, uint32_t *occupied_dev) {
-  MSC_REQUIRE(ch && view, "null argument");
+// What msc_chains_sweep and msc_chains_visit share: visits [v0, v1) of a call's nsweeps x nrows for every chain (visit v is
+// sweep v / nrows, position v % nrows of the order), with the outputs each of the two has (null: not wanted).
+struct ChainsOutputs {
+  uint32_t trace_every = 1;           // >= 1
+  uint64_t ntrace = 0;                // samples per chain of trace / occupied
+  int32_t *trace = nullptr;           // [nchains][ntrace][nrows]
+  uint32_t *occupied = nullptr;       // [nchains][ntrace]
+  double *logw = nullptr;             // [nchains]
+  float *visit_logp = nullptr;        // chain c's at + c * ld_logp
+  uint64_t ld_logp = 0;
+};
+static int chains_visits_impl(msc_chains *ch, const char *who, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                              uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev,
+                              uint64_t ld_order, uint64_t v0, uint64_t v1, const uint64_t *host_seeds, uint64_t sweep,
+                              const ChainsOutputs &out) {
   const uint32_t n = (uint32_t)ch->states.size();
-  if (n == 0) return MSC_OK;
-  MSC_REQUIRE((z_dev && host_seeds) || nrows == 0 || nsweeps == 0, "null argument");
+  MSC_REQUIRE((z_dev && host_seeds) || v0 >= v1, "null argument");
   MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
-  MSC_REQUIRE(ld_z >= nrows, "msc_chains_sweep: ld_z %llu < nrows %llu", (unsigned long long)ld_z, (unsigned long long)nrows);
-  MSC_REQUIRE(!order_dev || ld_order == 0 || ld_order >= nrows, "msc_chains_sweep: ld_order %llu is neither 0 (one order "
-              "for all chains) nor >= nrows %llu", (unsigned long long)ld_order, (unsigned long long)nrows);
-  const bool tracing = trace_dev != nullptr || occupied_dev != nullptr;
-  MSC_REQUIRE(!tracing || trace_every >= 1, "msc_chains_sweep: trace_every must be >= 1 with a trace or an occupied array");
+  MSC_REQUIRE(ld_z >= nrows, "%s: ld_z %llu < nrows %llu", who, (unsigned long long)ld_z, (unsigned long long)nrows);
+  MSC_REQUIRE(!order_dev || ld_order == 0 || ld_order >= nrows, "%s: ld_order %llu is neither 0 (one order "
+              "for all chains) nor >= nrows %llu", who, (unsigned long long)ld_order, (unsigned long long)nrows);
   for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_sweep: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
   msc_context *ctx = ch->ctx;
   MSC_HIP(hipSetDevice(ctx->device));
   MSC_TRY(device_error_check(ctx));
   for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  if (nrows == 0 || nsweeps == 0) return MSC_OK;
+  if (v0 >= v1) return MSC_OK;
   // every table of every member current before, as msc_sweep_sequential
   hipStream_t s = ctx->stream;
   double visit_us = 0.0;
@@ -3073,11 +3098,8 @@ extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const 
     visit_us = std::max(visit_us, seq_visit_us(st));
   }
   // the table of this call (pointers and alpha may have changed since the last one), through the pinned area whose turn it is
-  const uint64_t ntrace = tracing ? nsweeps / trace_every : 0;
-  const int a = ch->next;
-  ch->next ^= 1;
-  if (ch->pending[a]) MSC_HIP(hipEventSynchronize(ch->uploaded[a]));
-  ch->pending[a] = false;
+  int a = 0;
+  MSC_TRY(chains_stage(ch, &a));
   SeqChain *tab = ch->stage[a];
   for (uint32_t c = 0; c < n; c++) {
     const msc_state *st = ch->states[c];
@@ -3088,31 +3110,122 @@ extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const 
     e.crp = st->logpc;
     e.z = z_dev + (size_t)c * ld_z;
     e.order = order_dev ? order_dev + (size_t)c * ld_order : nullptr;
-    e.trace = trace_dev && ntrace ? trace_dev + (size_t)c * ntrace * nrows : nullptr;
-    e.occupied = occupied_dev && ntrace ? occupied_dev + (size_t)c * ntrace : nullptr;
+    e.trace = out.trace && out.ntrace ? out.trace + (size_t)c * out.ntrace * nrows : nullptr;
+    e.occupied = out.occupied && out.ntrace ? out.occupied + (size_t)c * out.ntrace : nullptr;
+    e.logw = out.logw ? out.logw + c : nullptr;
+    e.visit_logp = out.visit_logp ? out.visit_logp + (size_t)c * out.ld_logp : nullptr;
     e.seed = host_seeds[c];
     e.alpha = st->alpha;
     e.pad = 0;
   }
   MSC_HIP(hipMemcpyAsync(ch->table_dev, tab, sizeof(SeqChain) * n, hipMemcpyHostToDevice, s));
-  MSC_HIP(hipEventRecord(ch->uploaded[a], s));
-  ch->pending[a] = true;
+  MSC_TRY(chains_staged(ch, a, s));
   // a launch's visits: what one chain may take in the launch's time (as msc_sweep_sequential, by the costliest member),
   // divided by the rounds the grid runs in -- at this kernel's register count one workgroup is resident per CU
   const msc_state *st0 = ch->states[0];
-  const uint64_t visits = (uint64_t)nsweeps * nrows;
   const double one = std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / visit_us));
   const uint64_t rounds = (n + (uint32_t)std::max(1, ctx->num_cus) - 1) / (uint32_t)std::max(1, ctx->num_cus);
   const uint64_t per_launch = std::max<uint64_t>(1, (uint64_t)one / rounds);
-  for (uint64_t v0 = 0; v0 < visits; v0 += per_launch) {
-    const uint64_t v1 = std::min(visits, v0 + per_launch);
-    const int rc = launch_sweep_seq_chains(s, ch->table_dev, n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows, row_id0, v0,
-                                           v1, sweep, tracing ? trace_every : 1u);
+  for (uint64_t w0 = v0; w0 < v1; w0 += per_launch) {
+    const uint64_t w1 = std::min(v1, w0 + per_launch);
+    const int rc = launch_sweep_seq_chains(s, ch->table_dev, n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows, row_id0, w0,
+                                           w1, sweep, out.trace_every);
     if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq_chains does not take this shape");
     if (rc) return fail(MSC_EHIP, "k_sweep_seq_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
   }
   // the kernel kept every table of every member current: additive sums, fields, constants, counts and CRP terms
   for (msc_state *st : ch->states) st->valid.kept_current();
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                                uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep, uint32_t trace_every,
+                                int32_t *trace_dev, uint32_t *occupied_dev) {
+  MSC_REQUIRE(ch && view, "null argument");
+  if (ch->states.empty()) return MSC_OK;
+  const bool tracing = trace_dev != nullptr || occupied_dev != nullptr;
+  MSC_REQUIRE(!tracing || trace_every >= 1, "msc_chains_sweep: trace_every must be >= 1 with a trace or an occupied array");
+  ChainsOutputs out;
+  out.trace_every = tracing ? trace_every : 1u;
+  out.ntrace = tracing ? nsweeps / trace_every : 0;
+  out.trace = trace_dev;
+  out.occupied = occupied_dev;
+  return chains_visits_impl(ch, "msc_chains_sweep", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, 0,
+                            (uint64_t)nsweeps * nrows, host_seeds, sweep, out);
+}
+
+extern "C" int msc_chains_visit(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                                uint64_t pos0, uint64_t npos, const uint64_t *host_seeds, uint64_t sweep, double *logw_dev,
+                                float *visit_logp_dev, uint64_t ld_logp) {
+  MSC_REQUIRE(ch && view, "null argument");
+  MSC_REQUIRE(pos0 <= nrows && npos <= nrows - pos0, "msc_chains_visit: positions [%llu, %llu + %llu) beyond nrows %llu",
+              (unsigned long long)pos0, (unsigned long long)pos0, (unsigned long long)npos, (unsigned long long)nrows);
+  MSC_REQUIRE(!visit_logp_dev || ld_logp >= nrows, "msc_chains_visit: ld_logp %llu < nrows %llu", (unsigned long long)ld_logp,
+              (unsigned long long)nrows);
+  if (ch->states.empty() || npos == 0) return MSC_OK;
+  ChainsOutputs out;
+  out.logw = logw_dev;
+  out.visit_logp = visit_logp_dev;
+  out.ld_logp = ld_logp;
+  return chains_visits_impl(ch, "msc_chains_visit", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, pos0,
+                            pos0 + npos, host_seeds, sweep, out);
+}
+
+extern "C" int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, int32_t *z_dev, uint64_t ld_z, uint64_t nrows) {
+  MSC_REQUIRE(ch && host_ancestors, "null argument");
+  const uint32_t n = (uint32_t)ch->states.size();
+  MSC_REQUIRE(z_dev || nrows == 0, "null argument");
+  MSC_REQUIRE(ld_z >= nrows, "msc_chains_clone: ld_z %llu < nrows %llu", (unsigned long long)ld_z, (unsigned long long)nrows);
+  uint32_t npairs = 0;
+  for (uint32_t c = 0; c < n; c++) {
+    const uint32_t a = host_ancestors[c];
+    MSC_REQUIRE(a < n, "msc_chains_clone: ancestor %u of chain %u is not a chain (%u chains)", a, c, n);
+    MSC_REQUIRE(host_ancestors[a] == a, "msc_chains_clone: chain %u copies chain %u, which is itself overwritten (by chain "
+                                        "%u): a source must survive in place", c, a, host_ancestors[a]);
+    npairs += a != c;
+  }
+  for (uint32_t c = 0; c < n; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_clone: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  if (npairs == 0) return MSC_OK;
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  hipStream_t s = ctx->stream;
+  // a source's additive tables hold the truth before they are read (after a sweep they do: this launches nothing then)
+  for (uint32_t c = 0; c < n; c++)
+    if (host_ancestors[c] != c) MSC_TRY(ensure_additive(ch->states[host_ancestors[c]]));
+  int area = 0;
+  MSC_TRY(chains_stage(ch, &area));
+  ClonePair *tab = reinterpret_cast<ClonePair *>(ch->stage[area].get());
+  const msc_state *st0 = ch->states[0];
+  uint32_t p = 0;
+  for (uint32_t c = 0; c < n; c++) {
+    const uint32_t a = host_ancestors[c];
+    if (a == c) continue;
+    const msc_state *src = ch->states[a];
+    msc_state *dst = ch->states[c];
+    ClonePair &e = tab[p++];
+    e.src_i64 = src->red_i64;
+    e.dst_i64 = dst->red_i64;
+    e.src_f64 = src->red_f64;
+    e.dst_f64 = dst->red_f64;
+    e.src_z = z_dev + (size_t)a * ld_z;
+    e.dst_z = z_dev + (size_t)c * ld_z;
+  }
+  MSC_HIP(hipMemcpyAsync(ch->pairs_dev, tab, sizeof(ClonePair) * npairs, hipMemcpyHostToDevice, s));
+  MSC_TRY(chains_staged(ch, area, s));
+  if (launch_chains_clone(s, ch->pairs_dev, npairs, st0->n_i64, st0->n_f64, nrows))
+    return fail(MSC_EHIP, "k_chains_clone launch failed: %s", hipGetErrorString(hipGetLastError()));
+  // a destination's additive tables were replaced as a whole and alone hold its truth now, as after an accumulate that
+  // has not committed: the fields, the score constants and the CRP terms are rebuilt from them by the next call's ensure
+  // steps.  (additive_rewritten(), msc_state_reduce_unpack's event, would not do: that call comes between an uncommitted
+  // accumulate and a commit, so the fields are already marked stale there; a chain a sweep kept current has them marked
+  // current, and they would stay the destination's old ones.)
+  for (uint32_t c = 0; c < n; c++)
+    if (host_ancestors[c] != c) ch->states[c]->valid.accumulated();
   return MSC_OK;
 }
 

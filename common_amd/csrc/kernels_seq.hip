@@ -17,6 +17,10 @@
 //                 global memory.
 //   k_sweep_seq_chains   a grid of such workgroups, one independent chain each (msc_chains_sweep): what differs per chain
 //                 is a SeqChain entry of a device table; also a thinned trace and the occupied-slot count per sample.
+//                 Two nullable outputs per chain (msc_chains_visit): the visit's log predictive m + log(total) - log(n +
+//                 alpha) of the draw's own block max and sum, by order position, and its running sum in double.
+//   k_chains_clone   copies the additive tables and the z row of a source chain onto a destination, for a table of pairs
+//                 (msc_chains_clone): words as they are, so a clone holds its ancestor's bits.
 #include "commit_ops.hpp"
 #include "device_error.hpp"
 #include "family_math.hpp"
@@ -116,6 +120,7 @@ struct SeqShared {
   uint8_t skip[kSeqMaxFeat];      // masked for that feature (no part in the sums or the score)
   float wmax[kSeqThreads / 64], wsum[kSeqThreads / 64];   // per-wave max / sum of the draw
   uint32_t nempty;                // empty slots among [0, K)
+  uint32_t n;                     // rows seated: the sum of the group counts
   uint32_t below;                 // CDF steps below the dart
 };
 
@@ -135,6 +140,7 @@ MSC_DEV void seq_move(SeqShared &sh, const FeatDesc *__restrict__ feats, int nfe
     if (sign < 0 && c == 0) ne++;
     if (sign > 0 && c == 1) ne--;
     sh.nempty = ne;
+    sh.n += (uint32_t)sign;
     seq_split(ne > 0 ? log((double)alpha / (double)ne) : -(double)INFINITY, crp[2 * (size_t)kpad], crp[2 * (size_t)kpad + 2]);
     seq_split(log((double)alpha / ((double)ne + 1.0)), crp[2 * (size_t)kpad + 1], crp[2 * (size_t)kpad + 3]);
     if (zslot != nullptr) *zslot = (int32_t)g;
@@ -171,17 +177,30 @@ static __device__ unsigned long long g_seq_phase[6];
 // slices of K threads and slice q sums features q, q + nq, ... (partials summed in slice order: the same bits every run)
 // trace (nullable): after sweep s of the call, when (s + 1) % trace_every == 0, z of the row range goes to sample
 // (s + 1) / trace_every - 1; occupied (nullable): K - the empty slots at the same moments.
+// logw, visit_logp (nullable): the visit at position pos has the log predictive of its row given the tables at that
+// moment, inc = m + log(total) - log(n + alpha) in double (m, total: the draw's block max and sum; n: the rows seated, the
+// row itself not among them; -inf when total == 0 or m == -inf).  visit_logp[pos] = (float)inc; *logw += inc, visit by
+// visit in visit order by thread 0, in a register between the launch's first and last visit: the same adds however the
+// visits are cut into launches.  Neither changes a draw: with both null the visit is as it was.
 MSC_DEV void seq_visits(SeqShared &sh, const FeatDesc *__restrict__ feats, int nfeat, uint32_t K, uint32_t kpad,
                         uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *__restrict__ order,
                         uint64_t v0, uint64_t v1, uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32,
-                        float alpha, float *crp, int32_t *trace, uint32_t trace_every, uint32_t *occupied) {
+                        float alpha, float *crp, int32_t *trace, uint32_t trace_every, uint32_t *occupied, double *logw,
+                        float *visit_logp) {
   const uint32_t t = threadIdx.x, nt = kSeqThreads, lane = t & 63u, wave = t >> 6, nw = kSeqThreads / 64;
-  if (t == 0) sh.nempty = 0;
+  if (t == 0) sh.nempty = sh.n = 0;
   __syncthreads();
-  uint32_t mine = 0;
-  for (uint32_t k = t; k < K; k += nt) mine += cnt_u32[k] == 0u;
+  uint32_t mine = 0, mine_n = 0;
+  for (uint32_t k = t; k < K; k += nt) {
+    const uint32_t c = cnt_u32[k];
+    mine += c == 0u;
+    mine_n += c;
+  }
   atomicAdd(&sh.nempty, mine);
+  atomicAdd(&sh.n, mine_n);
   __syncthreads();
+  const bool want_inc = logw != nullptr || visit_logp != nullptr;
+  double lw = t == 0 && logw != nullptr ? *logw : 0.0;
   const float *lo0 = crp + crp_lo_cnt(kpad);
   const uint32_t nq = K < nt ? nt / K : 1u, q = t / K, kq = t - q * K;     // (scoring slices, K < the block)
   const uint32_t chunk = (K + nt - 1) / nt, kb = t * chunk;                  // the draw: thread t owns [kb, kb + chunk)
@@ -274,6 +293,13 @@ MSC_DEV void seq_visits(SeqShared &sh, const FeatDesc *__restrict__ feats, int n
             if (w < wave) c += ws;
             total += ws;
           }
+          if (want_inc && t == 0) {
+            const double inc = total == 0.f || m == -INFINITY
+                                   ? -(double)INFINITY
+                                   : (double)m + log((double)total) - log((double)sh.n + (double)alpha);
+            lw += inc;
+            if (visit_logp != nullptr) visit_logp[pos] = (float)inc;
+          }
           const float dart = philox_uniform01(seed, sweep + s, row_id0 + off) * total;
           uint32_t cnt = 0;
           for (uint32_t k = kb; k < kb + chunk && k < K; k++) {
@@ -298,6 +324,7 @@ MSC_DEV void seq_visits(SeqShared &sh, const FeatDesc *__restrict__ feats, int n
       __syncthreads();
     }
   }
+  if (t == 0 && logw != nullptr) *logw = lw;
 #ifdef MSC_SEQ_PHASES
   if (t == 0) {
     for (int i = 0; i < 5; i++) atomicAdd(&g_seq_phase[i], ph_acc[i]);
@@ -314,7 +341,7 @@ __global__ __launch_bounds__(kSeqThreads) void k_sweep_seq(const FeatDesc *__res
                                                            uint32_t *cnt_u32, float alpha, float *crp, int32_t *trace) {
   __shared__ SeqShared sh;
   seq_visits(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp,
-             trace, 1u, nullptr);
+             trace, 1u, nullptr, nullptr, nullptr);
 }
 
 // the same visits of gridDim.x independent chains (msc_chains_sweep): workgroup c carries chain c, whose state, z, order,
@@ -333,8 +360,10 @@ __global__ __launch_bounds__(kSeqThreads) void k_sweep_seq_chains(const SeqChain
   const uint32_t *order = c.order;
   const float alpha = c.alpha;
   const uint64_t seed = c.seed;
+  double *logw = c.logw;
+  float *visit_logp = c.visit_logp;
   seq_visits(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp,
-             trace, trace_every, occupied);
+             trace, trace_every, occupied, logw, visit_logp);
 }
 
 int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
@@ -353,6 +382,41 @@ int launch_sweep_seq_chains(hipStream_t stream, const SeqChain *chains_dev, uint
   if (nfeat < 0 || nfeat > kSeqMaxFeat || K == 0 || K > kSeqMaxGroups || nchains == 0 || trace_every == 0) return -2;
   hipLaunchKernelGGL(k_sweep_seq_chains, dim3(nchains), dim3(kSeqThreads), 0, stream, chains_dev, nfeat, K, kpad, row0,
                      nrows, row_id0, v0, v1, sweep, trace_every);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// nwords 32-bit words from src to dst by the blocks of grid row y: 16 bytes a lane where both ends are aligned to it
+MSC_DEV void clone_words(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, size_t nwords) {
+  const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
+    const size_t nvec = nwords / 4;
+    const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+    for (size_t i = i0; i < nvec; i += step) d4[i] = s4[i];
+    for (size_t i = nvec * 4 + i0; i < nwords; i += step) dst[i] = src[i];
+  } else {
+    for (size_t i = i0; i < nwords; i += step) dst[i] = src[i];
+  }
+}
+
+// pair blockIdx.y of the table: the source's additive tables (int64 sums, the group counts leading; float64 sums) and z
+// row onto the destination's.  A pair's source is no pair's destination (msc_chains_clone checks), so no block reads
+// what another writes.
+__global__ __launch_bounds__(256) void k_chains_clone(const ClonePair *__restrict__ pairs, size_t n_i64, size_t n_f64,
+                                                      size_t nrows) {
+  const ClonePair p = pairs[blockIdx.y];
+  clone_words(reinterpret_cast<const uint32_t *>(p.src_i64), reinterpret_cast<uint32_t *>(p.dst_i64), 2 * n_i64);
+  clone_words(reinterpret_cast<const uint32_t *>(p.src_f64), reinterpret_cast<uint32_t *>(p.dst_f64), 2 * n_f64);
+  clone_words(reinterpret_cast<const uint32_t *>(p.src_z), reinterpret_cast<uint32_t *>(p.dst_z), nrows);
+}
+
+int launch_chains_clone(hipStream_t stream, const ClonePair *pairs_dev, uint32_t npairs, size_t n_i64, size_t n_f64,
+                        size_t nrows) {
+  const size_t words = std::max(std::max(2 * n_i64, 2 * n_f64), nrows);
+  const uint32_t chunks = (uint32_t)std::min<size_t>(64, std::max<size_t>(1, (words / 4 + 255) / 256));
+  for (uint32_t p0 = 0; p0 < npairs; p0 += 65535u)      // (a grid's y extent; one launch up to 65535 pairs)
+    hipLaunchKernelGGL(k_chains_clone, dim3(chunks, std::min(npairs - p0, 65535u)), dim3(256), 0, stream, pairs_dev + p0,
+                       n_i64, n_f64, nrows);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -198,6 +198,8 @@ struct SeqChain {
   const uint32_t *order;   // uint32 [nrows] or null (ascending)
   int32_t *trace;          // int32 [ntrace][nrows] or null
   uint32_t *occupied;      // uint32 [ntrace] or null
+  double *logw;            // one double or null: the visits' log predictives are added to it (msc_chains_visit)
+  float *visit_logp;       // float [nrows] by order position or null: each visit's log predictive
   uint64_t seed;           // the chain's Philox key
   float alpha;
   uint32_t pad;
@@ -206,6 +208,18 @@ struct SeqChain {
 int launch_sweep_seq_chains(hipStream_t stream, const SeqChain *chains_dev, uint32_t nchains, int nfeat, uint32_t K,
                             uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t v0, uint64_t v1,
                             uint64_t sweep, uint32_t trace_every);
+// msc_chains_clone: pair p's source tables (red_i64[n_i64], red_f64[n_f64]) and z row [nrows] onto its destination's, one
+// launch for all pairs (grid: chunks x pairs); no source may be a destination
+struct ClonePair {
+  const long long *src_i64;
+  long long *dst_i64;
+  const double *src_f64;
+  double *dst_f64;
+  const int32_t *src_z;
+  int32_t *dst_z;
+};
+int launch_chains_clone(hipStream_t stream, const ClonePair *pairs_dev, uint32_t npairs, size_t n_i64, size_t n_f64,
+                        size_t nrows);
 
 // kernels_blocked.hip: the blocked Gibbs sampler (msc_blocked_*; abi.cpp route_blocked chooses the assign kernel)
 enum class BlockedKernel { nich1, staged, global };

@@ -20,7 +20,8 @@
 //                                                                                                 msc_split_merge (a kernel moved them)
 //   additive_lifted()          .       all 1       .          1                  .       .        ensure_additive; a resetting
 //                                                                                                 accumulate's zeroing in its place
-//   accumulated()              all 0   all 1       .          1                  .       0        accumulate_impl
+//   accumulated()              all 0   all 1       .          1                  .       0        accumulate_impl; msc_chains_clone
+//                                                                                                 (a destination's sums replaced)
 //   additive_rewritten()       .       .           .          .                  .       0        msc_state_reduce_unpack
 //   committed()                all 1   .           all 0      .                  0       0        commit, ensure_raw
 //   committed_and_prepared()   all 1   .           all 1      .                  1       0        commit_and_prepare

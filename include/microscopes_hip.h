@@ -422,6 +422,58 @@ int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *c
                      uint32_t trace_every, int32_t *trace_dev, uint32_t *occupied_dev);
 
 /*
+ * PART of one sweep of every chain, with the log predictive of every visit: what a particle filter over the rows needs
+ * (common_amd.ChainEnsemble.smc).  msc_chains_visit performs positions [pos0, pos0 + npos) of the order of ONE sweep for
+ * every chain: exactly the visits at those positions of
+ *   msc_chains_sweep(ch, view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, 1, host_seeds, sweep, ...)
+ * -- the same counters (row_id0 + offset, sweep), the same arithmetic in the same order, so the same bits in z and in
+ * every table.  Calls over [0, a), [a, b), ..., [y, nrows) together are that sweep.  z_dev, ld_z, order_dev, ld_order,
+ * host_seeds: as msc_chains_sweep.  On top of the sweep's work a visit has two outputs, which move no draw:
+ *   visit_logp_dev  nullable; float, chain c's row at visit_logp_dev + c * ld_logp, ld_logp >= nrows, indexed by order
+ *                   POSITION: the visit at position p writes entry p with
+ *                     inc = m + log(total) - log(n + alpha)   (in double, rounded to float)
+ *                   where m and total = sum_k exp(t_k - m) are the block max and sum the draw itself makes of the row's
+ *                   scores t_k (log pseudocount + the features' score_value, as the tables stand at that visit, after
+ *                   the row has left its own group) and n is the number of rows seated at that moment, the row itself
+ *                   not among them.  It is the row's log predictive density given the rows seated before it: the
+ *                   quantity msc_score_marginal defines, taken against the tables of that visit.  -inf when total == 0
+ *                   or m == -inf.  Entries of positions outside [pos0, pos0 + npos), and of a skipped visit, are left
+ *                   as they are;
+ *   logw_dev        nullable; double[nchains] on the device: chain c's entry is ADDED to (the caller zeroes it) -- inc in
+ *                   double, visit by visit in visit order, by one thread: no atomics, no partial sums, so its bits do
+ *                   not depend on how the positions are cut into calls, or a call into launches.
+ * On return (asynchronously, on the context's stream) every table of every member state is current, as after
+ * msc_chains_sweep.  npos == 0 returns MSC_OK and touches nothing.  The launch slicing by time budget, the two pinned
+ * staging areas, the families and limits are msc_chains_sweep's.
+ * Errors: MSC_EINVAL for pos0 + npos > nrows, visit_logp_dev with ld_logp < nrows, and whatever msc_chains_sweep
+ * refuses (null argument, nrows >= 2^32, ld_z < nrows, ld_order neither 0 nor >= nrows, rows outside the view, a column
+ * that does not fit a feature, a member between msc_sweep_step_begin and msc_state_commit_reduce); MSC_EDEVICE when an
+ * earlier kernel reported an error.  Nothing is written when a call is refused.
+ *
+ * msc_chains_clone: for every chain c with a = host_ancestors[c] != c, chain c BECOMES chain a: one launch copies, for all
+ * such pairs, state a's additive tables (the two buffers of msc_state_reduce_buffers: the int64 sums, the group counts
+ * leading, and the float64 sums) onto state c's and the z row z_dev + a * ld_z onto z_dev + c * ld_z (nrows entries,
+ * ld_z >= nrows).  The sums are copied, not accumulated again from z -- msc_accumulate adds its double sums with atomics
+ * in an order that varies from run to run -- so a clone holds its ancestor's bits.  host_ancestors: uint32[nchains] on the
+ * host, read before the call returns.  State c's reference fields, score constants and CRP terms are marked stale and
+ * rebuilt from the copied sums by the next call that needs them (the next msc_chains_visit / msc_chains_sweep, or a
+ * getter on the state); they come out as the ancestor's, which the same kernels' code built from the same sums.  Hyper-
+ * parameters and alpha are NOT copied: a chain keeps its own.  Reads: the sources' additive tables and z rows.  Writes:
+ * the destinations' only.  Sources, chains with host_ancestors[c] == c, and every state's hyper-parameters stay valid
+ * and untouched.  No random numbers are drawn.  Asynchronous on the context's stream.  An all-identity array returns
+ * MSC_OK and launches nothing.
+ * Errors, with nothing changed: MSC_EINVAL for a null argument, ld_z < nrows, an entry >= nchains (named), a source that
+ * is itself overwritten (host_ancestors[a] != a: ancestors must survive in place, so no pair reads what another writes),
+ * or a member between msc_sweep_step_begin and msc_state_commit_reduce; MSC_EDEVICE when an earlier kernel reported an
+ * error.
+ */
+int msc_chains_visit(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                     uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                     uint64_t pos0, uint64_t npos, const uint64_t *host_seeds, uint64_t sweep,
+                     double *logw_dev, float *visit_logp_dev, uint64_t ld_logp);
+int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, int32_t *z_dev, uint64_t ld_z, uint64_t nrows);
+
+/*
  * The BLOCKED (uncollapsed) Gibbs sampler for the truncated stick-breaking Dirichlet process mixture (Ishwaran & James,
  * JASA 2001): an exact sampler that is parallel over rows.  With ngroups = K slots a sweep draws, given the tables,
  * every slot's component parameters from their conjugate posteriors and the mixture weights from the stick-breaking
