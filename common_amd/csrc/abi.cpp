@@ -1,4 +1,8 @@
-// abi.cpp -- the extern "C" surface declared in include/microscopes_hip.h.
+// abi.cpp -- the core of the extern "C" surface declared in include/microscopes_hip.h: library and context, allocation,
+// dataviews, the state with its plan (plan_layout, plan_groups, bind_view), tables and ensure steps, the score,
+// accumulate and sweep routes and entries, the reduce and column-bound entries, relations and msc_value_op_single.
+// The subsystems built on it have a unit each -- blocked.cpp, chains.cpp, hyper.cpp, predict.cpp, summary.cpp -- and reach
+// it through abi_internal.hpp.
 // Host logic only: argument checking, table bookkeeping and kernel launches.
 // There is deliberately no CPU arithmetic path here: every score / update is a
 // kernel in kernels_*.hip, and context creation fails without a gfx950 device.
@@ -9,11 +13,9 @@
 #include <mutex>
 #include <new>
 
-#include "blocked_post.hpp"
+#include "abi_internal.hpp"
 #include "launchers.hpp"
-#include "linkage_host.hpp"
 #include "row_range.hpp"
-#include "splitmerge_math.hpp"
 
 namespace msc {
 
@@ -43,37 +45,6 @@ size_t primitive_size(int t) {
 }
 
 static bool family_ok(int f) { return f >= MSC_BB && f <= MSC_DM; }
-
-// What the library reads from the environment, all of it here (INTEGRATION.md "Environment" says what each switch does):
-// read afresh by every call that plans, routes or allocates, so that a test may set a switch between two calls.
-struct Switches {
-  bool tail_forced = false, no_narrow_tail = false, no_bb_fuse = false, sweep_graph = false;
-  uint64_t tail_min_rows = 0;                           // (tail_forced)
-  int loo_lds = -1, sweep_nich1 = 0, alloc_candidates = 12;
-  int marginal_tile = -1;                               // MSC_MARGINAL_TILE: 1 / 0 = the fused tile kernel for every plan it takes / for none
-
-  float alloc_accept_gbps = 6650.f;
-};
-static Switches read_switches() {
-  Switches sw;
-  if (const char *e = std::getenv("MSC_TAIL_MIN_ROWS")) sw.tail_forced = true, sw.tail_min_rows = (uint64_t)std::atoll(e);
-  sw.no_narrow_tail = std::getenv("MSC_NO_NARROW_TAIL") != nullptr, sw.no_bb_fuse = std::getenv("MSC_NO_BB_FUSE") != nullptr;
-  if (const char *e = std::getenv("MSC_LOO_LDS")) sw.loo_lds = std::atoi(e);
-  if (const char *e = std::getenv("MSC_SWEEP_NICH1")) sw.sweep_nich1 = std::atoi(e);
-  if (const char *e = std::getenv("MSC_MARGINAL_TILE")) sw.marginal_tile = std::atoi(e);
-  if (const char *g = std::getenv("MSC_SWEEP_GRAPH")) sw.sweep_graph = g[0] != '0' && g[0] != 0;
-  if (const char *e = std::getenv("MSC_ALLOC_CANDIDATES")) sw.alloc_candidates = std::atoi(e);
-  if (const char *e = std::getenv("MSC_ALLOC_ACCEPT_GBPS")) sw.alloc_accept_gbps = (float)std::atof(e);
-  return sw;
-}
-
-// count elements (at least one), zero-filled
-template <typename T>
-static int alloc_zeroed(DevBuf<T> &buf, size_t count) {
-  MSC_HIP(buf.alloc(count, 1));
-  MSC_HIP(hipMemset(buf, 0, std::max<size_t>(count, 1) * sizeof(T)));
-  return MSC_OK;
-}
 
 }  // namespace msc
 
@@ -114,7 +85,7 @@ static int device_error_word(int device, volatile uint32_t **host_out) {
   return MSC_OK;
 }
 // what the launching and synchronising entry points call first / last: an error a kernel of an earlier call reported
-static int device_error_check(msc_context *ctx) {
+int msc::device_error_check(msc_context *ctx) {
   volatile uint32_t *w = ctx ? ctx->err_host : nullptr;
   if (!w || w[0] == 0) return MSC_OK;
   std::atomic_thread_fence(std::memory_order_acquire);
@@ -1324,8 +1295,8 @@ extern "C" int msc_state_destroy(msc_state *st) {
   (void)hipSetDevice(st->ctx->device);
   (void)hipStreamSynchronize(st->ctx->stream);
   if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
-  if (st->pred_upload) (void)hipEventDestroy(st->pred_upload);
-  if (st->sm_pair) (void)msc_state_destroy(st->sm_pair);
+  if (st->pred.upload) (void)hipEventDestroy(st->pred.upload);
+  if (st->sm.pair) (void)msc_state_destroy(st->sm.pair);
   delete st;
   return MSC_OK;
 }
@@ -1340,7 +1311,7 @@ extern "C" int msc_state_shape(const msc_state *st, uint32_t *nfeatures, uint32_
 // dd / dm: the sum of the feature's alphas (FeatDesc::aux) follows its host hp block, in every host copy of the
 // descriptor; whether the family carries one.  The device side is the caller's: msc_state_set_hp uploads, hp_installed
 // does not (the kernel wrote it).
-static bool refresh_alpha_sum(msc_state *st, uint32_t feature) {
+bool msc::refresh_alpha_sum(msc_state *st, uint32_t feature) {
   const msc_feature_host &h = st->feats[feature];
   if (h.family != MSC_DD && h.family != MSC_DM) return false;
   double asum = 0;
@@ -1388,7 +1359,7 @@ static int launch_commit_all(msc_state *st) {
   return MSC_OK;
 }
 
-static int ensure_raw(msc_state *st) {
+int msc::ensure_raw(msc_state *st) {
   if (!st->valid.any_raw_stale()) return MSC_OK;
   MSC_TRY(launch_commit_all(st));
   st->valid.committed();
@@ -1396,7 +1367,7 @@ static int ensure_raw(msc_state *st) {
 }
 
 // refuses a call between msc_sweep_step_begin and msc_state_commit_reduce
-static int refuse_mid_step(const msc_state *st, const char *entry) {
+int msc::refuse_mid_step(const msc_state *st, const char *entry) {
   MSC_REQUIRE(!st->rng_bump_pending, "%s between msc_sweep_step_begin and msc_state_commit_reduce: the additive tables "
                                      "hold one rank's uncommitted sums", entry);
   return MSC_OK;
@@ -1675,8 +1646,8 @@ static int bind_dm_column(msc_state *st, uint32_t f, const msc_dataview *view, u
   return MSC_OK;
 }
 
-static int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
-                     uint64_t nrows) {
+int msc::bind_view(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                   uint64_t nrows) {
   MSC_REQUIRE(view, "null dataview");
   MSC_REQUIRE(view->ctx->device == st->ctx->device, "dataview and state live on different devices");
   MSC_REQUIRE(msc::rows_within(row0, nrows, view->nrows), "rows [%llu,%llu) outside the view (%llu rows)",
@@ -1774,7 +1745,7 @@ static uint32_t prepare_value_slices(const msc_state *st) {
   return std::min<uint32_t>(64, (rows + 3) / 4);
 }
 
-static int ensure_derived(msc_state *st) {
+int msc::ensure_derived(msc_state *st) {
   MSC_TRY(ensure_raw(st));
   if (!st->valid.any_derived_stale()) return MSC_OK;
   if (launch_prepare(st->ctx->stream, st->desc_dev, st->nfeat, st->kpad, prepare_value_slices(st)))
@@ -1791,7 +1762,7 @@ static int ensure_derived(msc_state *st) {
   return MSC_OK;
 }
 
-static int ensure_crp(msc_state *st) {
+int msc::ensure_crp(msc_state *st) {
   MSC_TRY(ensure_raw(st));
   if (!st->valid.crp_stale()) return MSC_OK;
   if (launch_crp_prepare(st->ctx->stream, st->cnt_u32, st->K, st->kpad, st->alpha, st->logpc))
@@ -1802,7 +1773,7 @@ static int ensure_crp(msc_state *st) {
 
 // the raw tables lifted into the additive ones where those are stale: the features in their order, then the counts
 // (niw lifts through its commit kernel run backwards)
-static int ensure_additive(msc_state *st) {
+int msc::ensure_additive(msc_state *st) {
   MSC_TRY(ensure_raw(st));
   hipStream_t s = st->ctx->stream;
   for (uint32_t f = 0; f < st->nfeat; f++)
@@ -1819,7 +1790,7 @@ static int ensure_additive(msc_state *st) {
 }
 
 // every table current: the reference's fields, the additive sums, the score constants, the CRP terms
-static int ensure_all_current(msc_state *st) {
+int msc::ensure_all_current(msc_state *st) {
   MSC_TRY(ensure_additive(st));
   MSC_TRY(ensure_derived(st));
   return ensure_crp(st);
@@ -1833,7 +1804,7 @@ static int ensure_all_current(msc_state *st) {
 
 // the rows the choice of kernels goes by: the bound view's, or those of the whole a sharded driver announced
 // (msc_state_set_sweep_rows) -- never a call's (route_sweep)
-static uint64_t view_rows(const msc_state *st) {
+uint64_t msc::view_rows(const msc_state *st) {
   return st->sweep_rows_hint ? st->sweep_rows_hint : st->bound_view ? st->bound_view->nrows : 0;
 }
 
@@ -1841,7 +1812,7 @@ static uint64_t view_rows(const msc_state *st) {
 // rebuilt at the head of every call that scores with the fused plan, one small launch
 // ... and so does what the plan's nich blocks go by (NichPlanInfo: is a block's c1 one number per group, how far a value may
 // lie before a product of four could overflow) -- the same launch
-static int refresh_fused_tables(msc_state *st) {
+int msc::refresh_fused_tables(msc_state *st) {
   const bool packed = stages_nich(st->tile_path);
   if (!st->fuse_any && !st->nich_blocks_any && !packed) return MSC_OK;
   if (launch_fuse_tables(st->ctx->stream, st->desc_fuse_dev, (int)st->fuse_split, (st->nich_blocks_any || packed) ? (int)st->fuse_nfeat : (int)st->fuse_split, st->kpad))
@@ -1895,7 +1866,7 @@ static bool loo_needs_heavy(const msc_state *st) {
 // with leave-one-out blocks in LDS, plan_groups) pays once the rows nearly fill the chip -- C3, 1M rows: 140 us staged, 196
 // gathered; a 131k-row chunk: 0.33 ms against 0.03.  Both give a row the same bits (test_gpu_score.py::
 // test_both_leave_one_out_kernels_give_a_row_the_same_bits), so the CALL's rows choose.
-static int run_loo_own(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z, bool crp) {
+int msc::run_loo_own(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z, bool crp) {
   const int lds = read_switches().loo_lds;
   const bool staged = st->loo_staged != 0 && (lds < 0 ? nrows >= (uint64_t)kLooRows * kLooThreads * st->ctx->num_cus * 3 / 4 : lds != 0);
   MSC_HIP(grow_retained(st->retired, st->own, nrows));
@@ -2017,8 +1988,8 @@ static ScoreRoute route_score(const msc_state *st, uint64_t nrows, const void *o
   return r;
 }
 
-static int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z_dev, bool crp,
-                     bool niw_f32, float *out_dev, uint64_t ld_out) {
+int msc::run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z_dev, bool crp,
+                   bool niw_f32, float *out_dev, uint64_t ld_out) {
   hipStream_t s = st->ctx->stream;
   const float *prior = crp ? st->logpc : nullptr;
   if (z_dev) MSC_TRY(run_loo_own(st, row0, nrows, z_dev, crp));
@@ -2144,15 +2115,11 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
   return MSC_OK;
 }
 
-static int commit(msc_state *st) {
+int msc::commit(msc_state *st) {
   MSC_TRY(launch_commit_all(st));
   st->valid.committed();
   return MSC_OK;
 }
-
-// internal flags of accumulate_impl, next to the public MSC_ACC_*: the additive tables are already zero (a fused
-// sweep kernel did it); commit and prepare in one launch, which also moves the random stream on (msc_sweep_step)
-enum : uint32_t { kAccZeroed = 0x100, kAccThenPrepare = 0x200 };
 
 static int commit_and_prepare(msc_state *st, bool bump_rng = true) {
   hipStream_t s = st->ctx->stream;
@@ -2172,8 +2139,8 @@ static int commit_and_prepare(msc_state *st, bool bump_rng = true) {
   return MSC_OK;
 }
 
-static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
-                           uint64_t nrows, const int32_t *z_dev, uint32_t flags) {
+int msc::accumulate_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                         uint64_t nrows, const int32_t *z_dev, uint32_t flags) {
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   hipStream_t s = st->ctx->stream;
   if (flags & MSC_ACC_RESET) {
@@ -2298,7 +2265,7 @@ static bool sweep_rows_pays(const msc_state *st, const Switches &sw, uint32_t gr
 }
 
 // no niw feature and no count beyond the tables: what the fused sweep kernels score
-static bool sweep_plain(const msc_state *st) {
+bool msc::sweep_plain(const msc_state *st) {
   for (uint32_t f = 0; f < st->nfeat; f++) if (gp_beyond_table(st, f)) return false;
   return st->n_niw == 0;
 }
@@ -2371,9 +2338,9 @@ static SweepRoute route_sweep(const msc_state *st, uint64_t nrows) {
 // index there, so consecutive sweeps need no host -> device traffic (and replay as a graph, msc_sweep_step)
 // `zeroed` non-null = part of a sweep step: the fused kernels also empty the additive tables for the accumulate pass
 // that follows (*zeroed says whether one did), and the increment of the sweep index is left to that pass's tail.
-static int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
-                             uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep,
-                             bool *zeroed = nullptr) {
+int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                           uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep,
+                           bool *zeroed) {
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   if (nrows == 0) return MSC_OK;
   if (!st->rng_valid || st->rng_seed != seed || st->rng_sweep != sweep) {
@@ -2494,9 +2461,6 @@ extern "C" int msc_sweep_assign(msc_state *st, const msc_dataview *view, const u
 // launches of a few microseconds each and the gaps between them are the cost, so its steady state -- same
 // view, rows and assignment vector, consecutive sweep indices -- is captured once as a HIP graph and replayed.
 // ---------------------------------------------------------------------------
-static int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
-                           uint64_t nrows, const int32_t *z_dev, uint32_t flags);
-
 extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                               uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
   MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
@@ -2611,621 +2575,6 @@ extern "C" int msc_sweep_step_stats(const msc_state *st, uint64_t *eager_steps, 
   MSC_REQUIRE(st, "null argument");
   if (eager_steps) *eager_steps = st->step_graph.n_eager;
   if (graph_steps) *graph_steps = st->step_graph.n_replayed;
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The sequential sweep (k_sweep_seq): one workgroup carries the chain; the state carries over in global memory between
-// launches, and a launch takes as many row visits as fit kSeqLaunchUs by seq_visit_us.
-// ---------------------------------------------------------------------------
-constexpr double kSeqLaunchUs = 20000.0;        // what one launch may take (estimated)
-constexpr uint64_t kSeqMaxVisitsPerLaunch = 10000;
-
-// An upper estimate of one row visit, in microseconds: a fixed part (barriers, the draw, a nich prepare) plus the table
-// entries a leave and a join rebuild and the (group, feature) scores; fitted to the visits of profiles/sequential.txt (one
-// nich column to the C3 mix, K = 16 to 1024): launches measured there at 11.9 ms on average, 26.3 ms the longest
-static double seq_visit_us(const msc_state *st) {
-  double rows = 0.0;                              // table entries prepare_group writes per (feature, group)
-  for (uint32_t f = 0; f < st->nfeat; f++) {
-    switch (st->feats[f].family) {
-      case MSC_BB: rows += 4; break;
-      case MSC_GP:
-      case MSC_BNB: rows += 2.0 * st->desc_host[f].vcap + 4; break;
-      case MSC_DD: rows += 2.0 * st->feats[f].dim + 2; break;
-      case MSC_NICH: rows += 14; break;
-      default: break;
-    }
-  }
-  return 16.0 + 0.02 * 2.0 * rows + 0.007 * (double)st->K * (double)st->nfeat;
-}
-
-// whether the sequential kernel takes a state: ok, or the status and why not
-struct SeqRoute { int rc = MSC_OK; const char *why = ""; };
-static SeqRoute route_sequential(const msc_state *st) {
-  SeqRoute r;
-  for (const auto &h : st->feats) {
-    // niw, dm: prepare kernels of their own (msc_entity_op sends them down the general path); bbnc: a slot that empties
-    // mid-sweep would be offered with a stale p (free slots' p is drawn between sweeps, mixture_state refresh_free_slots)
-    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
-      r.rc = MSC_EUNSUPPORTED;
-      r.why = "the sequential sweep takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
-      return r;
-    }
-  }
-  if (st->nfeat > (uint32_t)kSeqMaxFeat) {
-    r.rc = MSC_EUNSUPPORTED;
-    r.why = "the sequential sweep takes at most 256 features";
-  } else if (st->K > kSeqMaxGroups) {
-    r.rc = MSC_EUNSUPPORTED;
-    r.why = "the sequential sweep takes at most 8192 groups";
-  }
-  return r;
-}
-
-extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
-                                    uint64_t nrows, uint64_t row_id0, int32_t *z_dev, const uint32_t *order_dev,
-                                    uint32_t nsweeps, uint64_t seed, uint64_t sweep, int32_t *trace_dev) {
-  MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
-  MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
-  MSC_TRY(refuse_mid_step(st, "msc_sweep_sequential"));
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(device_error_check(st->ctx));
-  const SeqRoute route = route_sequential(st);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
-  MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  if (nrows == 0 || nsweeps == 0) return MSC_OK;
-  // every table current before (as msc_entity_op)
-  hipStream_t s = st->ctx->stream;
-  MSC_TRY(ensure_all_current(st));
-  const uint64_t visits = (uint64_t)nsweeps * nrows;
-  const uint64_t per_launch = (uint64_t)std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / seq_visit_us(st)));
-  for (uint64_t v0 = 0; v0 < visits; v0 += per_launch) {
-    const uint64_t v1 = std::min(visits, v0 + per_launch);
-    const int rc = launch_sweep_seq(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, row_id0, z_dev, order_dev,
-                                    v0, v1, seed, sweep, st->red_i64, st->cnt_u32, st->alpha, st->logpc, trace_dev);
-    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq does not take this shape");
-    if (rc) return fail(MSC_EHIP, "k_sweep_seq launch failed: %s", hipGetErrorString(hipGetLastError()));
-  }
-  // the kernel kept every table current: additive sums, fields, constants, counts and CRP terms
-  st->valid.kept_current();
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The blocked (uncollapsed) Gibbs sampler (kernels_blocked.hip, blocked_post.hpp): draw every slot's parameters and the
-// stick weights from the tables, then every row's slot independently under them.
-// ---------------------------------------------------------------------------
-// Which assign kernel a state takes, and whether the sampler takes it at all.  By the state alone: every kernel adds a
-// row's terms in the same order (blk_tile_scores), so a sub-range draws what the whole draws whichever is chosen.
-//   nich1   a single nich column: the row's value in a register, no LDS
-//   staged  up to 256 features: the workgroup's row values staged in LDS once, [feature][row] -- 256 rows a workgroup up
-//           to 32 features, 128 up to 64, 64 beyond (32 KiB at most, 64 KiB from 129 features on)
-//   global  more features than that: the values re-read from the columns for every eight slots
-// The split-merge move takes the same families and shapes (every kernel adds a row's terms in the same order, so the
-// choice never changes a bit); its staged kernel holds one feature fewer.  who: the caller, as the message names it.
-struct BlockedRoute { int rc = MSC_OK; std::string why; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
-constexpr uint32_t kBlockedStagedMax = 256;             // (at most 32 KiB of LDS a workgroup: several a compute unit)
-constexpr uint32_t kSplitMergeStagedMax = 255;          // (the codes and the waves' sums within 64 KiB of LDS a workgroup)
-static BlockedRoute route_blocked(const msc_state *st, const char *who, uint32_t staged_max) {
-  BlockedRoute r;
-  for (const auto &h : st->feats)
-    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
-      r.rc = MSC_EUNSUPPORTED;
-      r.why = std::string(who) + " takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
-      return r;
-    }
-  if (st->nfeat >= blocked::kStickTag) {
-    r.rc = MSC_EUNSUPPORTED;
-    r.why = std::string(who) + " takes fewer than 32767 features";
-    return r;
-  }
-  if (st->nfeat == 1 && st->feats[0].family == MSC_NICH) r.kernel = BlockedKernel::nich1;
-  else if (st->nfeat <= staged_max) {
-    r.kernel = BlockedKernel::staged;
-    r.block = st->nfeat <= 32 ? 256 : st->nfeat <= 64 ? 128 : 64;
-  }
-  return r;
-}
-static BlockedRoute route_sweep_blocked(const msc_state *st) { return route_blocked(st, "the blocked sweep", kBlockedStagedMax); }
-static BlockedRoute route_splitmerge(const msc_state *st) { return route_blocked(st, "split-merge", kSplitMergeStagedMax); }
-
-// a feature's slices in a state's parameter table (UINT32_MAX: row 0, the log weights), as msc_blocked_tables and
-// msc_split_merge_tables hand them out
-static void blocked_table_slices(const msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
-  const bool w = feature == UINT32_MAX;
-  if (dev) *dev = st->blk_tab + (w ? 0 : (size_t)st->blk_feats_host[feature].slice0 * st->kpad);
-  if (nslices) *nslices = w ? 1u : st->blk_feats_host[feature].nslices;
-  if (ld) *ld = st->kpad;
-}
-
-// the parameter table and the features as the kernels read them (columns from the current binding, if any)
-static int blocked_setup(msc_state *st) {
-  if (!st->blk_tab) {
-    uint32_t rows = 1;
-    for (const auto &h : st->feats) rows += blocked_slices(h.family, h.dim);
-    MSC_TRY(alloc_zeroed(st->blk_tab, (size_t)rows * st->kpad));
-    MSC_TRY(alloc_zeroed(st->blk_work, 2 * (size_t)st->K));
-    MSC_TRY(alloc_zeroed(st->blk_feats_dev, std::max<size_t>(1, st->nfeat)));
-    st->blk_rows = rows;
-  }
-  std::vector<BlkFeat> fs(st->nfeat);
-  uint32_t row = 1;
-  for (uint32_t f = 0; f < st->nfeat; f++) {
-    const msc_feature_host &h = st->feats[f];
-    const FeatDesc &d = st->desc_host[f];
-    BlkFeat &b = fs[f];
-    std::memset(&b, 0, sizeof(b));
-    switch (h.family) {
-      case MSC_BB: b.kind = MSC_BLK_SELECT; break;
-      case MSC_GP:
-      case MSC_BNB: b.kind = MSC_BLK_LINEAR; break;
-      case MSC_DD: b.kind = MSC_BLK_GATHER; break;
-      case MSC_NICH: b.kind = MSC_BLK_NICH; break;
-      default: b.kind = MSC_BLK_NOOP; break;
-    }
-    b.slice0 = row;
-    b.nslices = blocked_slices(h.family, h.dim);
-    row += b.nslices;
-    b.family = h.family;
-    b.dim = h.dim;
-    b.tag = f;
-    b.col = d.col;
-    b.mask = d.mask;
-    b.hp = h.hp_dev;
-    b.raw_u32 = h.raw_u32;
-    b.raw_f32 = h.raw_f32;
-  }
-  if (fs.size() != st->blk_feats_host.size() ||
-      (!fs.empty() && std::memcmp(fs.data(), st->blk_feats_host.data(), fs.size() * sizeof(BlkFeat)) != 0)) {
-    if (!fs.empty()) {
-      MSC_HIP(hipMemcpyAsync(st->blk_feats_dev, fs.data(), fs.size() * sizeof(BlkFeat), hipMemcpyHostToDevice, st->ctx->stream));
-      MSC_HIP(hipStreamSynchronize(st->ctx->stream));
-    }
-    st->blk_feats_host = std::move(fs);
-  }
-  return MSC_OK;
-}
-
-static int blocked_draw_impl(msc_state *st, uint64_t seed, uint64_t sweep) {
-  // the draw reads the reference's fields and the group counts: both current before (the additive sums and the score
-  // constants it does not read are left as they are)
-  MSC_TRY(ensure_raw(st));
-  MSC_TRY(blocked_setup(st));
-  if (launch_blocked_draw(st->ctx->stream, st->blk_feats_dev, st->nfeat, st->K, st->kpad, st->cnt_u32, st->alpha, seed, sweep,
-                          st->blk_work, st->blk_tab))
-    return MSC_EHIP;
-  st->valid.drawn();
-  return MSC_OK;
-}
-
-static int blocked_assign_impl(msc_state *st, const BlockedRoute &route, const msc_dataview *view, const uint32_t *cols,
-                               uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
-  MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  MSC_REQUIRE(st->valid.draw_current(), "msc_blocked_assign: no parameter draw made from the tables as they stand (msc_blocked_draw "
-                                        "first; whatever changes tables, hyper-parameters, alpha or group counts makes a draw stale)");
-  MSC_TRY(blocked_setup(st));
-  if (launch_blocked_assign(st->ctx->stream, route.kernel, route.block, st->blk_feats_dev, (int)st->nfeat, st->blk_tab, st->K,
-                            st->kpad, row0, nrows, row_id0, z_dev, seed, sweep))
-    return MSC_EHIP;
-  return MSC_OK;
-}
-
-extern "C" int msc_blocked_draw(msc_state *st, uint64_t seed, uint64_t sweep) {
-  MSC_REQUIRE(st, "null state");
-  MSC_TRY(refuse_mid_step(st, "msc_blocked_draw"));
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_sweep_blocked(st);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
-  return blocked_draw_impl(st, seed, sweep);
-}
-
-extern "C" int msc_blocked_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
-  MSC_REQUIRE(st, "null state");
-  MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  const BlockedRoute route = route_sweep_blocked(st);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
-  MSC_TRY(blocked_setup(st));
-  blocked_table_slices(st, feature, dev, nslices, ld);
-  return MSC_OK;
-}
-
-extern "C" int msc_blocked_assign(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
-                                  uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep) {
-  MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
-  MSC_TRY(refuse_mid_step(st, "msc_blocked_assign"));
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_sweep_blocked(st);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
-  return blocked_assign_impl(st, route, view, cols, row0, nrows, row_id0, z_dev, seed, sweep);
-}
-
-extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
-                                 uint64_t row_id0, int32_t *z_dev, uint32_t nsweeps, uint64_t seed, uint64_t sweep,
-                                 int32_t *trace_dev, uint32_t *top_slot_dev) {
-  MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
-  MSC_TRY(refuse_mid_step(st, "msc_sweep_blocked"));
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_sweep_blocked(st);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
-  MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  hipStream_t s = st->ctx->stream;
-  for (uint32_t i = 0; i < nsweeps; i++) {
-    MSC_TRY(blocked_draw_impl(st, seed, sweep + i));
-    MSC_TRY(blocked_assign_impl(st, route, view, cols, row0, nrows, row_id0, z_dev, seed, sweep + i));
-    MSC_TRY(accumulate_impl(st, view, cols, row0, nrows, z_dev, MSC_ACC_RESET));
-    if (trace_dev && nrows)
-      MSC_HIP(hipMemcpyAsync(trace_dev + (size_t)i * nrows, z_dev, nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (top_slot_dev && launch_blocked_top_slot(s, st->cnt_u32, st->K, top_slot_dev + i)) return MSC_EHIP;
-  }
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The split-merge move (kernels_splitmerge.hip, splitmerge_math.hpp): Metropolis-Hastings proposals that split one group
-// in two or merge two groups, the launch state reached by restricted BLOCKED Gibbs passes over the rows of the two groups.
-// ---------------------------------------------------------------------------
-// (Which assign kernel a state takes, and whether the move takes it at all: route_splitmerge, next to route_blocked.)
-// The pair state (three slots: the pair's two, and their union for score_data), created at the first call; its
-// hyper-parameters and alpha follow the state's before every call
-constexpr uint32_t kSmSlots = 3;
-static int sm_setup(msc_state *st) {
-  if (!st->sm_pair) {
-    std::vector<msc_feature_spec> specs(st->nfeat);
-    for (uint32_t f = 0; f < st->nfeat; f++) {
-      specs[f].family = st->feats[f].family;
-      specs[f].dim = st->feats[f].dim;
-    }
-    MSC_TRY(alloc_zeroed(st->sm_prop, 1));
-    MSC_TRY(alloc_zeroed(st->sm_sd, (size_t)st->nfeat * kSmSlots));
-    MSC_TRY(msc_state_create(st->ctx, specs.data(), st->nfeat, kSmSlots, &st->sm_pair));
-  }
-  msc_state *pair = st->sm_pair;
-  for (uint32_t f = 0; f < st->nfeat; f++)
-    if (pair->feats[f].hp != st->feats[f].hp)
-      MSC_TRY(msc_state_set_hp(pair, f, st->feats[f].hp.data(), st->feats[f].hp.size()));
-  pair->alpha = st->alpha;
-  return MSC_OK;
-}
-
-extern "C" int msc_split_merge(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
-                               uint64_t row_id0, int32_t *z_dev, uint32_t nproposals, uint32_t launch_iters, uint64_t seed,
-                               uint64_t sweep, double *log_dev, int32_t *trace_dev, int32_t *proposed_dev,
-                               uint64_t *counters_dev) {
-  MSC_REQUIRE(st && view && z_dev, "null argument");
-  MSC_TRY(refuse_mid_step(st, "msc_split_merge"));
-  MSC_REQUIRE(launch_iters <= 1024, "launch_iters %u beyond 1024", launch_iters);
-  MSC_REQUIRE(nrows < (1ull << 48), "msc_split_merge takes fewer than 2^48 rows");
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_splitmerge(st);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
-  MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  MSC_TRY(ensure_raw(st));                                 // (the group sizes: where a split finds its empty slot)
-  MSC_TRY(sm_setup(st));
-  msc_state *pair = st->sm_pair;
-  hipStream_t s = st->ctx->stream;
-  const uint32_t nparts = sm_assign_blocks(nrows, route.block);
-  MSC_HIP(reserve_synced(s, st->sm_ell, (size_t)std::max<uint64_t>(nrows, 1)));
-  MSC_HIP(reserve_synced(s, st->sm_part, nparts));
-  ZeroSpans zero;
-  zero.a = reinterpret_cast<unsigned long long *>(pair->red_i64.get());
-  zero.na = pair->n_i64;
-  zero.b = reinterpret_cast<unsigned long long *>(pair->red_f64.get());
-  zero.nb = pair->n_f64;
-  // the proposals move the group sizes on the device (k_sm_relabel); everything else is rebuilt at the end
-  st->valid.counts_changed();
-  for (uint32_t p = 0; p < nproposals; p++) {
-    const uint64_t sw = sweep + p;
-    if (launch_sm_begin(s, z_dev, nrows, row_id0, st->cnt_u32, st->K, seed, sw, st->sm_prop, st->sm_ell, zero)) return MSC_EHIP;
-    for (uint32_t t = 0; t <= launch_iters; t++) {
-      // the pair slots' suff-stats from the labels, their parameters and the K = 2 stick, then the rows' labels
-      MSC_TRY(accumulate_impl(pair, view, cols, row0, nrows, st->sm_ell, MSC_ACC_RESET | kAccZeroed));
-      MSC_TRY(blocked_setup(pair));
-      if (launch_blocked_draw(s, pair->blk_feats_dev, pair->nfeat, 2, pair->kpad, pair->cnt_u32, st->alpha,
-                              sm::stream_key(seed, sm::kStreamPass0 + t) ^ blocked::kKey, sw, pair->blk_work, pair->blk_tab))
-        return MSC_EHIP;
-      if (launch_sm_assign(s, route.kernel, route.block, t == launch_iters, t, pair->blk_feats_dev, (int)pair->nfeat,
-                           pair->blk_tab, pair->kpad, row0, nrows, row_id0, z_dev, st->sm_ell, st->sm_prop, seed, sw,
-                           st->sm_part, zero))
-        return MSC_EHIP;
-    }
-    if (proposed_dev && nrows)
-      MSC_HIP(hipMemcpyAsync(proposed_dev + (size_t)p * nrows, st->sm_ell, nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    // score_data of the two blocks and of their union (slot 2 = the sum of the additive tables of slots 0 and 1)
-    MSC_TRY(accumulate_impl(pair, view, cols, row0, nrows, st->sm_ell, MSC_ACC_RESET | kAccZeroed | MSC_ACC_NO_COMMIT));
-    if (launch_sm_merge_slots(s, pair->red_i64, (uint32_t)(pair->n_i64 / pair->kpad), pair->red_f64,
-                              (uint32_t)(pair->n_f64 / pair->kpad), pair->kpad))
-      return MSC_EHIP;
-    MSC_TRY(commit(pair));
-    if (launch_score_data(s, pair->desc_dev, (int)pair->nfeat, kSmSlots, pair->kpad, st->sm_sd))
-      return fail(MSC_EHIP, "k_score_data launch failed");
-    if (launch_sm_decide(s, st->sm_prop, st->sm_part, nparts, st->sm_sd, st->nfeat, pair->cnt_u32, st->alpha, seed, sw,
-                         log_dev ? log_dev + (size_t)p * 8 : nullptr, reinterpret_cast<unsigned long long *>(counters_dev)))
-      return MSC_EHIP;
-    if (launch_sm_relabel(s, nrows, z_dev, st->sm_ell, st->sm_prop, pair->cnt_u32, st->cnt_u32)) return MSC_EHIP;
-    if (trace_dev && nrows)
-      MSC_HIP(hipMemcpyAsync(trace_dev + (size_t)p * nrows, z_dev, nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  }
-  return accumulate_impl(st, view, cols, row0, nrows, z_dev, MSC_ACC_RESET);
-}
-
-extern "C" int msc_split_merge_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
-  MSC_REQUIRE(st, "null state");
-  MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  const BlockedRoute route = route_splitmerge(st);
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
-  MSC_TRY(sm_setup(st));
-  msc_state *pair = st->sm_pair;
-  MSC_TRY(blocked_setup(pair));
-  blocked_table_slices(pair, feature, dev, nslices, ld);
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Many sequential chains in one launch (k_sweep_seq_chains): workgroup c carries the chain of member state c.
-// ---------------------------------------------------------------------------
-struct msc_chains {
-  msc_context *ctx = nullptr;
-  std::vector<msc_state *> states;
-  // the per-chain table of a call: filled on the host in one of two pinned areas, taken in turn, and copied to table_dev
-  // on the stream.  uploaded[i] is recorded after the copy out of area i; the host waits for it before it refills area i,
-  // so no pending copy reads an area that is being written.  table_dev itself is ordered by the stream: the copy of
-  // a call queues behind the launches of the call before it.
-  msc::PinnedBuf<msc::SeqChain> stage[2];
-  hipEvent_t uploaded[2] = {nullptr, nullptr};
-  bool pending[2] = {false, false};
-  int next = 0;
-  msc::DevBuf<msc::SeqChain> table_dev;   // [nchains]
-  msc::DevBuf<msc::ClonePair> pairs_dev;  // [nchains]: the pairs of a msc_chains_clone, staged through the same two areas
-};
-static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
-
-// the pinned staging area whose turn it is, once no pending copy reads it; chains_staged records the copy out of it
-static int chains_stage(msc_chains *ch, int *area) {
-  const int a = ch->next;
-  ch->next ^= 1;
-  if (ch->pending[a]) MSC_HIP(hipEventSynchronize(ch->uploaded[a]));
-  ch->pending[a] = false;
-  *area = a;
-  return MSC_OK;
-}
-static int chains_staged(msc_chains *ch, int area, hipStream_t s) {
-  MSC_HIP(hipEventRecord(ch->uploaded[area], s));
-  ch->pending[area] = true;
-  return MSC_OK;
-}
-
-extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc_chains **out) {
-  MSC_REQUIRE(states && out, "null argument");
-  *out = nullptr;
-  MSC_REQUIRE(nchains >= 1, "msc_chains_create: at least one state");
-  for (uint32_t c = 0; c < nchains; c++) {
-    const msc_state *st = states[c];
-    MSC_REQUIRE(st, "msc_chains_create: state %u is null", c);
-    MSC_REQUIRE(st->ctx == states[0]->ctx, "msc_chains_create: state %u lives on another context than state 0", c);
-    for (uint32_t b = 0; b < c; b++)
-      MSC_REQUIRE(states[b] != st, "msc_chains_create: state %u is state %u again (two workgroups on one state's tables "
-                                   "would race)", c, b);
-    MSC_REQUIRE(st->K == states[0]->K, "msc_chains_create: state %u has %u groups, state 0 has %u", c, st->K, states[0]->K);
-    MSC_REQUIRE(st->nfeat == states[0]->nfeat, "msc_chains_create: state %u has %u features, state 0 has %u", c, st->nfeat,
-                states[0]->nfeat);
-    for (uint32_t f = 0; f < st->nfeat; f++)
-      MSC_REQUIRE(st->feats[f].family == states[0]->feats[f].family && st->feats[f].dim == states[0]->feats[f].dim,
-                  "msc_chains_create: feature %u of state %u (family %d, dim %u) differs from state 0's (family %d, dim %u)",
-                  f, c, st->feats[f].family, st->feats[f].dim, states[0]->feats[f].family, states[0]->feats[f].dim);
-  }
-  const SeqRoute route = route_sequential(states[0]);      // (equal feature lists and K: one answer for all)
-  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
-  msc_context *ctx = states[0]->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  std::unique_ptr<msc_chains> ch(new (std::nothrow) msc_chains());
-  if (!ch) return fail(MSC_ENOMEM, "out of host memory");
-  ch->ctx = ctx;
-  ch->states.assign(states, states + nchains);
-  hipError_t e = ch->table_dev.alloc(nchains);
-  if (e == hipSuccess) e = ch->pairs_dev.alloc(nchains);
-  for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = ch->stage[i].alloc(nchains);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ch->uploaded[i], hipEventDisableTiming);
-  }
-  if (e != hipSuccess) {
-    for (hipEvent_t ev : ch->uploaded) if (ev) (void)hipEventDestroy(ev);
-    return fail(MSC_EHIP, "msc_chains_create: %s", hipGetErrorString(e));
-  }
-  for (msc_state *st : ch->states) st->chain_members++;
-  *out = ch.release();
-  return MSC_OK;
-}
-
-extern "C" int msc_chains_destroy(msc_chains *ch) {
-  if (!ch) return MSC_OK;
-  (void)hipSetDevice(ch->ctx->device);
-  (void)hipStreamSynchronize(ch->ctx->stream);             // (a launch may still read the table)
-  for (int i = 0; i < 2; i++) {
-    if (ch->pending[i]) (void)hipEventSynchronize(ch->uploaded[i]);
-    if (ch->uploaded[i]) (void)hipEventDestroy(ch->uploaded[i]);
-  }
-  for (msc_state *st : ch->states) st->chain_members--;
-  delete ch;
-  return MSC_OK;
-}
-
-extern "C" int msc_chains_size(const msc_chains *ch, uint32_t *nchains) {
-  MSC_REQUIRE(ch && nchains, "null argument");
-  *nchains = (uint32_t)ch->states.size();
-  return MSC_OK;
-}
-
-// What msc_chains_sweep and msc_chains_visit share: visits [v0, v1) of a call's nsweeps x nrows for every chain (visit v is
-// sweep v / nrows, position v % nrows of the order), with the outputs each of the two has (null: not wanted).
-struct ChainsOutputs {
-  uint32_t trace_every = 1;           // >= 1
-  uint64_t ntrace = 0;                // samples per chain of trace / occupied
-  int32_t *trace = nullptr;           // [nchains][ntrace][nrows]
-  uint32_t *occupied = nullptr;       // [nchains][ntrace]
-  double *logw = nullptr;             // [nchains]
-  float *visit_logp = nullptr;        // chain c's at + c * ld_logp
-  uint64_t ld_logp = 0;
-};
-static int chains_visits_impl(msc_chains *ch, const char *who, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
-                              uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev,
-                              uint64_t ld_order, uint64_t v0, uint64_t v1, const uint64_t *host_seeds, uint64_t sweep,
-                              const ChainsOutputs &out) {
-  const uint32_t n = (uint32_t)ch->states.size();
-  MSC_REQUIRE((z_dev && host_seeds) || v0 >= v1, "null argument");
-  MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
-  MSC_REQUIRE(ld_z >= nrows, "%s: ld_z %llu < nrows %llu", who, (unsigned long long)ld_z, (unsigned long long)nrows);
-  MSC_REQUIRE(!order_dev || ld_order == 0 || ld_order >= nrows, "%s: ld_order %llu is neither 0 (one order "
-              "for all chains) nor >= nrows %llu", who, (unsigned long long)ld_order, (unsigned long long)nrows);
-  for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  if (v0 >= v1) return MSC_OK;
-  // every table of every member current before, as msc_sweep_sequential
-  hipStream_t s = ctx->stream;
-  double visit_us = 0.0;
-  for (msc_state *st : ch->states) {
-    MSC_TRY(ensure_all_current(st));
-    visit_us = std::max(visit_us, seq_visit_us(st));
-  }
-  // the table of this call (pointers and alpha may have changed since the last one), through the pinned area whose turn it is
-  int a = 0;
-  MSC_TRY(chains_stage(ch, &a));
-  SeqChain *tab = ch->stage[a];
-  for (uint32_t c = 0; c < n; c++) {
-    const msc_state *st = ch->states[c];
-    SeqChain &e = tab[c];
-    e.feats = st->desc_dev;
-    e.cnt_acc = st->red_i64;
-    e.cnt_u32 = st->cnt_u32;
-    e.crp = st->logpc;
-    e.z = z_dev + (size_t)c * ld_z;
-    e.order = order_dev ? order_dev + (size_t)c * ld_order : nullptr;
-    e.trace = out.trace && out.ntrace ? out.trace + (size_t)c * out.ntrace * nrows : nullptr;
-    e.occupied = out.occupied && out.ntrace ? out.occupied + (size_t)c * out.ntrace : nullptr;
-    e.logw = out.logw ? out.logw + c : nullptr;
-    e.visit_logp = out.visit_logp ? out.visit_logp + (size_t)c * out.ld_logp : nullptr;
-    e.seed = host_seeds[c];
-    e.alpha = st->alpha;
-    e.pad = 0;
-  }
-  MSC_HIP(hipMemcpyAsync(ch->table_dev, tab, sizeof(SeqChain) * n, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, a, s));
-  // a launch's visits: what one chain may take in the launch's time (as msc_sweep_sequential, by the costliest member),
-  // divided by the rounds the grid runs in -- at this kernel's register count one workgroup is resident per CU
-  const msc_state *st0 = ch->states[0];
-  const double one = std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / visit_us));
-  const uint64_t rounds = (n + (uint32_t)std::max(1, ctx->num_cus) - 1) / (uint32_t)std::max(1, ctx->num_cus);
-  const uint64_t per_launch = std::max<uint64_t>(1, (uint64_t)one / rounds);
-  for (uint64_t w0 = v0; w0 < v1; w0 += per_launch) {
-    const uint64_t w1 = std::min(v1, w0 + per_launch);
-    const int rc = launch_sweep_seq_chains(s, ch->table_dev, n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows, row_id0, w0,
-                                           w1, sweep, out.trace_every);
-    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq_chains does not take this shape");
-    if (rc) return fail(MSC_EHIP, "k_sweep_seq_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
-  }
-  // the kernel kept every table of every member current: additive sums, fields, constants, counts and CRP terms
-  for (msc_state *st : ch->states) st->valid.kept_current();
-  return MSC_OK;
-}
-
-extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
-                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
-                                uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep, uint32_t trace_every,
-                                int32_t *trace_dev, uint32_t *occupied_dev) {
-  MSC_REQUIRE(ch && view, "null argument");
-  if (ch->states.empty()) return MSC_OK;
-  const bool tracing = trace_dev != nullptr || occupied_dev != nullptr;
-  MSC_REQUIRE(!tracing || trace_every >= 1, "msc_chains_sweep: trace_every must be >= 1 with a trace or an occupied array");
-  ChainsOutputs out;
-  out.trace_every = tracing ? trace_every : 1u;
-  out.ntrace = tracing ? nsweeps / trace_every : 0;
-  out.trace = trace_dev;
-  out.occupied = occupied_dev;
-  return chains_visits_impl(ch, "msc_chains_sweep", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, 0,
-                            (uint64_t)nsweeps * nrows, host_seeds, sweep, out);
-}
-
-extern "C" int msc_chains_visit(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
-                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
-                                uint64_t pos0, uint64_t npos, const uint64_t *host_seeds, uint64_t sweep, double *logw_dev,
-                                float *visit_logp_dev, uint64_t ld_logp) {
-  MSC_REQUIRE(ch && view, "null argument");
-  MSC_REQUIRE(pos0 <= nrows && npos <= nrows - pos0, "msc_chains_visit: positions [%llu, %llu + %llu) beyond nrows %llu",
-              (unsigned long long)pos0, (unsigned long long)pos0, (unsigned long long)npos, (unsigned long long)nrows);
-  MSC_REQUIRE(!visit_logp_dev || ld_logp >= nrows, "msc_chains_visit: ld_logp %llu < nrows %llu", (unsigned long long)ld_logp,
-              (unsigned long long)nrows);
-  if (ch->states.empty() || npos == 0) return MSC_OK;
-  ChainsOutputs out;
-  out.logw = logw_dev;
-  out.visit_logp = visit_logp_dev;
-  out.ld_logp = ld_logp;
-  return chains_visits_impl(ch, "msc_chains_visit", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, pos0,
-                            pos0 + npos, host_seeds, sweep, out);
-}
-
-extern "C" int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, int32_t *z_dev, uint64_t ld_z, uint64_t nrows) {
-  MSC_REQUIRE(ch && host_ancestors, "null argument");
-  const uint32_t n = (uint32_t)ch->states.size();
-  MSC_REQUIRE(z_dev || nrows == 0, "null argument");
-  MSC_REQUIRE(ld_z >= nrows, "msc_chains_clone: ld_z %llu < nrows %llu", (unsigned long long)ld_z, (unsigned long long)nrows);
-  uint32_t npairs = 0;
-  for (uint32_t c = 0; c < n; c++) {
-    const uint32_t a = host_ancestors[c];
-    MSC_REQUIRE(a < n, "msc_chains_clone: ancestor %u of chain %u is not a chain (%u chains)", a, c, n);
-    MSC_REQUIRE(host_ancestors[a] == a, "msc_chains_clone: chain %u copies chain %u, which is itself overwritten (by chain "
-                                        "%u): a source must survive in place", c, a, host_ancestors[a]);
-    npairs += a != c;
-  }
-  for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_clone: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
-  if (npairs == 0) return MSC_OK;
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  hipStream_t s = ctx->stream;
-  // a source's additive tables hold the truth before they are read (after a sweep they do: this launches nothing then)
-  for (uint32_t c = 0; c < n; c++)
-    if (host_ancestors[c] != c) MSC_TRY(ensure_additive(ch->states[host_ancestors[c]]));
-  int area = 0;
-  MSC_TRY(chains_stage(ch, &area));
-  ClonePair *tab = reinterpret_cast<ClonePair *>(ch->stage[area].get());
-  const msc_state *st0 = ch->states[0];
-  uint32_t p = 0;
-  for (uint32_t c = 0; c < n; c++) {
-    const uint32_t a = host_ancestors[c];
-    if (a == c) continue;
-    const msc_state *src = ch->states[a];
-    msc_state *dst = ch->states[c];
-    ClonePair &e = tab[p++];
-    e.src_i64 = src->red_i64;
-    e.dst_i64 = dst->red_i64;
-    e.src_f64 = src->red_f64;
-    e.dst_f64 = dst->red_f64;
-    e.src_z = z_dev + (size_t)a * ld_z;
-    e.dst_z = z_dev + (size_t)c * ld_z;
-  }
-  MSC_HIP(hipMemcpyAsync(ch->pairs_dev, tab, sizeof(ClonePair) * npairs, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, area, s));
-  if (launch_chains_clone(s, ch->pairs_dev, npairs, st0->n_i64, st0->n_f64, nrows))
-    return fail(MSC_EHIP, "k_chains_clone launch failed: %s", hipGetErrorString(hipGetLastError()));
-  // a destination's additive tables were replaced as a whole and alone hold its truth now, as after an accumulate that
-  // has not committed: the fields, the score constants and the CRP terms are rebuilt from them by the next call's ensure
-  // steps.  (additive_rewritten(), msc_state_reduce_unpack's event, would not do: that call comes between an uncommitted
-  // accumulate and a commit, so the fields are already marked stale there; a chain a sweep kept current has them marked
-  // current, and they would stay the destination's old ones.)
-  for (uint32_t c = 0; c < n; c++)
-    if (host_ancestors[c] != c) ch->states[c]->valid.accumulated();
   return MSC_OK;
 }
 
@@ -3438,1146 +2787,5 @@ extern "C" int msc_value_op_single(msc_context *ctx, int family, uint32_t dim, i
   if (back.status != 1) return fail(MSC_EHIP, "k_value_op did not complete");
   if (op <= MSC_OP_REMOVE) std::memcpy(host_ss, mb + hd.ss_off, ss_bytes);
   else *score = back.score;
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// grid hyper-parameter inference (kernels_hp.hip)
-// ---------------------------------------------------------------------------
-// group blocks of a score launch: enough workgroups for a few per CU, at least one LDS stage of slots per block
-static uint32_t hp_group_blocks(const msc_state *st, size_t point_blocks) {
-  const uint32_t stages = (st->K + 63) / 64;
-  const size_t want = (4 * (size_t)st->ctx->num_cus + point_blocks - 1) / point_blocks;
-  return (uint32_t)std::max<size_t>(1, std::min<size_t>(stages, want));
-}
-
-extern "C" int msc_hp_grid_create(msc_state *st, uint32_t feature, const float *host_blocks, size_t block_floats,
-                                  uint32_t npoints, const double *host_logprior, msc_hp_grid **out) {
-  MSC_REQUIRE(st && host_blocks && out, "null argument");
-  *out = nullptr;
-  MSC_REQUIRE(npoints > 0, "a grid needs at least one point");
-  HpJob job;
-  std::memset(&job, 0, sizeof job);
-  if (feature == MSC_HP_CLUSTER) {
-    MSC_REQUIRE(block_floats == 1, "the alpha grid has blocks of one float, not %zu", block_floats);
-    for (uint32_t g = 0; g < npoints; g++)
-      MSC_REQUIRE(host_blocks[g] > 0.f, "alpha grid point %u is %g: alpha must be positive (group_manager.hpp:78)", g,
-                  (double)host_blocks[g]);
-    job.family = kHpCluster;
-  } else {
-    MSC_REQUIRE(feature < st->nfeat, "feature %u out of range", feature);
-    const msc_feature_host &h = st->feats[feature];
-    if (h.family == MSC_NIW)
-      return fail(MSC_EUNSUPPORTED, "feature %u: niw has no hyper-parameter grid (upstream defines none, and every point "
-                  "would need its own factorisation of Psi)", feature);
-    MSC_REQUIRE(block_floats == h.hp.size(), "feature %u: hp block has %zu floats, expected %zu", feature, block_floats,
-                h.hp.size());
-    job.family = h.family;
-    job.dim = h.dim;
-    job.nu32 = raw_u32_rows(h.family, h.dim);
-    job.nf32 = raw_f32_rows(h.family);
-    job.raw_u32 = h.raw_u32;
-    job.raw_f32 = h.raw_f32;
-  }
-  job.hpf = (uint32_t)block_floats;
-  job.npoints = npoints;
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  std::unique_ptr<msc_hp_grid> g(new (std::nothrow) msc_hp_grid());
-  if (!g) return fail(MSC_ENOMEM, "out of host memory");
-  g->st = st;
-  g->feature = feature;
-  g->blocks.assign(host_blocks, host_blocks + (size_t)npoints * block_floats);
-  const hipStream_t s = st->ctx->stream;
-  MSC_HIP(g->grid_dev.alloc(g->blocks.size()));
-  MSC_HIP(hipMemcpyAsync(g->grid_dev, g->blocks.data(), g->blocks.size() * sizeof(float), hipMemcpyHostToDevice, s));
-  if (host_logprior) {
-    MSC_HIP(g->logprior_dev.alloc(npoints));
-    MSC_HIP(hipMemcpyAsync(g->logprior_dev, host_logprior, (size_t)npoints * sizeof(double), hipMemcpyHostToDevice, s));
-  }
-  job.grid = g->grid_dev;
-  job.logprior = g->logprior_dev;
-  g->job = job;
-  MSC_HIP(g->job_dev.alloc(1));
-  MSC_HIP(hipMemcpyAsync(g->job_dev, &g->job, sizeof(HpJob), hipMemcpyHostToDevice, s));
-  MSC_HIP(hipStreamSynchronize(s));
-  *out = g.get();
-  st->hp_grids.push_back(std::move(g));
-  return MSC_OK;
-}
-
-extern "C" int msc_hp_grid_destroy(msc_hp_grid *grid) {
-  if (!grid) return MSC_OK;
-  msc_state *st = grid->st;
-  (void)hipSetDevice(st->ctx->device);
-  (void)hipStreamSynchronize(st->ctx->stream);
-  st->hp_grids.erase(std::remove_if(st->hp_grids.begin(), st->hp_grids.end(),
-                                    [grid](const std::unique_ptr<msc_hp_grid> &g) { return g.get() == grid; }),
-                     st->hp_grids.end());   // (the state owns its grids: this deletes it)
-  return MSC_OK;
-}
-
-extern "C" int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, double *out_dev) {
-  MSC_REQUIRE(grid && out_dev, "null argument");
-  msc_state *st = grid->st;
-  MSC_TRY(refuse_mid_step(st, "msc_hp_grid_score"));
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(ensure_raw(st));
-  const uint32_t np = grid->job.npoints;
-  if (grid->job.family == kHpCluster) {
-    if (launch_crp_grid_score(st->ctx->stream, grid->job_dev, np, st->cnt_u32, st->K, out_dev))
-      return fail(MSC_EHIP, "k_crp_grid_score launch failed");
-    return MSC_OK;
-  }
-  const uint32_t nblk = hp_group_blocks(st, (np + 255) / 256);
-  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_part, (size_t)nblk * np));
-  if (launch_hp_grid_score(st->ctx->stream, grid->job_dev, 1, np, st->K, st->kpad, st->cnt_u32, slots_dev, nblk,
-                           st->hp_part, out_dev))
-    return fail(MSC_EHIP, "k_hp_grid_score launch failed");
-  return MSC_OK;
-}
-
-// A kernel has written a feature's hp block (and, dd / dm, its alpha sum into the state's descriptor) on the device; the
-// host's bookkeeping follows as msc_state_set_hp keeps it: the host copy, the score tables' staleness and the alpha sum
-// in every host copy of the descriptor.  (msc_hp_grid_gibbs and msc_hp_slice.)
-static void hp_installed(msc_state *st, uint32_t feature, const float *blk) {
-  msc_feature_host &h = st->feats[feature];
-  std::copy(blk, blk + h.hp.size(), h.hp.begin());
-  st->valid.hp_changed(feature);
-  (void)refresh_alpha_sum(st, feature);
-}
-// the same for alpha, which the device takes from the host at the next call that reads it (msc_state_set_alpha)
-static void alpha_installed(msc_state *st, float alpha) {
-  st->alpha = alpha;
-  st->valid.alpha_changed();
-}
-
-extern "C" int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint32_t n, const uint8_t *slots_dev,
-                                 uint64_t seed, uint64_t sweep, uint32_t *chosen_host, double *const *scores_dev) {
-  MSC_REQUIRE(st && grids && chosen_host, "null argument");
-  MSC_REQUIRE(n > 0, "no grids");
-  MSC_TRY(refuse_mid_step(st, "msc_hp_grid_gibbs"));
-  // the feature grids first (one score launch), the alpha grid last; order[j] = the caller's index of job j
-  std::vector<uint32_t> order;
-  std::vector<bool> seen(st->nfeat + 1, false);
-  for (int pass = 0; pass < 2; pass++)
-    for (uint32_t i = 0; i < n; i++) {
-      MSC_REQUIRE(grids[i] && grids[i]->st == st, "grid %u is null or belongs to another state", i);
-      const bool cluster = grids[i]->feature == MSC_HP_CLUSTER;
-      if (cluster != (pass == 1)) continue;
-      const uint32_t slot = cluster ? st->nfeat : grids[i]->feature;
-      MSC_REQUIRE(!seen[slot], "two grids of %s %u in one step", cluster ? "alpha" : "feature", grids[i]->feature);
-      seen[slot] = true;
-      order.push_back(i);
-    }
-  const uint32_t nfj = (uint32_t)(order.size() - (seen[st->nfeat] ? 1 : 0));
-  size_t max_np = 0, pblocks = 0;
-  for (uint32_t j = 0; j < nfj; j++) {
-    const uint32_t np = grids[order[j]]->job.npoints;
-    max_np = std::max<size_t>(max_np, np);
-    pblocks += (np + 255) / 256;
-  }
-  const uint32_t nblk = nfj ? hp_group_blocks(st, pblocks) : 1;
-  std::vector<HpJob> &jobs = st->hp_jobs_host;
-  jobs.assign(n, HpJob());
-  size_t part = 0, out = 0;
-  for (uint32_t j = 0; j < n; j++) {
-    const msc_hp_grid *g = grids[order[j]];
-    HpJob &J = jobs[j];
-    J = g->job;
-    J.part_off = part;
-    J.out_off = out;
-    part += (size_t)nblk * J.npoints;
-    out += J.npoints;
-    J.scores_out = scores_dev ? scores_dev[order[j]] : nullptr;
-    if (g->feature == MSC_HP_CLUSTER) {
-      J.stream = UINT64_MAX - st->nfeat;
-    } else {
-      const msc_feature_host &h = st->feats[g->feature];
-      J.stream = UINT64_MAX - g->feature;
-      J.hp_dst = h.hp_dev;
-      J.aux_dst = h.family == MSC_DD || h.family == MSC_DM ? &st->desc_dev[g->feature].aux : nullptr;
-    }
-  }
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(ensure_raw(st));
-  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_part, part));
-  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_out, out));
-  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_jobs_dev, n));
-  MSC_HIP(reserve_synced(st->ctx->stream, st->hp_chosen_dev, n));
-  const hipStream_t s = st->ctx->stream;
-  MSC_HIP(hipMemcpyAsync(st->hp_jobs_dev, jobs.data(), n * sizeof(HpJob), hipMemcpyHostToDevice, s));
-  if (nfj && launch_hp_grid_score(s, st->hp_jobs_dev, nfj, (uint32_t)max_np, st->K, st->kpad, st->cnt_u32, slots_dev, nblk,
-                                  st->hp_part, st->hp_out))
-    return fail(MSC_EHIP, "k_hp_grid_score launch failed");
-  if (nfj < n && launch_crp_grid_score(s, st->hp_jobs_dev + nfj, jobs[nfj].npoints, st->cnt_u32, st->K, st->hp_out))
-    return fail(MSC_EHIP, "k_crp_grid_score launch failed");
-  if (launch_hp_grid_draw(s, st->hp_jobs_dev, n, st->hp_out, seed, sweep, st->hp_chosen_dev))
-    return fail(MSC_EHIP, "k_hp_grid_draw launch failed");
-  std::vector<uint32_t> picked(n);
-  MSC_HIP(hipMemcpyAsync(picked.data(), st->hp_chosen_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  MSC_HIP(hipStreamSynchronize(s));                   // the step's one wait
-  // the draw kernel has set the device hp (and a dd / dm descriptor's alpha sum); the host's bookkeeping follows as
-  // msc_state_set_hp / msc_state_set_alpha keep it
-  int rc = MSC_OK;
-  for (uint32_t j = 0; j < n; j++) {
-    const msc_hp_grid *g = grids[order[j]];
-    const uint32_t k = picked[j];
-    chosen_host[order[j]] = k;
-    if (k >= jobs[j].npoints) {
-      rc = fail(MSC_EINVAL, "grid %u: no point has a finite positive weight; nothing installed", order[j]);
-      continue;
-    }
-    const float *blk = g->blocks.data() + (size_t)k * jobs[j].hpf;
-    if (g->feature == MSC_HP_CLUSTER) alpha_installed(st, blk[0]);
-    else hp_installed(st, g->feature, blk);
-  }
-  return rc;
-}
-
-// ---------------------------------------------------------------------------
-// slice sampling of hyper-parameters and bbnc group parameters (downstream's hp / theta kernels; kernels_slice.hip)
-// ---------------------------------------------------------------------------
-static constexpr uint64_t kSliceKey = 0x2545F4914F6CDD1Dull;   // the slice steps' key is seed ^ this
-
-static size_t slice_align(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// the support of a coordinate: every coordinate sliced is a positive float but nich mu
-static const char *slice_unsupported(int family, uint32_t coord) {
-  switch (family) {
-    case MSC_BB: case MSC_BBNC: case MSC_GP: case MSC_NICH: return nullptr;
-    case MSC_BNB: return coord == 2 ? "bnb r is an integer" : nullptr;
-    case MSC_DD: case MSC_DM: return "dd / dm alphas are not sliced";
-    case MSC_NIW: return "niw hyper-parameters are not sliced";
-    default: return "the family has no hyper-parameters";
-  }
-}
-
-extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
-                            uint64_t seed, uint64_t sweep, float *values_host, uint32_t *evals_host) {
-  MSC_REQUIRE(st && coords, "null argument");
-  MSC_REQUIRE(n > 0, "no coordinates");
-  MSC_TRY(refuse_mid_step(st, "msc_hp_slice"));
-  // the targets in order of first appearance (slot nfeat = alpha), each with its entries in the caller's order
-  std::vector<int32_t> tix(st->nfeat + 1, -1);
-  std::vector<std::vector<uint32_t>> members;
-  std::vector<uint32_t> tslot;
-  for (uint32_t i = 0; i < n; i++) {
-    const msc_slice_coord &c = coords[i];
-    const bool cluster = c.feature == MSC_HP_CLUSTER;
-    uint32_t hpf = 1;
-    if (cluster) {
-      MSC_REQUIRE(c.coord == 0, "entry %u: alpha has one coordinate, not %u", i, c.coord);
-      MSC_REQUIRE(c.prior != MSC_PRIOR_NONINF_BETA, "entry %u: alpha has no partner for a noninformative beta prior", i);
-    } else {
-      MSC_REQUIRE(c.feature < st->nfeat, "entry %u: feature %u out of range", i, c.feature);
-      const msc_feature_host &h = st->feats[c.feature];
-      if (const char *why = slice_unsupported(h.family, c.coord))
-        return fail(MSC_EUNSUPPORTED, "entry %u (feature %u): %s", i, c.feature, why);
-      hpf = (uint32_t)h.hp.size();
-      MSC_REQUIRE(c.coord < hpf, "entry %u: coordinate %u outside feature %u's hp block of %u floats", i, c.coord,
-                  c.feature, hpf);
-      MSC_REQUIRE(c.prior != MSC_PRIOR_NONINF_BETA || (c.partner < hpf && c.partner != c.coord),
-                  "entry %u: partner %u is not another coordinate of feature %u", i, c.partner, c.feature);
-    }
-    MSC_REQUIRE(c.width > 0.f && std::isfinite(c.width), "entry %u: width %g is not a positive finite float", i,
-                (double)c.width);
-    MSC_REQUIRE(c.prior <= MSC_PRIOR_NONINF_BETA, "entry %u: unknown prior %u", i, c.prior);
-    MSC_REQUIRE(c.prior != MSC_PRIOR_EXPONENTIAL || (c.prior_a > 0.f && std::isfinite(c.prior_a)),
-                "entry %u: exponential prior with lambda %g", i, (double)c.prior_a);
-    MSC_REQUIRE(c.prior != MSC_PRIOR_NORMAL || (c.prior_b > 0.f && std::isfinite(c.prior_b) && std::isfinite(c.prior_a)),
-                "entry %u: normal prior with mu %g, sigma2 %g", i, (double)c.prior_a, (double)c.prior_b);
-    const uint32_t slot = cluster ? st->nfeat : c.feature;
-    if (tix[slot] < 0) {
-      tix[slot] = (int32_t)members.size();
-      members.emplace_back();
-      tslot.push_back(slot);
-    }
-    members[(size_t)tix[slot]].push_back(i);
-  }
-  const uint32_t nt = (uint32_t)members.size();
-  std::vector<SliceTarget> targets(nt);
-  std::vector<SliceCoord> dc(n);
-  std::vector<uint32_t> caller(n);                  // device entry -> the caller's index
-  uint32_t at = 0;
-  for (uint32_t t = 0; t < nt; t++) {
-    SliceTarget &T = targets[t];
-    std::memset(&T, 0, sizeof T);
-    const uint32_t slot = tslot[t];
-    T.target = slot;
-    T.first = at;
-    T.n = (uint32_t)members[t].size();
-    if (slot == st->nfeat) {
-      T.family = kHpCluster;
-      T.hpf = 1;
-      T.alpha = st->alpha;
-    } else {
-      const msc_feature_host &h = st->feats[slot];
-      T.family = h.family;
-      T.hpf = (uint32_t)h.hp.size();
-      T.nu32 = raw_u32_rows(h.family, h.dim);
-      T.nf32 = raw_f32_rows(h.family);
-      T.raw_u32 = h.raw_u32;
-      T.raw_f32 = h.raw_f32;
-      T.hp = h.hp_dev;
-    }
-    for (uint32_t i : members[t]) {
-      const msc_slice_coord &c = coords[i];
-      dc[at] = SliceCoord{c.coord, c.prior, c.prior == MSC_PRIOR_NONINF_BETA ? c.partner : 0u, c.width, c.prior_a,
-                          c.prior_b};
-      caller[at++] = i;
-    }
-  }
-  // one buffer: targets | entries | values | evals | status
-  const size_t o_coord = slice_align(nt * sizeof(SliceTarget)), o_val = o_coord + slice_align(n * sizeof(SliceCoord));
-  const size_t o_ev = o_val + slice_align(n * 4), o_stat = o_ev + slice_align(n * 4), total = o_stat + slice_align(n * 4);
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(ensure_raw(st));
-  MSC_HIP(reserve_synced(st->ctx->stream, st->slice_buf, total));
-  std::vector<unsigned char> up(o_val);
-  std::memcpy(up.data(), targets.data(), nt * sizeof(SliceTarget));
-  std::memcpy(up.data() + o_coord, dc.data(), n * sizeof(SliceCoord));
-  const hipStream_t s = st->ctx->stream;
-  unsigned char *b = st->slice_buf;
-  MSC_HIP(hipMemcpyAsync(b, up.data(), up.size(), hipMemcpyHostToDevice, s));
-  if (launch_hp_slice(s, reinterpret_cast<const SliceTarget *>(b), nt, reinterpret_cast<const SliceCoord *>(b + o_coord),
-                      st->K, st->kpad, st->cnt_u32, slots_dev, seed ^ kSliceKey, sweep, reinterpret_cast<float *>(b + o_val),
-                      reinterpret_cast<uint32_t *>(b + o_ev), reinterpret_cast<uint32_t *>(b + o_stat)))
-    return fail(MSC_EHIP, "k_hp_slice launch failed");
-  std::vector<unsigned char> down(total - o_val);
-  MSC_HIP(hipMemcpyAsync(down.data(), b + o_val, down.size(), hipMemcpyDeviceToHost, s));
-  MSC_HIP(hipStreamSynchronize(s));                   // the call's one wait
-  const float *val = reinterpret_cast<const float *>(down.data());
-  const uint32_t *ev = reinterpret_cast<const uint32_t *>(down.data() + (o_ev - o_val));
-  const uint32_t *stat = reinterpret_cast<const uint32_t *>(down.data() + (o_stat - o_val));
-  // the kernel has written every feature's final block into its device hp; the host's bookkeeping follows
-  int rc = MSC_OK;
-  for (uint32_t t = 0; t < nt; t++) {
-    const SliceTarget &T = targets[t];
-    if (T.family == kHpCluster) {
-      alpha_installed(st, val[T.first + T.n - 1]);
-    } else {
-      std::vector<float> blk = st->feats[T.target].hp;
-      for (uint32_t e = T.first; e < T.first + T.n; e++) blk[dc[e].coord] = val[e];
-      hp_installed(st, T.target, blk.data());
-    }
-  }
-  for (uint32_t e = 0; e < n; e++) {
-    const uint32_t i = caller[e];
-    if (values_host) values_host[i] = val[e];
-    if (evals_host) evals_host[i] = ev[e];
-    if (stat[e] == kSliceNonFinite)
-      rc = fail(MSC_EINVAL, "entry %u (%s %u, coordinate %u): the target at the current value is not finite; left "
-                "unchanged", i, coords[i].feature == MSC_HP_CLUSTER ? "alpha" : "feature",
-                coords[i].feature == MSC_HP_CLUSTER ? 0u : coords[i].feature, coords[i].coord);
-  }
-  return rc;
-}
-
-extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const float *widths, uint32_t n,
-                               const uint8_t *slots_dev, uint64_t seed, uint64_t sweep, uint64_t *evals_host) {
-  MSC_REQUIRE(st && features && widths, "null argument");
-  MSC_REQUIRE(n > 0, "no features");
-  MSC_TRY(refuse_mid_step(st, "msc_theta_slice"));
-  std::vector<bool> seen(st->nfeat, false);
-  std::vector<ThetaJob> jobs(n);
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t f = features[i];
-    MSC_REQUIRE(f < st->nfeat, "feature %u out of range", f);
-    const msc_feature_host &h = st->feats[f];
-    MSC_REQUIRE(h.family == MSC_BBNC, "feature %u is not bbnc: only bbnc groups carry a parameter", f);
-    MSC_REQUIRE(!seen[f], "feature %u twice in one call", f);
-    seen[f] = true;
-    MSC_REQUIRE(widths[i] > 0.f && std::isfinite(widths[i]), "feature %u: width %g is not a positive finite float", f,
-                (double)widths[i]);
-    jobs[i] = ThetaJob{h.raw_u32, h.raw_f32, h.hp_dev, widths[i], f};
-  }
-  const uint32_t nb = theta_slice_blocks(st->K);
-  const size_t np = (size_t)n * nb;
-  const size_t o_ev = slice_align(n * sizeof(ThetaJob)), o_bad = o_ev + np * 8, total = o_bad + slice_align(np * 4);
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(ensure_raw(st));
-  MSC_HIP(reserve_synced(st->ctx->stream, st->slice_buf, total));
-  const hipStream_t s = st->ctx->stream;
-  unsigned char *b = st->slice_buf;
-  MSC_HIP(hipMemcpyAsync(b, jobs.data(), n * sizeof(ThetaJob), hipMemcpyHostToDevice, s));
-  if (launch_theta_slice(s, reinterpret_cast<const ThetaJob *>(b), n, st->K, st->kpad, st->cnt_u32, slots_dev,
-                         seed ^ kSliceKey, sweep, reinterpret_cast<unsigned long long *>(b + o_ev),
-                         reinterpret_cast<uint32_t *>(b + o_bad)))
-    return fail(MSC_EHIP, "k_theta_slice launch failed");
-  std::vector<unsigned char> down(total - o_ev);
-  MSC_HIP(hipMemcpyAsync(down.data(), b + o_ev, down.size(), hipMemcpyDeviceToHost, s));
-  MSC_HIP(hipStreamSynchronize(s));                   // the call's one wait
-  const unsigned long long *ev = reinterpret_cast<const unsigned long long *>(down.data());
-  const uint32_t *bad = reinterpret_cast<const uint32_t *>(down.data() + np * 8);
-  int rc = MSC_OK;
-  for (uint32_t i = 0; i < n; i++) {
-    st->valid.hp_changed(features[i]);                // (p is read by the bbnc prepare and the fused bool tables)
-    uint64_t t = 0;
-    uint32_t first_bad = 0xffffffffu;
-    for (uint32_t x = 0; x < nb; x++) {
-      t += ev[(size_t)i * nb + x];
-      first_bad = std::min(first_bad, bad[(size_t)i * nb + x]);
-    }
-    if (evals_host) evals_host[i] = t;
-    if (first_bad != 0xffffffffu)
-      rc = fail(MSC_EINVAL, "feature %u, slot %u: the target at the current p is not finite; the slot is left unchanged",
-                features[i], first_bad);
-  }
-  return rc;
-}
-
-// ---------------------------------------------------------------------------
-// row predictive log-density (kernels_marginal.hip): a row's K totals -- what msc_score_value with the prior defines --
-// reduced to their log-sum-exp, arg-max and the arg-max's log responsibility
-// ---------------------------------------------------------------------------
-// Which kernels reduce a state's rows.  By the state and view_rows alone (THE SHARD RULE of route_sweep): the fused
-// kernels and the score kernels add a row's terms in different orders, so a call over a sub-range must take what the
-// whole call takes.
-//   nich1    a single nich feature (masked or not) up to 1024 groups: k_marginal_nich1, the own-group values computed inside
-//   tile     scalar features within the tables (no niw, no dm, no count beyond a table), K <= 256, a view of at least
-//            kTailMinRows rows (fewer rows do not fill the chip with 128-row workgroups: the score pass has shapes for
-//            them), on plans whose SCORE pass is the plain tile kernel too (tile_path == MSC_PATH_TILE): k_loo_own, then
-//            k_marginal_tile over the fused plan.  A plan with kernels of its own (role-split, nich-only, lookups-only)
-//            goes the generic way: its score pass plus k_row_lse beats the plain tile form (C3, 10^6 x 256: DESIGN.md 6g)
-//            until a fused form of those kernels exists.  MSC_MARGINAL_TILE=1 / 0 sends every such plan / none to the tile
-//            kernel (how the two were measured against each other).
-//   generic  everything else: run_score (leave-one-out + prior) into the scratch chunk, then k_row_lse over it
-enum class MarginalKind { nich1, tile, generic };
-static MarginalKind route_marginal(const msc_state *st) {
-  if (!sweep_plain(st)) return MarginalKind::generic;
-  if (st->nich1) return st->K <= 1024 ? MarginalKind::nich1 : MarginalKind::generic;
-  if (!st->has_dm && st->K <= 256 && view_rows(st) >= kTailMinRows) {
-    const int forced = read_switches().marginal_tile;
-    if (forced >= 0 ? forced != 0 : st->tile_path == MSC_PATH_TILE) return MarginalKind::tile;
-  }
-  return MarginalKind::generic;
-}
-
-extern "C" int msc_score_marginal(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
-                                  const int32_t *z_dev, uint32_t flags, float *logp_dev, int32_t *map_dev,
-                                  float *map_logresp_dev) {
-  MSC_REQUIRE(st && (logp_dev || nrows == 0), "null argument");
-  MSC_REQUIRE(flags == 0, "unknown flags 0x%x", flags);
-  MSC_TRY(refuse_mid_step(st, "msc_score_marginal"));
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(device_error_check(st->ctx));
-  MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  if (nrows == 0) return MSC_OK;
-  MSC_TRY(ensure_derived(st));
-  MSC_TRY(ensure_crp(st));
-  hipStream_t s = st->ctx->stream;
-  const int cus = st->ctx->num_cus;
-  MSC_HIP(grow_retained(st->retired, st->marg_norm, 2));
-  MSC_TRY(launch_marginal_norm(s, st->cnt_u32, st->K, st->alpha, st->marg_norm));
-  switch (route_marginal(st)) {                           // (the launchers report their own failures)
-    case MarginalKind::nich1:
-      return launch_marginal_nich1(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, z_dev, st->logpc, st->marg_norm, logp_dev,
-                                   map_dev, map_logresp_dev);
-    case MarginalKind::tile:
-      if (z_dev) MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
-      MSC_TRY(refresh_fused_tables(st));                  // (the kernel walks the fused plan)
-      return launch_marginal_tile(s, cus, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
-                                  z_dev, st->own, st->logpc, st->marg_norm, logp_dev, map_dev, map_logresp_dev);
-    case MarginalKind::generic: {
-      // (the chunk of SweepKind::generic: rows of K rounded up to 64 floats; the scratch is the state's and stays with it,
-      // grown to what the largest call asked for, at most 4 GiB of scores)
-      const uint64_t ld = std::min<uint64_t>(st->kpad, ((uint64_t)st->K + 63) & ~63ull);
-      const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((4096ull << 20) / (ld * sizeof(float)), nrows));
-      MSC_HIP(grow_retained(st->retired, st->scratch, chunk * ld));
-      for (uint64_t at = 0; at < nrows; at += chunk) {
-        const uint64_t n = std::min<uint64_t>(chunk, nrows - at);
-        MSC_TRY(run_score(st, row0 + at, n, z_dev ? z_dev + at : nullptr, true, false, st->scratch, ld));
-        MSC_TRY(launch_row_lse(s, cus, st->scratch, ld, st->K, n, z_dev ? z_dev + at : nullptr, st->marg_norm, logp_dev + at,
-                               map_dev ? map_dev + at : nullptr, map_logresp_dev ? map_logresp_dev + at : nullptr));
-      }
-      return MSC_OK;
-    }
-  }
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// posterior predictive sampling (group::sample_value, base.hpp:29, for a block of rows; kernels_pred.hip)
-// ---------------------------------------------------------------------------
-static constexpr uint64_t kPredGroupKey = 0xD1B54A32D192ED03ull;   // the group draw's key is seed ^ this
-
-extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
-                                     uint64_t nrows, uint64_t row_id0, const int32_t *z_dev, int32_t *z_out_dev,
-                                     uint32_t flags, uint64_t seed, uint64_t sweep, void *const *out_dev) {
-  MSC_REQUIRE(st && view && out_dev, "null argument");
-  MSC_REQUIRE((flags & ~MSC_PRED_MASKED_ONLY) == 0, "unknown flags 0x%x", flags);
-  MSC_TRY(refuse_mid_step(st, "msc_sample_predictive"));
-  for (uint32_t f = 0; f < st->nfeat; f++) {
-    if (out_dev[f] == nullptr) continue;
-    const int fam = st->feats[f].family;
-    if (fam == MSC_DM)
-      return fail(MSC_EUNSUPPORTED, "feature %u: dm has no sample_value upstream (dm.cpp:100-111)", f);
-    if (fam == MSC_NOOP) return fail(MSC_EUNSUPPORTED, "feature %u: the noop model has no values to draw", f);
-    MSC_REQUIRE(f < 0x8000u, "feature %u: the draw's Philox counter holds feature indices below 32768", f);
-  }
-  MSC_HIP(hipSetDevice(st->ctx->device));
-  MSC_TRY(device_error_check(st->ctx));
-  MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  if (nrows == 0) return MSC_OK;
-  MSC_TRY(ensure_derived(st));                              // (raw tables current; niw: the whitening matrices)
-  const hipStream_t s = st->ctx->stream;
-  // the features drawn and their parameter blocks
-  std::vector<PredFeat> pfs;
-  std::vector<size_t> par_off;                              // each drawn feature's first double in pred_par
-  size_t par_len = 0;
-  for (uint32_t f = 0; f < st->nfeat; f++) {
-    if (out_dev[f] == nullptr) continue;
-    const msc_feature_host &h = st->feats[f];
-    const FeatDesc &d = st->desc_host[f];
-    PredFeat p;
-    p.family = h.family;
-    p.dim = h.dim;
-    p.feature = f;
-    p.stride = pred_par_stride(h.family, h.dim);
-    p.par = nullptr;                                        // (set below, once the buffer is known)
-    p.hp = h.hp_dev;
-    p.raw_u32 = h.raw_u32;
-    p.raw_f32 = h.raw_f32;
-    p.niw_w64 = h.niw_w64;
-    p.col = d.col;
-    p.mask = d.mask;
-    p.out = out_dev[f];
-    pfs.push_back(p);
-    par_off.push_back(par_len);
-    par_len += (size_t)p.stride * st->K;
-  }
-  MSC_HIP(reserve_synced(st->ctx->stream, st->pred_par, par_len));
-  if (pfs.size() > st->pred_feats_dev.size() || !st->pred_feats_dev) st->pred_feats_host.clear();   // (a new buffer holds nothing)
-  MSC_HIP(reserve_synced(st->ctx->stream, st->pred_feats_dev, pfs.size()));
-  for (size_t i = 0; i < pfs.size(); i++) pfs[i].par = st->pred_par + par_off[i];
-  // the descriptors go up only when they changed (a loop of calls uploads nothing), from pinned staging memory: the copy
-  // reads it when it runs, so the host waits -- for the previous upload only -- before it writes the staging again
-  const size_t pbytes = pfs.size() * sizeof(PredFeat);
-  if (pbytes && (st->pred_feats_host.size() != pfs.size() ||
-                 std::memcmp(st->pred_feats_host.data(), pfs.data(), pbytes) != 0)) {
-    if (st->pred_stage.size() < pfs.size()) {
-      if (st->pred_upload_pending) MSC_HIP(hipEventSynchronize(st->pred_upload));
-      st->pred_upload_pending = false;
-      MSC_HIP(st->pred_stage.alloc(pfs.size()));   // (frees the smaller one first)
-    }
-    if (!st->pred_upload) MSC_HIP(hipEventCreateWithFlags(&st->pred_upload, hipEventDisableTiming));
-    if (st->pred_upload_pending) MSC_HIP(hipEventSynchronize(st->pred_upload));
-    std::memcpy(st->pred_stage, pfs.data(), pbytes);
-    MSC_HIP(hipMemcpyAsync(st->pred_feats_dev, st->pred_stage, pbytes, hipMemcpyHostToDevice, s));
-    MSC_HIP(hipEventRecord(st->pred_upload, s));
-    st->pred_upload_pending = true;
-    st->pred_feats_host = pfs;
-  }
-  if (launch_pred_prepare(s, st->pred_feats_dev, pfs, st->K, st->kpad)) return fail(MSC_EHIP, "k_pred_prepare launch failed");
-  // the group draw: the sweep's own assignment pass for rows that are all unassigned, under a key no sweep uses; the
-  // sweep's (seed, sweep) pair on the device is put back afterwards
-  const int32_t *z = z_dev;
-  if (z == nullptr) {
-    MSC_HIP(reserve_synced(st->ctx->stream, st->pred_z, nrows));
-    MSC_HIP(hipMemsetAsync(st->pred_z, 0xff, nrows * sizeof(int32_t), s));
-    const bool had = st->rng_valid;
-    const uint64_t had_seed = st->rng_seed, had_sweep = st->rng_sweep;
-    MSC_TRY(sweep_assign_impl(st, view, cols, row0, nrows, row_id0, st->pred_z, seed ^ kPredGroupKey, sweep));
-    st->rng_valid = false;
-    if (had) {
-      if (launch_rng_set(s, st->rng_dev, had_seed, had_sweep)) return fail(MSC_EHIP, "k_rng_set launch failed");
-      st->rng_valid = true;
-      st->rng_seed = had_seed;
-      st->rng_sweep = had_sweep;
-    }
-    z = st->pred_z;
-  }
-  if (launch_pred_sample(s, st->pred_feats_dev, pfs, st->K, row0, nrows, row_id0, z, z_out_dev,
-                         (flags & MSC_PRED_MASKED_ONLY) != 0, seed, sweep))
-    return fail(MSC_EHIP, "k_pred_sample launch failed");
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// z-matrix accumulator (microscopes.common.query.zmatrix; kernels_query.hip)
-// ---------------------------------------------------------------------------
-static size_t zm_count_words(uint32_t nt) { return (size_t)nt * (nt + 1) / 2 * kZmTile * kZmTile; }
-
-// the buffer's allocation, MSC_ENOMEM (with the footprint) when the device has no room
-static int zm_alloc(DevBuf<uint32_t> &buf, size_t bytes, const char *what, uint32_t m) {
-  const hipError_t e = buf.alloc(bytes / 4);
-  if (e == hipSuccess) return MSC_OK;
-  (void)hipGetLastError();
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
-    return fail(MSC_ENOMEM, "msc_zmatrix_create: m = %u needs %zu bytes for the %s (include/microscopes_hip.h gives the "
-                "footprint); the device has no room", m, bytes, what);
-  return fail(MSC_EHIP, "allocating the %s failed: %s", what, hipGetErrorString(e));
-}
-
-extern "C" int msc_zmatrix_create(msc_context *ctx, uint64_t n, const uint32_t *host_rows, uint32_t m, uint32_t nlabels,
-                                  msc_zmatrix **out) {
-  MSC_REQUIRE(ctx && out, "null argument");
-  *out = nullptr;
-  MSC_REQUIRE(n > 0, "msc_zmatrix_create: n is 0");
-  MSC_REQUIRE(host_rows || (uint64_t)m == n, "msc_zmatrix_create: without rows m (%u) must equal n (%llu)", m,
-              (unsigned long long)n);
-  MSC_REQUIRE(m >= 1 && m <= kZmMaxRows, "msc_zmatrix_create: m = %u outside [1, %u]", m, kZmMaxRows);
-  MSC_REQUIRE(nlabels >= 1 && nlabels <= kZmMaxLabels, "msc_zmatrix_create: nlabels = %u outside [1, %u]", nlabels,
-              kZmMaxLabels);
-  std::vector<uint32_t> rows(m);
-  for (uint32_t a = 0; a < m; a++) {
-    rows[a] = host_rows ? host_rows[a] : a;
-    MSC_REQUIRE(rows[a] < n, "msc_zmatrix_create: rows[%u] = %u is not below n = %llu", a, rows[a], (unsigned long long)n);
-  }
-  MSC_HIP(hipSetDevice(ctx->device));
-  std::unique_ptr<msc_zmatrix> zm(new (std::nothrow) msc_zmatrix());
-  if (!zm) return fail(MSC_ENOMEM, "out of host memory");
-  zm->ctx = ctx;
-  zm->n = n;
-  zm->m = m;
-  zm->nlabels = nlabels;
-  zm->nt = (m + kZmTile - 1) / kZmTile;
-  zm->wide = nlabels > 256;
-  const size_t batch_bytes = (size_t)zm->nt * kZmTile * kZmBatchWords * 4;
-  const size_t count_bytes = zm_count_words(zm->nt) * 4;
-  MSC_TRY(zm_alloc(zm->counts, count_bytes, "counts", m));
-  MSC_TRY(zm_alloc(zm->batch, batch_bytes, "sample batch", m));
-  MSC_TRY(zm_alloc(zm->bad, (kZmBatchMax + 1) * 4, "batch flags", m));
-  MSC_TRY(zm_alloc(zm->rows_dev, (size_t)m * 4, "rows", m));
-  MSC_TRY(zm_alloc(zm->order_dev, (size_t)m * 4, "order", m));
-  const hipStream_t s = ctx->stream;
-  MSC_HIP(hipMemsetAsync(zm->counts, 0, count_bytes, s));
-  MSC_HIP(hipMemsetAsync(zm->batch, 0, batch_bytes, s));
-  MSC_HIP(hipMemsetAsync(zm->bad, 0, (kZmBatchMax + 1) * 4, s));
-  MSC_HIP(hipMemcpyAsync(zm->rows_dev, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
-  MSC_HIP(hipStreamSynchronize(s));
-  *out = zm.release();
-  return MSC_OK;
-}
-
-// the staged samples into the counts, then an empty batch
-static int zmatrix_flush(msc_zmatrix *zm) {
-  if (zm->staged == 0) return MSC_OK;
-  const hipStream_t s = zm->ctx->stream;
-  if (launch_zm_count(s, zm->batch, zm->nt, zm->wide, zm->staged, zm->bad, zm->counts))
-    return fail(MSC_EHIP, "k_zm_count launch failed");
-  MSC_HIP(hipMemsetAsync(zm->batch, 0, (size_t)zm->nt * kZmTile * kZmBatchWords * 4, s));
-  MSC_HIP(hipMemsetAsync(zm->bad, 0, (kZmBatchMax + 1) * 4, s));
-  zm->staged = 0;
-  return MSC_OK;
-}
-
-extern "C" int msc_zmatrix_add(msc_zmatrix *zm, const int32_t *z_dev, uint32_t nsamples, uint64_t ld) {
-  MSC_REQUIRE(zm && z_dev, "null argument");
-  MSC_REQUIRE(ld >= zm->n, "msc_zmatrix_add: ld = %llu is below n = %llu", (unsigned long long)ld,
-              (unsigned long long)zm->n);
-  MSC_TRY(device_error_check(zm->ctx));
-  if (nsamples == 0) return MSC_OK;
-  MSC_HIP(hipSetDevice(zm->ctx->device));
-  const uint32_t cap = zm_batch_cap(zm->wide);
-  for (uint32_t done = 0; done < nsamples;) {
-    const uint32_t k = std::min(nsamples - done, cap - zm->staged);
-    if (launch_zm_stage(zm->ctx->stream, z_dev + (uint64_t)done * ld, ld, k, zm->rows_dev, zm->m, zm->nlabels, zm->wide,
-                        zm->staged, zm->bad, zm->batch))
-      return fail(MSC_EHIP, "k_zm_check / k_zm_pack launch failed");
-    zm->staged += k;
-    zm->nsamples += k;
-    done += k;
-    if (zm->staged == cap) MSC_TRY(zmatrix_flush(zm));
-  }
-  return MSC_OK;
-}
-
-extern "C" int msc_zmatrix_nsamples(const msc_zmatrix *zm, uint64_t *out) {
-  MSC_REQUIRE(zm && out, "null argument");
-  *out = zm->nsamples;
-  return MSC_OK;
-}
-
-static int zmatrix_write(msc_zmatrix *zm, const uint32_t *host_order, void *out_dev, uint64_t ld_out, bool norm) {
-  MSC_REQUIRE(zm && out_dev, "null argument");
-  MSC_REQUIRE(ld_out >= zm->m, "ld_out = %llu is below m = %u", (unsigned long long)ld_out, zm->m);
-  MSC_REQUIRE(!norm || zm->nsamples > 0, "msc_zmatrix_result: no sample has been added (empty assignments list)");
-  if (host_order) {
-    std::vector<uint8_t> seen(zm->m, 0);
-    for (uint32_t a = 0; a < zm->m; a++) {
-      MSC_REQUIRE(host_order[a] < zm->m && !seen[host_order[a]], "order is not a permutation of [0, %u): entry %u is %u",
-                  zm->m, a, host_order[a]);
-      seen[host_order[a]] = 1;
-    }
-  }
-  MSC_TRY(device_error_check(zm->ctx));
-  MSC_HIP(hipSetDevice(zm->ctx->device));
-  MSC_TRY(zmatrix_flush(zm));
-  const hipStream_t s = zm->ctx->stream;
-  if (host_order) MSC_HIP(hipMemcpyAsync(zm->order_dev, host_order, (size_t)zm->m * 4, hipMemcpyHostToDevice, s));
-  if (launch_zm_finish(s, zm->counts, zm->nt, zm->m, host_order ? zm->order_dev : nullptr, norm, (float)zm->nsamples,
-                       out_dev, ld_out))
-    return fail(MSC_EHIP, "k_zm_finish launch failed");
-  return MSC_OK;
-}
-
-extern "C" int msc_zmatrix_counts(msc_zmatrix *zm, const uint32_t *host_order, uint32_t *out_dev, uint64_t ld_out) {
-  return zmatrix_write(zm, host_order, out_dev, ld_out, false);
-}
-
-extern "C" int msc_zmatrix_result(msc_zmatrix *zm, const uint32_t *host_order, float *out_dev, uint64_t ld_out) {
-  return zmatrix_write(zm, host_order, out_dev, ld_out, true);
-}
-
-// candidate partitions against the counts (kernels_partition.hip): the checks both entries share, the flush, and the
-// label buffer of one chunk of candidates
-static int zm_partition_begin(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld, const char *who) {
-  MSC_REQUIRE(zm && cand_dev, "null argument");
-  MSC_REQUIRE(zm->nsamples > 0, "%s: no sample has been added", who);
-  MSC_REQUIRE(ncand > 0, "%s: ncand is 0", who);
-  MSC_REQUIRE(ld >= zm->n, "%s: ld = %llu is below n = %llu", who, (unsigned long long)ld, (unsigned long long)zm->n);
-  MSC_TRY(device_error_check(zm->ctx));
-  MSC_HIP(hipSetDevice(zm->ctx->device));
-  MSC_TRY(zmatrix_flush(zm));
-  return MSC_OK;
-}
-
-template <typename T>
-static int zm_partition_reserve(msc_zmatrix *zm, DevBuf<T> &buf, size_t n, const char *who, const char *what) {
-  const hipError_t e = reserve_synced(zm->ctx->stream, buf, n);
-  if (e == hipSuccess) return MSC_OK;
-  (void)hipGetLastError();
-  return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "%s: the %s of %zu bytes: %s", who, what, n * sizeof(T),
-              hipGetErrorString(e));
-}
-
-// w / size (either may be null) of candidates [0, k) at cand_dev into [k][m] arrays
-static int zm_partition_chunk_sums(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t k, uint64_t ld, uint64_t *w_dev,
-                                   uint32_t *size_dev) {
-  const hipStream_t s = zm->ctx->stream;
-  if (launch_zm_partition_gather(s, cand_dev, ld, k, zm->rows_dev, zm->m, zm->nt, zm->part_lab))
-    return fail(MSC_EHIP, "k_zm_partition_gather launch failed");
-  if (launch_zm_partition_sums(s, zm->counts, zm->nt, zm->m, zm->nsamples < kZmPartPackedMax, zm->part_lab, k, w_dev,
-                               size_dev))
-    return fail(MSC_EHIP, "k_zm_partition_sums launch failed");
-  return MSC_OK;
-}
-
-extern "C" int msc_zmatrix_partition_sums(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
-                                          uint64_t *w_dev, uint32_t *size_dev) {
-  const char *who = "msc_zmatrix_partition_sums";
-  MSC_TRY(zm_partition_begin(zm, cand_dev, ncand, ld, who));
-  if (!w_dev && !size_dev) return MSC_OK;
-  const uint32_t chunk = zm_partition_chunk(zm->nt);
-  MSC_TRY(zm_partition_reserve(zm, zm->part_lab, (size_t)chunk * zm->nt * kZmTile, who, "label buffer"));
-  for (uint32_t c0 = 0; c0 < ncand; c0 += chunk) {
-    const size_t o = (size_t)c0 * zm->m;
-    MSC_TRY(zm_partition_chunk_sums(zm, cand_dev + (uint64_t)c0 * ld, std::min(chunk, ncand - c0), ld,
-                                    w_dev ? w_dev + o : nullptr, size_dev ? size_dev + o : nullptr));
-  }
-  return MSC_OK;
-}
-
-// binder_num <= V m (m - 1) / 2 must fit an int64
-static int zm_partition_fits(const msc_zmatrix *zm, const char *who) {
-  const unsigned __int128 pairs = (unsigned __int128)zm->m * (zm->m - 1) / 2;
-  if (zm->nsamples > 0 && pairs * zm->nsamples >= ((unsigned __int128)1 << 63))
-    return fail(MSC_EUNSUPPORTED, "%s: m (m - 1) / 2 x nsamples = %u (%u - 1) / 2 x %llu does not fit 63 bits", who, zm->m,
-                zm->m, (unsigned long long)zm->nsamples);
-  return MSC_OK;
-}
-
-// the loss workspaces of one chunk, and T (and V into valid_dev, nullable): the loss of all rows in one cluster
-static int zm_partition_total(msc_zmatrix *zm, uint32_t chunk, uint64_t *valid_dev, const char *who) {
-  const size_t mpad = (size_t)zm->nt * kZmTile;
-  MSC_TRY(zm_partition_reserve(zm, zm->part_lab, chunk * mpad, who, "label buffer"));
-  MSC_TRY(zm_partition_reserve(zm, zm->part_w, (size_t)chunk * zm->m, who, "workspace of row sums"));
-  MSC_TRY(zm_partition_reserve(zm, zm->part_size, (size_t)chunk * zm->m, who, "workspace of cluster sizes"));
-  MSC_TRY(zm_partition_reserve(zm, zm->part_T, 1, who, "pair total"));
-  const hipStream_t s = zm->ctx->stream;
-  MSC_HIP(hipMemsetAsync(zm->part_lab, 0, mpad * 4, s));
-  if (launch_zm_partition_sums(s, zm->counts, zm->nt, zm->m, zm->nsamples < kZmPartPackedMax, zm->part_lab, 1,
-                               zm->part_w, zm->part_size))
-    return fail(MSC_EHIP, "k_zm_partition_sums launch failed");
-  if (launch_zm_partition_loss(s, zm->counts, zm->part_w, zm->part_size, zm->m, 1, true, zm->part_T, nullptr, nullptr,
-                               valid_dev))
-    return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
-  return MSC_OK;
-}
-
-extern "C" int msc_zmatrix_partition_loss(msc_zmatrix *zm, const int32_t *cand_dev, uint32_t ncand, uint64_t ld,
-                                          int64_t *binder_num_dev, double *vi_lb_dev, uint64_t *valid_dev) {
-  const char *who = "msc_zmatrix_partition_loss";
-  MSC_REQUIRE(zm && cand_dev, "null argument");
-  MSC_TRY(zm_partition_fits(zm, who));
-  MSC_TRY(zm_partition_begin(zm, cand_dev, ncand, ld, who));
-  if (!binder_num_dev && !vi_lb_dev && !valid_dev) return MSC_OK;
-  const uint32_t chunk = zm_partition_chunk(zm->nt);
-  MSC_TRY(zm_partition_total(zm, chunk, valid_dev, who));
-  const hipStream_t s = zm->ctx->stream;
-  if (!binder_num_dev && !vi_lb_dev) return MSC_OK;
-  for (uint32_t c0 = 0; c0 < ncand; c0 += chunk) {
-    const uint32_t k = std::min(chunk, ncand - c0);
-    MSC_TRY(zm_partition_chunk_sums(zm, cand_dev + (uint64_t)c0 * ld, k, ld, zm->part_w, zm->part_size));
-    if (launch_zm_partition_loss(s, zm->counts, zm->part_w, zm->part_size, zm->m, k, false, zm->part_T,
-                                 binder_num_dev ? binder_num_dev + c0 : nullptr, vi_lb_dev ? vi_lb_dev + c0 : nullptr,
-                                 nullptr))
-      return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
-  }
-  return MSC_OK;
-}
-
-// greedy row moves from given starts (kernels_refine.hip)
-extern "C" int msc_zmatrix_partition_refine(msc_zmatrix *zm, const int32_t *start_dev, uint32_t nstarts, uint64_t ld,
-                                            uint32_t max_sweeps, uint32_t max_clusters, const uint32_t *host_order,
-                                            int32_t *labels_dev, int64_t *binder_num_dev, uint32_t *sweeps_dev,
-                                            uint64_t *moves_dev) {
-  const char *who = "msc_zmatrix_partition_refine";
-  MSC_REQUIRE(zm && start_dev, "null argument");
-  const uint32_t m = zm->m;
-  MSC_REQUIRE(max_clusters >= 1 && max_clusters <= m, "%s: max_clusters = %u outside [1, m = %u]", who, max_clusters, m);
-  if (host_order) {
-    std::vector<uint8_t> seen(m, 0);
-    for (uint32_t a = 0; a < m; a++) {
-      MSC_REQUIRE(host_order[a] < m && !seen[host_order[a]], "%s: order is not a permutation of [0, %u): entry %u is %u",
-                  who, m, a, host_order[a]);
-      seen[host_order[a]] = 1;
-    }
-  }
-  MSC_REQUIRE(zm->nsamples > 0, "%s: no sample has been added", who);
-  MSC_REQUIRE(nstarts > 0, "%s: nstarts is 0", who);
-  MSC_REQUIRE(ld >= zm->n, "%s: ld = %llu is below n = %llu", who, (unsigned long long)ld, (unsigned long long)zm->n);
-  if (m > kZmRefineMaxRows || max_clusters > kZmRefineMaxClusters)
-    return fail(MSC_EUNSUPPORTED, "%s: m = %u, max_clusters = %u: at most %u positions and %u clusters", who, m,
-                max_clusters, kZmRefineMaxRows, kZmRefineMaxClusters);
-  MSC_TRY(zm_partition_fits(zm, who));
-  MSC_TRY(zm_partition_begin(zm, start_dev, nstarts, ld, who));
-  if (!labels_dev && !binder_num_dev && !sweeps_dev && !moves_dev) return MSC_OK;
-  const uint32_t chunk = zm_partition_chunk(zm->nt);
-  const uint64_t ldd = ((uint64_t)m + 3u) & ~(uint64_t)3u;
-  const uint32_t mpad = zm->nt * kZmTile;
-  MSC_TRY(zm_partition_total(zm, chunk, nullptr, who));
-  MSC_TRY(zm_partition_reserve(zm, zm->ref_dense, (size_t)m * ldd, who, "dense copy of the counts"));
-  MSC_TRY(zm_partition_reserve(zm, zm->ref_ids, (size_t)chunk * ldd, who, "cluster ids"));
-  MSC_TRY(zm_partition_reserve(zm, zm->ref_st, chunk, who, "running totals"));
-  MSC_TRY(zm_partition_reserve(zm, zm->ref_binder, chunk, who, "losses of the starts"));
-  const hipStream_t s = zm->ctx->stream;
-  if (host_order) MSC_HIP(hipMemcpyAsync(zm->order_dev, host_order, (size_t)m * 4, hipMemcpyHostToDevice, s));
-  if (launch_zm_finish(s, zm->counts, zm->nt, m, nullptr, false, (float)zm->nsamples, zm->ref_dense, ldd))
-    return fail(MSC_EHIP, "k_zm_finish launch failed");
-  const bool narrow = zm->nsamples * (uint64_t)m < (1ull << 32);      // s_k <= V (m - 1), V <= nsamples
-  std::vector<RefineStart> st_host;
-  for (uint32_t c0 = 0; c0 < nstarts; c0 += chunk) {
-    const uint32_t k = std::min(chunk, nstarts - c0);
-    MSC_TRY(zm_partition_chunk_sums(zm, start_dev + (uint64_t)c0 * ld, k, ld, zm->part_w, zm->part_size));
-    if (launch_zm_partition_loss(s, zm->counts, zm->part_w, zm->part_size, m, k, false, zm->part_T, zm->ref_binder, nullptr,
-                                 nullptr))
-      return fail(MSC_EHIP, "k_zm_partition_loss launch failed");
-    if (launch_zm_refine_init(s, zm->part_lab, mpad, m, max_clusters, k, zm->ref_ids, ldd, zm->ref_st))
-      return fail(MSC_EHIP, "k_zm_refine_init launch failed");
-    for (uint32_t sweep = 0; sweep < max_sweeps; sweep++) {
-      // every sweep is a launch and the stream is not waited for -- up to kRefineBlindSweeps of them; a caller who
-      // allows more pays one wait per kRefineBlindSweeps further ones, so that the launches end when the starts have
-      constexpr uint32_t kRefineBlindSweeps = 64;
-      if (sweep >= kRefineBlindSweeps && sweep % kRefineBlindSweeps == 0) {
-        st_host.resize(k);
-        MSC_HIP(hipMemcpyAsync(st_host.data(), zm->ref_st, (size_t)k * sizeof(RefineStart), hipMemcpyDeviceToHost, s));
-        MSC_HIP(hipStreamSynchronize(s));
-        bool any = false;
-        for (uint32_t i = 0; i < k; i++) any = any || st_host[i].active != 0u;
-        if (!any) break;
-      }
-      if (launch_zm_refine_sweep(s, zm->ref_dense, ldd, m, max_clusters, host_order ? zm->order_dev : nullptr, narrow, k,
-                                 zm->ref_ids, zm->ref_st))
-        return fail(MSC_EHIP, "k_zm_refine_sweep launch failed");
-    }
-    if (launch_zm_refine_finish(s, zm->ref_ids, ldd, m, max_clusters, k, zm->ref_st, zm->ref_binder,
-                                labels_dev ? labels_dev + (uint64_t)c0 * m : nullptr,
-                                binder_num_dev ? binder_num_dev + c0 : nullptr, sweeps_dev ? sweeps_dev + c0 : nullptr,
-                                moves_dev ? moves_dev + c0 : nullptr))
-      return fail(MSC_EHIP, "k_zm_refine_finish launch failed");
-  }
-  return MSC_OK;
-}
-
-extern "C" int msc_zmatrix_reset(msc_zmatrix *zm) {
-  MSC_REQUIRE(zm, "null argument");
-  MSC_HIP(hipSetDevice(zm->ctx->device));
-  const hipStream_t s = zm->ctx->stream;
-  MSC_HIP(hipMemsetAsync(zm->counts, 0, zm_count_words(zm->nt) * 4, s));
-  MSC_HIP(hipMemsetAsync(zm->batch, 0, (size_t)zm->nt * kZmTile * kZmBatchWords * 4, s));
-  MSC_HIP(hipMemsetAsync(zm->bad, 0, (kZmBatchMax + 1) * 4, s));
-  zm->staged = 0;
-  zm->nsamples = 0;
-  return MSC_OK;
-}
-
-extern "C" int msc_zmatrix_destroy(msc_zmatrix *zm) {
-  if (!zm) return MSC_OK;
-  (void)hipSetDevice(zm->ctx->device);
-  (void)hipStreamSynchronize(zm->ctx->stream);
-  delete zm;
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// single linkage of a dense z-matrix (scipy.cluster.hierarchy.linkage of 1 - Z; kernels_linkage.hip, linkage_host.hpp)
-// ---------------------------------------------------------------------------
-extern "C" int msc_linkage_single(msc_context *ctx, const float *z_dev, uint64_t ld, uint32_t n, uint32_t flags,
-                                  double *host_linkage, uint32_t *host_order) {
-  MSC_REQUIRE(ctx && z_dev, "null argument");
-  MSC_REQUIRE(flags == 0, "msc_linkage_single: flags = %u (none is defined)", flags);
-  MSC_REQUIRE(n >= 2, "msc_linkage_single: n = %u (a linkage needs two points)", n);
-  MSC_REQUIRE(ld >= n, "msc_linkage_single: ld = %llu is below n = %u", (unsigned long long)ld, n);
-  if (n > linkage::kMaxN)
-    return fail(MSC_EUNSUPPORTED, "msc_linkage_single: n = %u is above %u (one workgroup holds the chain's distances in "
-                "registers)", n, linkage::kMaxN);
-  MSC_TRY(device_error_check(ctx));
-  MSC_HIP(hipSetDevice(ctx->device));
-  const hipStream_t s = ctx->stream;
-  const size_t nvals = 3 * (size_t)(n - 1);
-  {
-    const hipError_t e = reserve_synced(s, ctx->linkage_edges, nvals);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "msc_linkage_single: the edge list of %zu bytes: %s",
-                  nvals * sizeof(double), hipGetErrorString(e));
-    }
-  }
-  if (launch_linkage_prim(s, z_dev, ld, n, ctx->linkage_edges)) return fail(MSC_EHIP, "k_linkage_prim launch failed");
-  std::vector<double> edges(nvals);
-  MSC_HIP(hipMemcpyAsync(edges.data(), ctx->linkage_edges, nvals * sizeof(double), hipMemcpyDeviceToHost, s));
-  MSC_HIP(hipStreamSynchronize(s));
-  MSC_TRY(device_error_check(ctx));
-  if (host_linkage || host_order) linkage::finish(edges.data(), n, host_linkage, host_order);
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// distances between partitions (kernels_distance.hip)
-// ---------------------------------------------------------------------------
-template <typename T>
-static int pd_reserve(msc_context *ctx, DevBuf<T> &buf, size_t n, const char *what) {
-  const hipError_t e = reserve_synced(ctx->stream, buf, n);
-  if (e == hipSuccess) return MSC_OK;
-  (void)hipGetLastError();
-  return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "msc_partition_distances: the %s of %zu bytes: %s", what,
-              n * sizeof(T), hipGetErrorString(e));
-}
-
-// which launches a block of partitions with cluster counts ka[0..na) x kb[0..nb) needs (route_pd_table decides per pair)
-static void pd_block_routes(const uint32_t *ka, uint32_t na, const uint32_t *kb, uint32_t nb, bool *lds, bool *global) {
-  uint32_t lo_a = kPdBad, hi_a = 0, lo_b = kPdBad, hi_b = 0;
-  bool bad = false;
-  for (uint32_t i = 0; i < na; i++)
-    if (ka[i] == kPdBad) bad = true; else lo_a = std::min(lo_a, ka[i]), hi_a = std::max(hi_a, ka[i]);
-  for (uint32_t j = 0; j < nb; j++)
-    if (kb[j] == kPdBad) bad = true; else lo_b = std::min(lo_b, kb[j]), hi_b = std::max(hi_b, kb[j]);
-  const bool any = hi_a != 0 && hi_b != 0;                  // a pair of two good partitions
-  *lds = bad || (any && route_pd_table(lo_a, lo_b) == PdRoute::lds);
-  *global = any && route_pd_table(hi_a, hi_b) == PdRoute::global;
-}
-
-extern "C" int msc_partition_distances(msc_context *ctx, const int32_t *a_dev, uint64_t lda, uint32_t na,
-                                       const int32_t *b_dev, uint64_t ldb, uint32_t nb, uint32_t m, uint32_t flags,
-                                       int64_t *pairs_ab_dev, double *nlogn_ab_dev, int64_t *pairs_a_dev,
-                                       double *nlogn_a_dev, uint32_t *nclusters_a_dev, int64_t *pairs_b_dev,
-                                       double *nlogn_b_dev, uint32_t *nclusters_b_dev) {
-  const char *who = "msc_partition_distances";
-  MSC_REQUIRE(ctx && a_dev, "%s: null argument", who);
-  MSC_REQUIRE(flags == 0, "%s: flags = %u (none is defined)", who, flags);
-  const bool mirror = b_dev == nullptr;
-  if (mirror) b_dev = a_dev, ldb = lda, nb = na;
-  MSC_REQUIRE(na > 0 && nb > 0 && m > 0, "%s: na = %u, nb = %u, m = %u: none may be 0", who, na, nb, m);
-  MSC_REQUIRE(lda >= m && ldb >= m, "%s: lda = %llu, ldb = %llu below m = %u", who, (unsigned long long)lda,
-              (unsigned long long)ldb, m);
-  if (m > kPdMaxRows)
-    return fail(MSC_EUNSUPPORTED, "%s: m = %u: at most %u rows (16-bit ids; up to %u clusters a partition)", who, m,
-                kPdMaxRows, kPdMaxClusters);
-  MSC_TRY(device_error_check(ctx));
-  MSC_HIP(hipSetDevice(ctx->device));
-  const hipStream_t s = ctx->stream;
-  const uint64_t ldi = ((uint64_t)m + 3u) & ~(uint64_t)3u;
-  MSC_TRY(pd_reserve(ctx, ctx->pd_ids, 2 * (size_t)kPdChunk * ldi, "cluster ids"));
-  MSC_TRY(pd_reserve(ctx, ctx->pd_k, 2 * (size_t)kPdChunk, "cluster counts"));
-  if (ctx->pd_log2_n < m || !ctx->pd_log2) {
-    ctx->pd_log2_n = 0;
-    MSC_TRY(pd_reserve(ctx, ctx->pd_log2, (size_t)m + 1, "table of log2 n"));
-    if (launch_pd_log2(s, ctx->pd_log2, m)) return fail(MSC_EHIP, "k_pd_log2 launch failed");
-    ctx->pd_log2_n = m;
-  }
-  uint16_t *ids_a = ctx->pd_ids, *ids_b = ids_a + (size_t)kPdChunk * ldi;
-  uint32_t *k_a = ctx->pd_k, *k_b = k_a + kPdChunk;
-  // the cluster counts come back to the host, a chunk at a time (one wait each): they say which launches a block needs
-  std::vector<uint32_t> ka_host(kPdChunk), kb_host(nb);
-  for (uint32_t a0 = 0; a0 < na; a0 += kPdChunk) {
-    const uint32_t nac = std::min(kPdChunk, na - a0);
-    if (launch_pd_canon(s, a_dev + (uint64_t)a0 * lda, lda, m, nac, ctx->pd_log2, a0, ids_a, ldi, k_a,
-                        pairs_a_dev ? pairs_a_dev + a0 : nullptr, nlogn_a_dev ? nlogn_a_dev + a0 : nullptr,
-                        nclusters_a_dev ? nclusters_a_dev + a0 : nullptr))
-      return fail(MSC_EHIP, "k_pd_canon launch failed");
-    MSC_HIP(hipMemcpyAsync(ka_host.data(), k_a, (size_t)nac * 4, hipMemcpyDeviceToHost, s));
-    MSC_HIP(hipStreamSynchronize(s));
-    for (uint32_t b0 = 0; b0 < nb; b0 += kPdChunk) {
-      const uint32_t nbc = std::min(kPdChunk, nb - b0);
-      const bool first = a0 == 0;                            // of this chunk of b: its own outputs are written now
-      if (mirror && !first && b0 + nbc <= a0) continue;      // (every pair of the block is another block's mirror image)
-      if (launch_pd_canon(s, b_dev + (uint64_t)b0 * ldb, ldb, m, nbc, ctx->pd_log2, b0, ids_b, ldi, k_b,
-                          first && pairs_b_dev ? pairs_b_dev + b0 : nullptr,
-                          first && nlogn_b_dev ? nlogn_b_dev + b0 : nullptr,
-                          first && nclusters_b_dev ? nclusters_b_dev + b0 : nullptr))
-        return fail(MSC_EHIP, "k_pd_canon launch failed");
-      if (first) {
-        MSC_HIP(hipMemcpyAsync(kb_host.data() + b0, k_b, (size_t)nbc * 4, hipMemcpyDeviceToHost, s));
-        MSC_HIP(hipStreamSynchronize(s));
-      }
-      if (!pairs_ab_dev && !nlogn_ab_dev) continue;
-      if (mirror && b0 + nbc <= a0) continue;
-      bool lds = false, global = false;
-      pd_block_routes(ka_host.data(), nac, kb_host.data() + b0, nbc, &lds, &global);
-      PdPairArgs p;
-      p.ids_a = ids_a, p.ids_b = ids_b, p.ldi = ldi, p.k_a = k_a, p.k_b = k_b;
-      p.m = m, p.na = nac, p.nb = nbc, p.a0 = a0, p.b0 = b0, p.ldo = nb, p.mirror = mirror ? 1u : 0u;
-      p.log2tab = ctx->pd_log2, p.table = nullptr, p.pairs_ab = pairs_ab_dev, p.nlogn_ab = nlogn_ab_dev;
-      if (global) {
-        if (!ctx->pd_table) {
-          const size_t cells = (size_t)kPdSlices * kPdSliceCells;
-          MSC_TRY(pd_reserve(ctx, ctx->pd_table, cells, "contingency tables"));
-          MSC_HIP(hipMemsetAsync(ctx->pd_table, 0, cells * 4, s));
-        }
-        p.table = ctx->pd_table;
-        if (launch_pd_pairs(s, ctx->num_cus, PdRoute::global, p)) return fail(MSC_EHIP, "k_pd_pairs launch failed");
-      }
-      if (lds && launch_pd_pairs(s, ctx->num_cus, PdRoute::lds, p)) return fail(MSC_EHIP, "k_pd_pairs launch failed");
-    }
-  }
-  return MSC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// greedy refinement under the exact expected variation of information (kernels_refine_vi.hip)
-// ---------------------------------------------------------------------------
-extern "C" int msc_vi_table(uint32_t m, int64_t *host_F) {
-  MSC_REQUIRE(host_F != nullptr, "msc_vi_table: host_F is null");
-  host_F[0] = 0;
-  for (uint32_t n = 1; n <= m; n++) host_F[n] = (int64_t)std::rint((double)n * std::log2((double)n) * 16777216.0);
-  return MSC_OK;
-}
-
-template <typename T>
-static int vi_reserve(msc_context *ctx, DevBuf<T> &buf, size_t n, const char *what) {
-  const hipError_t e = reserve_synced(ctx->stream, buf, n);
-  if (e == hipSuccess) return MSC_OK;
-  (void)hipGetLastError();
-  return fail(e == hipErrorOutOfMemory ? MSC_ENOMEM : MSC_EHIP, "msc_partition_refine_vi: the %s of %zu bytes: %s", what,
-              n * sizeof(T), hipGetErrorString(e));
-}
-
-extern "C" int msc_partition_refine_vi(msc_context *ctx, const int32_t *samples_dev, uint64_t lds, uint32_t nsamples,
-                                       uint32_t m, const int32_t *start_dev, uint64_t ld, uint32_t nstarts,
-                                       uint32_t max_sweeps, uint32_t max_clusters, const uint32_t *host_order,
-                                       size_t workspace_bytes, uint32_t flags, int32_t *labels_dev, int64_t *decrease_dev,
-                                       uint32_t *sweeps_dev, uint64_t *moves_dev) {
-  const char *who = "msc_partition_refine_vi";
-  MSC_REQUIRE(ctx && samples_dev && start_dev, "%s: null argument", who);
-  MSC_REQUIRE(flags == 0, "%s: flags = %u (none is defined)", who, flags);
-  MSC_REQUIRE(nsamples > 0 && nstarts > 0 && m > 0, "%s: nsamples = %u, nstarts = %u, m = %u: none may be 0", who, nsamples,
-              nstarts, m);
-  MSC_REQUIRE(lds >= m && ld >= m, "%s: lds = %llu, ld = %llu below m = %u", who, (unsigned long long)lds,
-              (unsigned long long)ld, m);
-  MSC_REQUIRE(max_clusters >= 1 && max_clusters <= m, "%s: max_clusters = %u outside [1, m = %u]", who, max_clusters, m);
-  if (host_order) {
-    std::vector<uint8_t> seen(m, 0);
-    for (uint32_t a = 0; a < m; a++) {
-      MSC_REQUIRE(host_order[a] < m && !seen[host_order[a]], "%s: order is not a permutation of [0, %u): entry %u is %u",
-                  who, m, a, host_order[a]);
-      seen[host_order[a]] = 1;
-    }
-  }
-  if (m > kViMaxRows || nsamples > kViMaxSamples || max_clusters > kViMaxClusters)
-    return fail(MSC_EUNSUPPORTED, "%s: m = %u, nsamples = %u, max_clusters = %u: at most %u rows, %u samples and %u clusters",
-                who, m, nsamples, max_clusters, kViMaxRows, kViMaxSamples, kViMaxClusters);
-  // the table, and the widths of everything made of it: |D| <= 3 S G_max and decrease <= 2 S F(m) stay under 2^62
-  if (ctx->vi_G_m != m || ctx->vi_G_host.size() != m) {
-    std::vector<int64_t> F((size_t)m + 1);
-    MSC_TRY(msc_vi_table(m, F.data()));
-    ctx->vi_G_m = 0;
-    ctx->vi_G_host.resize(m);
-    for (uint32_t n = 0; n < m; n++) ctx->vi_G_host[n] = F[n + 1] - F[n];
-  }
-  {
-    const long double lim = 4611686018427387904.0L;                 // 2^62
-    long double fm = 0.0L, gmax = 0.0L;
-    for (uint32_t n = 0; n < m; n++) fm += (long double)ctx->vi_G_host[n], gmax = std::max(gmax, (long double)ctx->vi_G_host[n]);
-    if (3.0L * nsamples * gmax >= lim || 2.0L * nsamples * fm >= lim)
-      return fail(MSC_EUNSUPPORTED, "%s: nsamples = %u, m = %u: a gain or the decrease may pass 62 bits", who, nsamples, m);
-  }
-  MSC_TRY(device_error_check(ctx));
-  MSC_HIP(hipSetDevice(ctx->device));
-  if (!labels_dev && !decrease_dev && !sweeps_dev && !moves_dev) return MSC_OK;
-  const hipStream_t s = ctx->stream;
-  const uint64_t ldi = ((uint64_t)m + 3u) & ~(uint64_t)3u;
-  const uint32_t S = nsamples, kcap = round_up(max_clusters, kViCellPad);
-  const size_t budget = workspace_bytes ? workspace_bytes : (size_t)2 << 30;
-  uint32_t chunk = std::min<uint32_t>(nstarts, 4096);
-  uint64_t cells_per_start = 0;
-  if (max_sweeps > 0) {
-    // the samples: ids, cluster counts, their running sums and the rows' stretch indices.  The host waits once, for the
-    // total of the cluster counts: it is what a start's cells, and so the chunk of starts, are sized by
-    MSC_TRY(vi_reserve(ctx, ctx->vi_sample_ids, (size_t)S * ldi, "ids of the samples"));
-    MSC_TRY(vi_reserve(ctx, ctx->vi_L, S, "cluster counts of the samples"));
-    MSC_TRY(vi_reserve(ctx, ctx->vi_off, (size_t)S + 1, "running sums of the cluster counts"));
-    MSC_TRY(vi_reserve(ctx, ctx->vi_row, (size_t)m * S, "stretch indices of the rows"));
-    if (launch_vi_canon(s, samples_dev, lds, m, kViMaxClusters, S, 0, ctx->vi_sample_ids, ldi, ctx->vi_L, nullptr))
-      return fail(MSC_EHIP, "k_vi_canon launch failed");
-    if (launch_vi_rows(s, ctx->vi_sample_ids, ldi, ctx->vi_L, S, m, ctx->vi_off, ctx->vi_row))
-      return fail(MSC_EHIP, "k_vi_offsets / k_vi_transpose launch failed");
-    uint32_t stretches = 0;
-    MSC_HIP(hipMemcpyAsync(&stretches, ctx->vi_off + S, 4, hipMemcpyDeviceToHost, s));
-    MSC_HIP(hipStreamSynchronize(s));
-    cells_per_start = (uint64_t)stretches * kcap;
-    const uint64_t bytes = cells_per_start * 2u;
-    if (bytes > budget)
-      return fail(MSC_EUNSUPPORTED, "%s: the contingency cells of one start take %llu bytes (%u stretches of %u cells of 2 "
-                  "bytes), workspace_bytes allows %zu", who, (unsigned long long)bytes, stretches, kcap, budget);
-    chunk = (uint32_t)std::min<uint64_t>(chunk, budget / bytes);
-    MSC_TRY(vi_reserve(ctx, ctx->vi_cells, (size_t)chunk * cells_per_start, "contingency cells"));
-    if (!ctx->vi_G || ctx->vi_G_m != m) {
-      ctx->vi_G_m = 0;
-      MSC_TRY(vi_reserve(ctx, ctx->vi_G, m, "table of G"));
-      MSC_HIP(hipMemcpyAsync(ctx->vi_G, ctx->vi_G_host.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
-      MSC_HIP(hipStreamSynchronize(s));
-      ctx->vi_G_m = m;
-    }
-    if (host_order) {
-      MSC_TRY(vi_reserve(ctx, ctx->vi_order, m, "visiting order"));
-      MSC_HIP(hipMemcpyAsync(ctx->vi_order, host_order, (size_t)m * 4, hipMemcpyHostToDevice, s));
-    }
-  }
-  MSC_TRY(vi_reserve(ctx, ctx->vi_ids, (size_t)chunk * ldi, "cluster ids"));
-  MSC_TRY(vi_reserve(ctx, ctx->vi_st, chunk, "running totals"));
-  ViSweepArgs p;
-  p.row = ctx->vi_row, p.S = S, p.m = m, p.max_clusters = max_clusters, p.kcap = kcap;
-  p.order = host_order ? ctx->vi_order.get() : nullptr, p.G = ctx->vi_G, p.ids = ctx->vi_ids, p.ldi = ldi;
-  p.cells = ctx->vi_cells, p.cells_per_start = cells_per_start, p.st = ctx->vi_st;
-  std::vector<RefineStart> st_host;
-  for (uint32_t c0 = 0; c0 < nstarts; c0 += chunk) {
-    const uint32_t k = std::min(chunk, nstarts - c0);
-    if (launch_vi_canon(s, start_dev + (uint64_t)c0 * ld, ld, m, max_clusters, k, c0, ctx->vi_ids, ldi, nullptr, ctx->vi_st))
-      return fail(MSC_EHIP, "k_vi_canon launch failed");
-    if (max_sweeps > 0) {
-      MSC_HIP(hipMemsetAsync(ctx->vi_cells, 0, (size_t)k * cells_per_start * 2u, s));
-      if (launch_vi_count(s, ctx->num_cus, p, k)) return fail(MSC_EHIP, "k_vi_count launch failed");
-    }
-    for (uint32_t sweep = 0; sweep < max_sweeps; sweep++) {
-      // every sweep is a launch and the stream is not waited for -- up to kViBlindSweeps of them; a caller who allows
-      // more pays one wait per kViBlindSweeps further ones, so that the launches end when the starts have
-      constexpr uint32_t kViBlindSweeps = 64;
-      if (sweep >= kViBlindSweeps && sweep % kViBlindSweeps == 0) {
-        st_host.resize(k);
-        MSC_HIP(hipMemcpyAsync(st_host.data(), ctx->vi_st, (size_t)k * sizeof(RefineStart), hipMemcpyDeviceToHost, s));
-        MSC_HIP(hipStreamSynchronize(s));
-        bool any = false;
-        for (uint32_t i = 0; i < k; i++) any = any || st_host[i].active != 0u;
-        if (!any) break;
-      }
-      if (launch_vi_sweep(s, p, k)) return fail(MSC_EHIP, "k_vi_sweep launch failed");
-    }
-    if (launch_vi_finish(s, ctx->vi_ids, ldi, m, max_clusters, k, ctx->vi_st,
-                         labels_dev ? labels_dev + (uint64_t)c0 * m : nullptr, decrease_dev ? decrease_dev + c0 : nullptr,
-                         sweeps_dev ? sweeps_dev + c0 : nullptr, moves_dev ? moves_dev + c0 : nullptr))
-      return fail(MSC_EHIP, "k_vi_finish launch failed");
-  }
   return MSC_OK;
 }

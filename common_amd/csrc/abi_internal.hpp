@@ -1,0 +1,77 @@
+// abi_internal.hpp -- the seam between the core of the C ABI's host side (abi.cpp: context, dataviews, the state, its
+// plan and tables, score and sweep) and the units that hold one subsystem each (blocked.cpp, chains.cpp, hyper.cpp,
+// predict.cpp, summary.cpp): the environment switches, and the core's helpers that such a unit calls.  abi.cpp defines
+// them; a helper that only abi.cpp uses is static there and is not listed.  No object with state lives here.
+#pragma once
+
+#include <cstdlib>
+
+#include "msc_internal.hpp"
+
+namespace msc {
+
+// What the library reads from the environment, all of it here (INTEGRATION.md "Environment" says what each switch does):
+// read afresh by every call that plans, routes or allocates, so that a test may set a switch between two calls.
+struct Switches {
+  bool tail_forced = false, no_narrow_tail = false, no_bb_fuse = false, sweep_graph = false;
+  uint64_t tail_min_rows = 0;                           // (tail_forced)
+  int loo_lds = -1, sweep_nich1 = 0, alloc_candidates = 12;
+  int marginal_tile = -1;                               // MSC_MARGINAL_TILE: 1 / 0 = the fused tile kernel for every plan it takes / for none
+
+  float alloc_accept_gbps = 6650.f;
+};
+inline Switches read_switches() {
+  Switches sw;
+  if (const char *e = std::getenv("MSC_TAIL_MIN_ROWS")) sw.tail_forced = true, sw.tail_min_rows = (uint64_t)std::atoll(e);
+  sw.no_narrow_tail = std::getenv("MSC_NO_NARROW_TAIL") != nullptr, sw.no_bb_fuse = std::getenv("MSC_NO_BB_FUSE") != nullptr;
+  if (const char *e = std::getenv("MSC_LOO_LDS")) sw.loo_lds = std::atoi(e);
+  if (const char *e = std::getenv("MSC_SWEEP_NICH1")) sw.sweep_nich1 = std::atoi(e);
+  if (const char *e = std::getenv("MSC_MARGINAL_TILE")) sw.marginal_tile = std::atoi(e);
+  if (const char *g = std::getenv("MSC_SWEEP_GRAPH")) sw.sweep_graph = g[0] != '0' && g[0] != 0;
+  if (const char *e = std::getenv("MSC_ALLOC_CANDIDATES")) sw.alloc_candidates = std::atoi(e);
+  if (const char *e = std::getenv("MSC_ALLOC_ACCEPT_GBPS")) sw.alloc_accept_gbps = (float)std::atof(e);
+  return sw;
+}
+
+// count elements (at least one), zero-filled
+template <typename T>
+int alloc_zeroed(DevBuf<T> &buf, size_t count) {
+  MSC_HIP(buf.alloc(count, 1));
+  MSC_HIP(hipMemset(buf, 0, std::max<size_t>(count, 1) * sizeof(T)));
+  return MSC_OK;
+}
+
+// ---- what abi.cpp defines (each is described where it is defined) ------------------------------------------------------
+// Hidden: the library does not export them, and a unit's call is a direct one, as it was when all of this was one file
+// (msc_chains_visit makes a dozen of them per member state and call).
+#pragma GCC visibility push(hidden)
+int device_error_check(msc_context *ctx);
+int refuse_mid_step(const msc_state *st, const char *entry);
+bool refresh_alpha_sum(msc_state *st, uint32_t feature);
+int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows);
+uint64_t view_rows(const msc_state *st);
+
+int ensure_raw(msc_state *st);
+int ensure_derived(msc_state *st);
+int ensure_crp(msc_state *st);
+int ensure_additive(msc_state *st);
+int ensure_all_current(msc_state *st);
+
+int refresh_fused_tables(msc_state *st);
+int run_loo_own(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z, bool crp);
+int run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z_dev, bool crp, bool niw_f32, float *out_dev,
+              uint64_t ld_out);
+
+// internal flags of accumulate_impl, next to the public MSC_ACC_*: the additive tables are already zero (a fused
+// sweep kernel did it); commit and prepare in one launch, which also moves the random stream on (msc_sweep_step)
+enum : uint32_t { kAccZeroed = 0x100, kAccThenPrepare = 0x200 };
+int commit(msc_state *st);
+int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                    const int32_t *z_dev, uint32_t flags);
+
+bool sweep_plain(const msc_state *st);
+int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                      uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep, bool *zeroed = nullptr);
+#pragma GCC visibility pop
+
+}  // namespace msc

@@ -1,0 +1,350 @@
+// chains.cpp -- the sequential collapsed Gibbs sweep and the ensembles of such chains (kernels_seq.hip):
+// msc_sweep_sequential and msc_chains_*.  Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
+#include <algorithm>
+#include <memory>
+#include <new>
+
+#include "abi_internal.hpp"
+#include "launchers.hpp"
+
+using namespace msc;
+
+// ---------------------------------------------------------------------------
+// The sequential sweep (k_sweep_seq): one workgroup carries the chain; the state carries over in global memory between
+// launches, and a launch takes as many row visits as fit kSeqLaunchUs by seq_visit_us.
+// ---------------------------------------------------------------------------
+constexpr double kSeqLaunchUs = 20000.0;        // what one launch may take (estimated)
+constexpr uint64_t kSeqMaxVisitsPerLaunch = 10000;
+
+// An upper estimate of one row visit, in microseconds: a fixed part (barriers, the draw, a nich prepare) plus the table
+// entries a leave and a join rebuild and the (group, feature) scores; fitted to the visits of profiles/sequential.txt (one
+// nich column to the C3 mix, K = 16 to 1024): launches measured there at 11.9 ms on average, 26.3 ms the longest
+static double seq_visit_us(const msc_state *st) {
+  double rows = 0.0;                              // table entries prepare_group writes per (feature, group)
+  for (uint32_t f = 0; f < st->nfeat; f++) {
+    switch (st->feats[f].family) {
+      case MSC_BB: rows += 4; break;
+      case MSC_GP:
+      case MSC_BNB: rows += 2.0 * st->desc_host[f].vcap + 4; break;
+      case MSC_DD: rows += 2.0 * st->feats[f].dim + 2; break;
+      case MSC_NICH: rows += 14; break;
+      default: break;
+    }
+  }
+  return 16.0 + 0.02 * 2.0 * rows + 0.007 * (double)st->K * (double)st->nfeat;
+}
+
+// whether the sequential kernel takes a state: ok, or the status and why not
+struct SeqRoute { int rc = MSC_OK; const char *why = ""; };
+static SeqRoute route_sequential(const msc_state *st) {
+  SeqRoute r;
+  for (const auto &h : st->feats) {
+    // niw, dm: prepare kernels of their own (msc_entity_op sends them down the general path); bbnc: a slot that empties
+    // mid-sweep would be offered with a stale p (free slots' p is drawn between sweeps, mixture_state refresh_free_slots)
+    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
+      r.rc = MSC_EUNSUPPORTED;
+      r.why = "the sequential sweep takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
+      return r;
+    }
+  }
+  if (st->nfeat > (uint32_t)kSeqMaxFeat) {
+    r.rc = MSC_EUNSUPPORTED;
+    r.why = "the sequential sweep takes at most 256 features";
+  } else if (st->K > kSeqMaxGroups) {
+    r.rc = MSC_EUNSUPPORTED;
+    r.why = "the sequential sweep takes at most 8192 groups";
+  }
+  return r;
+}
+
+extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                    uint64_t nrows, uint64_t row_id0, int32_t *z_dev, const uint32_t *order_dev,
+                                    uint32_t nsweeps, uint64_t seed, uint64_t sweep, int32_t *trace_dev) {
+  MSC_REQUIRE(st && view && (z_dev || nrows == 0), "null argument");
+  MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
+  MSC_TRY(refuse_mid_step(st, "msc_sweep_sequential"));
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  const SeqRoute route = route_sequential(st);
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  if (nrows == 0 || nsweeps == 0) return MSC_OK;
+  // every table current before (as msc_entity_op)
+  hipStream_t s = st->ctx->stream;
+  MSC_TRY(ensure_all_current(st));
+  const uint64_t visits = (uint64_t)nsweeps * nrows;
+  const uint64_t per_launch = (uint64_t)std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / seq_visit_us(st)));
+  for (uint64_t v0 = 0; v0 < visits; v0 += per_launch) {
+    const uint64_t v1 = std::min(visits, v0 + per_launch);
+    const int rc = launch_sweep_seq(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, row_id0, z_dev, order_dev,
+                                    v0, v1, seed, sweep, st->red_i64, st->cnt_u32, st->alpha, st->logpc, trace_dev);
+    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq does not take this shape");
+    if (rc) return fail(MSC_EHIP, "k_sweep_seq launch failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  // the kernel kept every table current: additive sums, fields, constants, counts and CRP terms
+  st->valid.kept_current();
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Many sequential chains in one launch (k_sweep_seq_chains): workgroup c carries the chain of member state c.
+// ---------------------------------------------------------------------------
+struct msc_chains {
+  msc_context *ctx = nullptr;
+  std::vector<msc_state *> states;
+  // the per-chain table of a call: filled on the host in one of two pinned areas, taken in turn, and copied to table_dev
+  // on the stream.  uploaded[i] is recorded after the copy out of area i; the host waits for it before it refills area i,
+  // so no pending copy reads an area that is being written.  table_dev itself is ordered by the stream: the copy of
+  // a call queues behind the launches of the call before it.
+  msc::PinnedBuf<msc::SeqChain> stage[2];
+  hipEvent_t uploaded[2] = {nullptr, nullptr};
+  bool pending[2] = {false, false};
+  int next = 0;
+  msc::DevBuf<msc::SeqChain> table_dev;   // [nchains]
+  msc::DevBuf<msc::ClonePair> pairs_dev;  // [nchains]: the pairs of a msc_chains_clone, staged through the same two areas
+};
+static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
+
+// the pinned staging area whose turn it is, once no pending copy reads it; chains_staged records the copy out of it
+static int chains_stage(msc_chains *ch, int *area) {
+  const int a = ch->next;
+  ch->next ^= 1;
+  if (ch->pending[a]) MSC_HIP(hipEventSynchronize(ch->uploaded[a]));
+  ch->pending[a] = false;
+  *area = a;
+  return MSC_OK;
+}
+static int chains_staged(msc_chains *ch, int area, hipStream_t s) {
+  MSC_HIP(hipEventRecord(ch->uploaded[area], s));
+  ch->pending[area] = true;
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc_chains **out) {
+  MSC_REQUIRE(states && out, "null argument");
+  *out = nullptr;
+  MSC_REQUIRE(nchains >= 1, "msc_chains_create: at least one state");
+  for (uint32_t c = 0; c < nchains; c++) {
+    const msc_state *st = states[c];
+    MSC_REQUIRE(st, "msc_chains_create: state %u is null", c);
+    MSC_REQUIRE(st->ctx == states[0]->ctx, "msc_chains_create: state %u lives on another context than state 0", c);
+    for (uint32_t b = 0; b < c; b++)
+      MSC_REQUIRE(states[b] != st, "msc_chains_create: state %u is state %u again (two workgroups on one state's tables "
+                                   "would race)", c, b);
+    MSC_REQUIRE(st->K == states[0]->K, "msc_chains_create: state %u has %u groups, state 0 has %u", c, st->K, states[0]->K);
+    MSC_REQUIRE(st->nfeat == states[0]->nfeat, "msc_chains_create: state %u has %u features, state 0 has %u", c, st->nfeat,
+                states[0]->nfeat);
+    for (uint32_t f = 0; f < st->nfeat; f++)
+      MSC_REQUIRE(st->feats[f].family == states[0]->feats[f].family && st->feats[f].dim == states[0]->feats[f].dim,
+                  "msc_chains_create: feature %u of state %u (family %d, dim %u) differs from state 0's (family %d, dim %u)",
+                  f, c, st->feats[f].family, st->feats[f].dim, states[0]->feats[f].family, states[0]->feats[f].dim);
+  }
+  const SeqRoute route = route_sequential(states[0]);      // (equal feature lists and K: one answer for all)
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
+  msc_context *ctx = states[0]->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<msc_chains> ch(new (std::nothrow) msc_chains());
+  if (!ch) return fail(MSC_ENOMEM, "out of host memory");
+  ch->ctx = ctx;
+  ch->states.assign(states, states + nchains);
+  hipError_t e = ch->table_dev.alloc(nchains);
+  if (e == hipSuccess) e = ch->pairs_dev.alloc(nchains);
+  for (int i = 0; i < 2 && e == hipSuccess; i++) {
+    e = ch->stage[i].alloc(nchains);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ch->uploaded[i], hipEventDisableTiming);
+  }
+  if (e != hipSuccess) {
+    for (hipEvent_t ev : ch->uploaded) if (ev) (void)hipEventDestroy(ev);
+    return fail(MSC_EHIP, "msc_chains_create: %s", hipGetErrorString(e));
+  }
+  for (msc_state *st : ch->states) st->chain_members++;
+  *out = ch.release();
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_destroy(msc_chains *ch) {
+  if (!ch) return MSC_OK;
+  (void)hipSetDevice(ch->ctx->device);
+  (void)hipStreamSynchronize(ch->ctx->stream);             // (a launch may still read the table)
+  for (int i = 0; i < 2; i++) {
+    if (ch->pending[i]) (void)hipEventSynchronize(ch->uploaded[i]);
+    if (ch->uploaded[i]) (void)hipEventDestroy(ch->uploaded[i]);
+  }
+  for (msc_state *st : ch->states) st->chain_members--;
+  delete ch;
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_size(const msc_chains *ch, uint32_t *nchains) {
+  MSC_REQUIRE(ch && nchains, "null argument");
+  *nchains = (uint32_t)ch->states.size();
+  return MSC_OK;
+}
+
+// What msc_chains_sweep and msc_chains_visit share: visits [v0, v1) of a call's nsweeps x nrows for every chain (visit v is
+// sweep v / nrows, position v % nrows of the order), with the outputs each of the two has (null: not wanted).
+struct ChainsOutputs {
+  uint32_t trace_every = 1;           // >= 1
+  uint64_t ntrace = 0;                // samples per chain of trace / occupied
+  int32_t *trace = nullptr;           // [nchains][ntrace][nrows]
+  uint32_t *occupied = nullptr;       // [nchains][ntrace]
+  double *logw = nullptr;             // [nchains]
+  float *visit_logp = nullptr;        // chain c's at + c * ld_logp
+  uint64_t ld_logp = 0;
+};
+static int chains_visits_impl(msc_chains *ch, const char *who, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                              uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev,
+                              uint64_t ld_order, uint64_t v0, uint64_t v1, const uint64_t *host_seeds, uint64_t sweep,
+                              const ChainsOutputs &out) {
+  const uint32_t n = (uint32_t)ch->states.size();
+  MSC_REQUIRE((z_dev && host_seeds) || v0 >= v1, "null argument");
+  MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
+  MSC_REQUIRE(ld_z >= nrows, "%s: ld_z %llu < nrows %llu", who, (unsigned long long)ld_z, (unsigned long long)nrows);
+  MSC_REQUIRE(!order_dev || ld_order == 0 || ld_order >= nrows, "%s: ld_order %llu is neither 0 (one order "
+              "for all chains) nor >= nrows %llu", who, (unsigned long long)ld_order, (unsigned long long)nrows);
+  for (uint32_t c = 0; c < n; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  if (v0 >= v1) return MSC_OK;
+  // every table of every member current before, as msc_sweep_sequential
+  hipStream_t s = ctx->stream;
+  double visit_us = 0.0;
+  for (msc_state *st : ch->states) {
+    MSC_TRY(ensure_all_current(st));
+    visit_us = std::max(visit_us, seq_visit_us(st));
+  }
+  // the table of this call (pointers and alpha may have changed since the last one), through the pinned area whose turn it is
+  int a = 0;
+  MSC_TRY(chains_stage(ch, &a));
+  SeqChain *tab = ch->stage[a];
+  for (uint32_t c = 0; c < n; c++) {
+    const msc_state *st = ch->states[c];
+    SeqChain &e = tab[c];
+    e.feats = st->desc_dev;
+    e.cnt_acc = st->red_i64;
+    e.cnt_u32 = st->cnt_u32;
+    e.crp = st->logpc;
+    e.z = z_dev + (size_t)c * ld_z;
+    e.order = order_dev ? order_dev + (size_t)c * ld_order : nullptr;
+    e.trace = out.trace && out.ntrace ? out.trace + (size_t)c * out.ntrace * nrows : nullptr;
+    e.occupied = out.occupied && out.ntrace ? out.occupied + (size_t)c * out.ntrace : nullptr;
+    e.logw = out.logw ? out.logw + c : nullptr;
+    e.visit_logp = out.visit_logp ? out.visit_logp + (size_t)c * out.ld_logp : nullptr;
+    e.seed = host_seeds[c];
+    e.alpha = st->alpha;
+    e.pad = 0;
+  }
+  MSC_HIP(hipMemcpyAsync(ch->table_dev, tab, sizeof(SeqChain) * n, hipMemcpyHostToDevice, s));
+  MSC_TRY(chains_staged(ch, a, s));
+  // a launch's visits: what one chain may take in the launch's time (as msc_sweep_sequential, by the costliest member),
+  // divided by the rounds the grid runs in -- at this kernel's register count one workgroup is resident per CU
+  const msc_state *st0 = ch->states[0];
+  const double one = std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / visit_us));
+  const uint64_t rounds = (n + (uint32_t)std::max(1, ctx->num_cus) - 1) / (uint32_t)std::max(1, ctx->num_cus);
+  const uint64_t per_launch = std::max<uint64_t>(1, (uint64_t)one / rounds);
+  for (uint64_t w0 = v0; w0 < v1; w0 += per_launch) {
+    const uint64_t w1 = std::min(v1, w0 + per_launch);
+    const int rc = launch_sweep_seq_chains(s, ch->table_dev, n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows, row_id0, w0,
+                                           w1, sweep, out.trace_every);
+    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq_chains does not take this shape");
+    if (rc) return fail(MSC_EHIP, "k_sweep_seq_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  // the kernel kept every table of every member current: additive sums, fields, constants, counts and CRP terms
+  for (msc_state *st : ch->states) st->valid.kept_current();
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                                uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep, uint32_t trace_every,
+                                int32_t *trace_dev, uint32_t *occupied_dev) {
+  MSC_REQUIRE(ch && view, "null argument");
+  if (ch->states.empty()) return MSC_OK;
+  const bool tracing = trace_dev != nullptr || occupied_dev != nullptr;
+  MSC_REQUIRE(!tracing || trace_every >= 1, "msc_chains_sweep: trace_every must be >= 1 with a trace or an occupied array");
+  ChainsOutputs out;
+  out.trace_every = tracing ? trace_every : 1u;
+  out.ntrace = tracing ? nsweeps / trace_every : 0;
+  out.trace = trace_dev;
+  out.occupied = occupied_dev;
+  return chains_visits_impl(ch, "msc_chains_sweep", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, 0,
+                            (uint64_t)nsweeps * nrows, host_seeds, sweep, out);
+}
+
+extern "C" int msc_chains_visit(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                                uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                                uint64_t pos0, uint64_t npos, const uint64_t *host_seeds, uint64_t sweep, double *logw_dev,
+                                float *visit_logp_dev, uint64_t ld_logp) {
+  MSC_REQUIRE(ch && view, "null argument");
+  MSC_REQUIRE(pos0 <= nrows && npos <= nrows - pos0, "msc_chains_visit: positions [%llu, %llu + %llu) beyond nrows %llu",
+              (unsigned long long)pos0, (unsigned long long)pos0, (unsigned long long)npos, (unsigned long long)nrows);
+  MSC_REQUIRE(!visit_logp_dev || ld_logp >= nrows, "msc_chains_visit: ld_logp %llu < nrows %llu", (unsigned long long)ld_logp,
+              (unsigned long long)nrows);
+  if (ch->states.empty() || npos == 0) return MSC_OK;
+  ChainsOutputs out;
+  out.logw = logw_dev;
+  out.visit_logp = visit_logp_dev;
+  out.ld_logp = ld_logp;
+  return chains_visits_impl(ch, "msc_chains_visit", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, pos0,
+                            pos0 + npos, host_seeds, sweep, out);
+}
+
+extern "C" int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, int32_t *z_dev, uint64_t ld_z, uint64_t nrows) {
+  MSC_REQUIRE(ch && host_ancestors, "null argument");
+  const uint32_t n = (uint32_t)ch->states.size();
+  MSC_REQUIRE(z_dev || nrows == 0, "null argument");
+  MSC_REQUIRE(ld_z >= nrows, "msc_chains_clone: ld_z %llu < nrows %llu", (unsigned long long)ld_z, (unsigned long long)nrows);
+  uint32_t npairs = 0;
+  for (uint32_t c = 0; c < n; c++) {
+    const uint32_t a = host_ancestors[c];
+    MSC_REQUIRE(a < n, "msc_chains_clone: ancestor %u of chain %u is not a chain (%u chains)", a, c, n);
+    MSC_REQUIRE(host_ancestors[a] == a, "msc_chains_clone: chain %u copies chain %u, which is itself overwritten (by chain "
+                                        "%u): a source must survive in place", c, a, host_ancestors[a]);
+    npairs += a != c;
+  }
+  for (uint32_t c = 0; c < n; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_clone: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  if (npairs == 0) return MSC_OK;
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  hipStream_t s = ctx->stream;
+  // a source's additive tables hold the truth before they are read (after a sweep they do: this launches nothing then)
+  for (uint32_t c = 0; c < n; c++)
+    if (host_ancestors[c] != c) MSC_TRY(ensure_additive(ch->states[host_ancestors[c]]));
+  int area = 0;
+  MSC_TRY(chains_stage(ch, &area));
+  ClonePair *tab = reinterpret_cast<ClonePair *>(ch->stage[area].get());
+  const msc_state *st0 = ch->states[0];
+  uint32_t p = 0;
+  for (uint32_t c = 0; c < n; c++) {
+    const uint32_t a = host_ancestors[c];
+    if (a == c) continue;
+    const msc_state *src = ch->states[a];
+    msc_state *dst = ch->states[c];
+    ClonePair &e = tab[p++];
+    e.src_i64 = src->red_i64;
+    e.dst_i64 = dst->red_i64;
+    e.src_f64 = src->red_f64;
+    e.dst_f64 = dst->red_f64;
+    e.src_z = z_dev + (size_t)a * ld_z;
+    e.dst_z = z_dev + (size_t)c * ld_z;
+  }
+  MSC_HIP(hipMemcpyAsync(ch->pairs_dev, tab, sizeof(ClonePair) * npairs, hipMemcpyHostToDevice, s));
+  MSC_TRY(chains_staged(ch, area, s));
+  if (launch_chains_clone(s, ch->pairs_dev, npairs, st0->n_i64, st0->n_f64, nrows))
+    return fail(MSC_EHIP, "k_chains_clone launch failed: %s", hipGetErrorString(hipGetLastError()));
+  // a destination's additive tables were replaced as a whole and alone hold its truth now, as after an accumulate that
+  // has not committed: the fields, the score constants and the CRP terms are rebuilt from them by the next call's ensure
+  // steps.  (additive_rewritten(), msc_state_reduce_unpack's event, would not do: that call comes between an uncommitted
+  // accumulate and a commit, so the fields are already marked stale there; a chain a sweep kept current has them marked
+  // current, and they would stay the destination's old ones.)
+  for (uint32_t c = 0; c < n; c++)
+    if (host_ancestors[c] != c) ch->states[c]->valid.accumulated();
+  return MSC_OK;
+}

@@ -221,7 +221,7 @@ struct ClonePair {
 int launch_chains_clone(hipStream_t stream, const ClonePair *pairs_dev, uint32_t npairs, size_t n_i64, size_t n_f64,
                         size_t nrows);
 
-// kernels_blocked.hip: the blocked Gibbs sampler (msc_blocked_*; abi.cpp route_blocked chooses the assign kernel)
+// kernels_blocked.hip: the blocked Gibbs sampler (msc_blocked_*; blocked.cpp route_blocked chooses the assign kernel)
 enum class BlockedKernel { nich1, staged, global };
 int launch_blocked_draw(hipStream_t stream, const BlkFeat *fs_dev, uint32_t nfeat, uint32_t K, uint32_t kpad,
                         const uint32_t *cnt, float alpha, uint64_t seed, uint64_t sweep, double *work, float *tab);
@@ -230,7 +230,7 @@ int launch_blocked_assign(hipStream_t stream, BlockedKernel kernel, uint32_t blo
                           int32_t *z, uint64_t seed, uint64_t sweep);
 int launch_blocked_top_slot(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint32_t *out);
 
-// kernels_splitmerge.hip: the split-merge move (msc_split_merge; abi.cpp route_splitmerge chooses the assign kernel).
+// kernels_splitmerge.hip: the split-merge move (msc_split_merge; blocked.cpp route_splitmerge chooses the assign kernel).
 // seed is the caller's: the launchers form the streams' keys (splitmerge_math.hpp).  `zero`: the pair state's additive
 // tables, emptied on the way for the accumulate pass that follows.
 int launch_sm_begin(hipStream_t stream, const int32_t *z, uint64_t nrows, uint64_t row_id0, const uint32_t *cnt, uint32_t K,
@@ -317,7 +317,7 @@ int launch_pred_sample(hipStream_t stream, const PredFeat *pfs_dev, const std::v
                        uint64_t row0, uint64_t nrows, uint64_t row_id0, const int32_t *z, int32_t *z_out,
                        bool masked_only, uint64_t seed, uint64_t sweep);
 
-// kernels_marginal.hip (msc_score_marginal; abi.cpp route_marginal chooses): norm = {log(n + alpha), log(n - 1 + alpha)} on the
+// kernels_marginal.hip (msc_score_marginal; predict.cpp route_marginal chooses): norm = {log(n + alpha), log(n - 1 + alpha)} on the
 // device; z null = no leave-one-out; map / logresp null = not wanted
 int launch_marginal_norm(hipStream_t stream, const uint32_t *cnt, uint32_t K, float alpha, double *norm);
 int launch_marginal_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, uint32_t K, uint32_t kpad, uint64_t row0,

@@ -462,6 +462,38 @@ __host__ __device__ inline size_t niw_b_index(uint32_t i) {
 
 }  // namespace msc
 
+// ---- workspaces of the opaque objects that one unit owns: the context's ----------------------------------------------
+namespace msc {
+// The workspaces a context keeps between calls for the posterior summaries of summary.cpp, each used by one entry point.
+// msc_linkage_single: the chain's edges, 3 (n - 1) doubles
+struct LinkageWork {
+  DevBuf<double> edges;
+};
+// msc_partition_distances: the ids and cluster counts of a chunk of a and a chunk of b, log2 n for n <= log2_n, and the
+// contingency tables of the pairs that do not fit LDS (zeroed once; the kernel leaves them zero)
+struct PdWork {
+  DevBuf<uint16_t> ids;
+  DevBuf<uint32_t> k;
+  DevBuf<double> log2;
+  uint32_t log2_n = 0;
+  DevBuf<uint32_t> table;
+};
+// msc_partition_refine_vi (kernels_refine_vi.hip), allocated at first use: the samples' ids [S][ldi], their cluster
+// counts and running sums, the stretch indices [m][S], G of msc_vi_table for m = G_m rows (0: none; the host copy is
+// what the upload reads), the visiting order, and a chunk of starts' ids, totals and contingency cells
+struct ViWork {
+  DevBuf<uint16_t> sample_ids;
+  DevBuf<uint32_t> L, off, row;
+  DevBuf<int64_t> G;
+  std::vector<int64_t> G_host;
+  uint32_t G_m = 0;
+  DevBuf<uint32_t> order;
+  DevBuf<uint16_t> ids;
+  DevBuf<RefineStart> st;
+  DevBuf<uint16_t> cells;
+};
+}  // namespace msc
+
 // ---- opaque objects ---------------------------------------------------------
 struct msc_context {
   int device = 0;
@@ -499,27 +531,9 @@ struct msc_context {
   bool sync_word_ok = true;                // cleared when the stream operation is refused: plain stream waits from then on
   // the device's error word {code, detail} (device_error.hpp), pinned and shared by every context on the device
   volatile uint32_t *err_host = nullptr;
-  // msc_linkage_single: the chain's edges, 3 (n - 1) doubles, kept between calls
-  msc::DevBuf<double> linkage_edges;
-  // msc_partition_distances, kept between calls: the ids and cluster counts of a chunk of a and a chunk of b, log2 n for
-  // n <= pd_log2_n, and the contingency tables of the pairs that do not fit LDS (zeroed once; the kernel leaves them zero)
-  msc::DevBuf<uint16_t> pd_ids;
-  msc::DevBuf<uint32_t> pd_k;
-  msc::DevBuf<double> pd_log2;
-  uint32_t pd_log2_n = 0;
-  msc::DevBuf<uint32_t> pd_table;
-  // msc_partition_refine_vi (kernels_refine_vi.hip), allocated at first use and kept: the samples' ids [S][ldi], their
-  // cluster counts and running sums, the stretch indices [m][S], G of msc_vi_table for m = vi_G_m rows (0: none; the
-  // host copy is what the upload reads), the visiting order, and a chunk of starts' ids, totals and contingency cells
-  msc::DevBuf<uint16_t> vi_sample_ids;
-  msc::DevBuf<uint32_t> vi_L, vi_off, vi_row;
-  msc::DevBuf<int64_t> vi_G;
-  std::vector<int64_t> vi_G_host;
-  uint32_t vi_G_m = 0;
-  msc::DevBuf<uint32_t> vi_order;
-  msc::DevBuf<uint16_t> vi_ids;
-  msc::DevBuf<msc::RefineStart> vi_st;
-  msc::DevBuf<uint16_t> vi_cells;
+  msc::LinkageWork linkage;               // msc_linkage_single (summary.cpp)
+  msc::PdWork pd;                         // msc_partition_distances (summary.cpp)
+  msc::ViWork vi;                         // msc_partition_refine_vi (summary.cpp)
 };
 
 struct msc_dataview {
@@ -584,6 +598,54 @@ struct msc_hp_grid {
   msc::HpJob job;                     // the grid alone (part_off = out_off = 0)
   msc::DevBuf<msc::HpJob> job_dev;
 };
+
+// ---- ... and the state's --------------------------------------------------------------------------------------------
+namespace msc {
+// grid hyper-parameter inference (hyper.cpp msc_hp_grid_*): the live grids (destroyed with the state at the latest) and
+// the workspaces of the calls, grown on demand
+struct HyperWork {
+  std::vector<std::unique_ptr<msc_hp_grid>> grids;
+  DevBuf<double> part;           // per (group block, point) partial sums
+  DevBuf<double> out;            // msc_hp_grid_gibbs: every grid's likelihoods
+  DevBuf<HpJob> jobs_dev;        // msc_hp_grid_gibbs: the grids of the call, then the indices drawn
+  DevBuf<uint32_t> chosen_dev;
+  std::vector<HpJob> jobs_host;
+  // slice sampling (hyper.cpp msc_hp_slice / msc_theta_slice): the call's targets and entries, then its outputs; grown on
+  // demand
+  DevBuf<unsigned char> slice_buf;
+};
+// posterior predictive sampling (predict.cpp msc_sample_predictive): the drawn features' descriptors and parameters, and
+// the scratch assignment of a group draw, grown on demand
+struct PredWork {
+  DevBuf<PredFeat> feats_dev;
+  DevBuf<double> par;
+  DevBuf<int32_t> z;
+  std::vector<PredFeat> feats_host;   // what feats_dev holds
+  PinnedBuf<PredFeat> stage;          // pinned staging of the upload
+  hipEvent_t upload = nullptr;        // recorded after the upload from stage; destroyed with the state
+  bool upload_pending = false;
+};
+// the blocked Gibbs sampler (blocked.cpp msc_blocked_*): the parameter table -- (1 + sum of the features' slices) rows of
+// kpad floats, row 0 the log stick weights -- the features as the kernels read them, the stick kernel's scratch
+// (log V, log(1 - V): 2 K doubles); whether the table was drawn from the tables as they stand: valid.draw_current()
+struct BlockedWork {
+  DevBuf<float> tab;
+  DevBuf<BlkFeat> feats_dev;
+  std::vector<BlkFeat> feats_host;
+  DevBuf<double> work;
+  uint32_t rows = 0;
+};
+// the split-merge move (blocked.cpp msc_split_merge): an internal three-slot state of the same features -- pair slots 0
+// and 1, slot 2 their union -- created at the first call and destroyed with its state; the pair labels of the call's
+// rows, the assign kernel's per-workgroup partials, the proposal descriptor and the pair state's score_data
+struct SplitMergeWork {
+  msc_state *pair = nullptr;
+  DevBuf<int32_t> ell;
+  DevBuf<double> part;
+  DevBuf<SmProp> prop;
+  DevBuf<float> sd;
+};
+}  // namespace msc
 
 struct msc_state {
   msc_context *ctx = nullptr;
@@ -668,46 +730,14 @@ struct msc_state {
   msc::DevBuf<double> niw_qown;      // q of every row's own group (niw leave-one-out), one a row
   msc::DevBuf<int32_t> one_z;        // a one-entry assignment vector (msc_entity_op's general path)
   msc::DevBuf<uint32_t> niw_scratch;   // row bucketing for niw accumulate: 2 K + 1 + rows uint32
-  // grid hyper-parameter inference (abi.cpp msc_hp_grid_*): the live grids (destroyed with the state at the latest) and
-  // the workspaces of the calls, grown on demand
-  std::vector<std::unique_ptr<msc_hp_grid>> hp_grids;
-  msc::DevBuf<double> hp_part;        // per (group block, point) partial sums
-  msc::DevBuf<double> hp_out;         // msc_hp_grid_gibbs: every grid's likelihoods
-  msc::DevBuf<msc::HpJob> hp_jobs_dev;   // msc_hp_grid_gibbs: the grids of the call, then the indices drawn
-  msc::DevBuf<uint32_t> hp_chosen_dev;
-  std::vector<msc::HpJob> hp_jobs_host;
-  // slice sampling (abi.cpp msc_hp_slice / msc_theta_slice): the call's targets and entries, then its outputs; grown on
-  // demand
-  msc::DevBuf<unsigned char> slice_buf;
-  // posterior predictive sampling (abi.cpp msc_sample_predictive): the drawn features' descriptors and parameters, and
-  // the scratch assignment of a group draw, grown on demand
-  msc::DevBuf<msc::PredFeat> pred_feats_dev;
-  msc::DevBuf<double> pred_par;
-  msc::DevBuf<int32_t> pred_z;
-  std::vector<msc::PredFeat> pred_feats_host;   // what pred_feats_dev holds
-  msc::PinnedBuf<msc::PredFeat> pred_stage;     // pinned staging of the upload
-  hipEvent_t pred_upload = nullptr;             // recorded after the upload from pred_stage
-  bool pred_upload_pending = false;
-  // the blocked Gibbs sampler (abi.cpp msc_blocked_*): the parameter table -- (1 + sum of the features' slices) rows of
-  // kpad floats, row 0 the log stick weights -- the features as the kernels read them, the stick kernel's scratch
-  // (log V, log(1 - V): 2 K doubles); whether the table was drawn from the tables as they stand: valid.draw_current()
-  msc::DevBuf<float> blk_tab;
-  msc::DevBuf<msc::BlkFeat> blk_feats_dev;
-  std::vector<msc::BlkFeat> blk_feats_host;
-  msc::DevBuf<double> blk_work;
-  uint32_t blk_rows = 0;
-  // the split-merge move (abi.cpp msc_split_merge): an internal three-slot state of the same features -- pair slots 0
-  // and 1, slot 2 their union -- created at the first call and destroyed with this one; the pair labels of the call's
-  // rows, the assign kernel's per-workgroup partials, the proposal descriptor and the pair state's score_data
-  msc_state *sm_pair = nullptr;
-  msc::DevBuf<int32_t> sm_ell;
-  msc::DevBuf<double> sm_part;
-  msc::DevBuf<msc::SmProp> sm_prop;
-  msc::DevBuf<float> sm_sd;
+  msc::HyperWork hp;                  // msc_hp_grid_*, msc_hp_slice, msc_theta_slice (hyper.cpp)
+  msc::PredWork pred;                 // msc_sample_predictive (predict.cpp)
+  msc::BlockedWork blk;               // msc_blocked_*, msc_sweep_blocked (blocked.cpp)
+  msc::SplitMergeWork sm;             // msc_split_merge (blocked.cpp)
   uint32_t chain_members = 0;                   // live msc_chains handles that hold this state: it cannot be destroyed meanwhile
 };
 
-// a z-matrix accumulator (abi.cpp msc_zmatrix_*, kernels_query.hip): m selected rows, counts as upper-triangle tiles
+// a z-matrix accumulator (summary.cpp msc_zmatrix_*, kernels_query.hip): m selected rows, counts as upper-triangle tiles
 struct msc_zmatrix {
   msc_context *ctx = nullptr;
   uint64_t n = 0;

@@ -7,9 +7,9 @@
 // the truth, whether additive and derived are in sync with it; per state, whether the additive copy of the counts and
 // the CRP table are in sync with the counts, and whether a draw was made from everything as it stands.
 //
-// The interface is the EVENTS that happen to a state (abi.cpp says which, never what to do to a flag):
+// The interface is the EVENTS that happen to a state (abi.cpp and the units beside it say which, never what to do to a flag):
 //
-//   event                      raw     additive    derived    counts' additive   crp     draw     abi.cpp
+//   event                      raw     additive    derived    counts' additive   crp     draw     who reports it
 //   created(n)                 all 1   all 1       all 0      1                  0       0        msc_state_create (all zero)
 //   fields_written(f)          .       f: 0        f: 0       .                  .       0        msc_state_set_ss
 //   hp_changed(f)              .       .           f: 0       .                  .       0        msc_state_set_hp, hp_installed,
