@@ -3,6 +3,7 @@
 A ChainEnsemble owns nchains State objects of one shape and their assignment vectors.  Chain c of a sweep does exactly what
 State.sweep_sequential does on ens.states[c] with the same seed and arguments; the ensemble only runs them side by side.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,10 @@ from . import smc as S
 from .runtime import _I32_U32, State
 
 _U64 = (1 << 64) - 1
+
+# what ChainEnsemble.run returns: the thinned trace (int32 device tensor [nchains, niters // trace_every, nrows] or None)
+# and the values every iteration's hp step installed (float32 host array [nchains, niters, ncoords])
+RunResult = collections.namedtuple("RunResult", ["trace", "values"])
 
 
 def trace_shape(nsweeps, trace_every, nchains, nrows):
@@ -227,6 +232,77 @@ class ChainEnsemble(object):
         L.check(self.ctx.lib.msc_chains_clone(self._h, (C.c_uint32 * self.nchains)(*anc), A.ptr(self.z),
                                               int(self.z.stride(0)), int(self.z.shape[1])))
 
+    # the hyper-parameter step ---------------------------------------------------
+    def _check_hp_slice(self, seed, slots):
+        """the argument checks of hp_slice that need no library -> (seeds, slots' pointer, ld_slots)"""
+        self._check_open()
+        seeds = chain_seeds(seed, self.nchains)
+        if slots is None:
+            return seeds, None, 0
+        if not isinstance(slots, torch.Tensor) or tuple(slots.shape) not in ((self.K,), (self.nchains, self.K)):
+            raise ValueError("slots must be a uint8 tensor [ngroups = %d] (all chains) or [nchains = %d, ngroups]"
+                             % (self.K, self.nchains))
+        sp = A.flat(slots, torch.uint8, slots.numel(), self.ctx.torch_device, "slots")
+        return seeds, sp, (self.K if slots.dim() == 2 else 0)
+
+    def hp_slice(self, coords, seed, sweep=0, slots=None):
+        """one slice step of each entry of `coords` on EVERY chain (msc_chains_hp_slice: one launch for the step, one for
+        the score and CRP tables it made stale, one host synchronisation).  coords: State.hp_slice's dicts, one list for
+        all chains.  seed: an int (chain c takes seed + c) or nchains ints.  slots: uint8 device mask of the counted
+        groups, [ngroups] for all chains or [nchains, ngroups] (default: each chain's non-empty ones).
+        -> (installed values float32 [nchains, n], evaluations uint32 [nchains, n]) as numpy.
+        Chain c ends exactly where ens.states[c].hp_slice(coords, chain_seeds(seed, nchains)[c], sweep, slots_c) would
+        have left it, bit for bit.  Afterwards the chains no longer share hyper-parameters and alpha (see smc())."""
+        seeds, sp, ld_slots = self._check_hp_slice(seed, slots)
+        coords = list(coords)
+        arr = State._slice_coord_array(coords)
+        values = np.zeros((self.nchains, len(coords)), dtype=np.float32)
+        evals = np.zeros((self.nchains, len(coords)), dtype=np.uint32)
+        for st in self.states:
+            st._drop_subsets()
+        L.check(self.ctx.lib.msc_chains_hp_slice(self._h, arr, len(coords), sp, ld_slots, (C.c_uint64 * self.nchains)(*seeds),
+                                                 int(sweep), values.ctypes.data_as(C.c_void_p),
+                                                 evals.ctypes.data_as(C.c_void_p)))
+        return values, evals
+
+    def run(self, view, niters, seed, hp=None, sweep=0, order=None, trace_every=None, zmatrix=None):
+        """niters iterations of the sampler on every chain: iteration i is self.sweep(view, 1, seed, sweep=sweep + i,
+        order=order) followed, when hp (a hypers.EnsembleHpSlice of this ensemble) is given, by hp.step(seed, sweep + i)
+        -- exactly those calls, so exactly what they give made by hand.  -> RunResult(trace, values): trace the int32
+        device tensor [nchains, niters // trace_every, nrows] of every chain's z after each trace_every-th iteration
+        (trace_every None: after every iteration when a zmatrix is given, else no trace and trace is None); values the
+        float32 host array [nchains, niters, ncoords] of what each step installed, in the order of hp.coords (ncoords =
+        0 without hp).  zmatrix: a ZMatrix over the view's rows that takes the whole trace in one add."""
+        self._check_open()
+        if self.z is None:
+            raise ValueError("no assignment yet: call assign() or seat() first")
+        niters, n = int(niters), int(view.nrows)
+        if niters < 0:
+            raise ValueError("niters must be >= 0")
+        if hp is not None and getattr(hp, "ens", None) is not self:
+            raise ValueError("hp must be an EnsembleHpSlice of this ensemble")
+        if zmatrix is not None and trace_every is None:
+            trace_every = 1
+        trace = None
+        if trace_every is not None:
+            shape = trace_shape(niters, trace_every, self.nchains, n)
+            if zmatrix is not None and (zmatrix.n != n or zmatrix.ctx is not self.ctx):
+                raise ValueError("zmatrix must be over the %d rows of the view, on the ensemble's context" % n)
+            trace = torch.empty(shape, dtype=torch.int32, device=self.ctx.torch_device)
+        ncoords = len(hp.coords) if hp is not None else 0
+        values = np.zeros((self.nchains, niters, ncoords), dtype=np.float32)
+        for i in range(niters):
+            self.sweep(view, 1, seed, sweep=sweep + i, order=order)
+            if hp is not None:
+                hp.step(seed, sweep + i)
+                if ncoords:
+                    values[:, i, :] = hp.last_values
+            if trace is not None and (i + 1) % trace_every == 0:
+                trace[:, (i + 1) // trace_every - 1, :].copy_(self.z)
+        if zmatrix is not None and trace.shape[1] > 0:
+            zmatrix.add(trace.view(-1, n))
+        return RunResult(trace=trace, values=values)
+
     def smc(self, view, seed, order=None, block=None, ess_threshold=0.5, resample_seed=None, final_resample=False, sweep=0):
         """A particle filter over the rows, the chains as particles -> smc.SMCResult, whose log_evidence estimates
         log p(X | hp, alpha), the marginal likelihood of the mixture.
@@ -240,7 +316,8 @@ class ChainEnsemble(object):
         ess_threshold = 0 never resamples (plain sequential importance sampling); float("inf") always does.  u comes from
         numpy.random.Generator(numpy.random.Philox(key=resample_seed)), resample_seed defaulting to the first chain's
         key; one random() is drawn per checkpoint whether or not it is used, so a run is reproducible from its arguments.
-        exp(log_evidence) is unbiased for p(X) whatever the threshold, provided all chains share hyper-parameters and alpha.
+        exp(log_evidence) is unbiased for p(X) whatever the threshold, provided all chains share hyper-parameters and alpha
+        -- which hp_slice() (and run() with an hp step) ends: every chain then holds its own; set them equal again first.
 
         final_resample: one more resampling after the last block, so that the particles end equally weighted: ens.z can go
         straight into a ZMatrix and ens.sweep can continue from them.

@@ -1735,7 +1735,7 @@ static uint32_t dm_value_slices(const msc_feature_host &h) {
 }
 
 // threads per (feature, group) that share the rows of a count / categorical table in the prepare kernels: ~4 rows each
-static uint32_t prepare_value_slices(const msc_state *st) {
+uint32_t msc::prepare_value_slices(const msc_state *st) {
   uint32_t rows = 1;
   for (uint32_t f = 0; f < st->nfeat; f++) {
     const int fam = st->feats[f].family;

@@ -1,10 +1,12 @@
 // abi_internal.hpp -- the seam between the core of the C ABI's host side (abi.cpp: context, dataviews, the state, its
 // plan and tables, score and sweep) and the units that hold one subsystem each (blocked.cpp, chains.cpp, hyper.cpp,
 // predict.cpp, summary.cpp): the environment switches, and the core's helpers that such a unit calls.  abi.cpp defines
-// them; a helper that only abi.cpp uses is static there and is not listed.  No object with state lives here.
+// them; a helper that only abi.cpp uses is static there and is not listed.  Last, the slice step's host side, which
+// hyper.cpp defines and chains.cpp shares.  No object with state lives here.
 #pragma once
 
 #include <cstdlib>
+#include <vector>
 
 #include "msc_internal.hpp"
 
@@ -51,6 +53,7 @@ bool refresh_alpha_sum(msc_state *st, uint32_t feature);
 int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows);
 uint64_t view_rows(const msc_state *st);
 
+uint32_t prepare_value_slices(const msc_state *st);
 int ensure_raw(msc_state *st);
 int ensure_derived(msc_state *st);
 int ensure_crp(msc_state *st);
@@ -72,6 +75,23 @@ int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32_t *col
 bool sweep_plain(const msc_state *st);
 int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                       uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep, bool *zeroed = nullptr);
+
+// ---- what hyper.cpp defines: the slice step's host side, shared by msc_hp_slice and msc_chains_hp_slice (chains.cpp) ----
+constexpr uint64_t kSliceKey = 0x2545F4914F6CDD1Dull;   // the slice steps' key is seed ^ this
+void hp_installed(msc_state *st, uint32_t feature, const float *blk);
+void alpha_installed(msc_state *st, float alpha);
+// a checked call's targets (tslot: the feature, or nfeat for alpha) and their entries in device order
+struct SlicePlan {
+  std::vector<uint32_t> tslot, first, count;   // per target: entries [first, first + count) of dc
+  std::vector<SliceCoord> dc;                  // per entry, targets one after the other
+  std::vector<uint32_t> caller;                // device entry -> the caller's index
+  uint32_t ntargets() const { return (uint32_t)tslot.size(); }
+  uint32_t n() const { return (uint32_t)dc.size(); }
+};
+int slice_plan(const msc_state *st, const msc_slice_coord *coords, uint32_t n, SlicePlan &plan);
+void slice_targets(const msc_state *st, const SlicePlan &plan, SliceTarget *targets);
+int slice_installed(msc_state *st, const SlicePlan &plan, const msc_slice_coord *coords, const float *val, const uint32_t *ev,
+                    const uint32_t *stat, float *values_host, uint32_t *evals_host, int64_t chain);
 #pragma GCC visibility pop
 
 }  // namespace msc

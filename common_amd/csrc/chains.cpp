@@ -102,6 +102,11 @@ struct msc_chains {
   int next = 0;
   msc::DevBuf<msc::SeqChain> table_dev;   // [nchains]
   msc::DevBuf<msc::ClonePair> pairs_dev;  // [nchains]: the pairs of a msc_chains_clone, staged through the same two areas
+  // msc_chains_hp_slice: one device buffer (chains | targets | entries | values | evals | status), grown by
+  // reserve_synced, and the host images of its two halves.  Every way out of that call past the upload waits for the
+  // stream, so no copy is pending when the next call rewrites an image.
+  msc::DevBuf<unsigned char> hp_buf;
+  std::vector<unsigned char> hp_up, hp_down;
 };
 static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
 
@@ -347,4 +352,93 @@ extern "C" int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, 
   for (uint32_t c = 0; c < n; c++)
     if (host_ancestors[c] != c) ch->states[c]->valid.accumulated();
   return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The slice step of every chain in one launch (k_hp_slice_chains), and the rebuild of what it made stale in another
+// (k_chains_prepare): msc_hp_slice on every member, with one host synchronisation for the call.
+// ---------------------------------------------------------------------------
+static size_t hp_align(size_t n) { return (n + 15) & ~(size_t)15; }
+
+extern "C" int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
+                                   uint64_t ld_slots, const uint64_t *host_seeds, uint64_t sweep, float *values_host,
+                                   uint32_t *evals_host) {
+  MSC_REQUIRE(ch && coords && host_seeds, "null argument");
+  MSC_REQUIRE(n > 0, "no coordinates");
+  const uint32_t nc = (uint32_t)ch->states.size();
+  if (nc == 0) return MSC_OK;
+  const msc_state *st0 = ch->states[0];
+  MSC_REQUIRE(!slots_dev || ld_slots == 0 || ld_slots >= st0->K, "msc_chains_hp_slice: ld_slots %llu is neither 0 (one mask "
+              "for all chains) nor >= ngroups %u", (unsigned long long)ld_slots, st0->K);
+  for (uint32_t c = 0; c < nc; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_hp_slice: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  // msc_hp_slice's argument checks, once: the members' feature lists are equal (msc_chains_create)
+  SlicePlan plan;
+  MSC_TRY(slice_plan(st0, coords, n, plan));
+  const uint32_t nt = plan.ntargets();
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  uint32_t slices = 1;
+  for (msc_state *st : ch->states) {
+    MSC_TRY(ensure_raw(st));
+    slices = std::max(slices, prepare_value_slices(st));   // (the count moves no bit: prepare_group deals whole rows out)
+  }
+  // one buffer: chains | targets [nchains][nt] | entries | values | evals | status, the last three [nchains][n]
+  const size_t cells = (size_t)nc * n;
+  const size_t o_tgt = hp_align(nc * sizeof(HpChain)), o_coord = o_tgt + hp_align((size_t)nc * nt * sizeof(SliceTarget));
+  const size_t o_val = o_coord + hp_align(n * sizeof(SliceCoord)), o_ev = o_val + hp_align(cells * 4);
+  const size_t o_stat = o_ev + hp_align(cells * 4), total = o_stat + hp_align(cells * 4);
+  hipStream_t s = ctx->stream;
+  MSC_HIP(reserve_synced(s, ch->hp_buf, total));
+  ch->hp_up.assign(o_val, 0);
+  HpChain *hc = reinterpret_cast<HpChain *>(ch->hp_up.data());
+  SliceTarget *tg = reinterpret_cast<SliceTarget *>(ch->hp_up.data() + o_tgt);
+  for (uint32_t c = 0; c < nc; c++) {
+    const msc_state *st = ch->states[c];
+    HpChain &e = hc[c];
+    e.feats = st->desc_dev;
+    e.cnt = st->cnt_u32;
+    e.slots = slots_dev ? slots_dev + (size_t)c * ld_slots : nullptr;
+    e.crp = st->logpc;
+    e.key = host_seeds[c] ^ kSliceKey;
+    e.alpha = st->alpha;
+    e.pad = 0;
+    slice_targets(st, plan, tg + (size_t)c * nt);
+  }
+  std::memcpy(ch->hp_up.data() + o_coord, plan.dc.data(), n * sizeof(SliceCoord));
+  unsigned char *b = ch->hp_buf;
+  MSC_HIP(hipMemcpyAsync(b, ch->hp_up.data(), o_val, hipMemcpyHostToDevice, s));
+  ch->hp_down.assign(total - o_val, 0);
+  int rc = MSC_OK;
+  if (launch_hp_slice_chains(s, reinterpret_cast<const SliceTarget *>(b + o_tgt), nt, reinterpret_cast<HpChain *>(b), nc,
+                             reinterpret_cast<const SliceCoord *>(b + o_coord), n, st0->K, st0->kpad, sweep,
+                             reinterpret_cast<float *>(b + o_val), reinterpret_cast<uint32_t *>(b + o_ev),
+                             reinterpret_cast<uint32_t *>(b + o_stat)))
+    rc = fail(MSC_EHIP, "k_hp_slice_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
+  // every chain's score tables from its new hp blocks, its CRP table from its new alpha (which the step left in its entry)
+  else if (launch_chains_prepare(s, reinterpret_cast<const HpChain *>(b), nc, st0->nfeat, st0->K, st0->kpad, slices))
+    rc = fail(MSC_EHIP, "k_chains_prepare launch failed: %s", hipGetErrorString(hipGetLastError()));
+  if (rc != MSC_OK) {
+    (void)hipStreamSynchronize(s);                    // (the upload may still read hp_up)
+    return rc;
+  }
+  MSC_HIP(hipMemcpyAsync(ch->hp_down.data(), b + o_val, total - o_val, hipMemcpyDeviceToHost, s));
+  MSC_HIP(hipStreamSynchronize(s));                   // the call's one wait
+  const float *val = reinterpret_cast<const float *>(ch->hp_down.data());
+  const uint32_t *ev = reinterpret_cast<const uint32_t *>(ch->hp_down.data() + (o_ev - o_val));
+  const uint32_t *stat = reinterpret_cast<const uint32_t *>(ch->hp_down.data() + (o_stat - o_val));
+  // per member what msc_hp_slice's bookkeeping reports (hp_changed / alpha_changed for what moved), then what the second
+  // launch rebuilt.  The first chain with a target that was not finite names the call's error.
+  for (uint32_t c = nc; c-- > 0;) {
+    msc_state *st = ch->states[c];
+    const size_t at = (size_t)c * n;
+    const int r = slice_installed(st, plan, coords, val + at, ev + at, stat + at, values_host ? values_host + at : nullptr,
+                                  evals_host ? evals_host + at : nullptr, (int64_t)c);
+    if (r != MSC_OK) rc = r;
+    st->valid.prepared();
+    st->valid.crp_prepared();
+  }
+  return rc;
 }

@@ -3,6 +3,7 @@
 // abi_internal.hpp.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <memory>
 #include <new>
 
@@ -108,15 +109,15 @@ extern "C" int msc_hp_grid_score(msc_hp_grid *grid, const uint8_t *slots_dev, do
 
 // A kernel has written a feature's hp block (and, dd / dm, its alpha sum into the state's descriptor) on the device; the
 // host's bookkeeping follows as msc_state_set_hp keeps it: the host copy, the score tables' staleness and the alpha sum
-// in every host copy of the descriptor.  (msc_hp_grid_gibbs and msc_hp_slice.)
-static void hp_installed(msc_state *st, uint32_t feature, const float *blk) {
+// in every host copy of the descriptor.  (msc_hp_grid_gibbs, msc_hp_slice and msc_chains_hp_slice.)
+void msc::hp_installed(msc_state *st, uint32_t feature, const float *blk) {
   msc_feature_host &h = st->feats[feature];
   std::copy(blk, blk + h.hp.size(), h.hp.begin());
   st->valid.hp_changed(feature);
   (void)refresh_alpha_sum(st, feature);
 }
 // the same for alpha, which the device takes from the host at the next call that reads it (msc_state_set_alpha)
-static void alpha_installed(msc_state *st, float alpha) {
+void msc::alpha_installed(msc_state *st, float alpha) {
   st->alpha = alpha;
   st->valid.alpha_changed();
 }
@@ -207,8 +208,6 @@ extern "C" int msc_hp_grid_gibbs(msc_state *st, msc_hp_grid *const *grids, uint3
 // ---------------------------------------------------------------------------
 // slice sampling of hyper-parameters and bbnc group parameters (downstream's hp / theta kernels; kernels_slice.hip)
 // ---------------------------------------------------------------------------
-static constexpr uint64_t kSliceKey = 0x2545F4914F6CDD1Dull;   // the slice steps' key is seed ^ this
-
 static size_t slice_align(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // the support of a coordinate: every coordinate sliced is a positive float but nich mu
@@ -222,15 +221,14 @@ static const char *slice_unsupported(int family, uint32_t coord) {
   }
 }
 
-extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
-                            uint64_t seed, uint64_t sweep, float *values_host, uint32_t *evals_host) {
-  MSC_REQUIRE(st && coords, "null argument");
-  MSC_REQUIRE(n > 0, "no coordinates");
-  MSC_TRY(refuse_mid_step(st, "msc_hp_slice"));
-  // the targets in order of first appearance (slot nfeat = alpha), each with its entries in the caller's order
+// The argument checks of a slice step and its plan: the targets in order of first appearance (slot nfeat = alpha), each
+// with its entries in the caller's order.  Reads of `st` only what msc_chains_create makes equal over an ensemble's
+// members (the feature list), so one plan serves them all.
+int msc::slice_plan(const msc_state *st, const msc_slice_coord *coords, uint32_t n, SlicePlan &plan) {
   std::vector<int32_t> tix(st->nfeat + 1, -1);
   std::vector<std::vector<uint32_t>> members;
-  std::vector<uint32_t> tslot;
+  std::vector<uint32_t> &tslot = plan.tslot;
+  tslot.clear();
   for (uint32_t i = 0; i < n; i++) {
     const msc_slice_coord &c = coords[i];
     const bool cluster = c.feature == MSC_HP_CLUSTER;
@@ -265,17 +263,33 @@ extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32
     members[(size_t)tix[slot]].push_back(i);
   }
   const uint32_t nt = (uint32_t)members.size();
-  std::vector<SliceTarget> targets(nt);
-  std::vector<SliceCoord> dc(n);
-  std::vector<uint32_t> caller(n);                  // device entry -> the caller's index
+  plan.first.assign(nt, 0);
+  plan.count.assign(nt, 0);
+  plan.dc.assign(n, SliceCoord());
+  plan.caller.assign(n, 0);
   uint32_t at = 0;
   for (uint32_t t = 0; t < nt; t++) {
+    plan.first[t] = at;
+    plan.count[t] = (uint32_t)members[t].size();
+    for (uint32_t i : members[t]) {
+      const msc_slice_coord &c = coords[i];
+      plan.dc[at] = SliceCoord{c.coord, c.prior, c.prior == MSC_PRIOR_NONINF_BETA ? c.partner : 0u, c.width, c.prior_a,
+                               c.prior_b};
+      plan.caller[at++] = i;
+    }
+  }
+  return MSC_OK;
+}
+
+// the plan's targets as state `st` holds them now: its tables, its hp blocks, its alpha
+void msc::slice_targets(const msc_state *st, const SlicePlan &plan, SliceTarget *targets) {
+  for (uint32_t t = 0; t < plan.ntargets(); t++) {
     SliceTarget &T = targets[t];
     std::memset(&T, 0, sizeof T);
-    const uint32_t slot = tslot[t];
+    const uint32_t slot = plan.tslot[t];
     T.target = slot;
-    T.first = at;
-    T.n = (uint32_t)members[t].size();
+    T.first = plan.first[t];
+    T.n = plan.count[t];
     if (slot == st->nfeat) {
       T.family = kHpCluster;
       T.hpf = 1;
@@ -290,13 +304,51 @@ extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32
       T.raw_f32 = h.raw_f32;
       T.hp = h.hp_dev;
     }
-    for (uint32_t i : members[t]) {
-      const msc_slice_coord &c = coords[i];
-      dc[at] = SliceCoord{c.coord, c.prior, c.prior == MSC_PRIOR_NONINF_BETA ? c.partner : 0u, c.width, c.prior_a,
-                          c.prior_b};
-      caller[at++] = i;
+  }
+}
+
+// A slice kernel has written every target's final values (val / ev / stat: the plan's n entries in device order) and
+// every feature's final block into its device hp; the host's bookkeeping of `st` follows, the caller's outputs (nullable,
+// in the caller's order) are filled, and a target that was not finite at its current value is reported -- naming the
+// chain when chain >= 0.
+int msc::slice_installed(msc_state *st, const SlicePlan &plan, const msc_slice_coord *coords, const float *val,
+                         const uint32_t *ev, const uint32_t *stat, float *values_host, uint32_t *evals_host, int64_t chain) {
+  int rc = MSC_OK;
+  for (uint32_t t = 0; t < plan.ntargets(); t++) {
+    const uint32_t first = plan.first[t], end = first + plan.count[t];
+    if (plan.tslot[t] == st->nfeat) {
+      alpha_installed(st, val[end - 1]);
+    } else {
+      std::vector<float> blk = st->feats[plan.tslot[t]].hp;
+      for (uint32_t e = first; e < end; e++) blk[plan.dc[e].coord] = val[e];
+      hp_installed(st, plan.tslot[t], blk.data());
     }
   }
+  char who[32] = "";
+  if (chain >= 0) std::snprintf(who, sizeof who, "chain %lld, ", (long long)chain);
+  for (uint32_t e = 0; e < plan.n(); e++) {
+    const uint32_t i = plan.caller[e];
+    if (values_host) values_host[i] = val[e];
+    if (evals_host) evals_host[i] = ev[e];
+    if (stat[e] == kSliceNonFinite)
+      rc = fail(MSC_EINVAL, "%sentry %u (%s %u, coordinate %u): the target at the current value is not finite; left "
+                "unchanged", who, i, coords[i].feature == MSC_HP_CLUSTER ? "alpha" : "feature",
+                coords[i].feature == MSC_HP_CLUSTER ? 0u : coords[i].feature, coords[i].coord);
+  }
+  return rc;
+}
+
+extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
+                            uint64_t seed, uint64_t sweep, float *values_host, uint32_t *evals_host) {
+  MSC_REQUIRE(st && coords, "null argument");
+  MSC_REQUIRE(n > 0, "no coordinates");
+  MSC_TRY(refuse_mid_step(st, "msc_hp_slice"));
+  SlicePlan plan;
+  MSC_TRY(slice_plan(st, coords, n, plan));
+  const uint32_t nt = plan.ntargets();
+  std::vector<SliceTarget> targets(nt);
+  slice_targets(st, plan, targets.data());
+  const std::vector<SliceCoord> &dc = plan.dc;
   // one buffer: targets | entries | values | evals | status
   const size_t o_coord = slice_align(nt * sizeof(SliceTarget)), o_val = o_coord + slice_align(n * sizeof(SliceCoord));
   const size_t o_ev = o_val + slice_align(n * 4), o_stat = o_ev + slice_align(n * 4), total = o_stat + slice_align(n * 4);
@@ -319,28 +371,7 @@ extern "C" int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32
   const float *val = reinterpret_cast<const float *>(down.data());
   const uint32_t *ev = reinterpret_cast<const uint32_t *>(down.data() + (o_ev - o_val));
   const uint32_t *stat = reinterpret_cast<const uint32_t *>(down.data() + (o_stat - o_val));
-  // the kernel has written every feature's final block into its device hp; the host's bookkeeping follows
-  int rc = MSC_OK;
-  for (uint32_t t = 0; t < nt; t++) {
-    const SliceTarget &T = targets[t];
-    if (T.family == kHpCluster) {
-      alpha_installed(st, val[T.first + T.n - 1]);
-    } else {
-      std::vector<float> blk = st->feats[T.target].hp;
-      for (uint32_t e = T.first; e < T.first + T.n; e++) blk[dc[e].coord] = val[e];
-      hp_installed(st, T.target, blk.data());
-    }
-  }
-  for (uint32_t e = 0; e < n; e++) {
-    const uint32_t i = caller[e];
-    if (values_host) values_host[i] = val[e];
-    if (evals_host) evals_host[i] = ev[e];
-    if (stat[e] == kSliceNonFinite)
-      rc = fail(MSC_EINVAL, "entry %u (%s %u, coordinate %u): the target at the current value is not finite; left "
-                "unchanged", i, coords[i].feature == MSC_HP_CLUSTER ? "alpha" : "feature",
-                coords[i].feature == MSC_HP_CLUSTER ? 0u : coords[i].feature, coords[i].coord);
-  }
-  return rc;
+  return slice_installed(st, plan, coords, val, ev, stat, values_host, evals_host, -1);
 }
 
 extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const float *widths, uint32_t n,

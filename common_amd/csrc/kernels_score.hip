@@ -93,6 +93,22 @@ __global__ __launch_bounds__(256) void k_crp_prepare(const uint32_t *__restrict_
   crp_prepare_block(cnt, K, kpad, alpha, crp);
 }
 
+// k_prepare and k_crp_prepare for every chain of an ensemble in one launch (msc_chains_hp_slice: the step has changed
+// hyper-parameters and alpha of every chain).  grid (group blocks x value slices, features + 1, chains): row y < nfeat
+// is k_prepare's thread for feature y of chain z's descriptors; row nfeat rewrites the chain's CRP table from its counts
+// and the alpha the step left in the chain's entry (its first block walks all K, as k_crp_prepare's one block does).
+__global__ __launch_bounds__(256) void k_chains_prepare(const HpChain *__restrict__ chains, uint32_t nfeat, uint32_t K,
+                                                         uint32_t kpad, uint32_t kblocks) {
+  const HpChain H = chains[blockIdx.z];
+  if (blockIdx.y == nfeat) {
+    if (blockIdx.x == 0) crp_prepare_block(H.cnt, K, kpad, H.alpha, H.crp);
+    return;
+  }
+  const uint32_t k = (blockIdx.x % kblocks) * 256 + threadIdx.x;
+  if (k >= kpad) return;
+  prepare_group(H.feats[blockIdx.y], k, kpad, blockIdx.x / kblocks, gridDim.x / kblocks);
+}
+
 // The tail of a sweep step in one launch: commit (additive -> raw) and prepare (raw -> score tables) of every
 // (feature, group), by the same thread so no grid-wide ordering is needed; the extra y-slice commits the group
 // sizes and derives the CRP terms from them (one block walks all K), and moves the step's random stream on.
@@ -1063,6 +1079,15 @@ int launch_entity_op(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, u
 int launch_crp_prepare(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint32_t kpad, float alpha,
                        float *crp) {
   hipLaunchKernelGGL(k_crp_prepare, dim3(1), dim3(256), 0, stream, cnt, K, kpad, alpha, crp);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_chains_prepare(hipStream_t stream, const HpChain *chains_dev, uint32_t nchains, uint32_t nfeat, uint32_t K,
+                          uint32_t kpad, uint32_t value_slices) {
+  const uint32_t kblocks = (kpad + 255) / 256;
+  for (uint32_t c0 = 0; c0 < nchains; c0 += kMaxGridYZ)            // (a grid's z extent ends at 65535)
+    hipLaunchKernelGGL(k_chains_prepare, dim3(kblocks * (value_slices ? value_slices : 1), nfeat + 1, std::min(kMaxGridYZ, nchains - c0)),
+                       dim3(256), 0, stream, chains_dev + c0, nfeat, K, kpad, kblocks);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -2,12 +2,15 @@
 //   k_hp_slice     one workgroup per target (a feature's chain of hp coordinates, or the CRP alpha): the whole update
 //                  loop of every coordinate runs here, each evaluation of the target one pass of the workgroup over the
 //                  feature's counted groups (staged in LDS once) and a fixed-order reduction
+//   k_hp_slice_chains  the same body on a grid of (targets, chains): the step of every chain of an ensemble in one launch
 //   k_theta_slice  one lane per (bbnc feature, counted slot): the slot's p, an O(1) target with ln B(alpha, beta) hoisted
 // The update is Neal (2003), "Slice sampling", Fig. 3 (stepping out, at most m = 64 steps) and Fig. 5 (shrinkage), with
 // every proposal rounded to float32 (what the tables hold) before the target is evaluated there, and the uniforms taken
 // from Philox4x32-10 blocks of a counter of the update's own (the layout is in the header).  tests/slice_helpers.py
 // restates the algorithm on the host, operation by operation.  No atomics on values and every sum in a fixed order: two
 // calls on the same tables give the same bits, and so do the ranks of a sharded sweep.
+#include <algorithm>
+
 #include "family_math.hpp"
 #include "launchers.hpp"
 #include "pred_samplers.hpp"
@@ -186,13 +189,13 @@ struct HpSliceTarget {
 };
 static_assert(kSliceWaves == 4, "HpSliceTarget::likelihood adds four wave partials");
 
-// grid (targets), block kSliceThreads.  Entry e of target t: Philox counter (t.target, e, sweep, b), key `key`.
-__global__ __launch_bounds__(kSliceThreads) void k_hp_slice(const SliceTarget *__restrict__ targets,
-                                                            const SliceCoord *__restrict__ coords, uint32_t K,
-                                                            uint32_t kpad, const uint32_t *__restrict__ cnt,
-                                                            const uint8_t *__restrict__ slots, uint64_t key,
-                                                            uint32_t sweep_lo, float *__restrict__ values,
-                                                            uint32_t *__restrict__ evals, uint32_t *__restrict__ status) {
+// One target, one workgroup: the body of k_hp_slice and k_hp_slice_chains (one body, two kernels: a chain of the ensemble
+// does the arithmetic of a single msc_hp_slice call on its state, in the same order).  Entry e of the target: Philox
+// counter (T.target, e, sweep, b), key `key`.  alpha_out: null, or where the alpha target leaves the installed alpha.
+MSC_DEV void hp_slice_target(const SliceTarget &T, const SliceCoord *__restrict__ coords, uint32_t K, uint32_t kpad,
+                             const uint32_t *__restrict__ cnt, const uint8_t *__restrict__ slots, uint64_t key,
+                             uint32_t sweep_lo, float *__restrict__ values, uint32_t *__restrict__ evals,
+                             uint32_t *__restrict__ status, float *alpha_out) {
   __shared__ uint32_t tab[3 * kSliceCap];
   __shared__ double wred[2][kSliceWaves];
   __shared__ double lg_s[kSliceThreads];
@@ -200,7 +203,6 @@ __global__ __launch_bounds__(kSliceThreads) void k_hp_slice(const SliceTarget *_
   __shared__ uint32_t occ_s[kSliceThreads];
   __shared__ uint32_t wcnt[kSliceWaves];
   __shared__ uint32_t spill_at;
-  const SliceTarget &T = targets[blockIdx.x];
   const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   HpSliceTarget g;
   g.family = T.family;
@@ -295,6 +297,31 @@ __global__ __launch_bounds__(kSliceThreads) void k_hp_slice(const SliceTarget *_
     }
   }
   if (T.hp != nullptr && threadIdx.x < T.hpf) T.hp[threadIdx.x] = g.cur(threadIdx.x);
+  if (alpha_out != nullptr && T.family == kHpCluster && threadIdx.x == 0) *alpha_out = g.c0;
+}
+
+// grid (targets), block kSliceThreads: the targets of one state
+__global__ __launch_bounds__(kSliceThreads) void k_hp_slice(const SliceTarget *__restrict__ targets,
+                                                            const SliceCoord *__restrict__ coords, uint32_t K,
+                                                            uint32_t kpad, const uint32_t *__restrict__ cnt,
+                                                            const uint8_t *__restrict__ slots, uint64_t key,
+                                                            uint32_t sweep_lo, float *__restrict__ values,
+                                                            uint32_t *__restrict__ evals, uint32_t *__restrict__ status) {
+  hp_slice_target(targets[blockIdx.x], coords, K, kpad, cnt, slots, key, sweep_lo, values, evals, status, nullptr);
+}
+
+// grid (targets, chains), block kSliceThreads: workgroup (t, c) takes target t of chain c from targets[c][t] and what is
+// per chain (counts, mask, key) from chains[c]; the coordinates are the ensemble's, the outputs [nchains][n]
+__global__ __launch_bounds__(kSliceThreads) void k_hp_slice_chains(const SliceTarget *__restrict__ targets, HpChain *chains,
+                                                                   const SliceCoord *__restrict__ coords, uint32_t n,
+                                                                   uint32_t K, uint32_t kpad, uint32_t sweep_lo,
+                                                                   float *__restrict__ values, uint32_t *__restrict__ evals,
+                                                                   uint32_t *__restrict__ status) {
+  const uint32_t c = blockIdx.y;
+  HpChain &H = chains[c];
+  const size_t at = (size_t)c * n;
+  hp_slice_target(targets[(size_t)c * gridDim.x + blockIdx.x], coords, K, kpad, H.cnt, H.slots, H.key, sweep_lo, values + at,
+                  evals + at, status + at, &H.alpha);
 }
 
 // the target of one bbnc slot: bbnc_score_data(hp, heads, tails, p) on (0, 1)
@@ -360,6 +387,19 @@ int launch_hp_slice(hipStream_t stream, const SliceTarget *targets_dev, uint32_t
                     float *values, uint32_t *evals, uint32_t *status) {
   hipLaunchKernelGGL(k_hp_slice, dim3(ntargets), dim3(kSliceThreads), 0, stream, targets_dev, coords_dev, K, kpad, cnt,
                      slots, key, (uint32_t)sweep, values, evals, status);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_hp_slice_chains(hipStream_t stream, const SliceTarget *targets_dev, uint32_t ntargets, HpChain *chains_dev,
+                           uint32_t nchains, const SliceCoord *coords_dev, uint32_t n, uint32_t K, uint32_t kpad,
+                           uint64_t sweep, float *values, uint32_t *evals, uint32_t *status) {
+  for (uint32_t c0 = 0; c0 < nchains; c0 += kMaxGridYZ) {          // (a grid's y extent ends at 65535)
+    const uint32_t nc = std::min(kMaxGridYZ, nchains - c0);
+    const size_t at = (size_t)c0 * n;
+    hipLaunchKernelGGL(k_hp_slice_chains, dim3(ntargets, nc), dim3(kSliceThreads), 0, stream,
+                       targets_dev + (size_t)c0 * ntargets, chains_dev + c0, coords_dev, n, K, kpad, (uint32_t)sweep,
+                       values + at, evals + at, status + at);
+  }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -303,6 +303,15 @@ int launch_hp_grid_draw(hipStream_t stream, const HpJob *jobs_dev, uint32_t njob
 int launch_hp_slice(hipStream_t stream, const SliceTarget *targets_dev, uint32_t ntargets, const SliceCoord *coords_dev,
                     uint32_t K, uint32_t kpad, const uint32_t *cnt, const uint8_t *slots, uint64_t key, uint64_t sweep,
                     float *values, uint32_t *evals, uint32_t *status);
+// the ensemble's step (msc_chains_hp_slice): targets_dev [nchains][ntargets], chains_dev [nchains], coords_dev [n] shared,
+// values / evals / status [nchains][n]; then the rebuild of every chain's score tables (prepare_group, value_slices
+// threads per (feature, group) as launch_prepare) and CRP table from chains_dev[c].alpha as the step left it
+constexpr uint32_t kMaxGridYZ = 65535;
+int launch_hp_slice_chains(hipStream_t stream, const SliceTarget *targets_dev, uint32_t ntargets, HpChain *chains_dev,
+                           uint32_t nchains, const SliceCoord *coords_dev, uint32_t n, uint32_t K, uint32_t kpad,
+                           uint64_t sweep, float *values, uint32_t *evals, uint32_t *status);
+int launch_chains_prepare(hipStream_t stream, const HpChain *chains_dev, uint32_t nchains, uint32_t nfeat, uint32_t K,
+                          uint32_t kpad, uint32_t value_slices);
 inline uint32_t theta_slice_blocks(uint32_t K) { return (K + 255) / 256; }
 int launch_theta_slice(hipStream_t stream, const ThetaJob *jobs_dev, uint32_t njobs, uint32_t K, uint32_t kpad,
                        const uint32_t *cnt, const uint8_t *slots, uint64_t key, uint64_t sweep,

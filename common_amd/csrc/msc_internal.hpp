@@ -254,6 +254,17 @@ struct SliceCoord {
   uint32_t coord, prior, partner;   // msc_slice_coord, as validated by msc_hp_slice
   float width, prior_a, prior_b;
 };
+// msc_chains_hp_slice: what is per chain of the ensemble's slice step (k_hp_slice_chains) and of the rebuild of the score
+// and CRP tables that follows it (k_chains_prepare, kernels_score.hip)
+struct HpChain {
+  const FeatDesc *feats;     // the chain's state: descriptors, group counts, CRP terms
+  const uint32_t *cnt;
+  const uint8_t *slots;      // the chain's mask of counted slots or null (the non-empty ones)
+  float *crp;
+  uint64_t key;              // the chain's Philox key of the slice step (seed ^ kSliceKey)
+  float alpha;               // alpha at the call; k_hp_slice_chains leaves the installed one here for the rebuild
+  uint32_t pad;
+};
 // msc_theta_slice: one bbnc feature of the call (a row of workgroups, one lane a slot)
 struct ThetaJob {
   const uint32_t *raw_u32;   // heads, tails

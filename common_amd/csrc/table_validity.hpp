@@ -25,8 +25,8 @@
 //   additive_rewritten()       .       .           .          .                  .       0        msc_state_reduce_unpack
 //   committed()                all 1   .           all 0      .                  0       0        commit, ensure_raw
 //   committed_and_prepared()   all 1   .           all 1      .                  1       0        commit_and_prepare
-//   prepared()                 .       .           all 1      .                  .       .        ensure_derived
-//   crp_prepared()             .       .           .          .                  1       .        ensure_crp
+//   prepared()                 .       .           all 1      .                  .       .        ensure_derived, msc_chains_hp_slice
+//   crp_prepared()             .       .           .          .                  1       .        ensure_crp, msc_chains_hp_slice
 //   kept_current()             all 1   all 1       all 1      1                  1       0        msc_entity_op's kernel,
 //                                                                                                 msc_sweep_sequential, msc_chains_sweep
 //   step_began()               .       .           .          .                  .       0        msc_sweep_step (a replayed graph

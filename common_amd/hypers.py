@@ -17,6 +17,7 @@ one kernel, one host synchronisation per step):
   slice_coords(desc, feature, hparams)            one feature's msc_slice_coord entries: {key or tuple of keys: (prior,
                                                    width)}, default desc.default_hyperpriors() with width 1.0
   FeatureHpSlice(state, descs, hparams, cparam)   the entries of a state's features (and alpha), .step(seed, sweep)
+  EnsembleHpSlice(ens, descs, hparams, cparam)    the same for a ChainEnsemble: every chain's step in one launch
 
 A sharded sweep (common_amd.dist.ShardedSweep) calls .step after commit_reduce: every rank holds the same tables and
 draws with the same seed, so every rank installs the same points without exchanging anything.
@@ -175,6 +176,38 @@ def slice_coords(desc, feature, hparams=None):
     return out
 
 
+def _slice_entries(features, descs, hparams=None, cparam=None):
+    """what FeatureHpSlice and EnsembleHpSlice build from their arguments -> (the entries of every feature in feature
+    order, then alpha's; the features that have entries; whether alpha has one).  features: the (family, dim) list of
+    the state or ensemble."""
+    if len(descs) != len(features):
+        raise ValueError("one model descriptor per state feature expected")
+    coords, sliced = [], []
+    for f, desc in enumerate(descs):
+        hp = None
+        if hparams is not None:
+            hp = hparams.get(f) if isinstance(hparams, dict) else hparams[f]
+        cs = slice_coords(desc, f, hp)
+        if not cs:
+            continue
+        if (desc.family, desc.dim) != tuple(features[f]):
+            raise ValueError("feature %d: descriptor does not match the state's feature" % f)
+        coords += cs
+        sliced.append(f)
+    has_alpha = False
+    if cparam is not None:
+        if set(cparam) != {"alpha"}:
+            raise ValueError("cparam takes one key, 'alpha'")
+        fn, w = cparam["alpha"]
+        kind, a, b = slice_prior(fn)
+        if kind == L.PRIOR_NONINF_BETA:
+            raise ValueError("alpha has no partner for the noninformative beta prior")
+        coords.append({"feature": "alpha", "coord": 0, "width": float(w), "prior": kind, "a": a, "b": b,
+                       "partner": 0})
+        has_alpha = True
+    return coords, sliced, has_alpha
+
+
 class FeatureHpSlice(object):
     """Slice steps over the hyper-parameters of a state's features (and, optionally, alpha): downstream's `hp` kernel.
 
@@ -184,32 +217,8 @@ class FeatureHpSlice(object):
     cparam: None or {"alpha": (prior, width)}."""
 
     def __init__(self, state, descs, hparams=None, cparam=None):
-        if len(descs) != len(state.features):
-            raise ValueError("one model descriptor per state feature expected")
         self.state, self.descs = state, list(descs)
-        self.coords, self.features = [], []
-        for f, desc in enumerate(descs):
-            hp = None
-            if hparams is not None:
-                hp = hparams.get(f) if isinstance(hparams, dict) else hparams[f]
-            cs = slice_coords(desc, f, hp)
-            if not cs:
-                continue
-            if (desc.family, desc.dim) != tuple(state.features[f]):
-                raise ValueError("feature %d: descriptor does not match the state's feature" % f)
-            self.coords += cs
-            self.features.append(f)
-        self.has_alpha = False
-        if cparam is not None:
-            if set(cparam) != {"alpha"}:
-                raise ValueError("cparam takes one key, 'alpha'")
-            fn, w = cparam["alpha"]
-            kind, a, b = slice_prior(fn)
-            if kind == L.PRIOR_NONINF_BETA:
-                raise ValueError("alpha has no partner for the noninformative beta prior")
-            self.coords.append({"feature": "alpha", "coord": 0, "width": float(w), "prior": kind, "a": a, "b": b,
-                                "partner": 0})
-            self.has_alpha = True
+        self.coords, self.features, self.has_alpha = _slice_entries(state.features, descs, hparams, cparam)
         self.last_evals = None
 
     def step(self, seed, sweep, slots=None):
@@ -221,4 +230,34 @@ class FeatureHpSlice(object):
         out = {f: unpack_hp(self.descs[f].family, self.state.get_hp(f), self.descs[f].dim) for f in self.features}
         if self.has_alpha:
             out["alpha"] = float(values[-1])
+        return out
+
+
+class EnsembleHpSlice(object):
+    """FeatureHpSlice for a ChainEnsemble: the same entries, built the same way from the same arguments (one list for all
+    chains), stepped on every chain in one launch (ChainEnsemble.hp_slice, msc_chains_hp_slice).  Constructing it touches
+    no device."""
+
+    def __init__(self, ens, descs, hparams=None, cparam=None):
+        self.ens, self.descs = ens, list(descs)
+        self.coords, self.features, self.has_alpha = _slice_entries(ens.features, descs, hparams, cparam)
+        self.last_evals = self.last_values = None
+
+    def step(self, seed, sweep, slots=None):
+        """one slice step of every coordinate of every chain -> a list of nchains dicts {feature: the chain's hp dict
+        now, "alpha": its alpha now (if sliced)}, built from the returned values and each state's host copy of its hp (no
+        device read per chain); .last_values float32 and .last_evals uint32, [nchains, n], are what the step installed
+        and the evaluations each update took"""
+        nchains = self.ens.nchains
+        if not self.coords:
+            self.last_values = np.zeros((nchains, 0), np.float32)
+            self.last_evals = np.zeros((nchains, 0), np.uint32)
+            return [{} for _ in range(nchains)]
+        self.last_values, self.last_evals = self.ens.hp_slice(self.coords, seed, sweep, slots=slots)
+        out = []
+        for c, st in enumerate(self.ens.states):
+            d = {f: unpack_hp(self.descs[f].family, st.get_hp(f), self.descs[f].dim) for f in self.features}
+            if self.has_alpha:
+                d["alpha"] = float(self.last_values[c, -1])
+            out.append(d)
         return out

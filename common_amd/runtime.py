@@ -736,6 +736,18 @@ class State(object):
     _PRIORS = {"flat": L.PRIOR_FLAT, "exponential": L.PRIOR_EXPONENTIAL, "normal": L.PRIOR_NORMAL,
                "noninf_beta": L.PRIOR_NONINF_BETA}
 
+    @classmethod
+    def _slice_coord_array(cls, coords):
+        """hp_slice's entry dicts -> the msc_slice_coord array the library takes (ChainEnsemble.hp_slice shares it)"""
+        arr = (L.SliceCoord * max(1, len(coords)))()
+        for i, c in enumerate(coords):
+            f = c["feature"]
+            prior = c.get("prior", L.PRIOR_FLAT)
+            arr[i] = L.SliceCoord(L.HP_CLUSTER if f in ("alpha", L.HP_CLUSTER) else int(f), int(c.get("coord", 0)),
+                                  float(c["width"]), cls._PRIORS.get(prior, prior) if isinstance(prior, str) else
+                                  int(prior), float(c.get("a", 0.0)), float(c.get("b", 0.0)), int(c.get("partner", 0)))
+        return arr
+
     def hp_slice(self, coords, seed, sweep, slots=None):
         """one slice step of each entry of `coords` (msc_hp_slice; one host synchronisation).  An entry is a dict with
         "feature" (a state feature, or "alpha" / L.HP_CLUSTER), "coord" (float index in the hp block; 0 for alpha),
@@ -744,13 +756,7 @@ class State(object):
         the non-empty ones).  -> (installed values float32, evaluations uint32), one per entry"""
         self._drop_subsets()
         coords = list(coords)
-        arr = (L.SliceCoord * max(1, len(coords)))()
-        for i, c in enumerate(coords):
-            f = c["feature"]
-            prior = c.get("prior", L.PRIOR_FLAT)
-            arr[i] = L.SliceCoord(L.HP_CLUSTER if f in ("alpha", L.HP_CLUSTER) else int(f), int(c.get("coord", 0)),
-                                  float(c["width"]), self._PRIORS.get(prior, prior) if isinstance(prior, str) else
-                                  int(prior), float(c.get("a", 0.0)), float(c.get("b", 0.0)), int(c.get("partner", 0)))
+        arr = self._slice_coord_array(coords)
         values = np.zeros(len(coords), dtype=np.float32)
         evals = np.zeros(len(coords), dtype=np.uint32)
         L.check(self.ctx.lib.msc_hp_slice(self._h, arr, len(coords), self._slots(slots), int(seed), int(sweep),

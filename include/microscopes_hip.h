@@ -758,6 +758,40 @@ int msc_hp_slice(msc_state *st, const msc_slice_coord *coords, uint32_t n, const
  */
 int msc_theta_slice(msc_state *st, const uint32_t *features, const float *widths, uint32_t n, const uint8_t *slots_dev,
                     uint64_t seed, uint64_t sweep, uint64_t *evals_host);
+/*
+ * The slice step of EVERY chain of an ensemble (msc_chains_create, above; declared here because it takes
+ * msc_slice_coord) in one launch: the other half of an iteration of the reference's runner (an assignment sweep, then
+ * the hp kernel, on every chain).  msc_chains_hp_slice leaves chain c exactly where
+ *   msc_hp_slice(state c, coords, n, the chain's mask, host_seeds[c], sweep, ...)
+ * would: the same counters (target, entry, sweep, b) under the chain's key host_seeds[c] ^ the slice key, the same
+ * arithmetic in the same order (one kernel body serves both calls), so the same bits in the installed values, in every
+ * hp block and in alpha.  A grid of (targets x chains) workgroups takes the step; a second launch then rebuilds, for
+ * every chain, what the step made stale -- the score tables of every feature from the new hp blocks and the CRP table
+ * from the new alpha -- with the bits the per-state rebuild (the next call that scores that state) would have written,
+ * so the next msc_chains_sweep / msc_chains_visit launches nothing before its kernel.
+ *   coords, n     ONE list for all chains (their feature lists are equal by msc_chains_create); msc_hp_slice's entries
+ *                 and msc_hp_slice's checks, made once, before anything is launched;
+ *   slots_dev     nullable; uint8 masks of the counted slots on the device.  ld_slots == 0: one mask of ngroups bytes
+ *                 for all chains; ld_slots >= ngroups: chain c's at slots_dev + c * ld_slots.  Null: every chain counts
+ *                 its non-empty slots;
+ *   host_seeds    uint64[nchains] on the host, read before the call returns;
+ *   values_host, evals_host   nullable; [nchains][n] on the host, each chain's row in the caller's entry order: the
+ *                 installed value and the evaluations of the target, as msc_hp_slice returns them.
+ * ONE host synchronisation for the whole call, whatever the number of chains.  The tables of the call (per-chain
+ * pointers and keys, per-chain targets, the entries) go through a device buffer the handle owns; it only grows, after a
+ * wait for the stream, and the host image it is copied from is rewritten only by the next call, every return past the
+ * copy having waited for the stream.  Every member's reference fields are made current before the launch.
+ * A target that is not finite at its current value (msc_hp_slice's case): that entry of that chain keeps its value,
+ * every other update of every chain is installed and book-kept, the rebuild runs, and the call returns MSC_EINVAL with
+ * a message that names the chain, the feature and the coordinate (the lowest such chain's last such entry).
+ * Errors, with nothing launched and nothing changed: MSC_EINVAL for a null argument, n == 0, ld_slots neither 0 nor >=
+ * ngroups, whatever msc_hp_slice refuses of an entry, or a member between msc_sweep_step_begin and
+ * msc_state_commit_reduce (the index is named); MSC_EUNSUPPORTED for a coordinate msc_hp_slice does not slice (dd
+ * alphas, bnb r); MSC_EDEVICE when an earlier kernel reported an error.
+ */
+int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
+                        uint64_t ld_slots, const uint64_t *host_seeds, uint64_t sweep, float *values_host,
+                        uint32_t *evals_host);
 
 /* ---- posterior predictive sampling (group::sample_value, base.hpp:29) ---- */
 #define MSC_PRED_MASKED_ONLY 0x1u /* draw masked entries only; observed ones are copied */

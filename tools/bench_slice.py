@@ -8,6 +8,17 @@
 Prints one JSON line.
 
     python tools/bench_slice.py [--steps 50] [--warmup 5] [--sample 200]
+
+With --chains the ensemble's step instead (ChainEnsemble.hp_slice, msc_chains_hp_slice), on one nich column and on the
+C3 mix at K = 256, states accumulated from --rows rows, for every ensemble size of the list.  Timed warm, with device
+events around the synchronous call, the two routes alternated on the SAME ensemble, median of --repeats:
+  ensemble   one ens.hp_slice over every default coordinate plus alpha;
+  loop       the route it replaces: ens.states[c].hp_slice for every chain (a launch, two copies, a wait each);
+  sweep      the first ens.sweep of ONE row after each, which carries the rebuild of the score and CRP tables the step
+             made stale (after the ensemble call they are current already).
+One JSON line per (mix, chains), printed and appended to --out (default profiles/chains_hp.txt).
+
+    python tools/bench_slice.py --chains 1,16,64,256 [--repeats 5] [--rows 4096] [--out profiles/chains_hp.txt]
 """
 import argparse
 import json
@@ -39,13 +50,75 @@ def timed(fn, steps, warmup):
     return ms
 
 
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def chains_case(ctx, name, descs, K, rows, nchains, repeats):
+    from common_amd.chains import chain_seeds
+    from tools.bench_configs import make_columns
+    spec = [(d.family, d.dim) for d in descs]
+    cols, z = make_columns(ctx, spec, rows, K, seed=73)
+    view = common_amd.DataView.from_tensors(ctx, cols)
+    ens = common_amd.ChainEnsemble(ctx, spec, K, nchains, alpha=1.0)
+    ens.assign(view, z)
+    sl = hypers.EnsembleHpSlice(ens, descs, cparam={"alpha": (sf.log_exponential(1.0), 1.0)})
+    keys = chain_seeds(7, nchains)
+
+    def loop(s):
+        for c, st in enumerate(ens.states):
+            st.hp_slice(sl.coords, keys[c], s)
+    t = dict(ensemble=[], sweep_after_ensemble=[], loop=[], sweep_after_loop=[])
+    evals = []
+    for r in range(repeats + 1):                            # (the first round is the warm-up)
+        torch.cuda.synchronize()
+        t["ensemble"].append(event_ms(lambda: evals.append(int(ens.hp_slice(sl.coords, 7, sweep=2 * r)[1].sum()))))
+        t["sweep_after_ensemble"].append(event_ms(lambda: ens.sweep(view, 1, 11, sweep=2 * r, nrows=1)))
+        t["loop"].append(event_ms(lambda: loop(2 * r + 1)))
+        t["sweep_after_loop"].append(event_ms(lambda: ens.sweep(view, 1, 11, sweep=2 * r + 1, nrows=1)))
+    ens.close()
+    rec = dict(what="chains_hp", mix=name, K=K, rows=rows, features=len(descs), chains=nchains, updates_per_chain=len(sl.coords),
+               evaluations_per_update_mean=round(float(np.mean(evals[1:])) / (nchains * len(sl.coords)), 2), repeats=repeats)
+    for k, v in t.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v[1:]]
+        rec[k + "_ms_median"] = round(float(np.median(v[1:])), 3)
+    rec["loop_over_ensemble"] = round(rec["loop_ms_median"] / rec["ensemble_ms_median"], 2)
+    rec["ensemble_faster_than_loop"] = bool(rec["ensemble_ms_median"] < rec["loop_ms_median"])
+    return rec
+
+
+def chains_main(args):
+    from common_amd import models
+    ctx = common_amd.Context(0)
+    sizes = [int(c) for c in args.chains.split(",")]
+    mixes = [("nich1", [models.nich]), ("c3", [models.bb, models.gp, models.dd(32), models.nich] * 16)]
+    for name, descs in mixes:
+        for nchains in sizes:
+            line = json.dumps(chains_case(ctx, name, descs, args.K, args.rows, nchains, args.repeats))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as fh:
+                    fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", default=None, help="ensemble sizes, e.g. 1,16,64,256: time the ensemble's step")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--rows", type=int, default=4096)
+    ap.add_argument("--out", default=os.path.join("profiles", "chains_hp.txt"))
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sample", type=int, default=200)
     ap.add_argument("--K", type=int, default=256)
     args = ap.parse_args()
+    if args.chains is not None:
+        return chains_main(args)
     ctx = common_amd.Context(0)
     rng = np.random.default_rng(1)
     K = args.K
