@@ -87,6 +87,27 @@ MSC_DEV double lgamma_pos(double x) {
   const double tail = r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0 - r2 * (1.0 / 1188.0)))));
   return (x - 0.5) * log(x) - x + kHalfLog2Pi + tail - shift;
 }
+// ---- differences of lgamma at LARGE arguments ---------------------------------------------------------------------
+// lgamma(x + w) - lgamma(x) is O(w ln x), but lgamma(x) itself is x ln x: taken as a difference of two evaluations the
+// result carries eps x ln x whatever its own size -- in double 5e-9 at x = 2^20, 6e-8 at 1e7, 7e-6 at 1e9, 4e-5 at 4e9
+// (measured against a 60-digit evaluation): a group of 1e7 rows already breaks the 1e-6 contract.
+// From kLgammaBig on the difference is therefore taken of the Stirling series term by term,
+//   lgamma(x + w) - lgamma(x) = (x + w - 1/2) log1p(w / x) + w (ln x - 1) + S(x + w) - S(x),
+//   S(x + w) - S(x) = -w / (12 x (x + w))       (the next term of the series differs by < 1e-21 there),
+// in which no term is larger than the result times ~ln x.  Below kLgammaBig the callers keep their old expressions --
+// and with them every bit of every result they ever produced (the error there is at most the 5e-9 above).
+// (A real call for the reason log_factorial_big gives: the branch is rare and its constants would be hoisted.  Every
+// such function is a LEAF -- the ones that need the series inline lgamma_rise_series -- because a call from within a
+// call costs the kernel a stack frame, i.e. scratch.)
+constexpr double kLgammaBig = 1048576.0;   // 2^20
+MSC_DEV double lgamma_rise_series(double x, double w) {
+  return (x + w - 0.5) * log1p(w / x) + w * (log(x) - 1.0) - w / (12.0 * x * (x + w));
+}
+static __device__ __attribute__((noinline)) double lgamma_rise_big(double x, double w) { return lgamma_rise_series(x, w); }
+// lgamma(x + w) - lgamma(x), x > 0, w >= 0
+MSC_DEV double lgamma_rise(double x, double w) {
+  return x >= kLgammaBig ? lgamma_rise_big(x, w) : lgamma(x + w) - lgamma(x);
+}
 // lgamma(a) - lgamma(a - v) for an integer 0 <= v <= a - (something positive): the log of a falling product
 // for the few-factor case, two Stirling evaluations otherwise
 MSC_DEV double lgamma_drop(double a, uint32_t v) {
@@ -186,13 +207,27 @@ MSC_DEV double dd_score_data(const float *hp, uint32_t dim, const uint32_t *coun
 //    e(a) comes from the prepare step (hi/lo floats), e(v) and ln(2 pi v) once per row.
 enum { GP_NSE_HI = 0, GP_NSE_LO = 1, GP_T0 = 2 };   // rows GP_T0 + v, v < FeatDesc::vcap: the exact table
 
+// Double cannot subtract them either once a group is large: lgamma(a + v) - lgamma(a) carries eps a ln a and
+// a ln b - (a + v) ln(1 + b) as much again -- 5.6e-8 at a = 1e7 (1e5 rows of mean 100), 5.7e-7 at 1e8, 7.2e-6 at 1e9
+// (1e7 rows), 3.9e-5 at 4e9 (1e8 rows of mean 40), against a 60-digit evaluation.  From a = kLgammaBig on the first
+// pair is lgamma_rise_big and the second is rewritten as -a log1p(1 / b) - v log1p(b) (a / b is the group's mean): every
+// term is then of the size of the result.  stirlerr(a), which Loader's form takes from the prepare step, is the same
+// kind of difference: there it is the Stirling tail itself.
+static __device__ __attribute__((noinline)) double gp_score_big(double a, double b, double v) {
+  return lgamma_rise_series(a, v) - lgamma(v + 1.0) - a * log1p(1.0 / b) - v * log1p(b);
+}
 MSC_DEV double gp_score_exact(double a, double b, double v) {
+  if (a >= kLgammaBig) return gp_score_big(a, b, v);
   return lgamma(a + v) - lgamma(a) - lgamma(v + 1.0) + a * log(b) - (a + v) * log1p(b);
+}
+static __device__ __attribute__((noinline)) double stirlerr_big(double a) {   // a >= kLgammaBig: two terms are exact to 1e-33
+  const double r = 1.0 / a;
+  return r * (1.0 / 12.0 - r * r * (1.0 / 360.0));
 }
 MSC_DEV void gp_prepare_consts(const float *hp, uint32_t count, uint32_t sum, float &nse_hi, float &nse_lo) {
   const double a = (double)hp[0] + (double)sum;
   (void)count;
-  const double stirlerr_a = lgamma(a + 1.0) - ((a + 0.5) * log(a) - a + kHalfLog2Pi);
+  const double stirlerr_a = a >= kLgammaBig ? stirlerr_big(a) : lgamma(a + 1.0) - ((a + 0.5) * log(a) - a + kHalfLog2Pi);
   split_hi_lo(-stirlerr_a, nse_hi, nse_lo);
 }
 MSC_DEV float gp_prepare_table(const float *hp, uint32_t count, uint32_t sum, uint32_t v) {
@@ -227,7 +262,17 @@ MSC_DEV double gp_score_data(const float *hp, uint32_t count, uint32_t sum, doub
 //            + lgamma(a+r) + lgamma(b+v) - lgamma(a+r+b+v)
 // Same evaluation scheme as gp: an exact per-group table (rows GP_T0 + v) for the counts the
 // bound column holds, and the formula in double for counts beyond the table.
+// Past a + b = kLgammaBig (the expression above, in double: 1.2e-7 off at 1e7 rows, 1.8e-6 at 1e8) the six large terms pair up into
+// three differences, each taken by lgamma_rise: B(a + r, b + v) / B(a, b) = rise(a, r) + rise(b, v) - rise(a + b, r + v).
+static __device__ __attribute__((noinline)) double bnb_score_big(double a, double b, double r, double v) {
+  double s = lgamma(r + v) - lgamma(v + 1.0) - lgamma(r);
+  s += a >= kLgammaBig ? lgamma_rise_series(a, r) : lgamma(a + r) - lgamma(a);
+  s += b >= kLgammaBig ? lgamma_rise_series(b, v) : lgamma(b + v) - lgamma(b);
+  const double ab = a + b;
+  return s - (ab >= kLgammaBig ? lgamma_rise_series(ab, r + v) : lgamma(ab + (r + v)) - lgamma(ab));
+}
 MSC_DEV double bnb_score_exact(double a, double b, double r, double v) {
+  if (a + b >= kLgammaBig) return bnb_score_big(a, b, r, v);
   return lgamma(r + v) - lgamma(v + 1.0) - lgamma(r) + lgamma(a + b) - lgamma(a) - lgamma(b) +
          lgamma(a + r) + lgamma(b + v) - lgamma(a + r + b + v);
 }
@@ -261,11 +306,13 @@ MSC_DEV void dm_split(double t, float &hi, float &lo) {
   hi = (float)h;
   lo = (float)(t - h);
 }
+// (lgamma_rise: the two lgamma of a category of 1e8 counts cancel at 2e9, not at the term's size -- 4.4e-7 off at
+// n = 1e8, 6.1e-6 at 1e9 per term, and a row sums dim + 1 of them)
 MSC_DEV double dm_cat_term(double alpha_i, double n_i, double x) {
-  return lgamma(alpha_i + n_i + x) - lgamma(alpha_i + n_i) - lgamma(x + 1.0);
+  return lgamma_rise(alpha_i + n_i, x) - lgamma(x + 1.0);
 }
 MSC_DEV double dm_sum_term(double A, double N, double X) {
-  return lgamma(A + N) - lgamma(A + N + X) + lgamma(X + 1.0);
+  return lgamma(X + 1.0) - lgamma_rise(A + N, X);
 }
 // score of the vector at `x` (dim int32) against counts read with stride `cstride` (in u32),
 // each lowered by the vector itself when loo
@@ -324,7 +371,7 @@ MSC_DEV NichPost nich_posterior(const float *hp, double n, double mean, double c
 }
 MSC_DEV void nich_coeffs(const NichPost &p, double &c0, double &c1, double &c2) {
   const double lambda = p.kappa / ((p.kappa + 1.0) * p.sigmasq);
-  c0 = lgamma(0.5 * p.nu + 0.5) - lgamma(0.5 * p.nu) + 0.5 * log(lambda / (kPi * p.nu));
+  c0 = lgamma_rise(0.5 * p.nu, 0.5) + 0.5 * log(lambda / (kPi * p.nu));   // (2.5e-7 off at 1e8 rows as two lgamma)
   c1 = 0.5 * p.nu + 0.5;
   c2 = lambda / p.nu;
 }
@@ -464,7 +511,9 @@ MSC_DEV void nich_loo_prepare(const float *hp, uint32_t count, float mean_f, flo
   out[NLOO_INV_N * stride] = count <= 1 ? 0.0 : 1.0 / n;
   out[NLOO_IKN * stride] = 1.0 / kn;
   out[NLOO_INV_NUN * stride] = 1.0 / nun;
-  const float c0 = (float)(lgamma_pos(0.5 * nun + 0.5) - lgamma_pos(0.5 * nun) + 0.5 * log(kfac / (kPi * nun)));
+  const double hn = 0.5 * nun;
+  const float c0 = (float)((hn >= kLgammaBig ? lgamma_rise_big(hn, 0.5) : lgamma_pos(0.5 * nun + 0.5) - lgamma_pos(0.5 * nun)) +
+                           0.5 * log(kfac / (kPi * nun)));
   const float c1 = (float)(0.5 * nun + 0.5);
   out[NLOO_C01 * stride] = __hiloint2double(__float_as_int(c1), __float_as_int(c0));
 }
@@ -507,8 +556,25 @@ MSC_DEV float nich_loo_tab_sweep(const float *hp, const double *t, size_t stride
 }
 // gp leave-one-out: posterior (a - v, b - 1) of the group's own (a, b); a' + v = a, so
 //   score = [lgamma(a) - lgamma(a - v)] - log v! + (a - v) ln b' - a ln(1 + b')
+// (from a = kLgammaBig on, as gp_score_big: the falling product's log, or the Stirling series' difference where a - v is
+// large too, and (a - v) ln b' - a ln(1 + b') = -(a - v) log1p(1 / b') - v log1p(b').  One leaf behind one branch: the
+// rows' path is the old code.)
+static __device__ __attribute__((noinline)) double gp_loo_big(double a, double b1, uint32_t v) {
+  const double x = (double)v, lo = a - x;
+  double drop;
+  if (v <= 12u) {
+    double prod = 1.0;
+    for (uint32_t i = 1; i <= v; i++) prod *= a - (double)i;
+    drop = log(prod);
+  } else {
+    drop = lo >= kLgammaBig ? lgamma_rise_series(lo, x) : lgamma_pos(a) - lgamma_pos(lo);
+  }
+  const double lf = v < 32u ? kLogFactorial[v] : lgamma_pos(x + 1.0);
+  return drop - lf - lo * log1p(1.0 / b1) - x * log1p(b1);
+}
 MSC_DEV double gp_loo(const float *hp, uint32_t count, uint32_t sum, uint32_t v) {
   const double a = (double)hp[0] + (double)sum, b1 = (double)hp[1] + (double)count - 1.0;
+  if (a >= kLgammaBig) return gp_loo_big(a, b1, v);
   return lgamma_drop(a, v) - log_factorial(v) + (a - (double)v) * log(b1) - a * log1p(b1);
 }
 MSC_DEV double nich_score_data(const float *hp, uint32_t count, float mean, float ctv) {

@@ -152,13 +152,13 @@ __global__ __launch_bounds__(64) void k_niw_prepare(const FeatDesc *__restrict__
     const double s = (kn + 1.0) / (kn * dof);
     const double logdet_sigma = logdet + dd * log(s);
     fd.tab[(size_t)NIW_C0 * kpad + k] =
-        (float)(lgamma(0.5 * (dof + dd)) - lgamma(0.5 * dof) - 0.5 * dd * log(dof * kPi) - 0.5 * logdet_sigma);
+        (float)(lgamma_rise(0.5 * dof, 0.5 * dd) - 0.5 * dd * log(dof * kPi) - 0.5 * logdet_sigma);
     fd.tab[(size_t)NIW_C1 * kpad + k] = (float)(0.5 * (dof + dd));
     split_hi_lo(logdet, fd.tab[(size_t)NIW_LOGDET_HI * kpad + k], fd.tab[(size_t)NIW_LOGDET_LO * kpad + k]);
     double a_loo = 0, b_loo = 0, c_loo = 0;
     if (n >= 1.0) {
       const double k1 = kn - 1.0, dof1 = dof - 1.0;
-      a_loo = lgamma(0.5 * (dof1 + dd)) - lgamma(0.5 * dof1) - 0.5 * dd * log(dof1 * kPi) - 0.5 * logdet -
+      a_loo = lgamma_rise(0.5 * dof1, 0.5 * dd) - 0.5 * dd * log(dof1 * kPi) - 0.5 * logdet -
               0.5 * dd * log(kn / (k1 * dof1));
       b_loo = 0.5 * (dof1 + dd - 1.0);
       c_loo = (kn + 1.0) / k1;
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(64) void k_niw_prepare(const FeatDesc *__restrict__
     fd.tab[(size_t)NIW_B_LOO * kpad + k] = (float)b_loo;
     fd.tab[(size_t)NIW_C_LOO * kpad + k] = (float)c_loo;
     double *c64 = fd.niw_c64 + (size_t)k * 8;     // the same constants, unrounded, for k_score_niw64
-    c64[0] = lgamma(0.5 * (dof + dd)) - lgamma(0.5 * dof) - 0.5 * dd * log(dof * kPi) - 0.5 * logdet_sigma;
+    c64[0] = lgamma_rise(0.5 * dof, 0.5 * dd) - 0.5 * dd * log(dof * kPi) - 0.5 * logdet_sigma;
     c64[1] = 0.5 * (dof + dd);
     c64[2] = a_loo; c64[3] = b_loo; c64[4] = c_loo;
   }

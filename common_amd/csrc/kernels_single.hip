@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64) void k_value_op(unsigned char *__restrict__ mb)
           }
           q /= s;                                     // Sigma = s * Psi_n
           const double dd = d;
-          score = lgamma(0.5 * (dof + dd)) - lgamma(0.5 * dof) - 0.5 * dd * log(dof * kPi) -
+          score = lgamma_rise(0.5 * dof, 0.5 * dd) - 0.5 * dd * log(dof * kPi) -
                   0.5 * (ldn + dd * log(s)) - 0.5 * (dof + dd) * log1p(q / dof);
         }
       } else {
