@@ -154,6 +154,9 @@ _SIGS = {
                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
     # (ch, host_ancestors, z_dev, ld_z, nrows)
     "msc_chains_clone": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.c_uint64]),
+    # (ch, view, cols, row0, nrows, features, nfeatures, logw_dev, flags, mix_dev, chain_logp_dev, ld_logp)
+    "msc_chains_score_marginal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32),
+                                            C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
     # (ch, coords, n, slots_dev, ld_slots, host_seeds, sweep, values_host, evals_host)
     "msc_chains_hp_slice": (C.c_int, [C.c_void_p, C.POINTER(SliceCoord), C.c_uint32, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p, C.c_void_p]),

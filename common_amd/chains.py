@@ -370,6 +370,82 @@ class ChainEnsemble(object):
         return S.SMCResult(log_evidence=log_evidence, log_weights=logw, weights=S.normalised_weights(logw), ess=ess_list,
                            resampled_at=resampled_at, ancestors=ancestors, truncated=truncated)
 
+    # the posterior-averaged row predictive density ---------------------------------
+    def _feature_list(self, what, feats):
+        """a sorted list of distinct feature indices of the states"""
+        out = sorted(int(f) for f in feats)
+        for i, f in enumerate(out):
+            if not 0 <= f < len(self.features):
+                raise ValueError("%s: feature %d outside the states (%d features)" % (what, f, len(self.features)))
+            if i and f == out[i - 1]:
+                raise ValueError("%s names feature %d twice" % (what, f))
+        return out
+
+    def predictive_logp(self, view, weights=None, features=None, given=None, per_chain=False, row0=0, nrows=None,
+                        cols=None, out=None):
+        """log p(x_r | data) ~ log sum_c w_c p(x_r | state_c) of rows [row0, row0 + nrows) of the view, averaged over
+        the chains in one pass (msc_chains_score_marginal; asynchronous) -> mix, a float32 device tensor [nrows]; with
+        per_chain -> (mix, chain_logp), chain_logp float32 [nchains, nrows] holding what ens.states[c].predictive_logp
+        defines for each chain.  The sum over the chains is taken in double in a fixed order: a call repeats its bits,
+        and a call over a sub-range gives the whole call's.
+        weights: None (equal), or float64 [nchains] LOG weights on the host or the device, normalised or not; -inf
+        leaves a chain out.  ens.logw after ens.smc(...) is the intended argument.
+        features=[f, ...]: only these features' entries are scored (default: all).
+        given=[f, ...]: -> mix(the selected features) - mix(given), the model-averaged CONDITIONAL log density of the
+        other selected entries given those of `given` (two calls of the entry point).  This is the ratio of two averages
+        over the chains -- log (sum_c w_c p_c(all)) / (sum_c w_c p_c(given)) -- not an average of per-chain ratios:
+        the chains that explain the given entries well count for more, as they should.  chain_logp stays the per-chain
+        log density of ALL selected entries.  given must be a subset of the selected features.
+        out: a float32 device tensor of at least nrows entries that receives mix."""
+        self._check_open()
+        dev = self.ctx.torch_device
+        row0, n = A.rows(int(view.nrows), row0, nrows)
+        if row0 + n > view.nrows:                      # (outputs are sized before the call: not left to the library)
+            raise ValueError("rows [%d, %d) outside the view (%d rows)" % (row0, row0 + n, view.nrows))
+        sel = None
+        if features is not None:
+            sel = self._feature_list("features", features)
+            if not sel:
+                raise ValueError("features must name at least one feature (None: all)")
+        giv = None
+        if given is not None:
+            giv = self._feature_list("given", given)
+            if not set(giv) <= set(range(len(self.features)) if sel is None else sel):
+                raise ValueError("given must be a subset of the selected features")
+        w = None
+        if weights is not None:
+            w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
+            if w.dtype != torch.float64 or tuple(w.shape) != (self.nchains,):
+                raise ValueError("weights must be float64 [nchains = %d] log weights" % self.nchains)
+        if out is not None:
+            A.flat(out, torch.float32, n, dev, "out")
+        # every argument is checked: from here on the device is used
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=dev)
+        op = A.ptr(out)
+        wp = None
+        if w is not None:
+            w = w.to(dev).contiguous()
+            wp = A.ptr(w)
+        logp = torch.empty((self.nchains, n), dtype=torch.float32, device=dev) if per_chain else None
+        for st in self.states:
+            st._bound_view = view        # (the library keeps no reference to a view: the states do, for the last one bound)
+        cp = self.states[0]._cols(cols)
+
+        def call(feats, mix_ptr, logp_t):
+            fa = (C.c_uint32 * len(feats))(*feats) if feats else None
+            L.check(self.ctx.lib.msc_chains_score_marginal(
+                self._h, view._h, cp, row0, n, fa, len(feats) if feats else 0, wp, 0, mix_ptr,
+                A.ptr(logp_t) if logp_t is not None and logp_t.numel() else None, n))
+
+        if n:
+            call(sel, op, logp)
+            if giv:
+                denom = torch.empty(n, dtype=torch.float32, device=dev)
+                call(giv, A.ptr(denom), None)
+                out[:n] -= denom
+        return (out, logp) if per_chain else out
+
     # lifetime -----------------------------------------------------------------
     def _check_open(self):
         if not getattr(self, "_h", None):

@@ -1,5 +1,6 @@
 // chains.cpp -- the sequential collapsed Gibbs sweep and the ensembles of such chains (kernels_seq.hip):
-// msc_sweep_sequential and msc_chains_*.  Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
+// msc_sweep_sequential and msc_chains_*, the ensemble's row predictive density among them
+// (kernels_chains_marginal.hip).  Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
 #include <algorithm>
 #include <memory>
 #include <new>
@@ -107,8 +108,18 @@ struct msc_chains {
   // stream, so no copy is pending when the next call rewrites an image.
   msc::DevBuf<unsigned char> hp_buf;
   std::vector<unsigned char> hp_up, hp_down;
+  // msc_chains_score_marginal: the call's table (MargChain [nchains] | MargFeat [nfeat]), staged through the same two
+  // areas (which hold marg_extra entries beyond nchains for the features' part); the normalised log weights and
+  // log(n + alpha) of every chain; the slices' (M, S) pairs, grown without a wait (the buffer it replaces may still be read)
+  msc::DevBuf<unsigned char> marg_tab;
+  msc::DevBuf<double> marg_w;             // [2 nchains]: lw | norm
+  msc::DevBuf<double> marg_part;
+  msc::Retired retired;
 };
 static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
+// entries of a staging area beyond nchains, for the MargFeat table of nfeat features behind the MargChain table
+static size_t marg_extra(uint32_t nfeat) { return ((size_t)nfeat * sizeof(msc::MargFeat) + sizeof(msc::SeqChain) - 1) / sizeof(msc::SeqChain); }
+static size_t marg_feat_at(uint32_t nchains) { return ((size_t)nchains * sizeof(msc::MargChain) + 15) & ~(size_t)15; }
 
 // the pinned staging area whose turn it is, once no pending copy reads it; chains_staged records the copy out of it
 static int chains_stage(msc_chains *ch, int *area) {
@@ -154,8 +165,10 @@ extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc
   ch->states.assign(states, states + nchains);
   hipError_t e = ch->table_dev.alloc(nchains);
   if (e == hipSuccess) e = ch->pairs_dev.alloc(nchains);
+  if (e == hipSuccess) e = ch->marg_tab.alloc(marg_feat_at(nchains) + (size_t)states[0]->nfeat * sizeof(MargFeat), 16);
+  if (e == hipSuccess) e = ch->marg_w.alloc(2 * (size_t)nchains);
   for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = ch->stage[i].alloc(nchains);
+    e = ch->stage[i].alloc(nchains + marg_extra(states[0]->nfeat));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ch->uploaded[i], hipEventDisableTiming);
   }
   if (e != hipSuccess) {
@@ -441,4 +454,102 @@ extern "C" int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords
     st->valid.crp_prepared();
   }
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// The posterior-averaged row predictive density over the chains (kernels_chains_marginal.hip)
+// ---------------------------------------------------------------------------
+// How the chains are cut over the grid's second dimension.  By the ensemble and view_rows alone (THE SHARD RULE of
+// route_marginal): the slices' parts are merged in slice order, so a call over a sub-range must cut as the whole call does.
+// A view of fewer than four workgroups of 256 rows a compute unit (what its LDS holds) is filled up with slices, at most
+// one a chain.
+static uint32_t route_chains_marginal(const msc_chains *ch) {
+  const uint32_t n = (uint32_t)ch->states.size();
+  const uint64_t blocks = std::max<uint64_t>(1, (view_rows(ch->states[0]) + 255) / 256);
+  const uint64_t want = 4ull * (uint64_t)std::max(1, ch->ctx->num_cus);
+  if (blocks >= want) return 1;
+  const uint32_t slices = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, 1024), (want + blocks - 1) / blocks);
+  const uint32_t per = (n + slices - 1) / slices;
+  return (n + per - 1) / per;
+}
+
+extern "C" int msc_chains_score_marginal(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                         uint64_t nrows, const uint32_t *features, uint32_t nfeatures, const double *logw_dev,
+                                         uint32_t flags, float *mix_dev, float *chain_logp_dev, uint64_t ld_logp) {
+  MSC_REQUIRE(ch && view, "null argument");
+  MSC_REQUIRE(flags == 0, "unknown flags 0x%x", flags);
+  MSC_REQUIRE(mix_dev || chain_logp_dev, "msc_chains_score_marginal: mix_dev and chain_logp_dev are both null");
+  MSC_REQUIRE(!chain_logp_dev || ld_logp >= nrows, "msc_chains_score_marginal: ld_logp %llu < nrows %llu",
+              (unsigned long long)ld_logp, (unsigned long long)nrows);
+  MSC_REQUIRE(nrows < (1ull << 32), "msc_chains_score_marginal takes at most 2^32 - 1 rows per call");
+  const uint32_t n = (uint32_t)ch->states.size();
+  if (n == 0) return MSC_OK;
+  const msc_state *st0 = ch->states[0];
+  const bool all = features == nullptr || nfeatures == 0;
+  if (!all)
+    for (uint32_t i = 0; i < nfeatures; i++) {
+      MSC_REQUIRE(features[i] < st0->nfeat, "msc_chains_score_marginal: feature %u outside the state (%u features)", features[i],
+                  st0->nfeat);
+      MSC_REQUIRE(i == 0 || features[i] > features[i - 1], "msc_chains_score_marginal: the feature list is not strictly "
+                  "ascending at entry %u", i);
+    }
+  for (uint32_t c = 0; c < n; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_score_marginal: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  // one tile plan serves every chain, so every member's exact count tables must have member 0's rows: they follow from
+  // the view's column maxima and the member's own column bounds (msc_state_set_col_bounds), which may differ
+  for (uint32_t c = 1; c < n; c++)
+    for (uint32_t f = 0; f < st0->nfeat; f++) {
+      const int fam = st0->feats[f].family;
+      MSC_REQUIRE((fam != MSC_GP && fam != MSC_BNB) || ch->states[c]->desc_host[f].vcap == st0->desc_host[f].vcap,
+                  "msc_chains_score_marginal: feature %u: state %u's exact count table has %u rows, state 0's %u (their "
+                  "column bounds differ: msc_state_set_col_bounds)", f, c, ch->states[c]->desc_host[f].vcap,
+                  st0->desc_host[f].vcap);
+    }
+  if (nrows == 0) return MSC_OK;
+  // every member's score tables and CRP terms current, as msc_score_marginal
+  for (msc_state *st : ch->states) {
+    MSC_TRY(ensure_derived(st));
+    MSC_TRY(ensure_crp(st));
+  }
+  hipStream_t s = ctx->stream;
+  const uint32_t nslices = route_chains_marginal(ch);
+  // the slices' workspace holds the whole VIEW's rows (what the slice count follows from): one size per view and device,
+  // so calls over sub-ranges of any lengths never grow it again
+  if (nslices > 1 && mix_dev)
+    MSC_HIP(grow_retained(ch->retired, ch->marg_part, 2 * (size_t)nslices * std::max<uint64_t>(nrows, view_rows(st0))));
+  // the table of this call, through the pinned area whose turn it is: the chains, then the selected features' tile plan
+  // (from member 0's bound descriptors: families and dims are equal by msc_chains_create, the count columns' table sizes
+  // were compared above)
+  const uint32_t nsel = all ? st0->nfeat : nfeatures;
+  int a = 0;
+  MSC_TRY(chains_stage(ch, &a));
+  unsigned char *area = reinterpret_cast<unsigned char *>(ch->stage[a].get());
+  MargChain *tab = reinterpret_cast<MargChain *>(area);
+  MargFeat *pf = reinterpret_cast<MargFeat *>(area + marg_feat_at(n));
+  for (uint32_t c = 0; c < n; c++) {
+    const msc_state *st = ch->states[c];
+    MargChain &e = tab[c];
+    e.feats = st->desc_dev;
+    e.cnt = st->cnt_u32;
+    e.crp = st->logpc;
+    e.logp = chain_logp_dev ? chain_logp_dev + (size_t)c * ld_logp : nullptr;
+    e.alpha = st->alpha;
+    e.pad = 0;
+  }
+  std::vector<uint32_t> sel(nsel);
+  for (uint32_t i = 0; i < nsel; i++) sel[i] = all ? i : features[i];
+  const CmPlan plan = plan_chains_marginal(st0->desc_host.data(), sel.data(), nsel, st0->K, pf);
+  const size_t bytes = marg_feat_at(n) + (size_t)nsel * sizeof(MargFeat);
+  unsigned char *dev = ch->marg_tab;
+  MSC_HIP(hipMemcpyAsync(dev, area, bytes, hipMemcpyHostToDevice, s));
+  MSC_TRY(chains_staged(ch, a, s));
+  double *lw = ch->marg_w, *norm = lw + n;
+  MSC_TRY(launch_chains_marginal_prep(s, reinterpret_cast<const MargChain *>(dev), n, st0->K, logw_dev, lw, norm));
+  return launch_chains_marginal(s, reinterpret_cast<const MargChain *>(dev), reinterpret_cast<const MargFeat *>(dev + marg_feat_at(n)),
+                                nsel, plan, n, nslices, st0->K, st0->kpad, row0, nrows, lw, norm, mix_dev, ch->marg_part);
 }

@@ -338,6 +338,41 @@ int launch_marginal_tile(hipStream_t stream, int num_cus, const FeatDesc *feats_
 int launch_row_lse(hipStream_t stream, int num_cus, const float *scores, uint64_t ld, uint32_t K, uint64_t nrows,
                    const int32_t *z, const double *norm, float *logp, int32_t *map, float *logresp);
 
+// kernels_chains_marginal.hip (msc_chains_score_marginal): what differs per chain, and per selected feature
+struct MargChain {
+  const FeatDesc *feats;   // the chain's state: descriptors, group counts, CRP terms
+  const uint32_t *cnt;
+  const float *crp;
+  float *logp;             // float [nrows] or null: the chain's row of chain_logp
+  float alpha;
+  uint32_t pad;
+};
+struct MargFeat {
+  uint32_t f;              // the feature's index in the state
+  uint32_t off;            // first float of its block in the LDS tile; 0xffffffff: its tables are read from global memory
+  uint32_t rows;           // table rows of the block (bb 2, dd dim, gp / bnb vcap, nich 6, noop 0)
+  uint32_t pad;
+};
+static_assert(sizeof(MargChain) <= sizeof(SeqChain), "a staging area holds nchains entries of either table");
+constexpr uint32_t kCmTileFloats = 10240;   // 40 KiB of LDS a workgroup: four workgroups of 256 rows a CU
+constexpr uint32_t kCmMinTile = 32;         // a feature is staged only while a tile of this many groups still fits
+struct CmPlan {
+  uint32_t TG = 0;          // groups a tile
+  uint32_t TS = 0;          // floats between two table rows of a tile: TG | 1
+  uint32_t lds_floats = 0;  // the launch's dynamic LDS
+  bool wide = false;        // tiles of whole batches of 32 groups: the wide-batch instantiation
+  bool large = false;       // a selected gp / bnb column may hold counts beyond the exact table: the instantiation with the large-count forms
+};
+// out[nsel]: the plan of the selected features sel[nsel] (ascending state indices); feats_host: the bound descriptors
+CmPlan plan_chains_marginal(const FeatDesc *feats_host, const uint32_t *sel, uint32_t nsel, uint32_t K, MargFeat *out);
+// lw / norm: double [nchains] each, written by the first launch and read by the second
+int launch_chains_marginal_prep(hipStream_t stream, const MargChain *chains_dev, uint32_t nchains, uint32_t K,
+                                const double *logw, double *lw, double *norm);
+// mix nullable; part: double [nslices][nrows][2], needed when nslices > 1 and mix is wanted
+int launch_chains_marginal(hipStream_t stream, const MargChain *chains_dev, const MargFeat *plan_dev, uint32_t nsel,
+                           const CmPlan &plan, uint32_t nchains, uint32_t nslices, uint32_t K, uint32_t kpad, uint64_t row0,
+                           uint64_t nrows, const double *lw, const double *norm, float *mix, double *part);
+
 // kernels_query.hip (msc_zmatrix_*): counts live as upper-triangle tiles of kZmTile x kZmTile u32 (zm_tile_base); the
 // batch is [rows rounded up to kZmTile][kZmBatchWords] u32, four 8-bit or two 16-bit labels a word; `bad` holds a flag
 // per batch slot (kZmBatchMax of them) and then the number of flagged slots

@@ -474,6 +474,52 @@ int msc_chains_visit(msc_chains *ch, const msc_dataview *view, const uint32_t *c
 int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, int32_t *z_dev, uint64_t ld_z, uint64_t nrows);
 
 /*
+ * The POSTERIOR-AVERAGED row predictive density over the chains of an ensemble, in one pass over (rows x chains):
+ *   mix[r] = logsumexp_c (lw_c + L[c][r])   ~   log p(x_r | data) = log sum_c w_c p(x_r | state_c)
+ * for rows [row0, row0 + nrows) of the view -- the held-out log-likelihood or anomaly score of the fitted model rather
+ * than of one sample; the difference of two calls over nested feature sets is a model-averaged conditional density.
+ *   L[c][r]   what msc_score_marginal(states[c], view, cols, row0, nrows, NULL, 0, ...) defines for logp_dev[r] (no
+ *             leave-one-out): logsumexp_k t[r][k] - log(n_c + alpha_c), taken over the SELECTED features only -- an
+ *             unselected feature contributes nothing to any t[r][k], exactly as a masked entry does.  The scores are the
+ *             score kernels' accurate form (table lookups, the compensated nich evaluation, the CRP term added as its
+ *             (hi, lo) pair, lo first; gp and bnb values beyond the exact table in the large-count forms of
+ *             msc_sweep_sequential); the sum over the groups is kept in double and L is formed in double.
+ *   features  host array of nfeatures strictly ascending feature indices < the states' feature count, read before the
+ *             call returns; NULL or nfeatures == 0: every feature.
+ *   logw_dev  nullable; double[nchains] on the device, only read: the chains' log weights, which need not be normalised:
+ *             lw_c = logw_dev[c] - logsumexp(logw_dev), in double on the device.  NULL: lw_c = -log(nchains).  A weight
+ *             of -inf excludes its chain.  If NO weight is finite -- all -inf -- or one is NaN or +inf, every entry of
+ *             mix is NaN (chain_logp is unaffected).
+ *   flags     reserved: 0.
+ *   mix_dev   nullable; float[nrows]: (float)logsumexp_c(lw_c + L[c][r]).  The sum over the chains is taken in double
+ *             in a FIXED order -- ascending chains within a slice of the chains, then ascending slices; no float
+ *             atomics -- so the same call gives the same bits on every run.  -inf when no chain of finite weight can
+ *             hold the row.
+ *   chain_logp_dev, ld_logp   nullable; float, chain c's row at chain_logp_dev + c * ld_logp (ld_logp >= nrows):
+ *             (float)L[c][r].  At least one of the two outputs is non-NULL.
+ * A one-hot weight vector (one finite entry, the others -inf) gives mix bit-equal to that chain's row of chain_logp.
+ * A row's results depend on nothing but the row: the size of the group tiles and the cut of the chains into slices follow
+ * from the ensemble, the device and the rows of the VIEW, never from row0 / nrows, so a call over a sub-range gives the
+ * whole call's bits.
+ * Families: those an ensemble holds (bb, gp, bnb, dd, nich, noop).  Every member is read-only apart from the view it is
+ * left bound to (a later msc_chains_sweep on the training view gives the bits it would have given without this call); its
+ * score tables and CRP terms are brought current first, as msc_score_marginal does.  The per-chain table reaches the
+ * device through the two pinned staging areas of msc_chains_sweep.  Asynchronous on the context's stream; the call itself
+ * does not synchronise with the device (it may wait for the upload of the call before last to leave its staging area,
+ * and binding a view whose count columns' maxima are not known yet finds them once, as every call that binds a view).
+ * nrows == 0 binds the view, writes nothing and returns MSC_OK.
+ * Errors, with nothing written: MSC_EINVAL for a null ch or view, both outputs NULL, chain_logp_dev with ld_logp < nrows,
+ * a feature list that is not strictly ascending or names a feature outside the state, non-zero flags, nrows >= 2^32,
+ * rows outside the view, a column that does not fit its feature, a member between msc_sweep_step_begin and
+ * msc_state_commit_reduce (the index is named), or a member whose exact gp / bnb table has other rows than member 0's
+ * (its own msc_state_set_col_bounds differ: one tile plan serves every chain); MSC_EDEVICE when an earlier kernel
+ * reported an error.
+ */
+int msc_chains_score_marginal(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                              const uint32_t *features, uint32_t nfeatures, const double *logw_dev, uint32_t flags,
+                              float *mix_dev, float *chain_logp_dev, uint64_t ld_logp);
+
+/*
  * The BLOCKED (uncollapsed) Gibbs sampler for the truncated stick-breaking Dirichlet process mixture (Ishwaran & James,
  * JASA 2001): an exact sampler that is parallel over rows.  With ngroups = K slots a sweep draws, given the tables,
  * every slot's component parameters from their conjugate posteriors and the mixture weights from the stick-breaking
