@@ -157,6 +157,10 @@ _SIGS = {
     # (ch, view, cols, row0, nrows, features, nfeatures, logw_dev, flags, mix_dev, chain_logp_dev, ld_logp)
     "msc_chains_score_marginal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32),
                                             C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
+    # (ch, view, cols, row0, nrows, row_id0, logw_dev, flags, seed, sweep, chain_out_dev, z_out_dev, out_dev)
+    "msc_chains_sample_predictive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                               C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     # (ch, coords, n, slots_dev, ld_slots, host_seeds, sweep, values_host, evals_host)
     "msc_chains_hp_slice": (C.c_int, [C.c_void_p, C.POINTER(SliceCoord), C.c_uint32, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -446,6 +446,75 @@ class ChainEnsemble(object):
                 out[:n] -= denom
         return (out, logp) if per_chain else out
 
+    # posterior predictive draws from the model average --------------------------------
+    def sample_predictive(self, view, weights=None, seed=0, sweep=0, masked_only=False, features=None, row0=0, nrows=None,
+                          row_id0=None, cols=None, out=None):
+        """Posterior predictive draws for rows [row0, row0 + nrows) of the view from the MODEL AVERAGE over the chains, in
+        one pass (msc_chains_sample_predictive; asynchronous): every row draws a chain with probability ~ w_c p(the row's
+        observed entries | state_c), a group of that chain, and its entries from that group's predictive
+        -> (dict feature -> device tensor of nrows values, chains int32 [nrows], groups int32 [nrows]).
+        A row no chain of finite weight can hold is skipped: chains = groups = -1 and its entries keep what `out` held.
+        weights: None (equal), or float64 [nchains] LOG weights on the host or the device, normalised or not; -inf leaves a
+        chain out.  ens.logw after ens.smc(...) is the intended argument.
+        features: state feature indices to draw (default: every feature but the noop ones, which have no values; whatever
+        is drawn, a row's chain and group are conditioned on all its observed entries).  out: optional
+        dict feature -> device tensor to write into.
+        Every drawn entry is, bit for bit, what ens.states[c].sample_predictive(view, z=groups, seed, sweep, ...) writes
+        for the rows with chains == c.  The draws are a fixed function of (seed, sweep, row_id0 + row): a call repeats its
+        bits and a call over a sub-range gives the whole call's; m independent draws of every row -- m imputations of a
+        data set -- are m calls with sweep = 0 .. m - 1."""
+        self._check_open()
+        dev = self.ctx.torch_device
+        row0, n = A.rows(int(view.nrows), row0, nrows)
+        if row0 + n > view.nrows:                      # (outputs are sized before the call: not left to the library)
+            raise ValueError("rows [%d, %d) outside the view (%d rows)" % (row0, row0 + n, view.nrows))
+        dtypes = State._PRED_DTYPES
+        feats = [f for f, (fam, _) in enumerate(self.features) if fam in dtypes] if features is None else [int(f) for f in features]
+        for f in feats:
+            if not 0 <= f < len(self.features):
+                raise ValueError("feature %d outside the states (%d features)" % (f, len(self.features)))
+            if self.features[f][0] not in dtypes:
+                raise L.MicroscopesHipError(-4, "feature %d: the family has no values to draw" % f)
+        w = None
+        if weights is not None:
+            w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
+            if w.dtype != torch.float64 or tuple(w.shape) != (self.nchains,):
+                raise ValueError("weights must be float64 [nchains = %d] log weights" % self.nchains)
+        seed, sweep = int(seed), int(sweep)
+        if not 0 <= seed <= _U64 or not 0 <= sweep <= _U64:
+            raise ValueError("seed and sweep must lie in [0, 2^64)")
+        out = dict(out or {})
+        for f in feats:
+            t = out.get(f)
+            if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (n,)):
+                raise ValueError("out[%d] must be a contiguous %s device tensor of shape %s" % (f, dtypes[self.features[f][0]], (n,)))
+            if t is not None:
+                A.flat(t, dtypes[self.features[f][0]], 0, dev, "out[%d]" % f)
+        # every argument is checked: from here on the device is used
+        ptrs = (C.c_void_p * len(self.features))()
+        for f in feats:
+            if out.get(f) is None:
+                out[f] = torch.empty((n,), dtype=dtypes[self.features[f][0]], device=dev)
+            ptrs[f] = A.ptr(out[f]) if n else None
+        chains = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        groups = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        wp = None
+        if w is not None:
+            w = w.to(dev).contiguous()
+            wp = A.ptr(w)
+        for st in self.states:
+            st._bound_view = view        # (the library keeps no reference to a view: the states do, for the last one bound)
+        L.check(self.ctx.lib.msc_chains_sample_predictive(
+            self._h, view._h, self.states[0]._cols(cols), row0, n, row0 if row_id0 is None else int(row_id0), wp,
+            L.PRED_MASKED_ONLY if masked_only else 0, seed, sweep, A.ptr(chains) if n else None,
+            A.ptr(groups) if n else None, ptrs))
+        return {f: out[f] for f in feats}, chains, groups
+
+    def impute(self, view, **kw):
+        """sample_predictive with masked_only=True: masked entries drawn, observed ones copied (the completed columns).
+        m imputations of the data set are m calls with sweep = 0 .. m - 1."""
+        return self.sample_predictive(view, masked_only=True, **kw)
+
     # lifetime -----------------------------------------------------------------
     def _check_open(self):
         if not getattr(self, "_h", None):

@@ -1,6 +1,6 @@
 // chains.cpp -- the sequential collapsed Gibbs sweep and the ensembles of such chains (kernels_seq.hip):
-// msc_sweep_sequential and msc_chains_*, the ensemble's row predictive density among them
-// (kernels_chains_marginal.hip).  Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
+// msc_sweep_sequential and msc_chains_*, the ensemble's row predictive density (kernels_chains_marginal.hip) and its
+// posterior predictive draws (kernels_chains_pred.hip) among them.  Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
 #include <algorithm>
 #include <memory>
 #include <new>
@@ -114,11 +114,17 @@ struct msc_chains {
   msc::DevBuf<unsigned char> marg_tab;
   msc::DevBuf<double> marg_w;             // [2 nchains]: lw | norm
   msc::DevBuf<double> marg_part;
+  // msc_chains_sample_predictive: the chains' rows of a chunk (float [nchains][chunk]) and the chunk's rows' chain and
+  // group (int32 [2][chunk]), grown as marg_part is; the call's output pointers travel behind the MargFeat table
+  msc::DevBuf<float> pred_lf;
+  msc::DevBuf<int32_t> pred_cz;
   msc::Retired retired;
 };
 static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
-// entries of a staging area beyond nchains, for the MargFeat table of nfeat features behind the MargChain table
-static size_t marg_extra(uint32_t nfeat) { return ((size_t)nfeat * sizeof(msc::MargFeat) + sizeof(msc::SeqChain) - 1) / sizeof(msc::SeqChain); }
+// bytes behind the MargChain table: the MargFeat table of nfeat features, then as many output pointers; and the entries of
+// a staging area beyond nchains that hold them
+static size_t marg_tail(uint32_t nfeat) { return (size_t)nfeat * (sizeof(msc::MargFeat) + sizeof(void *)); }
+static size_t marg_extra(uint32_t nfeat) { return (marg_tail(nfeat) + 16 + sizeof(msc::SeqChain) - 1) / sizeof(msc::SeqChain); }
 static size_t marg_feat_at(uint32_t nchains) { return ((size_t)nchains * sizeof(msc::MargChain) + 15) & ~(size_t)15; }
 
 // the pinned staging area whose turn it is, once no pending copy reads it; chains_staged records the copy out of it
@@ -165,7 +171,7 @@ extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc
   ch->states.assign(states, states + nchains);
   hipError_t e = ch->table_dev.alloc(nchains);
   if (e == hipSuccess) e = ch->pairs_dev.alloc(nchains);
-  if (e == hipSuccess) e = ch->marg_tab.alloc(marg_feat_at(nchains) + (size_t)states[0]->nfeat * sizeof(MargFeat), 16);
+  if (e == hipSuccess) e = ch->marg_tab.alloc(marg_feat_at(nchains) + marg_tail(states[0]->nfeat), 16);
   if (e == hipSuccess) e = ch->marg_w.alloc(2 * (size_t)nchains);
   for (int i = 0; i < 2 && e == hipSuccess; i++) {
     e = ch->stage[i].alloc(nchains + marg_extra(states[0]->nfeat));
@@ -473,6 +479,91 @@ static uint32_t route_chains_marginal(const msc_chains *ch) {
   return (n + per - 1) / per;
 }
 
+// what msc_chains_score_marginal and msc_chains_sample_predictive check and bind before anything is launched
+static int chains_marginal_begin(msc_chains *ch, const char *who, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                 uint64_t nrows) {
+  const uint32_t n = (uint32_t)ch->states.size();
+  const msc_state *st0 = ch->states[0];
+  for (uint32_t c = 0; c < n; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  // one tile plan serves every chain, so every member's exact count tables must have member 0's rows: they follow from
+  // the view's column maxima and the member's own column bounds (msc_state_set_col_bounds), which may differ
+  for (uint32_t c = 1; c < n; c++)
+    for (uint32_t f = 0; f < st0->nfeat; f++) {
+      const int fam = st0->feats[f].family;
+      MSC_REQUIRE((fam != MSC_GP && fam != MSC_BNB) || ch->states[c]->desc_host[f].vcap == st0->desc_host[f].vcap,
+                  "%s: feature %u: state %u's exact count table has %u rows, state 0's %u (their "
+                  "column bounds differ: msc_state_set_col_bounds)", who, f, c, ch->states[c]->desc_host[f].vcap,
+                  st0->desc_host[f].vcap);
+    }
+  return MSC_OK;
+}
+
+// The table of a call on the device, and what the first launch leaves beside it
+struct MargCall {
+  const MargChain *chains_dev = nullptr;
+  const MargFeat *plan_dev = nullptr;
+  void *const *outs_dev = nullptr;     // [nfeat], when the call gave outs
+  CmPlan plan;
+  uint32_t nsel = 0;
+  double *lw = nullptr, *norm = nullptr;
+};
+// Every member's score tables and CRP terms current, as msc_score_marginal; then the table of this call through the
+// pinned area whose turn it is -- the chains (chain c's row of chain_logp at logp + c * ld_logp), the selected features'
+// tile plan (from member 0's bound descriptors: families and dims are equal by msc_chains_create, the count columns'
+// table sizes were compared by chains_marginal_begin), the output pointers of a sampling call -- and
+// k_chains_marginal_prep's launch.
+static int chains_marginal_stage(msc_chains *ch, const uint32_t *features, uint32_t nfeatures, const double *logw_dev,
+                                 float *logp, uint64_t ld_logp, void *const *outs, MargCall &call) {
+  const uint32_t n = (uint32_t)ch->states.size();
+  const msc_state *st0 = ch->states[0];
+  const bool all = features == nullptr || nfeatures == 0;
+  for (msc_state *st : ch->states) {
+    MSC_TRY(ensure_derived(st));
+    MSC_TRY(ensure_crp(st));
+  }
+  hipStream_t s = ch->ctx->stream;
+  const uint32_t nsel = all ? st0->nfeat : nfeatures;
+  int a = 0;
+  MSC_TRY(chains_stage(ch, &a));
+  unsigned char *area = reinterpret_cast<unsigned char *>(ch->stage[a].get());
+  MargChain *tab = reinterpret_cast<MargChain *>(area);
+  MargFeat *pf = reinterpret_cast<MargFeat *>(area + marg_feat_at(n));
+  for (uint32_t c = 0; c < n; c++) {
+    const msc_state *st = ch->states[c];
+    MargChain &e = tab[c];
+    e.feats = st->desc_dev;
+    e.cnt = st->cnt_u32;
+    e.crp = st->logpc;
+    e.logp = logp ? logp + (size_t)c * ld_logp : nullptr;
+    e.alpha = st->alpha;
+    e.pad = 0;
+  }
+  std::vector<uint32_t> sel(nsel);
+  for (uint32_t i = 0; i < nsel; i++) sel[i] = all ? i : features[i];
+  call.plan = plan_chains_marginal(st0->desc_host.data(), sel.data(), nsel, st0->K, pf);
+  call.nsel = nsel;
+  size_t bytes = marg_feat_at(n) + (size_t)nsel * sizeof(MargFeat);
+  unsigned char *dev = ch->marg_tab;
+  if (outs != nullptr) {
+    std::memcpy(area + bytes, outs, (size_t)st0->nfeat * sizeof(void *));
+    call.outs_dev = reinterpret_cast<void *const *>(dev + bytes);
+    bytes += (size_t)st0->nfeat * sizeof(void *);
+  }
+  MSC_HIP(hipMemcpyAsync(dev, area, bytes, hipMemcpyHostToDevice, s));
+  MSC_TRY(chains_staged(ch, a, s));
+  call.chains_dev = reinterpret_cast<const MargChain *>(dev);
+  call.plan_dev = reinterpret_cast<const MargFeat *>(dev + marg_feat_at(n));
+  call.lw = ch->marg_w;
+  call.norm = call.lw + n;
+  return launch_chains_marginal_prep(s, call.chains_dev, n, st0->K, logw_dev, call.lw, call.norm);
+}
+
 extern "C" int msc_chains_score_marginal(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                                          uint64_t nrows, const uint32_t *features, uint32_t nfeatures, const double *logw_dev,
                                          uint32_t flags, float *mix_dev, float *chain_logp_dev, uint64_t ld_logp) {
@@ -493,63 +584,74 @@ extern "C" int msc_chains_score_marginal(msc_chains *ch, const msc_dataview *vie
       MSC_REQUIRE(i == 0 || features[i] > features[i - 1], "msc_chains_score_marginal: the feature list is not strictly "
                   "ascending at entry %u", i);
     }
-  for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_score_marginal: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  // one tile plan serves every chain, so every member's exact count tables must have member 0's rows: they follow from
-  // the view's column maxima and the member's own column bounds (msc_state_set_col_bounds), which may differ
-  for (uint32_t c = 1; c < n; c++)
-    for (uint32_t f = 0; f < st0->nfeat; f++) {
-      const int fam = st0->feats[f].family;
-      MSC_REQUIRE((fam != MSC_GP && fam != MSC_BNB) || ch->states[c]->desc_host[f].vcap == st0->desc_host[f].vcap,
-                  "msc_chains_score_marginal: feature %u: state %u's exact count table has %u rows, state 0's %u (their "
-                  "column bounds differ: msc_state_set_col_bounds)", f, c, ch->states[c]->desc_host[f].vcap,
-                  st0->desc_host[f].vcap);
-    }
+  MSC_TRY(chains_marginal_begin(ch, "msc_chains_score_marginal", view, cols, row0, nrows));
   if (nrows == 0) return MSC_OK;
-  // every member's score tables and CRP terms current, as msc_score_marginal
-  for (msc_state *st : ch->states) {
-    MSC_TRY(ensure_derived(st));
-    MSC_TRY(ensure_crp(st));
-  }
-  hipStream_t s = ctx->stream;
   const uint32_t nslices = route_chains_marginal(ch);
   // the slices' workspace holds the whole VIEW's rows (what the slice count follows from): one size per view and device,
   // so calls over sub-ranges of any lengths never grow it again
   if (nslices > 1 && mix_dev)
     MSC_HIP(grow_retained(ch->retired, ch->marg_part, 2 * (size_t)nslices * std::max<uint64_t>(nrows, view_rows(st0))));
-  // the table of this call, through the pinned area whose turn it is: the chains, then the selected features' tile plan
-  // (from member 0's bound descriptors: families and dims are equal by msc_chains_create, the count columns' table sizes
-  // were compared above)
-  const uint32_t nsel = all ? st0->nfeat : nfeatures;
-  int a = 0;
-  MSC_TRY(chains_stage(ch, &a));
-  unsigned char *area = reinterpret_cast<unsigned char *>(ch->stage[a].get());
-  MargChain *tab = reinterpret_cast<MargChain *>(area);
-  MargFeat *pf = reinterpret_cast<MargFeat *>(area + marg_feat_at(n));
-  for (uint32_t c = 0; c < n; c++) {
-    const msc_state *st = ch->states[c];
-    MargChain &e = tab[c];
-    e.feats = st->desc_dev;
-    e.cnt = st->cnt_u32;
-    e.crp = st->logpc;
-    e.logp = chain_logp_dev ? chain_logp_dev + (size_t)c * ld_logp : nullptr;
-    e.alpha = st->alpha;
-    e.pad = 0;
+  MargCall call;
+  MSC_TRY(chains_marginal_stage(ch, features, nfeatures, logw_dev, chain_logp_dev, ld_logp, nullptr, call));
+  return launch_chains_marginal(ch->ctx->stream, call.chains_dev, call.plan_dev, call.nsel, call.plan, n, nslices, st0->K,
+                                st0->kpad, row0, nrows, call.lw, call.norm, mix_dev, ch->marg_part);
+}
+
+// ---------------------------------------------------------------------------
+// Posterior predictive draws from the model average (kernels_chains_pred.hip)
+// ---------------------------------------------------------------------------
+// The rows of a call go through the handle's scratch -- the chains' rows Lf [nchains][chunk] floats, then the rows' chain
+// and group -- a chunk at a time: at most kPredScratchBytes of Lf and kPredChunkRows rows.  A row depends on the row alone,
+// so the cut moves no bit.
+constexpr uint64_t kPredScratchBytes = 256ull << 20;
+constexpr uint64_t kPredChunkRows = 1ull << 18;
+
+extern "C" int msc_chains_sample_predictive(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                            uint64_t nrows, uint64_t row_id0, const double *logw_dev, uint32_t flags,
+                                            uint64_t seed, uint64_t sweep, int32_t *chain_out_dev, int32_t *z_out_dev,
+                                            void *const *out_dev) {
+  MSC_REQUIRE(ch && view && out_dev, "null argument");
+  MSC_REQUIRE((flags & ~MSC_PRED_MASKED_ONLY) == 0, "unknown flags 0x%x", flags);
+  MSC_REQUIRE(nrows < (1ull << 32), "msc_chains_sample_predictive takes at most 2^32 - 1 rows per call");
+  const uint32_t n = (uint32_t)ch->states.size();
+  if (n == 0) return MSC_OK;
+  const msc_state *st0 = ch->states[0];
+  bool light = false, heavy = false;
+  for (uint32_t f = 0; f < st0->nfeat; f++) {
+    if (out_dev[f] == nullptr) continue;
+    const int fam = st0->feats[f].family;
+    if (fam == MSC_NOOP) return fail(MSC_EUNSUPPORTED, "feature %u: the noop model has no values to draw", f);
+    MSC_REQUIRE(f < 0x8000u, "feature %u: the draw's Philox counter holds feature indices below 32768", f);
+    const bool h = fam == MSC_GP || fam == MSC_BNB || fam == MSC_NICH;
+    heavy |= h;
+    light |= !h || (flags & MSC_PRED_MASKED_ONLY) != 0;      // (the copies of observed entries are the light kernel's)
   }
-  std::vector<uint32_t> sel(nsel);
-  for (uint32_t i = 0; i < nsel; i++) sel[i] = all ? i : features[i];
-  const CmPlan plan = plan_chains_marginal(st0->desc_host.data(), sel.data(), nsel, st0->K, pf);
-  const size_t bytes = marg_feat_at(n) + (size_t)nsel * sizeof(MargFeat);
-  unsigned char *dev = ch->marg_tab;
-  MSC_HIP(hipMemcpyAsync(dev, area, bytes, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, a, s));
-  double *lw = ch->marg_w, *norm = lw + n;
-  MSC_TRY(launch_chains_marginal_prep(s, reinterpret_cast<const MargChain *>(dev), n, st0->K, logw_dev, lw, norm));
-  return launch_chains_marginal(s, reinterpret_cast<const MargChain *>(dev), reinterpret_cast<const MargFeat *>(dev + marg_feat_at(n)),
-                                nsel, plan, n, nslices, st0->K, st0->kpad, row0, nrows, lw, norm, mix_dev, ch->marg_part);
+  MSC_TRY(chains_marginal_begin(ch, "msc_chains_sample_predictive", view, cols, row0, nrows));
+  if (nrows == 0) return MSC_OK;
+  // the scratch: Lf, then chain and group of the chunk's rows (the caller's arrays where it gave them)
+  // (a power of two from 4096 on: the buffers a growing scratch retires stay with the handle, and add up to less than
+  // the last one)
+  uint64_t chunk = 4096;
+  while (chunk < nrows && chunk < kPredChunkRows && 2 * chunk * n * sizeof(float) <= kPredScratchBytes) chunk *= 2;
+  MSC_HIP(grow_retained(ch->retired, ch->pred_lf, (size_t)n * chunk));
+  MSC_HIP(grow_retained(ch->retired, ch->pred_cz, 2 * (size_t)chunk));
+  float *Lf = ch->pred_lf;
+  MargCall call;
+  MSC_TRY(chains_marginal_stage(ch, nullptr, 0, logw_dev, Lf, chunk, out_dev, call));
+  hipStream_t s = ch->ctx->stream;
+  const uint32_t nslices = route_chains_marginal(ch);         // (the grid's cut only: with no mix, no slice writes a part)
+  for (uint64_t at = 0; at < nrows; at += chunk) {
+    const uint64_t m = std::min<uint64_t>(chunk, nrows - at);
+    int32_t *chain = chain_out_dev ? chain_out_dev + at : ch->pred_cz.get();
+    int32_t *z = z_out_dev ? z_out_dev + at : ch->pred_cz.get() + chunk;
+    MSC_TRY(launch_chains_marginal(s, call.chains_dev, call.plan_dev, call.nsel, call.plan, n, nslices, st0->K, st0->kpad,
+                                   row0 + at, m, call.lw, call.norm, nullptr, nullptr));
+    MSC_TRY(launch_chains_pick(s, call.lw, Lf, chunk, n, m, row_id0 + at, seed, sweep, chain));
+    MSC_TRY(launch_chains_draw(s, call.chains_dev, call.plan.large, st0->nfeat, st0->K, st0->kpad, row0 + at, m, row_id0 + at,
+                               seed, sweep, chain, z));
+    if (light || heavy)
+      MSC_TRY(launch_chains_values(s, call.chains_dev, call.outs_dev, light, heavy, st0->nfeat, st0->kpad, row0 + at, m,
+                                   row_id0 + at, at, chain, z, (flags & MSC_PRED_MASKED_ONLY) != 0, seed, sweep));
+  }
+  return MSC_OK;
 }

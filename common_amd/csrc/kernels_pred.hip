@@ -1,5 +1,6 @@
 // kernels_pred.hip -- gfx950 kernels of posterior predictive sampling (msc_sample_predictive, include/microscopes_hip.h):
 //   k_pred_prepare      one thread per (feature, group): raw suff-stats + hp -> the group's predictive parameters, in double
+//                       (the formulas: pred_params.hpp, shared with the ensemble's draw)
 //   k_pred_prepare_niw  one wave per niw group: mu', the lower Cholesky factor of the predictive scale, dof -- the factor is
 //                       the inverse of the whitening matrix k_niw_prepare already made (no second factorisation)
 //   k_pred_sample       one lane per row, the scalar features looped: every output column store is coalesced; <false>
@@ -10,6 +11,7 @@
 // pred_samplers.hpp, whose header comment also fixes the Philox counter of every draw.
 #include "family_math.hpp"
 #include "launchers.hpp"
+#include "pred_params.hpp"
 #include "pred_samplers.hpp"
 
 namespace msc {
@@ -26,41 +28,34 @@ __global__ __launch_bounds__(256) void k_pred_prepare(const PredFeat *__restrict
   const uint32_t *u = pf.raw_u32;
   double *par = pf.par + (size_t)k * pf.stride;
   switch (pf.family) {
-    case MSC_BB: {
-      const double h = u[k], t = u[kpad + k], a = hp[0], b = hp[1];
-      par[0] = (b + t) / (a + b + h + t);                         // P(v = 0)
-      break;
-    }
+    case MSC_BB: par[0] = predpar::bb_p0(hp, u, kpad, k); break;                       // P(v = 0)
     case MSC_BBNC: par[0] = 1.0 - (double)pf.raw_f32[k]; break;
     case MSC_GP: {
-      const double n = u[k], s = u[kpad + k];
-      par[0] = (double)hp[0] + s;                                 // Gamma shape of the rate
-      par[1] = 1.0 / ((double)hp[1] + n);                         // and its scale
+      const predpar::Gp p = predpar::gp(hp, u, kpad, k);
+      par[0] = p.shape;                                           // Gamma shape of the rate
+      par[1] = p.scale;                                           // and its scale
       break;
     }
     case MSC_BNB: {
-      const double n = u[k], s = u[kpad + k], r = hp[2];
-      par[0] = (double)hp[0] + r * n;
-      par[1] = (double)hp[1] + s;
-      par[2] = r;
+      const predpar::Bnb p = predpar::bnb(hp, u, kpad, k);
+      par[0] = p.a;
+      par[1] = p.b;
+      par[2] = p.r;
       break;
     }
     case MSC_DD: {
       double c = 0.0;
       for (uint32_t i = 0; i < pf.dim; i++) {
-        c += (double)hp[i] + (double)u[(size_t)(1 + i) * kpad + k];
+        c += predpar::dd_weight(hp, u, kpad, k, i);
         par[i] = c;                                               // cumulative weights; par[dim - 1] is the total
       }
       break;
     }
     case MSC_NICH: {
-      const double n = u[k], mean = pf.raw_f32[k], ctv = pf.raw_f32[kpad + k];
-      const double mu = hp[0], kappa = hp[1], sigmasq = hp[2], nu = hp[3];
-      const double kn = kappa + n, nun = nu + n, dm = mu - mean;
-      const double sigsq = (nu * sigmasq + ctv + n * kappa * dm * dm / kn) / nun;
-      par[0] = (kappa * mu + n * mean) / kn;
-      par[1] = sqrt(sigsq * (kn + 1.0) / kn);
-      par[2] = nun;
+      const predpar::Nich p = predpar::nich(hp, u, pf.raw_f32, kpad, k);
+      par[0] = p.mu;
+      par[1] = p.scale;
+      par[2] = p.nu;
       break;
     }
     default: break;

@@ -373,6 +373,19 @@ int launch_chains_marginal(hipStream_t stream, const MargChain *chains_dev, cons
                            const CmPlan &plan, uint32_t nchains, uint32_t nslices, uint32_t K, uint32_t kpad, uint64_t row0,
                            uint64_t nrows, const double *lw, const double *norm, float *mix, double *part);
 
+// kernels_chains_pred.hip (msc_chains_sample_predictive), after the two launches above have left lw and the chains' rows
+// Lf (float [nchains][ld], through MargChain::logp): the chain of every row (-1: skipped), its group in that chain, its
+// values.  chain / z: int32 [nrows]; outs_dev: one pointer a state feature (null: not drawn), a row's entry at `at` + its
+// offset from row0; large: the instantiation with the large-count forms of gp / bnb (CmPlan::large)
+int launch_chains_pick(hipStream_t stream, const double *lw, const float *Lf, uint64_t ld, uint32_t nchains, uint64_t nrows,
+                       uint64_t row_id0, uint64_t seed, uint64_t sweep, int32_t *chain);
+int launch_chains_draw(hipStream_t stream, const MargChain *chains_dev, bool large, uint32_t nfeat, uint32_t K, uint32_t kpad,
+                       uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t seed, uint64_t sweep, int32_t *chain,
+                       int32_t *z);
+int launch_chains_values(hipStream_t stream, const MargChain *chains_dev, void *const *outs_dev, bool light, bool heavy,
+                         uint32_t nfeat, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t at,
+                         const int32_t *chain, const int32_t *z, bool masked_only, uint64_t seed, uint64_t sweep);
+
 // kernels_query.hip (msc_zmatrix_*): counts live as upper-triangle tiles of kZmTile x kZmTile u32 (zm_tile_base); the
 // batch is [rows rounded up to kZmTile][kZmBatchWords] u32, four 8-bit or two 16-bit labels a word; `bad` holds a flag
 // per batch slot (kZmBatchMax of them) and then the number of flagged slots

@@ -520,6 +520,54 @@ int msc_chains_score_marginal(msc_chains *ch, const msc_dataview *view, const ui
                               float *mix_dev, float *chain_logp_dev, uint64_t ld_logp);
 
 /*
+ * POSTERIOR PREDICTIVE DRAWS from the model average of an ensemble -- multiple imputation, posterior predictive checks,
+ * synthetic rows -- for rows [row0, row0 + nrows) of the view, in one pass: row r draws a chain with probability
+ * ~ w_c p(x_r,observed | state_c), a group of that chain ~ CRP term x likelihood of the observed entries, and its entries
+ * from that group's predictive.  R = row_id0 + r is the row's global id.  flags: 0 or MSC_PRED_MASKED_ONLY.
+ *   chain_out_dev, z_out_dev   nullable; int32[nrows]: the chain and the group row r used, or -1 / -1 for a skipped row.
+ *   out_dev   one entry per state feature, as for msc_sample_predictive: NULL = not drawn, else nrows values of the
+ *             family's type (bb uint8, gp / bnb uint32, dd int32, nich float).
+ * 1. Chain weights.  Lf[c][r] is the float msc_chains_score_marginal(ch, view, cols, row0, nrows, NULL, 0, ...) writes to
+ *    chain_logp_dev for chain c and row r (every feature counts, masked entries contribute nothing, no leave-one-out);
+ *    lw_c is that call's normalised log weight of logw_dev (NULL: equal weights; -inf leaves a chain out).  The draw reads
+ *    those very bits: the two launches of that call run first, into a scratch of the handle.
+ * 2. Chain draw.  One Philox4x32-10 block, key = seed ^ 0xC2B2AE3D27D4EB4F, counter = (R & 0xffffffff, R >> 32,
+ *    sweep & 0xffffffff, 0x80000000); u1 from its words (w0, w1), u2 from (w2, w3), each msc_sample_predictive's two-word
+ *    uniform ((a >> 5) * 2^26 + (b >> 6) + 0.5) * 2^-53.  In double, chains ascending: a_c = lw_c + (double)Lf[c][r],
+ *    M = max a_c, e_c = exp(a_c - M) (0 for -inf), S = sum e_c; the row's chain is the smallest c whose running sum
+ *    e_0 + .. + e_c exceeds u1 * S, or, if rounding lets none exceed it, the last c with e_c > 0.  If no a_c is finite, or a
+ *    weight is NaN or +inf, the row is SKIPPED as msc_sample_predictive skips a row: chain_out[r] = z_out[r] = -1 and none
+ *    of its value outputs is written.
+ * 3. Group draw in the chosen chain c.  t[k], k ascending, is the float total msc_chains_score_marginal forms for (chain
+ *    c, row, group k): the features' scores added in ascending feature order (table lookups, the compensated nich
+ *    evaluation, gp / bnb counts beyond the exact table in the large-count forms), then the CRP term lo first and hi last,
+ *    empty slots sharing alpha.  In double, m = max t, e_k = exp(t[k] - m); a first pass over the groups forms m and
+ *    s = sum e_k together (s is rescaled when the maximum rises), a second the running sum: the group is the smallest k
+ *    whose running sum exceeds u2 * s, with the chain draw's fallback.
+ * 4. Values.  Every drawn entry of a row with chain c and group k equals, bit for bit, what
+ *    msc_sample_predictive(states[c], ..., z = k for that row, same flags, seed, sweep, row_id0) writes: the same counters
+ *    (key = seed, the 0x80000000 | f << 16 | b streams), the same parameter formulas in double read from chain c's raw
+ *    sufficient statistics and hp.  With MSC_PRED_MASKED_ONLY observed entries are copied.
+ * 5. A row's results depend on the row alone: a call over a sub-range with a matching row_id0 gives the whole call's bits,
+ *    and a repeated call the same bits.  The rows go through the handle's scratch (at most 256 MiB of Lf) a chunk at a
+ *    time, which moves no bit.  No atomics.  m imputations are m calls with sweep = 0 .. m - 1.
+ * 6. Every member is read-only apart from the view it is left bound to: tables, counts, hp, alpha and the sweeps' device
+ *    (seed, sweep) pair stay as they were (a later msc_chains_sweep on the training view gives the bits it would have
+ *    given without this call).  Asynchronous on the context's stream; the call synchronises with the device no more than
+ *    msc_chains_score_marginal does.
+ * Families: bb, gp, bnb, dd, nich; MSC_EUNSUPPORTED for a noop feature with a non-NULL output.
+ * nrows == 0 binds the view, writes nothing and returns MSC_OK.
+ * Errors, with nothing written: those of msc_chains_score_marginal -- MSC_EINVAL for a null ch or view, nrows >= 2^32, rows
+ * outside the view, a column that does not fit its feature, a member between msc_sweep_step_begin and
+ * msc_state_commit_reduce (the index is named), members whose exact gp / bnb tables differ in their rows -- and
+ * MSC_EINVAL for unknown flags, a null out_dev and a drawn feature index >= 32768; MSC_EDEVICE when an earlier kernel
+ * reported an error.
+ */
+int msc_chains_sample_predictive(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                 uint64_t nrows, uint64_t row_id0, const double *logw_dev, uint32_t flags, uint64_t seed,
+                                 uint64_t sweep, int32_t *chain_out_dev, int32_t *z_out_dev, void *const *out_dev);
+
+/*
  * The BLOCKED (uncollapsed) Gibbs sampler for the truncated stick-breaking Dirichlet process mixture (Ishwaran & James,
  * JASA 2001): an exact sampler that is parallel over rows.  With ngroups = K slots a sweep draws, given the tables,
  * every slot's component parameters from their conjugate posteriors and the mixture weights from the stick-breaking
