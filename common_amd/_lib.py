@@ -161,6 +161,11 @@ _SIGS = {
     "msc_chains_sample_predictive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                                C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    # (ch, view, cols, nrows, row_id0, z_dev, ld_z, nproposals, launch_iters, host_seeds, sweep, log_dev, trace_dev,
+    #  proposed_dev, counters_dev)
+    "msc_chains_split_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                         C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     # (ch, coords, n, slots_dev, ld_slots, host_seeds, sweep, values_host, evals_host)
     "msc_chains_hp_slice": (C.c_int, [C.c_void_p, C.POINTER(SliceCoord), C.c_uint32, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -46,6 +46,25 @@ def chain_seeds(seed, nchains):
     return seeds
 
 
+# what ChainEnsemble.split_merge returns: counters int64 device tensor [nchains, 5] = {splits proposed, splits accepted,
+# merges proposed, merges accepted, void} of THIS call; log float64 [nchains, nproposals, 8], trace and proposed int32
+# [nchains, nproposals, nrows] on the device, or None where not asked for
+SplitMergeResult = collections.namedtuple("SplitMergeResult", ["counters", "log", "trace", "proposed"])
+
+SPLIT_MERGE_MAX_LAUNCH_ITERS = 1024
+
+
+def split_merge_args(seed, nchains, nproposals, launch_iters):
+    """the argument checks of ChainEnsemble.split_merge that need no device -> (seeds, nproposals, launch_iters)"""
+    seeds = chain_seeds(seed, nchains)
+    nproposals, launch_iters = int(nproposals), int(launch_iters)
+    if not 0 <= nproposals < (1 << 32):
+        raise ValueError("nproposals must be in [0, 2^32)")
+    if not 0 <= launch_iters <= SPLIT_MERGE_MAX_LAUNCH_ITERS:
+        raise ValueError("launch_iters must be in [0, %d]" % SPLIT_MERGE_MAX_LAUNCH_ITERS)
+    return seeds, nproposals, launch_iters
+
+
 def _per_chain(what, value, nchains, is_one):
     """one value for all chains, or a sequence of one per chain -> list of nchains"""
     if value is None:
@@ -64,14 +83,16 @@ class ChainEnsemble(object):
     alpha: one float or nchains floats.  hps: one list with an hp (dict or packed array) per feature, used by every chain,
     or nchains such lists.  ens.states[c] is an ordinary State: get_ss, hp_slice, predictive_logp, set_hp, ... work on it
     between sweeps.  ens.z: int32 [nchains, nrows] on the device once assign() / seat() has run; ens.logw: float64
-    [nchains] on the device, zeroed there, the log weights visit() adds the visits' log predictives to."""
+    [nchains] on the device, zeroed there, the log weights visit() adds the visits' log predictives to;
+    ens.split_merge_counters: int64 [nchains, 5] on the device, zeroed there, what run(split_merge=n) adds its proposals'
+    counters to."""
 
     def __init__(self, ctx, features, ngroups, nchains, alpha=None, hps=None):
         nchains = int(nchains)
         if nchains < 1:
             raise ValueError("nchains must be >= 1")
         self.ctx, self.nchains, self.K = ctx, nchains, int(ngroups)
-        self.states, self._h, self.z, self.logw = [], None, None, None
+        self.states, self._h, self.z, self.logw, self.split_merge_counters = [], None, None, None, None
         alphas = _per_chain("alpha", alpha, nchains, lambda a: isinstance(a, (int, float, np.floating, np.integer)))
         hpsets = _per_chain("hps", hps, nchains, lambda h: len(h) > 0 and isinstance(h[0], (dict, np.ndarray)))
         try:
@@ -103,6 +124,7 @@ class ChainEnsemble(object):
         zt = zt.to(self.ctx.torch_device)
         self.z = (zt.expand(self.nchains, n) if zt.dim() == 1 else zt).contiguous().clone()
         self.logw = torch.zeros(self.nchains, dtype=torch.float64, device=self.ctx.torch_device)
+        self.split_merge_counters = torch.zeros((self.nchains, 5), dtype=torch.int64, device=self.ctx.torch_device)
         for c, st in enumerate(self.states):
             st.accumulate(view, self.z[c])
         self._view = view
@@ -265,9 +287,50 @@ class ChainEnsemble(object):
                                                  evals.ctypes.data_as(C.c_void_p)))
         return values, evals
 
-    def run(self, view, niters, seed, hp=None, sweep=0, order=None, trace_every=None, zmatrix=None):
+    # split-merge proposals --------------------------------------------------------
+    def split_merge(self, view, seed, sweep=0, nproposals=1, launch_iters=2, want_log=False, want_trace=False,
+                    want_proposed=False, row_id0=0):
+        """nproposals split-merge proposals on EVERY chain in one launch (msc_chains_split_merge; asynchronous, no host
+        synchronisation), proposal p with the sweep counter sweep + p.  seed: an int (chain c takes seed + c) or nchains
+        ints.  Chain c proposes, decides and moves as ens.states[c].split_merge(view, ens.z[c], seeds[c], sweep, nproposals,
+        launch_iters) does -- the same streams and arithmetic; only the order of the double sums differs -- over all rows of
+        the view.  Every table of every state must be that of its row of ens.z (as after assign(), sweep() or this call) and
+        is current again on return: a sweep can follow at once.
+        -> SplitMergeResult(counters, log, trace, proposed): counters int64 [nchains, 5] = {splits proposed, accepted,
+        merges proposed, accepted, void} of this call; with want_log float64 [nchains, nproposals, 8] = State.split_merge's
+        log rows; with want_trace int32 [nchains, nproposals, nrows], z after every proposal; with want_proposed int32
+        [nchains, nproposals, nrows], the proposed pair labels (-1 outside the two groups); all on the device, None where
+        not asked for.  A shape whose single proposal is estimated beyond a launch's budget raises MicroscopesHipError
+        (unsupported): loop over ens.states[c].split_merge there, whose kernels are parallel over rows."""
+        self._check_open()
+        seeds, nprop, iters = split_merge_args(seed, self.nchains, nproposals, launch_iters)
+        if self.z is None:
+            raise ValueError("no assignment yet: call assign() or seat() first")
+        n = int(view.nrows)
+        if self.z.shape[1] != n:
+            raise ValueError("the view has %d rows, the assignment %d" % (n, self.z.shape[1]))
+        dev = self.ctx.torch_device
+        counters = torch.zeros((self.nchains, 5), dtype=torch.int64, device=dev)
+        log = torch.zeros((self.nchains, nprop, 8), dtype=torch.float64, device=dev) if want_log else None
+        trace = torch.empty((self.nchains, nprop, n), dtype=torch.int32, device=dev) if want_trace else None
+        proposed = torch.empty((self.nchains, nprop, n), dtype=torch.int32, device=dev) if want_proposed else None
+        for st in self.states:
+            st._drop_subsets()
+            st._bound_view = view        # (the library keeps no reference to a view: the states do, for the last one bound)
+
+        def ptr(t):
+            return A.ptr(t) if t is not None and t.numel() else None
+
+        L.check(self.ctx.lib.msc_chains_split_merge(
+            self._h, view._h, self.states[0]._cols(None), n, int(row_id0), self._z_at(0), int(self.z.stride(0)), nprop, iters,
+            (C.c_uint64 * self.nchains)(*seeds), int(sweep), ptr(log), ptr(trace), ptr(proposed), A.ptr(counters)))
+        return SplitMergeResult(counters=counters, log=log, trace=trace, proposed=proposed)
+
+    def run(self, view, niters, seed, hp=None, sweep=0, order=None, trace_every=None, zmatrix=None, split_merge=None):
         """niters iterations of the sampler on every chain: iteration i is self.sweep(view, 1, seed, sweep=sweep + i,
-        order=order) followed, when hp (a hypers.EnsembleHpSlice of this ensemble) is given, by hp.step(seed, sweep + i)
+        order=order) followed, when split_merge=n is given, by self.split_merge(view, seed, sweep=(sweep + i) * n,
+        nproposals=n) (whose counters are added to ens.split_merge_counters) and, when hp (a hypers.EnsembleHpSlice of this
+        ensemble) is given, by hp.step(seed, sweep + i)
         -- exactly those calls, so exactly what they give made by hand.  -> RunResult(trace, values): trace the int32
         device tensor [nchains, niters // trace_every, nrows] of every chain's z after each trace_every-th iteration
         (trace_every None: after every iteration when a zmatrix is given, else no trace and trace is None); values the
@@ -281,6 +344,8 @@ class ChainEnsemble(object):
             raise ValueError("niters must be >= 0")
         if hp is not None and getattr(hp, "ens", None) is not self:
             raise ValueError("hp must be an EnsembleHpSlice of this ensemble")
+        if split_merge is not None and not 0 <= int(split_merge) < (1 << 32):
+            raise ValueError("split_merge must be None or a number of proposals in [0, 2^32)")
         if zmatrix is not None and trace_every is None:
             trace_every = 1
         trace = None
@@ -293,6 +358,9 @@ class ChainEnsemble(object):
         values = np.zeros((self.nchains, niters, ncoords), dtype=np.float32)
         for i in range(niters):
             self.sweep(view, 1, seed, sweep=sweep + i, order=order)
+            if split_merge is not None:
+                n_sm = int(split_merge)
+                self.split_merge_counters += self.split_merge(view, seed, sweep=(sweep + i) * n_sm, nproposals=n_sm).counters
             if hp is not None:
                 hp.step(seed, sweep + i)
                 if ncoords:

@@ -92,6 +92,11 @@ int slice_plan(const msc_state *st, const msc_slice_coord *coords, uint32_t n, S
 void slice_targets(const msc_state *st, const SlicePlan &plan, SliceTarget *targets);
 int slice_installed(msc_state *st, const SlicePlan &plan, const msc_slice_coord *coords, const float *val, const uint32_t *ev,
                     const uint32_t *stat, float *values_host, uint32_t *evals_host, int64_t chain);
+// ---- what blocked.cpp defines for msc_chains_split_merge (chains.cpp): the move's route for a member, and the member's
+// pair state as the pair half of its table entry (launchers.hpp SmChain) ----
+struct SmChain;
+int sm_chain_route(const msc_state *st);
+int sm_chain_pair(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t nrows, SmChain *entry);
 #pragma GCC visibility pop
 
 }  // namespace msc

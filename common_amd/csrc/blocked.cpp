@@ -273,6 +273,28 @@ extern "C" int msc_split_merge(msc_state *st, const msc_dataview *view, const ui
   return accumulate_impl(st, view, cols, row0, nrows, z_dev, MSC_ACC_RESET);
 }
 
+// What msc_chains_split_merge (chains.cpp) takes from here for one member: whether the move takes the state at all, and
+// the member's pair state -- created at the first call, its hyper-parameters and alpha following the member's, bound to the
+// view, its parameter-table features as the kernels read them -- as the pair half of the chain's table entry.
+namespace msc {
+int sm_chain_route(const msc_state *st) {
+  const BlockedRoute route = route_splitmerge(st);
+  return route.rc != MSC_OK ? fail(route.rc, "%s", route.why.c_str()) : MSC_OK;
+}
+int sm_chain_pair(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t nrows, SmChain *entry) {
+  MSC_TRY(sm_setup(st));
+  msc_state *pair = st->sm.pair;
+  MSC_TRY(bind_view(pair, view, cols, 0, nrows));
+  MSC_TRY(blocked_setup(pair));
+  entry->pair_feats = pair->desc_dev;
+  entry->pair_blk = pair->blk.feats_dev;
+  entry->pair_tab = pair->blk.tab;
+  entry->pair_cnt_acc = pair->red_i64;
+  entry->pair_cnt_u32 = pair->cnt_u32;
+  return MSC_OK;
+}
+}  // namespace msc
+
 extern "C" int msc_split_merge_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
   MSC_REQUIRE(st, "null state");
   MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);

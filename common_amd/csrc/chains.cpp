@@ -1,6 +1,7 @@
 // chains.cpp -- the sequential collapsed Gibbs sweep and the ensembles of such chains (kernels_seq.hip):
-// msc_sweep_sequential and msc_chains_*, the ensemble's row predictive density (kernels_chains_marginal.hip) and its
-// posterior predictive draws (kernels_chains_pred.hip) among them.  Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
+// msc_sweep_sequential and msc_chains_*, the ensemble's row predictive density (kernels_chains_marginal.hip), its
+// posterior predictive draws (kernels_chains_pred.hip) and its split-merge proposals (kernels_chains_sm.hip) among them.
+// Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
 #include <algorithm>
 #include <memory>
 #include <new>
@@ -118,6 +119,10 @@ struct msc_chains {
   // group (int32 [2][chunk]), grown as marg_part is; the call's output pointers travel behind the MargFeat table
   msc::DevBuf<float> pred_lf;
   msc::DevBuf<int32_t> pred_cz;
+  // msc_chains_split_merge: the call's table, staged through the same two areas (stage_entries sizes them for it), and
+  // the chains' pair labels, int32 [nchains][nrows], grown by reserve_synced
+  msc::DevBuf<msc::SmChain> sm_tab;       // [nchains]
+  msc::DevBuf<int32_t> sm_ell;
   msc::Retired retired;
 };
 static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
@@ -126,6 +131,11 @@ static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area h
 static size_t marg_tail(uint32_t nfeat) { return (size_t)nfeat * (sizeof(msc::MargFeat) + sizeof(void *)); }
 static size_t marg_extra(uint32_t nfeat) { return (marg_tail(nfeat) + 16 + sizeof(msc::SeqChain) - 1) / sizeof(msc::SeqChain); }
 static size_t marg_feat_at(uint32_t nchains) { return ((size_t)nchains * sizeof(msc::MargChain) + 15) & ~(size_t)15; }
+// the SeqChain entries of a staging area: nchains entries of the widest table (SmChain), or the marginal call's tail
+static size_t stage_entries(uint32_t nchains, uint32_t nfeat) {
+  const size_t sm = ((size_t)nchains * sizeof(msc::SmChain) + sizeof(msc::SeqChain) - 1) / sizeof(msc::SeqChain);
+  return std::max(sm, nchains + marg_extra(nfeat));
+}
 
 // the pinned staging area whose turn it is, once no pending copy reads it; chains_staged records the copy out of it
 static int chains_stage(msc_chains *ch, int *area) {
@@ -171,10 +181,11 @@ extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc
   ch->states.assign(states, states + nchains);
   hipError_t e = ch->table_dev.alloc(nchains);
   if (e == hipSuccess) e = ch->pairs_dev.alloc(nchains);
+  if (e == hipSuccess) e = ch->sm_tab.alloc(nchains);
   if (e == hipSuccess) e = ch->marg_tab.alloc(marg_feat_at(nchains) + marg_tail(states[0]->nfeat), 16);
   if (e == hipSuccess) e = ch->marg_w.alloc(2 * (size_t)nchains);
   for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = ch->stage[i].alloc(nchains + marg_extra(states[0]->nfeat));
+    e = ch->stage[i].alloc(stage_entries(nchains, states[0]->nfeat));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ch->uploaded[i], hipEventDisableTiming);
   }
   if (e != hipSuccess) {
@@ -370,6 +381,107 @@ extern "C" int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, 
   // current, and they would stay the destination's old ones.)
   for (uint32_t c = 0; c < n; c++)
     if (host_ancestors[c] != c) ch->states[c]->valid.accumulated();
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Split-merge proposals for every chain in one launch (k_sm_chains, kernels_chains_sm.hip): workgroup c makes the
+// proposals of member c and keeps its tables current, as the sweep's kernel does.
+// ---------------------------------------------------------------------------
+// An upper estimate of one proposal of one chain, in microseconds: a fixed part (anchors, coins, decision, apply) plus
+// launch_iters + 2 passes -- launch_iters + 1 of suff-stats, draws and labels, and the decision's suff-stats -- each a fixed
+// part (barriers, the stick), a part per feature (a barrier, the slots' draws in double), a part per row (its label, the
+// dart, the two-way softmax) and a part per (row, feature) (a row's value is read once for the sums and once for the
+// scores), a row being the work of one of 256 threads.
+// Fitted to profiles/chains_splitmerge.txt (one nich column and the C3 mix of 64 columns, 4 096 and 65 536 rows,
+// launch_iters 0 / 2 / 5, 1 to 256 chains): what a pass adds there is at most 0.0163 us a row on one nich column and
+// 0.605 us a row on the C3 mix, below 0.009 + 0.0095 D; the estimate is above the measured time per proposal at every
+// shape of the table, by 19 % where it is closest.
+constexpr double kSmFixedUs = 30.0, kSmPassUs = 25.0, kSmPassFeatUs = 3.0, kSmRowUs = 0.009, kSmRowFeatUs = 0.0095;
+static double sm_proposal_us(uint64_t nrows, uint32_t nfeat, uint32_t launch_iters) {
+  const double passes = (double)launch_iters + 2.0;
+  return kSmFixedUs + passes * (kSmPassUs + kSmPassFeatUs * (double)nfeat + (kSmRowUs + kSmRowFeatUs * (double)nfeat) * (double)nrows);
+}
+
+extern "C" int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t nrows,
+                                      uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, uint32_t nproposals,
+                                      uint32_t launch_iters, const uint64_t *host_seeds, uint64_t sweep, double *log_dev,
+                                      int32_t *trace_dev, int32_t *proposed_dev, uint64_t *counters_dev) {
+  MSC_REQUIRE(ch && view, "null argument");
+  const uint32_t n = (uint32_t)ch->states.size();
+  if (n == 0) return MSC_OK;
+  MSC_REQUIRE((z_dev && host_seeds) || nproposals == 0, "null argument");
+  MSC_REQUIRE(launch_iters <= 1024, "launch_iters %u beyond 1024", launch_iters);
+  MSC_REQUIRE(nrows == view->nrows, "msc_chains_split_merge covers the whole view: nrows %llu, the view has %llu rows",
+              (unsigned long long)nrows, (unsigned long long)view->nrows);
+  MSC_REQUIRE(nrows < (1ull << 32), "msc_chains_split_merge takes at most 2^32 - 1 rows");
+  MSC_REQUIRE(ld_z >= nrows, "msc_chains_split_merge: ld_z %llu < nrows %llu", (unsigned long long)ld_z,
+              (unsigned long long)nrows);
+  for (uint32_t c = 0; c < n; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_split_merge: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  const msc_state *st0 = ch->states[0];
+  MSC_TRY(sm_chain_route(st0));                             // (equal feature lists: one answer for all)
+  // a launch takes the whole proposals that fit the sweep's launch budget, by the estimate above times the rounds the grid
+  // runs in (one workgroup a compute unit is what the estimate was measured at).  What is refused is a proposal that
+  // alone exceeds the budget in ONE round: with more chains than compute units a launch of one proposal -- the least a
+  // launch can take -- runs `rounds` such rounds, as msc_chains_sweep's launch of one visit does.
+  msc_context *ctx = ch->ctx;
+  const double one_us = sm_proposal_us(nrows, st0->nfeat, launch_iters);
+  if (one_us > kSeqLaunchUs)
+    return fail(MSC_EUNSUPPORTED, "msc_chains_split_merge: one proposal over %llu rows x %u features at launch_iters %u is "
+                "estimated at %.0f us, beyond a launch's %.0f us: this kernel gives a chain one workgroup; "
+                "msc_split_merge (State.split_merge) on each member has the row-parallel kernels for large tables",
+                (unsigned long long)nrows, st0->nfeat, launch_iters, one_us, kSeqLaunchUs);
+  if (nproposals == 0) return MSC_OK;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  hipStream_t s = ctx->stream;
+  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, 0, nrows));
+  // every table of every member current before, as msc_chains_sweep
+  for (msc_state *st : ch->states) MSC_TRY(ensure_all_current(st));
+  MSC_HIP(reserve_synced(s, ch->sm_ell, (size_t)n * std::max<uint64_t>(nrows, 1)));
+  int a = 0;
+  MSC_TRY(chains_stage(ch, &a));
+  SmChain *tab = reinterpret_cast<SmChain *>(ch->stage[a].get());
+  for (uint32_t c = 0; c < n; c++) {
+    msc_state *st = ch->states[c];
+    SmChain &e = tab[c];
+    MSC_TRY(sm_chain_pair(st, view, cols, nrows, &e));
+    e.feats = st->desc_dev;
+    e.cnt_acc = st->red_i64;
+    e.cnt_u32 = st->cnt_u32;
+    e.crp = st->logpc;
+    e.z = z_dev + (size_t)c * ld_z;
+    e.ell = ch->sm_ell.get() + (size_t)c * nrows;
+    e.log = log_dev ? log_dev + (size_t)c * nproposals * 8 : nullptr;
+    e.trace = trace_dev ? trace_dev + (size_t)c * nproposals * nrows : nullptr;
+    e.proposed = proposed_dev ? proposed_dev + (size_t)c * nproposals * nrows : nullptr;
+    e.counters = counters_dev ? reinterpret_cast<unsigned long long *>(counters_dev) + (size_t)c * 5 : nullptr;
+    e.seed = host_seeds[c];
+    e.alpha = st->alpha;
+    e.pad = 0;
+  }
+  MSC_HIP(hipMemcpyAsync(ch->sm_tab, tab, sizeof(SmChain) * n, hipMemcpyHostToDevice, s));
+  MSC_TRY(chains_staged(ch, a, s));
+  const uint32_t cus = (uint32_t)std::max(1, ctx->num_cus);
+  const double rounds = (double)((n + cus - 1) / cus);
+  const uint32_t per_launch = (uint32_t)std::max(1.0, std::min((double)nproposals, kSeqLaunchUs / (one_us * rounds)));
+  const uint32_t pair_kpad = st0->sm.pair->kpad;
+  for (uint32_t p0 = 0; p0 < nproposals; p0 += per_launch) {
+    const uint32_t p1 = std::min(nproposals, p0 + per_launch);
+    const int rc = launch_sm_chains(s, ch->sm_tab, n, (int)st0->nfeat, st0->K, st0->kpad, pair_kpad, nrows, row_id0, p0, p1,
+                                    launch_iters, sweep);
+    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sm_chains does not take this shape");
+    if (rc) return fail(MSC_EHIP, "k_sm_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  // the kernel kept every table of every member current (which also drops a blocked draw made before); a member's pair
+  // state holds the last proposal's suff-stats, as after msc_split_merge's last commit
+  for (msc_state *st : ch->states) {
+    st->valid.kept_current();
+    st->sm.pair->valid.accumulated();
+    st->sm.pair->valid.committed();
+  }
   return MSC_OK;
 }
 

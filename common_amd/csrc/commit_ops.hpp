@@ -135,4 +135,21 @@ MSC_DEV void prepare_group(const FeatDesc &fd, uint32_t k, uint32_t kpad, uint32
   }
 }
 
+// score_data of one (feature, group) from the reference's fields: the body of k_score_data (kernels_state.hip), shared
+// with the ensemble's split-merge kernel (kernels_chains_sm.hip)
+MSC_DEV double score_data_group(const FeatDesc &fd, uint32_t k, uint32_t kpad) {
+  double s = 0;
+  switch (fd.family) {
+    case MSC_BB: s = bb_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k]); break;
+    case MSC_BBNC: s = bbnc_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k], fd.raw_f32[k]); break;
+    case MSC_GP: s = gp_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k], (double)fd.raw_f32[k]); break;
+    case MSC_DD: s = dd_score_data(fd.hp, fd.dim, fd.raw_u32 + kpad + k, kpad, fd.raw_u32[k]); break;
+    case MSC_NICH: s = nich_score_data(fd.hp, fd.raw_u32[k], fd.raw_f32[k], fd.raw_f32[kpad + k]); break;
+    case MSC_BNB: s = bnb_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k]); break;
+    case MSC_DM: s = dm_score_data(fd.hp, fd.dim, fd.raw_u32 + k, kpad, (double)fd.raw_f32[k]); break;
+    default: break;
+  }
+  return s;
+}
+
 }  // namespace msc

@@ -3,7 +3,9 @@
 //   k_blocked_sticks    one workgroup: V_k ~ Beta(1 + n_k, alpha + sum_{l > k} n_l) for every slot, then
 //                       log pi_k = log V_k + sum_{l < k} log(1 - V_l), summed in slot order in double
 //   k_blocked_draw      one thread per (feature, slot): the slot's parameters from their conjugate posterior, stored as
-//                       the float slices the assign kernels read (blocked_post.hpp)
+//                       the float slices the assign kernels read (blocked_post.hpp); a thread's work is
+//                       blocked_draw.hpp's blk_draw_slot, as a slot's stick draw is its blk_stick_slot: k_sm_chains
+//                       (kernels_chains_sm.hip) calls the same two
 //   k_blocked_assign    lane <-> row: s_k = log pi_k + sum_f loglik_f(x_rf | slot k) over all slots, eight slots at a
 //                       time with the slots' slices as wave-uniform operands; pass 1 keeps an online max and sum of exp,
 //                       pass 2 recomputes the scores and walks the CDF to u sum.  No cross-lane work.
@@ -13,6 +15,7 @@
 //   k_blocked_top_slot  the highest occupied slot
 // The row's value codes and the scores of eight slots (blk_code, blk_tile_scores) are blocked_score.hpp's, shared with
 // the split-merge move.
+#include "blocked_draw.hpp"
 #include "blocked_post.hpp"
 #include "blocked_score.hpp"
 #include "family_math.hpp"
@@ -48,10 +51,8 @@ __global__ __launch_bounds__(256) void k_blocked_sticks(const uint32_t *__restri
     __syncthreads();
     for (uint32_t i = t; i < n; i += blockDim.x) {
       const uint32_t k = (uint32_t)c0 + i;
-      double a, b, lv, l1;
-      blocked::stick_post((double)cnt[k], sh[i], (double)alpha, &a, &b);
-      pred::Stream s(key, k, sweep, blocked::kStickTag);
-      blocked::draw_stick(s, a, b, k + 1 == K, &lv, &l1);
+      double lv, l1;
+      blk_stick_slot((double)cnt[k], sh[i], (double)alpha, key, k, sweep, k + 1 == K, &lv, &l1);
       work[k] = lv;
       work[(size_t)K + k] = l1;
     }
@@ -83,44 +84,7 @@ __global__ __launch_bounds__(64) void k_blocked_draw(const BlkFeat *__restrict__
   const BlkFeat &bf = fs[blockIdx.y];
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K || bf.nslices == 0) return;
-  float *out = tab + (size_t)bf.slice0 * kpad + k;
-  const float *hp = bf.hp;
-  const uint32_t *u = bf.raw_u32;
-  switch (bf.family) {
-    case MSC_BB: {
-      double a, b;
-      blocked::bb_post(hp, (double)u[k], (double)u[kpad + k], &a, &b);
-      pred::Stream s(key, k, sweep, bf.tag);
-      blocked::draw_bb(s, a, b, out, kpad);
-      break;
-    }
-    case MSC_GP: {
-      double shape, rate;
-      blocked::gp_post(hp, (double)u[k], (double)u[kpad + k], &shape, &rate);
-      pred::Stream s(key, k, sweep, bf.tag);
-      blocked::draw_gp(s, shape, rate, out, kpad);
-      break;
-    }
-    case MSC_BNB: {
-      double a, b;
-      blocked::bnb_post(hp, (double)u[k], (double)u[kpad + k], &a, &b);
-      pred::Stream s(key, k, sweep, bf.tag);
-      blocked::draw_bnb(s, a, b, (double)hp[2], out, kpad);
-      break;
-    }
-    case MSC_NICH: {
-      double mu_n, kappa_n, sigmasq_n, nu_n;
-      blocked::nich_post(hp, (double)u[k], (double)bf.raw_f32[k], (double)bf.raw_f32[kpad + k], &mu_n, &kappa_n,
-                         &sigmasq_n, &nu_n);
-      pred::Stream s(key, k, sweep, bf.tag);
-      blocked::draw_nich(s, mu_n, kappa_n, sigmasq_n, nu_n, out, kpad);
-      break;
-    }
-    case MSC_DD:   // raw rows {count_sum, counts[dim]}
-      blocked::draw_dd(key, k, sweep, bf.tag, bf.dim, hp, u + (size_t)kpad + k, kpad, out, kpad);
-      break;
-    default: break;
-  }
+  blk_draw_slot(bf, k, kpad, key, sweep, tab);
 }
 
 __global__ __launch_bounds__(256) void k_blocked_top_slot(const uint32_t *__restrict__ cnt, uint32_t K,

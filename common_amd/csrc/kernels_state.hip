@@ -392,17 +392,7 @@ __global__ __launch_bounds__(256) void k_score_data(const FeatDesc *__restrict__
   const FeatDesc fd = feats[blockIdx.y];
   const uint32_t k = blockIdx.x * 256 + threadIdx.x;
   if (k >= K) return;
-  double s = 0;
-  switch (fd.family) {
-    case MSC_BB: s = bb_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k]); break;
-    case MSC_BBNC: s = bbnc_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k], fd.raw_f32[k]); break;
-    case MSC_GP: s = gp_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k], (double)fd.raw_f32[k]); break;
-    case MSC_DD: s = dd_score_data(fd.hp, fd.dim, fd.raw_u32 + kpad + k, kpad, fd.raw_u32[k]); break;
-    case MSC_NICH: s = nich_score_data(fd.hp, fd.raw_u32[k], fd.raw_f32[k], fd.raw_f32[kpad + k]); break;
-    case MSC_BNB: s = bnb_score_data(fd.hp, fd.raw_u32[k], fd.raw_u32[kpad + k]); break;
-    case MSC_DM: s = dm_score_data(fd.hp, fd.dim, fd.raw_u32 + k, kpad, (double)fd.raw_f32[k]); break;
-    default: break;
-  }
+  const double s = score_data_group(fd, k, kpad);
   out[(size_t)blockIdx.y * K + k] = (float)s;
 }
 

@@ -247,6 +247,34 @@ int launch_sm_decide(hipStream_t stream, SmProp *prop, const double *part, uint3
 int launch_sm_relabel(hipStream_t stream, uint64_t nrows, int32_t *z, const int32_t *ell, const SmProp *prop,
                       const uint32_t *pair_cnt, uint32_t *cnt);
 
+// kernels_chains_sm.hip: the same move for every chain of an ensemble in one launch (msc_chains_split_merge), workgroup c
+// on chain c: proposals [p0, p1) of the call, whole proposals only.  What differs per chain:
+constexpr int kSmChainsThreads = 256;      // the workgroup: one wave a SIMD, as the sequential chain's
+struct SmChain {
+  const FeatDesc *feats;       // the chain's state: descriptors, counts (additive, u32), CRP terms
+  long long *cnt_acc;
+  uint32_t *cnt_u32;
+  float *crp;
+  int32_t *z;                  // int32 [nrows]
+  const FeatDesc *pair_feats;  // the chain's pair state (blocked.cpp sm_setup): descriptors, parameter-table features,
+  const BlkFeat *pair_blk;     // the parameter table theta (msc_split_merge_tables' layout), the pair's counts
+  float *pair_tab;
+  long long *pair_cnt_acc;
+  uint32_t *pair_cnt_u32;
+  int32_t *ell;                // int32 [nrows]: the pair labels (the handle's scratch)
+  double *log;                 // double [nproposals][8] or null
+  int32_t *trace;              // int32 [nproposals][nrows] or null
+  int32_t *proposed;           // int32 [nproposals][nrows] or null
+  unsigned long long *counters;   // [5] or null
+  uint64_t seed;               // the chain's seed (the streams' keys: splitmerge_math.hpp)
+  float alpha;
+  uint32_t pad;
+};
+// -2: shape not covered (more than kSeqMaxFeat features)
+int launch_sm_chains(hipStream_t stream, const SmChain *chains_dev, uint32_t nchains, int nfeat, uint32_t K, uint32_t kpad,
+                     uint32_t pair_kpad, uint64_t nrows, uint64_t row_id0, uint32_t p0, uint32_t p1, uint32_t launch_iters,
+                     uint64_t sweep);
+
 // kernels_niw.hip
 int launch_niw_prepare(hipStream_t stream, const FeatDesc *feats_dev, uint32_t f, uint32_t dim, uint32_t K,
                        uint32_t kpad);

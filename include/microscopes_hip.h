@@ -678,6 +678,41 @@ int msc_split_merge(msc_state *st, const msc_dataview *view, const uint32_t *col
                     uint64_t sweep, double *log_dev, int32_t *trace_dev, int32_t *proposed_dev, uint64_t *counters_dev);
 int msc_split_merge_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld);
 
+/*
+ * SPLIT-MERGE PROPOSALS FOR EVERY CHAIN OF AN ENSEMBLE in one launch (kernels_chains_sm.hip k_sm_chains): workgroup c
+ * makes nproposals proposals on member c, proposal p with the sweep counter sweep + p under the key host_seeds[c].  A
+ * proposal is msc_split_merge's move above, step for step -- the same streams, anchors, coins, passes, draws, label darts,
+ * acceptance ratio and dart -- so chain c proposes, decides and moves as msc_split_merge(states[c], ..., host_seeds[c],
+ * ...) does.  Only the ORDER in which the double sums are formed differs (nich sum x and sum x^2, gp sum ln Gamma(v + 1),
+ * log q): a thread adds its rows r = t, t + 256, ... in that order, a wave's lanes combine by shuffles, the waves are added
+ * in wave order.  The order depends on nrows alone, so a call repeats its bits, and a call of P proposals gives the bits of
+ * calls of P1 + P2 = P proposals with sweep advanced by P1.  States whose suff-stats are integers (bb, bnb, dd) match
+ * msc_split_merge in every output bit but log q and log A.
+ *
+ * The call covers rows [0, nrows) of the view; nrows must be the view's row count.  z_dev: int32, chain c's row at
+ * z_dev + c * ld_z.  EVERY TABLE OF EVERY MEMBER MUST BE THAT OF ITS z ROW at the call -- as after msc_accumulate of the
+ * row, msc_chains_sweep or this call -- because an accepted proposal rewrites the two groups involved and leaves the rest
+ * as it was.  On return every table of every member is current for the new z (additive sums, fields, score constants,
+ * counts, CRP terms), as msc_chains_sweep leaves them: a sweep that follows launches nothing before its kernel.  A blocked
+ * draw made before is stale.  A void or rejected proposal changes nothing but its outputs.
+ *
+ * Outputs: msc_split_merge's with a leading chain dimension, all nullable, all device memory: log_dev
+ * double[nchains][nproposals][8], trace_dev and proposed_dev int32[nchains][nproposals][nrows], counters_dev
+ * uint64[nchains][5], added to.  msc_split_merge_tables(states[c], ...) afterwards gives theta* of chain c's last proposal.
+ *
+ * A launch takes the whole proposals that fit a launch's time budget by an estimate from (nrows, features, launch_iters);
+ * a chain has one workgroup, so the call suits an ensemble's shapes (thousands of rows a chain).  Asynchronous: no host
+ * synchronisation.  nproposals == 0 checks its arguments, writes nothing and returns MSC_OK.
+ * Errors, all before the first launch: MSC_EINVAL for a null argument, launch_iters > 1024, nrows != the view's rows,
+ * ld_z < nrows, a member between msc_sweep_step_begin and msc_state_commit_reduce (the index is named); MSC_EUNSUPPORTED
+ * when one proposal alone is estimated beyond the budget (use msc_split_merge on each member: its kernels are parallel
+ * over rows).  Families: bb, gp, bnb, dd, nich, noop (what an ensemble holds).
+ */
+int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t nrows,
+                           uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, uint32_t nproposals, uint32_t launch_iters,
+                           const uint64_t *host_seeds, uint64_t sweep, double *log_dev, int32_t *trace_dev,
+                           int32_t *proposed_dev, uint64_t *counters_dev);
+
 /* ---- multi-GPU hook ---------------------------------------------------- */
 /*
  * The additive form of every table, ready for a sum all-reduce across row
