@@ -1,6 +1,7 @@
 // abi.cpp -- the core of the extern "C" surface declared in include/microscopes_hip.h: library and context, allocation,
-// dataviews, the state with its plan (plan_layout, plan_groups, bind_view), tables and ensure steps, the score,
-// accumulate and sweep routes and entries, the reduce and column-bound entries, relations and msc_value_op_single.
+// dataviews, the state with its plan (plan_groups runs the steps of tile_plan.hpp; bind_view), tables and ensure steps,
+// the score, accumulate and sweep entries (they launch what the routes of route.hpp return), the reduce and column-bound
+// entries, relations and msc_value_op_single.
 // The subsystems built on it have a unit each -- blocked.cpp, chains.cpp, hyper.cpp, predict.cpp, summary.cpp -- and reach
 // it through abi_internal.hpp.
 // Host logic only: argument checking, table bookkeeping and kernel launches.
@@ -16,6 +17,7 @@
 #include "abi_internal.hpp"
 #include "launchers.hpp"
 #include "row_range.hpp"
+#include "tile_plan.hpp"
 
 namespace msc {
 
@@ -690,126 +692,6 @@ static void default_hp(int family, uint32_t dim, std::vector<float> &hp) {
   }
 }
 
-// The plan of the tile kernels (score_block.hpp).  They walk a reordered copy of the descriptors: first every
-// feature except the unmasked nich ones, in the caller's order, then the unmasked nich features, which get a phase
-// (and an inner loop) of their own.  (Float addition order follows this plan, not the caller's feature order.)
-// Consecutive features are packed into groups whose table blocks fit the LDS slot together: greedy, at most
-// kGrpRows rows per group, never across the two phases.
-// what the choice of kernels depends on, for one plan
-struct PlanFacts {
-  ScorePath path = MSC_PATH_TILE;      // (msc_state::tile_path)
-  bool tail_ok = false, tail_masked_nich = false, tail_dm = false;
-  uint32_t tail_max_rows = 0, tail_pack_rows = 0;
-};
-// the tile plans whose nich waves read the pack and the x matrix (msc::NichPos)
-static bool stages_nich(ScorePath path) { return path == MSC_PATH_TILE_ROLES || path == MSC_PATH_NICH_PACK; }
-
-// group packing, lookup kinds and runs of a plan `t` whose first `split` entries are the first phase (`extra`: one more
-// table row for a masked lookup column's zero row)
-static PlanFacts plan_layout(std::vector<FeatDesc> &t, uint32_t split, const std::vector<uint32_t> &extra, const Switches &sw) {
-  auto rows_of = [](const FeatDesc &d) -> uint32_t {
-    if (d.fuse_n >= 2) {
-      uint32_t rows = 1;
-      for (uint32_t j = 0; j < d.fuse_n; j++) rows *= d.fuse_radix;
-      return rows;
-    }
-    switch (d.family) {
-      case MSC_BB:
-      case MSC_BBNC: return 2;
-      case MSC_NICH: return 6;
-      // (a table up to the whole slot is staged -- on its own group if need be: a dd feature of 100 categories with 64 of
-      // them staged was a GENERIC feature to every tile kernel, 1.03 ms for four of them beside two nich columns on a
-      // million rows whatever K <= 256 is; staged whole they are lookup runs like any other)
-      case MSC_DD: return std::min<uint32_t>(d.dim, (uint32_t)kGrpRows);
-      case MSC_GP:
-      case MSC_BNB: return std::min<uint32_t>(d.vcap, (uint32_t)kGrpRows);
-      // dm: all dim + 1 tables or none (small counts: tens of rows).  Read from L2 they cost 2 KiB per row and
-      // stage -- 4 x dm(4) on 1M rows ran at the L2's bandwidth, 1.9 ms
-      case MSC_DM: return d.dm_meta != nullptr && d.dm_rows <= (uint32_t)kGrpRows ? d.dm_rows : 0;
-      default: return 0;
-    }
-  };
-  const uint32_t n = (uint32_t)t.size();
-  uint32_t f = 0;
-  while (f < n) {
-    const uint32_t limit = f < split ? split : n;
-    uint32_t used = 0, g = f;
-    while (g < limit && used + rows_of(t[g]) + extra[g] <= (uint32_t)kGrpRows) {
-      // (a nich block is staged whole: its members' constants are read side by side)
-      if (t[g].blk_end > g + 1 && t[g].blk_first == g && used > 0 && used + 6u * (t[g].blk_end - g) > (uint32_t)kGrpRows) break;
-      t[g].grp_off = used;
-      t[g].grp_rows = rows_of(t[g]) + extra[g];
-      used += t[g].grp_rows;
-      g++;
-    }
-    if (g == f) {                                           // (a block larger than the slot: a group of its own, nothing staged)
-      t[g].grp_off = 0;
-      t[g].grp_rows = 0;
-      g++;
-    }
-    for (uint32_t i = f; i < g; i++) t[i].grp_end = g;
-    f = g;
-  }
-  // Unmasked lookup features whose whole table is staged (so that no row can miss it) take the tight inner
-  // loop of the first phase; run_end lets a wave stay in it for a whole run of them.
-  for (uint32_t i = 0; i < n; i++) {
-    FeatDesc &d = t[i];
-    d.kind = MSC_KIND_GENERIC;
-    if (d.mask != nullptr || d.col == nullptr || d.grp_rows == 0) continue;
-    // (run_clamp: the largest row a value may select -- with the mask folded in that is the zero row)
-    if (d.fuse_n >= 2) d.kind = MSC_KIND_LOOKUP_U8, d.run_clamp = d.grp_rows - 1;
-    else if (d.family == MSC_BB || d.family == MSC_BBNC) d.kind = MSC_KIND_LOOKUP_U8, d.run_clamp = 1 + extra[i];
-    else if ((d.family == MSC_GP || d.family == MSC_BNB) && d.grp_rows >= d.vcap + extra[i]) d.kind = MSC_KIND_LOOKUP_U32, d.run_clamp = d.grp_rows - 1;
-    else if (d.family == MSC_DD && d.grp_rows >= d.dim + extra[i]) d.kind = MSC_KIND_LOOKUP_I32, d.run_clamp = d.dim - 1 + extra[i];
-  }
-  PlanFacts pf;
-  bool has_dm = false;
-  bool roles_ok = split > 0 && split < n;
-  for (uint32_t i = 0; i < n; i++) {
-    has_dm |= t[i].family == MSC_DM;
-    if (i < split && t[i].kind == MSC_KIND_GENERIC) roles_ok = false;
-  }
-  if (has_dm) roles_ok = false;
-  // the kernels whose waves are all nich waves (k_score_nich_pack): no first phase at all and two or more plain nich features,
-  // or a first phase of at most kPackMaxLookups lookup features beside at least twice as many nich features (the lookups
-  // are gathered from L2 there, ~0.03 ms a feature and million rows: 8 bb + 8 nich sweep 0.81 -> 0.70 ms, 2 gp + 12 nich
-  // 0.99 -> 0.86; with 16 bb + 4 nich -- four fused lookups, four nich -- the role-split kernels are as good or better)
-  const bool nich_only = (split == 0 && n >= 2) || (roles_ok && !has_dm && split <= (uint32_t)kPackMaxLookups && n - split >= 2 * split);
-  // staged lookup features and nothing else: k_score_lookups / k_sweep_lookups (sixteen lookup waves of 16 sums)
-  bool lookups_only = split == n && n > 0 && !has_dm;
-  for (uint32_t i = 0; i < n; i++) lookups_only &= t[i].kind != MSC_KIND_GENERIC;
-  // (roles_ok needs split < n and lookups_only split == n; nich_only wins over roles_ok)
-  pf.path = nich_only ? MSC_PATH_NICH_PACK : roles_ok ? MSC_PATH_TILE_ROLES : lookups_only ? MSC_PATH_LOOKUPS : MSC_PATH_TILE;
-  // the lane <-> row kernel for a partly filled last tile (k_score_tail_rows): lookup features only in the first phase
-  // (what it implements), whatever the second holds of plain nich features
-  pf.tail_ok = !sw.no_narrow_tail;
-  // (a masked nich column among them is evaluated like the second phase's features, under the row's mask; a dm feature
-  // whose dim + 1 tables are staged whole -- small counts: no row of the bound column is beyond them -- is dim + 1 lookups
-  // of (hi, lo) pairs, round 5; the kernel has one instantiation for either, none for both)
-  for (uint32_t i = 0; i < split; i++) {
-    const bool masked_nich = t[i].family == MSC_NICH && t[i].mask != nullptr && t[i].col != nullptr;
-    const bool staged_dm = t[i].family == MSC_DM && t[i].col != nullptr && t[i].dm_meta != nullptr && t[i].grp_rows != 0;
-    pf.tail_ok &= t[i].kind != MSC_KIND_GENERIC || masked_nich || staged_dm;
-    pf.tail_masked_nich |= masked_nich;
-    pf.tail_dm |= staged_dm;
-  }
-  if (pf.tail_dm && pf.tail_masked_nich) pf.tail_ok = false;
-  for (uint32_t i = split; i < n; i++) pf.tail_ok &= t[i].family == MSC_NICH && t[i].mask == nullptr && t[i].grp_rows == 6;
-  if (!pf.tail_ok) pf.tail_masked_nich = pf.tail_dm = false;
-  if (pf.tail_ok)
-    for (uint32_t i = 0; i < split; i++) {
-      const uint32_t rows = t[i].family == MSC_DM ? t[i].dm_rows : t[i].kind == MSC_KIND_GENERIC ? 0u : t[i].run_clamp + 1;
-      pf.tail_max_rows = std::max(pf.tail_max_rows, rows);
-      pf.tail_pack_rows += rows;
-    }
-  for (uint32_t i = n; i-- > 0;) {
-    FeatDesc &d = t[i];
-    if (d.kind == MSC_KIND_GENERIC) d.run_end = i;
-    else d.run_end = (i + 1 < d.grp_end && t[i + 1].kind != MSC_KIND_GENERIC) ? t[i + 1].run_end : i + 1;
-  }
-  return pf;
-}
-
 // The view's derived copies (msc_dataview::copies): the one of this kind and key, or null; and a new one.
 static const void *view_copy(const msc_dataview *view, msc_dataview::CopyKind kind, const std::vector<uint64_t> &key) {
   for (const msc_dataview::Copy &e : view->copies)
@@ -874,29 +756,13 @@ static bool nich_x_matrix(const msc_dataview *view, const std::vector<const void
   return true;
 }
 
-// The lookup index matrix of a plan's first phase tf[0 .. split) (msc::FeatDesc::lk_idx): a row's record is the groups'
-// features side by side, a byte each, every group from a dword boundary on; sets lk_goff at every group's first feature.
-// Kept by the view like the x matrix (C3: 36 features in ten groups, 48 bytes a row).  false: no matrix (cap reached, or no
-// memory) -- the plan does not take the kernels that read one.
-static bool look_idx_matrix(const msc_dataview *view, std::vector<FeatDesc> &tf, uint32_t split, const uint32_t **out, uint32_t *l4_out) {
-  std::vector<LookIdxSrc> src(split);
-  std::vector<uint64_t> key;
-  uint32_t l4 = 0;
-  for (uint32_t f0 = 0; f0 < split;) {
-    const uint32_t f1 = tf[f0].grp_end;
-    tf[f0].lk_goff = l4;
-    for (uint32_t i = f0; i < f1; i++) {
-      const FeatDesc &d = tf[i];
-      if (d.kind == MSC_KIND_GENERIC || d.col == nullptr || d.grp_off + d.run_clamp >= 256u) return false;
-      src[i] = LookIdxSrc{d.col, d.kind, d.run_clamp, d.grp_off, 4u * l4 + (i - f0)};
-      key.push_back(reinterpret_cast<uint64_t>(d.col));
-      key.push_back((uint64_t)d.kind | (uint64_t)d.run_clamp << 8 | (uint64_t)d.grp_off << 32);
-      key.push_back(src[i].byte_at);
-    }
-    l4 += (f1 - f0 + 3u) / 4u;
-    f0 = f1;
-  }
-  *l4_out = l4;
+// The lookup index matrix of a plan's first phase as tile_plan.hpp plan_look_idx laid it out (msc::FeatDesc::lk_idx).
+// Kept by the view like the x matrix.  false: no matrix (cap reached, or no memory) -- the plan does not take the kernels
+// that read one.
+static bool look_idx_matrix(const msc_dataview *view, const LookIdxLayout &lay, const uint32_t **out) {
+  const std::vector<LookIdxSrc> &src = lay.src;
+  std::vector<uint64_t> key = lay.key;
+  const uint32_t split = (uint32_t)src.size(), l4 = lay.l4;
   if ((*out = static_cast<const uint32_t *>(view_copy(view, msc_dataview::kLookIdx, key)))) return true;
   if (view_copies(view, msc_dataview::kLookIdx) >= kViewPackCap || split == 0) return false;
   DevBuf<uint8_t> dst;
@@ -920,250 +786,80 @@ static bool look_idx_matrix(const msc_dataview *view, std::vector<FeatDesc> &tf,
   return true;
 }
 
+// The plans of a state (tile_plan.hpp holds the steps and their rules): the steps in order, and between them what needs
+// the device -- the bound view's derived copies, the uploads.  st->plan is written whole at the end.
 static int plan_groups(msc_state *st) {
   const msc_dataview *const bview = bound_view_of(st);    // (null: no column pointer survives in desc_host either)
   const Switches sw = read_switches();
-  auto nich_tail = [](const FeatDesc &d) { return d.family == MSC_NICH && d.mask == nullptr && d.col != nullptr; };
-  std::vector<FeatDesc> &t = st->desc_tile_host;
-  t.clear();
-  for (FeatDesc &d : st->desc_host) d.blk_first = d.blk_end = 0, d.nich_info = nullptr;
-  std::vector<uint32_t> t_src;                              // t[i] is the caller's feature t_src[i]
+  TilePlan p;
+  std::vector<FeatDesc> &t = st->desc_tile_host, &tf = st->desc_fuse_host;
+  // the tile plan: phase order and nich blocks, sentinel copies, groups and lookup runs, leave-one-out stages
+  std::vector<uint32_t> nu_bits(st->nfeat, 0u);
   for (uint32_t i = 0; i < st->nfeat; i++)
-    if (!nich_tail(st->desc_host[i])) t.push_back(st->desc_host[i]), t_src.push_back(i);
-  st->tile_split = (uint32_t)t.size();
-  // The second phase, in BLOCKS (family_math.hpp "nich BLOCKS"): the plain nich features ordered by their nu prior
-  // (stable: the caller's order among equals), runs of an equal nu cut into blocks of at most kNichBlock, as even as they
-  // come (five are 3 + 2, not 4 + 1: a feature on its own pays the full logarithm).  Whether a block's c1 really are equal
-  // is for the head kernel to say (the counts are the suff-stats', not the plan's).
-  {
-    std::vector<uint32_t> tail;
-    for (uint32_t i = 0; i < st->nfeat; i++) if (nich_tail(st->desc_host[i])) tail.push_back(i);
-    auto nu_bits = [&](uint32_t i) { uint32_t b; std::memcpy(&b, &st->feats[i].hp[3], 4); return b; };
-    std::stable_sort(tail.begin(), tail.end(), [&](uint32_t a, uint32_t b) { return nu_bits(a) < nu_bits(b); });
-    st->nich_blocks_any = false;
-    for (size_t a = 0; a < tail.size();) {
-      size_t b = a + 1;
-      while (b < tail.size() && nu_bits(tail[b]) == nu_bits(tail[a])) b++;
-      const size_t n = b - a, nb = (n + kNichBlock - 1) / kNichBlock, base = n / nb, rem = n % nb;
-      for (size_t blk = 0, at = a; blk < nb; blk++) {
-        const size_t len = base + (blk < rem ? 1 : 0);
-        for (size_t j = 0; j < len; j++) {
-          FeatDesc d = st->desc_host[tail[at + j]];
-          d.blk_first = (uint32_t)(t.size() - j);
-          d.blk_end = d.blk_first + (uint32_t)len;
-          d.nich_info = st->nich_info + tail[at + j];
-          t.push_back(d);
-          t_src.push_back(tail[at + j]);
-        }
-        st->nich_blocks_any |= len >= 2;
-        at += len;
-      }
-      a = b;
-    }
-  }
-  // masked lookup columns: the tile plan reads the copy with the mask folded in (bind_view) and sees no mask -- a masked
-  // value selects the table's zero row, which the feature stages with the others (one more row: `extra`)
-  std::vector<uint32_t> extra(t.size(), 0u);
-  for (size_t i = 0; i < t.size(); i++) {
-    t[i].fuse_n = 0;
-    if (t[i].mask != nullptr && t[i].col_sentinel != nullptr) {
-      t[i].col = t[i].col_sentinel;
-      t[i].mask = nullptr;
-      extra[i] = 1;
-    }
-  }
-  const uint32_t n = st->nfeat, split = st->tile_split;
-  PlanFacts facts = plan_layout(t, split, extra, sw);
-  // The leave-one-out pass (k_loo_own_lds) stages what a row gathers per feature -- the lookup families' "value against
-  // the group minus one" tables, nich's twelve doubles per group -- for ALL kpad groups (a row's own group is any of
-  // them): consecutive features share the 64 KiB slot while their blocks fit; a feature whose block does not fit, or
-  // that is not of a staged kind, reads global memory inside its stage.
-  st->loo_staged = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    FeatDesc &d = t[i];
-    d.loo_off = d.loo_rows = 0;
-    uint32_t rows = 0;
-    if (d.kind != MSC_KIND_GENERIC && (d.loo_tab != nullptr || d.family == MSC_BBNC)) rows = d.run_clamp + 1;
-    else if (d.family == MSC_NICH && d.mask == nullptr && d.col != nullptr && d.loo64 != nullptr) rows = 2 * kNlooStride;
-    if (rows != 0 && (uint64_t)rows * st->kpad <= kLooSlotFloats) d.loo_rows = rows;
-  }
-  for (uint32_t f0 = 0; f0 < n;) {
-    uint32_t used = 0, g = f0;
-    while (g < n && g - f0 < (uint32_t)kLooStageFeats && used + t[g].loo_rows * st->kpad <= kLooSlotFloats) {
-      t[g].loo_off = used;
-      used += t[g].loo_rows * st->kpad;
-      st->loo_staged += t[g].loo_rows != 0;
-      g++;
-    }
-    for (uint32_t i = f0; i < g; i++) t[i].loo_stage_end = g;
-    f0 = g;
-  }
-  // The score / sweep kernels' plan: the unmasked bb / bbnc columns of the first phase come first, fused four (three, two)
-  // at a time -- one byte column of the members' bits, one table of 2^m rows (FeatDesc::fuse_*; k_fuse_tables fills the
-  // tables at the head of a call) -- then the other first-phase features in the caller's order, then the second phase.
-  // A quarter of the LDS reads and additions for the same sum; the order and the association of the terms --
-  // ((t0 + t1) + t2) + t3 per fused feature -- are the same in every kernel that walks this plan.  The leave-one-out
-  // pass walks the plan above.
-  std::vector<FeatDesc> &tf = st->desc_fuse_host;
-  std::vector<uint32_t> extra_f;
-  tf.clear();
-  // (the view is only looked at while it exists: a plan made after its view is gone -- msc_state_set_hp on a dd feature
-  // re-plans -- fuses nothing and holds no column; the next call that brings a view binds and plans again)
-  if (!st->nich_blocks_any)                                     // (no block of two or more: no records, no head-kernel work, no far rows)
-    for (FeatDesc &d : t) d.nich_info = nullptr;
-  const bool may_fuse = bview != nullptr && !sw.no_bb_fuse;
-  // (columns with a mask: their mask-folded copies, three states a value -- 0, 1, masked = the member's zero row --,
-  // three at a time against 27 rows)
-  std::vector<uint32_t> members[2];                        // [0] unmasked, [1] masked: the fusable features, in plan order
-  for (uint32_t i = 0; i < split; i++) {
-    const FeatDesc &d = t[i];
-    if (may_fuse && (d.family == MSC_BB || d.family == MSC_BBNC) && d.kind == MSC_KIND_LOOKUP_U8 && d.mask == nullptr &&
-        d.col != nullptr && d.tab != nullptr)
-      members[extra[i] ? 1 : 0].push_back(i);
-  }
-  struct Fused { uint32_t first, m, radix; };               // (first: index into members[radix - 2])
-  std::vector<Fused> quads;
-  for (uint32_t cls = 0; cls < 2; cls++) {
-    const size_t widest = cls == 0 ? 4 : 3;
-    size_t at = 0;
-    for (size_t left = members[cls].size(); left >= 2;) {
-      const uint32_t m = left == widest + 1 ? (uint32_t)widest - 1 : (uint32_t)std::min(widest, left);    // (never a single one left over)
-      quads.push_back(Fused{(uint32_t)at, m, 2u + cls});
-      at += m;
-      left -= m;
-    }
-  }
-  MSC_HIP(grow_retained(st->retired, st->fuse_tab, quads.size() * 32 * (size_t)st->kpad));
-  std::vector<bool> taken(n, false);
-  for (size_t q = 0; q < quads.size(); q++) {
-    const Fused &fq = quads[q];
-    const std::vector<uint32_t> &mem = members[fq.radix - 2];
-    FeatDesc d = t[mem[fq.first]];
+    if (st->feats[i].family == MSC_NICH) std::memcpy(&nu_bits[i], &st->feats[i].hp[3], 4);
+  const PhaseOrder po = plan_phases(st->desc_host, nu_bits, st->nich_info, t);
+  p.tile_split = po.split, p.nich_blocks_any = po.nich_blocks_any;
+  const std::vector<uint32_t> extra = plan_sentinels(t);
+  PlanFacts facts = plan_layout(t, po.split, extra, sw);
+  p.loo_staged = plan_loo_stages(t, st->kpad);
+  // the score / sweep kernels' plan: runs of bool columns fused (the view packs each run's columns into one), then the
+  // accumulate pass's list, then the fused plan's own groups and runs
+  const FusedRuns fr = plan_fused_runs(t, po.split, extra, bview != nullptr && !sw.no_bb_fuse);
+  MSC_HIP(grow_retained(st->retired, st->fuse_tab, fr.quads.size() * 32 * (size_t)st->kpad));
+  std::vector<const void *> packed(fr.quads.size(), nullptr);
+  for (size_t q = 0; q < fr.quads.size(); q++) {
     const void *cols[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (uint32_t j = 0; j < 4; j++) d.fuse_src[j] = nullptr;
-    for (uint32_t j = 0; j < fq.m; j++) {
-      const FeatDesc &mj = t[mem[fq.first + j]];
-      cols[j] = mj.col;
-      d.fuse_src[j] = mj.tab;
-      taken[mem[fq.first + j]] = true;
-    }
-    MSC_TRY(packed_column(bview, cols, (int)fq.m, fq.radix, &d.col));
-    d.fuse_n = fq.m;
-    d.fuse_radix = fq.radix;
-    d.col_type = MSC_TYPE_U8;
-    d.family = MSC_BB;
-    d.tab = st->fuse_tab + q * 32 * (size_t)st->kpad;
-    d.loo_tab = nullptr;
-    tf.push_back(d);
-    extra_f.push_back(0u);
+    for (uint32_t j = 0; j < fr.quads[q].m; j++) cols[j] = t[fr.member(q, j)].col;
+    MSC_TRY(packed_column(bview, cols, (int)fr.quads[q].m, fr.quads[q].radix, &packed[q]));
   }
-  for (uint32_t i = 0; i < n; i++)
-    if (!taken[i]) {
-      tf.push_back(t[i]);
-      extra_f.push_back(extra[i]);
-    }
-  // the accumulate pass's list: a fused feature reads z and its byte column once for all its members (their additive
-  // tables: fuse_acc); everything else as the caller gave it.  (Histograms of 2 m K counters: while they fit LDS.)
-  {
-    std::vector<FeatDesc> &ta = st->desc_acc_host;
-    ta.clear();
-    std::vector<bool> covered(n, false);
-    for (size_t q = 0; q < quads.size(); q++) {
-      const Fused &fq = quads[q];
-      if ((size_t)st->K * 8u * fq.m * 4u > 64u * 1024u) continue;
-      const std::vector<uint32_t> &mem = members[fq.radix - 2];
-      FeatDesc d = tf[q];
-      for (uint32_t j = 0; j < 4; j++) d.fuse_acc[j] = nullptr;
-      for (uint32_t j = 0; j < fq.m; j++) {
-        const uint32_t src = t_src[mem[fq.first + j]];
-        d.fuse_acc[j] = st->desc_host[src].acc_i64;
-        covered[src] = true;
-      }
-      ta.push_back(d);
-    }
-    for (uint32_t i = 0; i < n; i++)
-      if (!covered[i]) ta.push_back(st->desc_host[i]);
-  }
-  const std::vector<Fused> &fused = quads;
-  st->fuse_any = !fused.empty();
-  st->fuse_nfeat = (uint32_t)tf.size();
-  st->fuse_split = split - (n - st->fuse_nfeat);
-  for (uint32_t i = st->fuse_split; i < st->fuse_nfeat; i++) {     // (block bounds are indices into the plan they sit in)
-    tf[i].blk_first -= n - st->fuse_nfeat;
-    tf[i].blk_end -= n - st->fuse_nfeat;
-  }
-  if (st->fuse_any) facts = plan_layout(tf, st->fuse_split, extra_f, sw);
-  // what the role-split kernels' nich waves read (msc::NichPos): positions, the pack (k_fuse_tables fills it at the head
-  // of every call), the x matrix -- the last needs the view; without it (a plan made while no view is bound) the plan
-  // does not take those kernels, and the next call with a view plans again
-  for (FeatDesc &d : tf) d.rn_pack = nullptr, d.rn_pos = nullptr, d.rn_x = nullptr, d.rn_n2 = d.rn_n2p = 0;
-  for (FeatDesc &d : t) d.rn_pack = nullptr, d.rn_pos = nullptr, d.rn_x = nullptr, d.rn_n2 = d.rn_n2p = 0;
-  if (stages_nich(facts.path) && bview == nullptr) facts.path = MSC_PATH_TILE;
+  std::vector<uint32_t> extra_f;
+  plan_fused_list(t, po.split, extra, fr, packed, st->fuse_tab, st->kpad, tf, extra_f, p);
+  plan_acc_list(st->desc_host, po.t_src, tf, fr, st->K, st->desc_acc_host);
+  if (p.fuse_any) facts = plan_layout(tf, p.fuse_split, extra_f, sw);
+  // what the kernels of the three other paths read of the view: the x matrix beside the positions (the nich waves), the
+  // lookup index matrix (the lookup waves).  No view, or a view that cannot hold one more copy: the plan takes TILE
+  clear_view_reads(tf);
+  clear_view_reads(t);
+  facts.path = path_for_view(facts.path, bview != nullptr);
   if (stages_nich(facts.path)) {
-    const uint32_t s0 = st->fuse_split, n2 = st->fuse_nfeat - s0, n2p = (n2 + 3u) & ~3u;
-    std::vector<NichPos> pos(n2p);
-    std::vector<const void *> xcols(n2);
-    for (uint32_t i = 0; i < n2p; i++) {
-      NichPos &q = pos[i];
-      q.xlim = INFINITY, q.blk_ok = 0u;                       // (the head kernel writes these two for real positions)
-      if (i < n2) {
-        const FeatDesc &d = tf[s0 + i];
-        q.blk = (d.blk_first - s0) | (d.blk_end - d.blk_first) << 16, q.seg_end = d.grp_end - s0;
-        xcols[i] = d.col;
-      } else q.blk = i | 1u << 16, q.seg_end = n2p;
-    }
+    std::vector<NichPos> pos;
+    std::vector<const void *> xcols;
+    plan_nich_pos(tf, p.fuse_split, pos, xcols);
     const float *xm = nullptr;
     if (nich_x_matrix(bview, xcols, &xm)) {
-      MSC_HIP(hipMemcpyAsync(st->rn_pos, pos.data(), sizeof(NichPos) * n2p, hipMemcpyHostToDevice, st->ctx->stream));
+      MSC_HIP(hipMemcpyAsync(st->rn_pos, pos.data(), sizeof(NichPos) * pos.size(), hipMemcpyHostToDevice, st->ctx->stream));
       MSC_HIP(hipStreamSynchronize(st->ctx->stream));           // (`pos` is this function's)
-      FeatDesc &h = tf[s0];
-      h.rn_pack = st->rn_pack, h.rn_pos = st->rn_pos, h.rn_x = xm, h.rn_n2 = n2, h.rn_n2p = n2p;
+      FeatDesc &h = tf[p.fuse_split];
+      h.rn_pack = st->rn_pack, h.rn_pos = st->rn_pos, h.rn_x = xm, h.rn_n2 = (uint32_t)xcols.size(), h.rn_n2p = (uint32_t)pos.size();
     } else facts.path = MSC_PATH_TILE;                         // (no copy: the kernels that stage the nich constants need none)
   }
-  // ... and what their lookup waves read (FeatDesc::lk_idx): the first phase's slot rows, row by row
-  for (FeatDesc &d : tf) d.lk_idx = nullptr, d.lk_l4 = d.lk_goff = 0;
-  for (FeatDesc &d : t) d.lk_idx = nullptr, d.lk_l4 = d.lk_goff = 0;
-  if (bview == nullptr && facts.path == MSC_PATH_LOOKUPS) facts.path = MSC_PATH_TILE;
   if (facts.path == MSC_PATH_TILE_ROLES || facts.path == MSC_PATH_LOOKUPS) {
+    LookIdxLayout lay;
     const uint32_t *im = nullptr;
-    uint32_t l4 = 0;
-    if (look_idx_matrix(bview, tf, st->fuse_split, &im, &l4)) tf[0].lk_idx = im, tf[0].lk_l4 = l4;
+    if (plan_look_idx(tf, p.fuse_split, lay) && look_idx_matrix(bview, lay, &im)) tf[0].lk_idx = im, tf[0].lk_l4 = lay.l4;
     else facts.path = MSC_PATH_TILE;
   }
-  st->tile_path = facts.path;
-  {
-    // the prices the kernels are chosen by (launchers.hpp PlanCost): staged lookup features and table rows of the first
-    // phase, nich features (the second phase's, and masked ones evaluated in the first)
-    double lookups = 0, rows = 0, nich = (double)(st->fuse_nfeat - st->fuse_split);
-    for (uint32_t i = 0; i < st->fuse_split; i++) {
-      if (tf[i].family == MSC_NICH) nich += 1;
-      else if (tf[i].family == MSC_DM) lookups += 2.0 * (tf[i].dim + 1), rows += tf[i].grp_rows;   // (dim + 1 stages of (hi, lo) pairs)
-      else lookups += 1, rows += tf[i].grp_rows;
-    }
-    PlanCost pc;
-    const double first = 6.0 + 0.45 * lookups + 0.012 * rows;
-    pc.tile_round_us = facts.path == MSC_PATH_NICH_PACK ? 6.0 + 1.3 * nich + 3.0 * lookups : facts.path == MSC_PATH_TILE_ROLES ? first + 0.75 * nich
-                       : facts.path == MSC_PATH_LOOKUPS ? 0.75 * first : first + 1.5 * nich;
-    pc.sweep_round_us = pc.tile_round_us + 2.5;              // (+ the draws)
-    pc.tail_fixed_us = 2.0;                                  // (per launch and round of 1024 rows a CU: tools/scans/grid_scan.py at 1M rows,
-    pc.tail_group_us = 0.5 + 0.03 * lookups + 0.057 * nich;  //  K = 8 against K = 32 for six feature lists; C3: 2 + 2.5 a group)
-    st->plan_cost = pc;
-  }
-  st->tile_narrow_tail_ok = facts.tail_ok;
-  st->tail_masked_nich = facts.tail_masked_nich;
-  st->tail_dm = facts.tail_dm;
-  st->tail_max_rows = facts.tail_max_rows;
-  st->tail_pack_rows = facts.tail_pack_rows;
+  // the path, its prices, and what the lane <-> row kernel needs of the plan
+  p.tile_path = facts.path;
+  p.plan_cost = plan_prices(tf, p.fuse_split, facts.path);
+  p.tile_narrow_tail_ok = facts.tail_ok;
+  p.tail_masked_nich = facts.tail_masked_nich;
+  p.tail_dm = facts.tail_dm;
+  p.tail_max_rows = facts.tail_max_rows;
+  p.tail_pack_rows = facts.tail_pack_rows;
+  st->plan = p;
   return MSC_OK;
 }
 
+static void refresh_route_facts(msc_state *st);
 static int upload_desc(msc_state *st) {
   MSC_TRY(plan_groups(st));
+  refresh_route_facts(st);
   MSC_HIP(hipMemcpyAsync(st->desc_dev, st->desc_host.data(), sizeof(FeatDesc) * st->nfeat,
                          hipMemcpyHostToDevice, st->ctx->stream));
   MSC_HIP(hipMemcpyAsync(st->desc_tile_dev, st->desc_tile_host.data(), sizeof(FeatDesc) * st->nfeat,
                          hipMemcpyHostToDevice, st->ctx->stream));
-  MSC_HIP(hipMemcpyAsync(st->desc_fuse_dev, st->desc_fuse_host.data(), sizeof(FeatDesc) * st->fuse_nfeat,
+  MSC_HIP(hipMemcpyAsync(st->desc_fuse_dev, st->desc_fuse_host.data(), sizeof(FeatDesc) * st->plan.fuse_nfeat,
                          hipMemcpyHostToDevice, st->ctx->stream));
   MSC_HIP(hipMemcpyAsync(st->desc_acc_dev, st->desc_acc_host.data(), sizeof(FeatDesc) * st->desc_acc_host.size(),
                          hipMemcpyHostToDevice, st->ctx->stream));
@@ -1813,36 +1509,28 @@ uint64_t msc::view_rows(const msc_state *st) {
 // ... and so does what the plan's nich blocks go by (NichPlanInfo: is a block's c1 one number per group, how far a value may
 // lie before a product of four could overflow) -- the same launch
 int msc::refresh_fused_tables(msc_state *st) {
-  const bool packed = stages_nich(st->tile_path);
-  if (!st->fuse_any && !st->nich_blocks_any && !packed) return MSC_OK;
-  if (launch_fuse_tables(st->ctx->stream, st->desc_fuse_dev, (int)st->fuse_split, (st->nich_blocks_any || packed) ? (int)st->fuse_nfeat : (int)st->fuse_split, st->kpad))
+  const bool packed = stages_nich(st->plan.tile_path);
+  if (!st->plan.fuse_any && !st->plan.nich_blocks_any && !packed) return MSC_OK;
+  if (launch_fuse_tables(st->ctx->stream, st->desc_fuse_dev, (int)st->plan.fuse_split, (st->plan.nich_blocks_any || packed) ? (int)st->plan.fuse_nfeat : (int)st->plan.fuse_split, st->kpad))
     return fail(MSC_EHIP, "k_fuse_tables launch failed");
   return MSC_OK;
-}
-
-// Can k_score_tail_rows take this plan's partly filled last tile?  A plan it takes (plan_groups), at most kTailMaxGroups
-// groups there, and the largest staged table beside the second phase's block (64 floats a nich feature) in 64 KiB of LDS.
-static bool narrow_tail_fits(const msc_state *st) {
-  const size_t nich_bytes = (size_t)(st->fuse_nfeat - st->fuse_split) * 64 * sizeof(float);
-  return st->tile_narrow_tail_ok && st->K - (st->kpad - kGroupTile) <= kTailMaxGroups &&
-         nich_bytes + (size_t)std::max<uint32_t>(1u, st->tail_max_rows) * kTailStride * sizeof(float) <= 64u * 1024u;
 }
 
 // what the narrow kernels of a partly filled last tile need (launchers.hpp); the packed-table scratch grows on demand
 static int tail_plan(msc_state *st, TailPlan &tp, bool exact = true) {
   tp = TailPlan();
   tp.exact = exact;
-  if (!(tp.ok = narrow_tail_fits(st))) return MSC_OK;
-  MSC_HIP(grow_retained(st->retired, st->tail_pack, (size_t)st->tail_pack_rows * 64));
-  tp.masked_nich = st->tail_masked_nich;
-  tp.dm = st->tail_dm;
-  tp.max_rows = st->tail_max_rows;
-  tp.pack_rows = st->tail_pack_rows;
+  if (!(tp.ok = narrow_tail_fits(st->route))) return MSC_OK;
+  MSC_HIP(grow_retained(st->retired, st->tail_pack, (size_t)st->plan.tail_pack_rows * 64));
+  tp.masked_nich = st->plan.tail_masked_nich;
+  tp.dm = st->plan.tail_dm;
+  tp.max_rows = st->plan.tail_max_rows;
+  tp.pack_rows = st->plan.tail_pack_rows;
   tp.pack = st->tail_pack;
   return MSC_OK;
 }
 
-// (called inside calls that have just bound their view: bind_view leaves bound_view current)
+// (called where a view has just been bound or the plan is made: bind_view and plan_groups leave bound_view current)
 static bool gp_beyond_table(const msc_state *st, uint32_t f) {
   if (!st->bound_view || f >= st->bound_cols.size()) return false;
   const uint32_t c = st->bound_cols[f];
@@ -1852,12 +1540,30 @@ static bool gp_beyond_table(const msc_state *st, uint32_t f) {
   return false;
 }
 
+// What the routes read of the state (route.hpp RouteFacts), as of this bind or plan: upload_desc is the one place that
+// builds it, so a call walks no view metadata.  view_rows is the call's to refresh (route_facts_now).
+static void refresh_route_facts(msc_state *st) {
+  RouteFacts &rf = st->route;
+  rf.K = st->K, rf.kpad = st->kpad, rf.num_cus = st->ctx->num_cus;
+  rf.nich1 = st->nich1, rf.has_dm = st->has_dm, rf.n_niw = st->n_niw, rf.nfeat = st->nfeat;
+  rf.plan = st->plan;
+  rf.feats.resize(st->nfeat);
+  for (uint32_t f = 0; f < st->nfeat; f++)
+    rf.feats[f] = RouteFeat{st->feats[f].family, st->feats[f].dim, st->desc_host[f].vcap, gp_beyond_table(st, f)};
+  rf.niw1_max_groups = sweep_niw1_max_groups(st->feats[0].dim);
+  rf.nich1_rows_max_groups = sweep_nich1_rows_max_groups();
+}
+static const RouteFacts &route_facts_now(msc_state *st) {
+  st->route.view_rows = view_rows(st);
+  return st->route;
+}
+
 // does any row's leave-one-out value need the formula paths (dm always; gp / bnb when the column holds counts beyond the table)?
 static bool loo_needs_heavy(const msc_state *st) {
   for (uint32_t f = 0; f < st->nfeat; f++) {
     const int fam = st->feats[f].family;
     // (a count family's table covers 0 .. the bound column's maximum unless that exceeds the cap; dm likewise, by row total)
-    if ((is_count_family(fam) || fam == MSC_DM) && gp_beyond_table(st, f)) return true;
+    if ((is_count_family(fam) || fam == MSC_DM) && st->route.feats[f].beyond_table) return true;
   }
   return false;
 }
@@ -1868,64 +1574,12 @@ static bool loo_needs_heavy(const msc_state *st) {
 // test_both_leave_one_out_kernels_give_a_row_the_same_bits), so the CALL's rows choose.
 int msc::run_loo_own(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z, bool crp) {
   const int lds = read_switches().loo_lds;
-  const bool staged = st->loo_staged != 0 && (lds < 0 ? nrows >= (uint64_t)kLooRows * kLooThreads * st->ctx->num_cus * 3 / 4 : lds != 0);
+  const bool staged = st->plan.loo_staged != 0 && (lds < 0 ? nrows >= (uint64_t)kLooRows * kLooThreads * st->ctx->num_cus * 3 / 4 : lds != 0);
   MSC_HIP(grow_retained(st->retired, st->own, nrows));
   if (launch_loo_own(st->ctx->stream, loo_needs_heavy(st), staged, st->desc_tile_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, z,
                      crp ? st->logpc : nullptr, st->own))
     return fail(MSC_EHIP, "k_loo_own launch failed");
   return MSC_OK;
-}
-
-// PAIR mode of the role-split / nich-only / lookups-only kernels: one k-tile of at most 128 groups
-static bool pair_path(ScorePath path, uint32_t K) {
-  return (path == MSC_PATH_TILE_ROLES || path == MSC_PATH_NICH_PACK || path == MSC_PATH_LOOKUPS) && K <= 128;
-}
-
-// K <= 64 and nothing but scalar families whose tables all fit 64 KiB of LDS at 4 L groups per row: the narrow tiling
-// (kernels_sweep.hip k_narrow).  Returns L = lanes per row (4 / 8 / 16) or 0, and the table rows to stage.
-static int narrow_lanes(const msc_state *st, const Switches &sw, uint32_t *table_rows) {
-  // (32 lanes per row for K <= 128 was measured and loses to the 256-group tiling: 8 bb at K = 100, 0.52 against 0.20 ms)
-  if (st->K > 64) return 0;
-  // Views of many rows leave it to the lane <-> row kernel (round 3's; by view_rows: route_sweep's shard rule).  At a million rows that kernel is 1.3-2.7x the faster one (tools/scans/k_monotone.sh:
-  // sixteen dd32 columns at K = 32 0.34 -> 0.13 ms, 8 bb + 8 nich at K = 64 0.48 -> 0.26, sixteen nich at K = 32 0.30 -> 0.18);
-  // this tiling is for the small problems it was made for (C1: 10k rows, 8 us a pass): views below kNarrowMaxRows rows.
-  if (view_rows(st) >= kNarrowMaxRows && st->tile_narrow_tail_ok && !sw.tail_forced) return 0;
-  const int L = st->K <= 16 ? 4 : st->K <= 32 ? 8 : 16;
-  uint32_t rows = 0;
-  for (uint32_t f = 0; f < st->nfeat; f++) {
-    const msc_feature_host &h = st->feats[f];
-    switch (h.family) {
-      case MSC_BB: case MSC_BBNC: rows += 2; break;
-      case MSC_NICH: rows += 6; break;                                      // (NICH_ROWS)
-      case MSC_DD: rows += h.dim; break;
-      case MSC_GP: case MSC_BNB:
-        if (gp_beyond_table(st, f)) return 0;
-        rows += st->desc_host[f].vcap;
-        break;
-      case MSC_NOOP: break;
-      default: return 0;                                                    // niw, dm: their own kernels
-    }
-  }
-  if ((size_t)rows * L * 16 > 64u * 1024u) return 0;
-  // ... and only where it is the cheaper tiling for THIS plan (by the plan alone: the narrow kernel adds the features in
-  // the caller's order, the tile kernels in the plan's).
-  // Per million rows, us, at 16 lanes a row (tools/scans/grid_scan.py at 100k rows, k_monotone.sh): a bb column 30 (the tile
-  // plan fuses four of them into one lookup, this tiling cannot), dd / gp 50, nich 60, half of it at 8 lanes and no less at
-  // 4; against the tile kernels' rounds at the plan's price (launchers.hpp PlanCost; up to 128 groups the role-split /
-  // nich-only kernels run in PAIR mode).  32 bool columns at K = 64, 1M rows: 0.86 ms here, 0.30 on the tile kernel; 64 at
-  // K = 8, 100k rows: 0.10 against 0.04.
-  {
-    double us = 0;
-    for (uint32_t f = 0; f < st->nfeat; f++) {
-      const int fam = st->feats[f].family;
-      us += fam == MSC_BB || fam == MSC_BBNC ? 30.0 : fam == MSC_NICH ? 60.0 : fam == MSC_NOOP ? 0.0 : 50.0;
-    }
-    us *= std::max(L, 8) / 16.0;
-    const double tile = st->plan_cost.tile_round_us * (1.0e6 / 128.0 / st->ctx->num_cus) * (pair_path(st->tile_path, st->K) ? kPairTileShare : 1.0);
-    if (us > 1.25 * tile) return 0;
-  }
-  *table_rows = rows;
-  return L;
 }
 
 // k_score_nich1's launch shape for a pass of `nrows` x K into `out`: what msc_score_tune remembered for this very
@@ -1951,49 +1605,13 @@ static int nich1_shape_for(msc_context *ctx, const void *out, uint64_t nrows, ui
   return shape | (plain ? 0x100 : 0);
 }
 
-// Which kernels score `nrows` rows into `out`: k_narrow when `lanes` is set (narrow_lanes: by view_rows), else the scalar
-// features' pass on `path` as `shape` says -- by the call's rows: every shape gives the tile kernels' bits --, then niw's.
-struct ScoreRoute { int lanes = 0; uint32_t table_rows = 0; ScorePath path = MSC_PATH_TILE; ScoreShape shape; };
-static ScoreRoute route_score(const msc_state *st, uint64_t nrows, const void *out) {
-  const Switches sw = read_switches();
-  ScoreRoute r;
-  r.lanes = narrow_lanes(st, sw, &r.table_rows);
-  r.path = st->nich1 ? MSC_PATH_NICH1 : st->has_dm ? MSC_PATH_TILE_DM : st->tile_path;
-  if (r.lanes) return r;
-  if (r.path == MSC_PATH_NICH1) {
-    r.shape.nich1 = nich1_shape_for(st->ctx, out, nrows, st->K);
-    return r;
-  }
-  // few rows: the chunks -- serial chains, feature after feature -- spread over the chip in ONE round at 4 or 2 rows a
-  // wave (4 only while the 64-row workgroups fit one round: 20000 rows made 313 of them, 0.113 ms, where 157 of 128 take one)
-  const int cus = st->ctx->num_cus;
-  const uint32_t ktiles = st->kpad / kGroupTile, last_groups = st->K - (ktiles - 1) * kGroupTile;
-  const uint64_t round = (uint64_t)cus / ktiles;
-  const bool small4 = r.path != MSC_PATH_TILE_DM && (nrows + 63) / 64 <= round, small2 = small4 && (nrows + 31) / 32 <= round;
-  r.shape.wave_rows = small2 ? 2 : small4 ? 4 : 8;
-  r.shape.pair = !small4 && pair_path(r.path, st->K);
-  // a LAST tile of 65 .. 128 groups beyond full ones on the role-split kernels: PAIR mode at that tile (round 5), ~0.62 of a
-  // full tile's price where the lane <-> row kernel takes two or three launches
-  // else the last tile on the lane <-> row kernel when the plan allows and the rows are many (few -- a per-entity call's one
-  // -- are better off with lanes as groups): whichever the cost model of launchers.hpp prices lower for these rows
-  if (ktiles > 1 && r.path == MSC_PATH_TILE_ROLES && !small4 && last_groups > 64 && last_groups <= 128) r.shape.last = LastTile::pair;
-  if (r.shape.last == LastTile::pair || !narrow_tail_fits(st)) return r;
-  const PlanCost &pc = st->plan_cost;
-  const uint64_t c128 = (nrows + 127) / 128;
-  const double tile_us = (r.shape.pair ? kPairTileShare : 1.0) *
-                         (tile_rounds_us(c128 * ktiles, cus, false, pc) - (ktiles > 1 ? tile_rounds_us(c128 * (ktiles - 1), cus, false, pc) : 0.0));
-  const bool many_rows = sw.tail_forced ? nrows >= sw.tail_min_rows
-                                        : nrows >= kTailMinRows && tail_rows_us(last_groups, true, nrows, cus, pc) < tile_us;
-  if (many_rows) r.shape.last = LastTile::rows;
-  return r;
-}
-
 int msc::run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *z_dev, bool crp,
                    bool niw_f32, float *out_dev, uint64_t ld_out) {
   hipStream_t s = st->ctx->stream;
   const float *prior = crp ? st->logpc : nullptr;
   if (z_dev) MSC_TRY(run_loo_own(st, row0, nrows, z_dev, crp));
-  const ScoreRoute r = route_score(st, nrows, out_dev);
+  ScoreRoute r = route_score(route_facts_now(st), read_switches(), nrows);
+  if (!r.lanes && r.path == MSC_PATH_NICH1) r.shape.nich1 = nich1_shape_for(st->ctx, out_dev, nrows, st->K);
   if (r.lanes) {
     return launch_narrow(s, st->ctx->num_cus, r.lanes, r.table_rows, false, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows,
                          z_dev, st->own, prior, out_dev, ld_out, 0, nullptr, nullptr, ZeroSpans());
@@ -2006,11 +1624,11 @@ int msc::run_score(msc_state *st, uint64_t row0, uint64_t nrows, const int32_t *
       MSC_TRY(tail_plan(st, tail));
       MSC_TRY(refresh_fused_tables(st));
     }
-    MSC_TRY(launch_score(s, st->ctx->num_cus, r.path, tail, r.shape, nich1 ? st->desc_dev : st->desc_fuse_dev, (int)st->fuse_nfeat,
-                         (int)st->fuse_split, st->K, st->kpad, row0, nrows, z_dev, st->own, prior, out_dev, ld_out));
+    MSC_TRY(launch_score(s, st->ctx->num_cus, r.path, tail, r.shape, nich1 ? st->desc_dev : st->desc_fuse_dev, (int)st->plan.fuse_nfeat,
+                         (int)st->plan.fuse_split, st->K, st->kpad, row0, nrows, z_dev, st->own, prior, out_dev, ld_out));
     written = true;
     for (uint32_t f = 0; f < st->nfeat; f++)
-      if (gp_beyond_table(st, f) &&
+      if (st->route.feats[f].beyond_table &&
           launch_gp_large_fix(s, st->ctx->num_cus, st->desc_dev, (int)f, st->K, st->kpad, row0, nrows, z_dev, out_dev, ld_out))
         return fail(MSC_EHIP, "k_gp_large_fix launch failed");
   }
@@ -2054,7 +1672,7 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
   if (ms_out) *ms_out = 0.f;
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
-  const ScoreRoute r = route_score(st, nrows, out_dev);
+  const ScoreRoute r = route_score(route_facts_now(st), read_switches(), nrows);
   if (r.lanes || r.path != MSC_PATH_NICH1 || nrows == 0) return MSC_OK;
   MSC_TRY(ensure_derived(st));
   hipStream_t s = st->ctx->stream;
@@ -2062,7 +1680,7 @@ extern "C" int msc_score_tune(msc_state *st, const msc_dataview *view, const uin
   if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
     return fail(MSC_EINVAL, "msc_score_tune waits for the device: not on a capturing stream");
   auto launch = [&](int code) {
-    return launch_score(s, st->ctx->num_cus, MSC_PATH_NICH1, TailPlan(), ScoreShape{8, false, LastTile::tiles, code}, st->desc_dev, 1, (int)st->tile_split, st->K, st->kpad, row0,
+    return launch_score(s, st->ctx->num_cus, MSC_PATH_NICH1, TailPlan(), ScoreShape{8, false, LastTile::tiles, code}, st->desc_dev, 1, (int)st->plan.tile_split, st->K, st->kpad, row0,
                         nrows, nullptr, nullptr, nullptr, out_dev, ld_out);
   };
   hipEvent_t e0, e1;
@@ -2225,114 +1843,8 @@ extern "C" int msc_score_data(msc_state *st, float *out_dev) {
   return MSC_OK;
 }
 
-// score + sample in one kernel; niw and gp-beyond-table features and wide K need the materialised path
-// one niw feature of small dimension on few groups: the fused k_sweep_niw1
-static bool sweep_is_niw1(const msc_state *st) {
-  return st->nfeat == 1 && st->feats[0].family == MSC_NIW && (int)st->K <= sweep_niw1_max_groups(st->feats[0].dim);
-}
-
-// the lane <-> row kernel fills the chip from ~260k rows on; with fewer the tile kernels' rounds of 128-row chunks can be
-// shorter.  Decided on the view's row count, so every row range of it takes the same kernels.
-// (priced with the cost model of launchers.hpp: the lane <-> row launches -- plus, beyond 64 groups, the trip through
-// 128 floats per row and the row sampler -- against the rounds of the fused tile sweep kernel; for a tail beyond a full
-// tile, against one more tile pass, the materialised matrix and the sampler)
-// PAIR mode of the role-split sweep kernel (at most 128 groups; kernels_sweep.hip): its draw associates a row's entries
-// differently from the other tile kernels'
-static bool sweep_pair_mode(const msc_state *st) {
-  return view_rows(st) >= kTailMinRows && pair_path(st->tile_path, st->K);
-}
-static bool sweep_rows_pays(const msc_state *st, const Switches &sw, uint32_t groups) {
-  const uint64_t rows = view_rows(st);
-  if (sw.tail_forced) return rows >= sw.tail_min_rows;
-  if (rows < kTailMinRows) return false;
-  const int cus = st->ctx->num_cus;
-  const uint64_t c128 = (rows + 127) / 128;
-  const bool tail = groups < st->K;                       // the groups beyond a full first tile
-  const double sample_us = [&](uint64_t floats_per_row) { return 30.0 + (double)rows * floats_per_row * 4.0 / 2.0e6; }(tail ? st->K : 128);
-  double rows_us = tail_rows_us(groups, false, rows, cus, st->plan_cost), tile_us;
-  if (tail) {
-    rows_us *= 1.15;                                      // (the tile kernel's instantiation that reads the tail is that much slower)
-    tile_us = tile_rounds_us(c128, cus, false, st->plan_cost) + sample_us;                    // one more tile pass, then the sampler over K floats a row
-  } else {
-    if (groups > 64) rows_us += sample_us;
-    // (a fused sweep round = the scoring round -- its PAIR share up to 128 groups -- + the draws, which do not shrink with the
-    // plan or the mode: ~2.5 us a round; 8 bb columns at K = 64: 0.18 ms in PAIR mode, 0.10 on the lane <-> row kernel)
-    PlanCost pc = st->plan_cost;
-    pc.sweep_round_us = pc.tile_round_us * (sweep_pair_mode(st) ? kPairTileShare : 1.0) + 2.5;
-    tile_us = tile_rounds_us(c128, cus, true, pc);
-  }
-  return rows_us < tile_us;
-}
-
-// no niw feature and no count beyond the tables: what the fused sweep kernels score
-bool msc::sweep_plain(const msc_state *st) {
-  for (uint32_t f = 0; f < st->nfeat; f++) if (gp_beyond_table(st, f)) return false;
-  return st->n_niw == 0;
-}
-
-static bool sweep_is_fused(const msc_state *st) {
-  if (sweep_is_niw1(st)) return true;
-  if (!sweep_plain(st)) return false;
-  return st->nich1 ? st->K <= sweep_nich1_rows_max_groups() : st->K <= 256;
-}
-
-// How a sweep assigns a state's rows: the kind sweep_assign_impl switches on, and what that kind needs -- every kernel the
-// sweep launches, decided here (the launchers take it as it is).
-// THE SHARD RULE: some kernels add a row's terms in a different order from others, so the choice depends only on the plan
-// and on view_rows (the bound view's, or the whole's a sharded driver announced), never on the call's rows: that is what
-// makes a shard draw the same bits as the whole.  (A launch shape that draws the same bits at every row count may follow
-// the call's rows; the test that holds it so is named where it is chosen.)  Recomputed on every call (the bound view, the hint and the switches read
-// here change between calls).
-// (rows: K <= 64, the lane <-> row kernel draws its own row; rows_sampler: up to 128 groups, its scores into 128 floats a
-// row, then the row sampler; roles_tail: 256 < K <= 384, the groups beyond the tile from the narrow kernel -- or, 65 .. 128
-// of them on a role-split plan, the role-split kernel in PAIR mode (tail_pair) -- into tail_ld floats a row, then the fused
-// kernel over the tile draws over both; generic: chunks scored into scratch, then sampled)
-enum class SweepKind { niw1, nich1, nich1_rows, narrow, rows, rows_sampler, mixed, roles_tail, generic };
-struct SweepRoute {
-  SweepKind kind = SweepKind::generic;
-  int lanes = 0; uint32_t table_rows = 0;   // narrow (narrow_lanes)
-  bool transposed = false;                  // nich1: k_sweep_nich1_t
-  ScoreShape shape;                         // mixed: PAIR mode of the tile kernels (sweep_pair_mode), rows a wave
-  uint64_t tail_ld = 0;                     // roles_tail
-  bool tail_pair = false;                   // roles_tail
-};
-static SweepRoute route_sweep(const msc_state *st, uint64_t nrows) {
-  const Switches sw = read_switches();
-  const uint64_t cus = (uint64_t)st->ctx->num_cus;
-  SweepRoute r;
-  if (sweep_is_niw1(st)) {
-    r.kind = SweepKind::niw1;
-  } else if (sweep_is_fused(st)) {
-    if (st->nich1) {
-      r.kind = st->K > 1024 ? SweepKind::nich1_rows : SweepKind::nich1;
-      // enough rows for a 32-row chunk per wave over most of the chip: the transposed draw (k_sweep_nich1_t; measured ahead
-      // from ~16 k rows on at K = 256 and at K = 1024 alike -- 4 k rows: 15 vs 11 us, 16 k: 15 vs 18, 64 k: 19 vs 30,
-      // 512 k: 74 vs 120).  The two kernels draw different bits: by view_rows.
-      r.transposed = sw.sweep_nich1 == 2 || (sw.sweep_nich1 != 1 && view_rows(st) >= cus * 64);
-    } else if ((r.lanes = narrow_lanes(st, sw, &r.table_rows)) != 0) {
-      r.kind = SweepKind::narrow;
-    } else if (narrow_tail_fits(st) && st->K <= kTailMaxGroups && sweep_rows_pays(st, sw, st->K)) {
-      r.kind = st->K <= 64 ? SweepKind::rows : SweepKind::rows_sampler;
-    } else {
-      r.kind = SweepKind::mixed;
-      r.shape.pair = sweep_pair_mode(st);
-      // Few rows: R = 2 or 4 rows a wave (not 8) spread the chunks over the chip in one round.  k_sweep_tile<R, 16> then
-      // takes the place of a plan's own non-PAIR kernel: by view_rows.  R follows the call's rows: the same bits at every R
-      // (test_gpu_shard_views.py _kernels).
-      const bool small = (nrows + 63) / 64 <= cus, view_small = (view_rows(st) + 63) / 64 <= cus;
-      const int R = small ? ((nrows + 31) / 32 > cus ? 4 : 2) : view_small ? 4 : 8;
-      if (!st->has_dm && (view_small || st->tile_path == MSC_PATH_TILE)) r.shape.wave_rows = R;
-    }
-  } else if (!st->nich1 && !st->has_dm && st->tile_path != MSC_PATH_TILE && st->tile_narrow_tail_ok && st->K > 256 &&
-             st->K <= (uint32_t)kGroupTile + kTailMaxGroups && sweep_rows_pays(st, sw, st->K - kGroupTile) && sweep_plain(st)) {
-    r.tail_ld = st->K <= (uint32_t)kGroupTile + 64 ? 64 : 128;
-    // (65 .. 128 groups beyond the tile on a role-split plan: ONE pass of the role-split kernel in PAIR mode at tile 1
-    // instead of three launches of the lane <-> row kernel -- round 5)
-    r.tail_pair = st->tile_path == MSC_PATH_TILE_ROLES && r.tail_ld == 128;
-    if (r.tail_pair || narrow_tail_fits(st)) r.kind = SweepKind::roles_tail;
-  }
-  return r;
-}
+// no niw feature and no count beyond the tables (route.hpp), for the units that route by it
+bool msc::sweep_plain(const msc_state *st) { return sweep_plain(st->route); }
 
 // the sampling kernels read (seed, sweep) from the state's device pair and the step ends by incrementing the sweep
 // index there, so consecutive sweeps need no host -> device traffic (and replay as a graph, msc_sweep_step)
@@ -2358,7 +1870,7 @@ int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32
     zero.a = reinterpret_cast<unsigned long long *>(st->red_i64.get()); zero.na = st->n_i64;
     zero.b = reinterpret_cast<unsigned long long *>(st->red_f64.get()); zero.nb = st->n_f64;
   }
-  const SweepRoute r = route_sweep(st, nrows);
+  const SweepRoute r = route_sweep(route_facts_now(st), read_switches(), nrows);
   bool zeroes = true;                                   // the kernel emptied the additive tables on its way (with `zeroed`)
   switch (r.kind) {                                     // (the launchers report their own failures)
     case SweepKind::niw1:
@@ -2379,7 +1891,7 @@ int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32
     case SweepKind::mixed:
       MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
       MSC_TRY(refresh_fused_tables(st));                  // (these walk the fused plan)
-      MSC_TRY(launch_sweep_mixed(s, cus, st->has_dm, st->tile_path, r.shape, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero));
+      MSC_TRY(launch_sweep_mixed(s, cus, st->has_dm, st->plan.tile_path, r.shape, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad, row0, nrows, row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero));
       break;
     case SweepKind::rows:
     case SweepKind::rows_sampler: {
@@ -2388,12 +1900,12 @@ int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32
       TailPlan tail;
       MSC_TRY(tail_plan(st, tail, false));
       if (r.kind == SweepKind::rows) {
-        MSC_TRY(launch_sweep_rows(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows, row_id0,
+        MSC_TRY(launch_sweep_rows(s, cus, tail, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad, row0, nrows, row_id0,
                                   z_dev, st->own, st->logpc, st->rng_dev, zero));
         break;
       }
       MSC_HIP(grow_retained(st->retired, st->tail_scores, ((size_t)nrows + 16) * 128));
-      MSC_TRY(launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, 0, row0, nrows,
+      MSC_TRY(launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad, 0, row0, nrows,
                                 z_dev, st->own, st->logpc, st->tail_scores, 128));
       if (launch_sample_rows(s, cus, st->tail_scores, 128, st->K, nrows, row_id0, z_dev, st->rng_dev)) return fail(MSC_EHIP, "k_sample_rows launch failed");
       zeroes = false;                                     // (nothing emptied the additive tables on the way)
@@ -2407,11 +1919,11 @@ int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32
       // group: nothing else scores these groups for a draw)
       TailPlan tail;
       MSC_TRY(tail_plan(st, tail, false));
-      MSC_TRY(r.tail_pair ? launch_score_pair_tail(s, cus, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
+      MSC_TRY(r.tail_pair ? launch_score_pair_tail(s, cus, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad, row0, nrows,
                                                    z_dev, st->own, st->logpc, st->tail_scores, r.tail_ld)
-                          : launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad,
+                          : launch_score_tail(s, cus, tail, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad,
                                               kGroupTile, row0, nrows, z_dev, st->own, st->logpc, st->tail_scores - kGroupTile, r.tail_ld));
-      MSC_TRY(launch_sweep_roles_tail(s, cus, st->tile_path, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
+      MSC_TRY(launch_sweep_roles_tail(s, cus, st->plan.tile_path, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad, row0, nrows,
                                       row_id0, z_dev, st->own, st->logpc, st->rng_dev, zero, st->tail_scores));
       break;
     }
@@ -2510,7 +2022,7 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
   // the first two steps with a key run eagerly -- allocations, bindings and first-use setup happen there and the
   // state reaches its steady flags -- and the third is captured, if it is the fused kind (nothing in it then
   // allocates, copies to the host or waits)
-  if (g.seen < 2 || !next_sweep || !sweep_is_fused(st)) {
+  if (g.seen < 2 || !next_sweep || !sweep_is_fused(st->route)) {
     g.seen++;
     return eager();
   }

@@ -12,16 +12,7 @@
 
 namespace msc {
 
-// What the library reads from the environment, all of it here (INTEGRATION.md "Environment" says what each switch does):
-// read afresh by every call that plans, routes or allocates, so that a test may set a switch between two calls.
-struct Switches {
-  bool tail_forced = false, no_narrow_tail = false, no_bb_fuse = false, sweep_graph = false;
-  uint64_t tail_min_rows = 0;                           // (tail_forced)
-  int loo_lds = -1, sweep_nich1 = 0, alloc_candidates = 12;
-  int marginal_tile = -1;                               // MSC_MARGINAL_TILE: 1 / 0 = the fused tile kernel for every plan it takes / for none
-
-  float alloc_accept_gbps = 6650.f;
-};
+// the environment's switches (route.hpp Switches), read afresh by every call that plans, routes or allocates
 inline Switches read_switches() {
   Switches sw;
   if (const char *e = std::getenv("MSC_TAIL_MIN_ROWS")) sw.tail_forced = true, sw.tail_min_rows = (uint64_t)std::atoll(e);

@@ -425,7 +425,7 @@ MSC_DEV float nich_accum(float acc, float x, float smu_hi, float smu_lo, float c
 // 3/4 of a join (1.5), and a QUARTER of the compensated log1p that `acc -= c1 log1p(P)` costs (6 plain + 2 transcendental
 // per block): 6 plain + 0.5 transcendental where nich_accum is 9 + 2 (the mixed kernels run at the
 // issue rate of exactly this mix).  What it needs:
-//   * c1 bit-equal over the block for every group -- the host groups features by their nu prior (abi.cpp plan_groups),
+//   * c1 bit-equal over the block for every group -- the host groups features by their nu prior (tile_plan.hpp),
 //     the head kernel of every scoring / sweep call (kernels_state.hip k_fuse_tables) compares the c1 ln2 rows the
 //     suff-stats actually produced and clears the block's flag when they differ (suff-stats set feature by feature need
 //     not agree on the counts): such a block is evaluated feature by feature, nich_accum;

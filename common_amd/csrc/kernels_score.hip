@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void k_loo_own(const FeatDesc *__restrict__ fe
     s = __builtin_isinf(lm1) ? (double)crp[2 * (size_t)kpad + 1] + (double)crp[2 * (size_t)kpad + 3]
                              : (double)lm1 + (double)crp[crp_lo_cntm1(kpad) + g];
   }
-  // The kernel walks the tile plan's copy of the descriptors (abi.cpp plan_groups): runs of unmasked lookup features
+  // The kernel walks the tile plan's copy of the descriptors (tile_plan.hpp): runs of unmasked lookup features
   // first.  For those a feature is value -> table entry, two dependent loads and nothing else, and with one row per
   // thread nobody hides them: four features at a time, without a branch between the loads (the value fetch and the
   // clamp of the tile kernels' lookup runs), so that four loads are in flight where one was.  Everything else --
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) void k_loo_own(const FeatDesc *__restrict__ fe
 // its own group's entry -- 64 cache lines per wave instruction, two of them per nich feature and row (96 bytes of
 // constants) -- and the kernel ran at the rate the address unit splits such gathers, 0.25 ms for C3's 64 columns
 // (0.97 TB/s of 64-byte sectors for 4 + 4 useful bytes).  Here a workgroup of 1024 threads takes 4096 rows (four per
-// thread, coalesced) through the stages of the leave-one-out plan (abi.cpp plan_groups: consecutive features whose
+// thread, coalesced) through the stages of the leave-one-out plan (tile_plan.hpp: consecutive features whose
 // blocks -- the lookup families' leave-one-out tables, nich's six doubles per group, for all kpad groups -- share the
 // 128 KiB slot): the block copy is coalesced, the per-row reads are LDS reads at the lane's own address.  (Two workgroups
 // of 512 threads with 64 KiB each, covering each other's copies: 149 us on C3 against 140 -- twice the stages.)  Same terms, same order of the double sum as k_loo_own: same bits.
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(kLooThreads) void k_loo_own_lds(const FeatDesc *__r
   // the value latency is not what a stage waits for.  profiles/r05_loo_accumulate.txt)
   int f0 = 0;
   while (f0 < nfeat) {
-    const int f1 = (int)feats[f0].loo_stage_end;           // (at most kLooStageFeats features: abi.cpp plan_groups)
+    const int f1 = (int)feats[f0].loo_stage_end;           // (at most kLooStageFeats features: tile_plan.hpp)
     uint32_t w[kLooStageFeats][kLooRows];
     __syncthreads();                                      // the slot's previous readers are done
     // the blocks, 1 KiB per wave instruction straight into LDS (global_load_lds_dwordx4) ...
@@ -910,7 +910,7 @@ __global__ __launch_bounds__(1024, 4) void k_score_lookups(const FeatDesc *__res
 // the sums score_tile<SPLIT> forms for such a plan, same bits.  (The kernels that stage the nich constants through LDS
 // feature group by feature group ran sixteen nich columns on a million rows at 1.16 ms; this one: see DESIGN section 5.)
 // ---------------------------------------------------------------------------
-// LOOK: the plan has a first phase of a FEW lookup features (abi.cpp plan_groups: at most kPackMaxLookups): their table rows
+// LOOK: the plan has a first phase of a FEW lookup features (tile_plan.hpp: at most kPackMaxLookups): their table rows
 // are gathered from L2 into a second set of sums (pack_l2_lookups) -- (prior lo + lookups) + (nich features), as everywhere.
 template <bool LOO, bool CRP, bool PAIR, bool LOOK>
 __global__ __launch_bounds__(kNichPackWaves * 64, kNichPackWaves / 4) void k_score_nich_pack(const FeatDesc *__restrict__ feats, int nsplit, uint32_t K, uint32_t kpad, uint64_t row0,
@@ -1140,7 +1140,7 @@ const Nich1Shape kNich1Shapes[kNich1NumShapes] = {{4, 2}, {4, 1}, {4, 4}, {4, 6}
 // one LDS read per group at a constant offset from the row's table row (tables of the tail's groups alone, packed
 // [table row][64 groups] by k_tail_pack once per pass, staged with a 65-float row stride -- rows that differ in their
 // value hit different banks), a nich feature takes its constants per group as SCALAR operands (s_load from the feature's
-// table: no register, no LDS).  Same plan as the tile kernels (abi.cpp plan_groups: lookup features in the first phase,
+// table: no register, no LDS).  Same plan as the tile kernels (tile_plan.hpp: lookup features in the first phase,
 // plain nich features in the second), sums in plan order from the prior's low half, the prior's high half last, the
 // leave-one-out value in place of the row's own group.  TGP = the tail's groups rounded up to 16 (a lane's sums stay in
 // registers across the whole plan).  Every row count takes this kernel for the tail of an eligible state (launch_score),
@@ -1516,7 +1516,7 @@ static bool tail_rows_geometry(const TailPlan &tp, int num_cus, int nfeat, int n
                                unsigned &grid) {
   if (!tp.ok || (tp.pack_rows > 0 && tp.pack == nullptr)) return false;
   // the slot: up to 200 table rows (52 KiB) in what 64 KiB leave beside the second phase's block (64 floats a nich
-  // feature) -- two workgroups a CU; it holds the largest table (abi.cpp narrow_tail_fits)
+  // feature) -- two workgroups a CU; it holds the largest table (route.hpp narrow_tail_fits)
   const size_t nich_bytes = (size_t)(nfeat - nsplit) * 64 * sizeof(float);
   const uint32_t fit = (uint32_t)((64u * 1024u - nich_bytes) / (kTailStride * sizeof(float)));
   cap_rows = std::max<uint32_t>(1u, std::min<uint32_t>(tp.pack_rows, std::min<uint32_t>(200u, fit)));

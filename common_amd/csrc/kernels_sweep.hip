@@ -1627,7 +1627,7 @@ static int launch_narrow_t(hipStream_t stream, int num_cus, size_t lds_bytes, co
   if (gx > cap) gx = cap;
   return launch_narrow_s<L, 1, SWEEP>(stream, gx, lds_bytes, feats_dev, nfeat, K, kpad, row0, nrows, z, own, crp, out, ld, row_id0, z_out, rng, zero);
 }
-// lanes_per_row: 4, 8 or 16; table_rows: sum over features of narrow_table_rows (abi.cpp narrow_lanes: within 64 KiB)
+// lanes_per_row: 4, 8 or 16; table_rows: sum over features of narrow_table_rows (route.hpp narrow_lanes: within 64 KiB)
 int launch_narrow(hipStream_t stream, int num_cus, int lanes_per_row, uint32_t table_rows, bool sweep, const FeatDesc *feats_dev,
                   int nfeat, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z, const float *own,
                   const float *crp, float *out, uint64_t ld, uint64_t row_id0, int32_t *z_out, const uint64_t *rng,
@@ -1898,7 +1898,7 @@ int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath p
       hipLaunchKernelGGL((k_sweep_nich_pack<false, false>), (note_kernel(1, "k_sweep_nich_pack<false, false, 0>"), g), dim3(kNichPackWaves * 64), 0, stream, feats_dev, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero);
   }
   else if (pair && path == MSC_PATH_TILE_ROLES)
-    // PAIR mode (its draw sums a row's entries two to a lane where the other tile kernels sum four: abi.cpp route_sweep)
+    // PAIR mode (its draw sums a row's entries two to a lane where the other tile kernels sum four: route.hpp route_sweep)
     hipLaunchKernelGGL((k_sweep_tile_roles<0, true>), (note_kernel(1, "k_sweep_tile_roles<0, true>"), rows_grid(nrows, 256, cap)), dim3(1024), 0,
                        stream, feats_dev, nfeat, nsplit, K, kpad, row0, nrows, row_id0, z, own, crp, rng, zero, static_cast<const float *>(nullptr));
   else if (small4)
@@ -1916,7 +1916,7 @@ int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath p
   return launch_status("sweep kernel");
 }
 
-// 256 < K <= 384 (abi.cpp route_sweep): the kernel of the plan's path over the full tile -- TILE_ROLES the role-split
+// 256 < K <= 384 (route.hpp route_sweep): the kernel of the plan's path over the full tile -- TILE_ROLES the role-split
 // kernel, NICH_PACK the nich-only kernel (with a few lookups when nsplit > 0), LOOKUPS the lookups-only kernel --, the
 // tail's scores from `tail` (k_score_tail_rows wrote them)
 int launch_sweep_roles_tail(hipStream_t stream, int num_cus, ScorePath path, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K,

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "msc_internal.hpp"
+#include "route.hpp"
 
 namespace msc {
 
@@ -60,39 +61,10 @@ int launch_gp_large_fix(hipStream_t stream, int num_cus, const FeatDesc *feats_d
 struct Nich1Shape { int q, visits; };
 constexpr int kNich1NumShapes = 8;
 extern const Nich1Shape kNich1Shapes[kNich1NumShapes];
-constexpr uint32_t kTailMaxGroups = 128;
-constexpr uint64_t kNarrowMaxRows = 65536;   // views from this many rows on do not take the K <= 64 narrow tiling (abi.cpp narrow_lanes:
-                                             // at 100k rows its sweeps already cost 2.5x the lane <-> row kernel's, at 20k they are level)
-constexpr uint64_t kTailMinRows = 16384;     // fewer rows always stay with the tile kernels (lanes as groups)
-constexpr uint32_t kTailStride = 65;         // floats per table row k_score_tail_rows stages (64 groups + 1)
-// What a pass over `nrows` rows costs, in microseconds, on either kind of kernel -- only to choose between them.  The
-// prices follow the PLAN (abi.cpp plan_cost; measured on one MI355X, 1M rows: tools/scans/c3_pieces.py --spec=...,
-// tail_threshold.py, small_n.py, n_scan.py) -- with C3's prices for every plan (round 3) a state of lookup features only took the
-// lane <-> row kernel up to 128 groups and ran 32 bool columns at 0.58 ms (K = 128) and 0.87 (K = 64) where the tile pass
-// takes 0.34:
-//   tile kernels: one workgroup of 128 rows per CU and round; a round costs ~6 us + 0.45 a staged lookup feature + 0.012 a
-//   staged table row + 1.5 a nich feature (the role-split kernels overlap the two halves: half the nich share; the
-//   nich-only kernels 1.3 a feature); C3: 50 us a round of a scoring pass, 55 of a fused sweep; at most 128 groups on the
-//   role-split / nich-only kernels (PAIR mode, 256 rows a workgroup): kPairTileShare of that;
-//   lane <-> row kernel: a launch of g groups takes ~2 us + g (0.5 + 0.03 a lookup feature + 0.057 a nich feature) per round
-//   of 1024 rows a CU (two workgroups of 512); C3: 2 + 2.5 g (round 3 priced it 30 + 1.7 g: the same at 32-48 groups).
-// (struct PlanCost: msc_internal.hpp -- the state keeps its plan's)
-inline double tile_rounds_us(uint64_t workgroups, int num_cus, bool sweep, const PlanCost &pc = PlanCost()) {
-  return (sweep ? pc.sweep_round_us : pc.tile_round_us) * (double)((workgroups + (uint64_t)num_cus - 1) / (uint64_t)num_cus);
-}
-inline double tail_rows_us(uint32_t groups, bool exact, uint64_t nrows, int num_cus, const PlanCost &pc = PlanCost()) {
-  const uint32_t widest = exact ? 32u : 64u, nblk = (groups + widest - 1) / widest;      // (as launch_score_tail cuts them)
-  const uint32_t per = ((groups + nblk - 1) / nblk + 15u) / 16u * 16u;
-  // (a round of 1024 rows a CU that is not full costs less than a whole one -- the workgroups are 512 rows, most CUs get
-  // none -- but not in proportion: sixteen dd columns, two exact launches: 0.066 ms at 262k rows, 0.050 at 100k, ~0.04 at 70k)
-  const double frac = (double)nrows / (1024.0 * num_cus);
-  const double rounds = frac >= 1.0 ? frac : std::max(0.6, 0.4 + 0.6 * frac);      // (100k rows, 0.38 of a round: 0.75 of its price)
-  return (double)nblk * (pc.tail_fixed_us + pc.tail_group_us * per) * rounds;
-}
-// what k_score_tail_rows needs to score a partly filled last tile (<= kTailMaxGroups groups; abi.cpp: the plan's first
+// what k_score_tail_rows needs to score a partly filled last tile (<= kTailMaxGroups groups; tile_plan.hpp plan_layout: the plan's first
 // phase is lookup features only, the second plain nich features).  ok = false: the plan is not for it.
 struct TailPlan {
-  bool ok = false;            // (abi.cpp narrow_tail_fits: the plan, the tile and the LDS the staged tables need)
+  bool ok = false;            // (route.hpp narrow_tail_fits: the plan, the tile and the LDS the staged tables need)
   bool exact = true;          // the tile kernels' bits (two sums per group: score passes, where the row count picks the kernel);
                               // false: one sum per group, faster (sweeps: the choice of kernel follows the bound view's row count, not the call's)
   bool masked_nich = false;   // the first phase holds masked nich columns (the kernel's instantiation that evaluates them)
@@ -119,10 +91,6 @@ int launch_sweep_rows(hipStream_t stream, int num_cus, const TailPlan &tp, const
                       const uint64_t *rng, ZeroSpans zero);
 int launch_score_pair_tail(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, int nfeat, int nsplit, uint32_t K, uint32_t kpad,
                            uint64_t row0, uint64_t nrows, const int32_t *z, const float *own, const float *crp, float *tail, uint64_t ld);
-// How a pass runs (abi.cpp route_score): rows a wave of k_score_tile<R, 16> takes, PAIR mode, what scores a partly filled
-// last tile (the tile kernels, k_score_tail_rows, k_score_tile_roles in PAIR mode), k_score_nich1's code (nich1_shape_for)
-enum class LastTile { tiles, rows, pair };
-struct ScoreShape { int wave_rows = 8; bool pair = false; LastTile last = LastTile::tiles; int nich1 = 0; };
 int launch_score(hipStream_t stream, int num_cus, ScorePath path, const TailPlan &narrow_tail, const ScoreShape &shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
                  uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, const int32_t *z,
                  const float *own, const float *crp, float *out, uint64_t ld);
@@ -140,7 +108,7 @@ inline int launch_status(const char *what) {
   return e == hipSuccess ? 0 : fail(MSC_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
 }
 
-// kernels_sweep.hip (launchers launch what abi.cpp route_sweep chose: a shape it never sends is MSC_EHIP, reported)
+// kernels_sweep.hip (launchers launch what route.hpp route_sweep chose: a shape it never sends is MSC_EHIP, reported)
 int launch_sweep_nich1(hipStream_t stream, int num_cus, bool transposed, const FeatDesc *feats_dev, uint32_t K,
                        uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z,
                        const float *own, const float *crp, const uint64_t *rng_dev, ZeroSpans zero);
@@ -151,9 +119,7 @@ constexpr int kNichPackWaves = MSC_NICH_PACK_WAVES;   // waves a workgroup of th
 #ifndef MSC_NICH_PACK_NC
 #define MSC_NICH_PACK_NC 4
 #endif
-constexpr int kPackMaxLookups = 4;                      // lookup features (after fusing the bool columns) a plan may hold and still take the nich-only kernels
 constexpr int kNichPackNC = MSC_NICH_PACK_NC;          // groups of the lane a block part of the nich-only kernels takes (256 registers a wave there)
-constexpr double kPairTileShare = 0.62;     // what a pass of the role-split kernels costs in PAIR mode (<= 128 groups), of a full tile pass
 int launch_sweep_mixed(hipStream_t stream, int num_cus, bool has_dm, ScorePath path, const ScoreShape &shape, const FeatDesc *feats_dev, int nfeat, int nsplit,
                        uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z,
                        const float *own, const float *crp, const uint64_t *rng, ZeroSpans zero);

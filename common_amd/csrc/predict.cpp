@@ -31,7 +31,7 @@ static MarginalKind route_marginal(const msc_state *st) {
   if (st->nich1) return st->K <= 1024 ? MarginalKind::nich1 : MarginalKind::generic;
   if (!st->has_dm && st->K <= 256 && view_rows(st) >= kTailMinRows) {
     const int forced = read_switches().marginal_tile;
-    if (forced >= 0 ? forced != 0 : st->tile_path == MSC_PATH_TILE) return MarginalKind::tile;
+    if (forced >= 0 ? forced != 0 : st->plan.tile_path == MSC_PATH_TILE) return MarginalKind::tile;
   }
   return MarginalKind::generic;
 }
@@ -59,7 +59,7 @@ extern "C" int msc_score_marginal(msc_state *st, const msc_dataview *view, const
     case MarginalKind::tile:
       if (z_dev) MSC_TRY(run_loo_own(st, row0, nrows, z_dev, true));
       MSC_TRY(refresh_fused_tables(st));                  // (the kernel walks the fused plan)
-      return launch_marginal_tile(s, cus, st->desc_fuse_dev, (int)st->fuse_nfeat, (int)st->fuse_split, st->K, st->kpad, row0, nrows,
+      return launch_marginal_tile(s, cus, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad, row0, nrows,
                                   z_dev, st->own, st->logpc, st->marg_norm, logp_dev, map_dev, map_logresp_dev);
     case MarginalKind::generic: {
       // (the chunk of SweepKind::generic: rows of K rounded up to 64 floats; the scratch is the state's and stays with it,

@@ -331,7 +331,7 @@ MSC_DEV void score_dm_feature(const FeatDesc &fd, uint32_t kpad, uint32_t kb, in
   }
 }
 
-// The same feature with its tables staged in LDS by the group (abi.cpp plan_groups does that when all dim + 1 of
+// The same feature with its tables staged in LDS by the group (tile_plan.hpp does that when all dim + 1 of
 // them fit the slot: small counts).  Branch-free: what must not count -- a masked row, a row whose total is beyond
 // the tables (k_gp_large_fix scores it whole) -- reads entry 0, which is exactly zero; four rows' reads go out before
 // their adds.  (From L2 the lookups of 4 x dm(4) on 1M rows ran at 1.9 ms; staged, with the branches, 1.75; this: 1.38.)
@@ -387,7 +387,7 @@ MSC_DEV void score_dm_feature_staged(const FeatDesc &fd, int lane, uint64_t myro
 
 // ---------------------------------------------------------------------------
 // States without a dm feature.  The host packs consecutive features into groups whose table blocks
-// fit the 128 KiB LDS slot together (FeatDesc::grp_*, abi.cpp plan_groups); the workgroup copies a
+// fit the 128 KiB LDS slot together (FeatDesc::grp_*, tile_plan.hpp); the workgroup copies a
 // whole group, synchronises once, and then every wave runs through the group's features on its
 // own: value of its rows, lookups / evaluations, next feature.  Inside a group the waves drift
 // apart, so one wave's load latency sits under another's arithmetic; per (feature, 128-row chunk)
@@ -452,7 +452,7 @@ MSC_DEV void stage_group(const FeatDesc *__restrict__ feats, int f0, int f1, uin
 }
 
 // ---------------------------------------------------------------------------
-// second phase: the plain (unmasked) nich features, which the host puts last and in BLOCKS (abi.cpp plan_groups;
+// second phase: the plain (unmasked) nich features, which the host puts last and in BLOCKS (tile_plan.hpp;
 // family_math.hpp "nich BLOCKS").  Every tile kernel forms a row's second-phase sum by the same steps in the same order --
 // the features' summed c0, then block by block either ONE compensated log1p of the block's product (nich_block_finish) or,
 // where the head kernel found the block's c1 differing, nich_accum feature by feature -- so a row gets the same bits from
@@ -707,7 +707,7 @@ MSC_DEV void nich_block(const FeatDesc *__restrict__ feats, int f, const Src &sr
     nich_block_part<M, R, 3, NC, EST>(feats, f, src, xv, acc);
   }
 }
-// One SEGMENT of the second phase -- the features [f0, f1) of one LDS feature group (abi.cpp plan_layout; whole blocks) --
+// One SEGMENT of the second phase -- the features [f0, f1) of one LDS feature group (tile_plan.hpp plan_layout; whole blocks) --
 // in the order every kernel keeps: the segment's blocks of four that go as one, then those of three, of two, then every
 // feature left (on its own in the plan, or in a block whose c1 differ), nich_accum.  Four loops with ONE body each: a
 // single loop that branches to the four bodies costs ~300 bytes of scratch per lane (the allocator gives up on the 4 R
@@ -941,7 +941,7 @@ MSC_DEV void score_tile_nich_tail(const FeatDesc *__restrict__ feats, int f0, in
   }
   const bool blocks = uniform(as_scalar(feats)[first].nich_info != nullptr ? 1 : 0) != 0;
   while (f0 < nfeat) {
-    const int f1 = uniform((int)as_scalar(feats)[f0].grp_end);  // (a block never lies across two groups: abi.cpp plan_layout)
+    const int f1 = uniform((int)as_scalar(feats)[f0].grp_end);  // (a block never lies across two groups: tile_plan.hpp plan_layout)
     stage_group<W>(feats, f0, f1, kpad, ktile, lane, wave, lds);
     nich_segment<R, EST>(feats, f0, f1, blocks, NichFromLds{feats, lds, lane}, myrow, acc);
     f0 = f1;
