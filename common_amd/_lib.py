@@ -169,6 +169,14 @@ _SIGS = {
     # (ch, coords, n, slots_dev, ld_slots, host_seeds, sweep, values_host, evals_host)
     "msc_chains_hp_slice": (C.c_int, [C.c_void_p, C.POINTER(SliceCoord), C.c_uint32, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p, C.c_void_p]),
+    # (st, coords, n, slots_dev, out_dev)
+    "msc_score_joint": (C.c_int, [C.c_void_p, C.POINTER(SliceCoord), C.c_uint32, C.c_void_p, C.c_void_p]),
+    # (ch, coords, n, slots_dev, ld_slots, out_dev, ld_out)
+    "msc_chains_score_joint": (C.c_int, [C.c_void_p, C.POINTER(SliceCoord), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_uint64]),
+    # (ch, joint_dev, ld_joint, z_dev, ld_z, nrows, iter, best_dev, best_z_dev, ld_best, best_iter_dev)
+    "msc_chains_keep_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "msc_state_reduce_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "msc_state_commit_reduce": (C.c_int, [C.c_void_p]),

@@ -287,6 +287,24 @@ class ChainEnsemble(object):
                                                  evals.ctypes.data_as(C.c_void_p)))
         return values, evals
 
+    # the log joint ----------------------------------------------------------------
+    def score_joint(self, priors=None, slots=None, out=None):
+        """log p(X, z | hp, alpha) of EVERY chain and its parts in one launch (msc_chains_score_joint; asynchronous, no
+        host synchronisation, changes nothing): a float64 device tensor [nchains, nfeatures + 3], row c = (total,
+        score_assignment, the features' summed score_data ..., the hyper-priors' sum) of chain c -- bit for bit what
+        ens.states[c].score_joint(priors, slots_c) gives, whatever the number of chains.  priors: State.score_joint's
+        (one list for all chains, or a hypers.EnsembleHpSlice).  slots: uint8 device mask of the counted groups,
+        [ngroups] for all chains or [nchains, ngroups] (default: each chain's non-empty ones).  out: a float64 device
+        tensor of at least [nchains, nfeatures + 3] with contiguous rows (any row stride)."""
+        _, sp, ld_slots = self._check_hp_slice(0, slots)
+        arr, n = State._joint_priors(priors)
+        width = len(self.features) + 3
+        if out is None:
+            out = torch.empty((self.nchains, width), dtype=torch.float64, device=self.ctx.torch_device)
+        op, ld = A.matrix(out, torch.float64, self.nchains, width, self.ctx.torch_device, "out")
+        L.check(self.ctx.lib.msc_chains_score_joint(self._h, arr, n, sp, ld_slots, op, ld))
+        return out
+
     # split-merge proposals --------------------------------------------------------
     def split_merge(self, view, seed, sweep=0, nproposals=1, launch_iters=2, want_log=False, want_trace=False,
                     want_proposed=False, row_id0=0):
@@ -326,7 +344,8 @@ class ChainEnsemble(object):
             (C.c_uint64 * self.nchains)(*seeds), int(sweep), ptr(log), ptr(trace), ptr(proposed), A.ptr(counters)))
         return SplitMergeResult(counters=counters, log=log, trace=trace, proposed=proposed)
 
-    def run(self, view, niters, seed, hp=None, sweep=0, order=None, trace_every=None, zmatrix=None, split_merge=None):
+    def run(self, view, niters, seed, hp=None, sweep=0, order=None, trace_every=None, zmatrix=None, split_merge=None,
+            joint=None):
         """niters iterations of the sampler on every chain: iteration i is self.sweep(view, 1, seed, sweep=sweep + i,
         order=order) followed, when split_merge=n is given, by self.split_merge(view, seed, sweep=(sweep + i) * n,
         nproposals=n) (whose counters are added to ens.split_merge_counters) and, when hp (a hypers.EnsembleHpSlice of this
@@ -335,7 +354,11 @@ class ChainEnsemble(object):
         device tensor [nchains, niters // trace_every, nrows] of every chain's z after each trace_every-th iteration
         (trace_every None: after every iteration when a zmatrix is given, else no trace and trace is None); values the
         float32 host array [nchains, niters, ncoords] of what each step installed, in the order of hp.coords (ncoords =
-        0 without hp).  zmatrix: a ZMatrix over the view's rows that takes the whole trace in one add."""
+        0 without hp).  zmatrix: a ZMatrix over the view's rows that takes the whole trace in one add.
+        joint: a JointTracker of this ensemble; at the end of every iteration whose count (over all the runs the tracker
+        has seen) is a multiple of tracker.every, self.score_joint writes the chains' log joint into the tracker's next
+        sample and, with keep_best, msc_chains_keep_best keeps every chain's best z (iteration number sweep + i).  Two
+        asynchronous launches a sample; without `joint` run makes exactly the calls it made before."""
         self._check_open()
         if self.z is None:
             raise ValueError("no assignment yet: call assign() or seat() first")
@@ -346,6 +369,8 @@ class ChainEnsemble(object):
             raise ValueError("hp must be an EnsembleHpSlice of this ensemble")
         if split_merge is not None and not 0 <= int(split_merge) < (1 << 32):
             raise ValueError("split_merge must be None or a number of proposals in [0, 2^32)")
+        if joint is not None and (not isinstance(joint, JointTracker) or joint.ens is not self):
+            raise ValueError("joint must be a JointTracker of this ensemble")
         if zmatrix is not None and trace_every is None:
             trace_every = 1
         trace = None
@@ -367,6 +392,8 @@ class ChainEnsemble(object):
                     values[:, i, :] = hp.last_values
             if trace is not None and (i + 1) % trace_every == 0:
                 trace[:, (i + 1) // trace_every - 1, :].copy_(self.z)
+            if joint is not None:
+                joint._iteration(sweep + i, niters - i)
         if zmatrix is not None and trace.shape[1] > 0:
             zmatrix.add(trace.view(-1, n))
         return RunResult(trace=trace, values=values)
@@ -603,6 +630,107 @@ class ChainEnsemble(object):
             self.close()
         except Exception:
             pass
+
+
+def joint_tracker_args(every, keep_best):
+    """the argument checks of JointTracker that need no device -> (every, keep_best)"""
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError("every must be an int >= 1")
+    if not isinstance(keep_best, (bool, np.bool_)):
+        raise ValueError("keep_best must be True or False")
+    return int(every), bool(keep_best)
+
+
+class JointTracker(object):
+    """The trace of every chain's log joint over the iterations of ChainEnsemble.run(..., joint=tracker), and every
+    chain's best sample so far, all on the device: nothing is copied to the host and nothing waits until a result is read.
+
+    every: a sample after each every-th iteration, counted over all the runs the tracker sees.  keep_best: keep each
+    chain's highest-scoring z (msc_chains_keep_best: strictly greater wins, so the first of equal maxima stays; NaN never
+    wins).  priors: ChainEnsemble.score_joint's -- with them the total is log p(X, z, hp, alpha) up to the flat priors.
+      joint       float64 device tensor [nchains, samples, nfeatures + 3], ChainEnsemble.score_joint's rows
+      best_joint  float64 [nchains], -inf until a sample has been kept
+      best_z      int32 [nchains, nrows]
+      best_iter   int64 [nchains], the iteration (run's sweep + i numbering) of the best sample, -1 until one is kept
+    A tracker persists across run calls: a run that continues the numbering continues the trace and keeps an earlier
+    best that it does not beat."""
+
+    def __init__(self, ens, every=1, keep_best=True, priors=None):
+        self.every, self.keep_best = joint_tracker_args(every, keep_best)
+        if not isinstance(ens, ChainEnsemble):
+            raise ValueError("ens must be a ChainEnsemble")
+        State._joint_priors(priors)                       # (checked here, built at every call)
+        self.ens, self.priors = ens, priors
+        self.nsamples, self._seen = 0, 0
+        self._buf = self._best = self._best_z = self._best_iter = None
+
+    def _state(self):
+        """the device tensors, made when first needed (best_z needs the assignment's rows)"""
+        if self._best is None:
+            ens = self.ens
+            ens._check_open()
+            if ens.z is None:
+                raise ValueError("no assignment yet: call assign() or seat() on the ensemble first")
+            dev = ens.ctx.torch_device
+            self._buf = torch.empty((ens.nchains, 0, len(ens.features) + 3), dtype=torch.float64, device=dev)
+            self._best = torch.full((ens.nchains,), float("-inf"), dtype=torch.float64, device=dev)
+            self._best_z = torch.full((ens.nchains, int(ens.z.shape[1])), -1, dtype=torch.int32, device=dev)
+            self._best_iter = torch.full((ens.nchains,), -1, dtype=torch.int64, device=dev)
+        return self
+
+    joint = property(lambda self: self._state()._buf[:, :self.nsamples])
+    best_joint = property(lambda self: self._state()._best)
+    best_z = property(lambda self: self._state()._best_z)
+    best_iter = property(lambda self: self._state()._best_iter)
+
+    def _iteration(self, it, left):
+        """run's hook at the end of iteration number `it`, `left` iterations of the run still to come (this one
+        included): room for their samples is made at once, so a run grows the trace at most once"""
+        self._seen += 1
+        if self._seen % self.every:
+            return
+        self._state()
+        ens = self.ens
+        if self.nsamples == self._buf.shape[1]:
+            room = max(1, (self._seen - 1 + int(left)) // self.every - (self._seen // self.every - 1))
+            grown = torch.empty((ens.nchains, self.nsamples + room, self._buf.shape[2]), dtype=torch.float64,
+                                device=self._buf.device)
+            grown[:, :self.nsamples].copy_(self._buf[:, :self.nsamples])
+            self._buf = grown
+        row = self._buf[:, self.nsamples]
+        ens.score_joint(priors=self.priors, out=row)
+        if self.keep_best:
+            z = ens.z
+            L.check(ens.ctx.lib.msc_chains_keep_best(ens._h, A.ptr(row), int(self._buf.stride(0)), A.ptr(z), int(z.stride(0)),
+                                                     int(z.shape[1]), int(it), A.ptr(self._best), A.ptr(self._best_z),
+                                                     int(self._best_z.stride(0)), A.ptr(self._best_iter)))
+        self.nsamples += 1
+
+    def totals(self):
+        """the totals' trace as a host array [nchains, samples] (one synchronisation)"""
+        return self.joint[:, :, 0].cpu().numpy()
+
+    def map(self):
+        """(chain, z row, joint) of the best sample kept over all chains: the MAP sample of the run (one
+        synchronisation); z row an int32 device tensor [nrows]"""
+        if not self.keep_best:
+            raise ValueError("the tracker was made with keep_best=False")
+        best = self.best_joint.cpu().numpy()
+        kept = self.best_iter.cpu().numpy() >= 0
+        if not kept.any():
+            raise ValueError("no sample has been kept yet")
+        c = int(np.argmax(np.where(kept, best, -np.inf)))
+        return c, self.best_z[c], float(best[c])
+
+    def rhat(self):
+        """split-R-hat of the totals over the chains (diagnostics.split_rhat)"""
+        from . import diagnostics
+        return diagnostics.split_rhat(self.totals())
+
+    def ess(self):
+        """effective sample size of the totals over the chains (diagnostics.ess)"""
+        from . import diagnostics
+        return diagnostics.ess(self.totals())
 
 
 def _create(ctx, states):

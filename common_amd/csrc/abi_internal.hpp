@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "joint_math.hpp"
 #include "msc_internal.hpp"
 
 namespace msc {
@@ -83,6 +84,10 @@ int slice_plan(const msc_state *st, const msc_slice_coord *coords, uint32_t n, S
 void slice_targets(const msc_state *st, const SlicePlan &plan, SliceTarget *targets);
 int slice_installed(msc_state *st, const SlicePlan &plan, const msc_slice_coord *coords, const float *val, const uint32_t *ev,
                     const uint32_t *stat, float *values_host, uint32_t *evals_host, int64_t chain);
+// the joint score's checks of a state's features and of the call's entries (msc_hp_slice's), and the entries as the
+// kernels take them, in the caller's order; shared by msc_score_joint and msc_chains_score_joint (chains.cpp)
+int joint_entries(const msc_state *st, const char *who, const msc_slice_coord *coords, uint32_t n,
+                  std::vector<JointCoord> &entries);
 // ---- what blocked.cpp defines for msc_chains_split_merge (chains.cpp): the move's route for a member, and the member's
 // pair state as the pair half of its table entry (launchers.hpp SmChain) ----
 struct SmChain;

@@ -123,9 +123,12 @@ struct msc_chains {
   // the chains' pair labels, int32 [nchains][nrows], grown by reserve_synced
   msc::DevBuf<msc::SmChain> sm_tab;       // [nchains]
   msc::DevBuf<int32_t> sm_ell;
+  // msc_chains_score_joint: the call's table, grown by reserve_synced as hp_buf is and staged through the same two areas
+  msc::DevBuf<msc::JointChain> joint_tab; // [nchains]
   msc::Retired retired;
 };
 static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
+static_assert(sizeof(msc::JointChain) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
 // bytes behind the MargChain table: the MargFeat table of nfeat features, then as many output pointers; and the entries of
 // a staging area beyond nchains that hold them
 static size_t marg_tail(uint32_t nfeat) { return (size_t)nfeat * (sizeof(msc::MargFeat) + sizeof(void *)); }
@@ -572,6 +575,71 @@ extern "C" int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords
     st->valid.crp_prepared();
   }
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// The log joint of every chain in one launch (k_chains_score_joint), and the best sample of every chain kept on the
+// device (k_chains_keep_best).  Neither waits for the stream (but to grow the table once) nor changes a state.
+// ---------------------------------------------------------------------------
+extern "C" int msc_chains_score_joint(msc_chains *ch, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
+                                      uint64_t ld_slots, double *out_dev, uint64_t ld_out) {
+  MSC_REQUIRE(ch, "null argument");
+  const uint32_t nc = (uint32_t)ch->states.size();
+  if (nc == 0) return MSC_OK;
+  const msc_state *st0 = ch->states[0];
+  const joint::JointCheck chk = joint::check_score_joint("msc_chains_score_joint", out_dev != nullptr, coords != nullptr, n,
+                                                         st0->nfeat, ld_out, slots_dev != nullptr, ld_slots, st0->K);
+  MSC_REQUIRE(chk.ok, "%s", chk.message);
+  for (uint32_t c = 0; c < nc; c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_score_joint: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  // the checks of the features and of the entries, once: the members' feature lists are equal (msc_chains_create)
+  std::vector<JointCoord> entries;
+  MSC_TRY(joint_entries(st0, "msc_chains_score_joint", coords, n, entries));
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  for (msc_state *st : ch->states) MSC_TRY(ensure_raw(st));
+  hipStream_t s = ctx->stream;
+  MSC_HIP(reserve_synced(s, ch->joint_tab, nc));
+  int a = 0;
+  MSC_TRY(chains_stage(ch, &a));
+  JointChain *tab = reinterpret_cast<JointChain *>(ch->stage[a].get());
+  for (uint32_t c = 0; c < nc; c++) {
+    const msc_state *st = ch->states[c];
+    JointChain &e = tab[c];
+    e.feats = st->desc_dev;
+    e.cnt = st->cnt_u32;
+    e.slots = slots_dev ? slots_dev + (size_t)c * ld_slots : nullptr;
+    e.out = out_dev + (size_t)c * ld_out;
+    e.alpha = st->alpha;
+    e.pad = 0;
+  }
+  MSC_HIP(hipMemcpyAsync(ch->joint_tab, tab, sizeof(JointChain) * nc, hipMemcpyHostToDevice, s));
+  MSC_TRY(chains_staged(ch, a, s));
+  if (launch_chains_score_joint(s, ch->joint_tab, nc, st0->nfeat, st0->K, st0->kpad, entries.data(), n))
+    return fail(MSC_EHIP, "k_chains_score_joint launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_keep_best(msc_chains *ch, const double *joint_dev, uint64_t ld_joint, const int32_t *z_dev,
+                                    uint64_t ld_z, uint64_t nrows, uint64_t iter, double *best_dev, int32_t *best_z_dev,
+                                    uint64_t ld_best, int64_t *best_iter_dev) {
+  MSC_REQUIRE(ch, "null argument");
+  const joint::JointCheck chk = joint::check_keep_best("msc_chains_keep_best", joint_dev && z_dev && best_dev && best_z_dev &&
+                                                       best_iter_dev, ld_joint, nrows, ld_z, ld_best);
+  MSC_REQUIRE(chk.ok, "%s", chk.message);
+  MSC_REQUIRE(iter <= (uint64_t)INT64_MAX, "msc_chains_keep_best: iteration %llu does not fit best_iter's int64",
+              (unsigned long long)iter);
+  const uint32_t nc = (uint32_t)ch->states.size();
+  if (nc == 0) return MSC_OK;
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  if (launch_chains_keep_best(ctx->stream, nc, joint_dev, ld_joint, z_dev, ld_z, nrows, (int64_t)iter, best_dev, best_z_dev,
+                              ld_best, best_iter_dev))
+    return fail(MSC_EHIP, "k_chains_keep_best launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return MSC_OK;
 }
 
 // ---------------------------------------------------------------------------

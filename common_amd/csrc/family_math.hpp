@@ -602,6 +602,21 @@ MSC_DEV double hp_eval(int family, uint32_t dim, const float *h, const float *hp
   }
 }
 
+// MSC_PRIOR_* at x, in double (the partner: NONINF_BETA's other coordinate at its current value): the hyper-prior term of
+// a slice target (kernels_slice.hip) and of the joint score (kernels_joint.hip)
+MSC_DEV double slice_log_prior(uint32_t kind, double x, double a, double b, double partner) {
+#pragma clang fp contract(off)
+  switch (kind) {
+    case MSC_PRIOR_EXPONENTIAL: return x < 0.0 ? -INFINITY : log(a) - a * x;
+    case MSC_PRIOR_NORMAL: {
+      const double d = x - a;
+      return -0.5 * log(2.0 * kPi * b) - 0.5 * (d * d) / b;
+    }
+    case MSC_PRIOR_NONINF_BETA: return -2.5 * log(x + partner);
+    default: return 0.0;
+  }
+}
+
 // ============================ typed column loads ============================
 // runtime_cast::cast<T>(px, t) (runtime_type.hpp:145-166): load as the stored C
 // type, convert with the implicit C++ conversion.

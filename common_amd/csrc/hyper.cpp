@@ -1,5 +1,6 @@
 // hyper.cpp -- hyper-parameter inference on the device: grids (kernels_hp.hip: msc_hp_grid_*) and slice sampling
-// (kernels_slice.hip: msc_hp_slice, msc_theta_slice).  Host logic only; the core it stands on is abi.cpp, through
+// (kernels_slice.hip: msc_hp_slice, msc_theta_slice), and the log joint their targets add up to (kernels_joint.hip:
+// msc_score_joint).  Host logic only; the core it stands on is abi.cpp, through
 // abi_internal.hpp.
 #include <algorithm>
 #include <cmath>
@@ -425,4 +426,46 @@ extern "C" int msc_theta_slice(msc_state *st, const uint32_t *features, const fl
                 features[i], first_bad);
   }
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// the log joint log p(X, z | hp, alpha) of a state (kernels_joint.hip)
+// ---------------------------------------------------------------------------
+// What msc_score_joint and msc_chains_score_joint (chains.cpp) check of a state's feature list and of the entries before
+// anything is launched, and the entries as the kernels take them, in the CALLER's order (the order p is added in).
+int msc::joint_entries(const msc_state *st, const char *who, const msc_slice_coord *coords, uint32_t n,
+                       std::vector<JointCoord> &entries) {
+  for (uint32_t f = 0; f < st->nfeat; f++)
+    if (st->feats[f].family == MSC_NIW)
+      return fail(MSC_EUNSUPPORTED, "%s: feature %u is niw, whose score_data the double evaluator (hp_eval) does not have", who,
+                  f);
+  entries.clear();
+  if (n == 0) return MSC_OK;
+  SlicePlan plan;
+  MSC_TRY(slice_plan(st, coords, n, plan));          // msc_hp_slice's checks
+  entries.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const msc_slice_coord &c = coords[i];
+    entries.push_back(JointCoord{c.feature, c.coord, c.prior, c.prior == MSC_PRIOR_NONINF_BETA ? c.partner : c.coord,
+                                 c.prior_a, c.prior_b});
+  }
+  return MSC_OK;
+}
+
+extern "C" int msc_score_joint(msc_state *st, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
+                               double *out_dev) {
+  MSC_REQUIRE(st, "null state");
+  const joint::JointCheck chk = joint::check_score_joint("msc_score_joint", out_dev != nullptr, coords != nullptr, n, st->nfeat,
+                                                         joint::joint_row(st->nfeat), slots_dev != nullptr, 0, st->K);
+  MSC_REQUIRE(chk.ok, "%s", chk.message);
+  MSC_TRY(refuse_mid_step(st, "msc_score_joint"));
+  std::vector<JointCoord> entries;
+  MSC_TRY(joint_entries(st, "msc_score_joint", coords, n, entries));
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  MSC_TRY(device_error_check(st->ctx));
+  MSC_TRY(ensure_raw(st));
+  if (launch_score_joint(st->ctx->stream, st->desc_dev, st->nfeat, st->K, st->kpad, st->cnt_u32, slots_dev, st->alpha,
+                         entries.data(), n, out_dev))
+    return fail(MSC_EHIP, "k_score_joint launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return MSC_OK;
 }

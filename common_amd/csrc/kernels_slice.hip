@@ -103,20 +103,6 @@ MSC_DEV float slice_update(G &g, float x0, double w, const SliceUniforms &r, uin
   return x;
 }
 
-// MSC_PRIOR_* at x, in double (the partner: NONINF_BETA's other coordinate at its current value)
-MSC_DEV double slice_log_prior(uint32_t kind, double x, double a, double b, double partner) {
-#pragma clang fp contract(off)
-  switch (kind) {
-    case MSC_PRIOR_EXPONENTIAL: return x < 0.0 ? -INFINITY : log(a) - a * x;
-    case MSC_PRIOR_NORMAL: {
-      const double d = x - a;
-      return -0.5 * log(2.0 * kPi * b) - 0.5 * (d * d) / b;
-    }
-    case MSC_PRIOR_NONINF_BETA: return -2.5 * log(x + partner);
-    default: return 0.0;
-  }
-}
-
 // The target of one coordinate of k_hp_slice, evaluated by the whole workgroup: every thread holds the same values, so
 // every thread takes the same branches and meets the same barriers.
 struct HpSliceTarget {

@@ -312,6 +312,17 @@ int launch_theta_slice(hipStream_t stream, const ThetaJob *jobs_dev, uint32_t nj
                        unsigned long long *evals_part, uint32_t *bad_part);
 int launch_unpack(hipStream_t stream, const uint8_t *records, const uint8_t *mask, uint64_t nrows,
                   uint32_t rowsize, uint32_t maskrowsize, const void *feats_dev, uint32_t nfeat);
+// kernels_joint.hip (msc_score_joint / msc_chains_score_joint / msc_chains_keep_best): one workgroup per state or chain
+// writes the row of nfeatures + 3 doubles; coords: the n hyper-prior entries on the HOST (they travel as kernel
+// arguments, kJointCoords a launch); keep_best: one workgroup per chain
+int launch_score_joint(hipStream_t stream, const FeatDesc *feats_dev, uint32_t nfeat, uint32_t K, uint32_t kpad,
+                       const uint32_t *cnt, const uint8_t *slots, float alpha, const JointCoord *coords, uint32_t n,
+                       double *out);
+int launch_chains_score_joint(hipStream_t stream, const JointChain *chains_dev, uint32_t nchains, uint32_t nfeat, uint32_t K,
+                              uint32_t kpad, const JointCoord *coords, uint32_t n);
+int launch_chains_keep_best(hipStream_t stream, uint32_t nchains, const double *joint, uint64_t ld_joint, const int32_t *z,
+                            uint64_t ld_z, uint64_t nrows, int64_t iter, double *best, int32_t *best_z, uint64_t ld_best,
+                            int64_t *best_iter);
 
 // kernels_pred.hip
 int launch_pred_prepare(hipStream_t stream, const PredFeat *pfs_dev, const std::vector<PredFeat> &pfs, uint32_t K,

@@ -107,6 +107,27 @@ struct HpChain {
   float alpha;               // alpha at the call; k_hp_slice_chains leaves the installed one here for the rebuild
   uint32_t pad;
 };
+// msc_score_joint / msc_chains_score_joint (kernels_joint.hip): the hyper-prior entries of a call travel as a kernel
+// argument, kJointCoords of them a launch -- no table of them to upload, so the single-state call copies nothing at all.
+// Entries past the first launch's are added, in entry order still, by follow-up launches of k_joint_priors.
+constexpr uint32_t kJointCoords = 64;
+struct JointCoord {
+  uint32_t feature;          // the state feature, or MSC_HP_CLUSTER
+  uint32_t coord, prior, partner;
+  float prior_a, prior_b;
+};
+struct JointCoords {
+  JointCoord e[kJointCoords];
+};
+// what is per chain of the ensemble's call: the chain's state, its mask and its row of the output
+struct JointChain {
+  const FeatDesc *feats;
+  const uint32_t *cnt;
+  const uint8_t *slots;      // the chain's mask of counted slots or null (the non-empty ones)
+  double *out;               // the chain's row, nfeatures + 3 doubles
+  float alpha;
+  uint32_t pad;
+};
 // msc_theta_slice: one bbnc feature of the call (a row of workgroups, one lane a slot)
 struct ThetaJob {
   const uint32_t *raw_u32;   // heads, tails

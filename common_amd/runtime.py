@@ -779,6 +779,36 @@ class State(object):
                                              evals.ctypes.data_as(C.c_void_p)))
         return {f: int(e) for f, e in zip(feats, evals)}
 
+    # the log joint (msc_score_joint) ------------------------------------------------------------------------------------
+    @classmethod
+    def _joint_priors(cls, priors):
+        """score_joint's `priors` -> (the msc_slice_coord array or None, its length): None, a list of hp_slice's entry
+        dicts (the width may be left out: a prior has none), or what carries one as .coords (hypers.FeatureHpSlice,
+        EnsembleHpSlice).  ChainEnsemble.score_joint shares it."""
+        if priors is None:
+            return None, 0
+        coords = list(getattr(priors, "coords", priors))
+        for c in coords:
+            if not isinstance(c, dict) or "feature" not in c:
+                raise ValueError("priors must be hp_slice's entry dicts (or carry them as .coords), not %r" % (c,))
+        if not coords:
+            return None, 0
+        return cls._slice_coord_array([dict(c, width=c.get("width", 1.0)) for c in coords]), len(coords)
+
+    def score_joint(self, priors=None, slots=None, out=None):
+        """log p(X, z | hp, alpha) of the state and its parts: a float64 device tensor [nfeatures + 3] = (total,
+        score_assignment, the features' summed score_data over the counted groups ..., the hyper-priors' sum), all in
+        double on the device (msc_score_joint; asynchronous, changes nothing).  priors: hp_slice's entries whose priors
+        are added at the coordinates' current values (default: none, the last part is 0).  slots: uint8 device mask of
+        the counted groups (default: the non-empty ones)."""
+        arr, n = self._joint_priors(priors)
+        width = len(self.features) + 3
+        if out is None:
+            out = torch.empty(width, dtype=torch.float64, device=self.ctx.torch_device)
+        op = A.flat(out, torch.float64, width, self.ctx.torch_device, "out")
+        L.check(self.ctx.lib.msc_score_joint(self._h, arr, n, self._slots(slots), op))
+        return out
+
     # posterior predictive sampling -------------------------------------------
     _PRED_DTYPES = {L.BB: torch.uint8, L.BBNC: torch.uint8, L.GP: torch.uint32, L.BNB: torch.uint32, L.DD: torch.int32,
                     L.NICH: torch.float32, L.NIW: torch.float32}

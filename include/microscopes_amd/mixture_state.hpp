@@ -177,6 +177,24 @@ public:
     for (auto it = gm_.begin(); it != gm_.end(); ++it) total += v[it->second.data_];
     return total;
   }
+  // log p(X, z | hp, alpha) = score_assignment() + the sum over the components of score_likelihood(c), what the
+  // reference's users plot to judge burn-in (entity_state.hpp:76-83) -- in double on the device (msc_score_joint): one
+  // launch and one copy of eight bytes, where the float virtuals above round every term to float, download every slot
+  // and add on the host.  Every group the partition holds counts, empty ones included, as in score_likelihood.
+  double score_joint() const {
+    sync();
+    mixture_state *self = const_cast<mixture_state *>(this);
+    self->push_params(true);
+    partition_slots slots(*self);
+    double *out_dev = nullptr;
+    check(msc_device_alloc(ctx_, 8 * (hypers_.size() + 3), reinterpret_cast<void **>(&out_dev)));
+    double total = 0.0;
+    int rc = msc_score_joint(st_, nullptr, 0, slots.p, out_dev);
+    if (rc == MSC_OK) rc = msc_device_download(ctx_, &total, out_dev, 8);
+    msc_device_free(ctx_, out_dev);
+    check(rc);
+    return total;
+  }
 
   // ---- the supply of empty groups ----
   size_t create_group(common::rng_t &rng) override {

@@ -922,6 +922,59 @@ int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords, uint32_t 
                         uint64_t ld_slots, const uint64_t *host_seeds, uint64_t sweep, float *values_host,
                         uint32_t *evals_host);
 
+/* ---- the log joint log p(X, z | hp, alpha) of a state and of every chain; the best sample kept on the device ---- */
+/*
+ * What the reference's users plot to judge burn-in and rank samples by (score_assignment + the sum of score_likelihood,
+ * entity_state.hpp:76-83), in double on the device.  A state's score is a row of nfeatures + 3 doubles, F = nfeatures:
+ *   [0]      the total (((a + d_0) + d_1) + ... + d_{F-1}) + p, added in double in that written order
+ *   [1]      a = score_assignment(alpha) = occ ln alpha + sum lgamma(n_k) + lgamma(alpha) - lgamma(N + alpha) of the device
+ *            group counts, as msc_hp_grid_score's CRP grid and the slice step's alpha target write it
+ *   [2 + f]  d_f = the sum over the counted slots k of score_data(hp_f, group k), the sum a slice target of feature f
+ *            evaluates (counted: a non-zero group count, or with slots_dev a non-zero byte; no other slot is read)
+ *   [2 + F]  p = the sum over the n entries of coords, in entry order from 0, of the entry's prior (MSC_PRIOR_*, as
+ *            msc_hp_slice defines them) at the coordinate's CURRENT value (alpha, or a float of the device hp block;
+ *            NONINF_BETA with its partner's current value); width is checked and not used; 0 when n == 0
+ * The parts are kept apart so that a caller can plot the assignment term and the features' terms separately; adding
+ * them up in the written order in double gives the bits of [0].
+ * The order of the sums (one workgroup of 256 threads a state): a -- thread t adds lgamma(n_k), n_k and the occupied
+ * slots over k = t, t + 256, ... ascending, the 256 partials fold in a tree (t += t + w, w = 128, ..., 1); d_f -- thread t
+ * adds its counted slots k = t, t + 256, ... ascending, a wave of 64 folds by xor butterflies (32, ..., 1), the four waves
+ * are added (w0 + w1) + (w2 + w3); p -- one thread.  No atomics: the order depends on ngroups and nothing else, a call
+ * repeats its bits, and row c of msc_chains_score_joint equals msc_score_joint on member c bit for bit, whatever the
+ * number of chains in the launch (one kernel body serves both calls).
+ * noop contributes 0; bb, bbnc, bnb, gp, dd, dm and nich are supported (an ensemble holds neither bbnc nor dm).  bnb's
+ * score_data is the marginal up to the data-only term sum_i log C(r + v_i - 1, v_i), as everywhere in this library (its
+ * statistics cannot carry it): the same for every assignment, so traces, differences and ranks are unaffected.
+ * MSC_EUNSUPPORTED for a state with a niw feature: the double evaluator these sums run through (the slice targets' and
+ * the hp grids') has no niw.
+ * Both calls are asynchronous on the context's stream and change nothing in any state: a sweep after a call gives the
+ * bits it gives without it (the reference fields are made current first, as every call that reads them does).
+ * msc_score_joint copies nothing: the entries travel as kernel arguments, 64 a launch.  msc_chains_score_joint uploads
+ * one table (per-chain pointers and alpha) through a device buffer the handle owns, which only grows, after a wait for
+ * the stream (once), out of the pinned areas msc_chains_sweep stages its table through; no other wait.
+ *   coords, n     nullable with n == 0; else msc_hp_slice's entries and checks, made once before anything is launched;
+ *   slots_dev     nullable; as msc_hp_slice / msc_chains_hp_slice (ld_slots == 0: one mask for all chains);
+ *   out_dev       double[nfeatures + 3]; the chains' call: chain c's row at out_dev + c * ld_out, ld_out >= nfeatures + 3.
+ * Errors, with nothing launched and nothing written: MSC_EINVAL for a null output, a null coords with n > 0, ld_out <
+ * nfeatures + 3, ld_slots neither 0 nor >= ngroups, whatever msc_hp_slice refuses of an entry, or a state (a member:
+ * the index is named) between msc_sweep_step_begin and msc_state_commit_reduce; MSC_EUNSUPPORTED for niw, and for an
+ * entry msc_hp_slice does not slice; MSC_EDEVICE when an earlier kernel reported an error.
+ */
+int msc_score_joint(msc_state *st, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev, double *out_dev);
+int msc_chains_score_joint(msc_chains *ch, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
+                           uint64_t ld_slots, double *out_dev, uint64_t ld_out);       /* ld_out >= nfeatures + 3 */
+/*
+ * The best sample of every chain so far, kept on the device: for every chain c with joint_dev[c * ld_joint] >
+ * best_dev[c] -- strictly: a tie keeps the earlier sample, and a NaN never wins -- the chain's row z_dev + c * ld_z
+ * (nrows int32) is copied over best_z_dev + c * ld_best, best_dev[c] takes the total and best_iter_dev[c] takes iter.
+ * Start best_dev at -inf and best_iter_dev at -1.  A chain has one workgroup, which compares before it writes.
+ * Asynchronous, no wait; no state is read or changed.  MSC_EINVAL (nothing launched) for a null argument, ld_joint < 1,
+ * ld_z or ld_best < nrows, or an iter beyond int64; MSC_EDEVICE when an earlier kernel reported an error.
+ */
+int msc_chains_keep_best(msc_chains *ch, const double *joint_dev, uint64_t ld_joint, const int32_t *z_dev, uint64_t ld_z,
+                         uint64_t nrows, uint64_t iter, double *best_dev, int32_t *best_z_dev, uint64_t ld_best,
+                         int64_t *best_iter_dev);
+
 /* ---- posterior predictive sampling (group::sample_value, base.hpp:29) ---- */
 #define MSC_PRED_MASKED_ONLY 0x1u /* draw masked entries only; observed ones are copied */
 /*
