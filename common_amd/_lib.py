@@ -147,6 +147,11 @@ _SIGS = {
     "msc_chains_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                    C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64,
                                    C.c_uint32, C.c_void_p, C.c_void_p]),
+    # (ch, joint_dev, ld_joint, nrungs, beta_dev, rung_dev, parity, seed, sweep, proposed_dev, accepted_dev)
+    "msc_chains_exchange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    # (ch, joint_dev, ld_joint, beta_from_dev, beta_to_dev, logw_dev)
+    "msc_chains_anneal_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     # (ch, view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, pos0, npos, host_seeds, sweep, logw_dev,
     #  visit_logp_dev, ld_logp)
     "msc_chains_visit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,

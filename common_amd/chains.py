@@ -305,6 +305,46 @@ class ChainEnsemble(object):
         L.check(self.ctx.lib.msc_chains_score_joint(self._h, arr, n, sp, ld_slots, op, ld))
         return out
 
+    # tempered chains: the steps between sweeps -----------------------------------------
+    def exchange(self, joint, beta, rung, nrungs, parity, seed, sweep, counters):
+        """one replica-exchange step of every ladder of nrungs chains (msc_chains_exchange; asynchronous, one launch, no
+        state is read or changed).  joint: score_joint()'s rows, float64 device [nchains, nfeatures + 3]; beta float32 and
+        rung int32 device tensors [nchains] -- within ladder l, chains [l nrungs, (l + 1) nrungs), rung is a permutation of
+        0 .. nrungs - 1 (tempering.ladder gives the temperatures of the rungs).  For every j < nrungs - 1 with j % 2 ==
+        parity % 2 the chains a, b holding rungs j, j + 1 swap their entries of beta and rung when log u < (beta_a - beta_b)
+        (L_b - L_a), L the data log-likelihood summed from the joint row and u the Philox uniform of (key seed, counter
+        (l nrungs + j, sweep)) -- give it a key no sweep of the chains uses.  The temperatures move, the states stay.
+        counters: (proposed, accepted), int32 device tensors [nchains // nrungs, nrungs - 1], added to.  A ladder whose
+        rungs are no permutation is left alone and raises at the next call."""
+        self._check_open()
+        dev, nrungs = self.ctx.torch_device, int(nrungs)
+        if nrungs < 1 or self.nchains % nrungs:
+            raise ValueError("nchains = %d is no whole number of ladders of %d rungs" % (self.nchains, nrungs))
+        jp, ld = A.matrix(joint, torch.float64, self.nchains, len(self.features) + 3, dev, "joint")
+        bp = A.flat(beta, torch.float32, self.nchains, dev, "beta")
+        rp = A.flat(rung, torch.int32, self.nchains, dev, "rung")
+        proposed, accepted = counters
+        npairs = (self.nchains // nrungs) * (nrungs - 1)
+        pp = A.flat(proposed, _I32_U32, npairs, dev, "counters[0]")
+        ap = A.flat(accepted, _I32_U32, npairs, dev, "counters[1]")
+        seed, sweep, parity = int(seed), int(sweep), int(parity)
+        if not 0 <= seed <= _U64 or not 0 <= sweep <= _U64 or not 0 <= parity <= _U64:
+            raise ValueError("seed, sweep and parity must lie in [0, 2^64)")
+        L.check(self.ctx.lib.msc_chains_exchange(self._h, jp, ld, nrungs, bp, rp, parity, seed, sweep, pp, ap))
+
+    def anneal_weights(self, joint, beta_from, beta_to, logw=None):
+        """logw[c] += (beta_to[c] - beta_from[c]) L_c in double (msc_chains_anneal_weights; asynchronous, one launch): the
+        weight of one step of annealed importance sampling.  joint: score_joint()'s rows; beta_from, beta_to: float32 device
+        tensors [nchains]; logw: a float64 device tensor [nchains] (default ens.logw).  Equal temperatures leave an entry
+        untouched."""
+        self._check_open()
+        dev = self.ctx.torch_device
+        logw = self.logw if logw is None else logw
+        jp, ld = A.matrix(joint, torch.float64, self.nchains, len(self.features) + 3, dev, "joint")
+        L.check(self.ctx.lib.msc_chains_anneal_weights(
+            self._h, jp, ld, A.flat(beta_from, torch.float32, self.nchains, dev, "beta_from"),
+            A.flat(beta_to, torch.float32, self.nchains, dev, "beta_to"), A.flat(logw, torch.float64, self.nchains, dev, "logw")))
+
     # split-merge proposals --------------------------------------------------------
     def split_merge(self, view, seed, sweep=0, nproposals=1, launch_iters=2, want_log=False, want_trace=False,
                     want_proposed=False, row_id0=0):

@@ -104,7 +104,8 @@ int msc::device_error_check(msc_context *ctx) {
   if (code & 32u) add("msc_zmatrix_partition_refine: a start with more than max_clusters clusters (its outputs mean nothing; detail: start of its chunk)");
   if (code & 64u) add("msc_partition_distances: a partition with more than 1024 clusters (every output it takes part in is -1 or NaN; detail: its index in its set)");
   if (code & 128u) add("msc_partition_refine_vi: a sample with more than 1024 clusters or a start with more than max_clusters (its outputs mean nothing; detail: its index)");
-  if (code & ~255u) add("unknown device-side error");
+  if (code & 256u) add("msc_chains_exchange: rungs that are no permutation within a ladder (it was left as it was; detail: ladder)");
+  if (code & ~511u) add("unknown device-side error");
   return fail(MSC_EDEVICE, "reported by an earlier kernel on device %d: %s [detail of the first: %u]; rebuild the affected state's tables",
               ctx->device, what.c_str(), detail);
 }

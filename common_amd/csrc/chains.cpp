@@ -1,5 +1,6 @@
 // chains.cpp -- the sequential collapsed Gibbs sweep and the ensembles of such chains (kernels_seq.hip):
-// msc_sweep_sequential and msc_chains_*, the ensemble's row predictive density (kernels_chains_marginal.hip), its
+// msc_sweep_sequential and msc_chains_*, the exchange of temperatures and the annealing weights (kernels_temper.hip), the
+// ensemble's row predictive density (kernels_chains_marginal.hip), its
 // posterior predictive draws (kernels_chains_pred.hip) and its split-merge proposals (kernels_chains_sm.hip) among them.
 // Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
 #include <algorithm>
@@ -8,6 +9,7 @@
 
 #include "abi_internal.hpp"
 #include "launchers.hpp"
+#include "temper_math.hpp"
 
 using namespace msc;
 
@@ -639,6 +641,50 @@ extern "C" int msc_chains_keep_best(msc_chains *ch, const double *joint_dev, uin
   if (launch_chains_keep_best(ctx->stream, nc, joint_dev, ld_joint, z_dev, ld_z, nrows, (int64_t)iter, best_dev, best_z_dev,
                               ld_best, best_iter_dev))
     return fail(MSC_EHIP, "k_chains_keep_best launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return MSC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Between the sweeps of a tempered ensemble (kernels_temper.hip; the arithmetic and the checks: temper_math.hpp): the
+// exchange of temperatures between neighbouring rungs of every ladder, and the weights of an annealing step.  Neither
+// reads or changes a state, uploads a table or waits: one launch each on the arrays the caller holds.
+// ---------------------------------------------------------------------------
+extern "C" int msc_chains_exchange(msc_chains *ch, const double *joint_dev, uint64_t ld_joint, uint32_t nrungs, float *beta_dev,
+                                   int32_t *rung_dev, uint64_t parity, uint64_t seed, uint64_t sweep, uint32_t *proposed_dev,
+                                   uint32_t *accepted_dev) {
+  MSC_REQUIRE(ch, "null argument");
+  const uint32_t nc = (uint32_t)ch->states.size();
+  const uint32_t nfeat = nc ? ch->states[0]->nfeat : 0;
+  const joint::JointCheck chk = temper::check_exchange("msc_chains_exchange", joint_dev && beta_dev && rung_dev && proposed_dev &&
+                                                       accepted_dev, nrungs, nc, ld_joint, nfeat);
+  MSC_REQUIRE(chk.ok, "%s", chk.message);
+  if (nc == 0) return MSC_OK;
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  // the kernel reports a broken ladder into the context's error word, whose device address travels as an argument
+  void *err_dev = nullptr;
+  MSC_HIP(hipHostGetDevicePointer(&err_dev, const_cast<uint32_t *>(ctx->err_host), 0));
+  if (launch_chains_exchange(ctx->stream, nc, nfeat, joint_dev, ld_joint, nrungs, beta_dev, rung_dev, parity, seed, sweep,
+                             proposed_dev, accepted_dev, static_cast<uint32_t *>(err_dev)))
+    return fail(MSC_EHIP, "k_chains_exchange launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return MSC_OK;
+}
+
+extern "C" int msc_chains_anneal_weights(msc_chains *ch, const double *joint_dev, uint64_t ld_joint, const float *beta_from_dev,
+                                         const float *beta_to_dev, double *logw_dev) {
+  MSC_REQUIRE(ch, "null argument");
+  const uint32_t nc = (uint32_t)ch->states.size();
+  const uint32_t nfeat = nc ? ch->states[0]->nfeat : 0;
+  const joint::JointCheck chk = temper::check_anneal_weights("msc_chains_anneal_weights", joint_dev && beta_from_dev &&
+                                                             beta_to_dev && logw_dev, ld_joint, nfeat);
+  MSC_REQUIRE(chk.ok, "%s", chk.message);
+  if (nc == 0) return MSC_OK;
+  msc_context *ctx = ch->ctx;
+  MSC_HIP(hipSetDevice(ctx->device));
+  MSC_TRY(device_error_check(ctx));
+  if (launch_chains_anneal_weights(ctx->stream, nc, nfeat, joint_dev, ld_joint, beta_from_dev, beta_to_dev, logw_dev))
+    return fail(MSC_EHIP, "k_chains_anneal_weights launch failed: %s", hipGetErrorString(hipGetLastError()));
   return MSC_OK;
 }
 

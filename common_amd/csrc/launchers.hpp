@@ -323,6 +323,14 @@ int launch_chains_score_joint(hipStream_t stream, const JointChain *chains_dev, 
 int launch_chains_keep_best(hipStream_t stream, uint32_t nchains, const double *joint, uint64_t ld_joint, const int32_t *z,
                             uint64_t ld_z, uint64_t nrows, int64_t iter, double *best, int32_t *best_z, uint64_t ld_best,
                             int64_t *best_iter);
+// kernels_temper.hip (msc_chains_exchange / msc_chains_anneal_weights; the arithmetic: temper_math.hpp): joint is the
+// chains' rows as msc_chains_score_joint wrote them.  exchange: one thread a ladder of nrungs chains; anneal_weights: one
+// thread a chain; err_word_dev: the device address of the context's error word pair (a broken ladder is reported there)
+int launch_chains_exchange(hipStream_t stream, uint32_t nchains, uint32_t nfeat, const double *joint, uint64_t ld_joint,
+                           uint32_t nrungs, float *beta, int32_t *rung, uint64_t parity, uint64_t seed, uint64_t sweep,
+                           uint32_t *proposed, uint32_t *accepted, uint32_t *err_word_dev);
+int launch_chains_anneal_weights(hipStream_t stream, uint32_t nchains, uint32_t nfeat, const double *joint, uint64_t ld_joint,
+                                 const float *beta_from, const float *beta_to, double *logw);
 
 // kernels_pred.hip
 int launch_pred_prepare(hipStream_t stream, const PredFeat *pfs_dev, const std::vector<PredFeat> &pfs, uint32_t K,

@@ -975,6 +975,40 @@ int msc_chains_keep_best(msc_chains *ch, const double *joint_dev, uint64_t ld_jo
                          uint64_t nrows, uint64_t iter, double *best_dev, int32_t *best_z_dev, uint64_t ld_best,
                          int64_t *best_iter_dev);
 
+/* ---- tempered chains: replica exchange between temperatures, and the weights of an annealing step ---- */
+/*
+ * The two steps a tempered ensemble makes BETWEEN its sweeps, chain c targeting pi_beta(z) ~ p(z | alpha) p(X | z, hp)^beta
+ * at its own temperature beta_c.  (The sweep at a temperature is not part of the library yet: DESIGN.md 6v.)
+ * Both calls read the chains' joint rows exactly as msc_chains_score_joint wrote them (chain c's at joint_dev + c *
+ * ld_joint, ld_joint >= nfeatures + 3) and take from them the data log-likelihood
+ *   L_c = ((d_0 + d_1) + ...) + d_{F-1},   the entries [2, 2 + F), added in double in that written order.
+ * Both are asynchronous on the context's stream, wait for nothing, upload nothing and read or change no state.
+ *
+ * msc_chains_exchange: one step of replica exchange.  nchains must be a multiple of nrungs = R; ladder l owns chains [l R,
+ * (l + 1) R).  rung_dev: int32[nchains], the rung each chain holds -- within a ladder a permutation of 0 .. R - 1;
+ * beta_dev: float[nchains], the temperature each chain holds.  For every ladder and
+ * every j < R - 1 with j % 2 == parity % 2, in ascending j, with a and b the chains that hold rungs j and j + 1:
+ *   r = ((double)beta_a - (double)beta_b) * (L_b - L_a);   the swap is accepted when log(u) < r,
+ *   u = the Philox uniform of (key seed, counter (l R + j, sweep)), msc_sweep_assign's generator.
+ * A non-finite r (a NaN likelihood, inf - inf) rejects.  An accepted swap exchanges the two chains' entries of beta_dev
+ * and of rung_dev: the TEMPERATURES move, the states stay where they are, so no table is touched and the sweep that
+ * follows launches nothing before its kernel.  proposed_dev, accepted_dev: uint32[(nchains / R) (R - 1)], entry l (R - 1)
+ * + j counts the pair (j, j + 1) of ladder l; both are ADDED to (the caller zeroes them).  One thread walks a ladder, so
+ * the pairs of a ladder are decided one after another and a call repeats its bits.
+ * Errors: MSC_EINVAL, with nothing launched, for a null argument, nrungs == 0, nchains % nrungs != 0 or ld_joint <
+ * nfeatures + 3; MSC_EDEVICE when an earlier kernel reported an error.  A rung_dev that is no permutation within some
+ * ladder leaves THAT ladder as it was (entries and counters) and surfaces as MSC_EDEVICE at the next call.
+ *
+ * msc_chains_anneal_weights: logw_dev[c] += ((double)beta_to_dev[c] - (double)beta_from_dev[c]) * L_c in double, one
+ * thread per chain -- the weight of a step of annealed importance sampling.  Where beta_to == beta_from the entry is left
+ * untouched (an infinite L_c does not turn it into NaN).  MSC_EINVAL for a null argument or ld_joint < nfeatures + 3.
+ */
+int msc_chains_exchange(msc_chains *ch, const double *joint_dev, uint64_t ld_joint, uint32_t nrungs, float *beta_dev,
+                        int32_t *rung_dev, uint64_t parity, uint64_t seed, uint64_t sweep, uint32_t *proposed_dev,
+                        uint32_t *accepted_dev);
+int msc_chains_anneal_weights(msc_chains *ch, const double *joint_dev, uint64_t ld_joint, const float *beta_from_dev,
+                              const float *beta_to_dev, double *logw_dev);
+
 /* ---- posterior predictive sampling (group::sample_value, base.hpp:29) ---- */
 #define MSC_PRED_MASKED_ONLY 0x1u /* draw masked entries only; observed ones are copied */
 /*
