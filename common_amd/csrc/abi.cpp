@@ -992,7 +992,6 @@ extern "C" int msc_state_destroy(msc_state *st) {
   (void)hipSetDevice(st->ctx->device);
   (void)hipStreamSynchronize(st->ctx->stream);
   if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
-  if (st->pred.upload) (void)hipEventDestroy(st->pred.upload);
   if (st->sm.pair) (void)msc_state_destroy(st->sm.pair);
   delete st;
   return MSC_OK;

@@ -8,6 +8,7 @@
 #include <new>
 
 #include "abi_internal.hpp"
+#include "chains_layout.hpp"
 #include "launchers.hpp"
 #include "temper_math.hpp"
 
@@ -96,65 +97,75 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
 struct msc_chains {
   msc_context *ctx = nullptr;
   std::vector<msc_state *> states;
-  // the per-chain table of a call: filled on the host in one of two pinned areas, taken in turn, and copied to table_dev
-  // on the stream.  uploaded[i] is recorded after the copy out of area i; the host waits for it before it refills area i,
-  // so no pending copy reads an area that is being written.  table_dev itself is ordered by the stream: the copy of
-  // a call queues behind the launches of the call before it.
-  msc::PinnedBuf<msc::SeqChain> stage[2];
-  hipEvent_t uploaded[2] = {nullptr, nullptr};
-  bool pending[2] = {false, false};
-  int next = 0;
-  msc::DevBuf<msc::SeqChain> table_dev;   // [nchains]
-  msc::DevBuf<msc::ClonePair> pairs_dev;  // [nchains]: the pairs of a msc_chains_clone, staged through the same two areas
-  // msc_chains_hp_slice: one device buffer (chains | targets | entries | values | evals | status), grown by
-  // reserve_synced, and the host images of its two halves.  Every way out of that call past the upload waits for the
-  // stream, so no copy is pending when the next call rewrites an image.
-  msc::DevBuf<unsigned char> hp_buf;
-  std::vector<unsigned char> hp_up, hp_down;
-  // msc_chains_score_marginal: the call's table (MargChain [nchains] | MargFeat [nfeat]), staged through the same two
-  // areas (which hold marg_extra entries beyond nchains for the features' part); the normalised log weights and
-  // log(n + alpha) of every chain; the slices' (M, S) pairs, grown without a wait (the buffer it replaces may still be read)
-  msc::DevBuf<unsigned char> marg_tab;
+  // The table of a call, whichever call it is: filled on the host through `upload` and copied to call_tab on the stream.
+  // One device buffer serves every call because every ensemble call enqueues on ctx->stream: a call's copy queues behind
+  // the launches of the call before it, which are the last readers of what it overwrites.  (msc_context_set_stream
+  // between two calls leaves that ordering to the caller, as it does for every buffer of a state.)  Sized at create for
+  // the largest of the layouts that nchains and nfeat fix; msc_chains_hp_slice, whose block follows the call's
+  // coordinates, grows it by reserve_synced.
+  msc::StagedUpload upload;
+  msc::DevBuf<unsigned char> call_tab;
+  // msc_chains_hp_slice: what the call brings back (values | evals | status), grown by reserve_synced, and its host image
+  msc::DevBuf<unsigned char> hp_out;
+  std::vector<unsigned char> hp_down;
+  // msc_chains_score_marginal: the normalised log weights and log(n + alpha) of every chain; the slices' (M, S) pairs,
+  // grown without a wait (the buffer it replaces may still be read)
   msc::DevBuf<double> marg_w;             // [2 nchains]: lw | norm
   msc::DevBuf<double> marg_part;
   // msc_chains_sample_predictive: the chains' rows of a chunk (float [nchains][chunk]) and the chunk's rows' chain and
-  // group (int32 [2][chunk]), grown as marg_part is; the call's output pointers travel behind the MargFeat table
+  // group (int32 [2][chunk]), grown as marg_part is
   msc::DevBuf<float> pred_lf;
   msc::DevBuf<int32_t> pred_cz;
-  // msc_chains_split_merge: the call's table, staged through the same two areas (stage_entries sizes them for it), and
-  // the chains' pair labels, int32 [nchains][nrows], grown by reserve_synced
-  msc::DevBuf<msc::SmChain> sm_tab;       // [nchains]
+  // msc_chains_split_merge: the chains' pair labels, int32 [nchains][nrows], grown by reserve_synced
   msc::DevBuf<int32_t> sm_ell;
-  // msc_chains_score_joint: the call's table, grown by reserve_synced as hp_buf is and staged through the same two areas
-  msc::DevBuf<msc::JointChain> joint_tab; // [nchains]
   msc::Retired retired;
+
+  template <typename T>
+  T *table() const { return reinterpret_cast<T *>(call_tab.get()); }   // call_tab as the table the call uploaded
 };
-static_assert(sizeof(msc::ClonePair) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
-static_assert(sizeof(msc::JointChain) <= sizeof(msc::SeqChain), "a staging area holds nchains entries of either table");
-// bytes behind the MargChain table: the MargFeat table of nfeat features, then as many output pointers; and the entries of
-// a staging area beyond nchains that hold them
-static size_t marg_tail(uint32_t nfeat) { return (size_t)nfeat * (sizeof(msc::MargFeat) + sizeof(void *)); }
-static size_t marg_extra(uint32_t nfeat) { return (marg_tail(nfeat) + 16 + sizeof(msc::SeqChain) - 1) / sizeof(msc::SeqChain); }
-static size_t marg_feat_at(uint32_t nchains) { return ((size_t)nchains * sizeof(msc::MargChain) + 15) & ~(size_t)15; }
-// the SeqChain entries of a staging area: nchains entries of the widest table (SmChain), or the marginal call's tail
-static size_t stage_entries(uint32_t nchains, uint32_t nfeat) {
-  const size_t sm = ((size_t)nchains * sizeof(msc::SmChain) + sizeof(msc::SeqChain) - 1) / sizeof(msc::SeqChain);
-  return std::max(sm, nchains + marg_extra(nfeat));
+
+// the marginal / predictive call's block for nsel selected features
+static layout::MargBlock marg_block(const msc_chains *ch, uint32_t nsel) {
+  return layout::marg_block(ch->states.size(), nsel, ch->states[0]->nfeat, sizeof(MargChain), sizeof(MargFeat),
+                            sizeof(void *));
 }
 
-// the pinned staging area whose turn it is, once no pending copy reads it; chains_staged records the copy out of it
-static int chains_stage(msc_chains *ch, int *area) {
-  const int a = ch->next;
-  ch->next ^= 1;
-  if (ch->pending[a]) MSC_HIP(hipEventSynchronize(ch->uploaded[a]));
-  ch->pending[a] = false;
-  *area = a;
+// How every call on an ensemble begins.  No member mid-step (chains_refuse_mid_step, for a call that checks its own
+// arguments between that and the device); the device, and what an earlier kernel reported; with a view, the view bound
+// to every member; then the members' tables as current as the call's kernels need them.
+static int chains_refuse_mid_step(const msc_chains *ch, const char *who) {
+  for (uint32_t c = 0; c < ch->states.size(); c++)
+    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
+                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
   return MSC_OK;
 }
-static int chains_staged(msc_chains *ch, int area, hipStream_t s) {
-  MSC_HIP(hipEventRecord(ch->uploaded[area], s));
-  ch->pending[area] = true;
+static int chains_device(const msc_chains *ch) {
+  MSC_HIP(hipSetDevice(ch->ctx->device));
+  return device_error_check(ch->ctx);
+}
+enum class ChainsEnsure { none, raw, derived_crp, all_current };
+static int chains_enter(msc_chains *ch, const char *who, ChainsEnsure ensure, const msc_dataview *view = nullptr,
+                        const uint32_t *cols = nullptr, uint64_t row0 = 0, uint64_t nrows = 0) {
+  MSC_TRY(chains_refuse_mid_step(ch, who));
+  MSC_TRY(chains_device(ch));
+  if (view)
+    for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  for (msc_state *st : ch->states) {
+    if (ensure == ChainsEnsure::raw) MSC_TRY(ensure_raw(st));
+    if (ensure == ChainsEnsure::derived_crp) MSC_TRY(ensure_derived(st));
+    if (ensure == ChainsEnsure::derived_crp) MSC_TRY(ensure_crp(st));
+    if (ensure == ChainsEnsure::all_current) MSC_TRY(ensure_all_current(st));
+  }
   return MSC_OK;
+}
+
+// Whole units (row visits, proposals) of every chain that one launch takes: what one chain may take in kSeqLaunchUs at
+// unit_us a unit, kSeqMaxVisitsPerLaunch at most, divided by the rounds the grid runs in -- at these kernels' register
+// counts one workgroup is resident per CU.  At least one: the least a launch can take.
+static uint64_t chains_units_per_launch(const msc_chains *ch, double unit_us) {
+  const uint64_t n = ch->states.size(), cus = (uint64_t)std::max(1, ch->ctx->num_cus);
+  const double one = std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / unit_us));
+  return std::max<uint64_t>(1, (uint64_t)one / ((n + cus - 1) / cus));
 }
 
 extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc_chains **out) {
@@ -184,19 +195,13 @@ extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc
   if (!ch) return fail(MSC_ENOMEM, "out of host memory");
   ch->ctx = ctx;
   ch->states.assign(states, states + nchains);
-  hipError_t e = ch->table_dev.alloc(nchains);
-  if (e == hipSuccess) e = ch->pairs_dev.alloc(nchains);
-  if (e == hipSuccess) e = ch->sm_tab.alloc(nchains);
-  if (e == hipSuccess) e = ch->marg_tab.alloc(marg_feat_at(nchains) + marg_tail(states[0]->nfeat), 16);
+  // the largest table a call uploads but msc_chains_hp_slice's: an entry a chain, or the sampling call's block
+  const size_t entry = std::max({sizeof(SeqChain), sizeof(ClonePair), sizeof(SmChain), sizeof(JointChain)});
+  const size_t tab_bytes = std::max(nchains * entry, marg_block(ch.get(), states[0]->nfeat).bytes);
+  hipError_t e = ch->call_tab.alloc(tab_bytes);
+  if (e == hipSuccess) e = ch->upload.reserve(tab_bytes);
   if (e == hipSuccess) e = ch->marg_w.alloc(2 * (size_t)nchains);
-  for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = ch->stage[i].alloc(stage_entries(nchains, states[0]->nfeat));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ch->uploaded[i], hipEventDisableTiming);
-  }
-  if (e != hipSuccess) {
-    for (hipEvent_t ev : ch->uploaded) if (ev) (void)hipEventDestroy(ev);
-    return fail(MSC_EHIP, "msc_chains_create: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(MSC_EHIP, "msc_chains_create: %s", hipGetErrorString(e));
   for (msc_state *st : ch->states) st->chain_members++;
   *out = ch.release();
   return MSC_OK;
@@ -206,10 +211,6 @@ extern "C" int msc_chains_destroy(msc_chains *ch) {
   if (!ch) return MSC_OK;
   (void)hipSetDevice(ch->ctx->device);
   (void)hipStreamSynchronize(ch->ctx->stream);             // (a launch may still read the table)
-  for (int i = 0; i < 2; i++) {
-    if (ch->pending[i]) (void)hipEventSynchronize(ch->uploaded[i]);
-    if (ch->uploaded[i]) (void)hipEventDestroy(ch->uploaded[i]);
-  }
   for (msc_state *st : ch->states) st->chain_members--;
   delete ch;
   return MSC_OK;
@@ -242,25 +243,15 @@ static int chains_visits_impl(msc_chains *ch, const char *who, const msc_datavie
   MSC_REQUIRE(ld_z >= nrows, "%s: ld_z %llu < nrows %llu", who, (unsigned long long)ld_z, (unsigned long long)nrows);
   MSC_REQUIRE(!order_dev || ld_order == 0 || ld_order >= nrows, "%s: ld_order %llu is neither 0 (one order "
               "for all chains) nor >= nrows %llu", who, (unsigned long long)ld_order, (unsigned long long)nrows);
-  for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  // every table of every member current before visits are made, as msc_sweep_sequential
+  MSC_TRY(chains_enter(ch, who, v0 < v1 ? ChainsEnsure::all_current : ChainsEnsure::none, view, cols, row0, nrows));
   if (v0 >= v1) return MSC_OK;
-  // every table of every member current before, as msc_sweep_sequential
-  hipStream_t s = ctx->stream;
-  double visit_us = 0.0;
-  for (msc_state *st : ch->states) {
-    MSC_TRY(ensure_all_current(st));
-    visit_us = std::max(visit_us, seq_visit_us(st));
-  }
-  // the table of this call (pointers and alpha may have changed since the last one), through the pinned area whose turn it is
-  int a = 0;
-  MSC_TRY(chains_stage(ch, &a));
-  SeqChain *tab = ch->stage[a];
+  hipStream_t s = ch->ctx->stream;
+  double visit_us = 0.0;                                    // (as msc_sweep_sequential, by the costliest member)
+  for (const msc_state *st : ch->states) visit_us = std::max(visit_us, seq_visit_us(st));
+  // the table of this call (pointers and alpha may have changed since the last one)
+  SeqChain *tab = nullptr;
+  MSC_HIP(ch->upload.begin(sizeof(SeqChain) * n, &tab));
   for (uint32_t c = 0; c < n; c++) {
     const msc_state *st = ch->states[c];
     SeqChain &e = tab[c];
@@ -278,18 +269,13 @@ static int chains_visits_impl(msc_chains *ch, const char *who, const msc_datavie
     e.alpha = st->alpha;
     e.pad = 0;
   }
-  MSC_HIP(hipMemcpyAsync(ch->table_dev, tab, sizeof(SeqChain) * n, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, a, s));
-  // a launch's visits: what one chain may take in the launch's time (as msc_sweep_sequential, by the costliest member),
-  // divided by the rounds the grid runs in -- at this kernel's register count one workgroup is resident per CU
+  MSC_HIP(ch->upload.commit(s, ch->call_tab, sizeof(SeqChain) * n));
   const msc_state *st0 = ch->states[0];
-  const double one = std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / visit_us));
-  const uint64_t rounds = (n + (uint32_t)std::max(1, ctx->num_cus) - 1) / (uint32_t)std::max(1, ctx->num_cus);
-  const uint64_t per_launch = std::max<uint64_t>(1, (uint64_t)one / rounds);
+  const uint64_t per_launch = chains_units_per_launch(ch, visit_us);
   for (uint64_t w0 = v0; w0 < v1; w0 += per_launch) {
     const uint64_t w1 = std::min(v1, w0 + per_launch);
-    const int rc = launch_sweep_seq_chains(s, ch->table_dev, n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows, row_id0, w0,
-                                           w1, sweep, out.trace_every);
+    const int rc = launch_sweep_seq_chains(s, ch->table<SeqChain>(), n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows,
+                                           row_id0, w0, w1, sweep, out.trace_every);
     if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq_chains does not take this shape");
     if (rc) return fail(MSC_EHIP, "k_sweep_seq_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
   }
@@ -346,20 +332,15 @@ extern "C" int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, 
                                         "%u): a source must survive in place", c, a, host_ancestors[a]);
     npairs += a != c;
   }
-  for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_clone: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  MSC_TRY(chains_refuse_mid_step(ch, "msc_chains_clone"));
   if (npairs == 0) return MSC_OK;
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  hipStream_t s = ctx->stream;
+  MSC_TRY(chains_enter(ch, "msc_chains_clone", ChainsEnsure::none));
+  hipStream_t s = ch->ctx->stream;
   // a source's additive tables hold the truth before they are read (after a sweep they do: this launches nothing then)
   for (uint32_t c = 0; c < n; c++)
     if (host_ancestors[c] != c) MSC_TRY(ensure_additive(ch->states[host_ancestors[c]]));
-  int area = 0;
-  MSC_TRY(chains_stage(ch, &area));
-  ClonePair *tab = reinterpret_cast<ClonePair *>(ch->stage[area].get());
+  ClonePair *tab = nullptr;
+  MSC_HIP(ch->upload.begin(sizeof(ClonePair) * npairs, &tab));
   const msc_state *st0 = ch->states[0];
   uint32_t p = 0;
   for (uint32_t c = 0; c < n; c++) {
@@ -375,9 +356,8 @@ extern "C" int msc_chains_clone(msc_chains *ch, const uint32_t *host_ancestors, 
     e.src_z = z_dev + (size_t)a * ld_z;
     e.dst_z = z_dev + (size_t)c * ld_z;
   }
-  MSC_HIP(hipMemcpyAsync(ch->pairs_dev, tab, sizeof(ClonePair) * npairs, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, area, s));
-  if (launch_chains_clone(s, ch->pairs_dev, npairs, st0->n_i64, st0->n_f64, nrows))
+  MSC_HIP(ch->upload.commit(s, ch->call_tab, sizeof(ClonePair) * npairs));
+  if (launch_chains_clone(s, ch->table<ClonePair>(), npairs, st0->n_i64, st0->n_f64, nrows))
     return fail(MSC_EHIP, "k_chains_clone launch failed: %s", hipGetErrorString(hipGetLastError()));
   // a destination's additive tables were replaced as a whole and alone hold its truth now, as after an accumulate that
   // has not committed: the fields, the score constants and the CRP terms are rebuilt from them by the next call's ensure
@@ -422,16 +402,13 @@ extern "C" int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, 
   MSC_REQUIRE(nrows < (1ull << 32), "msc_chains_split_merge takes at most 2^32 - 1 rows");
   MSC_REQUIRE(ld_z >= nrows, "msc_chains_split_merge: ld_z %llu < nrows %llu", (unsigned long long)ld_z,
               (unsigned long long)nrows);
-  for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_split_merge: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  MSC_TRY(chains_refuse_mid_step(ch, "msc_chains_split_merge"));
   const msc_state *st0 = ch->states[0];
   MSC_TRY(sm_chain_route(st0));                             // (equal feature lists: one answer for all)
   // a launch takes the whole proposals that fit the sweep's launch budget, by the estimate above times the rounds the grid
   // runs in (one workgroup a compute unit is what the estimate was measured at).  What is refused is a proposal that
   // alone exceeds the budget in ONE round: with more chains than compute units a launch of one proposal -- the least a
   // launch can take -- runs `rounds` such rounds, as msc_chains_sweep's launch of one visit does.
-  msc_context *ctx = ch->ctx;
   const double one_us = sm_proposal_us(nrows, st0->nfeat, launch_iters);
   if (one_us > kSeqLaunchUs)
     return fail(MSC_EUNSUPPORTED, "msc_chains_split_merge: one proposal over %llu rows x %u features at launch_iters %u is "
@@ -439,16 +416,12 @@ extern "C" int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, 
                 "msc_split_merge (State.split_merge) on each member has the row-parallel kernels for large tables",
                 (unsigned long long)nrows, st0->nfeat, launch_iters, one_us, kSeqLaunchUs);
   if (nproposals == 0) return MSC_OK;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  hipStream_t s = ctx->stream;
-  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, 0, nrows));
   // every table of every member current before, as msc_chains_sweep
-  for (msc_state *st : ch->states) MSC_TRY(ensure_all_current(st));
+  MSC_TRY(chains_enter(ch, "msc_chains_split_merge", ChainsEnsure::all_current, view, cols, 0, nrows));
+  hipStream_t s = ch->ctx->stream;
   MSC_HIP(reserve_synced(s, ch->sm_ell, (size_t)n * std::max<uint64_t>(nrows, 1)));
-  int a = 0;
-  MSC_TRY(chains_stage(ch, &a));
-  SmChain *tab = reinterpret_cast<SmChain *>(ch->stage[a].get());
+  SmChain *tab = nullptr;
+  MSC_HIP(ch->upload.begin(sizeof(SmChain) * n, &tab));
   for (uint32_t c = 0; c < n; c++) {
     msc_state *st = ch->states[c];
     SmChain &e = tab[c];
@@ -467,16 +440,13 @@ extern "C" int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, 
     e.alpha = st->alpha;
     e.pad = 0;
   }
-  MSC_HIP(hipMemcpyAsync(ch->sm_tab, tab, sizeof(SmChain) * n, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, a, s));
-  const uint32_t cus = (uint32_t)std::max(1, ctx->num_cus);
-  const double rounds = (double)((n + cus - 1) / cus);
-  const uint32_t per_launch = (uint32_t)std::max(1.0, std::min((double)nproposals, kSeqLaunchUs / (one_us * rounds)));
+  MSC_HIP(ch->upload.commit(s, ch->call_tab, sizeof(SmChain) * n));
+  const uint32_t per_launch = (uint32_t)std::min<uint64_t>(nproposals, chains_units_per_launch(ch, one_us));
   const uint32_t pair_kpad = st0->sm.pair->kpad;
   for (uint32_t p0 = 0; p0 < nproposals; p0 += per_launch) {
     const uint32_t p1 = std::min(nproposals, p0 + per_launch);
-    const int rc = launch_sm_chains(s, ch->sm_tab, n, (int)st0->nfeat, st0->K, st0->kpad, pair_kpad, nrows, row_id0, p0, p1,
-                                    launch_iters, sweep);
+    const int rc = launch_sm_chains(s, ch->table<SmChain>(), n, (int)st0->nfeat, st0->K, st0->kpad, pair_kpad, nrows, row_id0,
+                                    p0, p1, launch_iters, sweep);
     if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sm_chains does not take this shape");
     if (rc) return fail(MSC_EHIP, "k_sm_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
   }
@@ -494,8 +464,6 @@ extern "C" int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, 
 // The slice step of every chain in one launch (k_hp_slice_chains), and the rebuild of what it made stale in another
 // (k_chains_prepare): msc_hp_slice on every member, with one host synchronisation for the call.
 // ---------------------------------------------------------------------------
-static size_t hp_align(size_t n) { return (n + 15) & ~(size_t)15; }
-
 extern "C" int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
                                    uint64_t ld_slots, const uint64_t *host_seeds, uint64_t sweep, float *values_host,
                                    uint32_t *evals_host) {
@@ -506,31 +474,23 @@ extern "C" int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords
   const msc_state *st0 = ch->states[0];
   MSC_REQUIRE(!slots_dev || ld_slots == 0 || ld_slots >= st0->K, "msc_chains_hp_slice: ld_slots %llu is neither 0 (one mask "
               "for all chains) nor >= ngroups %u", (unsigned long long)ld_slots, st0->K);
-  for (uint32_t c = 0; c < nc; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_hp_slice: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  MSC_TRY(chains_refuse_mid_step(ch, "msc_chains_hp_slice"));
   // msc_hp_slice's argument checks, once: the members' feature lists are equal (msc_chains_create)
   SlicePlan plan;
   MSC_TRY(slice_plan(st0, coords, n, plan));
   const uint32_t nt = plan.ntargets();
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  uint32_t slices = 1;
-  for (msc_state *st : ch->states) {
-    MSC_TRY(ensure_raw(st));
-    slices = std::max(slices, prepare_value_slices(st));   // (the count moves no bit: prepare_group deals whole rows out)
-  }
-  // one buffer: chains | targets [nchains][nt] | entries | values | evals | status, the last three [nchains][n]
-  const size_t cells = (size_t)nc * n;
-  const size_t o_tgt = hp_align(nc * sizeof(HpChain)), o_coord = o_tgt + hp_align((size_t)nc * nt * sizeof(SliceTarget));
-  const size_t o_val = o_coord + hp_align(n * sizeof(SliceCoord)), o_ev = o_val + hp_align(cells * 4);
-  const size_t o_stat = o_ev + hp_align(cells * 4), total = o_stat + hp_align(cells * 4);
-  hipStream_t s = ctx->stream;
-  MSC_HIP(reserve_synced(s, ch->hp_buf, total));
-  ch->hp_up.assign(o_val, 0);
-  HpChain *hc = reinterpret_cast<HpChain *>(ch->hp_up.data());
-  SliceTarget *tg = reinterpret_cast<SliceTarget *>(ch->hp_up.data() + o_tgt);
+  MSC_TRY(chains_enter(ch, "msc_chains_hp_slice", ChainsEnsure::raw));
+  uint32_t slices = 1;                                // (the count moves no bit: prepare_group deals whole rows out)
+  for (const msc_state *st : ch->states) slices = std::max(slices, prepare_value_slices(st));
+  // up, through the call table: chains | targets [nchains][nt] | entries; down: values | evals | status, [nchains][n] each
+  const layout::HpBlocks lay = layout::hp_blocks(nc, nt, n, sizeof(HpChain), sizeof(SliceTarget), sizeof(SliceCoord));
+  hipStream_t s = ch->ctx->stream;
+  MSC_HIP(reserve_synced(s, ch->call_tab, lay.up_bytes));
+  MSC_HIP(reserve_synced(s, ch->hp_out, lay.down_bytes));
+  unsigned char *up = nullptr;
+  MSC_HIP(ch->upload.begin(lay.up_bytes, &up));
+  HpChain *hc = reinterpret_cast<HpChain *>(up + lay.chains);
+  SliceTarget *tg = reinterpret_cast<SliceTarget *>(up + lay.targets);
   for (uint32_t c = 0; c < nc; c++) {
     const msc_state *st = ch->states[c];
     HpChain &e = hc[c];
@@ -543,28 +503,24 @@ extern "C" int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords
     e.pad = 0;
     slice_targets(st, plan, tg + (size_t)c * nt);
   }
-  std::memcpy(ch->hp_up.data() + o_coord, plan.dc.data(), n * sizeof(SliceCoord));
-  unsigned char *b = ch->hp_buf;
-  MSC_HIP(hipMemcpyAsync(b, ch->hp_up.data(), o_val, hipMemcpyHostToDevice, s));
-  ch->hp_down.assign(total - o_val, 0);
-  int rc = MSC_OK;
-  if (launch_hp_slice_chains(s, reinterpret_cast<const SliceTarget *>(b + o_tgt), nt, reinterpret_cast<HpChain *>(b), nc,
-                             reinterpret_cast<const SliceCoord *>(b + o_coord), n, st0->K, st0->kpad, sweep,
-                             reinterpret_cast<float *>(b + o_val), reinterpret_cast<uint32_t *>(b + o_ev),
-                             reinterpret_cast<uint32_t *>(b + o_stat)))
-    rc = fail(MSC_EHIP, "k_hp_slice_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
+  std::memcpy(up + lay.coords, plan.dc.data(), n * sizeof(SliceCoord));
+  MSC_HIP(ch->upload.commit(s, ch->call_tab, lay.up_bytes));
+  unsigned char *b = ch->call_tab, *o = ch->hp_out;
+  if (launch_hp_slice_chains(s, reinterpret_cast<const SliceTarget *>(b + lay.targets), nt,
+                             reinterpret_cast<HpChain *>(b + lay.chains), nc, reinterpret_cast<const SliceCoord *>(b + lay.coords),
+                             n, st0->K, st0->kpad, sweep, reinterpret_cast<float *>(o + lay.values),
+                             reinterpret_cast<uint32_t *>(o + lay.evals), reinterpret_cast<uint32_t *>(o + lay.status)))
+    return fail(MSC_EHIP, "k_hp_slice_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
   // every chain's score tables from its new hp blocks, its CRP table from its new alpha (which the step left in its entry)
-  else if (launch_chains_prepare(s, reinterpret_cast<const HpChain *>(b), nc, st0->nfeat, st0->K, st0->kpad, slices))
-    rc = fail(MSC_EHIP, "k_chains_prepare launch failed: %s", hipGetErrorString(hipGetLastError()));
-  if (rc != MSC_OK) {
-    (void)hipStreamSynchronize(s);                    // (the upload may still read hp_up)
-    return rc;
-  }
-  MSC_HIP(hipMemcpyAsync(ch->hp_down.data(), b + o_val, total - o_val, hipMemcpyDeviceToHost, s));
+  if (launch_chains_prepare(s, reinterpret_cast<const HpChain *>(b + lay.chains), nc, st0->nfeat, st0->K, st0->kpad, slices))
+    return fail(MSC_EHIP, "k_chains_prepare launch failed: %s", hipGetErrorString(hipGetLastError()));
+  ch->hp_down.resize(lay.down_bytes);
+  MSC_HIP(hipMemcpyAsync(ch->hp_down.data(), o, lay.down_bytes, hipMemcpyDeviceToHost, s));
   MSC_HIP(hipStreamSynchronize(s));                   // the call's one wait
-  const float *val = reinterpret_cast<const float *>(ch->hp_down.data());
-  const uint32_t *ev = reinterpret_cast<const uint32_t *>(ch->hp_down.data() + (o_ev - o_val));
-  const uint32_t *stat = reinterpret_cast<const uint32_t *>(ch->hp_down.data() + (o_stat - o_val));
+  const float *val = reinterpret_cast<const float *>(ch->hp_down.data() + lay.values);
+  const uint32_t *ev = reinterpret_cast<const uint32_t *>(ch->hp_down.data() + lay.evals);
+  const uint32_t *stat = reinterpret_cast<const uint32_t *>(ch->hp_down.data() + lay.status);
+  int rc = MSC_OK;
   // per member what msc_hp_slice's bookkeeping reports (hp_changed / alpha_changed for what moved), then what the second
   // launch rebuilt.  The first chain with a target that was not finite names the call's error.
   for (uint32_t c = nc; c-- > 0;) {
@@ -581,7 +537,7 @@ extern "C" int msc_chains_hp_slice(msc_chains *ch, const msc_slice_coord *coords
 
 // ---------------------------------------------------------------------------
 // The log joint of every chain in one launch (k_chains_score_joint), and the best sample of every chain kept on the
-// device (k_chains_keep_best).  Neither waits for the stream (but to grow the table once) nor changes a state.
+// device (k_chains_keep_best).  Neither waits for the stream nor changes a state.
 // ---------------------------------------------------------------------------
 extern "C" int msc_chains_score_joint(msc_chains *ch, const msc_slice_coord *coords, uint32_t n, const uint8_t *slots_dev,
                                       uint64_t ld_slots, double *out_dev, uint64_t ld_out) {
@@ -592,21 +548,14 @@ extern "C" int msc_chains_score_joint(msc_chains *ch, const msc_slice_coord *coo
   const joint::JointCheck chk = joint::check_score_joint("msc_chains_score_joint", out_dev != nullptr, coords != nullptr, n,
                                                          st0->nfeat, ld_out, slots_dev != nullptr, ld_slots, st0->K);
   MSC_REQUIRE(chk.ok, "%s", chk.message);
-  for (uint32_t c = 0; c < nc; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "msc_chains_score_joint: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", c);
+  MSC_TRY(chains_refuse_mid_step(ch, "msc_chains_score_joint"));
   // the checks of the features and of the entries, once: the members' feature lists are equal (msc_chains_create)
   std::vector<JointCoord> entries;
   MSC_TRY(joint_entries(st0, "msc_chains_score_joint", coords, n, entries));
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  for (msc_state *st : ch->states) MSC_TRY(ensure_raw(st));
-  hipStream_t s = ctx->stream;
-  MSC_HIP(reserve_synced(s, ch->joint_tab, nc));
-  int a = 0;
-  MSC_TRY(chains_stage(ch, &a));
-  JointChain *tab = reinterpret_cast<JointChain *>(ch->stage[a].get());
+  MSC_TRY(chains_enter(ch, "msc_chains_score_joint", ChainsEnsure::raw));
+  hipStream_t s = ch->ctx->stream;
+  JointChain *tab = nullptr;
+  MSC_HIP(ch->upload.begin(sizeof(JointChain) * nc, &tab));
   for (uint32_t c = 0; c < nc; c++) {
     const msc_state *st = ch->states[c];
     JointChain &e = tab[c];
@@ -617,9 +566,8 @@ extern "C" int msc_chains_score_joint(msc_chains *ch, const msc_slice_coord *coo
     e.alpha = st->alpha;
     e.pad = 0;
   }
-  MSC_HIP(hipMemcpyAsync(ch->joint_tab, tab, sizeof(JointChain) * nc, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, a, s));
-  if (launch_chains_score_joint(s, ch->joint_tab, nc, st0->nfeat, st0->K, st0->kpad, entries.data(), n))
+  MSC_HIP(ch->upload.commit(s, ch->call_tab, sizeof(JointChain) * nc));
+  if (launch_chains_score_joint(s, ch->table<JointChain>(), nc, st0->nfeat, st0->K, st0->kpad, entries.data(), n))
     return fail(MSC_EHIP, "k_chains_score_joint launch failed: %s", hipGetErrorString(hipGetLastError()));
   return MSC_OK;
 }
@@ -635,11 +583,9 @@ extern "C" int msc_chains_keep_best(msc_chains *ch, const double *joint_dev, uin
               (unsigned long long)iter);
   const uint32_t nc = (uint32_t)ch->states.size();
   if (nc == 0) return MSC_OK;
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  if (launch_chains_keep_best(ctx->stream, nc, joint_dev, ld_joint, z_dev, ld_z, nrows, (int64_t)iter, best_dev, best_z_dev,
-                              ld_best, best_iter_dev))
+  MSC_TRY(chains_device(ch));
+  if (launch_chains_keep_best(ch->ctx->stream, nc, joint_dev, ld_joint, z_dev, ld_z, nrows, (int64_t)iter, best_dev,
+                              best_z_dev, ld_best, best_iter_dev))
     return fail(MSC_EHIP, "k_chains_keep_best launch failed: %s", hipGetErrorString(hipGetLastError()));
   return MSC_OK;
 }
@@ -659,13 +605,11 @@ extern "C" int msc_chains_exchange(msc_chains *ch, const double *joint_dev, uint
                                                        accepted_dev, nrungs, nc, ld_joint, nfeat);
   MSC_REQUIRE(chk.ok, "%s", chk.message);
   if (nc == 0) return MSC_OK;
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
+  MSC_TRY(chains_device(ch));
   // the kernel reports a broken ladder into the context's error word, whose device address travels as an argument
   void *err_dev = nullptr;
-  MSC_HIP(hipHostGetDevicePointer(&err_dev, const_cast<uint32_t *>(ctx->err_host), 0));
-  if (launch_chains_exchange(ctx->stream, nc, nfeat, joint_dev, ld_joint, nrungs, beta_dev, rung_dev, parity, seed, sweep,
+  MSC_HIP(hipHostGetDevicePointer(&err_dev, const_cast<uint32_t *>(ch->ctx->err_host), 0));
+  if (launch_chains_exchange(ch->ctx->stream, nc, nfeat, joint_dev, ld_joint, nrungs, beta_dev, rung_dev, parity, seed, sweep,
                              proposed_dev, accepted_dev, static_cast<uint32_t *>(err_dev)))
     return fail(MSC_EHIP, "k_chains_exchange launch failed: %s", hipGetErrorString(hipGetLastError()));
   return MSC_OK;
@@ -680,10 +624,8 @@ extern "C" int msc_chains_anneal_weights(msc_chains *ch, const double *joint_dev
                                                              beta_to_dev && logw_dev, ld_joint, nfeat);
   MSC_REQUIRE(chk.ok, "%s", chk.message);
   if (nc == 0) return MSC_OK;
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  if (launch_chains_anneal_weights(ctx->stream, nc, nfeat, joint_dev, ld_joint, beta_from_dev, beta_to_dev, logw_dev))
+  MSC_TRY(chains_device(ch));
+  if (launch_chains_anneal_weights(ch->ctx->stream, nc, nfeat, joint_dev, ld_joint, beta_from_dev, beta_to_dev, logw_dev))
     return fail(MSC_EHIP, "k_chains_anneal_weights launch failed: %s", hipGetErrorString(hipGetLastError()));
   return MSC_OK;
 }
@@ -710,13 +652,8 @@ static int chains_marginal_begin(msc_chains *ch, const char *who, const msc_data
                                  uint64_t nrows) {
   const uint32_t n = (uint32_t)ch->states.size();
   const msc_state *st0 = ch->states[0];
-  for (uint32_t c = 0; c < n; c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
-  msc_context *ctx = ch->ctx;
-  MSC_HIP(hipSetDevice(ctx->device));
-  MSC_TRY(device_error_check(ctx));
-  for (msc_state *st : ch->states) MSC_TRY(bind_view(st, view, cols, row0, nrows));
+  // where rows are scored, every member's score tables and CRP terms current, as msc_score_marginal
+  MSC_TRY(chains_enter(ch, who, nrows ? ChainsEnsure::derived_crp : ChainsEnsure::none, view, cols, row0, nrows));
   // one tile plan serves every chain, so every member's exact count tables must have member 0's rows: they follow from
   // the view's column maxima and the member's own column bounds (msc_state_set_col_bounds), which may differ
   for (uint32_t c = 1; c < n; c++)
@@ -739,27 +676,22 @@ struct MargCall {
   uint32_t nsel = 0;
   double *lw = nullptr, *norm = nullptr;
 };
-// Every member's score tables and CRP terms current, as msc_score_marginal; then the table of this call through the
-// pinned area whose turn it is -- the chains (chain c's row of chain_logp at logp + c * ld_logp), the selected features'
-// tile plan (from member 0's bound descriptors: families and dims are equal by msc_chains_create, the count columns'
-// table sizes were compared by chains_marginal_begin), the output pointers of a sampling call -- and
+// The table of this call through the call table -- the chains (chain c's row of chain_logp at logp + c * ld_logp), the
+// selected features' tile plan (from member 0's bound descriptors: families and dims are equal by msc_chains_create, the
+// count columns' table sizes were compared by chains_marginal_begin), the output pointers of a sampling call -- and
 // k_chains_marginal_prep's launch.
 static int chains_marginal_stage(msc_chains *ch, const uint32_t *features, uint32_t nfeatures, const double *logw_dev,
                                  float *logp, uint64_t ld_logp, void *const *outs, MargCall &call) {
   const uint32_t n = (uint32_t)ch->states.size();
   const msc_state *st0 = ch->states[0];
   const bool all = features == nullptr || nfeatures == 0;
-  for (msc_state *st : ch->states) {
-    MSC_TRY(ensure_derived(st));
-    MSC_TRY(ensure_crp(st));
-  }
   hipStream_t s = ch->ctx->stream;
   const uint32_t nsel = all ? st0->nfeat : nfeatures;
-  int a = 0;
-  MSC_TRY(chains_stage(ch, &a));
-  unsigned char *area = reinterpret_cast<unsigned char *>(ch->stage[a].get());
-  MargChain *tab = reinterpret_cast<MargChain *>(area);
-  MargFeat *pf = reinterpret_cast<MargFeat *>(area + marg_feat_at(n));
+  const layout::MargBlock blk = marg_block(ch, nsel);
+  unsigned char *area = nullptr;
+  MSC_HIP(ch->upload.begin(blk.bytes, &area));
+  MargChain *tab = reinterpret_cast<MargChain *>(area + blk.chains);
+  MargFeat *pf = reinterpret_cast<MargFeat *>(area + blk.feats);
   for (uint32_t c = 0; c < n; c++) {
     const msc_state *st = ch->states[c];
     MargChain &e = tab[c];
@@ -774,17 +706,14 @@ static int chains_marginal_stage(msc_chains *ch, const uint32_t *features, uint3
   for (uint32_t i = 0; i < nsel; i++) sel[i] = all ? i : features[i];
   call.plan = plan_chains_marginal(st0->desc_host.data(), sel.data(), nsel, st0->K, pf);
   call.nsel = nsel;
-  size_t bytes = marg_feat_at(n) + (size_t)nsel * sizeof(MargFeat);
-  unsigned char *dev = ch->marg_tab;
+  unsigned char *dev = ch->call_tab;
   if (outs != nullptr) {
-    std::memcpy(area + bytes, outs, (size_t)st0->nfeat * sizeof(void *));
-    call.outs_dev = reinterpret_cast<void *const *>(dev + bytes);
-    bytes += (size_t)st0->nfeat * sizeof(void *);
+    std::memcpy(area + blk.outs, outs, (size_t)st0->nfeat * sizeof(void *));
+    call.outs_dev = reinterpret_cast<void *const *>(dev + blk.outs);
   }
-  MSC_HIP(hipMemcpyAsync(dev, area, bytes, hipMemcpyHostToDevice, s));
-  MSC_TRY(chains_staged(ch, a, s));
-  call.chains_dev = reinterpret_cast<const MargChain *>(dev);
-  call.plan_dev = reinterpret_cast<const MargFeat *>(dev + marg_feat_at(n));
+  MSC_HIP(ch->upload.commit(s, dev, outs ? blk.bytes : blk.outs));
+  call.chains_dev = reinterpret_cast<const MargChain *>(dev + blk.chains);
+  call.plan_dev = reinterpret_cast<const MargFeat *>(dev + blk.feats);
   call.lw = ch->marg_w;
   call.norm = call.lw + n;
   return launch_chains_marginal_prep(s, call.chains_dev, n, st0->K, logw_dev, call.lw, call.norm);

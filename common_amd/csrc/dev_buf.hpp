@@ -1,5 +1,5 @@
-// dev_buf.hpp -- the one owner of the host library's HIP allocations (device memory, or pinned host memory), and the
-// two ways a buffer of a state grows.
+// dev_buf.hpp -- the one owner of the host library's HIP allocations (device memory, or pinned host memory), the two
+// ways a buffer of a state grows, and the one way a table filled on the host goes up (StagedUpload).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -93,5 +93,58 @@ hipError_t reserve_synced(hipStream_t s, DevBuf<T> &buf, size_t n) {
   buf.reset();
   return buf.alloc(n, 1);
 }
+
+// A table that a call fills on the host and copies to the device on a stream: two pinned areas taken in turn, and an
+// event per area recorded behind the copy out of it.  begin() waits for that event before it hands the area out again, so
+// no pending copy reads an area that is being written; the device side is ordered by the stream alone.  (Not copyable:
+// the areas are not.)
+class StagedUpload {
+ public:
+  ~StagedUpload() {   // (the pinned areas go after this body: no copy reads them then)
+    for (Area &a : area_) {
+      if (a.pending) (void)hipEventSynchronize(a.copied);
+      if (a.copied) (void)hipEventDestroy(a.copied);
+    }
+  }
+  // both areas at least `bytes` now, so that no later begin() of that size allocates
+  hipError_t reserve(size_t bytes) {
+    const hipError_t e = ready(area_[0], bytes);
+    return e != hipSuccess ? e : ready(area_[1], bytes);
+  }
+  // *host: the area whose turn it is, of at least `bytes`, as the table type the caller fills (the one place a staging
+  // area is read as a type).  An area too small is idle once its event has passed, so it is freed and allocated anew.
+  template <typename T>
+  hipError_t begin(size_t bytes, T **host) {
+    const hipError_t e = ready(area_[turn_], bytes);
+    *host = reinterpret_cast<T *>(area_[turn_].mem.get());
+    return e;
+  }
+  // the first `bytes` of the area begun to dev, on the stream; the turn passes to the other area
+  hipError_t commit(hipStream_t s, void *dev, size_t bytes) {
+    Area &a = area_[turn_];
+    turn_ ^= 1;
+    hipError_t e = hipMemcpyAsync(dev, a.mem.get(), bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipEventRecord(a.copied, s);
+    if (e == hipSuccess) a.pending = true;
+    return e;
+  }
+
+ private:
+  struct Area {
+    PinnedBuf<unsigned char> mem;
+    hipEvent_t copied = nullptr;
+    bool pending = false;
+  };
+  static hipError_t ready(Area &a, size_t bytes) {
+    hipError_t e = a.pending ? hipEventSynchronize(a.copied) : hipSuccess;
+    if (e != hipSuccess) return e;
+    a.pending = false;
+    if (!a.copied) e = hipEventCreateWithFlags(&a.copied, hipEventDisableTiming);
+    if (e == hipSuccess && (a.mem.size() < bytes || !a.mem)) e = a.mem.alloc(bytes, 1);
+    return e;
+  }
+  Area area_[2];
+  int turn_ = 0;
+};
 
 }  // namespace msc

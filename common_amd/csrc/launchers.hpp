@@ -366,7 +366,6 @@ struct MargFeat {
   uint32_t rows;           // table rows of the block (bb 2, dd dim, gp / bnb vcap, nich 6, noop 0)
   uint32_t pad;
 };
-static_assert(sizeof(MargChain) <= sizeof(SeqChain), "a staging area holds nchains entries of either table");
 constexpr uint32_t kCmTileFloats = 10240;   // 40 KiB of LDS a workgroup: four workgroups of 256 rows a CU
 constexpr uint32_t kCmMinTile = 32;         // a feature is staged only while a tile of this many groups still fits
 struct CmPlan {

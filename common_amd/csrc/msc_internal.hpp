@@ -480,9 +480,7 @@ struct PredWork {
   DevBuf<double> par;
   DevBuf<int32_t> z;
   std::vector<PredFeat> feats_host;   // what feats_dev holds
-  PinnedBuf<PredFeat> stage;          // pinned staging of the upload
-  hipEvent_t upload = nullptr;        // recorded after the upload from stage; destroyed with the state
-  bool upload_pending = false;
+  StagedUpload upload;                // how feats_dev is written
 };
 // the blocked Gibbs sampler (blocked.cpp msc_blocked_*): the parameter table -- (1 + sum of the features' slices) rows of
 // kpad floats, row 0 the log stick weights -- the features as the kernels read them, the stick kernel's scratch

@@ -133,22 +133,14 @@ extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, co
   if (pfs.size() > st->pred.feats_dev.size() || !st->pred.feats_dev) st->pred.feats_host.clear();   // (a new buffer holds nothing)
   MSC_HIP(reserve_synced(st->ctx->stream, st->pred.feats_dev, pfs.size()));
   for (size_t i = 0; i < pfs.size(); i++) pfs[i].par = st->pred.par + par_off[i];
-  // the descriptors go up only when they changed (a loop of calls uploads nothing), from pinned staging memory: the copy
-  // reads it when it runs, so the host waits -- for the previous upload only -- before it writes the staging again
+  // the descriptors go up only when they changed (a loop of calls uploads nothing)
   const size_t pbytes = pfs.size() * sizeof(PredFeat);
   if (pbytes && (st->pred.feats_host.size() != pfs.size() ||
                  std::memcmp(st->pred.feats_host.data(), pfs.data(), pbytes) != 0)) {
-    if (st->pred.stage.size() < pfs.size()) {
-      if (st->pred.upload_pending) MSC_HIP(hipEventSynchronize(st->pred.upload));
-      st->pred.upload_pending = false;
-      MSC_HIP(st->pred.stage.alloc(pfs.size()));   // (frees the smaller one first)
-    }
-    if (!st->pred.upload) MSC_HIP(hipEventCreateWithFlags(&st->pred.upload, hipEventDisableTiming));
-    if (st->pred.upload_pending) MSC_HIP(hipEventSynchronize(st->pred.upload));
-    std::memcpy(st->pred.stage, pfs.data(), pbytes);
-    MSC_HIP(hipMemcpyAsync(st->pred.feats_dev, st->pred.stage, pbytes, hipMemcpyHostToDevice, s));
-    MSC_HIP(hipEventRecord(st->pred.upload, s));
-    st->pred.upload_pending = true;
+    PredFeat *stage = nullptr;
+    MSC_HIP(st->pred.upload.begin(pbytes, &stage));
+    std::memcpy(stage, pfs.data(), pbytes);
+    MSC_HIP(st->pred.upload.commit(s, st->pred.feats_dev, pbytes));
     st->pred.feats_host = pfs;
   }
   if (launch_pred_prepare(s, st->pred.feats_dev, pfs, st->K, st->kpad)) return fail(MSC_EHIP, "k_pred_prepare launch failed");
