@@ -1498,12 +1498,6 @@ int msc::ensure_all_current(msc_state *st) {
 // scalar families go through one fused kernel (scores summed over features in registers);
 // every niw feature then adds its MFMA pass on top.
 
-// the rows the choice of kernels goes by: the bound view's, or those of the whole a sharded driver announced
-// (msc_state_set_sweep_rows) -- never a call's (route_sweep)
-uint64_t msc::view_rows(const msc_state *st) {
-  return st->sweep_rows_hint ? st->sweep_rows_hint : st->bound_view ? st->bound_view->nrows : 0;
-}
-
 // the tables of the plan's fused bb runs follow their members' (whatever updated those -- prepare, commit, an entity op):
 // rebuilt at the head of every call that scores with the fused plan, one small launch
 // ... and so does what the plan's nich blocks go by (NichPlanInfo: is a block's c1 one number per group, how far a value may
@@ -1553,8 +1547,10 @@ static void refresh_route_facts(msc_state *st) {
   rf.niw1_max_groups = sweep_niw1_max_groups(st->feats[0].dim);
   rf.nich1_rows_max_groups = sweep_nich1_rows_max_groups();
 }
-static const RouteFacts &route_facts_now(msc_state *st) {
-  st->route.view_rows = view_rows(st);
+// The facts as a call routes on them, in this unit and the others.  view_rows: the rows the choice of kernels goes by --
+// the bound view's, or those of the whole a sharded driver announced (msc_state_set_sweep_rows), never a call's (route_sweep)
+const RouteFacts &msc::route_facts_now(msc_state *st) {
+  st->route.view_rows = st->sweep_rows_hint ? st->sweep_rows_hint : st->bound_view ? st->bound_view->nrows : 0;
   return st->route;
 }
 
@@ -1843,9 +1839,6 @@ extern "C" int msc_score_data(msc_state *st, float *out_dev) {
   return MSC_OK;
 }
 
-// no niw feature and no count beyond the tables (route.hpp), for the units that route by it
-bool msc::sweep_plain(const msc_state *st) { return sweep_plain(st->route); }
-
 // the sampling kernels read (seed, sweep) from the state's device pair and the step ends by incrementing the sweep
 // index there, so consecutive sweeps need no host -> device traffic (and replay as a graph, msc_sweep_step)
 // `zeroed` non-null = part of a sweep step: the fused kernels also empty the additive tables for the accumulate pass
@@ -1928,16 +1921,8 @@ int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32
       break;
     }
     case SweepKind::generic: {
-      // score a chunk of rows (leave-one-out + prior) into scratch, then sample it
-      // (rows of K rounded up to 64 floats, not of the padded table width: at K = 300 the chunk is 320 wide, not 512 --
-      // neither the score kernels nor the sampler touch a row beyond K)
-      const uint64_t ld = std::min<uint64_t>(st->kpad, ((uint64_t)st->K + 63) & ~63ull);
-      // Up to 4 GiB of scores per chunk (288 GB of HBM: the scratch is not what runs out): fewer and larger launches beat
-      // keeping the chunk cache-resident (single nich, 1M rows x 300 groups, 32 / 64 / 128 / 256 / 512 MiB: 1.88 / 1.55 /
-      // 1.28 / 1.13 / 1.05 ms), a state with niw features wants >= 4 waves per SIMD on its MFMA kernel, and the
-      // leave-one-out pass takes its staged kernel only when the rows fill the chip -- C3's columns at K = 512, 1M rows:
-      // 5.39 ms a sweep step with 256 MiB chunks (eight of them), 4.95 with 1 GiB, 4.63 with the whole 2 GiB at once
-      const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((4096ull << 20) / (ld * sizeof(float)), nrows));
+      // score a chunk of rows (leave-one-out + prior) into scratch, then sample it (the chunk: route_calls.hpp score_chunk)
+      const auto [ld, chunk] = score_chunk(st->K, st->kpad, nrows);
       MSC_HIP(grow_retained(st->retired, st->scratch, chunk * ld));
       for (uint64_t at = 0; at < nrows; at += chunk) {
         const uint64_t n = std::min<uint64_t>(chunk, nrows - at);

@@ -43,7 +43,7 @@ int device_error_check(msc_context *ctx);
 int refuse_mid_step(const msc_state *st, const char *entry);
 bool refresh_alpha_sum(msc_state *st, uint32_t feature);
 int bind_view(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows);
-uint64_t view_rows(const msc_state *st);
+const RouteFacts &route_facts_now(msc_state *st);   // what a unit hands the routes of route.hpp / route_calls.hpp
 
 uint32_t prepare_value_slices(const msc_state *st);
 int ensure_raw(msc_state *st);
@@ -64,7 +64,6 @@ int commit(msc_state *st);
 int accumulate_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                     const int32_t *z_dev, uint32_t flags);
 
-bool sweep_plain(const msc_state *st);
 int sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                       uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep, bool *zeroed = nullptr);
 
@@ -91,7 +90,7 @@ int joint_entries(const msc_state *st, const char *who, const msc_slice_coord *c
 // ---- what blocked.cpp defines for msc_chains_split_merge (chains.cpp): the move's route for a member, and the member's
 // pair state as the pair half of its table entry (launchers.hpp SmChain) ----
 struct SmChain;
-int sm_chain_route(const msc_state *st);
+int sm_chain_route(msc_state *st);
 int sm_chain_pair(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t nrows, SmChain *entry);
 #pragma GCC visibility pop
 

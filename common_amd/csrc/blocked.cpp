@@ -15,39 +15,7 @@ using namespace msc;
 // The blocked (uncollapsed) Gibbs sampler (kernels_blocked.hip, blocked_post.hpp): draw every slot's parameters and the
 // stick weights from the tables, then every row's slot independently under them.
 // ---------------------------------------------------------------------------
-// Which assign kernel a state takes, and whether the sampler takes it at all.  By the state alone: every kernel adds a
-// row's terms in the same order (blk_tile_scores), so a sub-range draws what the whole draws whichever is chosen.
-//   nich1   a single nich column: the row's value in a register, no LDS
-//   staged  up to 256 features: the workgroup's row values staged in LDS once, [feature][row] -- 256 rows a workgroup up
-//           to 32 features, 128 up to 64, 64 beyond (32 KiB at most, 64 KiB from 129 features on)
-//   global  more features than that: the values re-read from the columns for every eight slots
-// The split-merge move takes the same families and shapes (every kernel adds a row's terms in the same order, so the
-// choice never changes a bit); its staged kernel holds one feature fewer.  who: the caller, as the message names it.
-struct BlockedRoute { int rc = MSC_OK; std::string why; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
-constexpr uint32_t kBlockedStagedMax = 256;             // (at most 32 KiB of LDS a workgroup: several a compute unit)
-constexpr uint32_t kSplitMergeStagedMax = 255;          // (the codes and the waves' sums within 64 KiB of LDS a workgroup)
-static BlockedRoute route_blocked(const msc_state *st, const char *who, uint32_t staged_max) {
-  BlockedRoute r;
-  for (const auto &h : st->feats)
-    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
-      r.rc = MSC_EUNSUPPORTED;
-      r.why = std::string(who) + " takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
-      return r;
-    }
-  if (st->nfeat >= blocked::kStickTag) {
-    r.rc = MSC_EUNSUPPORTED;
-    r.why = std::string(who) + " takes fewer than 32767 features";
-    return r;
-  }
-  if (st->nfeat == 1 && st->feats[0].family == MSC_NICH) r.kernel = BlockedKernel::nich1;
-  else if (st->nfeat <= staged_max) {
-    r.kernel = BlockedKernel::staged;
-    r.block = st->nfeat <= 32 ? 256 : st->nfeat <= 64 ? 128 : 64;
-  }
-  return r;
-}
-static BlockedRoute route_sweep_blocked(const msc_state *st) { return route_blocked(st, "the blocked sweep", kBlockedStagedMax); }
-static BlockedRoute route_splitmerge(const msc_state *st) { return route_blocked(st, "split-merge", kSplitMergeStagedMax); }
+// (Which assign kernel a state takes, and whether the sampler takes it at all: route_calls.hpp route_sweep_blocked.)
 
 // a feature's slices in a state's parameter table (UINT32_MAX: row 0, the log weights), as msc_blocked_tables and
 // msc_split_merge_tables hand them out
@@ -135,7 +103,7 @@ extern "C" int msc_blocked_draw(msc_state *st, uint64_t seed, uint64_t sweep) {
   MSC_TRY(refuse_mid_step(st, "msc_blocked_draw"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_sweep_blocked(st);
+  const BlockedRoute route = route_sweep_blocked(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   return blocked_draw_impl(st, seed, sweep);
 }
@@ -144,7 +112,7 @@ extern "C" int msc_blocked_tables(msc_state *st, uint32_t feature, const float *
   MSC_REQUIRE(st, "null state");
   MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
   MSC_HIP(hipSetDevice(st->ctx->device));
-  const BlockedRoute route = route_sweep_blocked(st);
+  const BlockedRoute route = route_sweep_blocked(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(blocked_setup(st));
   blocked_table_slices(st, feature, dev, nslices, ld);
@@ -157,7 +125,7 @@ extern "C" int msc_blocked_assign(msc_state *st, const msc_dataview *view, const
   MSC_TRY(refuse_mid_step(st, "msc_blocked_assign"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_sweep_blocked(st);
+  const BlockedRoute route = route_sweep_blocked(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   return blocked_assign_impl(st, route, view, cols, row0, nrows, row_id0, z_dev, seed, sweep);
 }
@@ -169,7 +137,7 @@ extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const 
   MSC_TRY(refuse_mid_step(st, "msc_sweep_blocked"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_sweep_blocked(st);
+  const BlockedRoute route = route_sweep_blocked(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   hipStream_t s = st->ctx->stream;
@@ -188,7 +156,7 @@ extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const 
 // The split-merge move (kernels_splitmerge.hip, splitmerge_math.hpp): Metropolis-Hastings proposals that split one group
 // in two or merge two groups, the launch state reached by restricted BLOCKED Gibbs passes over the rows of the two groups.
 // ---------------------------------------------------------------------------
-// (Which assign kernel a state takes, and whether the move takes it at all: route_splitmerge, next to route_blocked.)
+// (Which assign kernel a state takes, and whether the move takes it at all: route_calls.hpp route_splitmerge.)
 // The pair state (three slots: the pair's two, and their union for score_data), created at the first call; its
 // hyper-parameters and alpha follow the state's before every call
 constexpr uint32_t kSmSlots = 3;
@@ -221,7 +189,7 @@ extern "C" int msc_split_merge(msc_state *st, const msc_dataview *view, const ui
   MSC_REQUIRE(nrows < (1ull << 48), "msc_split_merge takes fewer than 2^48 rows");
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const BlockedRoute route = route_splitmerge(st);
+  const BlockedRoute route = route_splitmerge(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   MSC_TRY(ensure_raw(st));                                 // (the group sizes: where a split finds its empty slot)
@@ -277,8 +245,8 @@ extern "C" int msc_split_merge(msc_state *st, const msc_dataview *view, const ui
 // the member's pair state -- created at the first call, its hyper-parameters and alpha following the member's, bound to the
 // view, its parameter-table features as the kernels read them -- as the pair half of the chain's table entry.
 namespace msc {
-int sm_chain_route(const msc_state *st) {
-  const BlockedRoute route = route_splitmerge(st);
+int sm_chain_route(msc_state *st) {
+  const BlockedRoute route = route_splitmerge(route_facts_now(st));
   return route.rc != MSC_OK ? fail(route.rc, "%s", route.why.c_str()) : MSC_OK;
 }
 int sm_chain_pair(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t nrows, SmChain *entry) {
@@ -299,7 +267,7 @@ extern "C" int msc_split_merge_tables(msc_state *st, uint32_t feature, const flo
   MSC_REQUIRE(st, "null state");
   MSC_REQUIRE(feature == UINT32_MAX || feature < st->nfeat, "feature %u out of range", feature);
   MSC_HIP(hipSetDevice(st->ctx->device));
-  const BlockedRoute route = route_splitmerge(st);
+  const BlockedRoute route = route_splitmerge(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(sm_setup(st));
   msc_state *pair = st->sm.pair;

@@ -16,51 +16,9 @@ using namespace msc;
 
 // ---------------------------------------------------------------------------
 // The sequential sweep (k_sweep_seq): one workgroup carries the chain; the state carries over in global memory between
-// launches, and a launch takes as many row visits as fit kSeqLaunchUs by seq_visit_us.
+// launches, and a launch takes as many row visits as fit kSeqLaunchUs by seq_visit_us (route_calls.hpp: whether the
+// kernel takes a state, route_sequential; a launch's share, units_per_launch).
 // ---------------------------------------------------------------------------
-constexpr double kSeqLaunchUs = 20000.0;        // what one launch may take (estimated)
-constexpr uint64_t kSeqMaxVisitsPerLaunch = 10000;
-
-// An upper estimate of one row visit, in microseconds: a fixed part (barriers, the draw, a nich prepare) plus the table
-// entries a leave and a join rebuild and the (group, feature) scores; fitted to the visits of profiles/sequential.txt (one
-// nich column to the C3 mix, K = 16 to 1024): launches measured there at 11.9 ms on average, 26.3 ms the longest
-static double seq_visit_us(const msc_state *st) {
-  double rows = 0.0;                              // table entries prepare_group writes per (feature, group)
-  for (uint32_t f = 0; f < st->nfeat; f++) {
-    switch (st->feats[f].family) {
-      case MSC_BB: rows += 4; break;
-      case MSC_GP:
-      case MSC_BNB: rows += 2.0 * st->desc_host[f].vcap + 4; break;
-      case MSC_DD: rows += 2.0 * st->feats[f].dim + 2; break;
-      case MSC_NICH: rows += 14; break;
-      default: break;
-    }
-  }
-  return 16.0 + 0.02 * 2.0 * rows + 0.007 * (double)st->K * (double)st->nfeat;
-}
-
-// whether the sequential kernel takes a state: ok, or the status and why not
-struct SeqRoute { int rc = MSC_OK; const char *why = ""; };
-static SeqRoute route_sequential(const msc_state *st) {
-  SeqRoute r;
-  for (const auto &h : st->feats) {
-    // niw, dm: prepare kernels of their own (msc_entity_op sends them down the general path); bbnc: a slot that empties
-    // mid-sweep would be offered with a stale p (free slots' p is drawn between sweeps, mixture_state refresh_free_slots)
-    if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC) {
-      r.rc = MSC_EUNSUPPORTED;
-      r.why = "the sequential sweep takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)";
-      return r;
-    }
-  }
-  if (st->nfeat > (uint32_t)kSeqMaxFeat) {
-    r.rc = MSC_EUNSUPPORTED;
-    r.why = "the sequential sweep takes at most 256 features";
-  } else if (st->K > kSeqMaxGroups) {
-    r.rc = MSC_EUNSUPPORTED;
-    r.why = "the sequential sweep takes at most 8192 groups";
-  }
-  return r;
-}
 
 extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                                     uint64_t nrows, uint64_t row_id0, int32_t *z_dev, const uint32_t *order_dev,
@@ -70,7 +28,7 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
   MSC_TRY(refuse_mid_step(st, "msc_sweep_sequential"));
   MSC_HIP(hipSetDevice(st->ctx->device));
   MSC_TRY(device_error_check(st->ctx));
-  const SeqRoute route = route_sequential(st);
+  const SeqRoute route = route_sequential(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   if (nrows == 0 || nsweeps == 0) return MSC_OK;
@@ -78,7 +36,7 @@ extern "C" int msc_sweep_sequential(msc_state *st, const msc_dataview *view, con
   hipStream_t s = st->ctx->stream;
   MSC_TRY(ensure_all_current(st));
   const uint64_t visits = (uint64_t)nsweeps * nrows;
-  const uint64_t per_launch = (uint64_t)std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / seq_visit_us(st)));
+  const uint64_t per_launch = units_per_launch(1, st->ctx->num_cus, seq_visit_us(route_facts_now(st)));
   for (uint64_t v0 = 0; v0 < visits; v0 += per_launch) {
     const uint64_t v1 = std::min(visits, v0 + per_launch);
     const int rc = launch_sweep_seq(s, st->desc_dev, (int)st->nfeat, st->K, st->kpad, row0, nrows, row_id0, z_dev, order_dev,
@@ -159,15 +117,6 @@ static int chains_enter(msc_chains *ch, const char *who, ChainsEnsure ensure, co
   return MSC_OK;
 }
 
-// Whole units (row visits, proposals) of every chain that one launch takes: what one chain may take in kSeqLaunchUs at
-// unit_us a unit, kSeqMaxVisitsPerLaunch at most, divided by the rounds the grid runs in -- at these kernels' register
-// counts one workgroup is resident per CU.  At least one: the least a launch can take.
-static uint64_t chains_units_per_launch(const msc_chains *ch, double unit_us) {
-  const uint64_t n = ch->states.size(), cus = (uint64_t)std::max(1, ch->ctx->num_cus);
-  const double one = std::max(1.0, std::min((double)kSeqMaxVisitsPerLaunch, kSeqLaunchUs / unit_us));
-  return std::max<uint64_t>(1, (uint64_t)one / ((n + cus - 1) / cus));
-}
-
 extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc_chains **out) {
   MSC_REQUIRE(states && out, "null argument");
   *out = nullptr;
@@ -187,7 +136,7 @@ extern "C" int msc_chains_create(msc_state *const *states, uint32_t nchains, msc
                   "msc_chains_create: feature %u of state %u (family %d, dim %u) differs from state 0's (family %d, dim %u)",
                   f, c, st->feats[f].family, st->feats[f].dim, states[0]->feats[f].family, states[0]->feats[f].dim);
   }
-  const SeqRoute route = route_sequential(states[0]);      // (equal feature lists and K: one answer for all)
+  const SeqRoute route = route_sequential(route_facts_now(states[0]));   // (equal feature lists and K: one answer for all)
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why);
   msc_context *ctx = states[0]->ctx;
   MSC_HIP(hipSetDevice(ctx->device));
@@ -248,7 +197,7 @@ static int chains_visits_impl(msc_chains *ch, const char *who, const msc_datavie
   if (v0 >= v1) return MSC_OK;
   hipStream_t s = ch->ctx->stream;
   double visit_us = 0.0;                                    // (as msc_sweep_sequential, by the costliest member)
-  for (const msc_state *st : ch->states) visit_us = std::max(visit_us, seq_visit_us(st));
+  for (msc_state *st : ch->states) visit_us = std::max(visit_us, seq_visit_us(route_facts_now(st)));
   // the table of this call (pointers and alpha may have changed since the last one)
   SeqChain *tab = nullptr;
   MSC_HIP(ch->upload.begin(sizeof(SeqChain) * n, &tab));
@@ -271,7 +220,7 @@ static int chains_visits_impl(msc_chains *ch, const char *who, const msc_datavie
   }
   MSC_HIP(ch->upload.commit(s, ch->call_tab, sizeof(SeqChain) * n));
   const msc_state *st0 = ch->states[0];
-  const uint64_t per_launch = chains_units_per_launch(ch, visit_us);
+  const uint64_t per_launch = units_per_launch(n, ch->ctx->num_cus, visit_us);
   for (uint64_t w0 = v0; w0 < v1; w0 += per_launch) {
     const uint64_t w1 = std::min(v1, w0 + per_launch);
     const int rc = launch_sweep_seq_chains(s, ch->table<SeqChain>(), n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows,
@@ -404,7 +353,7 @@ extern "C" int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, 
               (unsigned long long)nrows);
   MSC_TRY(chains_refuse_mid_step(ch, "msc_chains_split_merge"));
   const msc_state *st0 = ch->states[0];
-  MSC_TRY(sm_chain_route(st0));                             // (equal feature lists: one answer for all)
+  MSC_TRY(sm_chain_route(ch->states[0]));                   // (equal feature lists: one answer for all)
   // a launch takes the whole proposals that fit the sweep's launch budget, by the estimate above times the rounds the grid
   // runs in (one workgroup a compute unit is what the estimate was measured at).  What is refused is a proposal that
   // alone exceeds the budget in ONE round: with more chains than compute units a launch of one proposal -- the least a
@@ -441,7 +390,7 @@ extern "C" int msc_chains_split_merge(msc_chains *ch, const msc_dataview *view, 
     e.pad = 0;
   }
   MSC_HIP(ch->upload.commit(s, ch->call_tab, sizeof(SmChain) * n));
-  const uint32_t per_launch = (uint32_t)std::min<uint64_t>(nproposals, chains_units_per_launch(ch, one_us));
+  const uint32_t per_launch = (uint32_t)std::min<uint64_t>(nproposals, units_per_launch(n, ch->ctx->num_cus, one_us));
   const uint32_t pair_kpad = st0->sm.pair->kpad;
   for (uint32_t p0 = 0; p0 < nproposals; p0 += per_launch) {
     const uint32_t p1 = std::min(nproposals, p0 + per_launch);
@@ -633,19 +582,8 @@ extern "C" int msc_chains_anneal_weights(msc_chains *ch, const double *joint_dev
 // ---------------------------------------------------------------------------
 // The posterior-averaged row predictive density over the chains (kernels_chains_marginal.hip)
 // ---------------------------------------------------------------------------
-// How the chains are cut over the grid's second dimension.  By the ensemble and view_rows alone (THE SHARD RULE of
-// route_marginal): the slices' parts are merged in slice order, so a call over a sub-range must cut as the whole call does.
-// A view of fewer than four workgroups of 256 rows a compute unit (what its LDS holds) is filled up with slices, at most
-// one a chain.
-static uint32_t route_chains_marginal(const msc_chains *ch) {
-  const uint32_t n = (uint32_t)ch->states.size();
-  const uint64_t blocks = std::max<uint64_t>(1, (view_rows(ch->states[0]) + 255) / 256);
-  const uint64_t want = 4ull * (uint64_t)std::max(1, ch->ctx->num_cus);
-  if (blocks >= want) return 1;
-  const uint32_t slices = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, 1024), (want + blocks - 1) / blocks);
-  const uint32_t per = (n + slices - 1) / slices;
-  return (n + per - 1) / per;
-}
+// (How the chains are cut over the grid's second dimension, and the tile plan of a call: route_calls.hpp
+// route_chains_marginal and plan_chains_marginal -- by the ensemble, the features and the view's rows, never the call's.)
 
 // what msc_chains_score_marginal and msc_chains_sample_predictive check and bind before anything is launched
 static int chains_marginal_begin(msc_chains *ch, const char *who, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
@@ -677,9 +615,9 @@ struct MargCall {
   double *lw = nullptr, *norm = nullptr;
 };
 // The table of this call through the call table -- the chains (chain c's row of chain_logp at logp + c * ld_logp), the
-// selected features' tile plan (from member 0's bound descriptors: families and dims are equal by msc_chains_create, the
-// count columns' table sizes were compared by chains_marginal_begin), the output pointers of a sampling call -- and
-// k_chains_marginal_prep's launch.
+// selected features' tile plan (from member 0's facts as of its binding: families and dims are equal by
+// msc_chains_create, the count columns' table sizes were compared by chains_marginal_begin), the output pointers of a
+// sampling call -- and k_chains_marginal_prep's launch.
 static int chains_marginal_stage(msc_chains *ch, const uint32_t *features, uint32_t nfeatures, const double *logw_dev,
                                  float *logp, uint64_t ld_logp, void *const *outs, MargCall &call) {
   const uint32_t n = (uint32_t)ch->states.size();
@@ -704,7 +642,7 @@ static int chains_marginal_stage(msc_chains *ch, const uint32_t *features, uint3
   }
   std::vector<uint32_t> sel(nsel);
   for (uint32_t i = 0; i < nsel; i++) sel[i] = all ? i : features[i];
-  call.plan = plan_chains_marginal(st0->desc_host.data(), sel.data(), nsel, st0->K, pf);
+  call.plan = plan_chains_marginal(st0->route.feats.data(), sel.data(), nsel, st0->K, pf);
   call.nsel = nsel;
   unsigned char *dev = ch->call_tab;
   if (outs != nullptr) {
@@ -741,11 +679,12 @@ extern "C" int msc_chains_score_marginal(msc_chains *ch, const msc_dataview *vie
     }
   MSC_TRY(chains_marginal_begin(ch, "msc_chains_score_marginal", view, cols, row0, nrows));
   if (nrows == 0) return MSC_OK;
-  const uint32_t nslices = route_chains_marginal(ch);
+  const uint64_t view_rows = route_facts_now(ch->states[0]).view_rows;
+  const uint32_t nslices = route_chains_marginal(n, view_rows, ch->ctx->num_cus);
   // the slices' workspace holds the whole VIEW's rows (what the slice count follows from): one size per view and device,
   // so calls over sub-ranges of any lengths never grow it again
   if (nslices > 1 && mix_dev)
-    MSC_HIP(grow_retained(ch->retired, ch->marg_part, 2 * (size_t)nslices * std::max<uint64_t>(nrows, view_rows(st0))));
+    MSC_HIP(grow_retained(ch->retired, ch->marg_part, 2 * (size_t)nslices * std::max<uint64_t>(nrows, view_rows)));
   MargCall call;
   MSC_TRY(chains_marginal_stage(ch, features, nfeatures, logw_dev, chain_logp_dev, ld_logp, nullptr, call));
   return launch_chains_marginal(ch->ctx->stream, call.chains_dev, call.plan_dev, call.nsel, call.plan, n, nslices, st0->K,
@@ -756,10 +695,7 @@ extern "C" int msc_chains_score_marginal(msc_chains *ch, const msc_dataview *vie
 // Posterior predictive draws from the model average (kernels_chains_pred.hip)
 // ---------------------------------------------------------------------------
 // The rows of a call go through the handle's scratch -- the chains' rows Lf [nchains][chunk] floats, then the rows' chain
-// and group -- a chunk at a time: at most kPredScratchBytes of Lf and kPredChunkRows rows.  A row depends on the row alone,
-// so the cut moves no bit.
-constexpr uint64_t kPredScratchBytes = 256ull << 20;
-constexpr uint64_t kPredChunkRows = 1ull << 18;
+// and group -- a chunk at a time (route_calls.hpp pred_chunk).  A row depends on the row alone, so the cut moves no bit.
 
 extern "C" int msc_chains_sample_predictive(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                                             uint64_t nrows, uint64_t row_id0, const double *logw_dev, uint32_t flags,
@@ -784,17 +720,16 @@ extern "C" int msc_chains_sample_predictive(msc_chains *ch, const msc_dataview *
   MSC_TRY(chains_marginal_begin(ch, "msc_chains_sample_predictive", view, cols, row0, nrows));
   if (nrows == 0) return MSC_OK;
   // the scratch: Lf, then chain and group of the chunk's rows (the caller's arrays where it gave them)
-  // (a power of two from 4096 on: the buffers a growing scratch retires stay with the handle, and add up to less than
-  // the last one)
-  uint64_t chunk = 4096;
-  while (chunk < nrows && chunk < kPredChunkRows && 2 * chunk * n * sizeof(float) <= kPredScratchBytes) chunk *= 2;
+  const uint64_t chunk = pred_chunk(n, nrows);
   MSC_HIP(grow_retained(ch->retired, ch->pred_lf, (size_t)n * chunk));
   MSC_HIP(grow_retained(ch->retired, ch->pred_cz, 2 * (size_t)chunk));
   float *Lf = ch->pred_lf;
   MargCall call;
   MSC_TRY(chains_marginal_stage(ch, nullptr, 0, logw_dev, Lf, chunk, out_dev, call));
   hipStream_t s = ch->ctx->stream;
-  const uint32_t nslices = route_chains_marginal(ch);         // (the grid's cut only: with no mix, no slice writes a part)
+  // (the grid's cut only: with no mix, no slice writes a part)
+  const uint32_t nslices = route_chains_marginal(n, route_facts_now(ch->states[0]).view_rows, ch->ctx->num_cus);
+  const int batch = chains_draw_batch(st0->K, call.plan.large);
   for (uint64_t at = 0; at < nrows; at += chunk) {
     const uint64_t m = std::min<uint64_t>(chunk, nrows - at);
     int32_t *chain = chain_out_dev ? chain_out_dev + at : ch->pred_cz.get();
@@ -802,8 +737,8 @@ extern "C" int msc_chains_sample_predictive(msc_chains *ch, const msc_dataview *
     MSC_TRY(launch_chains_marginal(s, call.chains_dev, call.plan_dev, call.nsel, call.plan, n, nslices, st0->K, st0->kpad,
                                    row0 + at, m, call.lw, call.norm, nullptr, nullptr));
     MSC_TRY(launch_chains_pick(s, call.lw, Lf, chunk, n, m, row_id0 + at, seed, sweep, chain));
-    MSC_TRY(launch_chains_draw(s, call.chains_dev, call.plan.large, st0->nfeat, st0->K, st0->kpad, row0 + at, m, row_id0 + at,
-                               seed, sweep, chain, z));
+    MSC_TRY(launch_chains_draw(s, call.chains_dev, call.plan.large, batch, st0->nfeat, st0->K, st0->kpad, row0 + at, m,
+                               row_id0 + at, seed, sweep, chain, z));
     if (light || heavy)
       MSC_TRY(launch_chains_values(s, call.chains_dev, call.outs_dev, light, heavy, st0->nfeat, st0->kpad, row0 + at, m,
                                    row_id0 + at, at, chain, z, (flags & MSC_PRED_MASKED_ONLY) != 0, seed, sweep));

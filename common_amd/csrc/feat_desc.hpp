@@ -199,6 +199,18 @@ enum { MSC_KIND_GENERIC = 0, MSC_KIND_LOOKUP_U8 = 1, MSC_KIND_LOOKUP_U32 = 2, MS
 // families whose score is a lookup of the row's count in an exact per-group table
 MSC_HOST_DEVICE inline bool is_count_family(int family) { return family == MSC_GP || family == MSC_BNB; }
 
+// rows of a feature's block in a tile of k_chains_marginal (0: nothing to stage)
+MSC_HOST_DEVICE inline uint32_t cm_table_rows(int family, uint32_t dim, uint32_t vcap) {
+  switch (family) {
+    case MSC_BB: return 2u;
+    case MSC_DD: return dim;
+    case MSC_GP:
+    case MSC_BNB: return vcap;
+    case MSC_NICH: return 6u;                              // (NICH_ROWS)
+    default: return 0u;
+  }
+}
+
 // (nich: kNlooStride doubles per group, group-major -- a row's leave-one-out pass reads ONE group's six constants: side
 // by side they are 48 bytes, one cache line mostly; family_math.hpp NLOO_*)
 constexpr uint32_t kNlooStride = 6;

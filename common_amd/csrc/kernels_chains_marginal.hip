@@ -17,7 +17,7 @@
 //                             first, the batch pushed onto the lane's (max, sum) of the chain (chains_merge.hpp row_push).
 //                             After the last tile L is finished in double and lw_c + L is pushed onto the lane's (M, S) of
 //                             the slice (w_push).  A feature whose tables do not fit a tile of kCmMinTile groups beside the
-//                             ones before it is read from global memory instead (plan_chains_marginal).
+//                             ones before it is read from global memory instead (route_calls.hpp plan_chains_marginal).
 //                             The row's values are re-read per batch from the view's columns (the same few cache lines for
 //                             every chain and tile: L1 / L2 hits), not staged: up to 256 features of 256 rows do not fit
 //                             beside the tables, and a value is one coalesced load per B table reads.
@@ -27,7 +27,7 @@
 //                             part[slice][row] and
 //   k_chains_marginal_finish  merges a row's slices in ascending slice order (w_merge) and rounds once.
 // A row's results depend on nothing but the row, the tile size and the slice cut, and the host derives those two from the
-// ensemble and the bound view's rows alone (chains.cpp route_chains_marginal): a sub-range call gives the whole call's bits.
+// ensemble and the bound view's rows alone (route_calls.hpp plan_chains_marginal, route_chains_marginal): a sub-range call gives the whole call's bits.
 // No float atomics anywhere: the same bits on every run.
 #include "chains_merge.hpp"
 #include "family_math.hpp"
@@ -37,17 +37,7 @@
 
 namespace msc {
 
-// rows of feature fd's block in a tile (0: nothing to stage)
-__host__ __device__ inline uint32_t cm_table_rows(int family, uint32_t dim, uint32_t vcap) {
-  switch (family) {
-    case MSC_BB: return 2u;
-    case MSC_DD: return dim;
-    case MSC_GP:
-    case MSC_BNB: return vcap;
-    case MSC_NICH: return (uint32_t)NICH_ROWS;
-    default: return 0u;
-  }
-}
+static_assert(NICH_ROWS == 6, "cm_table_rows (feat_desc.hpp) counts a nich block's rows");
 
 __global__ __launch_bounds__(256) void k_chains_marginal_prep(const MargChain *__restrict__ chains, uint32_t nchains, uint32_t K,
                                                               const double *__restrict__ logw, double *__restrict__ lw,
@@ -89,11 +79,7 @@ __global__ __launch_bounds__(256) void k_chains_marginal_prep(const MargChain *_
   }
 }
 
-// groups a lane sums in registers before it pushes them: what a feature costs a lane apart from its table reads -- its
-// plan entry, the descriptor's fields, the row's value -- is paid once a batch, so tiles of whole wide batches take
-// kCmBatchWide; narrower tiles (few groups, or tables too tall for 32 groups of them) take kCmBatch
-constexpr int kCmBatch = 8, kCmBatchWide = 32;
-constexpr uint32_t kCmNotStaged = 0xffffffffu;  // MargFeat::off of a feature whose tables stay in global memory
+// (kCmBatch / kCmBatchWide, the groups a lane sums in registers before it pushes them, and kCmNotStaged: route_calls.hpp)
 
 // acc[j] += score_value of raw value v against the B groups whose table entries are b[row * stride + j]: b is a
 // feature's block of the LDS tile (stride TS; entries past the tile's groups lie inside the allocation and are dropped by
@@ -223,42 +209,6 @@ __global__ __launch_bounds__(256) void k_chains_marginal_finish(const double *__
     w = cmerge::w_merge(w, cmerge::WPart{p[0], p[1]});
   }
   mix[rel] = cmerge::w_finish(w);
-}
-
-// ---------------------------------------------------------------------------
-// The tile plan of a call: which selected features' tables are staged, where, and how many groups a tile holds.  From the
-// features alone (their families, dims and the bound column's vcap): every member of an ensemble has the same.
-CmPlan plan_chains_marginal(const FeatDesc *feats_host, const uint32_t *sel, uint32_t nsel, uint32_t K, MargFeat *out) {
-  // features are staged in order while a tile of kCmMinTile groups of them fits; the others read global memory
-  const uint32_t min_ts = (std::min<uint32_t>(K, kCmMinTile)) | 1u;
-  CmPlan p;
-  uint32_t rows = 2;
-  for (uint32_t i = 0; i < nsel; i++) {
-    const FeatDesc &d = feats_host[sel[i]];
-    const uint32_t r = cm_table_rows(d.family, d.dim, d.vcap);
-    if ((d.family == MSC_GP || d.family == MSC_BNB) && d.vcap >= kGpMaxTable) p.large = true;   // (vcap = min(column max + 1, the cap))
-    MargFeat &m = out[i];
-    m.f = sel[i];
-    m.rows = r;
-    m.pad = 0;
-    if (r == 0 || (uint64_t)(rows + r) * min_ts + kCmBatchWide > kCmTileFloats) {
-      m.off = kCmNotStaged;
-      if (r == 0) m.off = 0;                                // (noop: nothing to stage, nothing to read)
-      continue;
-    }
-    m.off = rows;                                           // (in rows for now)
-    rows += r;
-  }
-  uint32_t tg = std::min<uint32_t>(K, (kCmTileFloats - kCmBatchWide) / rows - 1u);
-  p.wide = tg >= (uint32_t)kCmBatchWide;
-  const uint32_t batch = p.wide ? kCmBatchWide : kCmBatch;
-  if (tg > batch) tg -= tg % batch;                         // whole batches
-  p.TG = std::max<uint32_t>(tg, 1u);
-  p.TS = p.TG | 1u;
-  p.lds_floats = rows * p.TS + kCmBatchWide;                // (a batch's reads past the tile's groups stay inside)
-  for (uint32_t i = 0; i < nsel; i++)
-    if (out[i].off != kCmNotStaged) out[i].off *= p.TS;
-  return p;
 }
 
 int launch_chains_marginal_prep(hipStream_t stream, const MargChain *chains_dev, uint32_t nchains, uint32_t K,

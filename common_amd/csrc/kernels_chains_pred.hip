@@ -38,10 +38,8 @@ namespace msc {
 
 // groups a lane sums in registers at a time.  What a feature costs a lane apart from its table reads -- the descriptor's
 // fields, the row's value, the chain's table address, each a load that waits for the one before -- is paid once a batch:
-// kCpBatchWide from kCpWideFrom groups on, kCpBatch below (a batch reads whole, also past the last group).  Both divide
-// the tables' row stride (kpad), so a batch never reads past a table row.
-constexpr int kCpBatch = 8, kCpBatchWide = 32;
-constexpr uint32_t kCpWideFrom = 64;
+// kCpBatchWide from kCpWideFrom groups on, kCpBatch below (route_calls.hpp chains_draw_batch chooses; a batch reads
+// whole, also past the last group).  Both divide the tables' row stride (kpad), so a batch never reads past a table row.
 static_assert(kGroupTile % kCpBatch == 0 && kGroupTile % kCpBatchWide == 0, "a batch never reads past a table row");
 
 __global__ __launch_bounds__(256) void k_chains_pick(const double *__restrict__ lw, const float *__restrict__ Lf, uint64_t ld,
@@ -237,13 +235,14 @@ int launch_chains_pick(hipStream_t stream, const double *lw, const float *Lf, ui
   return launch_status("k_chains_pick");
 }
 
-int launch_chains_draw(hipStream_t stream, const MargChain *chains_dev, bool large, uint32_t nfeat, uint32_t K, uint32_t kpad,
-                       uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t seed, uint64_t sweep, int32_t *chain,
-                       int32_t *z) {
-  if (K == 0 || kpad < K || kpad % kCpBatchWide != 0 || nrows == 0 || nrows >= (1ull << 32))
+int launch_chains_draw(hipStream_t stream, const MargChain *chains_dev, bool large, int batch, uint32_t nfeat, uint32_t K,
+                       uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t seed, uint64_t sweep,
+                       int32_t *chain, int32_t *z) {
+  const bool wide = batch == kCpBatchWide;
+  if (K == 0 || kpad < K || kpad % kCpBatchWide != 0 || nrows == 0 || nrows >= (1ull << 32) || (!wide && batch != kCpBatch) ||
+      (wide && large))
     return fail(MSC_EHIP, "launch_chains_draw: a shape no route sends");
   const dim3 grid((unsigned)((nrows + 255) / 256));
-  const bool wide = K >= kCpWideFrom;
 #define MSC_CP_LAUNCH(LARGE, B)                                                                                            \
   hipLaunchKernelGGL((k_chains_draw<LARGE, B>), grid, dim3(256), 0, stream, chains_dev, nfeat, K, kpad, row0, nrows, row_id0, \
                      seed, sweep, chain, z)

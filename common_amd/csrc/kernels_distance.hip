@@ -15,7 +15,7 @@
 //                between the phases, merges equal neighbours before it adds, and a wave whose 256 keys are all equal adds
 //                once (the all-in-one pair would otherwise put 64 lanes on one address).  The table is in LDS (u32 cells,
 //                kPdLdsCells of them) or in the workgroup's slice of a global workspace (kPdSliceCells cells, zeroed when
-//                it was allocated): route_pd_table (launchers.hpp) says which, per pair, from the two cluster counts; a
+//                it was allocated): route_pd_table (route_calls.hpp) says which, per pair, from the two cluster counts; a
 //                launch computes the pairs of its own route and leaves the others to the other launch.
 // Bounds: an id is below its partition's cluster count K <= kPdMaxClusters by construction (k_pd_canon), so a key is below
 // K_a K_b, which is at most kPdLdsCells on the LDS route and at most kPdSliceCells on the other.

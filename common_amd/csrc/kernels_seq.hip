@@ -13,7 +13,7 @@
 //                   join   as leave, for the drawn group; the row's slot in z is written there
 //                 Only the two groups that changed, and the empty-slot terms, have their CRP terms rewritten; the count of
 //                 empty slots lives in LDS for the launch.  The score tables are read from global memory (L2 at these
-//                 sizes).  A launch takes the visits that fit a time budget (chains.cpp seq_visit_us); the state carries over in
+//                 sizes).  A launch takes the visits that fit a time budget (route_calls.hpp seq_visit_us); the state carries over in
 //                 global memory.
 //   k_sweep_seq_chains   a grid of such workgroups, one independent chain each (msc_chains_sweep): what differs per chain
 //                 is a SeqChain entry of a device table; also a thinned trace and the occupied-slot count per sample.

@@ -1,9 +1,10 @@
-// launchers.hpp -- host entry points of the kernel translation units.
+// launchers.hpp -- host entry points of the kernel translation units.  They launch what the routes chose (route.hpp,
+// route_calls.hpp: the only places that choose); nothing is chosen here.
 #pragma once
 #include <algorithm>
 
 #include "msc_internal.hpp"
-#include "route.hpp"
+#include "route_calls.hpp"
 
 namespace msc {
 
@@ -147,9 +148,8 @@ int launch_rng_set(hipStream_t stream, uint64_t *rng_dev, uint64_t seed, uint64_
 int launch_rng_bump(hipStream_t stream, uint64_t *rng_dev);
 
 // kernels_seq.hip: visits [v0, v1) of the sequential sweep (msc_sweep_sequential), one workgroup; -2: shape not covered
+// (kSeqMaxGroups, kSeqMaxFeat: route_calls.hpp route_sequential)
 constexpr int kSeqThreads = 256;           // the workgroup: one wave a SIMD, room for prepare_group and the score paths
-constexpr uint32_t kSeqMaxGroups = 8192;   // the groups' scores sit in LDS (32 KiB)
-constexpr int kSeqMaxFeat = 256;           // features whose row values the workgroup stages
 int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
                      uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *order, uint64_t v0, uint64_t v1,
                      uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32, float alpha, float *crp,
@@ -187,8 +187,7 @@ struct ClonePair {
 int launch_chains_clone(hipStream_t stream, const ClonePair *pairs_dev, uint32_t npairs, size_t n_i64, size_t n_f64,
                         size_t nrows);
 
-// kernels_blocked.hip: the blocked Gibbs sampler (msc_blocked_*; blocked.cpp route_blocked chooses the assign kernel)
-enum class BlockedKernel { nich1, staged, global };
+// kernels_blocked.hip: the blocked Gibbs sampler (msc_blocked_*; route_calls.hpp route_blocked chooses the assign kernel)
 int launch_blocked_draw(hipStream_t stream, const BlkFeat *fs_dev, uint32_t nfeat, uint32_t K, uint32_t kpad,
                         const uint32_t *cnt, float alpha, uint64_t seed, uint64_t sweep, double *work, float *tab);
 int launch_blocked_assign(hipStream_t stream, BlockedKernel kernel, uint32_t block, const BlkFeat *fs_dev, int nfeat,
@@ -196,7 +195,7 @@ int launch_blocked_assign(hipStream_t stream, BlockedKernel kernel, uint32_t blo
                           int32_t *z, uint64_t seed, uint64_t sweep);
 int launch_blocked_top_slot(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint32_t *out);
 
-// kernels_splitmerge.hip: the split-merge move (msc_split_merge; blocked.cpp route_splitmerge chooses the assign kernel).
+// kernels_splitmerge.hip: the split-merge move (msc_split_merge; route_calls.hpp route_splitmerge chooses the assign kernel).
 // seed is the caller's: the launchers form the streams' keys (splitmerge_math.hpp).  `zero`: the pair state's additive
 // tables, emptied on the way for the accumulate pass that follows.
 int launch_sm_begin(hipStream_t stream, const int32_t *z, uint64_t nrows, uint64_t row_id0, const uint32_t *cnt, uint32_t K,
@@ -339,7 +338,7 @@ int launch_pred_sample(hipStream_t stream, const PredFeat *pfs_dev, const std::v
                        uint64_t row0, uint64_t nrows, uint64_t row_id0, const int32_t *z, int32_t *z_out,
                        bool masked_only, uint64_t seed, uint64_t sweep);
 
-// kernels_marginal.hip (msc_score_marginal; predict.cpp route_marginal chooses): norm = {log(n + alpha), log(n - 1 + alpha)} on the
+// kernels_marginal.hip (msc_score_marginal; route_calls.hpp route_marginal chooses): norm = {log(n + alpha), log(n - 1 + alpha)} on the
 // device; z null = no leave-one-out; map / logresp null = not wanted
 int launch_marginal_norm(hipStream_t stream, const uint32_t *cnt, uint32_t K, float alpha, double *norm);
 int launch_marginal_nich1(hipStream_t stream, int num_cus, const FeatDesc *feats_dev, uint32_t K, uint32_t kpad, uint64_t row0,
@@ -351,7 +350,8 @@ int launch_marginal_tile(hipStream_t stream, int num_cus, const FeatDesc *feats_
 int launch_row_lse(hipStream_t stream, int num_cus, const float *scores, uint64_t ld, uint32_t K, uint64_t nrows,
                    const int32_t *z, const double *norm, float *logp, int32_t *map, float *logresp);
 
-// kernels_chains_marginal.hip (msc_chains_score_marginal): what differs per chain, and per selected feature
+// kernels_chains_marginal.hip (msc_chains_score_marginal): what differs per chain (per selected feature: MargFeat, and
+// the call's tile plan CmPlan, both of route_calls.hpp plan_chains_marginal)
 struct MargChain {
   const FeatDesc *feats;   // the chain's state: descriptors, group counts, CRP terms
   const uint32_t *cnt;
@@ -360,23 +360,6 @@ struct MargChain {
   float alpha;
   uint32_t pad;
 };
-struct MargFeat {
-  uint32_t f;              // the feature's index in the state
-  uint32_t off;            // first float of its block in the LDS tile; 0xffffffff: its tables are read from global memory
-  uint32_t rows;           // table rows of the block (bb 2, dd dim, gp / bnb vcap, nich 6, noop 0)
-  uint32_t pad;
-};
-constexpr uint32_t kCmTileFloats = 10240;   // 40 KiB of LDS a workgroup: four workgroups of 256 rows a CU
-constexpr uint32_t kCmMinTile = 32;         // a feature is staged only while a tile of this many groups still fits
-struct CmPlan {
-  uint32_t TG = 0;          // groups a tile
-  uint32_t TS = 0;          // floats between two table rows of a tile: TG | 1
-  uint32_t lds_floats = 0;  // the launch's dynamic LDS
-  bool wide = false;        // tiles of whole batches of 32 groups: the wide-batch instantiation
-  bool large = false;       // a selected gp / bnb column may hold counts beyond the exact table: the instantiation with the large-count forms
-};
-// out[nsel]: the plan of the selected features sel[nsel] (ascending state indices); feats_host: the bound descriptors
-CmPlan plan_chains_marginal(const FeatDesc *feats_host, const uint32_t *sel, uint32_t nsel, uint32_t K, MargFeat *out);
 // lw / norm: double [nchains] each, written by the first launch and read by the second
 int launch_chains_marginal_prep(hipStream_t stream, const MargChain *chains_dev, uint32_t nchains, uint32_t K,
                                 const double *logw, double *lw, double *norm);
@@ -388,12 +371,13 @@ int launch_chains_marginal(hipStream_t stream, const MargChain *chains_dev, cons
 // kernels_chains_pred.hip (msc_chains_sample_predictive), after the two launches above have left lw and the chains' rows
 // Lf (float [nchains][ld], through MargChain::logp): the chain of every row (-1: skipped), its group in that chain, its
 // values.  chain / z: int32 [nrows]; outs_dev: one pointer a state feature (null: not drawn), a row's entry at `at` + its
-// offset from row0; large: the instantiation with the large-count forms of gp / bnb (CmPlan::large)
+// offset from row0; large: the instantiation with the large-count forms of gp / bnb (CmPlan::large); batch: the groups a
+// lane sums at a time (route_calls.hpp chains_draw_batch)
 int launch_chains_pick(hipStream_t stream, const double *lw, const float *Lf, uint64_t ld, uint32_t nchains, uint64_t nrows,
                        uint64_t row_id0, uint64_t seed, uint64_t sweep, int32_t *chain);
-int launch_chains_draw(hipStream_t stream, const MargChain *chains_dev, bool large, uint32_t nfeat, uint32_t K, uint32_t kpad,
-                       uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t seed, uint64_t sweep, int32_t *chain,
-                       int32_t *z);
+int launch_chains_draw(hipStream_t stream, const MargChain *chains_dev, bool large, int batch, uint32_t nfeat, uint32_t K,
+                       uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t seed, uint64_t sweep,
+                       int32_t *chain, int32_t *z);
 int launch_chains_values(hipStream_t stream, const MargChain *chains_dev, void *const *outs_dev, bool light, bool heavy,
                          uint32_t nfeat, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t at,
                          const int32_t *chain, const int32_t *z, bool masked_only, uint64_t seed, uint64_t sweep);
@@ -455,7 +439,7 @@ int launch_linkage_prim(hipStream_t stream, const float *z, uint64_t ld, uint32_
 // kernels_distance.hip (msc_partition_distances): partitions are canonicalised a chunk of kPdChunk at a time into 16-bit
 // ids [chunk][ldi] (ldi = m rounded up to 4) and cluster counts k (kPdBad: more than kPdMaxClusters, reported as
 // MSC_DEVERR_DISTANCE_CLUSTERS); the pair kernel then takes a block of a chunk of a against a chunk of b.  A pair's
-// contingency table lives where route_pd_table says -- the one place that picks: in LDS while K_a K_b cells fit, else in
+// contingency table lives where route_pd_table (route_calls.hpp) says -- the one place that picks: in LDS while K_a K_b cells fit, else in
 // the workgroup's slice of a global workspace of kPdSlices x kPdSliceCells u32 (zeroed when allocated; the kernel leaves
 // it zero).  launch_pd_pairs(route) computes the pairs of the block that take `route` and leaves the others alone; the
 // LDS launch also writes -1 / NaN for the pairs of a kPdBad partition.  -2: a shape the launcher does not take
@@ -464,13 +448,8 @@ constexpr uint32_t kPdMaxClusters = kZmRefineMaxClusters;
 constexpr uint32_t kPdBad = 0xFFFFFFFFu;
 constexpr uint32_t kPdChunk = 256;
 constexpr uint32_t kPdTile = 8;                              // b's a work item of the pair kernel takes
-constexpr uint32_t kPdLdsCells = 15u * 1024u;                // 60 KiB of the 64 a workgroup declares; the rest holds the partial sums
 constexpr uint32_t kPdSliceCells = kPdMaxClusters * kPdMaxClusters;
 constexpr uint32_t kPdSlices = 128;
-enum class PdRoute { lds, global };
-__host__ __device__ inline PdRoute route_pd_table(uint32_t ka, uint32_t kb) {
-  return (uint64_t)ka * kb <= kPdLdsCells ? PdRoute::lds : PdRoute::global;
-}
 struct PdPairArgs {
   const uint16_t *ids_a, *ids_b;   // [na][ldi], [nb][ldi]
   uint64_t ldi;
@@ -512,14 +491,7 @@ struct ViSweepArgs {
   uint64_t cells_per_start;
   RefineStart *st;
 };
-// the one place that picks the sweep kernel's instantiation: the 64-id slots a thread keeps sums for in one pass over
-// the samples, 1, 2, 4 or 8 (sixteen would not fit the 128 registers of a thread of sixteen waves: past 512 ids in use
-// the kernel makes two passes)
-inline int route_vi_refine(uint32_t kcap) {
-  int nk = 1;
-  while (nk < 8 && (uint32_t)nk * 64u < kcap) nk *= 2;
-  return nk;
-}
+// (the sweep kernel's instantiation: route_calls.hpp route_vi_refine)
 int bind_error_word_refine_vi(uint32_t *word_dev);
 int launch_vi_canon(hipStream_t stream, const int32_t *lab, uint64_t ld, uint32_t m, uint32_t cap, uint32_t nparts,
                     uint32_t part0, uint16_t *ids, uint64_t ldi, uint32_t *count, RefineStart *st);

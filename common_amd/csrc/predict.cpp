@@ -13,28 +13,7 @@ using namespace msc;
 // row predictive log-density (kernels_marginal.hip): a row's K totals -- what msc_score_value with the prior defines --
 // reduced to their log-sum-exp, arg-max and the arg-max's log responsibility
 // ---------------------------------------------------------------------------
-// Which kernels reduce a state's rows.  By the state and view_rows alone (THE SHARD RULE of route_sweep): the fused
-// kernels and the score kernels add a row's terms in different orders, so a call over a sub-range must take what the
-// whole call takes.
-//   nich1    a single nich feature (masked or not) up to 1024 groups: k_marginal_nich1, the own-group values computed inside
-//   tile     scalar features within the tables (no niw, no dm, no count beyond a table), K <= 256, a view of at least
-//            kTailMinRows rows (fewer rows do not fill the chip with 128-row workgroups: the score pass has shapes for
-//            them), on plans whose SCORE pass is the plain tile kernel too (tile_path == MSC_PATH_TILE): k_loo_own, then
-//            k_marginal_tile over the fused plan.  A plan with kernels of its own (role-split, nich-only, lookups-only)
-//            goes the generic way: its score pass plus k_row_lse beats the plain tile form (C3, 10^6 x 256: DESIGN.md 6g)
-//            until a fused form of those kernels exists.  MSC_MARGINAL_TILE=1 / 0 sends every such plan / none to the tile
-//            kernel (how the two were measured against each other).
-//   generic  everything else: run_score (leave-one-out + prior) into the scratch chunk, then k_row_lse over it
-enum class MarginalKind { nich1, tile, generic };
-static MarginalKind route_marginal(const msc_state *st) {
-  if (!sweep_plain(st)) return MarginalKind::generic;
-  if (st->nich1) return st->K <= 1024 ? MarginalKind::nich1 : MarginalKind::generic;
-  if (!st->has_dm && st->K <= 256 && view_rows(st) >= kTailMinRows) {
-    const int forced = read_switches().marginal_tile;
-    if (forced >= 0 ? forced != 0 : st->plan.tile_path == MSC_PATH_TILE) return MarginalKind::tile;
-  }
-  return MarginalKind::generic;
-}
+// (Which kernels reduce a state's rows: route_calls.hpp route_marginal, by the state and the view's rows alone.)
 
 extern "C" int msc_score_marginal(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                                   const int32_t *z_dev, uint32_t flags, float *logp_dev, int32_t *map_dev,
@@ -52,7 +31,7 @@ extern "C" int msc_score_marginal(msc_state *st, const msc_dataview *view, const
   const int cus = st->ctx->num_cus;
   MSC_HIP(grow_retained(st->retired, st->marg_norm, 2));
   MSC_TRY(launch_marginal_norm(s, st->cnt_u32, st->K, st->alpha, st->marg_norm));
-  switch (route_marginal(st)) {                           // (the launchers report their own failures)
+  switch (route_marginal(route_facts_now(st), read_switches())) {                        // (the launchers report their own failures)
     case MarginalKind::nich1:
       return launch_marginal_nich1(s, cus, st->desc_dev, st->K, st->kpad, row0, nrows, z_dev, st->logpc, st->marg_norm, logp_dev,
                                    map_dev, map_logresp_dev);
@@ -62,10 +41,9 @@ extern "C" int msc_score_marginal(msc_state *st, const msc_dataview *view, const
       return launch_marginal_tile(s, cus, st->desc_fuse_dev, (int)st->plan.fuse_nfeat, (int)st->plan.fuse_split, st->K, st->kpad, row0, nrows,
                                   z_dev, st->own, st->logpc, st->marg_norm, logp_dev, map_dev, map_logresp_dev);
     case MarginalKind::generic: {
-      // (the chunk of SweepKind::generic: rows of K rounded up to 64 floats; the scratch is the state's and stays with it,
-      // grown to what the largest call asked for, at most 4 GiB of scores)
-      const uint64_t ld = std::min<uint64_t>(st->kpad, ((uint64_t)st->K + 63) & ~63ull);
-      const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((4096ull << 20) / (ld * sizeof(float)), nrows));
+      // (the chunk of SweepKind::generic; the scratch is the state's and stays with it, grown to what the largest call
+      // asked for)
+      const auto [ld, chunk] = score_chunk(st->K, st->kpad, nrows);
       MSC_HIP(grow_retained(st->retired, st->scratch, chunk * ld));
       for (uint64_t at = 0; at < nrows; at += chunk) {
         const uint64_t n = std::min<uint64_t>(chunk, nrows - at);

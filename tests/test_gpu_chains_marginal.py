@@ -53,8 +53,9 @@ _cache = {}
 
 
 def slice_cut(nchains, view_rows):
-    """(chains a slice, slices) of a call: route_chains_marginal (common_amd/csrc/chains.cpp) and the launcher's cut,
-    restated -- a view below four workgroups of 256 rows a compute unit is filled up with slices, at most one a chain"""
+    """(chains a slice, slices) of a call: route_chains_marginal (common_amd/csrc/route_calls.hpp, held to its rule by
+    tests/cxx/test_route_calls.cpp) and the launcher's cut, restated for the device the suite runs on -- a view below four
+    workgroups of 256 rows a compute unit is filled up with slices, at most one a chain"""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     blocks, want = max(1, -(-view_rows // 256)), 4 * max(1, cus)
     slices = 1 if blocks >= want else min(nchains, 1024, -(-want // blocks))

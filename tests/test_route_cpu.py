@@ -33,3 +33,16 @@ def test_routes_read_no_state():
     for rule in ("narrow_lanes", "sweep_rows_pays", "sweep_pair_mode", "pair_path", "sweep_is_niw1"):
         assert not re.search(r"\b%s\(" % rule, abi), rule
     assert len(re.findall(r"\broute_sweep\(", abi)) == 1 and len(re.findall(r"\broute_score\(", abi)) == 2
+    # ... and so are the routes of every other call (route_calls.hpp): the units and the kernel files hold none
+    def code_of(name):
+        return "\n".join(ln.split("//")[0] for ln in open(os.path.join(CSRC, name)).read().splitlines())
+    calls = code_of("route_calls.hpp")
+    for word in ("msc_state", "msc_context", "msc_chains", "getenv", "hip"):
+        assert word not in calls, word
+    for unit in ("blocked.cpp", "predict.cpp", "chains.cpp"):
+        assert not re.search(r"static\s+\w[\w:<> ]*\s+route_\w+\(", code_of(unit)), unit
+    for name in sorted(os.listdir(CSRC)):
+        if name.startswith("kernels_") and name.endswith(".hip"):
+            assert not re.search(r"\bplan_chains_marginal\([^;{]*\)\s*\{", code_of(name)), name
+            assert not re.search(r"^[\w:<>&\* ]+\bplan_\w+\([^;{]*\)\s*\{", code_of(name), re.M), name
+    assert not re.search(r"^[\w:<>&\* ]*\broute_\w+\([^;{]*\)\s*\{", code_of("launchers.hpp"), re.M)
