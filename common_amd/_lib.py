@@ -147,6 +147,12 @@ _SIGS = {
     "msc_chains_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                    C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64,
                                    C.c_uint32, C.c_void_p, C.c_void_p]),
+    # (ch, view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, nsweeps, host_seeds, sweep, beta_dev,
+    #  trace_every, trace_dev, occupied_dev)
+    "msc_chains_sweep_tempered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                            C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                            C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                            C.c_void_p]),
     # (ch, joint_dev, ld_joint, nrungs, beta_dev, rung_dev, parity, seed, sweep, proposed_dev, accepted_dev)
     "msc_chains_exchange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -12,6 +12,7 @@ import torch
 from . import _args as A
 from . import _lib as L
 from . import smc as S
+from . import tempering as T
 from .runtime import _I32_U32, State
 
 _U64 = (1 << 64) - 1
@@ -143,14 +144,20 @@ class ChainEnsemble(object):
 
     # the sweep ----------------------------------------------------------------
     def sweep(self, view, nsweeps, seed, sweep=0, order=None, trace_every=None, zmatrix=None, want_occupied=False, row0=0,
-              nrows=None, row_id0=None, cols=None):
+              nrows=None, row_id0=None, cols=None, beta=None):
         """nsweeps sequential sweeps of every chain over rows [row0, row0 + nrows) (msc_chains_sweep; asynchronous).
         seed: an int (chain c takes seed + c) or nchains ints; sweep: the counter's sweep index of the first sweep.
         order: uint32 / int32 device tensor [nrows] (all chains) or [nchains, nrows] of offsets from row0.
         trace_every = e: -> the int32 device tensor [nchains, nsweeps // e, nrows] holding z of the row range after every
         e-th sweep; with want_occupied -> (trace, occupied), occupied int32 [nchains, nsweeps // e] the groups in use at
         those moments.  zmatrix: a ZMatrix over the nrows rows that takes the whole trace in one add (trace_every
-        defaults to 1 then).  Without any of the three -> None."""
+        defaults to 1 then).  Without any of the three -> None.
+        beta: None, exactly the call above; otherwise every chain is swept at its own temperature
+        (msc_chains_sweep_tempered; asynchronous too): a float32 device tensor [nchains], read on the device when the
+        sweep runs -- what exchange() swapped in it is what the sweep sees -- or a float or nchains floats, made into
+        one.  Chain c targets p(z | alpha) p(X | z, hp)^beta[c]; at beta = 1 every bit is the untempered call's, at
+        beta = 0 no feature is read (from seat(): a draw from the CRP prior).  A NaN, negative or infinite entry stops
+        its chain for the call and raises MicroscopesHipError at the next one."""
         self._check_open()
         if self.z is None:
             raise ValueError("no assignment yet: call assign() or seat() first")
@@ -162,6 +169,10 @@ class ChainEnsemble(object):
         if not 0 <= nsweeps < (1 << 32):
             raise ValueError("nsweeps must be in [0, 2^32)")
         seeds = chain_seeds(seed, self.nchains)
+        bp = None
+        if beta is not None:
+            beta = self._beta(beta)                  # (kept alive until the call is made)
+            bp = A.ptr(beta)
         op, ld_order = None, 0
         if order is not None:
             op, ld_order = A.flat(order, _I32_U32, n, dev, "order"), (n if order.dim() == 2 else 0)
@@ -180,17 +191,36 @@ class ChainEnsemble(object):
         for st in self.states:
             st._drop_subsets()
             st._bound_view = view        # (the library keeps no reference to a view: the states do, for the last one bound)
-        L.check(self.ctx.lib.msc_chains_sweep(
-            self._h, view._h, self.states[0]._cols(cols), row0, n, row0 if row_id0 is None else int(row_id0),
-            self._z_at(row0), int(self.z.stride(0)), op, ld_order, nsweeps, (C.c_uint64 * self.nchains)(*seeds), int(sweep),
-            0 if trace_every is None else int(trace_every),
-            A.ptr(trace) if trace is not None and trace.numel() else None,
-            A.ptr(occupied) if occupied is not None and occupied.numel() else None))
+        head = (self._h, view._h, self.states[0]._cols(cols), row0, n, row0 if row_id0 is None else int(row_id0),
+                self._z_at(row0), int(self.z.stride(0)), op, ld_order, nsweeps, (C.c_uint64 * self.nchains)(*seeds), int(sweep))
+        tail = (0 if trace_every is None else int(trace_every),
+                A.ptr(trace) if trace is not None and trace.numel() else None,
+                A.ptr(occupied) if occupied is not None and occupied.numel() else None)
+        if bp is None:
+            L.check(self.ctx.lib.msc_chains_sweep(*(head + tail)))
+        else:
+            L.check(self.ctx.lib.msc_chains_sweep_tempered(*(head + (bp,) + tail)))
         if zmatrix is not None and trace.shape[1] > 0:
             zmatrix.add(trace.view(-1, n))
         if trace is None:
             return None
         return (trace, occupied) if want_occupied else trace
+
+    def _beta(self, beta):
+        """the temperatures of a tempered sweep as a float32 device tensor [nchains]: such a tensor as it is, or one made
+        from a float (all chains) or nchains floats"""
+        dev = self.ctx.torch_device
+        if isinstance(beta, torch.Tensor):
+            if tuple(beta.shape) != (self.nchains,):
+                raise ValueError("beta must hold nchains = %d temperatures (got shape %s)" % (self.nchains, tuple(beta.shape)))
+            A.flat(beta, torch.float32, self.nchains, dev, "beta")
+            return beta
+        b = np.asarray(beta, dtype=np.float32)
+        if b.ndim == 0:
+            b = np.full(self.nchains, b, dtype=np.float32)
+        if b.shape != (self.nchains,):
+            raise ValueError("beta must be one float or nchains = %d floats (got shape %s)" % (self.nchains, b.shape))
+        return torch.from_numpy(b).to(dev)
 
     # part of a sweep, with the visits' log predictives --------------------------
     def _order(self, order, n):
@@ -504,6 +534,125 @@ class ChainEnsemble(object):
         truncated = bool((seen[:, 1:].sum(1) >= self.K).any().item()) if n else False
         return S.SMCResult(log_evidence=log_evidence, log_weights=logw, weights=S.normalised_weights(logw), ess=ess_list,
                            resampled_at=resampled_at, ancestors=ancestors, truncated=truncated)
+
+    # tempered chains: the drivers ---------------------------------------------------------
+    def run_tempered(self, view, niters, seed, betas, sweep=0, order=None, trace_every=None, zmatrix=None, state=None):
+        """niters iterations of replica exchange (parallel tempering) -> tempering.TemperedResult.
+
+        betas: the ladder of R temperatures, rung 0 first (tempering.ladder gives such ladders; betas[0] = 1 makes rung 0
+        the posterior); nchains must be a multiple of R.  Ladder l owns chains [l R, (l + 1) R) and chain l R + j starts on
+        rung j; with state=an earlier TemperedResult the run continues from copies of its beta, rung, proposed and
+        accepted (give it the sweep counter the earlier run ended at).  Iteration i, with counter s = sweep + i, is
+        exactly these calls in this order, so exactly what they give made by hand:
+          self.sweep(view, 1, seed, sweep=s, order=order, beta=beta)
+          self.score_joint(out=joint)
+          when (i + 1) % trace_every == 0: device copies of ens.z and rung into the next sample of trace and rungs --
+              after the sweep and BEFORE the exchange, so a sample belongs to the rung its chain was swept at
+          self.exchange(joint, beta, rung, R, parity=s, seed=tempering.exchange_key(seed), sweep=s,
+                        counters=(proposed, accepted))
+        The loop makes no host synchronisation.  trace_every None: no trace (1 when a zmatrix is given).  zmatrix: a ZMatrix
+        over the view's rows that takes tempering.cold_samples(trace, rungs) -- the samples taken on rung 0 -- in one add
+        after the loop.
+        There is no hyper-parameter step and no split-merge here: as built both take the likelihood at full weight, so
+        neither leaves pi_beta invariant.  The swap rule compares the chains' likelihoods under ONE model: all chains of a
+        ladder must share hyper-parameters and alpha -- which hp_slice() (and run() with an hp step) ends: every chain
+        then holds its own; set them equal again first."""
+        self._check_open()
+        if self.z is None:
+            raise ValueError("no assignment yet: call assign() or seat() first")
+        niters, n = int(niters), int(view.nrows)
+        if niters < 0:
+            raise ValueError("niters must be >= 0")
+        ladder = np.asarray(betas, dtype=np.float32).ravel()
+        R = int(ladder.size)
+        if R < 1 or self.nchains % R:
+            raise ValueError("nchains = %d is no whole number of ladders of %d rungs" % (self.nchains, R))
+        if state is not None and not isinstance(state, T.TemperedResult):
+            raise ValueError("state must be a TemperedResult of an earlier run_tempered")
+        if zmatrix is not None and trace_every is None:
+            trace_every = 1
+        dev, nl = self.ctx.torch_device, self.nchains // R
+        trace = rungs = None
+        if trace_every is not None:
+            shape = trace_shape(niters, trace_every, self.nchains, n)
+            if zmatrix is not None and (zmatrix.n != n or zmatrix.ctx is not self.ctx):
+                raise ValueError("zmatrix must be over the %d rows of the view, on the ensemble's context" % n)
+            trace = torch.empty(shape, dtype=torch.int32, device=dev)
+            rungs = torch.empty(shape[:2], dtype=torch.int32, device=dev)
+        if state is None:
+            beta = torch.from_numpy(np.tile(ladder, nl)).to(dev)
+            rung = torch.arange(R, dtype=torch.int32).repeat(nl).to(dev)
+            proposed = torch.zeros((nl, R - 1), dtype=torch.int32, device=dev)
+            accepted = torch.zeros((nl, R - 1), dtype=torch.int32, device=dev)
+        else:
+            beta, rung, proposed, accepted = (t.clone() for t in (state.beta, state.rung, state.proposed, state.accepted))
+            if tuple(beta.shape) != (self.nchains,) or tuple(rung.shape) != (self.nchains,) or \
+                    tuple(proposed.shape) != (nl, R - 1) or tuple(accepted.shape) != (nl, R - 1):
+                raise ValueError("state is not that of %d ladders of %d rungs" % (nl, R))
+        joint = torch.empty((self.nchains, len(self.features) + 3), dtype=torch.float64, device=dev)
+        key = T.exchange_key(seed)
+        for i in range(niters):
+            s = sweep + i
+            self.sweep(view, 1, seed, sweep=s, order=order, beta=beta)
+            self.score_joint(out=joint)
+            if trace is not None and (i + 1) % trace_every == 0:
+                trace[:, (i + 1) // trace_every - 1, :].copy_(self.z)
+                rungs[:, (i + 1) // trace_every - 1].copy_(rung)
+            self.exchange(joint, beta, rung, R, parity=s, seed=key, sweep=s, counters=(proposed, accepted))
+        if zmatrix is not None and trace.shape[1] > 0:
+            cold = T.cold_samples(trace, rungs)
+            if cold.shape[0] > 0:
+                zmatrix.add(cold)
+        return T.TemperedResult(trace=trace, rungs=rungs, beta=beta, rung=rung, proposed=proposed, accepted=accepted,
+                                joint=joint)
+
+    def ais(self, view, betas, seed, sweeps_per_temp=1, order=None, sweep=0):
+        """Annealed importance sampling (Neal 2001), the chains as independent runs -> tempering.AISResult, whose
+        log_evidence estimates log p(X | hp, alpha) -- a second unbiased estimator beside smc().
+
+        betas: a non-decreasing host array of T temperatures with betas[0] == 0 and betas[-1] == 1 (as float32, what the
+        device sees); anything else is a ValueError before the device is touched.  The steps: seat(view), which zeroes
+        ens.logw; one sweep at beta = 0 with counter `sweep`, a draw from the CRP prior; then for t = 1 .. T - 1
+        score_joint, anneal_weights(joint, betas[t - 1], betas[t]) and sweeps_per_temp sweeps at betas[t], the counters
+        running on from sweep + 1.  One synchronisation, at the end, brings ens.logw to the host; log_evidence =
+        smc.log_mean_exp(logw).  exp(log_evidence) is unbiased provided all chains share hyper-parameters and alpha (see
+        smc()).
+        result.truncated: True when some chain had all ngroups slots occupied at the END of some sweep (the occupied
+        counts of sweep(want_occupied=True), reduced on the device): a new group may have been refused there, and the
+        estimate is for the mixture truncated to ngroups slots.  It is an end-of-sweep check: a chain that filled every
+        slot within a sweep and emptied one again before its end is not seen."""
+        b = T.ais_betas(betas)
+        self._check_open()
+        spt = int(sweeps_per_temp)
+        if spt < 0:
+            raise ValueError("sweeps_per_temp must be >= 0")
+        seeds = chain_seeds(seed, self.nchains)
+        dev = self.ctx.torch_device
+        self.seat(view)
+        joint = torch.empty((self.nchains, len(self.features) + 3), dtype=torch.float64, device=dev)
+        full = torch.zeros((), dtype=torch.bool, device=dev)
+        counter = [int(sweep)]
+
+        def at(value):
+            return torch.full((self.nchains,), float(value), dtype=torch.float32, device=dev)
+
+        def one_sweep(beta):
+            _, occupied = self.sweep(view, 1, seeds, sweep=counter[0], order=order, want_occupied=True, beta=beta)
+            if occupied.numel() and int(view.nrows):          # (no row, no visit: nothing was written)
+                full.logical_or_((occupied >= self.K).any())
+            counter[0] += 1
+
+        one_sweep(at(b[0]))
+        for t in range(1, len(b)):
+            self.score_joint(out=joint)
+            now = at(b[t])
+            self.anneal_weights(joint, at(b[t - 1]), now)
+            for _ in range(spt):
+                one_sweep(now)
+        down = torch.cat([self.logw, full.to(torch.float64).reshape(1)]).cpu().numpy()      # the one synchronisation
+        logw, truncated = down[:-1].copy(), bool(down[-1] != 0.0)
+        return T.AISResult(log_evidence=S.log_mean_exp(logw), log_weights=logw, weights=S.normalised_weights(logw),
+                           ess=S.ess(logw), truncated=truncated)
 
     # the posterior-averaged row predictive density ---------------------------------
     def _feature_list(self, what, feats):

@@ -105,7 +105,8 @@ int msc::device_error_check(msc_context *ctx) {
   if (code & 64u) add("msc_partition_distances: a partition with more than 1024 clusters (every output it takes part in is -1 or NaN; detail: its index in its set)");
   if (code & 128u) add("msc_partition_refine_vi: a sample with more than 1024 clusters or a start with more than max_clusters (its outputs mean nothing; detail: its index)");
   if (code & 256u) add("msc_chains_exchange: rungs that are no permutation within a ladder (it was left as it was; detail: ladder)");
-  if (code & ~511u) add("unknown device-side error");
+  if (code & 512u) add("msc_chains_sweep_tempered: a chain's temperature is NaN, negative or infinite (the chain made no visit; detail: chain)");
+  if (code & ~1023u) add("unknown device-side error");
   return fail(MSC_EDEVICE, "reported by an earlier kernel on device %d: %s [detail of the first: %u]; rebuild the affected state's tables",
               ctx->device, what.c_str(), detail);
 }

@@ -1,5 +1,5 @@
 // chains.cpp -- the sequential collapsed Gibbs sweep and the ensembles of such chains (kernels_seq.hip):
-// msc_sweep_sequential and msc_chains_*, the exchange of temperatures and the annealing weights (kernels_temper.hip), the
+// msc_sweep_sequential and msc_chains_*, the sweep at a temperature, the exchange of temperatures and the annealing weights (kernels_temper.hip), the
 // ensemble's row predictive density (kernels_chains_marginal.hip), its
 // posterior predictive draws (kernels_chains_pred.hip) and its split-merge proposals (kernels_chains_sm.hip) among them.
 // Host logic only; the core it stands on is abi.cpp, through abi_internal.hpp.
@@ -171,8 +171,10 @@ extern "C" int msc_chains_size(const msc_chains *ch, uint32_t *nchains) {
   return MSC_OK;
 }
 
-// What msc_chains_sweep and msc_chains_visit share: visits [v0, v1) of a call's nsweeps x nrows for every chain (visit v is
-// sweep v / nrows, position v % nrows of the order), with the outputs each of the two has (null: not wanted).
+// What msc_chains_sweep, msc_chains_sweep_tempered and msc_chains_visit share: visits [v0, v1) of a call's nsweeps x nrows
+// for every chain (visit v is sweep v / nrows, position v % nrows of the order), with the outputs each has (null: not
+// wanted).  beta_dev (msc_chains_sweep_tempered; else null): the chains' temperatures on the device, handed to the
+// kernel as they lie -- never read or uploaded here, so what msc_chains_exchange swapped is what the launch reads.
 struct ChainsOutputs {
   uint32_t trace_every = 1;           // >= 1
   uint64_t ntrace = 0;                // samples per chain of trace / occupied
@@ -185,8 +187,9 @@ struct ChainsOutputs {
 static int chains_visits_impl(msc_chains *ch, const char *who, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
                               uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev,
                               uint64_t ld_order, uint64_t v0, uint64_t v1, const uint64_t *host_seeds, uint64_t sweep,
-                              const ChainsOutputs &out) {
+                              const ChainsOutputs &out, const float *beta_dev = nullptr) {
   const uint32_t n = (uint32_t)ch->states.size();
+  const char *kernel = beta_dev ? "k_sweep_seq_chains_tempered" : "k_sweep_seq_chains";
   MSC_REQUIRE((z_dev && host_seeds) || v0 >= v1, "null argument");
   MSC_REQUIRE(nrows < (1ull << 32), "the sequential sweep takes at most 2^32 - 1 rows per call");
   MSC_REQUIRE(ld_z >= nrows, "%s: ld_z %llu < nrows %llu", who, (unsigned long long)ld_z, (unsigned long long)nrows);
@@ -223,10 +226,12 @@ static int chains_visits_impl(msc_chains *ch, const char *who, const msc_datavie
   const uint64_t per_launch = units_per_launch(n, ch->ctx->num_cus, visit_us);
   for (uint64_t w0 = v0; w0 < v1; w0 += per_launch) {
     const uint64_t w1 = std::min(v1, w0 + per_launch);
-    const int rc = launch_sweep_seq_chains(s, ch->table<SeqChain>(), n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows,
-                                           row_id0, w0, w1, sweep, out.trace_every);
-    if (rc == -2) return fail(MSC_EUNSUPPORTED, "k_sweep_seq_chains does not take this shape");
-    if (rc) return fail(MSC_EHIP, "k_sweep_seq_chains launch failed: %s", hipGetErrorString(hipGetLastError()));
+    const int rc = beta_dev ? launch_sweep_seq_chains_tempered(s, ch->table<SeqChain>(), beta_dev, n, (int)st0->nfeat, st0->K,
+                                                               st0->kpad, row0, nrows, row_id0, w0, w1, sweep, out.trace_every)
+                            : launch_sweep_seq_chains(s, ch->table<SeqChain>(), n, (int)st0->nfeat, st0->K, st0->kpad, row0, nrows,
+                                                      row_id0, w0, w1, sweep, out.trace_every);
+    if (rc == -2) return fail(MSC_EUNSUPPORTED, "%s does not take this shape", kernel);
+    if (rc) return fail(MSC_EHIP, "%s launch failed: %s", kernel, hipGetErrorString(hipGetLastError()));
   }
   // the kernel kept every table of every member current: additive sums, fields, constants, counts and CRP terms
   for (msc_state *st : ch->states) st->valid.kept_current();
@@ -248,6 +253,29 @@ extern "C" int msc_chains_sweep(msc_chains *ch, const msc_dataview *view, const 
   out.occupied = occupied_dev;
   return chains_visits_impl(ch, "msc_chains_sweep", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order, 0,
                             (uint64_t)nsweeps * nrows, host_seeds, sweep, out);
+}
+
+// msc_chains_sweep with every chain at its own temperature: the same prologue, table and launch slicing; the kernel is
+// k_sweep_seq_chains_tempered, which reads beta_dev[c] on the device at every launch.  No wait, no upload of beta.
+extern "C" int msc_chains_sweep_tempered(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0,
+                                         uint64_t nrows, uint64_t row_id0, int32_t *z_dev, uint64_t ld_z,
+                                         const uint32_t *order_dev, uint64_t ld_order, uint32_t nsweeps,
+                                         const uint64_t *host_seeds, uint64_t sweep, const float *beta_dev, uint32_t trace_every,
+                                         int32_t *trace_dev, uint32_t *occupied_dev) {
+  MSC_REQUIRE(ch && view, "null argument");
+  if (ch->states.empty()) return MSC_OK;
+  const uint64_t visits = (uint64_t)nsweeps * nrows;
+  MSC_REQUIRE(beta_dev || visits == 0, "msc_chains_sweep_tempered: beta_dev is null");
+  const bool tracing = trace_dev != nullptr || occupied_dev != nullptr;
+  MSC_REQUIRE(!tracing || trace_every >= 1, "msc_chains_sweep_tempered: trace_every must be >= 1 with a trace or an occupied "
+                                            "array");
+  ChainsOutputs out;
+  out.trace_every = tracing ? trace_every : 1u;
+  out.ntrace = tracing ? nsweeps / trace_every : 0;
+  out.trace = trace_dev;
+  out.occupied = occupied_dev;
+  return chains_visits_impl(ch, "msc_chains_sweep_tempered", view, cols, row0, nrows, row_id0, z_dev, ld_z, order_dev, ld_order,
+                            0, visits, host_seeds, sweep, out, beta_dev);
 }
 
 extern "C" int msc_chains_visit(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,

@@ -21,6 +21,7 @@ enum : uint32_t {
   MSC_DEVERR_DISTANCE_CLUSTERS = 64u, // k_pd_canon: a partition with more than 1024 clusters (its outputs are -1 / NaN); detail = its index in its set
   MSC_DEVERR_VI_CLUSTERS = 128u,     // k_vi_canon: a sample with more than 1024 clusters or a start with more than max_clusters (it is not refined); detail = its index
   MSC_DEVERR_TEMPER = 256u,          // k_chains_exchange: rungs that are no permutation within a ladder (it is left as it was; detail = ladder)
+  MSC_DEVERR_TEMPER_BETA = 512u,     // k_sweep_seq_chains_tempered: a chain's temperature is NaN, negative or infinite (the chain makes no visit; detail = chain)
 };
 
 static __device__ uint32_t *g_dev_error = nullptr;

@@ -19,6 +19,10 @@
 //                 is a SeqChain entry of a device table; also a thinned trace and the occupied-slot count per sample.
 //                 Two nullable outputs per chain (msc_chains_visit): the visit's log predictive m + log(total) - log(n +
 //                 alpha) of the draw's own block max and sum, by order position, and its running sum in double.
+//   k_sweep_seq_chains_tempered   the same grid with chain c at its own temperature beta[c] (msc_chains_sweep_tempered):
+//                 a slot's score is log pseudocount + beta * (the features' sum), each slice partial going on by one fused
+//                 multiply-add in the place of the add (temper_math.hpp); beta == 0 reads no feature table.  A second
+//                 instantiation of the workgroup's function: the two kernels above keep their code.
 //   k_chains_clone   copies the additive tables and the z row of a source chain onto a destination, for a table of pairs
 //                 (msc_chains_clone): words as they are, so a clone holds its ancestor's bits.
 #include "commit_ops.hpp"
@@ -27,6 +31,7 @@
 #include "launchers.hpp"
 #include "score_block.hpp"
 #include "seq_score.hpp"
+#include "temper_math.hpp"
 
 namespace msc {
 
@@ -158,11 +163,16 @@ static __device__ unsigned long long g_seq_phase[6];
 // row itself not among them; -inf when total == 0 or m == -inf).  visit_logp[pos] = (float)inc; *logw += inc, visit by
 // visit in visit order by thread 0, in a register between the launch's first and last visit: the same adds however the
 // visits are cut into launches.  Neither changes a draw: with both null the visit is as it was.
+// kTempered (k_sweep_seq_chains_tempered; beta finite and >= 0, else unused): the slices' partials go on as
+// temper::tempered_add(beta, partial, sk); at beta == 0 the score phase reads no feature table and adds no partial -- the
+// slot's score is the CRP term's hi + lo -- while read, leave and join are as ever.  With kTempered false no line differs.
+template <bool kTempered>
 MSC_DEV void seq_visits(SeqShared &sh, const FeatDesc *__restrict__ feats, int nfeat, uint32_t K, uint32_t kpad,
                         uint64_t row0, uint64_t nrows, uint64_t row_id0, int32_t *z, const uint32_t *__restrict__ order,
                         uint64_t v0, uint64_t v1, uint64_t seed, uint64_t sweep, long long *cnt_acc, uint32_t *cnt_u32,
                         float alpha, float *crp, int32_t *trace, uint32_t trace_every, uint32_t *occupied, double *logw,
-                        float *visit_logp) {
+                        float *visit_logp, float beta) {
+  const bool prior_only = kTempered && beta == 0.f;        // (-0.0f too)
   const uint32_t t = threadIdx.x, nt = kSeqThreads, lane = t & 63u, wave = t >> 6, nw = kSeqThreads / 64;
   if (t == 0) sh.nempty = sh.n = 0;
   __syncthreads();
@@ -212,7 +222,8 @@ MSC_DEV void seq_visits(SeqShared &sh, const FeatDesc *__restrict__ feats, int n
         if (ph == 1) {
           SEQ_STAMP(1);
           // ---- score: feature sums ----
-          if (nq > 1) {
+          if (prior_only) {                              // (beta == 0: no feature table is read, sh.sc holds no partial)
+          } else if (nq > 1) {
             if (q < nq) {
               float acc = 0.f;
               for (uint32_t f = q; f < (uint32_t)nfeat; f += nq) {
@@ -243,7 +254,11 @@ MSC_DEV void seq_visits(SeqShared &sh, const FeatDesc *__restrict__ feats, int n
           for (uint32_t k = kb; k < kb + chunk && k < K; k++) {
             const bool used = cnt_u32[k] != 0u;
             float sk = used ? crp[k] : e_hi;
-            for (uint32_t j = 0; j < nq; j++) sk += sh.sc[j * K + k];
+            if (!kTempered) {
+              for (uint32_t j = 0; j < nq; j++) sk += sh.sc[j * K + k];
+            } else if (!prior_only) {
+              for (uint32_t j = 0; j < nq; j++) sk = temper::tempered_add(beta, sh.sc[j * K + k], sk);
+            }
             sk += used ? lo0[k] : e_lo;
             sh.sc[k] = sk;
             m = fmaxf(m, sk);
@@ -316,8 +331,8 @@ __global__ __launch_bounds__(kSeqThreads) void k_sweep_seq(const FeatDesc *__res
                                                            uint64_t v1, uint64_t seed, uint64_t sweep, long long *cnt_acc,
                                                            uint32_t *cnt_u32, float alpha, float *crp, int32_t *trace) {
   __shared__ SeqShared sh;
-  seq_visits(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp,
-             trace, 1u, nullptr, nullptr, nullptr);
+  seq_visits<false>(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha,
+                    crp, trace, 1u, nullptr, nullptr, nullptr, 1.f);
 }
 
 // the same visits of gridDim.x independent chains (msc_chains_sweep): workgroup c carries chain c, whose state, z, order,
@@ -338,8 +353,36 @@ __global__ __launch_bounds__(kSeqThreads) void k_sweep_seq_chains(const SeqChain
   const uint64_t seed = c.seed;
   double *logw = c.logw;
   float *visit_logp = c.visit_logp;
-  seq_visits(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha, crp,
-             trace, trace_every, occupied, logw, visit_logp);
+  seq_visits<false>(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha,
+                    crp, trace, trace_every, occupied, logw, visit_logp, 1.f);
+}
+
+// k_sweep_seq_chains with chain c at the temperature beta[c], read here once per launch (msc_chains_sweep_tempered; the
+// entries' logw and visit_logp are not read: a tempered visit has no weight).  A beta that is none -- NaN, negative,
+// infinite -- is reported with the chain as its detail and the chain's workgroup makes no visit: it writes no sample and
+// changes neither z nor a table; the other chains run as usual.
+__global__ __launch_bounds__(kSeqThreads) void k_sweep_seq_chains_tempered(const SeqChain *__restrict__ chains,
+                                                                           const float *__restrict__ beta_dev, int nfeat,
+                                                                           uint32_t K, uint32_t kpad, uint64_t row0,
+                                                                           uint64_t nrows, uint64_t row_id0, uint64_t v0,
+                                                                           uint64_t v1, uint64_t sweep, uint32_t trace_every) {
+  __shared__ SeqShared sh;
+  const float beta = beta_dev[blockIdx.x];
+  if (!temper::beta_ok(beta)) {                          // (uniform: the whole block leaves)
+    if (threadIdx.x == 0) report_device_error(MSC_DEVERR_TEMPER_BETA, blockIdx.x);
+    return;
+  }
+  const SeqChain &c = chains[blockIdx.x];
+  const FeatDesc *feats = c.feats;
+  int32_t *z = c.z, *trace = c.trace;
+  long long *cnt_acc = c.cnt_acc;
+  uint32_t *cnt_u32 = c.cnt_u32, *occupied = c.occupied;
+  float *crp = c.crp;
+  const uint32_t *order = c.order;
+  const float alpha = c.alpha;
+  const uint64_t seed = c.seed;
+  seq_visits<true>(sh, feats, nfeat, K, kpad, row0, nrows, row_id0, z, order, v0, v1, seed, sweep, cnt_acc, cnt_u32, alpha,
+                   crp, trace, trace_every, occupied, nullptr, nullptr, beta);
 }
 
 int launch_sweep_seq(hipStream_t stream, const FeatDesc *feats_dev, int nfeat, uint32_t K, uint32_t kpad, uint64_t row0,
@@ -358,6 +401,17 @@ int launch_sweep_seq_chains(hipStream_t stream, const SeqChain *chains_dev, uint
   if (nfeat < 0 || nfeat > kSeqMaxFeat || K == 0 || K > kSeqMaxGroups || nchains == 0 || trace_every == 0) return -2;
   hipLaunchKernelGGL(k_sweep_seq_chains, dim3(nchains), dim3(kSeqThreads), 0, stream, chains_dev, nfeat, K, kpad, row0,
                      nrows, row_id0, v0, v1, sweep, trace_every);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_sweep_seq_chains_tempered(hipStream_t stream, const SeqChain *chains_dev, const float *beta_dev, uint32_t nchains,
+                                     int nfeat, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
+                                     uint64_t v0, uint64_t v1, uint64_t sweep, uint32_t trace_every) {
+  if (nfeat < 0 || nfeat > kSeqMaxFeat || K == 0 || K > kSeqMaxGroups || nchains == 0 || trace_every == 0 ||
+      beta_dev == nullptr)
+    return -2;
+  hipLaunchKernelGGL(k_sweep_seq_chains_tempered, dim3(nchains), dim3(kSeqThreads), 0, stream, chains_dev, beta_dev, nfeat, K,
+                     kpad, row0, nrows, row_id0, v0, v1, sweep, trace_every);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -174,6 +174,11 @@ struct SeqChain {
 int launch_sweep_seq_chains(hipStream_t stream, const SeqChain *chains_dev, uint32_t nchains, int nfeat, uint32_t K,
                             uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0, uint64_t v0, uint64_t v1,
                             uint64_t sweep, uint32_t trace_every);
+// ... with chain c at the temperature beta_dev[c] (msc_chains_sweep_tempered): float [nchains] on the device, read by the
+// kernel once per launch; the entries' logw and visit_logp are not read
+int launch_sweep_seq_chains_tempered(hipStream_t stream, const SeqChain *chains_dev, const float *beta_dev, uint32_t nchains,
+                                     int nfeat, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
+                                     uint64_t v0, uint64_t v1, uint64_t sweep, uint32_t trace_every);
 // msc_chains_clone: pair p's source tables (red_i64[n_i64], red_f64[n_f64]) and z row [nrows] onto its destination's, one
 // launch for all pairs (grid: chunks x pairs); no source may be a destination
 struct ClonePair {

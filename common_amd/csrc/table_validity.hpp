@@ -28,7 +28,8 @@
 //   prepared()                 .       .           all 1      .                  .       .        ensure_derived, msc_chains_hp_slice
 //   crp_prepared()             .       .           .          .                  1       .        ensure_crp, msc_chains_hp_slice
 //   kept_current()             all 1   all 1       all 1      1                  1       0        msc_entity_op's kernel,
-//                                                                                                 msc_sweep_sequential, msc_chains_sweep
+//                                                                                                 msc_sweep_sequential, msc_chains_sweep,
+//                                                                                                 msc_chains_sweep_tempered
 //   step_began()               .       .           .          .                  .       0        msc_sweep_step (a replayed graph
 //                                                                                                 passes none of the events above)
 //   drawn()                    .       .           .          .                  .       1        blocked_draw_impl

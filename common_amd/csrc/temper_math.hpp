@@ -1,7 +1,8 @@
 // temper_math.hpp -- what msc_chains_exchange / msc_chains_anneal_weights (kernels_temper.hip) fix that needs no device:
 // the data log-likelihood of a chain from its joint row, the log ratio of a swap between two temperatures, the rule by
 // which it is accepted, which rung pairs an exchange proposes, the ladder's walk, the annealing increment, and the checks
-// of the calls' shapes.  Host only: no HIP header, nothing else of the library but joint_math.hpp (the row's layout) --
+// of the calls' shapes; and of the sweep at a temperature (msc_chains_sweep_tempered, kernels_seq.hip) which temperatures a
+// chain can be swept at and how a score partial goes onto a slot's score.  Host only: no HIP header, nothing else of the library but joint_math.hpp (the row's layout) --
 // tests/cxx/temper_math_host.cpp builds it with the host compiler; the kernels and the entry points call the same functions.
 //
 // The tempered target of a chain at temperature beta is pi_beta(z) ~ p(z | alpha) p(X | z, hp)^beta.  With L_c = log p(X |
@@ -104,6 +105,17 @@ MSC_JOINT_HD bool anneal_step(float beta_from, float beta_to, double l, double *
   *logw = *logw + ((double)beta_to - (double)beta_from) * l;
   return true;
 }
+
+// ---- the sweep at a temperature (msc_chains_sweep_tempered, k_sweep_seq_chains_tempered in kernels_seq.hip) ----
+// A temperature a chain can be swept at: finite and >= 0 (-0.0f is 0; beta > 1 sharpens towards the MAP).  NaN, a negative
+// or an infinite beta is none: its chain makes no visit and is reported (MSC_DEVERR_TEMPER_BETA).
+MSC_JOINT_HD bool beta_ok(float beta) { return beta >= 0.f && __builtin_isfinite(beta); }
+
+// One score partial of a slot -- the features' sum of one scoring slice -- going onto the slot's score sk at temperature
+// beta: sk + beta * partial with ONE rounding, where the untempered sweep has sk + partial.  At beta = 1 the product is
+// exact, so the bits are that add's; beta is not factored out of the slices' sum, which would round once more and
+// elsewhere.  The caller adds no partial at beta == 0 (0 * -inf is no number).
+MSC_JOINT_HD float tempered_add(float beta, float partial, float sk) { return __builtin_fmaf(beta, partial, sk); }
 
 // ---- the calls' shape checks: ok, or the message of the first one that fails ----
 inline joint::JointCheck check_exchange(const char *who, bool have_all, uint32_t nrungs, uint32_t nchains, uint64_t ld_joint,

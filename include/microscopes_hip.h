@@ -975,10 +975,31 @@ int msc_chains_keep_best(msc_chains *ch, const double *joint_dev, uint64_t ld_jo
                          uint64_t nrows, uint64_t iter, double *best_dev, int32_t *best_z_dev, uint64_t ld_best,
                          int64_t *best_iter_dev);
 
-/* ---- tempered chains: replica exchange between temperatures, and the weights of an annealing step ---- */
+/* ---- tempered chains: the sweep at a temperature, replica exchange, and the weights of an annealing step ---- */
 /*
- * The two steps a tempered ensemble makes BETWEEN its sweeps, chain c targeting pi_beta(z) ~ p(z | alpha) p(X | z, hp)^beta
- * at its own temperature beta_c.  (The sweep at a temperature is not part of the library yet: DESIGN.md 6v.)
+ * msc_chains_sweep_tempered: msc_chains_sweep with chain c at its own temperature beta_dev[c], targeting
+ *   pi_beta(z) ~ p(z | alpha) p(X | z, hp)^beta       (beta = 1: the posterior; 0: the CRP prior; > 1 sharpens).
+ * Every argument but beta_dev is msc_chains_sweep's, with its layout, launch slicing, limits and errors.
+ *   beta_dev      float[nchains] ON THE DEVICE, read by the kernel once per launch.  The call neither uploads nor reads
+ *                 it and waits for nothing, so the temperatures msc_chains_exchange swapped on the stream are what the
+ *                 next sweep reads.
+ * A visit scores slot k as log pseudocount_k + beta * (the features' score_value sum): each of the sweep's partial sums
+ * goes on by one fused multiply-add in the place and order of msc_chains_sweep's add, beta is not factored out, and so at
+ * beta = 1 every bit -- z, tables, trace, occupied -- is msc_chains_sweep's.  At beta == 0 (-0.0f too) the score reads no
+ * feature table and adds no partial (no 0 * -inf): the slot's score is the CRP term alone, while the row still leaves
+ * and joins its groups' suff-stats; a sweep at beta = 0 from all-unassigned is a draw from the CRP prior.
+ * A beta that is NaN, negative or infinite stops ITS chain for the launch: no visit, no sample written, z and tables as
+ * they were; the other chains run, and the next call returns MSC_EDEVICE naming this one (detail: the chain).
+ * Errors: MSC_EINVAL, with nothing launched, for a null beta_dev when nsweeps * nrows > 0, and whatever msc_chains_sweep
+ * refuses.  There is no tempered msc_chains_visit: a visit's log predictive keeps its untempered meaning.
+ */
+int msc_chains_sweep_tempered(msc_chains *ch, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
+                              uint64_t row_id0, int32_t *z_dev, uint64_t ld_z, const uint32_t *order_dev, uint64_t ld_order,
+                              uint32_t nsweeps, const uint64_t *host_seeds, uint64_t sweep, const float *beta_dev,
+                              uint32_t trace_every, int32_t *trace_dev, uint32_t *occupied_dev);
+
+/*
+ * The two steps a tempered ensemble makes BETWEEN its sweeps, chain c targeting pi_beta(z) at its own temperature beta_c.
  * Both calls read the chains' joint rows exactly as msc_chains_score_joint wrote them (chain c's at joint_dev + c *
  * ld_joint, ld_joint >= nfeatures + 3) and take from them the data log-likelihood
  *   L_c = ((d_0 + d_1) + ...) + d_{F-1},   the entries [2, 2 + F), added in double in that written order.

@@ -14,8 +14,14 @@ route without the ensemble, back-to-back State.sweep_sequential calls on the sam
 and scaled to C: the calls run one after another, one compute unit each).  Writes microseconds per visit per chain,
 aggregate visits per second and the ratio to that loop into --out, with the date and the commit.
 
+With --chains ... --tempered: for each of the two shapes and every chain count, ChainEnsemble.sweep(beta=) at beta = 1 and
+at beta = 0.5 (msc_chains_sweep_tempered) next to the untempered ChainEnsemble.sweep on the same ensemble -- every timed
+call is listed, so the spread of repeated calls stands beside the ratios -- then one iteration of run_tempered (sweep +
+joint + exchange) on four-rung ladders and a 33-temperature ais.  Writes --out (default profiles/chains_tempered.txt).
+
     python tools/bench_sequential.py [--rows 10000] [--steps 3] [--route-rows 300] [--posterior] [--phases]
     python tools/bench_sequential.py --chains 1,16,64,256,512 [--sweep-rows 10000] [--out profiles/chains.txt]
+    python tools/bench_sequential.py --chains 256 --tempered --rows 4096 --sweep-rows 4096 --steps 7
 """
 import argparse
 import ctypes as C
@@ -173,6 +179,58 @@ def chains(ctx, mix, N, K, counts, steps, sweep_rows, loop_chains):
     return res
 
 
+def tempered(ctx, mix, N, K, counts, steps):
+    """one result per chain count: whole sweeps of the N rows by every chain, untempered and at beta = 1 and 0.5, the three
+    taken in turn `steps` times after a warm-up round; an iteration of run_tempered; a 33-temperature ais"""
+    from common_amd import tempering
+    spec = MIXES[mix]
+    cols, z = make_columns(ctx, spec, N, K, seed=K + len(spec))
+    view = common_amd.DataView.from_tensors(ctx, cols)
+    dev = ctx.torch_device
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    res = []
+    for nc in counts:
+        ens = common_amd.ChainEnsemble(ctx, spec, K, nc, alpha=1.0)
+        ens.assign(view, z)
+        torch.cuda.synchronize()
+        betas = {"untempered": None, "beta_1": torch.ones(nc, dtype=torch.float32, device=dev),
+                 "beta_0.5": torch.full((nc,), 0.5, dtype=torch.float32, device=dev)}
+        ms = {k: [] for k in betas}
+        for s in range(steps + 1):                        # (the first round is the warm-up)
+            for k, b in betas.items():
+                t = timed(lambda: ens.sweep(view, 1, 1000, sweep=s, beta=b))
+                if s:
+                    ms[k].append(round(t, 3))
+        base = float(np.median(ms["untempered"]))
+        out = dict(mix=mix, K=K, N=N, features=len(spec), chains=nc, sweep_ms=ms,
+                   untempered_spread=round((max(ms["untempered"]) - min(ms["untempered"])) / base, 4),
+                   ratio_beta_1=round(float(np.median(ms["beta_1"])) / base, 4),
+                   ratio_beta_0_5=round(float(np.median(ms["beta_0.5"])) / base, 4))
+        if nc % 4 == 0:
+            ladder = tempering.ladder(4, "linear")
+            state = ens.run_tempered(view, 1, 1000, ladder, sweep=100)      # (warm-up)
+            it = []
+            for s in range(steps):
+                it.append(round(timed(lambda: ens.run_tempered(view, 1, 1000, ladder, sweep=101 + s, state=state)), 3))
+            out["run_tempered_iteration_ms"] = it
+        t0 = time.perf_counter()
+        r = ens.ais(view, np.linspace(0.0, 1.0, 33), 1000)
+        out["ais_33_temperatures_s"] = round(time.perf_counter() - t0, 3)
+        out["ais_log_evidence"], out["ais_ess"] = round(r.log_evidence, 3), round(r.ess, 2)
+        ens.close()
+        res.append(out)
+        print(json.dumps(out), flush=True)
+    return res
+
+
 def commit_id():
     import subprocess
     try:
@@ -188,7 +246,8 @@ def main():
     ap.add_argument("--sweep-rows", type=int, default=10000, help="--chains: rows of the N a timed sweep visits")
     ap.add_argument("--loop-chains", type=int, default=16, help="--chains: states the single-chain loop is timed on")
     ap.add_argument("--commit", default=None, help="--chains: the commit the figures belong to (default: git's HEAD)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "chains.txt"))
+    ap.add_argument("--tempered", action="store_true", help="--chains: time the sweep at a temperature and its drivers")
+    ap.add_argument("--out", default=None, help="default profiles/chains.txt, with --tempered profiles/chains_tempered.txt")
     ap.add_argument("--rows", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--route-rows", type=int, default=300)
@@ -199,6 +258,22 @@ def main():
     if a.chains:
         import datetime
         counts = [int(c) for c in a.chains.split(",")]
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "chains_tempered.txt" if a.tempered else "chains.txt")
+        if a.tempered:
+            lines = ["# The sweep at a temperature (msc_chains_sweep_tempered, k_sweep_seq_chains_tempered) and its drivers: %s, %s, "
+                     "commit %s" % (torch.cuda.get_device_name(0), datetime.date.today().isoformat(), a.commit or commit_id()),
+                     "# sweep_ms: every timed call, one whole sweep of the N rows by every chain, device events around the call, "
+                     "the three kinds taken in turn %d times after a warm-up round; untempered_spread = (max - min) / median of "
+                     "the untempered calls; ratio_* = median tempered / median untempered;" % a.steps,
+                     "# run_tempered_iteration_ms: one iteration (sweep + joint + exchange) on ladders of four rungs, events "
+                     "around the call; ais_33_temperatures_s: seat + 33 sweeps + 32 joints and weight steps, host clock"]
+            for mix in ("nich1", "c3_d64"):
+                lines += [json.dumps(r) for r in tempered(ctx, mix, a.rows, 256, counts, a.steps)]
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+            return
         lines = ["# Many sequential chains in one launch (msc_chains_sweep, k_sweep_seq_chains): %s, %s, commit %s"
                  % (torch.cuda.get_device_name(0), datetime.date.today().isoformat(), a.commit or commit_id()),
                  "# one sweep of rows_swept rows by every chain, best of %d warm calls, device events around the call;"
