@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Generate tests/golden/heavy.json: score_value, leave-one-out score_value and score_data of every family on the heavy
-rungs of tests/heavy_cases.py, evaluated with mpmath at 60 digits.
+rungs of tests/heavy_cases.py, and the CRP term score_assignment of the heavy layouts' group counts, evaluated with
+mpmath at 60 digits.
 
 The double twin (oracle/) cannot arbitrate at these sizes: it takes the same differences of lgamma in double as the
 device's prepare steps, and those cancel at the size of lgamma's value (1e9 ln 1e9), not of the result.  Here every
@@ -261,8 +262,23 @@ def family_table(name):
     return out
 
 
+def score_assignment(counts, alpha):
+    """the CRP term of a partition with these group sizes: occ ln(alpha) + sum lgamma(n_k) + lgamma(alpha) - lgamma(N + alpha)
+    over the occupied groups (group_manager.hpp score_assignment)"""
+    a = M(alpha)
+    occ = [int(c) for c in counts if c > 0]
+    return len(occ) * log(a) + sum(lg(mpf(c)) for c in occ) + lg(a) - lg(mpf(sum(occ)) + a)
+
+
+def assignment_table():
+    """-> {layout key: score_assignment} at alpha = float32(1.3), for the count vectors of hc.layout_counts"""
+    return dict(alpha=float(hc.ALPHA32),
+                **{key: float(score_assignment(hc.layout_counts(R, K), hc.ALPHA32)) for key, (R, K) in hc.LAYOUT_KEYS.items()})
+
+
 def generate():
-    return dict(dps=mp.dps, counts=hc.COUNTS, families={name: family_table(name) for name in hc.FAMILIES})
+    return dict(dps=mp.dps, counts=hc.COUNTS, families={name: family_table(name) for name in hc.FAMILIES},
+                score_assignment=assignment_table())
 
 
 def _enc(o):
@@ -282,7 +298,7 @@ def main():
     with open(hc.FIXTURE, "w") as fh:
         fh.write('{"counts": %s, "dps": %d, "families": {\n' % (_enc(doc["counts"]), doc["dps"]))
         fh.write(",\n".join('"%s": %s' % (n, _enc(doc["families"][n])) for n in sorted(doc["families"])))
-        fh.write("\n}}\n")
+        fh.write("\n}, \"score_assignment\": %s}\n" % _enc(doc["score_assignment"]))
     print("wrote %s: %d bytes" % (hc.FIXTURE, os.path.getsize(hc.FIXTURE)))
 
 

@@ -22,8 +22,13 @@ def test_generator_reproduces_the_committed_fixture():
         "make_heavy_golden", os.path.join(os.path.dirname(hc.FIXTURE), "make_heavy_golden.py"))
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
-    fresh, kept = gen.generate()["families"], hc.load_fixture()
+    doc = gen.generate()
+    fresh, kept = doc["families"], hc.load_fixture()
     assert sorted(fresh) == sorted(kept) == sorted(hc.FAMILIES)
+    crp = hc.load_score_assignment()
+    assert doc["score_assignment"]["alpha"] == float(hc.ALPHA32) and sorted(crp) == sorted(hc.LAYOUT_KEYS)
+    for key in crp:
+        assert abs(doc["score_assignment"][key] - crp[key]) <= 1e-15 * abs(crp[key]), key
     for name, d in fresh.items():
         ok = np.array(d["loo_ok"], dtype=bool)
         assert np.array_equal(ok, kept[name]["loo_ok"]), name
