@@ -986,13 +986,23 @@ extern "C" int msc_state_create(msc_context *ctx, const msc_feature_spec *featur
   return MSC_OK;
 }
 
+// the one place that destroys a captured step (msc_sweep_step): whatever the executable holds that no longer stands --
+// another key, the kernels or table sizes of an old plan -- the next steps count afresh
+static void drop_step_graph(msc_state *st) {
+  msc_state::StepGraph &g = st->step_graph;
+  if (!g.exec) return;
+  (void)hipGraphExecDestroy(g.exec);
+  g.exec = nullptr;
+  g.seen = 0;
+}
+
 extern "C" int msc_state_destroy(msc_state *st) {
   if (!st) return MSC_OK;
   MSC_REQUIRE(st->chain_members == 0, "msc_state_destroy: the state is a member of %u live msc_chains handle(s), whose "
                                       "table holds its buffers; destroy those first (msc_chains_destroy)", st->chain_members);
   (void)hipSetDevice(st->ctx->device);
   (void)hipStreamSynchronize(st->ctx->stream);
-  if (st->step_graph.exec) (void)hipGraphExecDestroy(st->step_graph.exec);
+  drop_step_graph(st);
   if (st->sm.pair) (void)msc_state_destroy(st->sm.pair);
   delete st;
   return MSC_OK;
@@ -1065,8 +1075,8 @@ int msc::ensure_raw(msc_state *st) {
 
 // refuses a call between msc_sweep_step_begin and msc_state_commit_reduce
 int msc::refuse_mid_step(const msc_state *st, const char *entry) {
-  MSC_REQUIRE(!st->rng_bump_pending, "%s between msc_sweep_step_begin and msc_state_commit_reduce: the additive tables "
-                                     "hold one rank's uncommitted sums", entry);
+  MSC_REQUIRE(!st->rng.mid_step(), "%s between msc_sweep_step_begin and msc_state_commit_reduce: the additive tables "
+                                   "hold one rank's uncommitted sums", entry);
   return MSC_OK;
 }
 
@@ -1849,11 +1859,9 @@ int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32
                            bool *zeroed) {
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   if (nrows == 0) return MSC_OK;
-  if (!st->rng_valid || st->rng_seed != seed || st->rng_sweep != sweep) {
+  if (!st->rng.holds(seed, sweep)) {
     if (launch_rng_set(st->ctx->stream, st->rng_dev, seed, sweep)) return fail(MSC_EHIP, "k_rng_set launch failed");
-    st->rng_valid = true;
-    st->rng_seed = seed;
-    st->rng_sweep = sweep;
+    st->rng.set(seed, sweep);
   }
   MSC_TRY(ensure_derived(st));
   MSC_TRY(ensure_crp(st));
@@ -1940,7 +1948,7 @@ int msc::sweep_assign_impl(msc_state *st, const msc_dataview *view, const uint32
     return MSC_OK;
   }
   if (launch_rng_bump(s, st->rng_dev)) return fail(MSC_EHIP, "k_rng_bump launch failed");
-  st->rng_sweep = sweep + 1;
+  st->rng.advanced();
   return MSC_OK;
 }
 
@@ -1970,47 +1978,48 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
     st->step_graph.n_eager++;
     bool zeroed = false;
     MSC_TRY(sweep_assign_impl(st, view, cols, row0, nrows, row_id0, z_dev, seed, sweep, &zeroed));
-    st->rng_valid = false;                              // (until the tail has moved the device's pair on)
+    st->rng.tail_owes();                                // (until the tail has moved the device's pair on)
     MSC_TRY(accumulate_impl(st, view, cols, row0, nrows, z_dev,
                             MSC_ACC_RESET | kAccThenPrepare | (zeroed ? (uint32_t)kAccZeroed : 0u)));
-    st->rng_valid = true;
-    st->rng_sweep = sweep + 1;
+    st->rng.tail_paid();
     return MSC_OK;
   };
   MSC_TRY(bind_view(st, view, cols, row0, nrows));       // (uploads and waits if the binding changed: never inside a capture)
   msc_state::StepGraph &g = st->step_graph;
   // Replay is opt-in: on ROCm 7.2 / MI355X a graph launch of the step's 3-5 kernels measured 4-5 us SLOWER than
   // launching them (27 -> 32 us at N = 10k), and instantiation costs milliseconds (sweep step).
-  const bool no_graph = !read_switches().sweep_graph;
+  StepInputs in{read_switches().sweep_graph, g.disabled, g.exec != nullptr};
   if (nrows == 0) return accumulate_impl(st, view, cols, row0, 0, z_dev, MSC_ACC_RESET);   // (no row draws anything)
-  if (no_graph || g.disabled) return eager();
-  std::vector<uint32_t> colv(st->nfeat);
-  for (uint32_t f = 0; f < st->nfeat; f++) colv[f] = cols ? cols[f] : f;
-  const bool same_key = g.view == view && g.view_serial == view->serial && g.row0 == row0 && g.nrows == nrows &&
-                        g.row_id0 == row_id0 && g.z == z_dev && g.alpha == st->alpha && g.cols == colv;
-  if (!same_key) {
-    if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-    g.view = view; g.view_serial = view->serial; g.row0 = row0; g.nrows = nrows; g.row_id0 = row_id0; g.z = z_dev;
-    g.alpha = st->alpha; g.cols = colv;
-    g.seen = 0;
+  StepKey key;
+  TableValidity::Snapshot entry;   // (which device tables are current: a captured step must leave them, and the pair, as it found them)
+  if (in.graph_on && !in.disabled) {                    // (the rule reads nothing else otherwise: a plain step builds no key)
+    key = {view, z_dev, view->serial, row0, nrows, row_id0, st->alpha, std::vector<uint32_t>(st->nfeat)};
+    for (uint32_t f = 0; f < st->nfeat; f++) key.cols[f] = cols ? cols[f] : f;
+    entry = st->valid.snapshot();
+    in.same_key = key == g.key;
+    in.seen = g.seen;
+    in.holds = st->rng.holds(seed, sweep);
+    in.flags_equal = entry == g.flags;
+    in.fused = sweep_is_fused(st->route);
   }
-  const bool next_sweep = st->rng_valid && st->rng_seed == seed && st->rng_sweep == sweep;
-  // (which device tables are current, and the random stream's pair: a captured step must leave both as it found them)
-  const TableValidity::Snapshot entry = st->valid.snapshot();
-  const bool rng_was_valid = st->rng_valid;
-  if (g.exec) {
-    if (!next_sweep || entry != g.flags) return eager();
-    MSC_HIP(hipGraphLaunch(g.exec, s));
-    g.n_replayed++;
-    st->rng_sweep = sweep + 1;      // (the graph ends with k_rng_bump; the flags end as they began)
-    return MSC_OK;
-  }
-  // the first two steps with a key run eagerly -- allocations, bindings and first-use setup happen there and the
-  // state reaches its steady flags -- and the third is captured, if it is the fused kind (nothing in it then
-  // allocates, copies to the host or waits)
-  if (g.seen < 2 || !next_sweep || !sweep_is_fused(st->route)) {
-    g.seen++;
-    return eager();
+  switch (step_action(in)) {                            // (step_rules.hpp)
+    case StepAction::eager:
+      return eager();
+    case StepAction::rekey:
+      drop_step_graph(st);
+      g.key = std::move(key);
+      g.seen = 0;
+      [[fallthrough]];
+    case StepAction::count:
+      g.seen++;
+      return eager();
+    case StepAction::replay:
+      MSC_HIP(hipGraphLaunch(g.exec, s));
+      g.n_replayed++;
+      st->rng.advanced();
+      return MSC_OK;
+    case StepAction::capture:
+      break;
   }
   // record on the library's own stream (the caller's may be the null stream), replay on the caller's
   msc_context *ctx = st->ctx;
@@ -2021,28 +2030,30 @@ extern "C" int msc_sweep_step(msc_state *st, const msc_dataview *view, const uin
     g.disabled = true;
     return eager();
   }
-  const uint64_t sweep_before = st->rng_sweep;
+  const RngMirror rng_entry = st->rng.snapshot();
   ctx->stream = ctx->record_stream;
   const int rc = eager();
   ctx->stream = s;
   g.n_eager--;                      // (recorded, not run)
   hipGraph_t graph = nullptr;
   const hipError_t ec = hipStreamEndCapture(ctx->record_stream, &graph);
+  // (the mirror by validity alone: a recorded step legitimately moves the sweep index on)
   bool ok = rc == MSC_OK && ec == hipSuccess && graph != nullptr && st->valid.snapshot() == entry &&
-            st->rng_valid == rng_was_valid;
+            st->rng.valid() == rng_entry.valid();
   if (ok && hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
     g.exec = nullptr;
     ok = false;
   }
   if (graph) (void)hipGraphDestroy(graph);
   if (!ok) {
-    // nothing of the captured step has run: put the host's view of the state back and run the step as it is
+    // nothing of the captured step has run: put the host's view of the state back and run the step as it is.  (The
+    // mirror whole: a recorded step reports tail_owes and tail_paid alone -- the pair held at entry, so nothing set it,
+    // and only msc_sweep_step_begin defers -- so validity and the sweep index are all that can differ.)
     (void)hipGetLastError();
-    if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+    drop_step_graph(st);
     g.disabled = true;
     st->valid.restore(entry);
-    st->rng_valid = rng_was_valid;
-    st->rng_sweep = sweep_before;
+    st->rng.restore(rng_entry);
     return eager();
   }
   g.flags = entry;
@@ -2062,9 +2073,7 @@ extern "C" int msc_sweep_step_begin(msc_state *st, const msc_dataview *view, con
   if (nrows == 0) return accumulate_impl(st, view, cols, row0, 0, z_dev, MSC_ACC_RESET | MSC_ACC_NO_COMMIT);
   bool zeroed = false;
   MSC_TRY(sweep_assign_impl(st, view, cols, row0, nrows, row_id0, z_dev, seed, sweep, &zeroed));
-  st->rng_valid = false;                                // (until the commit has moved the device's pair on)
-  st->rng_bump_pending = true;
-  st->rng_next_sweep = sweep + 1;
+  st->rng.deferred();                                   // (until the commit has moved the device's pair on)
   return accumulate_impl(st, view, cols, row0, nrows, z_dev,
                          MSC_ACC_RESET | MSC_ACC_NO_COMMIT | (zeroed ? (uint32_t)kAccZeroed : 0u));
 }
@@ -2115,13 +2124,9 @@ extern "C" int msc_state_reduce_unpack(msc_state *st) {
 // here, once; 0 = back to the view's count.
 extern "C" int msc_state_set_sweep_rows(msc_state *st, uint64_t global_rows) {
   MSC_REQUIRE(st, "null state");
-  if (st->sweep_rows_hint != global_rows && st->step_graph.exec) {
-    // (the hint chooses kernels -- lane <-> row or tile, PAIR mode, the narrow tiling -- for every view the state scores:
-    // a captured step holds the old choice, and replaying it would draw other bits than the whole does.  ADVICE r04)
-    (void)hipGraphExecDestroy(st->step_graph.exec);
-    st->step_graph.exec = nullptr;
-    st->step_graph.seen = 0;
-  }
+  // (the hint chooses kernels -- lane <-> row or tile, PAIR mode, the narrow tiling -- for every view the state scores:
+  // a captured step holds the old choice, and replaying it would draw other bits than the whole does.  ADVICE r04)
+  if (st->sweep_rows_hint != global_rows) drop_step_graph(st);
   st->sweep_rows_hint = global_rows;
   return MSC_OK;
 }
@@ -2164,12 +2169,7 @@ extern "C" int msc_state_set_col_bounds(msc_state *st, const uint32_t *bounds, s
     }
   }
   if (nb == st->col_bounds) return MSC_OK;
-  if (st->step_graph.exec) {
-    // (a captured step holds the kernels and table sizes of the old plan: ADVICE r04, as for msc_state_set_sweep_rows)
-    (void)hipGraphExecDestroy(st->step_graph.exec);
-    st->step_graph.exec = nullptr;
-    st->step_graph.seen = 0;
-  }
+  drop_step_graph(st);   // (a captured step holds the kernels and table sizes of the old plan: ADVICE r04, as for msc_state_set_sweep_rows)
   st->col_bounds = std::move(nb);
   st->rebind = true;
   return MSC_OK;
@@ -2179,13 +2179,9 @@ extern "C" int msc_state_commit_reduce(msc_state *st) {
   MSC_REQUIRE(st, "null state");
   MSC_HIP(hipSetDevice(st->ctx->device));
   // (what follows a reduce is the next sweep's scoring: commit and prepare in one launch, as in msc_sweep_step)
-  const bool bump = st->rng_bump_pending;
+  const bool bump = st->rng.mid_step();
   MSC_TRY(commit_and_prepare(st, bump));
-  if (bump) {
-    st->rng_bump_pending = false;
-    st->rng_valid = true;
-    st->rng_sweep = st->rng_next_sweep;
-  }
+  if (bump) st->rng.deferred_paid();
   return MSC_OK;
 }
 

@@ -93,8 +93,8 @@ static layout::MargBlock marg_block(const msc_chains *ch, uint32_t nsel) {
 // to every member; then the members' tables as current as the call's kernels need them.
 static int chains_refuse_mid_step(const msc_chains *ch, const char *who) {
   for (uint32_t c = 0; c < ch->states.size(); c++)
-    MSC_REQUIRE(!ch->states[c]->rng_bump_pending, "%s: state %u is between msc_sweep_step_begin and "
-                                                  "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
+    MSC_REQUIRE(!ch->states[c]->rng.mid_step(), "%s: state %u is between msc_sweep_step_begin and "
+                                                "msc_state_commit_reduce: its additive tables hold uncommitted sums", who, c);
   return MSC_OK;
 }
 static int chains_device(const msc_chains *ch) {

@@ -15,6 +15,7 @@
 #include "dev_buf.hpp"
 #include "feat_desc.hpp"
 #include "route.hpp"
+#include "step_rules.hpp"
 #include "table_validity.hpp"
 
 namespace msc {
@@ -557,22 +558,20 @@ struct msc_state {
   msc::DevBuf<double> marg_norm;  // msc_score_marginal: {log(n + alpha), log(n - 1 + alpha)}, rewritten by every call
   msc::DevBuf<float> rows_table;  // k_sweep_nich1_rows: per-group constants as scalar operands (single nich, K > 1024)
   msc::DevBuf<uint32_t> colmax_dev;
-  // (seed, sweep index) of the sampling kernels, device-resident (kernels_sweep.hip); the host tracks what it holds
+  // (seed, sweep index) of the sampling kernels, device-resident (kernels_sweep.hip), and what the host believes it holds
+  // (step_rules.hpp: the calls report events to the mirror; rng.mid_step() is also how a call learns that the state is
+  // between msc_sweep_step_begin and msc_state_commit_reduce)
   msc::DevBuf<uint64_t> rng_dev;
-  uint64_t rng_seed = 0, rng_sweep = 0;
-  bool rng_valid = false;
-  bool rng_bump_pending = false;       // msc_sweep_step_begin left the increment of the sweep index to msc_state_commit_reduce
-  uint64_t rng_next_sweep = 0;
-  // a whole sweep step (assign + accumulate + commit) captured as a graph for its steady state (abi.cpp msc_sweep_step)
+  msc::RngMirror rng;
+  // a whole sweep step (assign + accumulate + commit) captured as a graph for its steady state (abi.cpp msc_sweep_step;
+  // step_rules.hpp step_action decides from key, seen and disabled; abi.cpp drop_step_graph is the one place that
+  // destroys the executable)
   struct StepGraph {
     hipGraphExec_t exec = nullptr;
-    const void *view = nullptr, *z = nullptr;
-    uint64_t view_serial = 0, row0 = 0, nrows = 0, row_id0 = 0;
-    float alpha = 0.f;
-    std::vector<uint32_t> cols;
-    msc::TableValidity::Snapshot flags;   // validity flags of the state at step entry
-    int seen = 0;                      // eager steps with this key so far
-    bool disabled = false;
+    msc::StepKey key;                       // what the executable was captured, or the eager steps are counted, under
+    msc::TableValidity::Snapshot flags;     // validity flags of the state at the captured step's entry
+    int seen = 0;                           // eager steps with this key so far
+    bool disabled = false;                  // a capture failed: every later step runs eagerly
     uint64_t n_eager = 0, n_replayed = 0;   // steps run either way (msc_sweep_step_stats)
   } step_graph;
   msc::DevBuf<double> niw_qown;      // q of every row's own group (niw leave-one-out), one a row

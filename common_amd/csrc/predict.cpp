@@ -128,15 +128,12 @@ extern "C" int msc_sample_predictive(msc_state *st, const msc_dataview *view, co
   if (z == nullptr) {
     MSC_HIP(reserve_synced(st->ctx->stream, st->pred.z, nrows));
     MSC_HIP(hipMemsetAsync(st->pred.z, 0xff, nrows * sizeof(int32_t), s));
-    const bool had = st->rng_valid;
-    const uint64_t had_seed = st->rng_seed, had_sweep = st->rng_sweep;
+    const RngMirror had = st->rng.snapshot();
     MSC_TRY(sweep_assign_impl(st, view, cols, row0, nrows, row_id0, st->pred.z, seed ^ kPredGroupKey, sweep));
-    st->rng_valid = false;
-    if (had) {
-      if (launch_rng_set(s, st->rng_dev, had_seed, had_sweep)) return fail(MSC_EHIP, "k_rng_set launch failed");
-      st->rng_valid = true;
-      st->rng_seed = had_seed;
-      st->rng_sweep = had_sweep;
+    st->rng.invalidate();
+    if (had.valid()) {
+      if (launch_rng_set(s, st->rng_dev, had.seed(), had.sweep())) return fail(MSC_EHIP, "k_rng_set launch failed");
+      st->rng.restore(had);
     }
     z = st->pred.z;
   }

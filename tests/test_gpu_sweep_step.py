@@ -97,6 +97,27 @@ def test_step_after_rebinding_another_view(gpu_ctx, graph, monkeypatch):
     _same_tables(ea, gr, nfeat)
 
 
+def test_group_draw_between_replays(gpu_ctx, monkeypatch):
+    """sample_predictive without z draws the rows' groups with the sweep's own assignment pass, under a key of its own:
+    it borrows the device's (seed, sweep) pair and puts it back, so the captured step goes on replaying"""
+    monkeypatch.setenv("MSC_SWEEP_GRAPH", "1")
+    view, (ea, za), (gr, zg), nfeat = _pair(gpu_ctx, [(orc.BB, 0), (orc.NICH, 0)], 2000, 25, seed=3)
+
+    def step(sweep):
+        ea.sweep_assign(view, za, seed=1, sweep=sweep); ea.accumulate(view, za)
+        gr.sweep_step(view, zg, seed=1, sweep=sweep)
+        assert torch.equal(za, zg), sweep
+    for sweep in range(5):                      # steps 0-1 eager, 2 captured, 3-4 replayed
+        step(sweep)
+    gr.sample_predictive(view, seed=8, sweep=0)
+    for sweep in range(5, 9):
+        step(sweep)
+    _same_tables(ea, gr, nfeat)
+    # (what the commit before the mirror of the pair had one owner gave for these nine steps: the draw leaves the pair and
+    # the validity flags as it found them, and steps 5-8 replay)
+    assert gr.sweep_step_stats() == (2, 7)
+
+
 def test_sharded_driver_uses_the_step_when_alone(gpu_ctx):
     from common_amd.dist import ShardedSweep
     view, (ea, za), (gr, zg), nfeat = _pair(gpu_ctx, [(orc.NICH, 0)], 4000, 32, seed=12)
