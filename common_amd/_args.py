@@ -75,3 +75,11 @@ def rows(view_rows, row0, nrows):
     if row0 < 0 or n < 0:
         raise ValueError("rows [%d, %d) outside the view (%d rows)" % (row0, row0 + n, view_rows))
     return row0, n
+
+
+def index(i, count, name):
+    """i as an index into `count` items (a negative one is refused: ctypes would wrap it to uint32)"""
+    i = int(i)
+    if not 0 <= i < count:
+        raise ValueError("%s %d out of range (%d)" % (name, i, count))
+    return i

@@ -128,6 +128,8 @@ _SIGS = {
     "msc_blocked_draw": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "msc_blocked_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32)]),
+    "msc_blocked_niw_params": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_uint32)]),
     "msc_blocked_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                      C.c_uint64, C.c_uint64]),
     "msc_sweep_blocked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,

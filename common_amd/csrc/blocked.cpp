@@ -5,6 +5,7 @@
 #include <string>
 
 #include "abi_internal.hpp"
+#include "blocked_niw.hpp"
 #include "blocked_post.hpp"
 #include "launchers.hpp"
 #include "splitmerge_math.hpp"
@@ -35,6 +36,14 @@ static int blocked_setup(msc_state *st) {
     MSC_TRY(alloc_zeroed(st->blk.work, 2 * (size_t)st->K));
     MSC_TRY(alloc_zeroed(st->blk.feats_dev, std::max<size_t>(1, st->nfeat)));
     st->blk.rows = rows;
+  }
+  // a state of one niw feature (BlockedKernel::niw1): the drawn matrices in double, zero until the first draw
+  if (st->nfeat == 1 && st->feats[0].family == MSC_NIW && !st->blk.niw_mean) {
+    const uint32_t d = st->feats[0].dim;
+    MSC_TRY(alloc_zeroed(st->blk.niw_mean, (size_t)st->K * d));
+    MSC_TRY(alloc_zeroed(st->blk.niw_whiten, (size_t)st->K * blocked::ntri(d)));
+    MSC_TRY(alloc_zeroed(st->blk.niw_w64, (size_t)st->K * niw_w_stream(d)));
+    MSC_TRY(alloc_zeroed(st->blk.niw_mu64, (size_t)st->K * niw_b_stream(d)));
   }
   std::vector<BlkFeat> fs(st->nfeat);
   uint32_t row = 1;
@@ -74,13 +83,18 @@ static int blocked_setup(msc_state *st) {
   return MSC_OK;
 }
 
-static int blocked_draw_impl(msc_state *st, uint64_t seed, uint64_t sweep) {
+static int blocked_draw_impl(msc_state *st, const BlockedRoute &route, uint64_t seed, uint64_t sweep) {
   // the draw reads the reference's fields and the group counts: both current before (the additive sums and the score
   // constants it does not read are left as they are)
   MSC_TRY(ensure_raw(st));
   MSC_TRY(blocked_setup(st));
-  if (launch_blocked_draw(st->ctx->stream, st->blk.feats_dev, st->nfeat, st->K, st->kpad, st->cnt_u32, st->alpha, seed, sweep,
-                          st->blk.work, st->blk.tab))
+  if (route.kernel == BlockedKernel::niw1) {
+    if (launch_blocked_draw_niw(st->ctx->stream, st->blk.feats_dev, st->K, st->kpad, st->cnt_u32, st->alpha, seed, sweep,
+                                st->blk.work, st->blk.tab, st->blk.niw_mean, st->blk.niw_whiten, st->blk.niw_w64,
+                                st->blk.niw_mu64))
+      return MSC_EHIP;
+  } else if (launch_blocked_draw(st->ctx->stream, st->blk.feats_dev, st->nfeat, st->K, st->kpad, st->cnt_u32, st->alpha, seed,
+                                 sweep, st->blk.work, st->blk.tab))
     return MSC_EHIP;
   st->valid.drawn();
   return MSC_OK;
@@ -92,8 +106,12 @@ static int blocked_assign_impl(msc_state *st, const BlockedRoute &route, const m
   MSC_REQUIRE(st->valid.draw_current(), "msc_blocked_assign: no parameter draw made from the tables as they stand (msc_blocked_draw "
                                         "first; whatever changes tables, hyper-parameters, alpha or group counts makes a draw stale)");
   MSC_TRY(blocked_setup(st));
-  if (launch_blocked_assign(st->ctx->stream, route.kernel, route.block, st->blk.feats_dev, (int)st->nfeat, st->blk.tab, st->K,
-                            st->kpad, row0, nrows, row_id0, z_dev, seed, sweep))
+  if (route.kernel == BlockedKernel::niw1) {
+    if (launch_blocked_assign_niw(st->ctx->stream, st->feats[0].dim, st->blk.feats_dev, st->blk.tab, st->blk.niw_w64,
+                                  st->blk.niw_mu64, st->K, st->kpad, row0, nrows, row_id0, z_dev, seed, sweep))
+      return MSC_EHIP;
+  } else if (launch_blocked_assign(st->ctx->stream, route.kernel, route.block, st->blk.feats_dev, (int)st->nfeat, st->blk.tab,
+                                   st->K, st->kpad, row0, nrows, row_id0, z_dev, seed, sweep))
     return MSC_EHIP;
   return MSC_OK;
 }
@@ -105,7 +123,7 @@ extern "C" int msc_blocked_draw(msc_state *st, uint64_t seed, uint64_t sweep) {
   MSC_TRY(device_error_check(st->ctx));
   const BlockedRoute route = route_sweep_blocked(route_facts_now(st));
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
-  return blocked_draw_impl(st, seed, sweep);
+  return blocked_draw_impl(st, route, seed, sweep);
 }
 
 extern "C" int msc_blocked_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld) {
@@ -116,6 +134,21 @@ extern "C" int msc_blocked_tables(msc_state *st, uint32_t feature, const float *
   if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
   MSC_TRY(blocked_setup(st));
   blocked_table_slices(st, feature, dev, nslices, ld);
+  return MSC_OK;
+}
+
+extern "C" int msc_blocked_niw_params(msc_state *st, uint32_t feature, const double **mean, const double **whiten,
+                                      uint32_t *dim) {
+  MSC_REQUIRE(st, "null state");
+  MSC_REQUIRE(feature < st->nfeat, "feature %u out of range", feature);
+  MSC_HIP(hipSetDevice(st->ctx->device));
+  const BlockedRoute route = route_sweep_blocked(route_facts_now(st));
+  if (route.rc != MSC_OK) return fail(route.rc, "%s", route.why.c_str());
+  MSC_REQUIRE(route.kernel == BlockedKernel::niw1, "msc_blocked_niw_params: feature %u is not a niw feature", feature);
+  MSC_TRY(blocked_setup(st));
+  if (mean) *mean = st->blk.niw_mean;
+  if (whiten) *whiten = st->blk.niw_whiten;
+  if (dim) *dim = st->feats[feature].dim;
   return MSC_OK;
 }
 
@@ -142,7 +175,7 @@ extern "C" int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const 
   MSC_TRY(bind_view(st, view, cols, row0, nrows));
   hipStream_t s = st->ctx->stream;
   for (uint32_t i = 0; i < nsweeps; i++) {
-    MSC_TRY(blocked_draw_impl(st, seed, sweep + i));
+    MSC_TRY(blocked_draw_impl(st, route, seed, sweep + i));
     MSC_TRY(blocked_assign_impl(st, route, view, cols, row0, nrows, row_id0, z_dev, seed, sweep + i));
     MSC_TRY(accumulate_impl(st, view, cols, row0, nrows, z_dev, MSC_ACC_RESET));
     if (trace_dev && nrows)

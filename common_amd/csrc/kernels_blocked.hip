@@ -193,6 +193,8 @@ int launch_blocked_assign(hipStream_t stream, BlockedKernel kernel, uint32_t blo
       hipLaunchKernelGGL((k_blocked_assign<MODE_GLOBAL>), (note_kernel(1, "k_blocked_assign<0>"), grid), dim3(block), 0,
                          stream, fs_dev, nfeat, tab, K, kpad, row0, nrows, row_id0, z, seed, sweep);
       break;
+    case BlockedKernel::niw1:                      // (kernels_blocked_niw.hip launch_blocked_assign_niw)
+      return fail(MSC_EHIP, "k_blocked_assign: no route sends a niw state here");
   }
   return launch_status("k_blocked_assign");
 }

@@ -284,6 +284,8 @@ int launch_sm_assign(hipStream_t stream, BlockedKernel kernel, uint32_t block, b
       sm_assign_mode<MODE_GLOBAL>(stream, final, grid, block, 0, fs_dev, nfeat, tab, kpad, row0, nrows, row_id0, z, ell, prop,
                                   key, sweep, part, zero);
       break;
+    case BlockedKernel::niw1:                      // (route_splitmerge refuses every niw state)
+      return fail(MSC_EHIP, "k_sm_assign: no route sends a niw state here");
   }
   return launch_status("k_sm_assign");
 }

@@ -200,6 +200,16 @@ int launch_blocked_assign(hipStream_t stream, BlockedKernel kernel, uint32_t blo
                           int32_t *z, uint64_t seed, uint64_t sweep);
 int launch_blocked_top_slot(hipStream_t stream, const uint32_t *cnt, uint32_t K, uint32_t *out);
 
+// kernels_blocked_niw.hip: the same sampler for a state of one niw feature of dim <= 32 (BlockedKernel::niw1).  The draw:
+// the stick weights, then every slot's mean[K][dim], whiten[K][dim (dim + 1) / 2] and, from the same doubles, the operand
+// streams w64 / mu64 of the assign kernel (msc_internal.hpp niw_w_index / niw_b_index)
+int launch_blocked_draw_niw(hipStream_t stream, const BlkFeat *fs_dev, uint32_t K, uint32_t kpad, const uint32_t *cnt,
+                            float alpha, uint64_t seed, uint64_t sweep, double *work, float *tab, double *mean,
+                            double *whiten, double *w64, double *mu64);
+int launch_blocked_assign_niw(hipStream_t stream, uint32_t dim, const BlkFeat *fs_dev, const float *tab, const double *w64,
+                              const double *mu64, uint32_t K, uint32_t kpad, uint64_t row0, uint64_t nrows, uint64_t row_id0,
+                              int32_t *z, uint64_t seed, uint64_t sweep);
+
 // kernels_splitmerge.hip: the split-merge move (msc_split_merge; route_calls.hpp route_splitmerge chooses the assign kernel).
 // seed is the caller's: the launchers form the streams' keys (splitmerge_math.hpp).  `zero`: the pair state's additive
 // tables, emptied on the way for the accumulate pass that follows.

@@ -194,6 +194,7 @@ inline uint32_t blocked_slices(int family, uint32_t dim) {
     case MSC_BNB: return 2;
     case MSC_NICH: return 3;
     case MSC_DD: return dim;
+    case MSC_NIW: return 1;     // (c; the matrices are BlockedWork's doubles, blocked_niw.hpp)
     default: return 0;
   }
 }
@@ -485,13 +486,17 @@ struct PredWork {
 };
 // the blocked Gibbs sampler (blocked.cpp msc_blocked_*): the parameter table -- (1 + sum of the features' slices) rows of
 // kpad floats, row 0 the log stick weights -- the features as the kernels read them, the stick kernel's scratch
-// (log V, log(1 - V): 2 K doubles); whether the table was drawn from the tables as they stand: valid.draw_current()
+// (log V, log(1 - V): 2 K doubles); whether the table was drawn from the tables as they stand: valid.draw_current().
+// A state of one niw feature (BlockedKernel::niw1) also owns, from its first draw on, the drawn matrices in double:
+// mean[K][dim], whiten[K][dim (dim + 1) / 2] (msc_blocked_niw_params) and the same V, V mu as the assign kernel's operand
+// streams, [K][niw_w_stream(dim)] and [K][niw_b_stream(dim)]
 struct BlockedWork {
   DevBuf<float> tab;
   DevBuf<BlkFeat> feats_dev;
   std::vector<BlkFeat> feats_host;
   DevBuf<double> work;
   uint32_t rows = 0;
+  DevBuf<double> niw_mean, niw_whiten, niw_w64, niw_mu64;
 };
 // the split-merge move (blocked.cpp msc_split_merge): an internal three-slot state of the same features -- pair slots 0
 // and 1, slot 2 their union -- created at the first call and destroyed with its state; the pair labels of the call's

@@ -7,6 +7,7 @@
 
 #include <string>
 
+#include "blocked_niw.hpp"
 #include "blocked_post.hpp"
 #include "route.hpp"
 
@@ -21,13 +22,22 @@ namespace msc {
 //   global  more features than that: the values re-read from the columns for every eight slots
 // The split-merge move takes the same families and shapes (every kernel adds a row's terms in the same order, so the
 // choice never changes a bit); its staged kernel holds one feature fewer.  who: the caller, as the message names it.
-enum class BlockedKernel { nich1, staged, global };
+//   niw1    the blocked sweep alone (niw_alone): a state whose ONLY feature is one niw column of dim <= 32 -- kernels of
+//           its own (kernels_blocked_niw.hip: the parameter draw leaves matrices, the assign pass runs on the f64 matrix
+//           pipe, 256 rows a workgroup).  A niw feature beside others, and any niw state in split-merge, is refused.
+enum class BlockedKernel { nich1, staged, global, niw1 };
 struct BlockedRoute { int rc = MSC_OK; std::string why; BlockedKernel kernel = BlockedKernel::global; uint32_t block = 256; };
 constexpr uint32_t kBlockedStagedMax = 256;             // (at most 32 KiB of LDS a workgroup: several a compute unit)
 constexpr uint32_t kSplitMergeStagedMax = 255;          // (the codes and the waves' sums within 64 KiB of LDS a workgroup)
-inline BlockedRoute route_blocked(const RouteFacts &rf, const char *who, uint32_t staged_max) {
+inline BlockedRoute route_blocked(const RouteFacts &rf, const char *who, uint32_t staged_max, bool niw_alone = false) {
   BlockedRoute r;
   const auto refuse = [&](const char *what) { r.rc = MSC_EUNSUPPORTED, r.why = std::string(who) + what; return r; };
+  if (niw_alone && rf.nfeat == 1 && rf.feats.size() == 1 && rf.feats[0].family == MSC_NIW) {
+    // (kNiwMaxDim = 32, two 16-blocks: k_blocked_assign_niw<1>, <2>)
+    if (rf.feats[0].dim > blocked::kNiwMaxDim) return refuse(" takes a niw feature of dimension at most 32");
+    r.kernel = BlockedKernel::niw1;
+    return r;
+  }
   for (const RouteFeat &h : rf.feats)
     if (h.family == MSC_NIW || h.family == MSC_DM || h.family == MSC_BBNC)
       return refuse(" takes bb, gp, bnb, dd, nich and noop features (the state holds niw, dm or bbnc)");
@@ -39,7 +49,7 @@ inline BlockedRoute route_blocked(const RouteFacts &rf, const char *who, uint32_
   }
   return r;
 }
-inline BlockedRoute route_sweep_blocked(const RouteFacts &rf) { return route_blocked(rf, "the blocked sweep", kBlockedStagedMax); }
+inline BlockedRoute route_sweep_blocked(const RouteFacts &rf) { return route_blocked(rf, "the blocked sweep", kBlockedStagedMax, true); }
 inline BlockedRoute route_splitmerge(const RouteFacts &rf) { return route_blocked(rf, "split-merge", kSplitMergeStagedMax); }
 
 // ---- the sequential sweep and the ensembles of such chains (kernels_seq.hip, kernels_chains_sm.hip) ---------------------

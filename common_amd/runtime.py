@@ -600,6 +600,18 @@ class State(object):
         (msc_blocked_tables; the slices per family are listed in include/microscopes_hip.h)"""
         return self._tables(self.ctx.lib.msc_blocked_tables, self.K)
 
+    def blocked_niw_params(self, f=0):
+        """{"mean": float64[K, d], "whiten": float64[K, d (d + 1) / 2]}: views onto the matrices of the latest draw of a
+        state of one niw feature -- the slot's mean and its lower-triangular whitening matrix V packed by rows, entry
+        (i, j) at i (i + 1) / 2 + j (msc_blocked_niw_params)"""
+        f = A.index(f, len(self.features), "feature")
+        pm, pw, d = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        L.check(self.ctx.lib.msc_blocked_niw_params(self._h, f, C.byref(pm), C.byref(pw), C.byref(d)))
+        dev, d = self.ctx.torch_device, d.value
+        nt = d * (d + 1) // 2
+        return {"mean": _alias_tensor(pm.value, self.K * d, torch.float64, dev, self).view(self.K, d),
+                "whiten": _alias_tensor(pw.value, self.K * nt, torch.float64, dev, self).view(self.K, nt)}
+
     def blocked_assign(self, view, z, seed, sweep, row0=0, nrows=None, row_id0=None, cols=None):
         """every row's slot drawn independently under the parameters of the latest blocked_draw (msc_blocked_assign)"""
         self._rows_call(self.ctx.lib.msc_blocked_assign, view, z, seed, sweep, row0, nrows, row_id0, cols)

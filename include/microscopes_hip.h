@@ -616,10 +616,33 @@ int msc_chains_sample_predictive(msc_chains *ch, const msc_dataview *view, const
  * truncation binds and K should be raised.  Asynchronous; the reference's fields, the additive sums and the group
  * counts are current on return, and msc_sweep_step's device (seed, sweep) pair and graph are untouched.
  *
- * Families: bb, gp, bnb, dd, nich and noop.  States with niw, dm or bbnc features: MSC_EUNSUPPORTED from all four.
+ * Families: bb, gp, bnb, dd, nich and noop.  States with niw, dm or bbnc features: MSC_EUNSUPPORTED from all four --
+ * but for one shape, the Dirichlet-process Gaussian mixture:
+ *
+ * A state whose ONLY feature is one niw column of dim <= 32 is taken by all four calls (dim 33 .. 128: MSC_EUNSUPPORTED,
+ * "the blocked sweep takes a niw feature of dimension at most 32"; split-merge and the sequential sweep refuse it as
+ * before).  With kappa' = kappa + n, nu' = nu + n, mu' = (kappa mu + sum_x) / kappa', Psi' = psi + sum_xxT + kappa mu mu^T
+ * - kappa' mu' mu'^T = L L^T, a slot draws a lower-triangular whitening matrix V = T L^-1, T lower triangular with
+ * T_ii^2 ~ chi2(nu' - dim + 1 + i) (0-based: the degrees of freedom increase down the diagonal) and T_ij ~ N(0, 1), j < i,
+ * so that Sigma = (V^T V)^-1 ~ IW(Psi', nu'); and mu = mu' + V^-1 z / sqrt(kappa'), z ~ N(0, I).
+ *
+ *   family  posterior draw                                                   slices                   log-lik. of value x
+ *   niw     V, mu as above                                                   -(dim / 2) log 2 pi      s0 - |V x - V mu|^2 / 2
+ *                                                                            + sum_i log V_ii         (V, mu: in double, below)
+ *
+ * Row i of a slot's matrix draws from the stream of (slot | (i + 1) << 32, feature) -- counter words slot, i + 1, sweep,
+ * 0x80000000 | feature << 16 | block; every other stream above has a second word of 0 --: z_i first, then T_i0 ..
+ * T_i,i-1, then the chi-square of T_ii.  The assign pass evaluates |V x - V mu|^2 in double (a row with any masked
+ * element scores log pi_k alone).
+ *
+ * msc_blocked_niw_params: the matrices of the latest draw, in double, as the assign pass reads them: *mean =
+ * double[K][*dim], *whiten = double[K][*dim (*dim + 1) / 2], V's lower triangle packed by rows (entry (i, j), j <= i, at
+ * i (i + 1) / 2 + j).  Every value is finite; zeros before the first draw.  The pointers stay valid for the state's
+ * life.  A state of any other shape: the refusal msc_blocked_draw gives it, or MSC_EINVAL where it holds no niw feature.
  */
 int msc_blocked_draw(msc_state *st, uint64_t seed, uint64_t sweep);
 int msc_blocked_tables(msc_state *st, uint32_t feature, const float **dev, uint32_t *nslices, uint32_t *ld);
+int msc_blocked_niw_params(msc_state *st, uint32_t feature, const double **mean, const double **whiten, uint32_t *dim);
 int msc_blocked_assign(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,
                        uint64_t row_id0, int32_t *z_dev, uint64_t seed, uint64_t sweep);
 int msc_sweep_blocked(msc_state *st, const msc_dataview *view, const uint32_t *cols, uint64_t row0, uint64_t nrows,

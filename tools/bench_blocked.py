@@ -3,12 +3,15 @@
     C2        one nich column, N = 1e6, K = 256
     C3        the mix bb + gp + dd(32) + nich x 16 (D = 64), N = 1e6, K = 256
     C5 shard  one nich column, N = 12.5e6, K = 1024
+    C4        one niw column of dim 32, N = 262144, K = 128 (c4d16: dim 16) -- the Dirichlet-process Gaussian mixture;
+              beside the niw scoring pass (msc_score_value), the unchanged code the assign pass is measured against
 with the blocked sweep's split into draw / assign / accumulate (each timed on its own, the assign against a standing
 draw) and, for the pass-by-pass comparison, the collapsed fused assignment pass alone (msc_sweep_assign).  With
 --occupied: on N = 2e4 rows of the small C3 mix (bb, gp, dd(9), nich) from eight true clusters with K = 64, the occupied
 groups after 50 sweeps of sweep_blocked and of sweep_sequential (recorded, not asserted).  Writes everything to --out.
 
     python tools/bench_blocked.py [c2] [c3] [c5] [--steps 10] [--occupied] [--out profiles/blocked.txt]
+    python tools/bench_blocked.py c4 c4d16 --out profiles/blocked_niw.txt     (the measured lines of that file)
 """
 import argparse
 import datetime
@@ -23,13 +26,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import common_amd  # noqa: E402
-from common_amd import BB, DD, GP, NICH  # noqa: E402
+from common_amd import BB, DD, GP, NICH, NIW  # noqa: E402
 from tools.bench_configs import make_columns  # noqa: E402
 
 SHAPES = {
     "c2": ("C2 nich N=1e6 K=256", [(NICH, 0)], 1_000_000, 256),
     "c3": ("C3 mix bb+gp+dd32+nich x16 N=1e6 K=256", [(BB, 0), (GP, 0), (DD, 32), (NICH, 0)] * 16, 1_000_000, 256),
     "c5": ("C5 shard nich N=12.5e6 K=1024", [(NICH, 0)], 12_500_000, 1024),
+    "c4": ("C4 niw dim=32 N=262144 K=128", [(NIW, 32)], 262_144, 128),
+    "c4d16": ("C4 niw dim=16 N=262144 K=128", [(NIW, 16)], 262_144, 128),
 }
 
 
@@ -64,6 +69,12 @@ def shape(ctx, key, steps):
     st.accumulate(view, zs)
     avg, mn = timed(lambda i: st.sweep_assign(view, zs, 73, 1000 + i), steps)
     res.update(collapsed_assign_ms=round(avg, 4))
+    if any(f == NIW for f, _ in spec):
+        st.accumulate(view, zs)
+        out = torch.empty((N, K), dtype=torch.float32, device=ctx.torch_device)
+        avg, mn = timed(lambda i: st.score_value(view, out=out), steps)
+        res.update(score_value_ms=round(avg, 4), score_value_ms_min=round(mn, 4), score_kernel=ctx.lib.msc_last_kernel(0).decode())
+        del out
     del st
     # the blocked sweep
     sb = common_amd.State(ctx, spec, K)
@@ -83,6 +94,8 @@ def shape(ctx, key, steps):
                step_rows_per_s=round(N / (res["sweep_step_ms"] * 1e-3)),
                assign_vs_collapsed_assign=round(res["assign_ms"] / res["collapsed_assign_ms"], 3),
                blocked_vs_step=round(res["sweep_blocked_ms"] / res["sweep_step_ms"], 3))
+    if "score_value_ms" in res:
+        res.update(assign_vs_score_value=round(res["assign_ms"] / res["score_value_ms"], 3))
     return res
 
 
